@@ -14,13 +14,32 @@ oracle = port of the reference's SEAL path, timed on a bounded sample).  The who
 import argparse
 import json
 import os
+import shutil
 import sys
+import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs DIR: what the timed path handed its caller in the last timed step, one DIR/<name>.npy per array, in float64 - ciphertext
+    words and decrypted residues are integers below 2^53, which float64 holds exactly.  Same arguments, same inputs, keys and encryption
+    randomness: two builds of the project can be compared array for array."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.uint64) for k, v in arrays.items()}
+    total = sum(8 * a.size for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py --dump-outputs: %d bytes of outputs exceed the %d byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.size == 0 or int(a.max()) < 1 << 53, name
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float64))
 
 
 def uniform_ct_words(rng, q, n, count, polys=2):
@@ -177,7 +196,7 @@ def single_image_workload(args, rank, world, local, dist, torch, result_fd):
     else:
         w = dict(zip(("Weights_0", "Weights_1", "Biases_2", "Weights_3", "Biases_3"), cm.reference_weights()))
         images = cm.synthetic_images(args.warmup + args.steps, seed=1000 + (rank if args.shard == "images" else 0))
-    results, dt, verified, kept = [], 0.0, None, None
+    results, dt, verified, kept, tsv_dir = [], 0.0, None, None, None
     if active:
         Factory = EncryptedSealBfvFactory(**parms)
         env = Factory.AllocateComputationEnv()
@@ -185,7 +204,8 @@ def single_image_workload(args, rank, world, local, dist, torch, result_fd):
             reader = networks.cifar_reader(Factory=Factory)
             net = networks.LoLaCifar(Factory, reader, W, B, timing=False)
         else:
-            tsv = "/tmp/bench_lola_rank%d.tsv" % rank
+            tsv_dir = tempfile.mkdtemp(prefix="bench_lola_")
+            tsv = os.path.join(tsv_dir, "images.tsv")
             with open(tsv, "w") as f:
                 for img in images:
                     f.write("7\t784\t" + "\t".join("%d:%d" % (i, int(img[i])) for i in np.nonzero(img)[0]) + "\n")
@@ -276,6 +296,13 @@ def single_image_workload(args, rank, world, local, dist, torch, result_fd):
             flag = torch.tensor([1 if verified else 0], dtype=torch.int32, device=dev)
             dist.all_reduce(flag, op=dist.ReduceOp.MIN)
             verified = bool(flag.item())
+    if args.dump_outputs and rank == 0 and active:             # the last timed image's result ciphertexts (and, LoLa-MNIST, their decrypted slots)
+        last = {}
+        for p_, a, e in zip(parms["primes"], results[-1].GetColumn(0).eVectors, env.Environments):
+            last["result_ciphertexts_p%d" % p_] = e.ctx.ct_download(a.encData.h, a.encData.first, a.encData.count).reshape(a.encData.count, 2, e.ctx.k, e.ctx.n)
+            if not cifar:
+                last["result_slots_mod_p%d" % p_] = [int(v) for v in a._decrypt_ints(e)]
+        dump_outputs(args.dump_outputs, last)
     import hashlib
     digest = hashlib.sha256()                                  # the result ciphertext WORDS of this rank's timed images (reproducible under --client-seed)
     for m in results:
@@ -283,6 +310,8 @@ def single_image_workload(args, rank, world, local, dist, torch, result_fd):
             digest.update(e.ctx.ct_download(a.encData.h, a.encData.first, a.encData.count).tobytes())
     for m in results:
         m.Dispose()
+    if tsv_dir is not None:
+        shutil.rmtree(tsv_dir, ignore_errors=True)
     if rank == 0:
         images_done = args.steps * (world if args.shard == "images" else 1)
         out = {"metric": "encrypted images/sec (%s single-image inference, N=%d)" % ("LoLa-CIFAR shapes" if cifar else "LoLa-MNIST", parms["n"]),
@@ -435,6 +464,14 @@ def single_image_lines(gpu_index):
     return lola, cifar
 
 
+def _at_least(lo):
+    def parse(v):
+        if int(v) < lo:
+            raise argparse.ArgumentTypeError("must be >= %d" % lo)
+        return int(v)
+    return parse
+
+
 def _conv_tile():
     """BENCH_CONV_TILE=2 or 1x2: outputs of neighbouring positions share a gather list (same outputs; developer A/B switch)."""
     v = os.environ.get("BENCH_CONV_TILE", "1")
@@ -516,8 +553,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--stub", action="store_true", help="launcher plumbing only (gloo, no device work): what the CPU test of `--gpus N` runs")
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--steps", type=_at_least(1), default=20, help="timed steps")
+    ap.add_argument("--warmup", type=_at_least(0), default=3, help="untimed steps before them")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--weights", choices=("trained", "synthetic"), default="trained",
                     help="trained: the reference's CryptoNets/Weights.cs (shipped as package data); synthetic: random-init weights of the same shapes")
@@ -536,7 +573,13 @@ def main():
                     "every Galois key and the client keys are broadcast with RCCL and adopted in place (default: every rank is its own client)")
     ap.add_argument("--client-seed", type=int, default=None, help="lola / cifar: reproducible keys and encryption randomness (tests: two runs must give the same ciphertext words)")
     ap.add_argument("--no-single-image", action="store_true", help="default workload: skip the LoLa-MNIST / LoLa-CIFAR sub-benchmarks (BASELINE configs 4 and 5) of the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float64, rank 0): default workload - the 10 "
+                         "logit ciphertexts and the decrypted logits of every plaintext prime; lola / cifar - the last image's result ciphertexts (lola: and their "
+                         "decrypted slots), keys and encryption seeded with --client-seed (default 0 when dumping)")
     args = ap.parse_args()
+    if args.dump_outputs and args.client_seed is None and args.workload != "cryptonets":
+        args.client_seed = 0                              # reproducible keys and encryption randomness: the dumped words are comparable between runs
 
     # N > 1 without a launcher around us: start the ranks ourselves (the driver's own torchrun line sets WORLD_SIZE and is honoured as is)
     if (args.gpus > 1 or os.environ.get("BENCH_SELF_LAUNCH")) and "WORLD_SIZE" not in os.environ:      # BENCH_SELF_LAUNCH=1: also at N = 1 (GPU test of the launcher)
@@ -650,6 +693,7 @@ def main():
     import hashlib
     verified = True
     digest = hashlib.sha256()
+    outputs = {}
     for ch in chans:
         gg = ch.g
         dh = gg.pt_alloc(10)
@@ -657,7 +701,12 @@ def main():
         got = np.ascontiguousarray(gg.decode_batch(dh, 0, 10).T)
         gg.free(dh)
         verified = verified and bool(np.array_equal(got, cm.model_mod_p_dense(x_int, layers, gg.t)))
-        digest.update(gg.ct_download(ch.h5, 0, 10).tobytes())
+        words = gg.ct_download(ch.h5, 0, 10)
+        digest.update(words.tobytes())
+        outputs["logit_ciphertexts_p%d" % gg.t] = words.reshape(10, 2, gg.k, gg.n)   # the 10 output ciphertexts of the batch ([poly][limb][N] words)
+        outputs["logits_mod_p%d" % gg.t] = got                    # (8192, 10): their decrypted slots, image by logit
+    if args.dump_outputs and rank == 0:                           # (before the sections below reuse the channels' buffers)
+        dump_outputs(args.dump_outputs, outputs)
 
     if dist is not None:                                  # every rank checked its own batch: report the conjunction
         flag = torch.tensor([1 if verified else 0], dtype=torch.int32, device=dev)

@@ -227,14 +227,18 @@ print("TRIES", " ".join(str(t) for t in tries), fifth.get_option("stream_tries")
 @pytest.mark.gpu
 @pytest.mark.parametrize("dummies", [0, 3])
 def test_contexts_of_one_process_get_a_hardware_queue_each(dummies):
-    """HIP deals the streams of a process onto 4 hardware queues in creation order (null stream and transfer queue included); two contexts
-    on one queue run their kernels one after the other (LoLa-MNIST: 10.7 instead of 8.0 ms per image, profiles/r03_stream_queues.txt).
-    cn_ctx_create measures (two spin kernels overlap or do not) and keeps the first stream that overlaps with every live context's:
-    whatever streams the process created before, the four plaintext-prime contexts of a LoLa factory report a successful choice and still
-    evaluate correctly; a fifth context finds no free queue, says so (< 0) and works on the first stream it got.  (Own process: the cached
-    contexts of this test session would occupy the queues.)"""
+    """HIP deals the streams of a process onto GPU_MAX_HW_QUEUES hardware queues (4 unless the environment sets it) in creation order (null
+    stream and transfer queue included); two contexts on one queue run their kernels one after the other (LoLa-MNIST: 10.7 instead of 8.0 ms
+    per image, profiles/r03_stream_queues.txt).  cn_ctx_create measures (two spin kernels overlap or do not) and keeps the first stream that
+    overlaps with every live context's: whatever streams the process created before, as many of the four plaintext-prime contexts of a LoLa
+    factory as there are queues report a successful choice, the others say that they found no free queue (< 0) and work on the first stream
+    they got, and all of them evaluate correctly; so does a fifth context.  (Own process: the cached contexts of this test session would
+    occupy the queues.)"""
     r = subprocess.run([sys.executable, "-c", _QUEUE_SCRIPT % ROOT, str(dummies)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     tries = [int(x) for x in [l for l in r.stdout.splitlines() if l.startswith("TRIES")][0].split()[1:]]
-    assert tries[0] == 1 and all(t != 0 for t in tries[:4]) and sum(t >= 1 for t in tries[:4]) >= 3, tries       # (a timing measurement: one miss on a loaded host is tolerated)
-    assert tries[4] != 0, tries                          # (< 0 on every box seen: four queues, four contexts - not asserted, it is a measurement)
+    queues = min(4, int(os.environ.get("GPU_MAX_HW_QUEUES") or 4))      # what the child's HIP runtime deals its streams onto
+    own = sum(t >= 1 for t in tries[:4])
+    assert tries[0] == 1 and all(t != 0 for t in tries[:4]), tries
+    assert (queues - 1 if queues > 2 else queues) <= own <= queues, (queues, tries)   # (a timing measurement: with 3-4 queues one miss on a loaded host is tolerated)
+    assert tries[4] != 0, tries                          # (< 0 on every box seen with four queues: four queues, four contexts - not asserted, it is a measurement)

@@ -14,7 +14,7 @@ TWIN = os.path.join(INTEG, "GpuAtomicSealBfvEncryptedVector.cs")
 FACTORY = os.path.join(INTEG, "GpuSealBfvFactory.cs")
 
 # members of AtomicSealBfvEncryptedEnvironment / AtomicSealBfvEncryptedVector / OperationsCount that EncryptedSealBfvVector.cs,
-# EncryptedSealBfvMatrix.cs, IFactory.cs, CryptoTracker.cs, BaseLayer.cs and CryptoNets.cs use (collected from /root/reference)
+# EncryptedSealBfvMatrix.cs, IFactory.cs, CryptoTracker.cs, BaseLayer.cs and CryptoNets.cs use (collected from the reference's sources)
 USED_MEMBERS = ["Dim", "plainmodulusValue", "Write", "Scale", "GenerateEncryptionKeys", "BlockSize", "decryptor", "SumAllSlotsTask", "SumAllSlots",
                 "SubtractTask", "StackTask", "SaveToStream", "RotateTask", "Read", "PointwiseMultiplyTask", "PermuteTask", "ParentFactory",
                 "LoadFromStream", "IsEncrypted", "InterleaveTask", "GenerateSparseOfArray", "Format", "DuplicateTask", "DotProductTask",
@@ -58,11 +58,11 @@ def test_pinvoke_file_is_generated_from_the_header():
     assert sorted(names) == sorted(_native.SIGNATURES)
 
 
-@pytest.mark.parametrize("path", [TWIN, FACTORY])
-def test_twin_calls_match_the_c_abi(path):
+@pytest.mark.parametrize("name", [os.path.basename(TWIN), os.path.basename(FACTORY)])      # (file names: test ids independent of the checkout's location)
+def test_twin_calls_match_the_c_abi(name):
     import gen_cs_pinvoke
     protos = {n: len(p) for _, n, p in gen_cs_pinvoke.prototypes()}
-    src = open(path).read()
+    src = open(os.path.join(INTEG, name)).read()
     calls = _calls(src)
     assert calls, "no libcnhip calls found"
     for name, nargs in calls:
@@ -107,17 +107,16 @@ def test_twin_defines_every_member_the_unchanged_files_use():
     assert "class GpuSealBfvFactory : EncryptedSealBfvFactory" in f and f.count("{") == f.count("}")
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/HE Wrapper"), reason="the reference checkout is only present in the build container")
+def _reference_facts():
+    """what tests/golden/make_reference_facts.py collected from a checkout of the reference (the tests need none)"""
+    import json
+    return json.load(open(os.path.join(ROOT, "tests", "golden", "reference_facts.json")))
+
+
 def test_member_list_is_current_with_the_reference():
     """every `x.Member` the unchanged wrapper files apply to the atomic classes is in USED_MEMBERS"""
-    base = "/root/reference/HE Wrapper"
-    found = set()
-    for f in ("EncryptedSealBfvVector.cs", "EncryptedSealBfvMatrix.cs", "IFactory.cs", "CryptoTracker.cs"):
-        txt = open(os.path.join(base, f), encoding="utf-8-sig").read()
-        found |= set(re.findall(r"eVectors\[[a-z0-9]*\]\.([A-Za-z]+)", txt))
-        found |= set(re.findall(r"AtomicSealBfvEncryptedVector\.([A-Za-z]+)", txt))
-        found |= set(re.findall(r"Environments\[[a-z0-9]*\]\.([A-Za-z]+)", txt))
-        found |= set(re.findall(r"envs\[i\]\.([A-Za-z]+)", txt))
+    found = set(_reference_facts()["wrapper_members"])
+    assert found, "no members recorded"
     assert found <= set(USED_MEMBERS), found - set(USED_MEMBERS)
 
 
@@ -154,15 +153,16 @@ def test_sealnet_manifest_covers_the_twin():
     assert "CtHeader" not in src and "mem.GetBuffer()" not in src
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/HE Wrapper"), reason="the reference checkout is only present in the build container")
 def test_sealnet_manifest_reference_backing_is_real():
-    """`used by the reference itself` entries: the cited line of the reference's own source shows the member"""
+    """`used by the reference itself` entries: the cited line of the reference's own source shows the member (the text the entry's pattern
+    matched on that line, recorded by tests/golden/make_reference_facts.py: a new citation or pattern needs a new record)"""
+    cited = _reference_facts()["cited_uses"]
     for m in _manifest():
         if "reference_use" not in m:
             continue
-        f, line = m["reference_use"].rsplit(":", 1)
-        lines = open(os.path.join("/root/reference", f), encoding="utf-8-sig").read().splitlines()
-        assert re.search(m["reference_pattern"], lines[int(line) - 1]), (m["type"], m["member"], lines[int(line) - 1])
+        hit = cited.get(m["reference_use"], {}).get(m["reference_pattern"])
+        assert hit is not None, ("no record of this citation", m["type"], m["member"], m["reference_use"])
+        assert re.search(m["reference_pattern"], hit), (m["type"], m["member"], hit)
 
 
 @pytest.mark.parametrize("path", ["GpuAtomicSealBfvEncryptedVector.cs", "GpuSealBfvFactory.cs", "CnHip.cs"])
