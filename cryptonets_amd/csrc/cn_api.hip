@@ -397,6 +397,7 @@ extern "C" int cn_get_option(cn_ctx *ctx, const char *name, int *value) { API_BO
     else if (!strcmp(name, "enc_fused")) *value = ctx->enc_fused;
     else if (!strcmp(name, "fold_zero")) *value = ctx->fold_zero;
     else if (!strcmp(name, "folded_zero_encryptions")) *value = (int)std::min<uint64_t>(ctx->folded_zero, 0x7fffffff);    // zero encryptions folded so far (tests)
+    else if (!strcmp(name, "mul_relin_pipelined")) *value = (int)std::min<uint64_t>(ctx->mr_pipelined, 0x7fffffff);      // Multiply + Relinearize batches run in parts over two streams (tests)
     else if (!strcmp(name, "behz_small_base")) *value = ctx->hc.bsk[ctx->hc.kb - 1].q < (1ull << 49);     // auxiliary primes below 2^49 (FP64 kernels) instead of SEAL's 61-bit ones
     else if (!strcmp(name, "behz_f64")) *value = ctx->hc.behz_f64 && ctx->use_f64;
     else if (!strcmp(name, "aux_primes")) *value = (int)ctx->hc.kb;

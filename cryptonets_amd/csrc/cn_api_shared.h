@@ -158,19 +158,26 @@ bool aux_stream_ready(cn_ctx *ctx);
 // stagger of the primes 12.2-12.6; two parts 12.4-12.5, four 12.7, five 12.4); CN_SQ_PARTS / CN_SQ_SPLIT (cut points in per mille) for experiments.
 // mul(first, count), ks(first, count) launch on ctx->stream.
 static const uint32_t SQ_HALVES_MIN = 512;       // (the 100-ciphertext layer of CryptoNets pipelined as well: 12.35 -> 13.4 ms per batch, visit AY)
-template <class FM, class FK> static int pipelined_halves(cn_ctx *ctx, uint32_t c, FM mul, FK ks) {
+// the parts of a pipelined batch of c ciphertexts: part i = [first[i], first[i + 1]); returns the number of parts P (first[] holds P + 1 entries, P <= 8)
+static inline uint32_t pipeline_cuts(uint32_t c, uint32_t first[9]) {
     static const uint32_t parts_env = [] { const char *e = getenv("CN_SQ_PARTS"); const int v = e ? atoi(e) : 3; return (uint32_t)(v >= 2 && v <= 8 ? v : 3); }();
     const uint32_t P = std::min<uint32_t>(parts_env, c / 128 ? c / 128 : 1);
-    if (P < 2) { CHECK(mul(0u, c)); return ks(0u, c); }
-    uint32_t first[9]; first[0] = 0;
+    first[0] = 0; first[P] = c;
+    if (P < 2) return P;
     for (uint32_t i = 1; i < P; i++) first[i] = (uint32_t)(((uint64_t)c * i / P + 7) & ~7ull);
-    first[P] = c;
     static const std::vector<uint32_t> cuts = [] {                    // experiment: CN_SQ_SPLIT="250,625" = the cut points in per mille (P - 1 of them, increasing)
         std::vector<uint32_t> v; const char *e = getenv("CN_SQ_SPLIT");
         while (e && *e) { v.push_back((uint32_t)atoi(e)); e = strchr(e, ','); if (e) e++; }
         return v; }();
     if (cuts.empty() && P == 3) { first[1] = (uint32_t)(((uint64_t)c * 3 / 10 + 7) & ~7ull); first[2] = (uint32_t)(((uint64_t)c * 7 / 10 + 7) & ~7ull); }
     if (cuts.size() + 1 == P) for (uint32_t i = 1; i < P; i++) first[i] = std::min<uint32_t>(c, (uint32_t)(((uint64_t)c * cuts[i - 1] / 1000 + 7) & ~7ull));
+    return P;
+}
+template <class FM, class FK> static int pipelined_halves(cn_ctx *ctx, uint32_t c, FM mul, FK ks) {
+    uint32_t first[9];
+    const uint32_t P = pipeline_cuts(c, first);
+    if (P < 2) { CHECK(mul(0u, c)); return ks(0u, c); }
+    ctx->mr_pipelined++;
     int rc = 0;
     for (uint32_t i = 0; i < P && !rc; i++) {
         const bool aux = (i & 1) != 0;
@@ -184,7 +191,10 @@ template <class FM, class FK> static int pipelined_halves(cn_ctx *ctx, uint32_t 
         if (!rc && aux && i + 2 >= P && hipEventRecord(ctx->ev_join, ctx->stream) != hipSuccess) rc = fail(CN_ERR_HIP, "hipEventRecord failed");      // the last part on the second stream
         if (aux) std::swap(ctx->stream, ctx->stream2);
     }
-    CHECK(rc);
+    if (rc) {                                                         // work may be queued on the second stream: the context's stream still waits for it, so that
+        if (hipEventRecord(ctx->ev_join, ctx->stream2) == hipSuccess) (void)hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0);   // the next call cannot reuse scratch under it
+        return rc;
+    }
     HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
     return 0;
 }
@@ -194,6 +204,14 @@ int ensure_ks_part(cn_ctx *ctx, size_t need);
 uint32_t ks_digit_max_blocks();
 uint32_t ks_wide_max_blocks();
 int ks_planned_mode(cn_ctx *ctx, uint32_t cnt, int galois);
+// may a Multiply + Relinearize of c ciphertexts run through pipelined_halves?  Only if the key switch of every part is the fused kernel: the two-launch forms keep their
+// partial products in the context's ONE arena ks_part (and may re-allocate it), which the parts on the two streams would share
+static inline bool pipeline_fused_ks(cn_ctx *ctx, uint32_t c) {
+    uint32_t first[9];
+    const uint32_t P = pipeline_cuts(c, first);
+    for (uint32_t i = 0; i < P; i++) if (ks_planned_mode(ctx, first[i + 1] - first[i], 0) != 0) return false;
+    return P >= 2;
+}
 int do_keyswitch(cn_ctx *ctx, const uint64_t *target, size_t tstride, const uint64_t *add0, const uint64_t *add1, size_t astride, const KsKey &key, uint64_t *out, uint32_t cnt, int galois, const uint64_t *extra = nullptr, size_t xstride = 0, uint64_t *const *out_tab = nullptr, uint32_t perm_elt = 0, const KsItem *items = nullptr, uint32_t next_elt = 0, uint64_t *next_out = nullptr);
 bool ks_pair14_ok(cn_ctx *ctx, uint32_t cnt, int galois, const KsKey &key);
 uint32_t chunk_for(cn_ctx *ctx, size_t per_ct, uint32_t count);

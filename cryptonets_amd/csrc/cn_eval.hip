@@ -608,12 +608,23 @@ extern "C" int cn_relinearize(cn_ctx *ctx, cn_handle in3, uint32_t ii, cn_handle
     ctx->st.Relinarization += count;
     return 0;
 API_END }
+// cn_mul_relin: does [oi, oi + count) of `out` intersect the span operand x reads - [xi, xi + (count - 1) xstride] - in the same handle, other than as exactly the same
+// range (in place)?  Chunks and pipelined parts write results while later ones still read operands: such calls are refused.  Handles and indices only (no lookup):
+// also checked before a call is published without the lock (defer = 2)
+static int mul_relin_overlap(cn_handle x, uint32_t xi, uint32_t xstride, cn_handle out, uint32_t oi, uint32_t count) {
+    if (x != out || !count) return 0;
+    const uint64_t lo = xi, hi = (uint64_t)xi + (uint64_t)(count - 1) * xstride + 1, olo = oi, ohi = (uint64_t)oi + count;
+    if ((lo == olo && hi == ohi) || hi <= olo || ohi <= lo) return 0;
+    return fail(CN_ERR_ARG, "mul_relin: an operand range and the result range overlap partially (use the same range or disjoint ranges)");
+}
 extern "C" int cn_mul_relin(cn_ctx *ctx, cn_handle a, uint32_t ai, uint32_t astride, cn_handle b, uint32_t bi, uint32_t bstride, cn_handle out,
                             uint32_t oi, uint32_t count) {
+    CHECK(mul_relin_overlap(a, ai, astride, out, oi, count)); CHECK(mul_relin_overlap(b, bi, bstride, out, oi, count));
     if (submit_async(ctx) && count <= DEFER_STAGED_MAX) return ring_push(ctx, SUB_MUL_RELIN, count, a, ai, b, bi, out, oi, astride, bstride);      // PointwiseMultiply of one column
     API_BODY LOCK_ONLY; return mul_relin_body(ctx, a, ai, astride, b, bi, bstride, out, oi, count); API_END
 }
 int mul_relin_body(cn_ctx *ctx, cn_handle a, uint32_t ai, uint32_t astride, cn_handle b, uint32_t bi, uint32_t bstride, cn_handle out, uint32_t oi, uint32_t count) {
+    CHECK(mul_relin_overlap(a, ai, astride, out, oi, count)); CHECK(mul_relin_overlap(b, bi, bstride, out, oi, count));
     if (deferring(ctx)) return defer_mul_relin(ctx, a, ai, astride, b, bi, bstride, out, oi, count);
     CHECK(cn_defer_flush(ctx));
     GETCT(A, a, 2); GETCT(B, b, 2); GETCT(O, out, 2);
@@ -632,7 +643,9 @@ int mul_relin_body(cn_ctx *ctx, cn_handle a, uint32_t ai, uint32_t astride, cn_h
         uint64_t *t3 = salloc<uint64_t>(ctx, (size_t)c * 3 * kn);
         auto mul = [&](uint32_t f, uint32_t n_) { return do_multiply(ctx, pa + (size_t)(s + f) * astride * A->item_words, astride, pb + (size_t)(s + f) * bstride * B->item_words, bstride, t3 + (size_t)f * 3 * kn, n_); };
         auto ksw = [&](uint32_t f, uint32_t n_) { uint64_t *t = t3 + (size_t)f * 3 * kn; return do_keyswitch(ctx, t + 2 * kn, 3 * kn, t, t + kn, 3 * kn, ctx->rlk, O->d + (oi + s + f) * O->item_words, n_, 0); };
-        if (ctx->sq_halves && !ctx->sq_overlap && ctx->hc.logn <= 13 && c >= SQ_HALVES_MIN && !ctx->capturing && aux_stream_ready(ctx)) { CHECK(pipelined_halves(ctx, c, mul, ksw)); continue; }
+        if (ctx->sq_halves && !ctx->sq_overlap && ctx->hc.logn <= 13 && c >= SQ_HALVES_MIN && !ctx->capturing && pipeline_fused_ks(ctx, c) && aux_stream_ready(ctx)) {
+            CHECK(pipelined_halves(ctx, c, mul, ksw)); continue;
+        }
         CHECK(mul(0, c));
         CHECK(ksw(0, c));
     }

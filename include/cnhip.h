@@ -103,6 +103,8 @@ int cn_ctx_wait_for(cn_ctx *ctx, cn_ctx *other);
  * N <= 8192 runs as two halves software-pipelined over two streams of the context - the Multiply of the second half beside the key switch of the first (its HBM-bound base
  * extension / floor fill what the FP64-bound key switch leaves).  Same words; every later call on the context is ordered behind both halves.  A caller that issues its plaintext
  * primes one after the other (or from parallel tasks) gets what bench.py's half-batch stagger of the primes gets (12.6 -> 12.0 ms per CryptoNets batch); a staggered caller nothing.
+ * A batch runs in parts only if every part takes the fused key switch.  With "ks_wide" 1 or 2, or in automatic mode when a part has at most 160 (ciphertext, limb)
+ * blocks, it runs on one stream: the two-launch key switch keeps its partial products in one arena per context.  "mul_relin_pipelined" counts the batches run in parts.
  * "sq_overlap" = 0 (default; 1: the q-side transform kernel of a batched squaring on a second stream beside the base extension - measured slower in
  * the two-context batch, profiles/r06_square_overlap.txt).
  * "gemm_order" = 1 (default): slice-major workgroup order of the VALU scalar GEMM (every input slice fetched once per XCD), 0 = group-major.
@@ -132,7 +134,8 @@ int cn_ctx_wait_for(cn_ctx *ctx, cn_ctx *other);
 int cn_set_option(cn_ctx *ctx, const char *name, int value);
 /* reads a switch back, or a choice the library made: "behz_small_base" (1: auxiliary primes below 2^49 - the FP64 kernels - k+1 of them,
  * or k+2 where k+1 are too few (N = 16384); 0: SEAL's 61-bit base, taken whenever log2 t + log2 N + log2 q + 2 < log2(B m_sk) does not
- * hold for the small primes or a data prime has 49 bits or more), "behz_f64", "aux_primes" (primes of B plus m_sk), "pending_calls" (deferred calls not yet launched), "f64", "defer", "ks_wide", "ks_xi", "ks_pair14", "ks_chain", "mp_bcast", "sq_fused", "sq_pipe", "enc_fused", "mp_fused" */
+ * hold for the small primes or a data prime has 49 bits or more), "behz_f64", "aux_primes" (primes of B plus m_sk), "pending_calls" (deferred calls not yet launched), "f64", "defer", "ks_wide", "ks_xi", "ks_pair14", "ks_chain", "mp_bcast", "sq_fused", "sq_pipe", "enc_fused", "mp_fused",
+ * "mul_relin_pipelined" (cn_mul_relin chunks and flushed groups of queued Multiply + Relinearize calls that ran in parts over the context's two streams, "sq_halves"; counts up) */
 int cn_get_option(cn_ctx *ctx, const char *name, int *value);
 /* SEAL DefaultParams.CoeffModulus128(n) (AtomicSealBfvVector.cs:146); returns count, fills q (<=9) */
 int cn_default_coeff_modulus(uint32_t n, uint64_t *q);
@@ -247,7 +250,12 @@ int cn_multiply(cn_ctx *ctx, cn_handle a, uint32_t ai, cn_handle b, uint32_t bi,
 /* Evaluator.Relinearize size3 -> size2 (AtomicSealBfvVector.cs:462,547,787,840) */
 int cn_relinearize(cn_ctx *ctx, cn_handle in3, uint32_t ii, cn_handle out, uint32_t oi, uint32_t count);
 /* HOT LOOP B: Multiply + Relinearize per block (PointwiseMultiply, AtomicSealBfvVector.cs:839-840;
- * SquareActivation.cs:10-13).  a_stride/b_stride 0 broadcast one operand (PointwiseMultiplySparseDimOne). */
+ * SquareActivation.cs:10-13).  a_stride/b_stride 0 broadcast one operand (PointwiseMultiplySparseDimOne).
+ * Overlaps: operand x touches [xi, xi + (count - 1) x_stride] of its handle (one index for x_stride 0).  When x is the output handle, that span must
+ * either be disjoint from [oi, oi + count) or be exactly that range (in place: oi == xi, stride 1).  Any other intersection is refused with CN_ERR_ARG
+ * and nothing is written - a batch runs in chunks and in parts on two streams, whose results are stored while later ones still read operands.  The
+ * operands may overlap each other freely.  The rule is checked when the call is made in every "defer" mode, before a call of up to 4 ciphertexts is
+ * published without the lock (defer = 2). */
 int cn_mul_relin(cn_ctx *ctx, cn_handle a, uint32_t ai, uint32_t a_stride, cn_handle b, uint32_t bi, uint32_t b_stride,
                  cn_handle out, uint32_t oi, uint32_t count);
 
