@@ -16,7 +16,7 @@ CSRC = os.path.join(_PKG, "csrc")
 # one translation unit per kernel family: hipcc compiles them in parallel (the register-radix kernels alone are ~180 instantiations)
 SOURCES = [os.path.join(CSRC, f) for f in (
     "cn_api.hip", "cn_eval.hip", "cn_client.hip", "cn_defer.hip", "cn_multi.hip", "cn_host.cpp", "cn_tables.cpp", "cn_l_gemm.hip", "cn_l_behz.hip",
-    "cn_l_rr_u64.hip", "cn_l_rr_f64.hip", "cn_l_rr_f64l.hip", "cn_l_ks_u64.hip", "cn_l_ks_f64.hip", "cn_l_ks_f64l.hip")]
+    "cn_l_rr_u64.hip", "cn_l_rr_f64.hip", "cn_l_rr_f64l.hip", "cn_l_ks_u64.hip", "cn_l_ks_f64.hip", "cn_l_ks_f64l.hip", "cn_level.hip", "cn_l_modswitch.hip")]
 OBJ_DIR = os.path.join(_PKG, "lib", "obj")
 
 U64P = C.POINTER(C.c_uint64)
@@ -121,6 +121,8 @@ SIGNATURES = {
     "cn_ctx_destroy": (C.c_int, [_CTX]),
     "cn_sync": (C.c_int, [_CTX]),
     "cn_ctx_wait_for": (C.c_int, [_CTX, _CTX]),
+    "cn_ctx_create_level": (C.c_int, [_CTX, _u32, C.POINTER(_CTX)]),
+    "cn_mod_switch": (C.c_int, [_CTX, _H, _u32, _u32, _CTX, _H, _u32]),
     "cn_set_option": (C.c_int, [_CTX, C.c_char_p, C.c_int]),
     "cn_get_option": (C.c_int, [_CTX, C.c_char_p, C.POINTER(C.c_int)]),
     "cn_default_coeff_modulus": (C.c_int, [_u32, U64P]),
@@ -245,13 +247,49 @@ class Context:
             q = default_coeff_modulus(n)
         self.n, self.t, self.q, self.k = int(n), int(t), [int(x) for x in q], len(q)
         self.dbc, self.gdbc, self.device = dbc, gdbc, device
-        self.ctw = 2 * self.k * self.n
-        self._ct_size = {}
         qa = (C.c_uint64 * self.k)(*self.q)
         h = _CTX()
         self._h = None
         self._chk(self.L.cn_ctx_create(self.n, qa, self.k, self.t, dbc, gdbc, device, C.byref(h)))
+        self._adopt(h, None)
+
+    def _adopt(self, h, parent):
+        """the state every context object carries besides its parameters (also the constructor of a level context: Context.level)"""
+        self.ctw = 2 * self.k * self.n
+        self._ct_size = {}
         self._h = h
+        self._parent, self._levels = parent, {}
+
+    # ---- modulus switching (SEAL 3.2 ModSwitchToNext / ModSwitchTo; include/cnhip.h: cn_ctx_create_level, cn_mod_switch)
+    @property
+    def limbs(self):
+        """number of coefficient moduli of this context (its level)"""
+        return self.k
+
+    @property
+    def parent(self):
+        """the context this level context was sliced from (None for a context of its own)"""
+        return self._parent
+
+    def level(self, limbs):
+        """the level context over q[:limbs] (1 <= limbs < k), created once per context and cached: the parent's options and a slice of every
+        key the parent holds when it is created.  A level context owns its keys and its stream and outlives its parent (cn_ctx_create_level):
+        close() of the parent leaves its levels open - each is released by its own close() (or when it is collected)."""
+        limbs = int(limbs)
+        if limbs not in self._levels:
+            h = _CTX()
+            self._chk(self.L.cn_ctx_create_level(self._h, limbs, C.byref(h)))
+            c = Context.__new__(Context)
+            c.L, c.n, c.t, c.q, c.k = self.L, self.n, self.t, self.q[:limbs], limbs
+            c.dbc, c.gdbc, c.device = self.dbc, self.gdbc, self.device
+            c._adopt(h, self)
+            self._levels[limbs] = c
+        return self._levels[limbs]
+
+    def mod_switch(self, src, ii, count, dst, out, oi):
+        """out[oi:oi+count] (a handle of `dst`, a context on this one's chain with fewer limbs) = the ciphertexts src[ii:ii+count] of this context
+        switched down to dst's level (successive drops of the last prime with rounding); ordered on the device, no host wait"""
+        self._chk(self.L.cn_mod_switch(self._h, src, ii, count, dst._h, out, oi))
 
     def _chk(self, rc):
         if rc:

@@ -318,6 +318,7 @@ void ctx_teardown(cn_ctx *ctx) {
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     if (ctx->ev_order) (void)hipEventDestroy(ctx->ev_order);
+    if (ctx->ev_ms) (void)hipEventDestroy(ctx->ev_ms);
     cn_stagger_forget(ctx);
     if (ctx->ev_front) (void)hipEventDestroy(ctx->ev_front);
     if (ctx->stream2) { (void)hipStreamSynchronize(ctx->stream2); (void)hipStreamDestroy(ctx->stream2); }
@@ -363,6 +364,7 @@ extern "C" int cn_set_option(cn_ctx *ctx, const char *name, int value) { API_BOD
         return 0;
     }
     if (!strcmp(name, "ks_xi")) {                // decomposition convention of the key switch (DevConsts::ks_xi); the keys must be of the same convention
+        if (ctx->level && (value != 0) != (ctx->hc.ks_xi != 0)) return fail(CN_ERR_ARG, "ks_xi of a level context is its parent's (its keys are)");
         if (ctx->capturing || ctx->graphs_alive) return fail(CN_ERR_ARG, "ks_xi cannot change while a graph is recorded or alive (its kernels were chosen for the other convention)");
         HIPCHK(hipStreamSynchronize(ctx->stream));
         ctx->hc.ks_xi = value != 0;
@@ -459,10 +461,10 @@ int set_key(cn_ctx *ctx, KsKey &slot, const uint64_t *words, size_t count, size_
     return 0;
 }
 extern "C" int cn_set_relin_key(cn_ctx *ctx, const uint64_t *words, size_t count, int is_dev) { API_BODY
-    LOCK; NOT_CAPTURING("cn_set_relin_key"); return set_key(ctx, ctx->rlk, words, count, cn_key_words(ctx, 0), is_dev);
+    LOCK; NOT_CAPTURING("cn_set_relin_key"); NOT_LEVEL("cn_set_relin_key"); return set_key(ctx, ctx->rlk, words, count, cn_key_words(ctx, 0), is_dev);
 API_END }
 extern "C" int cn_set_galois_key(cn_ctx *ctx, uint64_t elt, const uint64_t *words, size_t count, int is_dev) { API_BODY
-    LOCK; NOT_CAPTURING("cn_set_galois_key");
+    LOCK; NOT_CAPTURING("cn_set_galois_key"); NOT_LEVEL("cn_set_galois_key");
     if (!(elt & 1) || elt >= 2ull * ctx->hc.n) return fail(CN_ERR_ARG, "invalid Galois element");
     return set_key(ctx, ctx->gk[elt], words, count, cn_key_words(ctx, 1), is_dev);
 API_END }

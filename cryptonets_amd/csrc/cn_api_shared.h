@@ -277,6 +277,10 @@ int raw_ntt(cn_ctx *ctx, void *p, uint32_t limbs, int base, int inverse);
 
 #define launch_count cn_launch_count
 #define NOT_CAPTURING(what) do { if (ctx->capturing) return fail(CN_ERR_ARG, what " is not possible while a graph is recorded (cn_graph_begin .. cn_graph_end)"); } while (0)
+// a level context (cn_ctx_create_level) gets its keys from its parent only (SEAL 3.2 generates keys at the first level only)
+#define NOT_LEVEL(what) do { if (ctx->level) return fail(CN_ERR_ARG, what " is not possible on a level context (its keys are its parent's, sliced)"); } while (0)
+// the BEHZ multiply and the key switch are not run on one coefficient modulus (include/cnhip.h: cn_ctx_create_level)
+#define TWO_LIMBS(what) do { if (ctx->hc.k < 2) return fail(CN_ERR_ARG, what " needs at least 2 coefficient moduli (a 1-limb context runs the linear operations, encryption and decryption)"); } while (0)
 #define KS_DIGIT_MAX_BLOCKS ks_digit_max_blocks()
 #define KS_WIDE_MAX_BLOCKS ks_wide_max_blocks()
 #define DISPATCH_K2(fn, ...) switch (ctx->hc.k) { \

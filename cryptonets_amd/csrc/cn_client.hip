@@ -12,7 +12,7 @@ int set_plain_key(cn_ctx *ctx, uint64_t **slot, const uint64_t *words, size_t co
 }
 // any key in either representation (include/cnhip.h)
 extern "C" int cn_load_key(cn_ctx *ctx, int which, uint64_t elt, const uint64_t *words, size_t count, int is_dev, int form) { API_BODY
-    LOCK; NOT_CAPTURING("cn_load_key");
+    LOCK; NOT_CAPTURING("cn_load_key"); NOT_LEVEL("cn_load_key");
     if (form != 0 && form != 1) return fail(CN_ERR_ARG, "key form must be 0 (NTT) or 1 (coefficients)");
     switch (which) {
         case 0: return set_key(ctx, ctx->rlk, words, count, cn_key_words(ctx, 0), is_dev, form == 1);
@@ -24,8 +24,8 @@ extern "C" int cn_load_key(cn_ctx *ctx, int which, uint64_t elt, const uint64_t 
     }
     return fail(CN_ERR_ARG, "unknown key kind %d", which);
 API_END }
-extern "C" int cn_set_public_key(cn_ctx *ctx, const uint64_t *words, size_t count) { API_BODY LOCK; NOT_CAPTURING("cn_set_public_key"); return set_plain_key(ctx, &ctx->pk, words, count, ctx->ctw2); API_END }
-extern "C" int cn_set_secret_key(cn_ctx *ctx, const uint64_t *words, size_t count) { API_BODY LOCK; NOT_CAPTURING("cn_set_secret_key"); return set_plain_key(ctx, &ctx->sk, words, count, ctx->ctw2 / 2); API_END }
+extern "C" int cn_set_public_key(cn_ctx *ctx, const uint64_t *words, size_t count) { API_BODY LOCK; NOT_CAPTURING("cn_set_public_key"); NOT_LEVEL("cn_set_public_key"); return set_plain_key(ctx, &ctx->pk, words, count, ctx->ctw2); API_END }
+extern "C" int cn_set_secret_key(cn_ctx *ctx, const uint64_t *words, size_t count) { API_BODY LOCK; NOT_CAPTURING("cn_set_secret_key"); NOT_LEVEL("cn_set_secret_key"); return set_plain_key(ctx, &ctx->sk, words, count, ctx->ctw2 / 2); API_END }
 // which: 0 relin, 1 galois(elt), 2 public, 3 secret.  Exports u64 residues (FP64-form keys are converted back).
 extern "C" int cn_get_key(cn_ctx *ctx, int which, uint64_t elt, uint64_t *host, size_t count) { API_BODY
     LOCK; NOT_CAPTURING("cn_get_key");
@@ -138,7 +138,7 @@ API_END }
 // KeyGenerator (AtomicSealBfvVector.cs:62-74,163-173 runs it inside SEAL): secret, public, relinearisation and the default Galois
 // key set (2N-1, 3^(2^i), 3^(-2^i)) generated on the device from the ChaCha20 sampler.
 extern "C" int cn_keygen(cn_ctx *ctx, uint64_t seed, int with_galois) { API_BODY
-    LOCK; NOT_CAPTURING("cn_keygen");
+    LOCK; NOT_CAPTURING("cn_keygen"); NOT_LEVEL("cn_keygen");
     const uint32_t n = ctx->hc.n, k = ctx->hc.k; const size_t kn = (size_t)k * n;
     if (!ctx->sk) HIPCHK(hipMalloc((void **)&ctx->sk, kn * 8));
     if (!ctx->pk) HIPCHK(hipMalloc((void **)&ctx->pk, 2 * kn * 8));

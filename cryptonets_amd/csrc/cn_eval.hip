@@ -583,7 +583,7 @@ uint32_t chunk_for(cn_ctx *ctx, size_t per_ct, uint32_t count) {
     return (uint32_t)std::min<size_t>(c, count);
 }
 
-extern "C" int cn_multiply(cn_ctx *ctx, cn_handle a, uint32_t ai, cn_handle b, uint32_t bi, cn_handle out3, uint32_t oi, uint32_t count) { API_BODY
+extern "C" int cn_multiply(cn_ctx *ctx, cn_handle a, uint32_t ai, cn_handle b, uint32_t bi, cn_handle out3, uint32_t oi, uint32_t count) { API_BODY TWO_LIMBS("cn_multiply");
     LOCK; GETCT(A, a, 2); GETCT(B, b, 2); GETCT(O, out3, 3);
     if (!range_ok(A, ai, count) || !range_ok(B, bi, count) || !range_ok(O, oi, count)) return fail(CN_ERR_ARG, "index out of range");
     if (!count) return 0;
@@ -597,7 +597,7 @@ extern "C" int cn_multiply(cn_ctx *ctx, cn_handle a, uint32_t ai, cn_handle b, u
     }
     return 0;
 API_END }
-extern "C" int cn_relinearize(cn_ctx *ctx, cn_handle in3, uint32_t ii, cn_handle out, uint32_t oi, uint32_t count) { API_BODY
+extern "C" int cn_relinearize(cn_ctx *ctx, cn_handle in3, uint32_t ii, cn_handle out, uint32_t oi, uint32_t count) { API_BODY TWO_LIMBS("cn_relinearize");
     LOCK; GETCT(I, in3, 3); GETCT(O, out, 2);
     if (!range_ok(I, ii, count) || !range_ok(O, oi, count)) return fail(CN_ERR_ARG, "index out of range");
     if (!ctx->rlk.d) return fail(CN_ERR_NOKEY, "relinearization keys not set");
@@ -619,6 +619,7 @@ static int mul_relin_overlap(cn_handle x, uint32_t xi, uint32_t xstride, cn_hand
 }
 extern "C" int cn_mul_relin(cn_ctx *ctx, cn_handle a, uint32_t ai, uint32_t astride, cn_handle b, uint32_t bi, uint32_t bstride, cn_handle out,
                             uint32_t oi, uint32_t count) {
+    TWO_LIMBS("cn_mul_relin");
     CHECK(mul_relin_overlap(a, ai, astride, out, oi, count)); CHECK(mul_relin_overlap(b, bi, bstride, out, oi, count));
     if (submit_async(ctx) && count <= DEFER_STAGED_MAX) return ring_push(ctx, SUB_MUL_RELIN, count, a, ai, b, bi, out, oi, astride, bstride);      // PointwiseMultiply of one column
     API_BODY LOCK_ONLY; return mul_relin_body(ctx, a, ai, astride, b, bi, bstride, out, oi, count); API_END
@@ -709,7 +710,7 @@ int galois_impl(cn_ctx *ctx, Buffer *I, uint32_t ii, uint64_t elt, Buffer *O, ui
     return do_galois(ctx, I->d + ii * I->item_words, elt, O->d + oi * O->item_words, tmp, count);
 }
 bool galois_key_present(cn_ctx *ctx, uint64_t elt) { auto it = ctx->gk.find(elt); return it != ctx->gk.end() && it->second.d; }
-extern "C" int cn_apply_galois(cn_ctx *ctx, cn_handle in, uint32_t ii, uint64_t elt, cn_handle out, uint32_t oi, uint32_t count) { API_BODY
+extern "C" int cn_apply_galois(cn_ctx *ctx, cn_handle in, uint32_t ii, uint64_t elt, cn_handle out, uint32_t oi, uint32_t count) { API_BODY TWO_LIMBS("cn_apply_galois");
     LOCK; GETCT(I, in, 2); GETCT(O, out, 2);
     return galois_impl(ctx, I, ii, elt, O, oi, count);
 API_END }
@@ -839,7 +840,7 @@ int rotate_jobs(cn_ctx *ctx, std::vector<RotJob> &jobs) {
     return 0;
 }
 
-extern "C" int cn_rotate_rows(cn_ctx *ctx, cn_handle in, uint32_t ii, int steps, cn_handle out, uint32_t oi, uint32_t count) { API_BODY
+extern "C" int cn_rotate_rows(cn_ctx *ctx, cn_handle in, uint32_t ii, int steps, cn_handle out, uint32_t oi, uint32_t count) { API_BODY TWO_LIMBS("cn_rotate_rows");
     LOCK_ONLY; GETCT(I, in, 2); GETCT(O, out, 2);
     if (deferring(ctx) && count && count <= DEFER_STAGED_MAX) {
         if (!range_ok(I, ii, count) || !range_ok(O, oi, count)) return fail(CN_ERR_ARG, "index out of range");
@@ -850,7 +851,7 @@ extern "C" int cn_rotate_rows(cn_ctx *ctx, cn_handle in, uint32_t ii, int steps,
     return rotate_rows_impl(ctx, I, ii, steps, O, oi, count);
 API_END }
 // RotateRows of n ciphertexts by n different step counts, one launch chain (see include/cnhip.h)
-extern "C" int cn_rotate_rows_many(cn_ctx *ctx, cn_handle in, const uint32_t *ii, const int *steps, uint32_t n, cn_handle out, const uint32_t *oi) { API_BODY
+extern "C" int cn_rotate_rows_many(cn_ctx *ctx, cn_handle in, const uint32_t *ii, const int *steps, uint32_t n, cn_handle out, const uint32_t *oi) { API_BODY TWO_LIMBS("cn_rotate_rows_many");
     LOCK_ONLY; GETCT(I, in, 2); GETCT(O, out, 2);
     if (!n) return 0;
     if (!ii || !steps || !oi) return fail(CN_ERR_ARG, "null argument");
@@ -907,7 +908,7 @@ int rotate_columns_add_impl(cn_ctx *ctx, Buffer *I, uint32_t ii, Buffer *A, uint
     uint64_t *tmp = salloc<uint64_t>(ctx, count * ctx->ctw2);
     return do_galois(ctx, I->d + ii * I->item_words, 2ull * ctx->hc.n - 1, O->d + oi * O->item_words, tmp, count, A->d + ai * A->item_words);
 }
-extern "C" int cn_rotate_rows_add(cn_ctx *ctx, cn_handle in, uint32_t ii, int steps, cn_handle acc, uint32_t ai, cn_handle out, uint32_t oi, uint32_t count) { API_BODY
+extern "C" int cn_rotate_rows_add(cn_ctx *ctx, cn_handle in, uint32_t ii, int steps, cn_handle acc, uint32_t ai, cn_handle out, uint32_t oi, uint32_t count) { API_BODY TWO_LIMBS("cn_rotate_rows_add");
     LOCK_ONLY; GETCT(I, in, 2); GETCT(A, acc, 2); GETCT(O, out, 2);
     if (deferring(ctx) && count && count <= DEFER_STAGED_MAX) {
         if (!range_ok(I, ii, count) || !range_ok(A, ai, count) || !range_ok(O, oi, count)) return fail(CN_ERR_ARG, "index out of range");
@@ -917,7 +918,7 @@ extern "C" int cn_rotate_rows_add(cn_ctx *ctx, cn_handle in, uint32_t ii, int st
     CHECK(cn_defer_flush(ctx));
     return rotate_rows_add_impl(ctx, I, ii, steps, A, ai, O, oi, count);
 API_END }
-extern "C" int cn_rotate_columns_add(cn_ctx *ctx, cn_handle in, uint32_t ii, cn_handle acc, uint32_t ai, cn_handle out, uint32_t oi, uint32_t count) { API_BODY
+extern "C" int cn_rotate_columns_add(cn_ctx *ctx, cn_handle in, uint32_t ii, cn_handle acc, uint32_t ai, cn_handle out, uint32_t oi, uint32_t count) { API_BODY TWO_LIMBS("cn_rotate_columns_add");
     LOCK_ONLY; GETCT(I, in, 2); GETCT(A, acc, 2); GETCT(O, out, 2);
     if (deferring(ctx) && count && count <= DEFER_STAGED_MAX) {
         if (!range_ok(I, ii, count) || !range_ok(A, ai, count) || !range_ok(O, oi, count)) return fail(CN_ERR_ARG, "index out of range");
@@ -963,7 +964,7 @@ int sum_slots_impl(cn_ctx *ctx, Buffer *H, uint32_t first, uint32_t count, uint3
     for (uint32_t steps = 1; steps < len; steps *= 2) CHECK(rotate_rows_add_impl(ctx, H, first, -(int)steps, H, first, H, first, count));
     return 0;
 }
-extern "C" int cn_sum_slots(cn_ctx *ctx, cn_handle h, uint32_t first, uint32_t count, uint32_t length) { API_BODY
+extern "C" int cn_sum_slots(cn_ctx *ctx, cn_handle h, uint32_t first, uint32_t count, uint32_t length) { API_BODY TWO_LIMBS("cn_sum_slots");
     LOCK_ONLY; GETCT(H, h, 2);
     if (!range_ok(H, first, count)) return fail(CN_ERR_ARG, "index out of range");
     if (!count) return 0;
@@ -979,7 +980,7 @@ extern "C" int cn_sum_slots(cn_ctx *ctx, cn_handle h, uint32_t first, uint32_t c
 API_END }
 // out[r] = SumAllSlots(v * pt[r], length) for r < rows: every row of a plaintext matrix against ONE packed ciphertext
 // (EncryptedSealBfvMatrix.Mul row-major, EncryptedSealBfvMatrix.cs:79-120 -> DotProduct, AtomicSealBfvVector.cs:963-977).
-extern "C" int cn_rowdot_batch(cn_ctx *ctx, cn_handle v, uint32_t vi, cn_handle pt, uint32_t pi, uint32_t rows, uint32_t length, cn_handle out, uint32_t oi) { API_BODY
+extern "C" int cn_rowdot_batch(cn_ctx *ctx, cn_handle v, uint32_t vi, cn_handle pt, uint32_t pi, uint32_t rows, uint32_t length, cn_handle out, uint32_t oi) { API_BODY TWO_LIMBS("cn_rowdot_batch");
     LOCK; GETCT(V, v, 2); GETCT(O, out, 2); GETPT(P, pt);
     if (!rows) return 0;
     if (V == O && vi >= oi && vi < oi + rows) return fail(CN_ERR_ARG, "row-dot batch cannot overwrite its input");
@@ -1000,7 +1001,7 @@ extern "C" int cn_rowdot_batch(cn_ctx *ctx, cn_handle v, uint32_t vi, cn_handle 
     if (length == 1) return 0;
     return sum_slots_impl(ctx, O, oi, rows, length);
 API_END }
-extern "C" int cn_rotate_columns(cn_ctx *ctx, cn_handle in, uint32_t ii, cn_handle out, uint32_t oi, uint32_t count) { API_BODY
+extern "C" int cn_rotate_columns(cn_ctx *ctx, cn_handle in, uint32_t ii, cn_handle out, uint32_t oi, uint32_t count) { API_BODY TWO_LIMBS("cn_rotate_columns");
     LOCK_ONLY; GETCT(I, in, 2); GETCT(O, out, 2);
     if (deferring(ctx) && count && count <= DEFER_STAGED_MAX) {
         if (!range_ok(I, ii, count) || !range_ok(O, oi, count)) return fail(CN_ERR_ARG, "index out of range");

@@ -67,6 +67,13 @@ struct DevConsts {
     // exact key switches; the keys of one do not work with the digits of the other.  qhat_q[l][j] = (q/q_l) mod q_j (0 unless j == l: only the diagonal is used).
     uint32_t ks_xi;
     uint64_t qhat_q[CN_MAXK][CN_MAXK];
+    // (q/q_l)^-1 mod q_l of the key-switch digits under "ks_xi" = 1, where q is the TOP modulus of the context's chain: equal to inv_qhat_q
+    // in a context from cn_ctx_create; a level context (cn_ctx_create_level) inherits its parent's, because its keys carry the parent's
+    // [q/q_l]_{q_l} 2^(dbc d) s' (the BEHZ tables above stay those of its own modulus)
+    uint64_t ks_inv_qhat_q[CN_MAXK];
+    // modulus switching (cn_mod_switch, SEAL's mod_switch_scale_to_next): dropping prime p keeps limbs i < p with
+    // x_i' = (x_i - (r mod q_i) + (h_p mod q_i)) q_p^-1 mod q_i,  r = (x_p + h_p) mod q_p,  h_p = floor(q_p / 2)
+    uint64_t ms_inv[CN_MAXK][CN_MAXK], ms_invs[CN_MAXK][CN_MAXK], ms_h[CN_MAXK][CN_MAXK];   // [p][i]: q_p^-1 mod q_i, its Shoup quotient, h_p mod q_i
 };
 
 // host-side precompute (cn_tables.cpp). tw_host must hold (k+kb+1)*4*n words; index_map (n entries) receives the

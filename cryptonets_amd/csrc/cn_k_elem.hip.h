@@ -155,7 +155,7 @@ static __global__ void __launch_bounds__(1024) k_keyswitch(const uint64_t *__res
         const uint32_t nd = galois ? C->gk_dig[l] : C->rl_dig[l];
         const uint64_t *src = target + (size_t)ct * tgt_stride + (size_t)l * n;
         const bool xi = C->ks_xi != 0;             // digits of [c_l (q/q_l)^-1]_{q_l} instead of c_l (cn_set_option("ks_xi"))
-        const DMod ql = C->q[l]; const uint64_t xf = C->inv_qhat_q[l];
+        const DMod ql = C->q[l]; const uint64_t xf = C->ks_inv_qhat_q[l];
         for (uint32_t d = 0; d < nd; d++, kp += 2 * kn) {
             const int sh = dbc * (int)d;
 #pragma unroll

@@ -17,7 +17,7 @@ template <int RN, int L> struct KsFwd<ArF64T<RN>, L> { typedef typename std::con
 // exact modular product per source word, once per (workgroup, source limb); wave-uniform branch, off by default
 DEV void ks_premultiply(uint64_t (&raw)[16], const DevConsts *C, uint32_t l) {
     if (C->ks_xi) {
-        const DMod ql = C->q[l]; const uint64_t f = C->inv_qhat_q[l];
+        const DMod ql = C->q[l]; const uint64_t f = C->ks_inv_qhat_q[l];
 #pragma unroll
         for (int r = 0; r < 16; r++) raw[r] = mulmod(raw[r], f, ql);
     }
@@ -129,7 +129,7 @@ __global__ void __launch_bounds__(NttPlan<L>::NT, MINW) k_keyswitch_rr(const uin
             request(nraw, min(l + 1, k - 1));
         } else request(raw, l);
         if constexpr (XI) {
-            const DMod ql = C->q[l]; const uint64_t xf = C->inv_qhat_q[l];
+            const DMod ql = C->q[l]; const uint64_t xf = C->ks_inv_qhat_q[l];
 #pragma unroll
             for (int r = 0; r < 16; r++) raw[r] = mulmod(raw[r], xf, ql);
         }
@@ -237,7 +237,7 @@ __global__ void __launch_bounds__(NttPlan<13>::NT) k_keyswitch_split14(const uin
             for (int r = 0; r < 16; r++) {
                 const uint32_t e = pass_index<L, SA, 0>(tl, r);
                 uint64_t sx = src[e], sy = src[e + n2];
-                if constexpr (XI) { const DMod ql = C->q[l]; const uint64_t xf = C->inv_qhat_q[l]; sx = mulmod(sx, xf, ql); sy = mulmod(sy, xf, ql); }   // digits of xi_l
+                if constexpr (XI) { const DMod ql = C->q[l]; const uint64_t xf = C->ks_inv_qhat_q[l]; sx = mulmod(sx, xf, ql); sy = mulmod(sy, xf, ql); }   // digits of xi_l
                 T X = A.load((sx >> sh) & mask), Y = A.load((sy >> sh) & mask);
                 AR::fwd(X, Y, A.fw, 1, A.m);        // stage 0 of the 2N'-point transform: (x + w y, x - w y), w = root[1]
                 v[r] = h ? Y : X;
@@ -308,7 +308,7 @@ template <class AR, bool XI, bool WHOLE> struct Ks14Stage0 {
     typedef typename AR::T T;
     const DevConsts *C; typename AR::Mod m; double sg, w1; uint64_t mask;
     NTT_DEV T operator()(uint64_t sx, uint64_t sy, uint32_t l, int sh) const {
-        if constexpr (XI) { const DMod ql = C->q[l]; const uint64_t xf = C->inv_qhat_q[l]; sx = mulmod(sx, xf, ql); sy = mulmod(sy, xf, ql); }   // digits of xi_l
+        if constexpr (XI) { const DMod ql = C->q[l]; const uint64_t xf = C->ks_inv_qhat_q[l]; sx = mulmod(sx, xf, ql); sy = mulmod(sy, xf, ql); }   // digits of xi_l
         const T X = AR::from_u64(WHOLE ? sx : (sx >> sh) & mask), Y = AR::from_u64(WHOLE ? sy : (sy >> sh) & mask);
         return AR::center(__fma_rn(sg, AR::mulmod(Y, w1, m), X), m);         // x +- w y
     }

@@ -36,6 +36,7 @@ extern "C" int cn_ctx_broadcast_keys(cn_ctx **ctxs, int n) {
     for (int i = 1; i < n; i++) {
         cn_ctx *c = ctxs[i];
         if (!c || c == root) return fail(CN_ERR_ARG, "context %d is null or the root itself", i);
+        if (c->level) return fail(CN_ERR_ARG, "context %d is a level context (its keys are its parent's, sliced)", i);
         bool same = c->hc.n == root->hc.n && c->hc.k == root->hc.k && c->hc.t.q == root->hc.t.q && c->hc.dbc == root->hc.dbc && c->hc.gdbc == root->hc.gdbc;
         for (uint32_t j = 0; same && j < root->hc.k; j++) same = c->hc.q[j].q == root->hc.q[j].q;
         if (!same) return fail(CN_ERR_ARG, "context %d has other encryption parameters than the root", i);

@@ -198,6 +198,10 @@ struct cn_ctx {
     SubmitRing *ring = nullptr;
     ReadyRing *ready = nullptr;
     int async_rc = 0; std::string async_msg;        // first error of a record executed from the ring: reported by the next synchronising call
+    // modulus switching (cn_level.hip): a level context (cn_ctx_create_level) holds keys sliced from its parent's and refuses key generation and key
+    // uploads; ev_ms marks the point of this context's stream the other context of a cn_mod_switch waits for
+    bool level = false;
+    hipEvent_t ev_ms = nullptr;
 };
 
 // ---------------------------------------------------------------- kernel launchers (cn_l_*.hip)
@@ -269,5 +273,7 @@ struct GemmLaunch {
 inline uint32_t gemm_f64_rows(uint32_t K) { return ((K + 15) & ~15u) + 16; }
 int cn_l_gemm(cn_ctx *c, const GemmLaunch &g);
 int cn_l_gemm_mfma(cn_ctx *c, const GemmLaunch &g);   // k_scalar_gemm_mfma: W = weight digit fragments, idx rows of ksteps * 32 entries
+// modulus switching (cn_l_modswitch.hip): `items` (ciphertext, poly) pairs [items][ks][N] -> [items][kd][N] on c's stream with the constants of the source context
+int cn_l_mod_switch(cn_ctx *c, const uint64_t *src, uint64_t *dst, const DevConsts *src_consts, uint32_t ks, uint32_t kd, uint32_t items, uint32_t logn);
 
 inline void cn_launch_count(cn_ctx *c, int n = 1) { c->st.kernel_launches += n; }

@@ -255,6 +255,13 @@ int cn_build_consts(DevConsts *c, uint32_t n, const uint64_t *q, uint32_t k, uin
     }
     c->ks_xi = 0;
     for (uint32_t l = 0; l < k; l++) for (uint32_t j = 0; j < k; j++) c->qhat_q[l][j] = prod_except(q, k, (int)l, q[j]);
+    for (uint32_t l = 0; l < k; l++) c->ks_inv_qhat_q[l] = c->inv_qhat_q[l];
+    for (uint32_t p = 1; p < k; p++)
+        for (uint32_t i = 0; i < p; i++) {
+            c->ms_inv[p][i] = invm_prime(q[p] % q[i], q[i]);
+            c->ms_invs[p][i] = (uint64_t)(((u128)c->ms_inv[p][i] << 64) / q[i]);
+            c->ms_h[p][i] = (q[p] >> 1) % q[i];
+        }
     return 0;
 }
 

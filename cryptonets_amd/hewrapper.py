@@ -161,6 +161,76 @@ def _fan_out(envs, fn):
     return results
 
 
+# ------------------------------------------------------------------------------------------------ levels (modulus switching)
+def _level_lift(ctx, parent_ctx, ctwords):
+    """a ciphertext at the level q[:l] of `parent_ctx`'s chain -> a ciphertext over all of q that decrypts to the SAME plaintext with the same noise
+    budget: x -> (Q/Q') x mod Q per coefficient (limb j < l: x_j (Q/Q' mod q_j); the other limbs: 0, since q_j divides Q/Q').  Exact: t (Q/Q') x mod Q =
+    (Q/Q') (t x mod Q'), so round(t v / Q) and the centred norm relative to Q are those of the level.  A host-side client (SEAL at the first level)
+    decrypts and probes level ciphertexts through it."""
+    l, k, n = ctx.k, parent_ctx.k, ctx.n
+    w = np.ascontiguousarray(ctwords, dtype=np.uint64).reshape(-1, l, n)
+    P = 1
+    for qj in parent_ctx.q[l:]:
+        P *= int(qj)
+    out = np.zeros((w.shape[0], k, n), dtype=np.uint64)
+    for j in range(l):
+        qj = int(parent_ctx.q[j])
+        out[:, j] = ((w[:, j].astype(object) * (P % qj)) % qj).astype(np.uint64)
+    return out.reshape(-1)
+
+
+class _LevelClient:
+    """The data owner's side of a level environment (Decryptor / noise probes of ciphertexts at the level; keys and encryption stay at the
+    first level, as in SEAL 3.2).  Host clients see the exact lift of the ciphertext to the first level (_level_lift)."""
+
+    def __init__(self, ctx, root_ctx, parent):
+        self.ctx, self.root_ctx, self.parent = ctx, root_ctx, parent
+
+    def decrypt(self, ct):
+        return self.parent.decrypt(_level_lift(self.ctx, self.root_ctx, ct))
+
+    def noise_budget_words(self, ct):
+        return self.parent.noise_budget_words(_level_lift(self.ctx, self.root_ctx, ct))
+
+
+class _LevelDeviceClient(_LevelClient):
+    """... of a device client: the level context holds the slice of the secret key, decryption and probes run where the ciphertext lives"""
+
+    def decrypt_device(self, ct_handle, first, count):
+        pt = self.ctx.pt_alloc(count)
+        try:
+            self.ctx.decrypt(ct_handle, first, count, pt, 0)
+            return self.ctx.pt_download(pt, 0, count)
+        finally:
+            self.ctx.free(pt)
+
+    def noise_budget(self, ct_handle, first=0, count=1):
+        return self.ctx.invariant_noise_budget(ct_handle, first, count, exact_bits=True)
+
+    def decrypt(self, ct):
+        w = np.ascontiguousarray(ct, dtype=np.uint64)
+        h = self.ctx.ct_alloc(1, w.size // (self.ctx.k * self.ctx.n))
+        try:
+            self.ctx.ct_upload(h, 0, w[None, :])
+            return self.decrypt_device(h, 0, 1)[0]
+        finally:
+            self.ctx.free(h)
+
+
+def _ctx_limbs(ctx):
+    return getattr(ctx, "k", None)
+
+
+def _check_level(env, *vectors):
+    """SEAL's parameter-mismatch check (Evaluator: "encrypted1 and encrypted2 parameter mismatch"): every ciphertext operand must be at the
+    level of the environment the operation runs in"""
+    want = _ctx_limbs(env.ctx)
+    for v in vectors:
+        d = getattr(v, "encData", None)
+        if d is not None and want is not None and _ctx_limbs(d.buf.ctx) not in (None, want):
+            raise Exception("parameter mismatch: an operand is at level %d, the environment at level %d (ModSwitchTo first)" % (_ctx_limbs(d.buf.ctx), want))
+
+
 # ------------------------------------------------------------------------------------------------ atomic layer
 class AtomicSealBfvEncryptedEnvironment:
     """One plaintext modulus = one device context + its evaluation keys (AtomicSealBfvVector.cs:19-206)."""
@@ -169,6 +239,30 @@ class AtomicSealBfvEncryptedEnvironment:
         self.ctx, self.client = ctx, client
         self.plainmodulusValue = ctx.t
         self.ParentFactory = None
+        self._root, self._levels = self, {}
+
+    # -- levels (SEAL 3.2 has no special prime: every prefix q[:l] of the coefficient modulus is a level) -------------------------------
+    @property
+    def Limbs(self):
+        """coefficient moduli of this environment (its level)"""
+        return self.ctx.k
+
+    def Level(self, limbs):
+        """the environment of the level q[:limbs] of this environment's chain (created once, cached at the first level): a level context
+        (keys sliced from the first level's, cn_ctx_create_level) and the client's side of it.  Level(Limbs of the first level) is the first level."""
+        root = self._root
+        limbs = int(limbs)
+        if limbs == root.ctx.k:
+            return root
+        if limbs not in root._levels:
+            if not hasattr(root.ctx, "level"):
+                raise Exception("this context has no modulus-switching chain")
+            lctx = root.ctx.level(limbs)
+            cls = _LevelDeviceClient if hasattr(root.client, "decrypt_device") else _LevelClient
+            e = AtomicSealBfvEncryptedEnvironment(lctx, cls(lctx, root.ctx, root.client))
+            e.ParentFactory, e._root = root.ParentFactory, root
+            root._levels[limbs] = e
+        return root._levels[limbs]
 
     @property
     def SlotCount(self):
@@ -438,6 +532,33 @@ class AtomicSealBfvEncryptedVector:
             ctx.ct_upload(self.encData.h, 0, np.stack([env.client.encrypt(p) for p in plains]))
         pv.release()
 
+    # -- modulus switching (SEAL 3.2 Evaluator.ModSwitchToNext / ModSwitchTo) --------------------------------------------------------
+    @property
+    def Limbs(self):
+        """level of the ciphertexts (coefficient moduli kept), None for a plaintext vector"""
+        return None if self.encData is None else _ctx_limbs(self.encData.buf.ctx)
+
+    def ModSwitchTo(self, limbs, env):
+        """a NEW vector at the level q[:limbs], bound to env.Level(limbs) (operate on it, decrypt it and write it with that environment);
+        `env` is the environment this vector is at.  Plaintext vectors are level-free and are returned as they are."""
+        if self.encData is None:
+            return self
+        _check_level(env, self)
+        lenv = env.Level(limbs)
+        if lenv is env:
+            return self
+        if limbs >= env.ctx.k:
+            raise Exception("ModSwitchTo: level %d is not below the vector's level %d" % (limbs, env.ctx.k))
+        d = self.encData
+        t = AtomicSealBfvEncryptedVector._new(Scale=self.Scale, Dim=self.Dim, Format=self.Format, IsSigned=self.IsSigned)
+        t.encData = _Buf(lenv.ctx, "ct", d.count, d.buf.size).view()
+        env.ctx.mod_switch(d.h, d.first, d.count, lenv.ctx, t.encData.h, 0)
+        return t
+
+    def ModSwitchToNext(self, env):
+        """ModSwitchTo one prime down (the last prime of the vector's level is dropped)"""
+        return self.ModSwitchTo(env.ctx.k - 1, env)
+
     # -- persistence (AtomicSealBfvVector.cs:1273-1345) ------------------------------------------------------------
     def Write(self, stream, env):
         from . import serialization
@@ -478,6 +599,7 @@ class AtomicSealBfvEncryptedVector:
     @staticmethod
     def DenseMatrixBySparseVectorMultiply(denses, sparse, env):
         """AtomicSealBfvVector.cs:434-521: out_block[i] = sum_k denses[k].block[i] * sparse[k]."""
+        _check_level(env, sparse, *denses)
         if len(denses) != sparse.Dim:
             raise Exception("dimensions do not match")
         if sparse.Format != EVectorFormat.sparse:
@@ -694,6 +816,7 @@ class AtomicSealBfvEncryptedVector:
     def SparseMultiply(self, v, colIndex, env):
         """AtomicSealBfvVector.cs:529-598: every block of this (dense) vector times ELEMENT colIndex of the sparse vector v.
         (No caller in the reference's networks - kept for interface parity)"""
+        _check_level(env, self, v)
         ev = v
         if colIndex >= ev.Dim:
             raise Exception("index exceeds dimension")
@@ -731,6 +854,7 @@ class AtomicSealBfvEncryptedVector:
 
     def PointwiseMultiply(self, v, env):
         """AtomicSealBfvVector.cs:813-860"""
+        _check_level(env, self, v)
         ev = v
         if self.IsSigned != ev.IsSigned:
             raise Exception("Can't mix signed and unsigned numbers.")
@@ -818,6 +942,7 @@ class AtomicSealBfvEncryptedVector:
     # -- linear ---------------------------------------------------------------------------------------------
     def Add(self, v, env):
         """AtomicSealBfvVector.cs:983-1024"""
+        _check_level(env, self, v)
         if self.Scale == 0:
             return v
         if v.Scale == 0:
@@ -849,6 +974,7 @@ class AtomicSealBfvEncryptedVector:
 
     def Subtract(self, v, env):
         """AtomicSealBfvVector.cs:1238-1271"""
+        _check_level(env, self, v)
         if v.Scale == 0:
             return self
         if self.Scale != v.Scale:
@@ -1065,6 +1191,22 @@ class EncryptedSealBfvEnvironment:
     def Primes(self):
         return [e.plainmodulusValue for e in self.Environments]
 
+    @property
+    def Limbs(self):
+        return self.Environments[0].Limbs
+
+    def Level(self, limbs):
+        """the environment of the level q[:limbs] for every plaintext prime (cached: the same object for the same level)"""
+        root = self.__dict__.get("_root", self)
+        if int(limbs) == root.Environments[0].ctx.k:
+            return root
+        cache = root.__dict__.setdefault("_levels", {})
+        if int(limbs) not in cache:
+            e = EncryptedSealBfvEnvironment([x.Level(limbs) for x in root.Environments], root.ParentFactory)
+            e.bigFactor, e.preComputedCoefficients, e._root = root.bigFactor, root.preComputedCoefficients, root
+            cache[int(limbs)] = e
+        return cache[int(limbs)]
+
 
 class EncryptedSealBfvVector:
     """Values split over the plaintext primes; every op fans out to eVectors[i] (EncryptedSealBfvVector.cs:150-573)."""
@@ -1178,6 +1320,13 @@ class EncryptedSealBfvVector:
         I = [i for i, s in enumerate(selections) if s is not None]
         sel, sh = [selections[i] for i in I], [shifts[i] for i in I]
         return EncryptedSealBfvVector._of(self._each(lambda i, e: self.eVectors[i].Permute([x.eVectors[i] for x in sel], sh, outputDim, e), env), self.Scale)
+
+    def ModSwitchTo(self, limbs, env):
+        """every plaintext prime's vector switched to the level q[:limbs]; the result belongs to env.Level(limbs)"""
+        return EncryptedSealBfvVector._of([v.ModSwitchTo(limbs, e) for v, e in zip(self.eVectors, env.Environments)], self.Scale)
+
+    def ModSwitchToNext(self, env):
+        return self.ModSwitchTo(env.Limbs - 1, env)
 
     def Write(self, stream, env):
         """EncryptedSealBfvVector.cs:430-439"""

@@ -115,6 +115,16 @@ class Parameters:
     def __eq__(self, o):
         return (self.n, self.q, self.t, self.sigma) == (o.n, o.q, o.t, o.sigma)
 
+    def level(self, limbs):
+        """the parameters of a level of this chain: q[:limbs] (SEAL 3.2 has no special prime - every prefix of q is a level), same N, t, sigma"""
+        if not 1 <= limbs <= self.k:
+            raise ValueError("a level keeps 1 .. %d coefficient moduli (got %d)" % (self.k, limbs))
+        return Parameters(self.n, self.q[:limbs], self.t, self.sigma)
+
+    def chain(self):
+        """{parms_id: limbs} of every level of the chain, the first (all of q) included"""
+        return {self.level(l).parms_id(): l for l in range(1, self.k + 1)}
+
 
 # ------------------------------------------------------------------------------------------------ SEAL objects
 def save_plaintext(f, coeffs, parms_id=PARMS_ID_ZERO, scale=1.0):
@@ -165,6 +175,31 @@ def load_ciphertext(f, parms, want_ntt_form=None):
         if int(limbs[:, j].max()) >= q:
             raise BadStream("ciphertext is not valid for the encryption parameters")
     return data, int(size)
+
+
+def load_ciphertext_any_level(f, parms, want_ntt_form=None):
+    """-> (words, size, limbs): Ciphertext.Load + is_valid_for of SEAL 3.2 for a context with a modulus-switching chain - the parms_id may be
+    that of any level of `parms` (q[:limbs], 1 <= limbs <= k); sizes and residues are checked against that level's moduli.
+    load_ciphertext accepts the first level only."""
+    pid = _rd(f, 32)
+    limbs = parms.chain().get(pid)
+    if limbs is None:
+        raise BadStream("ciphertext is not valid for the encryption parameters")
+    data, size = load_ciphertext(_Prefixed(pid, f), parms.level(limbs), want_ntt_form)
+    return data, size, limbs
+
+
+class _Prefixed:
+    """`head` followed by the rest of the stream `f` (a parms_id read ahead)"""
+
+    def __init__(self, head, f):
+        self.head, self.f = head, f
+
+    def read(self, nbytes):
+        if self.head:
+            out, self.head = self.head[:nbytes], self.head[nbytes:]
+            return out + (self.f.read(nbytes - len(out)) if nbytes > len(out) else b"")
+        return self.f.read(nbytes)
 
 
 def save_kswitch_keys(f, parms, dbc, entries):
@@ -315,8 +350,9 @@ def _expect(s, text):
 
 
 def write_atomic_vector(s, vec, env):
-    """AtomicSealBfvEncryptedVector.Write (AtomicSealBfvVector.cs:1273-1302); `s` is a text stream"""
-    ctx = env.ctx
+    """AtomicSealBfvEncryptedVector.Write (AtomicSealBfvVector.cs:1273-1302); `s` is a text stream.  Ciphertexts are written at their own level
+    (the parms_id of q[:l] when the vector was switched down, SEAL's Ciphertext.Save)."""
+    ctx = vec.encData.buf.ctx if vec.encData is not None else env.ctx
     parms = Parameters(ctx.n, ctx.q, ctx.t)
     s.write("<Start EncryptedVector>\n")
     s.write(_fmt_double(vec.Scale) + "\n")
@@ -343,9 +379,11 @@ def write_atomic_vector(s, vec, env):
 
 
 def read_atomic_vector(s, env):
-    """AtomicSealBfvEncryptedVector.Read (AtomicSealBfvVector.cs:1304-1345)"""
+    """AtomicSealBfvEncryptedVector.Read (AtomicSealBfvVector.cs:1304-1345).  Ciphertexts may be at any level of `env`'s chain (SEAL 3.2's
+    Ciphertext.Load + is_valid_for): the vector then lives at that level - its `Limbs`, environment env.Level(vec.Limbs)."""
     from .hewrapper import AtomicSealBfvEncryptedVector, EVectorFormat, _Buf
-    ctx = env.ctx
+    root = getattr(env, "_root", env)
+    ctx = root.ctx
     parms = Parameters(ctx.n, ctx.q, ctx.t)
     _expect(s, "<Start EncryptedVector>")
     try:
@@ -362,12 +400,17 @@ def read_atomic_vector(s, env):
     if length <= 0:
         raise BadStream("Bad stream format. (empty vector)")
     if mode == "Encrypted":
-        cts = []
+        cts, level = [], None
         for _ in range(length):
-            w, size = load_ciphertext(mem, parms, want_ntt_form=False)
+            w, size, limbs = load_ciphertext_any_level(mem, parms, want_ntt_form=False)
             if size != 2:
                 raise BadStream("Bad stream format. (ciphertext size %d)" % size)
+            if level is not None and limbs != level:
+                raise BadStream("Bad stream format. (ciphertexts of one vector at different levels)")
+            level = limbs
             cts.append(w)
+        if level != parms.k:
+            ctx = root.Level(level).ctx
         vec.encData = _Buf(ctx, "ct", length).view()
         ctx.ct_upload(vec.encData.h, 0, np.stack(cts))
     elif mode == "Plain":

@@ -56,6 +56,29 @@ int cn_sync(cn_ctx *ctx);
  * stagger them - the FP64-bound key switch of one channel then runs beside the HBM-bound layers of the other instead of beside its twin
  * (bench.py --stagger).  Neither context is synchronised with the host. */
 int cn_ctx_wait_for(cn_ctx *ctx, cn_ctx *other);
+/* ---- modulus switching = Evaluator.ModSwitchToNext(Inplace) / ModSwitchTo (SEAL 3.2 evaluator.h: mod_switch_scale_to_next; the reference
+ * never calls it - AtomicSealBfvVector.cs keeps every ciphertext at the first level).  SEAL 3.2 has no special prime: the chain is
+ * q[0..k), q[0..k-1), ..., q[0..1).
+ * cn_ctx_create_level: a LEVEL CONTEXT over q[0..limbs), 1 <= limbs < k: the parent's N, t, dbc, gdbc, device and settled options ("f64", "ks_xi",
+ * "legacy_ntt", the kernel switches; not "defer"), its own stream and tables (transforms, BEHZ, decryption), and a slice of every key the parent holds
+ * at the time of the call - relinearisation and Galois keys: entries (l, d) with l < limbs, the first `limbs` limbs of both polynomials; public and
+ * secret key: the first `limbs` limbs (device-to-device copies, one per key).  It owns its keys and outlives its parent; a level of a level context
+ * works (a chain).  Under "ks_xi" = 1 it decomposes xi_l = [c_l (Q/q_l)^-1]_{q_l} with the chain's TOP modulus Q, which its sliced keys carry.
+ * cn_keygen, cn_set_relin_key, cn_set_galois_key, cn_load_key, cn_set_public_key, cn_set_secret_key and changing "ks_xi" return CN_ERR_ARG on it
+ * (SEAL 3.2 generates keys at the first level only).
+ * ONE-LIMB CONTEXTS (a level of 1, or cn_ctx_create with k = 1) run the linear operations, plaintext products, scalar GEMMs, encryption,
+ * decryption and cn_noise_poly.  cn_multiply, cn_relinearize, cn_mul_relin and every rotation (cn_apply_galois, cn_rotate_rows(_many,_add),
+ * cn_rotate_columns(_add), cn_sum_slots, cn_rowdot_batch) return CN_ERR_ARG there. */
+int cn_ctx_create_level(cn_ctx *parent, uint32_t limbs, cn_ctx **out);
+/* out[oi + i] = ModSwitchTo(in[ii + i], level of dst), i < count: k_src - k_dst successive drops of the last prime with rounding,
+ * x' = floor((x + floor(q_last / 2)) / q_last) mod Q' per coefficient (x = CRT value), as SEAL's mod_switch_to loops.  Size-2 and size-3
+ * ciphertexts (both handles the same size).  dst must be on the chain of src: same device, N and t, q_dst a strict prefix of q_src, the same
+ * key-switch convention (and under "ks_xi" = 1 a level of src's chain).  Otherwise, and for bad handles or ranges or while either context records a
+ * graph: CN_ERR_ARG and no switch is enqueued, `out` is not written.  Not deferrable: takes both context locks (more limbs first) and submits both
+ * contexts' queued calls first - also when the handle or range checks then refuse the call (handles may come from the lock-free ring, "defer" = 2);
+ * the context checks (chain, capture) refuse before anything is submitted.  Ordering without a host wait (events): the switch reads `in` after the work submitted to src before the call, writes `out` after
+ * the work submitted to dst before it; later dst calls see the result, later src calls wait for the read. */
+int cn_mod_switch(cn_ctx *src, cn_handle in, uint32_t ii, uint32_t count, cn_ctx *dst, cn_handle out, uint32_t oi);
 /* tuning switches (A/B testing): "f64" = 1 (default) runs transforms of moduli < 2^49 and key switching in exact FP64
  * (set BEFORE uploading keys), 0 = integer Shoup path everywhere; "legacy_ntt" = 1 selects the radix-2 LDS kernels;
  * "ks_wide" = -1 (default: automatic by batch size) / 0 fused one-launch kernel / 1 two launches with one workgroup per digit
