@@ -95,14 +95,14 @@ int range_ok(const Buffer *b, uint32_t first, uint32_t count, uint32_t stride) {
 int cn_run_ntt(cn_ctx *c, uint64_t *data, uint32_t limbs, uint32_t base_off, uint32_t nmod, int inverse) {
     if (!limbs) return 0;
     uint32_t n = c->hc.n;
-    bool f64 = c->use_f64;
+    bool f64 = c->opt.f64;
     for (uint32_t m = base_off; m < base_off + nmod; m++) f64 = f64 && c->hc.f64ok[m];
     bool light = f64;
     for (uint32_t m = base_off; m < base_off + nmod && light; m++) {
         uint64_t q = m < c->hc.k ? c->hc.q[m].q : (m < c->hc.k + c->hc.kb ? c->hc.bsk[m - c->hc.k].q : c->hc.t.q);
         if (q >> 44) light = false;
     }
-    bool done = !c->legacy_ntt && rr_ops[light ? POL_F64L : (f64 ? POL_F64 : POL_U64)]->ntt(c, data, limbs, base_off, nmod, inverse);
+    bool done = !c->opt.legacy_ntt && rr_ops[light ? POL_F64L : (f64 ? POL_F64 : POL_U64)]->ntt(c, data, limbs, base_off, nmod, inverse);
     if (!done) {
         uint32_t nt = std::min<uint32_t>(512, n / 2);
         hipLaunchKernelGGL(k_ntt, dim3(limbs), dim3(nt), (size_t)n * 8, c->stream, data, c->dc, base_off, nmod, inverse);
@@ -193,6 +193,34 @@ int pick_stream(cn_ctx *c) {
     for (hipStream_t s : rejected) if (s != c->stream) (void)hipStreamDestroy(s);
     return 0;
 }
+// The tunables of CnTunables (cn_runtime.h): cn_set_option / cn_get_option by name and, where `env` is set, an environment override read at creation.
+// A flag stores "non-zero = on"; an enumerated switch refuses a value outside lo..hi, its environment override is clamped into the range.
+struct OptionSpec { const char *name; int CnTunables::*member; int lo, hi; bool flag; const char *env; };
+static const OptionSpec kOptions[] = {
+    {"f64",           &CnTunables::f64,           0, 1, true,  nullptr},          // default: CN_NO_F64 (ctx_init); affects keys uploaded AFTER the call
+    {"legacy_ntt",    &CnTunables::legacy_ntt,    0, 1, true,  "CN_LEGACY_NTT"},
+    {"gemm_order",    &CnTunables::gemm_order,    0, 1, false, "CN_GEMM_ORDER"},
+    {"ks_perm_fused", &CnTunables::ks_perm_fused, 0, 1, true,  nullptr},
+    {"ks_xcd",        &CnTunables::ks_xcd,        0, 2, false, "CN_KS_XCD"},      // default by N (ctx_init)
+    {"sq_fused",      &CnTunables::sq_fused,      0, 1, true,  "CN_SQ_FUSED"},
+    {"sq_lds",        &CnTunables::sq_lds,        0, 1, true,  "CN_SQ_LDS"},
+    {"sq_pipe",       &CnTunables::sq_pipe,       0, 2, false, "CN_SQ_PIPE"},
+    {"sq_halves",     &CnTunables::sq_halves,     0, 2, false, "CN_SQ_HALVES"},
+    {"enc_fused",     &CnTunables::enc_fused,     0, 2, false, "CN_ENC_FUSED"},
+    {"fold_zero",     &CnTunables::fold_zero,     0, 1, true,  "CN_FOLD_ZERO"},
+    {"gemm_mfma",     &CnTunables::gemm_mfma,     0, 1, true,  "CN_GEMM_MFMA"},   // affects GEMMs planned AFTER the call
+    {"gemm_pair",     &CnTunables::gemm_pair,     0, 1, true,  "CN_GEMM_PAIR"},   // likewise
+    {"mp_fused",      &CnTunables::mp_fused,      0, 1, true,  "CN_MP_FUSED"},
+    {"ks_wide",       &CnTunables::ks_wide,      -1, 2, false, nullptr},
+    {"ks_split14",    &CnTunables::ks_split14,    0, 1, true,  nullptr},
+    {"ks_pair14",     &CnTunables::ks_pair14,     0, 1, true,  "CN_KS_PAIR14"},
+    {"ks_chain",      &CnTunables::ks_chain,      0, 1, true,  "CN_KS_CHAIN"},
+    {"mp_bcast",      &CnTunables::mp_bcast,      0, 1, true,  nullptr},
+};
+static const OptionSpec *find_option(const char *name) {
+    for (const OptionSpec &o : kOptions) if (!strcmp(name, o.name)) return &o;
+    return nullptr;
+}
 extern "C" int cn_ctx_create(uint32_t n, const uint64_t *q, uint32_t k, uint64_t t, int dbc, int gdbc, int device, cn_ctx **out) {
     if (!out || !q) return fail(CN_ERR_ARG, "null argument");
     int ndev = cn_device_count();
@@ -242,7 +270,6 @@ int ctx_init(cn_ctx *c, uint32_t n, uint32_t k, int device, std::vector<uint64_t
             HIPCHK(hipMemcpy(c->twdh, th.data(), th.size() * 8, hipMemcpyHostToDevice));
             c->hc.twdh = c->twdh;
         }
-        c->use_f64 = !(getenv("CN_NO_F64") && atoi(getenv("CN_NO_F64")));
     }
     HIPCHK(hipMalloc((void **)&c->dc, sizeof(DevConsts)));
     HIPCHK(hipMemcpy(c->dc, &c->hc, sizeof(DevConsts), hipMemcpyHostToDevice));
@@ -252,28 +279,14 @@ int ctx_init(cn_ctx *c, uint32_t n, uint32_t k, int device, std::vector<uint64_t
     c->smax = (size_t)((env ? atof(env) : 24.0) * (double)(1ull << 30));
     env = getenv("CN_POOL_GB");
     c->pool_max = (size_t)((env ? atof(env) : 8.0) * (double)(1ull << 30));
-    c->legacy_ntt = getenv("CN_LEGACY_NTT") && atoi(getenv("CN_LEGACY_NTT"));
-    c->ks_tight = getenv("CN_KS_TIGHT") && atoi(getenv("CN_KS_TIGHT"));
+    c->opt.f64 = !(getenv("CN_NO_F64") && atoi(getenv("CN_NO_F64")));
     // fused key switch, workgroup order: limb-major up to N = 8192 (one key slice per XCD L2 at a time: 2.34 GiB fetched per 845-ciphertext launch
     // against 3.99 GiB in (ciphertext, limb) order and 3.0 GiB with the limbs of a ciphertext on one XCD, same kernel time -
     // profiles/r03_pmc_keyswitch_orders.txt); (ciphertext, limb) order at N = 16384, where limb-major measured 30 % slower in round 1
-    c->ks_xcd = c->hc.logn <= 13 ? 2 : 1;            // N = 16384 (k_keyswitch_pair14): the k workgroups of a ciphertext on one XCD - they share its source limbs in that L2 (34.3 vs 35.1 ms per 5488-ciphertext link)
-    if (getenv("CN_KS_XCD")) c->ks_xcd = atoi(getenv("CN_KS_XCD"));
-    if (getenv("CN_KS_PAIR14")) c->ks_pair14 = atoi(getenv("CN_KS_PAIR14")) != 0;             // A/B switches of the N = 16384 key switch (round 5)
-    if (getenv("CN_KS_CHAIN")) c->ks_chain = atoi(getenv("CN_KS_CHAIN")) != 0;
-    if (getenv("CN_SQ_FUSED")) c->sq_fused = atoi(getenv("CN_SQ_FUSED")) != 0;
-    if (getenv("CN_SQ_LDS")) c->sq_lds = atoi(getenv("CN_SQ_LDS")) != 0;
-    if (getenv("CN_SQ_PIPE")) c->sq_pipe = atoi(getenv("CN_SQ_PIPE"));
-    if (getenv("CN_SQ_OVERLAP")) c->sq_overlap = atoi(getenv("CN_SQ_OVERLAP")) != 0;
-    if (getenv("CN_SQ_HALVES")) c->sq_halves = std::max(0, std::min(2, atoi(getenv("CN_SQ_HALVES"))));
-    if (getenv("CN_DEFER_STAGGER")) c->defer_stagger = atoi(getenv("CN_DEFER_STAGGER")) != 0;
-    if (getenv("CN_ENC_FUSED")) c->enc_fused = atoi(getenv("CN_ENC_FUSED"));
-    if (getenv("CN_FOLD_ZERO")) c->fold_zero = atoi(getenv("CN_FOLD_ZERO")) != 0;
+    c->opt.ks_xcd = c->hc.logn <= 13 ? 2 : 1;        // N = 16384 (k_keyswitch_pair14): the k workgroups of a ciphertext on one XCD - they share its source limbs in that L2 (34.3 vs 35.1 ms per 5488-ciphertext link)
+    for (const OptionSpec &o : kOptions)
+        if (const char *e = o.env ? getenv(o.env) : nullptr) c->opt.*o.member = o.flag ? atoi(e) != 0 : std::max(o.lo, std::min(o.hi, atoi(e)));
     HIPCHK(hipDeviceGetAttribute(&c->cus, hipDeviceAttributeMultiprocessorCount, device));
-    if (getenv("CN_GEMM_MFMA")) c->gemm_mfma = atoi(getenv("CN_GEMM_MFMA")) != 0;
-    if (getenv("CN_GEMM_PAIR")) c->gemm_pair = atoi(getenv("CN_GEMM_PAIR")) != 0;
-    if (getenv("CN_GEMM_ORDER")) c->gemm_order = atoi(getenv("CN_GEMM_ORDER"));
-    if (getenv("CN_MP_FUSED")) c->mp_fused = atoi(getenv("CN_MP_FUSED")) != 0;          // A/B switch of the fused squaring kernel
     size_t lds = (size_t)ntt_lds_words(n) * 8;
     if (lds > 48 * 1024) {                 // N >= 8192: the padded LDS image exceeds the default dynamic-LDS limit
         CHECK(big_lds(k_ntt, lds)); CHECK(big_lds(k_galois_lds, (size_t)n * 8)); CHECK(big_lds(k_galois_limbs, (size_t)n * 8));
@@ -319,8 +332,6 @@ void ctx_teardown(cn_ctx *ctx) {
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     if (ctx->ev_order) (void)hipEventDestroy(ctx->ev_order);
     if (ctx->ev_ms) (void)hipEventDestroy(ctx->ev_ms);
-    cn_stagger_forget(ctx);
-    if (ctx->ev_front) (void)hipEventDestroy(ctx->ev_front);
     if (ctx->stream2) { (void)hipStreamSynchronize(ctx->stream2); (void)hipStreamDestroy(ctx->stream2); }
     if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
     if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
@@ -332,28 +343,11 @@ void ctx_teardown(cn_ctx *ctx) {
 extern "C" int cn_set_option(cn_ctx *ctx, const char *name, int value) { API_BODY
     LOCK;
     if (!name) return fail(CN_ERR_ARG, "null option name");
-    if (!strcmp(name, "f64")) { ctx->use_f64 = value != 0; return 0; }              // affects keys uploaded AFTER the call
-    if (!strcmp(name, "legacy_ntt")) { ctx->legacy_ntt = value != 0; return 0; }
-    if (!strcmp(name, "ks_tight")) { ctx->ks_tight = value != 0; return 0; }
-    if (!strcmp(name, "gemm_order")) { ctx->gemm_order = value; return 0; }                  // 1 slice-major (default), 0 group-major
-    if (!strcmp(name, "ks_perm_fused")) { ctx->ks_perm_fused = value != 0; return 0; }      // rotations of small batches: automorphism inside the key-switch kernels (default 1)
-    if (!strcmp(name, "ks_xcd")) { ctx->ks_xcd = value; return 0; }              // 0 (ct, limb) order, 1 the limbs of a ciphertext on one XCD, 2 limb-major
-    if (!strcmp(name, "sq_fused")) { ctx->sq_fused = value != 0; return 0; }
-    if (!strcmp(name, "sq_lds")) { ctx->sq_lds = value != 0; return 0; }
-    if (!strcmp(name, "sq_pipe")) { ctx->sq_pipe = value; return 0; }
-    if (!strcmp(name, "sq_overlap")) { ctx->sq_overlap = value != 0; return 0; }
-    if (!strcmp(name, "sq_halves")) { if (value < 0 || value > 2) return fail(CN_ERR_ARG, "sq_halves: 0, 1 or 2"); ctx->sq_halves = value; return 0; }
-    if (!strcmp(name, "defer_stagger")) { ctx->defer_stagger = value != 0; return 0; }
-    if (!strcmp(name, "enc_fused")) { ctx->enc_fused = value; return 0; }          // 0 three launches, 1 k_encrypt_fused, 2 k_encrypt_split
-    if (!strcmp(name, "fold_zero")) { ctx->fold_zero = value != 0; return 0; }      // queued zero encryptions that only feed a queued scalar product: folded by linearity (default 1)
-    if (!strcmp(name, "gemm_mfma")) { ctx->gemm_mfma = value != 0; return 0; }        // affects GEMMs planned AFTER the call
-    if (!strcmp(name, "gemm_pair")) { ctx->gemm_pair = value != 0; return 0; }        // likewise
-    if (!strcmp(name, "mp_fused")) { ctx->mp_fused = value != 0; return 0; }
-    if (!strcmp(name, "ks_wide")) { ctx->ks_wide = value; return 0; }
-    if (!strcmp(name, "ks_split14")) { ctx->ks_split14 = value != 0; return 0; }
-    if (!strcmp(name, "ks_pair14")) { ctx->ks_pair14 = value != 0; return 0; }
-    if (!strcmp(name, "ks_chain")) { ctx->ks_chain = value != 0; return 0; }
-    if (!strcmp(name, "mp_bcast")) { ctx->mp_bcast = value != 0; return 0; }
+    if (const OptionSpec *o = find_option(name)) {
+        if (!o->flag && (value < o->lo || value > o->hi)) return fail(CN_ERR_ARG, "%s: %d .. %d", name, o->lo, o->hi);
+        ctx->opt.*o->member = o->flag ? value != 0 : value;
+        return 0;
+    }
     if (!strcmp(name, "defer")) {                // 0 immediate, 1 queued under the context lock, 2 queued through the lock-free submission ring; the queue was drained by LOCK
         if (value < 0 || value > 2) return fail(CN_ERR_ARG, "defer: 0, 1 or 2");
         ctx->defer.store(value, std::memory_order_release);
@@ -377,35 +371,18 @@ API_END }
 extern "C" int cn_get_option(cn_ctx *ctx, const char *name, int *value) { API_BODY
     LOCK_ONLY;
     if (!name || !value) return fail(CN_ERR_ARG, "null argument");
-    if (!strcmp(name, "f64")) *value = ctx->use_f64;
+    if (const OptionSpec *o = find_option(name)) *value = ctx->opt.*o->member;
     else if (!strcmp(name, "defer")) *value = ctx->defer.load(std::memory_order_relaxed);
+    else if (!strcmp(name, "ks_xi")) *value = (int)ctx->hc.ks_xi;
+    // read-only diagnostics: choices the library made and counters (tests)
     else if (!strcmp(name, "pin_laps")) *value = (int)ctx->pin_laps;                      // laps of the pinned upload ring (each one waits for the stream)
     else if (!strcmp(name, "ready_handles")) *value = (int)ctx->ready->size();          // allocated single-ciphertext arrays waiting for a lock-free cn_ct_alloc
-    else if (!strcmp(name, "ks_wide")) *value = ctx->ks_wide;
-    else if (!strcmp(name, "ks_xi")) *value = (int)ctx->hc.ks_xi;
-    else if (!strcmp(name, "ks_xcd")) *value = ctx->ks_xcd;
-    else if (!strcmp(name, "ks_pair14")) *value = ctx->ks_pair14;
-    else if (!strcmp(name, "ks_chain")) *value = ctx->ks_chain;
-    else if (!strcmp(name, "mp_bcast")) *value = ctx->mp_bcast;
-    else if (!strcmp(name, "sq_fused")) *value = ctx->sq_fused;
-    else if (!strcmp(name, "mp_fused")) *value = ctx->mp_fused;
-    else if (!strcmp(name, "gemm_mfma")) *value = ctx->gemm_mfma;
-    else if (!strcmp(name, "gemm_pair")) *value = ctx->gemm_pair;
-    else if (!strcmp(name, "sq_lds")) *value = ctx->sq_lds;
-    else if (!strcmp(name, "sq_pipe")) *value = ctx->sq_pipe;
-    else if (!strcmp(name, "sq_overlap")) *value = ctx->sq_overlap;
-    else if (!strcmp(name, "sq_halves")) *value = ctx->sq_halves;
-    else if (!strcmp(name, "defer_stagger")) *value = ctx->defer_stagger;
-    else if (!strcmp(name, "enc_fused")) *value = ctx->enc_fused;
-    else if (!strcmp(name, "fold_zero")) *value = ctx->fold_zero;
-    else if (!strcmp(name, "folded_zero_encryptions")) *value = (int)std::min<uint64_t>(ctx->folded_zero, 0x7fffffff);    // zero encryptions folded so far (tests)
-    else if (!strcmp(name, "mul_relin_pipelined")) *value = (int)std::min<uint64_t>(ctx->mr_pipelined, 0x7fffffff);      // Multiply + Relinearize batches run in parts over two streams (tests)
+    else if (!strcmp(name, "folded_zero_encryptions")) *value = (int)std::min<uint64_t>(ctx->folded_zero, 0x7fffffff);    // zero encryptions folded so far
+    else if (!strcmp(name, "mul_relin_pipelined")) *value = (int)std::min<uint64_t>(ctx->mr_pipelined, 0x7fffffff);      // Multiply + Relinearize batches run in parts over two streams
     else if (!strcmp(name, "behz_small_base")) *value = ctx->hc.bsk[ctx->hc.kb - 1].q < (1ull << 49);     // auxiliary primes below 2^49 (FP64 kernels) instead of SEAL's 61-bit ones
-    else if (!strcmp(name, "behz_f64")) *value = ctx->hc.behz_f64 && ctx->use_f64;
+    else if (!strcmp(name, "behz_f64")) *value = ctx->hc.behz_f64 && ctx->opt.f64;
     else if (!strcmp(name, "aux_primes")) *value = (int)ctx->hc.kb;
     else if (!strcmp(name, "pending_calls")) *value = (int)ctx->dq->ops.size();
-    else if (!strcmp(name, "ks_perm_fused")) *value = ctx->ks_perm_fused;
-    else if (!strcmp(name, "gemm_order")) *value = ctx->gemm_order;
     else if (!strcmp(name, "stream_tries")) *value = ctx->stream_tries;           // streams created until one had a hardware queue of its own (< 0: none had)
     else return fail(CN_ERR_ARG, "unknown option %s", name);
     return 0;
@@ -437,7 +414,7 @@ extern "C" int cn_ctx_wait_for(cn_ctx *ctx_, cn_ctx *other) {
 extern "C" size_t cn_key_words(cn_ctx *ctx, int which) { return (size_t)(which ? ctx->hc.gk_tot : ctx->hc.rl_tot) * ctx->ctw2; }
 
 // does this context keep its key-switch keys as FP64 images (the FP64 key-switch kernels read doubles)?
-bool keys_as_f64(const cn_ctx *ctx) { return ctx->use_f64 && ctx->hc.q_f64 && !ctx->legacy_ntt && ctx->hc.logn >= 10 && ctx->hc.logn <= 14; }
+bool keys_as_f64(const cn_ctx *ctx) { return ctx->opt.f64 && ctx->hc.q_f64 && !ctx->opt.legacy_ntt && ctx->hc.logn >= 10 && ctx->hc.logn <= 14; }
 // coeff_form: the words are coefficient-form polynomials [..][k][N]; the device transforms them with its own tables (cn_load_key, form 1)
 int set_key(cn_ctx *ctx, KsKey &slot, const uint64_t *words, size_t count, size_t expect, int is_dev, bool coeff_form) {
     if (!words || count != expect) return fail(CN_ERR_ARG, "key has %zu words, expected %zu", count, expect);

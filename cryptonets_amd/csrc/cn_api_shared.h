@@ -105,7 +105,6 @@ struct RotJob { const uint64_t *src; uint64_t *dst; int steps; std::vector<uint6
 
 // ---- functions defined in one unit and used by the others
 int cn_run_ntt(cn_ctx *c, uint64_t *data, uint32_t limbs, uint32_t base_off, uint32_t nmod, int inverse);
-void cn_stagger_forget(cn_ctx *ctx);
 const NoiseTab &cn_noise_table();          // thresholds of the noise sampler (cn_client.hip)
 std::vector<Slab> &slabs_of(cn_ctx *ctx);
 bool in_slab(cn_ctx *ctx, const void *p);
@@ -155,26 +154,20 @@ bool aux_stream_ready(cn_ctx *ctx);
 // of the part before it (event), its key switch behind its own Multiply (stream order) - [mul 0][ks 0 | mul 1][ks 1 | mul 2][ks 2]: the HBM-bound base extension / floor and
 // the transform kernels of a Multiply fill what the FP64-bound key switch of the part before leaves.  The context's stream continues behind the last part of either stream.
 // Three parts of 30 / 40 / 30 % measured best for the CryptoNets batch (profiles/r06_mulrelin_parts.txt: plain loop of the two primes 12.6 -> 12.0-12.2 ms, the half-batch
-// stagger of the primes 12.2-12.6; two parts 12.4-12.5, four 12.7, five 12.4); CN_SQ_PARTS / CN_SQ_SPLIT (cut points in per mille) for experiments.
+// stagger of the primes 12.2-12.6; two parts 12.4-12.5, four 12.7, five 12.4).
 // mul(first, count), ks(first, count) launch on ctx->stream.
 static const uint32_t SQ_HALVES_MIN = 512;       // (the 100-ciphertext layer of CryptoNets pipelined as well: 12.35 -> 13.4 ms per batch, visit AY)
-// the parts of a pipelined batch of c ciphertexts: part i = [first[i], first[i + 1]); returns the number of parts P (first[] holds P + 1 entries, P <= 8)
-static inline uint32_t pipeline_cuts(uint32_t c, uint32_t first[9]) {
-    static const uint32_t parts_env = [] { const char *e = getenv("CN_SQ_PARTS"); const int v = e ? atoi(e) : 3; return (uint32_t)(v >= 2 && v <= 8 ? v : 3); }();
-    const uint32_t P = std::min<uint32_t>(parts_env, c / 128 ? c / 128 : 1);
+// the parts of a pipelined batch of c ciphertexts: part i = [first[i], first[i + 1]); returns the number of parts P = min(3, max(1, c / 128)) (first[] holds P + 1
+// entries).  Three parts are cut at 30 and 70 %, two at the half; every cut is rounded up to a multiple of 8.
+static inline uint32_t pipeline_cuts(uint32_t c, uint32_t first[4]) {
+    const uint32_t P = std::min<uint32_t>(3, std::max<uint32_t>(1, c / 128));
     first[0] = 0; first[P] = c;
-    if (P < 2) return P;
-    for (uint32_t i = 1; i < P; i++) first[i] = (uint32_t)(((uint64_t)c * i / P + 7) & ~7ull);
-    static const std::vector<uint32_t> cuts = [] {                    // experiment: CN_SQ_SPLIT="250,625" = the cut points in per mille (P - 1 of them, increasing)
-        std::vector<uint32_t> v; const char *e = getenv("CN_SQ_SPLIT");
-        while (e && *e) { v.push_back((uint32_t)atoi(e)); e = strchr(e, ','); if (e) e++; }
-        return v; }();
-    if (cuts.empty() && P == 3) { first[1] = (uint32_t)(((uint64_t)c * 3 / 10 + 7) & ~7ull); first[2] = (uint32_t)(((uint64_t)c * 7 / 10 + 7) & ~7ull); }
-    if (cuts.size() + 1 == P) for (uint32_t i = 1; i < P; i++) first[i] = std::min<uint32_t>(c, (uint32_t)(((uint64_t)c * cuts[i - 1] / 1000 + 7) & ~7ull));
+    if (P == 2) first[1] = (c / 2 + 7) & ~7u;
+    if (P == 3) { first[1] = (uint32_t)(((uint64_t)c * 3 / 10 + 7) & ~7ull); first[2] = (uint32_t)(((uint64_t)c * 7 / 10 + 7) & ~7ull); }
     return P;
 }
 template <class FM, class FK> static int pipelined_halves(cn_ctx *ctx, uint32_t c, FM mul, FK ks) {
-    uint32_t first[9];
+    uint32_t first[4];
     const uint32_t P = pipeline_cuts(c, first);
     if (P < 2) { CHECK(mul(0u, c)); return ks(0u, c); }
     ctx->mr_pipelined++;
@@ -207,7 +200,7 @@ int ks_planned_mode(cn_ctx *ctx, uint32_t cnt, int galois);
 // may a Multiply + Relinearize of c ciphertexts run through pipelined_halves?  Only if the key switch of every part is the fused kernel: the two-launch forms keep their
 // partial products in the context's ONE arena ks_part (and may re-allocate it), which the parts on the two streams would share
 static inline bool pipeline_fused_ks(cn_ctx *ctx, uint32_t c) {
-    uint32_t first[9];
+    uint32_t first[4];
     const uint32_t P = pipeline_cuts(c, first);
     for (uint32_t i = 0; i < P; i++) if (ks_planned_mode(ctx, first[i + 1] - first[i], 0) != 0) return false;
     return P >= 2;

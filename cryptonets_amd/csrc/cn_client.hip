@@ -197,8 +197,8 @@ int encrypt_chain(cn_ctx *ctx, uint32_t cnt, const uint64_t *ptd, uint32_t pt_st
     hipLaunchKernelGGL(k_sample_small, dim3((unsigned)(((uint64_t)cnt * (n / 16) + 255) / 256)), dim3(256), 0, ctx->stream, us, n, 0, 1u, cnt, key, seed, 0u, item0, (const EncTab *)dtab, cn_noise_table());
     hipLaunchKernelGGL(k_sample_small, dim3((unsigned)(((uint64_t)cnt * 2 * (n / 8) + 255) / 256)), dim3(256), 0, ctx->stream, es, n, 1, 2u, cnt, key, seed, 1u, item0, (const EncTab *)dtab, cn_noise_table());
     if (!htab) ctx->rng_item += cnt;
-    const bool f64 = ctx->use_f64 && ctx->hc.q_f64;
-    if (ctx->enc_fused && !ctx->legacy_ntt) {                 // one kernel behind the samplers: u stays in registers between its transform and the two components
+    const bool f64 = ctx->opt.f64 && ctx->hc.q_f64;
+    if (ctx->opt.enc_fused && !ctx->opt.legacy_ntt) {                 // one kernel behind the samplers: u stays in registers between its transform and the two components
         uint64_t qmax = 0; for (uint32_t j = 0; j < k; j++) qmax = std::max(qmax, ctx->hc.q[j].q);
         const int pol = f64 ? ((qmax >> 44) ? POL_F64 : POL_F64L) : POL_U64;
         if (rr_ops[pol]->enc_fused(ctx, us, ptd, pt_stride_words, out, cnt, es, dtab)) {

@@ -109,28 +109,7 @@ int flush_gemm_group(cn_ctx *ctx, DeferQueue *q, const std::vector<const DOp *> 
         memcpy(&A[(size_t)o * K], &q->addr[ops[o]->terms], (size_t)K * 8);
         memcpy(&Wt[(size_t)o * K], &q->wt[ops[o]->terms], (size_t)K * 8);
     }
-    // Windows that share at least half of their inputs are merged in pairs, like cn_gemm_plan_create does for the batched path (pair_gather_lists: every shared input then
-    // travels from L2 to a CU once - the CryptoNets convolution 371 -> 299 us).  Round 5 measured this inside the flush as a LOSS (16.1-17.7 against 15.1-15.5 ms per batch: the
-    // pairing ran on the flushing thread under the lock every caller waited for).  Round 6, with the flush off the callers' path and index tables (below): alone on the device the paired
-    // convolution is as fast as a plan's (310 against 500 us unpaired), end to end nothing moves and the pairing's host time sits at the head of a batch (profiles/r06_defer_pair_ab.txt).
-    // OFF unless CN_DEFER_PAIR=1.
-    static const bool pair_on = getenv("CN_DEFER_PAIR") && atoi(getenv("CN_DEFER_PAIR"));
-    if (pair_on && ctx->gemm_pair && ar.small && K <= 64 && O >= 2) {
-        std::unordered_map<uint64_t, int32_t> id_of; std::vector<uint64_t> addr_of;
-        std::vector<int32_t> gidx((size_t)O * K);
-        for (size_t x = 0; x < A.size(); x++) {
-            if (!A[x]) { gidx[x] = -1; continue; }
-            auto it = id_of.find(A[x]);
-            if (it == id_of.end()) { it = id_of.emplace(A[x], (int32_t)addr_of.size()).first; addr_of.push_back(A[x]); }
-            gidx[x] = it->second;
-        }
-        std::vector<uint64_t> W2; uint32_t K2 = K;
-        if (pair_gather_lists(O, K2, gidx, Wt.data(), W2)) {
-            K = K2; Wt.swap(W2);
-            A.assign((size_t)O * K, 0);
-            for (size_t x = 0; x < A.size(); x++) if (gidx[x] >= 0) A[x] = addr_of[gidx[x]];
-        }
-    }
+    // (the gather lists are not paired here as cn_gemm_plan_create pairs them: end to end neutral, the pairing's host time at the head of a batch - profiles/r06_defer_pair_ab.txt)
     // group the outputs that gather the same inputs (PoolLayer: every map of one corner shares its patch; a dense layer: one group)
     std::map<std::vector<uint64_t>, std::vector<uint32_t>> groups;
     for (uint32_t o = 0; o < O; o++) groups[std::vector<uint64_t>(A.begin() + (size_t)o * K, A.begin() + (size_t)(o + 1) * K)].push_back(o);
@@ -172,7 +151,7 @@ int flush_gemm_group(cn_ctx *ctx, DeferQueue *q, const std::vector<const DOp *> 
     // Index tables instead of address tables (round 6).  Every array the library hands out starts on a 256-byte boundary, so the operands of a flush group are 32-bit offsets in units
     // of 32 words from the lowest address among them - the INDEX-table kernels of a plan (one 16-byte scalar load per four gather entries, offsets multiplied on the scalar unit)
     // instead of the address-table variants (two loads per four, a 64-bit select per term): dense layer 242 -> 221 us alone on the device, convolution 506 -> 492
-    // (310 with CN_DEFER_PAIR=1; profiles/r06_defer_pair_ab.txt); end to end neutral.  Needs a bias on every output or on none; CN_DEFER_REL=0 keeps the address tables (A/B).
+    // (310 with the gather lists paired, profiles/r06_defer_pair_ab.txt); end to end neutral.  Needs a bias on every output or on none; CN_DEFER_REL=0 keeps the address tables (A/B).
     static const bool rel_on = !(getenv("CN_DEFER_REL") && !atoi(getenv("CN_DEFER_REL")));
     uint64_t ibase = ~0ull, obase_a = ~0ull, bbase = ~0ull;
     bool rel = rel_on && (!any_bias || all_bias);
@@ -200,7 +179,7 @@ int flush_gemm_group(cn_ctx *ctx, DeferQueue *q, const std::vector<const DOp *> 
         CHECK(ensure_scratch(ctx, al(host.size())));
         char *tables; CHECK(upload_tmp(ctx, host.data(), host.size(), &tables));
         GemmLaunch gl{small, two, false, MT, (const uint64_t *)ibase, tables, tables + off_w, tables + off_oidx, any_bias ? (const uint64_t *)bbase : nullptr, tables + off_bidx,
-                      (uint64_t *)obase_a, G, M, K, lazy, Kp, 0, WP, (M + 31) / 32, (K + 31) / 32, 2, (uint32_t)ctx->gemm_order, one};
+                      (uint64_t *)obase_a, G, M, K, lazy, Kp, 0, WP, (M + 31) / 32, (K + 31) / 32, 2, (uint32_t)ctx->opt.gemm_order, one};
         gl.in_unit = gl.out_unit = gl.bias_unit = 32;
         return mfma ? cn_l_gemm_mfma(ctx, gl) : cn_l_gemm(ctx, gl);
     }
@@ -213,7 +192,7 @@ int flush_gemm_group(cn_ctx *ctx, DeferQueue *q, const std::vector<const DOp *> 
     CHECK(ensure_scratch(ctx, al(host.size())));
     char *tables; CHECK(upload_tmp(ctx, host.data(), host.size(), &tables));
     GemmLaunch gl{small, two, true, MT, fallback, tables, tables + off_w, tables + off_oidx, nullptr, any_bias ? tables + off_bidx : nullptr, nullptr,
-                  G, M, K, lazy, Kp, 0, WP, (M + 31) / 32, (K + 31) / 32, 2, (uint32_t)ctx->gemm_order, one};
+                  G, M, K, lazy, Kp, 0, WP, (M + 31) / 32, (K + 31) / 32, 2, (uint32_t)ctx->opt.gemm_order, one};
     return mfma ? cn_l_gemm_mfma(ctx, gl) : cn_l_gemm(ctx, gl);
 }
 int flush_elementwise_group(cn_ctx *ctx, const std::vector<const DOp *> &ops, int type) {
@@ -225,80 +204,6 @@ int flush_elementwise_group(cn_ctx *ctx, const std::vector<const DOp *> &ops, in
     if (type == DOP_ADD || type == DOP_SUB) hipLaunchKernelGGL(k_addsub_tab, dim3(limbs * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, dt, ctx->dc, ctx->chunks, type == DOP_SUB);
     else hipLaunchKernelGGL(k_add_plain_tab, dim3(limbs * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, dt, ctx->dc, ctx->chunks, type == DOP_SUBPLAIN);
     HIPCHK(hipGetLastError()); launch_count(ctx);
-    return 0;
-}
-// Staggered plaintext-prime channels for the UNCHANGED caller (round 6, `defer_stagger`; THREE FORMS MEASURED, NONE WITH A GAIN - OFF BY DEFAULT, profiles/r06_stagger_ab.txt).  The reference runs the same layer on every plaintext prime from the same caller threads
-// (EncryptedSealBfvVector.cs:225-236), so the two contexts of a CryptoNets device flush their big squaring layers within microseconds of each other and their kernel chains run in
-// lock step - key switch beside key switch (both FP64-issue bound), element-wise BEHZ steps beside each other (both HBM bound).  The batched bench alternates the two channels'
-// "fronts" (convolution + Multiply) with cn_ctx_wait_for, so that a front always runs beside the OTHER channel's key switch: 12.0-12.2 against 12.7-12.9 ms per batch, and it is the
-// device-side ordering that does it, not the split into two calls (profiles/r06_stagger_ab.txt, visit N).  Here the library does the same for queued squaring groups of >= 256
-// ciphertexts when exactly two contexts of a device take part: front #k of the first context (A) waits for front #(k-1) of the second (B), B's #k for A's #k - device-side events,
-// strict alternation A0 B0 A1 B1 ... whatever order the host flushes them in.  When the partner has not ENQUEUED the front that is waited for yet (the two flushes are triggered
-// microseconds apart by different threads), the flushing thread waits for it on the host, at most STAGGER_HOST_WAIT_US - a partner that never comes is skipped, counts that drift
-// apart re-pair.  Two earlier forms measured no gain and are gone: waiting for whoever flushed last (a leader swap stalls the leader for the trailing context's front), and a fixed
-// leader without the host wait (B's flush often precedes A's: no stagger, or a delayed front that is just a delay).  This third form engages (14 device-side waits in 16 fronts,
-// one host wait ran out) and still measures 14.1-14.8 against 13.9 ms per batch (taps skipped, 16 threads, three alternating pairs): what the batched program gains from the same
-// alternation does not carry over to the flush pattern of the unchanged caller (its convolution, dense and second squaring layers are flushed on their own, ahead of the fronts).
-namespace {
-struct StaggerPair {
-    cn_ctx *c[2] = {nullptr, nullptr}; uint64_t n[2] = {0, 0}; hipEvent_t ev[2] = {nullptr, nullptr};
-    bool off = false;                 // more than two contexts stagger on this device: nobody waits
-    uint64_t waits = 0, timeouts = 0, ahead = 0, first = 0;      // CN_DEFER_TRACE: device-side waits placed / host waits that ran out / partner ahead / nothing to wait for
-};
-std::mutex g_front_mu;
-StaggerPair g_pair[64];              // per device
-}
-static const uint32_t STAGGER_MIN_CTS = 256;
-static const int STAGGER_HOST_WAIT_US = 400;
-void cn_stagger_forget(cn_ctx *ctx) {             // a context that goes away takes its events with it: the pairing of its device starts over
-    std::lock_guard<std::mutex> lk(g_front_mu);
-    StaggerPair &p = g_pair[(unsigned)ctx->device % 64];
-    if (p.c[0] == ctx || p.c[1] == ctx) {
-        if (getenv("CN_DEFER_TRACE") && (p.waits || p.timeouts)) fprintf(stderr, "stagger device %d: %llu device-side waits, %llu host waits ran out, %llu partner ahead, %llu first, fronts %llu / %llu\n",
-            ctx->device, (unsigned long long)p.waits, (unsigned long long)p.timeouts, (unsigned long long)p.ahead, (unsigned long long)p.first, (unsigned long long)p.n[0], (unsigned long long)p.n[1]);
-        p = StaggerPair();
-    }
-}
-static int stagger_slot(StaggerPair &p, cn_ctx *ctx) {      // (mutex held) 0 / 1, or -1: not a participant
-    if (p.off) return -1;
-    for (int i = 0; i < 2; i++) if (p.c[i] == ctx) return i;
-    for (int i = 0; i < 2; i++) if (!p.c[i]) {        // a late joiner lines up with its partner's latest front: A's #k follows B's #(k-1), B's #k follows A's #k
-        p.c[i] = ctx;
-        p.n[i] = i == 0 ? p.n[1] : (p.n[0] ? p.n[0] - 1 : 0);
-        return i;
-    }
-    p.off = true;
-    return -1;
-}
-static int stagger_front_begin(cn_ctx *ctx) {
-    const auto t0 = std::chrono::steady_clock::now();
-    for (;;) {
-        {
-            std::lock_guard<std::mutex> lk(g_front_mu);
-            StaggerPair &p = g_pair[(unsigned)ctx->device % 64];
-            const int i = stagger_slot(p, ctx);
-            if (i < 0 || !p.c[1 - i]) return 0;
-            const uint64_t k = p.n[i], need = i == 0 ? k : k + 1, have = p.n[1 - i];       // A's #k follows B's #(k-1): B has recorded k fronts; B's #k follows A's #k: A has recorded k + 1
-            if (need == 0) { p.first++; return 0; }
-            if (have == need) { if (p.ev[1 - i]) HIPCHK(hipStreamWaitEvent(ctx->stream, p.ev[1 - i], 0)); p.waits++; return 0; }
-            if (have > need) { p.ahead++; if (have > need + 2) { p.n[0] = p.n[1] = 0; } return 0; }   // the partner is ahead: nothing to wait for (far ahead: the counts drifted - re-pair)
-            if (std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count() > STAGGER_HOST_WAIT_US) { p.timeouts++; return 0; }
-        }
-        if (std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count() > 4 * STAGGER_HOST_WAIT_US) return 0;
-        std::this_thread::yield();                // the partner's flush is microseconds away (another thread, the other context's lock)
-    }
-}
-static int stagger_front_end(cn_ctx *ctx) {
-    if (!ctx->ev_front) HIPCHK(hipEventCreateWithFlags(&ctx->ev_front, hipEventDisableTiming));
-    std::lock_guard<std::mutex> lk(g_front_mu);
-    StaggerPair &p = g_pair[(unsigned)ctx->device % 64];
-    const int i = stagger_slot(p, ctx);
-    if (i < 0) return 0;
-    HIPCHK(hipEventRecord(ctx->ev_front, ctx->stream));
-    p.ev[i] = ctx->ev_front; p.n[i]++;
-    static const bool trace = getenv("CN_DEFER_TRACE") != nullptr;
-    if (trace && i == 1 && p.n[i] % 4 == 0) fprintf(stderr, "stagger device %d: fronts %llu / %llu, %llu device-side waits, %llu host waits ran out, %llu partner ahead, %llu first\n", ctx->device,
-        (unsigned long long)p.n[0], (unsigned long long)p.n[1], (unsigned long long)p.waits, (unsigned long long)p.timeouts, (unsigned long long)p.ahead, (unsigned long long)p.first);
     return 0;
 }
 // all queued Multiply + Relinearize calls of one level: the batched BEHZ pipeline + ONE key switch, operands and results through tables
@@ -321,15 +226,12 @@ int flush_mulrelin_group(cn_ctx *ctx, const std::vector<const DOp *> &all) {
             CHECK(upload_tmp(ctx, ho.data(), c, &dout));
             uint64_t *t3 = salloc<uint64_t>(ctx, (size_t)c * 3 * kn);
             if (!t3) return fail(CN_ERR_HIP, "internal: scratch exhausted in deferred multiply");
-            const bool stagger = ctx->defer_stagger && c >= STAGGER_MIN_CTS && !ctx->capturing;
             auto mul = [&](uint32_t f, uint32_t n_) { return do_multiply(ctx, nullptr, 1, nullptr, 1, t3 + (size_t)f * 3 * kn, n_, da + f, (sq ? da : db) + f); };
             auto ksw = [&](uint32_t f, uint32_t n_) { uint64_t *t = t3 + (size_t)f * 3 * kn; return do_keyswitch(ctx, t + 2 * kn, 3 * kn, t, t + kn, 3 * kn, ctx->rlk, nullptr, n_, 0, nullptr, 0, dout + f); };
-            if (ctx->sq_halves >= 2 && !stagger && !ctx->sq_overlap && ctx->hc.logn <= 13 && c >= SQ_HALVES_MIN && !ctx->capturing && pipeline_fused_ks(ctx, c) && aux_stream_ready(ctx)) {
+            if (ctx->opt.sq_halves >= 2 && ctx->hc.logn <= 13 && c >= SQ_HALVES_MIN && !ctx->capturing && pipeline_fused_ks(ctx, c) && aux_stream_ready(ctx)) {
                 CHECK(pipelined_halves(ctx, c, mul, ksw)); continue;
             }
-            if (stagger) CHECK(stagger_front_begin(ctx));
             CHECK(mul(0, c));
-            if (stagger) CHECK(stagger_front_end(ctx));
             CHECK(ksw(0, c));
         }
     }
@@ -506,7 +408,7 @@ int flush_encrypt_group(cn_ctx *ctx, const std::vector<const DOp *> &ops) {
 // the weighted sums of folded zero encryptions (cn_defer_flush), added onto the outputs of the scalar products `gemms` (launched just before): the samplers draw
 // u, e1, e2 of every folded encryption exactly as flush_encrypt_group would have (its nonce, its item), k_encrypt_fold does the rest
 bool zero_fold_ok(cn_ctx *ctx) {
-    return ctx->pk && ctx->enc_fused && !ctx->legacy_ntt && ctx->use_f64 && ctx->hc.q_f64 && ctx->hc.logn >= 10 && ctx->hc.logn <= 13;
+    return ctx->pk && ctx->opt.enc_fused && !ctx->opt.legacy_ntt && ctx->opt.f64 && ctx->hc.q_f64 && ctx->hc.logn >= 10 && ctx->hc.logn <= 13;
 }
 int flush_zero_folds(cn_ctx *ctx, DeferQueue *q, const std::vector<const DOp *> &gemms) {
     const uint32_t n = ctx->hc.n;
@@ -592,7 +494,7 @@ int cn_defer_flush(cn_ctx *ctx) {
         // not materialised: their weighted sum is folded onto the scalar product's output by linearity (k_encrypt_fold: same words, a fifth of the transforms, the
         // scalar product reads no extra ciphertexts and the outputs of a border patch share their gather list again).  Conditions, all on whole arrays: the
         // encryption is the last writer of its array, exactly one queued call reads it - a scalar product on a deeper level - and the caller has released it.
-        if (ctx->fold_zero && zero_fold_ok(ctx)) {
+        if (ctx->opt.fold_zero && zero_fold_ok(ctx)) {
             std::unordered_map<const uint64_t *, int32_t> cand;
             size_t zero_encs = 0;
             for (size_t x = 0; x < ops.size(); x++) {

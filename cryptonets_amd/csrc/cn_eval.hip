@@ -68,10 +68,10 @@ int mul_plain_fused(cn_ctx *ctx, Buffer *A, uint32_t ai, bool a_bcast, Buffer *P
     uint64_t *o = O->d + oi * O->item_words;
     const uint64_t *src = A->d + ai * A->item_words;
     // one input ciphertext broadcast over the outputs: it must survive until the last block has read it
-    bool f64 = ctx->use_f64, light = true;
+    bool f64 = ctx->opt.f64, light = true;
     for (uint32_t m = 0; m < k; m++) { f64 = f64 && ctx->hc.f64ok[m]; if (ctx->hc.q[m].q >> 44) light = false; }
     const int pol = f64 && light ? POL_F64L : (f64 ? POL_F64 : POL_U64);
-    if (a_bcast && pstride && count >= 4 && ctx->mp_bcast) {      // one ciphertext x many plaintexts: transform the ciphertext once, the plaintexts inside the product kernel
+    if (a_bcast && pstride && count >= 4 && ctx->opt.mp_bcast) {      // one ciphertext x many plaintexts: transform the ciphertext once, the plaintexts inside the product kernel
         uint64_t *ctn = nx ? nx->ctn : nullptr;
         if (!nx) { CHECK(ensure_scratch(ctx, al(A->item_words * 8))); ctn = salloc<uint64_t>(ctx, A->item_words); }
         if (!ctn) return fail(CN_ERR_HIP, "internal: scratch exhausted in multiply_plain");
@@ -102,7 +102,7 @@ int mul_plain_fused(cn_ctx *ctx, Buffer *A, uint32_t ai, bool a_bcast, Buffer *P
     ctx->st.PlainMultiplication += count;
     return 0;
 }
-bool mul_plain_takes_bcast(cn_ctx *ctx, uint32_t count) { return ctx->mp_fused && ctx->mp_bcast && !ctx->legacy_ntt && ctx->hc.logn >= 10 && ctx->hc.logn <= 14 && count >= 4; }
+bool mul_plain_takes_bcast(cn_ctx *ctx, uint32_t count) { return ctx->opt.mp_fused && ctx->opt.mp_bcast && !ctx->opt.legacy_ntt && ctx->hc.logn >= 10 && ctx->hc.logn <= 14 && count >= 4; }
 int mul_plain_impl(cn_ctx *ctx, Buffer *A, uint32_t ai, bool a_bcast, Buffer *P, uint32_t pi, uint32_t pstride, Buffer *O, uint32_t oi, uint32_t count,
                           const BcastNext *nx) {
     if (!range_ok(A, ai, a_bcast ? 1 : count) || !range_ok(O, oi, count) || !range_ok(P, pi, pstride ? count : 1, pstride ? pstride : 1))
@@ -112,7 +112,7 @@ int mul_plain_impl(cn_ctx *ctx, Buffer *A, uint32_t ai, bool a_bcast, Buffer *P,
         return fail(CN_ERR_ARG, "multiply_plain: input and output ranges overlap partially (use the same range or disjoint ranges)");
     const uint32_t n = ctx->hc.n, k = ctx->hc.k, npt = pstride ? count : 1;
     for (uint32_t c = 0; c < npt; c++) if (P->pt_zero[pi + c * pstride]) return fail(CN_ERR_ZERO, "plain cannot be zero");
-    if (ctx->mp_fused && !ctx->legacy_ntt && ctx->hc.logn >= 10 && ctx->hc.logn <= 14) return mul_plain_fused(ctx, A, ai, a_bcast, P, pi, pstride, O, oi, count, nx);
+    if (ctx->opt.mp_fused && !ctx->opt.legacy_ntt && ctx->hc.logn >= 10 && ctx->hc.logn <= 14) return mul_plain_fused(ctx, A, ai, a_bcast, P, pi, pstride, O, oi, count, nx);
     if (nx) return fail(CN_ERR_ARG, "internal: chained row-dot batch outside the fused product");
     CHECK(ensure_scratch(ctx, al((size_t)npt * k * n * 8)));
     uint64_t *lift = salloc<uint64_t>(ctx, (size_t)npt * k * n);
@@ -180,7 +180,7 @@ GemmArith gemm_arith(cn_ctx *ctx, bool weights_small) {
     const int bits = 64 - __builtin_clzll(qmax);
     GemmArith g;
     g.bits = bits;
-    g.small = weights_small && ctx->use_f64 && bits <= 49;       // the kernel folds its limb sums with exact-FP64 modular arithmetic (q < 2^49.4)
+    g.small = weights_small && ctx->opt.f64 && bits <= 49;       // the kernel folds its limb sums with exact-FP64 modular arithmetic (q < 2^49.4)
     g.two = bits <= 44;                                          // 2 limbs of 22 bits, else 3 limbs of 17 bits
     if (g.small) g.lazy = g.two ? 1024u : 32768u;                // terms whose limb products (< 2^42 / 2^37) still sum exactly below 2^52
     else g.lazy = (2 * bits >= 127) ? 1u : (uint32_t)std::min<uint64_t>(1u << 20, 1ull << (127 - 2 * bits));   // products of two values < q_max in 128 bits
@@ -190,7 +190,7 @@ GemmArith gemm_arith(cn_ctx *ctx, bool weights_small) {
 // ---- the matrix-core form of a scalar GEMM (k_scalar_gemm_mfma): eligibility, weight digit planes, A fragments
 // 6 signed base-256 digits cover residues below 2^46 (x + 0x80..80 must stay below 2^48); i32 accumulators hold K * P * 2^14 < 2^31
 bool gemm_mfma_ok(cn_ctx *ctx, const GemmArith &ar, uint32_t M, uint32_t K) {
-    return ctx->gemm_mfma && ar.small && ar.bits <= 46 && M >= 16 && (uint64_t)K * 3 < (1u << 17) && !(ctx->hc.n & 31);
+    return ctx->opt.gemm_mfma && ar.small && ar.bits <= 46 && M >= 16 && (uint64_t)K * 3 < (1u << 17) && !(ctx->hc.n & 31);
 }
 uint32_t gemm_weight_planes(cn_ctx *ctx, const uint64_t *W, size_t count) {
     uint64_t amax = 0;
@@ -281,7 +281,7 @@ int build_gemm_plan(cn_ctx *ctx, const int32_t *idx, const uint64_t *W, uint32_t
         if (BP && (bias_idx[o] < 0 || (uint32_t)bias_idx[o] >= BP->count)) return fail(CN_ERR_ARG, "bias index out of range");
     }
     std::vector<uint64_t> W2;
-    if (ctx->gemm_pair && gemm_arith(ctx, gemm_weights_small(ctx, W, (size_t)O * K)).small && pair_gather_lists(O, K, gidx, W, W2)) W = W2.data();
+    if (ctx->opt.gemm_pair && gemm_arith(ctx, gemm_weights_small(ctx, W, (size_t)O * K)).small && pair_gather_lists(O, K, gidx, W, W2)) W = W2.data();
     // group outputs that gather the same inputs (PoolLayer: every map of one corner shares its patch)
     std::map<std::vector<int32_t>, std::vector<uint32_t>> groups;
     for (uint32_t o = 0; o < O; o++) groups[std::vector<int32_t>(gidx.begin() + (size_t)o * K, gidx.begin() + (size_t)(o + 1) * K)].push_back(o);
@@ -340,7 +340,7 @@ int run_gemm_plan(cn_ctx *ctx, const GemmPlan &P, const char *tables, Buffer *I,
         bias = BP->d;
     }
     GemmLaunch gl{P.small, P.two, false, P.MT, I->d, tables, tables + P.off_w, tables + P.off_oidx, bias, tables + P.off_bidx, OB->d,
-                  P.G, P.M, P.K, P.lazy, P.Kp, oi, P.P, P.mtiles, P.ksteps, I->size, (uint32_t)ctx->gemm_order, P.one};
+                  P.G, P.M, P.K, P.lazy, P.Kp, oi, P.P, P.mtiles, P.ksteps, I->size, (uint32_t)ctx->opt.gemm_order, P.one};
     CHECK(P.mfma ? cn_l_gemm_mfma(ctx, gl) : cn_l_gemm(ctx, gl));
     ctx->st.PlainMultiplication += P.nnz; ctx->st.Addition += P.nnz - P.O;
     if (P.has_bias) ctx->st.PlainAddition += P.O;
@@ -381,8 +381,8 @@ API_END }
 // ---------------------------------------------------------------- BEHZ multiply / key switching
 // tensor product fused into the inverse transform (register-radix sizes only); returns false when the caller must fall back
 bool run_intt_tensor(cn_ctx *c, const uint64_t *A, const uint64_t *B, uint64_t *D, uint32_t cnt, uint32_t base_off, uint32_t Lm) {
-    if (c->legacy_ntt || c->hc.logn < 10 || c->hc.logn > 14) return false;
-    bool f64 = c->use_f64, light = true;
+    if (c->opt.legacy_ntt || c->hc.logn < 10 || c->hc.logn > 14) return false;
+    bool f64 = c->opt.f64, light = true;
     for (uint32_t m = base_off; m < base_off + Lm; m++) {
         f64 = f64 && c->hc.f64ok[m];
         uint64_t q = m < c->hc.k ? c->hc.q[m].q : c->hc.bsk[m - c->hc.k].q;
@@ -394,7 +394,7 @@ bool run_intt_tensor(cn_ctx *c, const uint64_t *A, const uint64_t *B, uint64_t *
 }
 // squaring: forward transforms, tensor and inverse transforms of one (ciphertext, limb) in ONE kernel (FP64 policies)
 bool square_fused_ok(cn_ctx *c, uint32_t base_off, uint32_t Lm, bool &light) {
-    if (!c->sq_fused || c->legacy_ntt || !c->use_f64 || c->hc.logn < 10 || c->hc.logn > 14) return false;
+    if (!c->opt.sq_fused || c->opt.legacy_ntt || !c->opt.f64 || c->hc.logn < 10 || c->hc.logn > 14) return false;
     light = true;
     for (uint32_t m = base_off; m < base_off + Lm; m++) {
         if (!c->hc.f64ok[m]) return false;
@@ -448,24 +448,11 @@ int do_multiply(cn_ctx *ctx, const uint64_t *a, uint32_t astride, const uint64_t
     if (!square) { bq = salloc<uint64_t>(ctx, (size_t)cnt * 2 * k * n); bb = salloc<uint64_t>(ctx, (size_t)cnt * 2 * kb * n); }
     uint64_t *dq = salloc<uint64_t>(ctx, (size_t)cnt * 3 * k * n), *db = salloc<uint64_t>(ctx, (size_t)cnt * 3 * kb * n);
     if ((!fused && !aq) || !ab || (!square && (!bq || !bb)) || !dq || !db) return fail(CN_ERR_HIP, "internal: scratch exhausted in multiply");
-    // Squaring of a batch, "sq_overlap": the q-side transform kernel needs only the input, the Bsk side needs k_behz_extend's output - so the q side runs on a second
-    // stream of the context beside [extend -> Bsk side] and joins in front of k_behz_floor (round 6).  The two resident transform kernels cannot share a CU
-    // (130 KiB of LDS each), but the HBM-bound base extension (no LDS, few registers) runs beside the q side's workgroups instead of in front of them.
-    const bool overlap = fused && ctx->sq_overlap && !ctx->capturing && cnt >= 64 && aux_stream_ready(ctx);
-    if (overlap) {
-        HIPCHK(hipEventRecord(ctx->ev_fork, ctx->stream));
-        HIPCHK(hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
-        std::swap(ctx->stream, ctx->stream2);
-        run_square_fused(ctx, a, (size_t)astride * 2 * k * n, atab, dq, cnt, 0, k, lq);
-        std::swap(ctx->stream, ctx->stream2);
-        HIPCHK(hipEventRecord(ctx->ev_join, ctx->stream2));
-    }
     CHECK(cn_l_behz_extend(ctx, a, astride, atab, aq, ab, cnt));
     if (!square) CHECK(cn_l_behz_extend(ctx, b, bstride, btab, bq, bb, cnt));
     if (fused) {
-        if (!overlap) run_square_fused(ctx, a, (size_t)astride * 2 * k * n, atab, dq, cnt, 0, k, lq);
+        run_square_fused(ctx, a, (size_t)astride * 2 * k * n, atab, dq, cnt, 0, k, lq);
         run_square_fused(ctx, ab, (size_t)2 * kb * n, nullptr, db, cnt, k, kb, lb);
-        if (overlap) HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
     } else {
     CHECK(cn_run_ntt(ctx, aq, cnt * 2 * k, 0, k, 0)); CHECK(cn_run_ntt(ctx, ab, cnt * 2 * kb, k, kb, 0));
     if (!square) { CHECK(cn_run_ntt(ctx, bq, cnt * 2 * k, 0, k, 0)); CHECK(cn_run_ntt(ctx, bb, cnt * 2 * kb, k, kb, 0)); }
@@ -510,10 +497,10 @@ uint32_t ks_wide_max_blocks() {               // (ciphertext, limb) blocks up to
 // the variant do_keyswitch takes for `cnt` ciphertexts: 0 = the fused kernel, 1 / 2 = two launches (KsArgs::mode)
 int ks_planned_mode(cn_ctx *ctx, uint32_t cnt, int galois) {
     const uint32_t k = ctx->hc.k, tot_dig = galois ? ctx->hc.gk_tot : ctx->hc.rl_tot;
-    const bool rr = !ctx->legacy_ntt && ctx->hc.logn >= 10 && ctx->hc.logn <= 14;
-    if (!(rr && (ctx->ks_wide > 0 || (ctx->ks_wide < 0 && cnt * k <= KS_WIDE_MAX_BLOCKS)))) return 0;
+    const bool rr = !ctx->opt.legacy_ntt && ctx->hc.logn >= 10 && ctx->hc.logn <= 14;
+    if (!(rr && (ctx->opt.ks_wide > 0 || (ctx->opt.ks_wide < 0 && cnt * k <= KS_WIDE_MAX_BLOCKS)))) return 0;
     // N = 16384: 1024-thread workgroups cannot hold two accumulator sets without spilling -> per-digit only
-    const int mode = ctx->ks_wide == 2 || (ctx->ks_wide < 0 && cnt * k > KS_DIGIT_MAX_BLOCKS && ctx->hc.logn < 14) ? 2 : 1;
+    const int mode = ctx->opt.ks_wide == 2 || (ctx->opt.ks_wide < 0 && cnt * k > KS_DIGIT_MAX_BLOCKS && ctx->hc.logn < 14) ? 2 : 1;
     return (size_t)cnt * (mode == 2 ? k : tot_dig) * ctx->ctw2 * 8 > ctx->smax ? 0 : mode;
 }
 // perm_elt != 0 (two-launch variants only - the caller asks ks_planned_mode first): target / add0 are the c1 / c0 of the ciphertext a rotation
@@ -529,9 +516,9 @@ int do_keyswitch(cn_ctx *ctx, const uint64_t *target, size_t tstride, const uint
     KsArgs a{target, tstride, add0, add1, astride, key.d, out, cnt, galois, extra, xstride,
              key.f64 ? (bits >= 50 ? 1u : (1u << std::min(10, 50 - bits))) : 0xffffffffu,     // lazy FP64 accumulators: |term| <= 2.1 q, sum below 2^52
              0, out_tab};
-    if (ctx->ks_xcd == 1) a.xcd_cts = cnt & ~7u;
-    else if (ctx->ks_xcd == 2) a.xcd_cts = 0x80000000u;
-    const bool rr = !ctx->legacy_ntt && ctx->hc.logn >= 10 && ctx->hc.logn <= 14;                // register-radix kernels available
+    if (ctx->opt.ks_xcd == 1) a.xcd_cts = cnt & ~7u;
+    else if (ctx->opt.ks_xcd == 2) a.xcd_cts = 0x80000000u;
+    const bool rr = !ctx->opt.legacy_ntt && ctx->hc.logn >= 10 && ctx->hc.logn <= 14;                // register-radix kernels available
     a.mode = ks_planned_mode(ctx, cnt, galois);
     if (a.mode) CHECK(ensure_ks_part(ctx, (size_t)cnt * (a.mode == 2 ? k : tot_dig) * ctx->ctw2 * 8));
     a.perm_elt = perm_elt; a.items = items;
@@ -540,9 +527,9 @@ int do_keyswitch(cn_ctx *ctx, const uint64_t *target, size_t tstride, const uint
     if ((perm_elt || items || next_elt) && !a.mode && !(pair && !items)) return fail(CN_ERR_ARG, "internal: automorphism inside the fused key switch");
     if (pair) {                                                                                      // N = 16384: both 8192-point halves of a limb in one workgroup, one launch
         CHECK(ensure_ks_part(ctx, (size_t)cnt * ctx->ctw2 * 8));
-        a.xcd_cts = ctx->ks_xcd == 1 ? (cnt & ~7u) : 0u;
+        a.xcd_cts = ctx->opt.ks_xcd == 1 ? (cnt & ~7u) : 0u;
         ks_ops[bits <= 44 ? POL_F64L : POL_F64]->pair14(ctx, a);
-    } else if (a.mode == 0 && rr && key.f64 && ctx->hc.logn == 14 && ctx->hc.twdh && ctx->ks_split14) {   // ... as two workgroups per limb + a combining pass (rounds 1-4; A/B)
+    } else if (a.mode == 0 && rr && key.f64 && ctx->hc.logn == 14 && ctx->hc.twdh && ctx->opt.ks_split14) {   // ... as two workgroups per limb + a combining pass (rounds 1-4; A/B)
         CHECK(ensure_ks_part(ctx, (size_t)cnt * ctx->ctw2 * 8));
         ks_ops[bits <= 44 ? POL_F64L : POL_F64]->split14(ctx, a);
         hipLaunchKernelGGL(k_ks_combine14, dim3(cnt * 2 * k * (n / 512)), dim3(256), 0, ctx->stream, (const uint64_t *)ctx->ks_part, add0, add1, astride, out, ctx->dc,
@@ -576,7 +563,7 @@ int do_keyswitch(cn_ctx *ctx, const uint64_t *target, size_t tstride, const uint
     return 0;
 }
 bool ks_pair14_ok(cn_ctx *ctx, uint32_t cnt, int galois, const KsKey &key) {
-    return ctx->ks_pair14 && ctx->ks_split14 && !ctx->legacy_ntt && ctx->hc.logn == 14 && ctx->hc.twdh && key.f64 && ks_planned_mode(ctx, cnt, galois) == 0;
+    return ctx->opt.ks_pair14 && ctx->opt.ks_split14 && !ctx->opt.legacy_ntt && ctx->hc.logn == 14 && ctx->hc.twdh && key.f64 && ks_planned_mode(ctx, cnt, galois) == 0;
 }
 uint32_t chunk_for(cn_ctx *ctx, size_t per_ct, uint32_t count) {
     size_t c = std::max<size_t>(1, ctx->smax / per_ct);
@@ -644,7 +631,7 @@ int mul_relin_body(cn_ctx *ctx, cn_handle a, uint32_t ai, uint32_t astride, cn_h
         uint64_t *t3 = salloc<uint64_t>(ctx, (size_t)c * 3 * kn);
         auto mul = [&](uint32_t f, uint32_t n_) { return do_multiply(ctx, pa + (size_t)(s + f) * astride * A->item_words, astride, pb + (size_t)(s + f) * bstride * B->item_words, bstride, t3 + (size_t)f * 3 * kn, n_); };
         auto ksw = [&](uint32_t f, uint32_t n_) { uint64_t *t = t3 + (size_t)f * 3 * kn; return do_keyswitch(ctx, t + 2 * kn, 3 * kn, t, t + kn, 3 * kn, ctx->rlk, O->d + (oi + s + f) * O->item_words, n_, 0); };
-        if (ctx->sq_halves && !ctx->sq_overlap && ctx->hc.logn <= 13 && c >= SQ_HALVES_MIN && !ctx->capturing && pipeline_fused_ks(ctx, c) && aux_stream_ready(ctx)) {
+        if (ctx->opt.sq_halves && ctx->hc.logn <= 13 && c >= SQ_HALVES_MIN && !ctx->capturing && pipeline_fused_ks(ctx, c) && aux_stream_ready(ctx)) {
             CHECK(pipelined_halves(ctx, c, mul, ksw)); continue;
         }
         CHECK(mul(0, c));
@@ -683,7 +670,7 @@ int do_galois(cn_ctx *ctx, const uint64_t *in, uint64_t elt, uint64_t *out, uint
     }
     if (pre || next_elt) return fail(CN_ERR_ARG, "internal: rotation chain outside the one-launch key switch");
     // small batches (two-launch key switch): no permutation pass - the key-switch kernels apply the automorphism while they load c1 and c0
-    if (!shifted && ctx->ks_perm_fused && ks_planned_mode(ctx, count, 1) != 0) {
+    if (!shifted && ctx->opt.ks_perm_fused && ks_planned_mode(ctx, count, 1) != 0) {
         CHECK(do_keyswitch(ctx, in + kn, 2 * kn, in, nullptr, 2 * kn, it->second, out, count, 1, acc, ctx->ctw2, nullptr, (uint32_t)elt));
         ctx->st.Rotation += count;
         if (acc) ctx->st.Addition += count;
@@ -784,8 +771,8 @@ int rotate_jobs(cn_ctx *ctx, std::vector<RotJob> &jobs) {
     for (RotJob &j : jobs) { CHECK(rotation_hops(ctx, j.steps, j.elts)); rounds = std::max(rounds, j.elts.size()); }
     bool aliased = false;
     for (uint32_t a = 0; a < n && !aliased; a++) for (uint32_t b = 0; b < n; b++) if (a != b && (jobs[a].dst == jobs[b].src || jobs[a].dst == jobs[b].dst)) { aliased = true; break; }
-    bool tables_ok = ctx->ks_perm_fused && !aliased && ks_planned_mode(ctx, n, 1) != 0;
-    if (!tables_ok && !aliased && ctx->ks_perm_fused && n > 1) {
+    bool tables_ok = ctx->opt.ks_perm_fused && !aliased && ks_planned_mode(ctx, n, 1) != 0;
+    if (!tables_ok && !aliased && ctx->opt.ks_perm_fused && n > 1) {
         // More rotations than ONE table-driven two-launch key switch takes (LoLa-CIFAR's ConvertToColumnVector: 83 maps at N = 16384 - 664 (ciphertext, limb)
         // blocks against the 160 up to which a key switch runs as two launches): pieces of the largest size that does, each a launch chain of its own, instead
         // of 83 x ~4 single-ciphertext rotations of two launches each (round 5: 632 -> ~40 launches per plaintext prime and image).  Independent jobs: any order.
@@ -934,7 +921,7 @@ API_END }
 std::vector<uint64_t> sum_slots_chain_elts(cn_ctx *ctx, uint32_t count, uint32_t length) {
     const uint32_t n = ctx->hc.n, half = n / 2;
     std::vector<uint64_t> elts;
-    bool ok = ctx->ks_chain && count > 0;
+    bool ok = ctx->opt.ks_chain && count > 0;
     uint32_t l2 = length ? length : n;
     if (l2 >= half) { elts.push_back(2ull * n - 1); l2 = half; }
     for (uint32_t steps = 1; steps < l2 && ok; steps *= 2) { if (has_direct_key(ctx, -(int)steps)) elts.push_back(cn_galois_elt_from_step(ctx, -(int)steps)); else ok = false; }

@@ -55,11 +55,11 @@ template <int L> static void l_square_fused(cn_ctx *c, const uint64_t *A, size_t
         if constexpr (L <= 13) {
             // pipelined resident kernel (k_square_pipe): one workgroup per CU and modulus for the whole launch; pays once a workgroup squares several blocks
             const uint32_t per_limb = std::min<uint32_t>((uint32_t)std::max(1, c->cus) / Lm, cnt);
-            if (per_limb >= 1 && (c->sq_pipe == 2 || (c->sq_pipe && cnt >= 4 * per_limb))) {
+            if (per_limb >= 1 && (c->opt.sq_pipe == 2 || (c->opt.sq_pipe && cnt >= 4 * per_limb))) {
                 hipLaunchKernelGGL((k_square_pipe<L, AR>), dim3(per_limb * Lm), dim3(NttPlan<L>::NT), lds + ((size_t)8 << L), c->stream, A, astride, atab, D, c->dc, base_off, Lm, cnt);
                 return;
             }
-            if (c->sq_lds) {             // NTT-form operand parked in LDS (one workgroup per CU) instead of in the outputs' place (two)
+            if (c->opt.sq_lds) {             // NTT-form operand parked in LDS (one workgroup per CU) instead of in the outputs' place (two)
                 hipLaunchKernelGGL((k_square_fused<L, AR, true>), dim3(cnt * Lm), dim3(NttPlan<L>::NT), lds + ((size_t)8 << L), c->stream, A, astride, atab, D, c->dc, base_off, Lm);
                 return;
             }
@@ -107,7 +107,7 @@ static bool enc_tail(cn_ctx *, const uint64_t *, const uint64_t *, uint32_t, uin
 // Encryptor.Encrypt behind the samplers as ONE kernel (N <= 8192; N = 16384 keeps the three-launch chain: 1024-thread workgroups have 128 VGPRs per thread)
 template <int L> static void l_enc_fused(cn_ctx *c, const int8_t *us, const uint64_t *pt, uint32_t pts, uint64_t *out, uint32_t cnt, const int8_t *noise, const void *tab) {
     if constexpr (L <= 13) {
-        if (c->enc_fused == 2 && kF64)               // (the integer policy spills 17-21 registers at 128: it keeps the one-block form)
+        if (c->opt.enc_fused == 2 && kF64)               // (the integer policy spills 17-21 registers at 128: it keeps the one-block form)
             hipLaunchKernelGGL((k_encrypt_split<L, AR>), dim3(cnt * 2 * c->hc.k), dim3(NttPlan<L>::NT), (size_t)ntt_lds_words(1u << L) * 8, c->stream, us, c->pk, pt, pts, out, c->dc,
                                noise, (const EncTab *)tab);
         else

@@ -28,12 +28,7 @@ static int slice_ks_key(cn_ctx *child, const cn_ctx *parent, const KsKey &from, 
 }
 static int adopt_from_parent(cn_ctx *c, cn_ctx *parent) {
     const uint32_t k = c->hc.k;
-    c->use_f64 = parent->use_f64; c->legacy_ntt = parent->legacy_ntt; c->ks_tight = parent->ks_tight; c->gemm_order = parent->gemm_order;
-    c->ks_perm_fused = parent->ks_perm_fused; c->ks_xcd = parent->ks_xcd; c->sq_fused = parent->sq_fused; c->sq_lds = parent->sq_lds;
-    c->sq_pipe = parent->sq_pipe; c->sq_overlap = parent->sq_overlap; c->sq_halves = parent->sq_halves; c->defer_stagger = parent->defer_stagger;
-    c->enc_fused = parent->enc_fused; c->fold_zero = parent->fold_zero; c->gemm_mfma = parent->gemm_mfma; c->gemm_pair = parent->gemm_pair;
-    c->mp_fused = parent->mp_fused; c->ks_wide = parent->ks_wide; c->ks_split14 = parent->ks_split14; c->ks_pair14 = parent->ks_pair14;
-    c->ks_chain = parent->ks_chain; c->mp_bcast = parent->mp_bcast;
+    c->opt = parent->opt;
     memcpy(c->rng_key, parent->rng_key, sizeof c->rng_key);
     c->hc.ks_xi = parent->hc.ks_xi;
     for (uint32_t l = 0; l < k; l++) c->hc.ks_inv_qhat_q[l] = parent->hc.ks_inv_qhat_q[l];

@@ -121,10 +121,41 @@ struct CnGuard {
     CnGuard &operator=(const CnGuard &) = delete;
 };
 
+// Per-context tuning switches, all producing the same words.  Names, ranges and environment overrides: the option table of cn_api.hip
+// (cn_set_option / cn_get_option, include/cnhip.h); a level context copies them from its parent whole.  Booleans are 0 / 1.
+// Switches removed after their variants measured no gain: staggered squaring groups in the flush (profiles/r06_stagger_ab.txt), the q side of a batched squaring on the
+// second stream (profiles/r06_square_overlap.txt), the 128-VGPR fused key switch (profiles/HISTORY.md, round 1).
+struct CnTunables {
+    int f64 = 1;              // transforms of moduli < 2^49 and key switching in exact FP64; 0 (CN_NO_F64=1): integer (Shoup) transforms everywhere
+    int legacy_ntt = 0;       // 1: radix-2 LDS kernels (the only ones below N = 1024)
+    int gemm_order = 1;       // scalar GEMM (VALU kernels): 1 = slice-major workgroup order (every input slice fetched once per XCD), 0 = group-major
+    int ks_perm_fused = 1;    // rotations through the two-launch key switch apply the automorphism while loading (no k_galois_lds pass)
+    int ks_xcd = 0;           // fused key switch, workgroup order: 0 (ciphertext, limb); 1 the k workgroups of a ciphertext on one XCD (share its source limbs in
+                              // that L2); 2 limb-major (one key slice per XCD L2 at a time).  Default by N (ctx_init)
+    int sq_fused = 1;         // squarings: forward transforms + tensor + inverse transforms in one kernel; 0 = separate launches
+    int sq_lds = 1;           // fused squaring with the NTT-form operand parked in LDS (N <= 8192) - HBM traffic = the algorithmic 2 reads + 3 writes per
+                              // block (profiles/r02_pmc_square_gemm.txt); 0: parked in the outputs' place (two workgroups per CU)
+    int sq_pipe = 1;          // 1: fused squaring of a batch (>= 4 blocks per resident workgroup) on the pipelined resident kernel k_square_pipe; 0: k_square_fused; 2: k_square_pipe for any count (tests)
+    int sq_halves = 1;        // Multiply + Relinearize of >= 512 ciphertexts (N <= 8192) in parts software-pipelined over the context's two streams (pipelined_halves,
+                              // cn_api_shared.h).  1: the batched entry point cn_mul_relin; 2: also the queued per-ciphertext calls of a flush (measured slower there); 0: off
+    int enc_fused = 2;        // 2: a block per (ciphertext, component, limb) - k_encrypt_split, two workgroups per CU: 420 against 542 us per 784 ciphertexts; 1: one block per
+                              // (ciphertext, limb) behind the samplers (k_encrypt_fused, N <= 8192); 0: expand + batched transform + k_encrypt_tail
+    int fold_zero = 1;        // queued fresh encryptions of zero whose only reader is a queued scalar product and which have been released: folded by linearity (k_encrypt_fold); 0: materialised
+    int gemm_mfma = 1;        // scalar GEMMs with >= 16 outputs per gather list on the int8 matrix cores (exact); 0: FP64 kernel
+    int gemm_pair = 1;        // planned scalar GEMMs: gather lists that share at least half of their inputs are merged in pairs (pair_gather_lists); 0: the caller's lists
+    int mp_fused = 1;         // dense MultiplyPlain as k_lift_ntt + k_mul_plain_fused; 0 = the six separate launches
+    int ks_wide = -1;         // -1 auto (small batches), 0 fused kernel, 1 two-launch with a workgroup per digit, 2 two-launch per source limb
+    int ks_split14 = 1;       // N = 16384: key switch as two 8192-point halves per limb (no register spills); 0 = fused 1024-thread kernel
+    int ks_pair14 = 1;        // ... both halves in ONE launch per rotation (k_keyswitch_pair14); 0 = k_keyswitch_split14 + k_ks_combine14 (+ k_galois_lds)
+    int ks_chain = 1;         // SumAllSlots at N = 16384: every link of the rotate-and-add chain hands sigma_next(c1) to the next one (no permutation pass between links)
+    int mp_bcast = 1;         // one ciphertext x many plaintexts (row-dot batches) as ONE launch that transforms the plaintexts (k_mul_plain_bcast); 0: k_lift_ntt + k_mul_plain_fused
+};
+
 struct DeferQueue;            // cn_api_shared.h / cn_defer.hip
 struct cn_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
+    CnTunables opt;
     DevConsts hc;             // host copy
     DevConsts *dc = nullptr;  // device copy
     uint64_t *tw = nullptr;
@@ -132,7 +163,6 @@ struct cn_ctx {
     HandleTable bufs;
     KsKey rlk{nullptr, false, false};
     double *twd = nullptr, *twdh = nullptr;
-    bool use_f64 = true;      // CN_NO_F64=1 / cn_set_option("f64",0): integer (Shoup) transforms everywhere
     std::map<uint64_t, KsKey> gk;
     uint64_t *sk = nullptr, *pk = nullptr;   // client-side keys (NTT form) when the data owner's GPU runs keygen/encrypt/decrypt
     uint64_t rng_item = 0;                    // running polynomial counter of the sampler (part of the ChaCha20 block counter)
@@ -146,51 +176,26 @@ struct cn_ctx {
     std::vector<uint32_t> index_map;   // BatchEncoder slot -> coefficient position
     uint32_t *d_index_map = nullptr;   // the same table in HBM (cn_encode_batch / cn_decode_batch)
     size_t ctw2;              // words of a size-2 ciphertext
-    bool legacy_ntt = false;  // CN_LEGACY_NTT=1: radix-2 LDS kernels (A/B reference)
     // freed ciphertext / plaintext arrays are kept per size and handed out again: every op of a context is ordered on its
     // stream, so reuse needs no synchronisation, while hipFree / hipMalloc cost ~60 / ~25 us and a device-wide sync each
     // (a LoLa inference allocates and frees ~300 temporaries per plaintext prime)
     std::unordered_map<size_t, std::vector<uint64_t *>> pool;
     size_t pool_bytes = 0, pool_max;
     void *slabs = nullptr;                // std::vector<Slab>*: small arrays are carved out of slabs (one hipMalloc per <= 64 arrays), cn_api.hip
-    bool ks_split14 = true;   // N = 16384: key switch as two 8192-point halves per limb (no register spills); 0 = fused 1024-thread kernel
-    bool ks_pair14 = true;    // ... both halves in ONE launch per rotation (k_keyswitch_pair14, round 5); 0 = k_keyswitch_split14 + k_ks_combine14 (+ k_galois_lds)
-    bool ks_chain = true;     // SumAllSlots at N = 16384: every link of the rotate-and-add chain hands sigma_next(c1) to the next one (no permutation pass between links)
-    int ks_wide = -1;         // -1 auto (small batches), 0 fused kernel, 1 two-launch with a workgroup per digit, 2 two-launch per source limb
-    void *ks_part = nullptr; size_t ks_part_cap = 0;   // its partial products [ct][digit][2][k][N]
+    void *ks_part = nullptr; size_t ks_part_cap = 0;   // partial products of the two-launch key switch [ct][digit][2][k][N]
     char *pin = nullptr, *pin_dev = nullptr; size_t pin_off = 0; uint32_t pin_laps = 0;           // ring of pinned host memory for the small table uploads (cn_api.hip: pin_block)
     char *stage = nullptr; size_t stage_cap = 0;       // staging arena of the deferred per-ciphertext rotations / plaintext products (gather, batched call, scatter)
-    int ks_xcd = 0;           // cn_set_option("ks_xcd", v) / CN_KS_XCD=v: fused key switch, workgroup order: 0 (ciphertext, limb); 1 the k workgroups of a
-    int gemm_order = 1;                          // scalar GEMM (VALU kernels): 1 = slice-major workgroup order (every input slice fetched once per XCD), 0 = group-major
-    bool ks_perm_fused = true;                    // rotations through the two-launch key switch apply the automorphism while loading (no k_galois_lds pass)
     int stream_tries = 0;                        // streams created until one had a hardware queue of its own (cn_api.hip: pick_stream)
     std::atomic<int> probe_pins{0};              // > 0: a cn_ctx_create on this device is measuring this context's stream; cn_ctx_destroy waits
-                              // ciphertext on one XCD (share its source limbs in that L2); 2 limb-major (one key slice per XCD L2 at a time)
-    bool ks_tight = false;    // CN_KS_TIGHT=1: 128-VGPR key-switch variant (2 workgroups per CU, accumulators spill to scratch)
     std::atomic<bool> capturing{false};   // between cn_graph_begin and cn_graph_end: work is recorded on the stream, nothing that synchronises or allocates may run
     std::vector<std::unique_ptr<char[]>> cap_staged;                 // host blocks of the upload nodes recorded so far
     std::vector<std::pair<uint64_t *, size_t>> cap_allocs;           // arrays handed out while recording
     int graphs_alive = 0;     // graphs carry the addresses of the scratch arenas: those must not move while one exists
-    bool mp_fused = true;     // dense MultiplyPlain as k_lift_ntt + k_mul_plain_fused; cn_set_option("mp_fused", 0) = the six separate launches
-    bool mp_bcast = true;     // ... one ciphertext x many plaintexts (row-dot batches) as ONE launch that transforms the plaintexts (k_mul_plain_bcast, round 5); 0: the two launches above
-    bool gemm_pair = true;    // planned scalar GEMMs: gather lists that share at least half of their inputs are merged in pairs (pair_gather_lists); cn_set_option("gemm_pair", 0): the caller's lists
-    bool gemm_mfma = true;    // scalar GEMMs with >= 16 outputs per gather list on the int8 matrix cores (exact); cn_set_option("gemm_mfma", 0): FP64 kernel
     int cus = 0;              // compute units of the device
-    bool sq_lds = true;       // fused squaring with the NTT-form operand parked in LDS (N <= 8192) - HBM traffic = the algorithmic 2 reads + 3 writes per
-                              // block (profiles/r02_pmc_square_gemm.txt); cn_set_option("sq_lds", 0): parked in the outputs' place (two workgroups per CU)
     uint64_t folded_zero = 0;  // zero encryptions folded so far
     uint64_t mr_pipelined = 0; // cn_mul_relin chunks and flushed Multiply + Relinearize groups that ran through pipelined_halves
-    bool fold_zero = true;    // queued fresh encryptions of zero whose only reader is a queued scalar product and which have been released: folded by linearity (k_encrypt_fold, round 6); cn_set_option("fold_zero", 0): materialised
-    int enc_fused = 2;        // 2 (default, round 6): a block per (ciphertext, component, limb) - k_encrypt_split, two workgroups per CU: 420 against 542 us per 784 ciphertexts; 1: Encryptor.Encrypt behind the samplers as one kernel (k_encrypt_fused, N <= 8192); cn_set_option("enc_fused", 0): expand + batched transform + k_encrypt_tail
-    int sq_pipe = 1;          // 1: fused squaring of a batch (>= 4 blocks per resident workgroup) on the pipelined resident kernel k_square_pipe; 0: k_square_fused; 2: k_square_pipe for any count (tests)
     uint64_t uid = 0;         // creation order within the process (cn_ctx_create)
-    bool defer_stagger = false; hipEvent_t ev_front = nullptr;   // deferred flush of a big Multiply + Relinearize group: its Multiply waits for the front of the context that flushed one last
-                                                                // on this device (cn_defer.hip: staggered plaintext-prime channels); three forms measured, none with a gain - OFF by default: cn_set_option("defer_stagger", 1) / CN_DEFER_STAGGER=1
-    int sq_halves = 1;        // Multiply + Relinearize of >= 512 ciphertexts (N <= 8192) as two halves software-pipelined over the context's two streams: the Multiply of the second half beside the key
-                              // switch of the first (pipelined_halves, cn_api_shared.h).  1 (default): the batched entry point cn_mul_relin; 2: also the queued per-ciphertext calls of a flush (measured slower there); 0: off
-    bool sq_overlap = false;  // squaring of a batch: the q-side transform kernel on a second stream beside [k_behz_extend -> Bsk side] (cn_eval.hip: do_multiply); CN_SQ_OVERLAP / cn_set_option
-    hipStream_t stream2 = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr; bool stream2_failed = false;
-    bool sq_fused = true;     // squarings: forward transforms + tensor + inverse transforms in one kernel; cn_set_option("sq_fused", 0) = separate launches
+    hipStream_t stream2 = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr; bool stream2_failed = false;   // second stream of pipelined_halves (aux_stream_ready)
     // deferred submission (cn_set_option("defer", 1)): per-ciphertext calls are queued and flushed as batched launches; 2: ... and submitted without the
     // context lock through `ring` (cn_submit.h), executed by whoever drains it
     std::atomic<int> defer{0};

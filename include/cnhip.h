@@ -79,24 +79,58 @@ int cn_ctx_create_level(cn_ctx *parent, uint32_t limbs, cn_ctx **out);
  * the context checks (chain, capture) refuse before anything is submitted.  Ordering without a host wait (events): the switch reads `in` after the work submitted to src before the call, writes `out` after
  * the work submitted to dst before it; later dst calls see the result, later src calls wait for the read. */
 int cn_mod_switch(cn_ctx *src, cn_handle in, uint32_t ii, uint32_t count, cn_ctx *dst, cn_handle out, uint32_t oi);
-/* tuning switches (A/B testing): "f64" = 1 (default) runs transforms of moduli < 2^49 and key switching in exact FP64
- * (set BEFORE uploading keys), 0 = integer Shoup path everywhere; "legacy_ntt" = 1 selects the radix-2 LDS kernels;
- * "ks_wide" = -1 (default: automatic by batch size) / 0 fused one-launch kernel / 1 two launches with one workgroup per digit
- * (1-2 ciphertexts; 1-6 until round 3) / 2 two launches with one workgroup per source limb (3-32 ciphertexts);
- * "ks_tight" = 1 the 128-VGPR fused variant; "ks_split14" = 1 (default) runs the N = 16384 key switch as two 8192-point
- * halves per limb (no register spills), 0 = the fused 1024-thread kernel; "sq_fused" = 1 (default) runs the transforms and the tensor
- * of a squaring (Multiply(a, a): SquareActivation) as one kernel per base, 0 = separate launches; "mp_fused" = 1 (default) runs a dense
- * MultiplyPlain as two launches (lift + transform of the plaintexts; transform, product, inverse transform of the ciphertext limbs),
- * 0 = six; "sq_lds" = 1 (default) parks the NTT-form operand of a fused squaring in LDS (N <= 8192), 0 = in the outputs' place; "sq_pipe" = 1 (default) runs the fused squaring of a batch on the
- * pipelined resident kernel (k_square_pipe: one workgroup per CU and modulus, inverse root table in LDS, next operand prefetched), 0 = k_square_fused; "enc_fused" = 2 (default, round 6) runs Encryptor.Encrypt behind the samplers as ONE kernel with a block per (ciphertext, component, limb) (N <= 8192,
- * FP64 policies: two workgroups per CU), 1 = a block per (ciphertext, limb) (the ternary u goes from the sampler's int8 polynomial through one transform and stays in registers
- * for both components), 0 = expansion + batched transform + tail kernel;
- * "gemm_mfma" = 1 (default) runs wide scalar GEMMs (cn_scalar_gemm / cn_scalar_dot batches with >= 16 outputs) on the int8 matrix
- * cores; "gemm_pair" = 1 (default) lets cn_scalar_gemm / cn_gemm_plan_create merge gather lists that share at least half of their inputs in pairs
- * (small signed weights, lists of <= 64 entries and <= 5 outputs: the windows of a convolution - every shared input then travels to a CU once, not twice),
- * 0 = the caller's lists as they are (environment: CN_GEMM_PAIR; CN_GEMM_ONE_LIMB=0 keeps the small-weight kernel on its two-limb form).
- * All variants produce identical words. */
-/* "defer" = 1: DEFERRED SUBMISSION for callers that issue one evaluator call per ciphertext from many threads - the unchanged
+/* Options of a context.  The tuning switches (A/B testing) all produce identical words.  cn_set_option refuses an unknown name, and a value
+ * outside the range of an enumerated switch, with CN_ERR_ARG and keeps the old value; a flag takes any value, non-zero = on.  An environment
+ * override is read when the context is created (a value out of range is clamped).  A level context takes its parent's values.
+ *
+ *   name             values  default               environment      what it selects
+ *   "f64"            flag    1                     CN_NO_F64=1: 0   transforms of moduli < 2^49 and key switching in exact FP64; 0 = the integer
+ *                                                                   Shoup path everywhere.  Set it BEFORE uploading keys
+ *   "legacy_ntt"     flag    0                     CN_LEGACY_NTT    the radix-2 LDS kernels (the only ones below N = 1024)
+ *   "gemm_order"     0..1    1                     CN_GEMM_ORDER    VALU scalar GEMM: 1 slice-major workgroup order (every input slice fetched once
+ *                                                                   per XCD), 0 group-major
+ *   "ks_perm_fused"  flag    1                     -                a rotation of a small batch (two-launch key switch) has no permutation pass: the
+ *                                                                   key-switch kernels apply the automorphism while they load c1 and c0; 0 = k_galois_lds
+ *   "ks_xcd"         0..2    2 (N <= 8192),        CN_KS_XCD        workgroup order of the fused key switch: 0 (ciphertext, limb), 1 the limbs of a
+ *                            1 (N = 16384)                          ciphertext on one XCD, 2 limb-major (one key slice per XCD L2 at a time)
+ *   "sq_fused"       flag    1                     CN_SQ_FUSED      transforms and tensor of a squaring (Multiply(a, a): SquareActivation) as one kernel
+ *                                                                   per base; 0 = separate launches
+ *   "sq_lds"         flag    1                     CN_SQ_LDS        the NTT-form operand of a fused squaring parked in LDS (N <= 8192); 0 = in the
+ *                                                                   outputs' place
+ *   "sq_pipe"        0..2    1                     CN_SQ_PIPE       1: the fused squaring of a batch on the pipelined resident kernel k_square_pipe (one
+ *                                                                   workgroup per CU and modulus, next operand prefetched); 0 k_square_fused; 2
+ *                                                                   k_square_pipe for any count
+ *   "sq_halves"      0..2    1                     CN_SQ_HALVES     Multiply + Relinearize of a batch pipelined in parts over two streams (below):
+ *                                                                   1 cn_mul_relin, 2 also the flush of queued calls (measured slower there), 0 off
+ *   "enc_fused"      0..2    2                     CN_ENC_FUSED     Encryptor.Encrypt behind the samplers: 2 one kernel with a block per (ciphertext,
+ *                                                                   component, limb) (N <= 8192, FP64 policies); 1 a block per (ciphertext, limb), u in
+ *                                                                   registers for both components; 0 expansion + batched transform + tail kernel
+ *   "fold_zero"      flag    1                     CN_FOLD_ZERO     queued zero encryptions folded into the scalar product that reads them (below)
+ *   "gemm_mfma"      flag    1                     CN_GEMM_MFMA     wide scalar GEMMs (>= 16 outputs per gather list) on the int8 matrix cores; 0 = the
+ *                                                                   FP64 kernel.  Affects GEMMs planned after the call
+ *   "gemm_pair"      flag    1                     CN_GEMM_PAIR     cn_scalar_gemm / cn_gemm_plan_create merge gather lists that share at least half of
+ *                                                                   their inputs in pairs (small signed weights, lists of <= 64 entries and <= 5
+ *                                                                   outputs); 0 = the caller's lists.  Affects GEMMs planned after the call
+ *   "mp_fused"       flag    1                     CN_MP_FUSED      a dense MultiplyPlain as two launches (lift + transform of the plaintexts; transform,
+ *                                                                   product, inverse transform of the ciphertext limbs); 0 = six
+ *   "ks_wide"        -1..2   -1                    -                -1 automatic by batch size, 0 the fused one-launch kernel, 1 two launches with a
+ *                                                                   workgroup per digit, 2 two launches with a workgroup per source limb
+ *   "ks_split14"     flag    1                     -                N = 16384: the key switch as two 8192-point halves per limb (no register spills);
+ *                                                                   0 = the fused 1024-thread kernel
+ *   "ks_pair14"      flag    1                     CN_KS_PAIR14     N = 16384, batches: both halves of a limb in ONE launch, a rotation's c1 permuted
+ *                                                                   once per ciphertext and its c0 inside the kernel; 0 = permutation pass, two
+ *                                                                   workgroups per limb, combining pass
+ *   "ks_chain"       flag    1                     CN_KS_CHAIN      every link of a cn_sum_slots / cn_rowdot_batch rotate-and-add chain leaves the next
+ *                                                                   link's permuted c1 beside its result (no permutation pass between links)
+ *   "mp_bcast"       flag    1                     -                cn_rowdot_batch transforms its ONE ciphertext once and the row plaintexts inside the
+ *                                                                   product kernel; 0 = k_lift_ntt + k_mul_plain_fused
+ *   "defer"          0..2    0                     -                deferred submission of per-ciphertext calls (below)
+ *   "ks_xi"          flag    0                     -                decomposition convention of the key switch (below)
+ *
+ * Removed after their variants measured no gain: staggered squaring groups in the flush (profiles/r06_stagger_ab.txt), the q side of a batched
+ * squaring on a second stream (profiles/r06_square_overlap.txt), the 128-VGPR fused key switch (profiles/HISTORY.md, round 1).
+ *
+ * "defer" = 1: DEFERRED SUBMISSION for callers that issue one evaluator call per ciphertext from many threads - the unchanged
  * NeuralNetworks layers of the reference (PoolLayer.cs:67-80,113-121,182,214; EncryptedSealBfvMatrix.cs:79-120,140-154; LLInterleaveLayer.cs;
  * Utils.cs:46-88).  cn_scalar_dot, cn_add, cn_sub, cn_add_plain, cn_mul_relin, cn_encrypt and - on up to 4 ciphertexts per call - cn_mul_plain,
  * cn_rotate_rows(_add), cn_rotate_columns(_add), cn_sum_slots, cn_copy are then queued with their operand addresses, ordered by data dependence,
@@ -105,7 +139,7 @@ int cn_mod_switch(cn_ctx *src, cn_handle in, uint32_t ii, uint32_t count, cn_ctx
  * (cn_sync, downloads, ...) needs the results.  Same words as immediate calls; argument errors (ranges, zero plaintexts, missing Galois keys) are
  * reported by the call that made them, device errors by the call that triggered the flush.  cn_free of a handle with pending readers is safe
  * (the array returns to the pool after the flush).
- * "defer" = 2 (round 6): the same queue, fed WITHOUT THE CONTEXT LOCK.  cn_scalar_dot, cn_add, cn_sub, cn_add_plain, cn_mul_relin (up to 4 ciphertexts per
+ * "defer" = 2: the same queue, fed WITHOUT THE CONTEXT LOCK.  cn_scalar_dot, cn_add, cn_sub, cn_add_plain, cn_mul_relin (up to 4 ciphertexts per
  * call), cn_encrypt (up to 4), cn_encrypt_zero_new, cn_free, cn_free_many and cn_ct_alloc(1, 2) do not take the lock: a call claims the next slot of a
  * multi-producer ring with one atomic add, writes a 64-byte record (handles and indices as passed) and returns 0; whoever finds the lock free executes
  * the published records in claim order - a total order consistent with happens-before between the caller's threads, which is what the dependence
@@ -114,51 +148,44 @@ int cn_mod_switch(cn_ctx *src, cn_handle in, uint32_t ii, uint32_t count, cn_ctx
  * an error is reported ONCE by the next call that synchronises with the context (cn_sync, downloads, cn_stats_get, any non-deferrable entry point:
  * "a call submitted without the lock (defer = 2) failed ..."), the calls around it are executed.  For callers that come from Defaults.ThreadCount =
  * Environment.ProcessorCount threads (HE Wrapper/Defaults.cs:11-15, Utils.cs:46-88): the unchanged CryptoNets layers run at the same rate from 4, 16 and
- * 256 threads.  cn_live_handles does not count the ready handles; "ready_handles" reads their number; "pin_laps" the laps of the context's pinned
- * upload ring (small tables of a flush; 32 MiB, CN_PIN_RING_MIB in the environment; a lap waits for the stream once).
- * "fold_zero" = 1 (default, round 6): a queued fresh encryption of zero (cn_encrypt with pt = 0 / cn_encrypt_zero_new) that only feeds ONE queued scalar
+ * 256 threads.  cn_live_handles does not count the ready handles.
+ * "fold_zero" = 1: a queued fresh encryption of zero (cn_encrypt with pt = 0 / cn_encrypt_zero_new) that only feeds ONE queued scalar
  * product and has been released by the caller (PoolLayer.ElementAt / ReleaseTemp, PoolLayer.cs:67-90) is not materialised: sum_t w_t Enc_t(0) is
  * added onto the scalar product's output by linearity - exact modular arithmetic on the same sampler draws (nonce, item), the SAME words as with
- * "fold_zero" = 0, a fifth of the transforms.  All or nothing per flush (every queued zero encryption must qualify).  "folded_zero_encryptions" reads the count.
- * "defer_stagger" = 0 (default; 1: the Multiply of a queued squaring group of >= 256 ciphertexts waits on the device for the Multiply of an older context of the same device -
- * measured without a gain, profiles/r06_stagger_ab.txt).
- * "sq_halves" = 1 (default, round 6; 0 off; 2: also inside the flush of queued per-ciphertext calls - measured slower there): cn_mul_relin of >= 512 ciphertexts at
- * N <= 8192 runs as two halves software-pipelined over two streams of the context - the Multiply of the second half beside the key switch of the first (its HBM-bound base
- * extension / floor fill what the FP64-bound key switch leaves).  Same words; every later call on the context is ordered behind both halves.  A caller that issues its plaintext
- * primes one after the other (or from parallel tasks) gets what bench.py's half-batch stagger of the primes gets (12.6 -> 12.0 ms per CryptoNets batch); a staggered caller nothing.
- * A batch runs in parts only if every part takes the fused key switch.  With "ks_wide" 1 or 2, or in automatic mode when a part has at most 160 (ciphertext, limb)
- * blocks, it runs on one stream: the two-launch key switch keeps its partial products in one arena per context.  "mul_relin_pipelined" counts the batches run in parts.
- * "sq_overlap" = 0 (default; 1: the q-side transform kernel of a batched squaring on a second stream beside the base extension - measured slower in
- * the two-context batch, profiles/r06_square_overlap.txt).
- * "gemm_order" = 1 (default): slice-major workgroup order of the VALU scalar GEMM (every input slice fetched once per XCD), 0 = group-major.
- * "ks_perm_fused" = 1 (default): a rotation of a small batch (two-launch key switch) has no permutation pass - the key-switch kernels apply the
- * automorphism while they load c1 and c0; 0 = k_galois_lds in front of them.  "stream_tries" (read only): streams cn_ctx_create tried until one had a
- * hardware queue of its own (< 0: none had; CN_STREAM_PROBE=0 takes the first).
- * Environment switches read once per process (A/B measurements, all default to the measured best): CN_STREAM_PROBE=0 (no hardware-queue selection),
- * CN_TABLES_ZERO_COPY=0 (small operand tables are copied to the device instead of read from the pinned ring), CN_KS_WIDE_MAX / CN_KS_DIGIT_MAX ((ciphertext,
- * limb) blocks up to which a key switch runs as two launches: 160 / with one workgroup per digit: 10), CN_GEMM_ORDER, CN_DEFER_TRACE=1 (one stderr line
- * per flushed queue level: calls per kind, launches).
- * "ks_xcd": workgroup order of the fused key switch - 0 (ciphertext, limb), 1 the limbs of a ciphertext on one XCD (default at N = 16384), 2 limb-major
- * (default up to N = 8192: one key slice per XCD L2 at a time).
- * N = 16384, batches (round 5): "ks_pair14" = 1 (default) runs a key switch as ONE launch - both 8192-point halves of a limb in one workgroup, the last
- * inverse stage and the addends applied on the way out, a rotation's c1 permuted once per ciphertext and its c0 inside the kernel; 0 = the three launches of
- * rounds 1-4 (permutation pass, two workgroups per limb, combining pass).  "ks_chain" = 1 (default): every link of a cn_sum_slots / cn_rowdot_batch
- * rotate-and-add chain leaves the NEXT link's permuted c1 beside its result (no permutation pass between links).  "mp_bcast" = 1 (default): cn_rowdot_batch
- * transforms its ONE ciphertext once and the row plaintexts inside the product kernel (one launch); 0 = k_lift_ntt + k_mul_plain_fused.  Environment:
- * CN_KS_PAIR14, CN_KS_CHAIN (the same switches for a whole process), CN_DEFER_MERGE_GEMM=0 (deferred scalar products of one flush keep their levels:
- * one launch per level instead of one per term count).  Environment: CN_LOCK_GRACE_NS / CN_LOCK_COMBINE switch the two context-lock experiments that
- * are kept but off (cn_host.cpp).
+ * "fold_zero" = 0, a fifth of the transforms.  All or nothing per flush (every queued zero encryption must qualify).
+ * "sq_halves": cn_mul_relin of >= 512 ciphertexts at N <= 8192 runs in parts software-pipelined over two streams of the context - the Multiply of a part
+ * beside the key switch of the part before (its HBM-bound base extension / floor fill what the FP64-bound key switch leaves).  Same words; every later call
+ * on the context is ordered behind all parts.  A caller that issues its plaintext primes one after the other (or from parallel tasks) gets what bench.py's
+ * half-batch stagger of the primes gets (12.6 -> 12.0 ms per CryptoNets batch); a staggered caller nothing.  A batch runs in parts only if every part takes
+ * the fused key switch.  With "ks_wide" 1 or 2, or in automatic mode when a part has at most 160 (ciphertext, limb) blocks, it runs on one stream: the
+ * two-launch key switch keeps its partial products in one arena per context.
  * "ks_xi": DECOMPOSITION CONVENTION of the key switch (relinearisation and rotations).  0 (default): base-2^dbc digits of the raw residue c_l of every
  * source limb l; key (l, d) = (-(a s + e) + 2^(dbc d) s' [in limb l only], a) - SURVEY 9.5, the form in which the CRT basis element
  * (q/q_l) [(q/q_l)^-1]_{q_l} is folded into the key.  1: digits of xi_l = [c_l (q/q_l)^-1]_{q_l}; key (l, d) = (-(a s + e) + (q/q_l) 2^(dbc d) s' [in every
  * limb], a) - the xi_q decomposition as the BEHZ paper writes it.  Both are exact key switches and decrypt identically with their own keys; keys of
  * one convention give garbage under the other.  Set it BEFORE cn_keygen / the key uploads; the start-up self-test of the host mirrors
- * (hewrapper.AtomicSealBfvEncryptedEnvironment.SelfTest, the C# twin's SelfTest) picks the one the client's evaluator obeys. */
+ * (hewrapper.AtomicSealBfvEncryptedEnvironment.SelfTest, the C# twin's SelfTest) picks the one the client's evaluator obeys.
+ *
+ * Environment switches read once per process (A/B measurements, all default to the measured best): CN_STREAM_PROBE=0 (no hardware-queue selection),
+ * CN_TABLES_ZERO_COPY=0 (small operand tables are copied to the device instead of read from the pinned ring), CN_KS_WIDE_MAX / CN_KS_DIGIT_MAX ((ciphertext,
+ * limb) blocks up to which a key switch runs as two launches: 160 / with one workgroup per digit: 10), CN_GEMM_ONE_LIMB=0 (the small-weight GEMM kernel
+ * keeps its two-limb form), CN_DEFER_MERGE_GEMM=0 (deferred scalar products of one flush keep their levels: one launch per level instead of one per term
+ * count), CN_PIN_RING_MIB (size of the pinned upload ring, 32 MiB), CN_DEFER_TRACE=1 (one stderr line per flushed queue level: calls per kind,
+ * launches), CN_LOCK_GRACE_NS / CN_LOCK_COMBINE (the two context-lock experiments that are kept but off, cn_host.cpp). */
 int cn_set_option(cn_ctx *ctx, const char *name, int value);
-/* reads a switch back, or a choice the library made: "behz_small_base" (1: auxiliary primes below 2^49 - the FP64 kernels - k+1 of them,
- * or k+2 where k+1 are too few (N = 16384); 0: SEAL's 61-bit base, taken whenever log2 t + log2 N + log2 q + 2 < log2(B m_sk) does not
- * hold for the small primes or a data prime has 49 bits or more), "behz_f64", "aux_primes" (primes of B plus m_sk), "pending_calls" (deferred calls not yet launched), "f64", "defer", "ks_wide", "ks_xi", "ks_pair14", "ks_chain", "mp_bcast", "sq_fused", "sq_pipe", "enc_fused", "mp_fused",
- * "mul_relin_pipelined" (cn_mul_relin chunks and flushed groups of queued Multiply + Relinearize calls that ran in parts over the context's two streams, "sq_halves"; counts up) */
+/* reads back every option of cn_set_option's list, or one of these read-only values:
+ *   "behz_small_base"          1: auxiliary primes below 2^49 - the FP64 kernels - k+1 of them, or k+2 where k+1 are too few (N = 16384); 0: SEAL's
+ *                              61-bit base, taken whenever log2 t + log2 N + log2 q + 2 < log2(B m_sk) does not hold for the small primes or a data
+ *                              prime has 49 bits or more
+ *   "behz_f64"                 the BEHZ steps run on the FP64 kernels
+ *   "aux_primes"               primes of B plus m_sk
+ *   "pending_calls"            deferred calls not yet launched
+ *   "ready_handles"            single-ciphertext arrays waiting for a lock-free cn_ct_alloc ("defer" = 2)
+ *   "pin_laps"                 laps of the context's pinned upload ring (small tables of a flush; a lap waits for the stream once)
+ *   "folded_zero_encryptions"  zero encryptions folded so far ("fold_zero")
+ *   "mul_relin_pipelined"      cn_mul_relin chunks and flushed groups of queued Multiply + Relinearize calls that ran in parts over the context's two
+ *                              streams ("sq_halves"; counts up)
+ *   "stream_tries"             streams cn_ctx_create tried until one had a hardware queue of its own (< 0: none had; CN_STREAM_PROBE=0 takes the first) */
 int cn_get_option(cn_ctx *ctx, const char *name, int *value);
 /* SEAL DefaultParams.CoeffModulus128(n) (AtomicSealBfvVector.cs:146); returns count, fills q (<=9) */
 int cn_default_coeff_modulus(uint32_t n, uint64_t *q);
