@@ -381,6 +381,7 @@ extern "C" int cn_get_option(cn_ctx *ctx, const char *name, int *value) { API_BO
     else if (!strcmp(name, "mul_relin_pipelined")) *value = (int)std::min<uint64_t>(ctx->mr_pipelined, 0x7fffffff);      // Multiply + Relinearize batches run in parts over two streams
     else if (!strcmp(name, "behz_small_base")) *value = ctx->hc.bsk[ctx->hc.kb - 1].q < (1ull << 49);     // auxiliary primes below 2^49 (FP64 kernels) instead of SEAL's 61-bit ones
     else if (!strcmp(name, "behz_f64")) *value = ctx->hc.behz_f64 && ctx->opt.f64;
+    else if (!strcmp(name, "mod_switch_f64")) *value = ctx->ms_f64;                     // the last cn_mod_switch on this context ran in FP64
     else if (!strcmp(name, "aux_primes")) *value = (int)ctx->hc.kb;
     else if (!strcmp(name, "pending_calls")) *value = (int)ctx->dq->ops.size();
     else if (!strcmp(name, "stream_tries")) *value = ctx->stream_tries;           // streams created until one had a hardware queue of its own (< 0: none had)

@@ -74,6 +74,9 @@ struct DevConsts {
     // modulus switching (cn_mod_switch, SEAL's mod_switch_scale_to_next): dropping prime p keeps limbs i < p with
     // x_i' = (x_i - (r mod q_i) + (h_p mod q_i)) q_p^-1 mod q_i,  r = (x_p + h_p) mod q_p,  h_p = floor(q_p / 2)
     uint64_t ms_inv[CN_MAXK][CN_MAXK], ms_invs[CN_MAXK][CN_MAXK], ms_h[CN_MAXK][CN_MAXK];   // [p][i]: q_p^-1 mod q_i, its Shoup quotient, h_p mod q_i
+    // the same constants as exact doubles for k_mod_switch_f64 (chains whose moduli are all below 2^49): ms_invd centred in (-q_i/2, q_i/2],
+    // ms_hd[p][p] = h_p itself
+    double ms_invd[CN_MAXK][CN_MAXK], ms_hd[CN_MAXK][CN_MAXK];
 };
 
 // host-side precompute (cn_tables.cpp). tw_host must hold (k+kb+1)*4*n words; index_map (n entries) receives the

@@ -204,9 +204,11 @@ struct cn_ctx {
     ReadyRing *ready = nullptr;
     int async_rc = 0; std::string async_msg;        // first error of a record executed from the ring: reported by the next synchronising call
     // modulus switching (cn_level.hip): a level context (cn_ctx_create_level) holds keys sliced from its parent's and refuses key generation and key
-    // uploads; ev_ms marks the point of this context's stream the other context of a cn_mod_switch waits for
+    // uploads; ev_ms marks the point of this context's stream the other context of a cn_mod_switch waits for; ms_f64: the last cn_mod_switch
+    // this context took part in ran the exact-FP64 kernel (cn_get_option "mod_switch_f64")
     bool level = false;
     hipEvent_t ev_ms = nullptr;
+    bool ms_f64 = false;
 };
 
 // ---------------------------------------------------------------- kernel launchers (cn_l_*.hip)
@@ -279,6 +281,7 @@ inline uint32_t gemm_f64_rows(uint32_t K) { return ((K + 15) & ~15u) + 16; }
 int cn_l_gemm(cn_ctx *c, const GemmLaunch &g);
 int cn_l_gemm_mfma(cn_ctx *c, const GemmLaunch &g);   // k_scalar_gemm_mfma: W = weight digit fragments, idx rows of ksteps * 32 entries
 // modulus switching (cn_l_modswitch.hip): `items` (ciphertext, poly) pairs [items][ks][N] -> [items][kd][N] on c's stream with the constants of the source context
-int cn_l_mod_switch(cn_ctx *c, const uint64_t *src, uint64_t *dst, const DevConsts *src_consts, uint32_t ks, uint32_t kd, uint32_t items, uint32_t logn);
+int cn_l_mod_switch(cn_ctx *c, const uint64_t *src, uint64_t *dst, const DevConsts *src_consts, uint32_t ks, uint32_t kd, uint32_t items, uint32_t logn,
+                    bool f64, bool *ran_f64);
 
 inline void cn_launch_count(cn_ctx *c, int n = 1) { c->st.kernel_launches += n; }

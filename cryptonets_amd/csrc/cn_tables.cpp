@@ -261,7 +261,9 @@ int cn_build_consts(DevConsts *c, uint32_t n, const uint64_t *q, uint32_t k, uin
             c->ms_inv[p][i] = invm_prime(q[p] % q[i], q[i]);
             c->ms_invs[p][i] = (uint64_t)(((u128)c->ms_inv[p][i] << 64) / q[i]);
             c->ms_h[p][i] = (q[p] >> 1) % q[i];
+            c->ms_invd[p][i] = c->ms_inv[p][i] > q[i] / 2 ? -(double)(q[i] - c->ms_inv[p][i]) : (double)c->ms_inv[p][i]; c->ms_hd[p][i] = (double)c->ms_h[p][i];
         }
+    for (uint32_t p = 1; p < k; p++) c->ms_hd[p][p] = (double)(q[p] >> 1);
     return 0;
 }
 

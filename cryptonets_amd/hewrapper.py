@@ -221,6 +221,13 @@ def _ctx_limbs(ctx):
     return getattr(ctx, "k", None)
 
 
+def _env_at(env, limbs):
+    """the environment of level `limbs` on env's chain (env itself for None - plaintext operands - or an environment without levels)"""
+    if limbs is None or not hasattr(env, "Level"):
+        return env
+    return env.Level(limbs)
+
+
 def _check_level(env, *vectors):
     """SEAL's parameter-mismatch check (Evaluator: "encrypted1 and encrypted2 parameter mismatch"): every ciphertext operand must be at the
     level of the environment the operation runs in"""
@@ -461,8 +468,9 @@ class AtomicSealBfvEncryptedVector:
             r.encData = _Buf(env.ctx, "ct", v.encData.count).view()
             env.ctx.copy(v.encData.h, v.encData.first, r.encData.h, 0, v.encData.count)
         if v.plainDense is not None:
-            r.plainDense = _Buf(env.ctx, "pt", v.plainDense.count).view()
-            env.ctx.copy(v.plainDense.h, v.plainDense.first, r.plainDense.h, 0, v.plainDense.count)
+            pd = v._pd(env.ctx)
+            r.plainDense = _Buf(env.ctx, "pt", pd.count).view()
+            env.ctx.copy(pd.h, pd.first, r.plainDense.h, 0, pd.count)
             r.plainZero = list(v.plainZero)
         if v.plainSparse is not None:
             r.plainSparse = list(v.plainSparse)
@@ -586,11 +594,26 @@ class AtomicSealBfvEncryptedVector:
         self.Scale = scale
 
     def Dispose(self):
-        cached = self.__dict__.pop("_sparse_as_dense", None)
-        for v in (self.encData, self.plainDense, cached[1] if cached else None):
+        cached = [c[1] for c in self.__dict__.pop("_sparse_as_dense", {}).values()] + list(self.__dict__.pop("_pd_levels", {}).values())
+        for v in [self.encData, self.plainDense] + cached:
             if v is not None:
                 v.release()
         self.encData = self.plainDense = self.plainSparse = None
+
+    def _pd(self, ctx):
+        """the dense plaintexts as a view of `ctx`'s handles.  A plaintext is level-free (N words mod t), but a device handle belongs to one
+        context: at the context they were encoded with, the vector's own; at a level of its chain, a copy made on first use and kept with the
+        vector (once per vector and level, never per call; released by Dispose)"""
+        pd = self.plainDense
+        if pd.buf.ctx is ctx:
+            return pd
+        cache = self.__dict__.setdefault("_pd_levels", {})
+        v = cache.get(ctx)
+        if v is None or not v.live:
+            v = _Buf(ctx, "pt", pd.count).view()
+            ctx.pt_upload(v.h, 0, pd.buf.ctx.pt_download(pd.h, pd.first, pd.count))
+            cache[ctx] = v
+        return v
 
     def _plain_is_zero(self, i):
         return self.plainZero[i] if self.plainDense is not None else self.plainSparse[i] == 0
@@ -647,8 +670,8 @@ class AtomicSealBfvEncryptedVector:
                 for k in range(K):
                     if denses[k]._plain_is_zero(i):
                         continue
-                    ctx.mul_plain(sparse.encData.h, sparse.encData.first + k, denses[k].plainDense.h, denses[k].plainDense.first + i,
-                                  terms.h, k, 1)
+                    pd = denses[k]._pd(ctx)
+                    ctx.mul_plain(sparse.encData.h, sparse.encData.first + k, pd.h, pd.first + i, terms.h, k, 1)
                     used.append(k)
                 if not used:
                     raise Exception("AddMany of an empty list")
@@ -796,10 +819,11 @@ class AtomicSealBfvEncryptedVector:
                 raise Exception("plain cannot be zero")
             ctx.mul_scalar(self.encData.h, self.encData.first, np.array([w], dtype=np.uint64), t.encData.h, 0, self.encData.count, broadcast=True)
         else:                                        # plain blocks x encrypted constant
-            cnt = self.plainDense.count
+            pd = self._pd(ctx)
+            cnt = pd.count
             t.encData = _Buf(ctx, "ct", cnt).view()
             for i in range(cnt):
-                ctx.mul_plain(ev.encData.h, ev.encData.first, self.plainDense.h, self.plainDense.first + i, t.encData.h, i, 1)
+                ctx.mul_plain(ev.encData.h, ev.encData.first, pd.h, pd.first + i, t.encData.h, i, 1)
         return t
 
     def _encrypt_zero_into(self, env, buf_h, index):
@@ -840,7 +864,8 @@ class AtomicSealBfvEncryptedVector:
                 if self.plainZero[i]:
                     self._encrypt_zero_into(env, t.encData.h, i)
                 else:
-                    ctx.mul_plain(ev.encData.h, ev.encData.first + colIndex, self.plainDense.h, self.plainDense.first + i, t.encData.h, i, 1)
+                    pd = self._pd(ctx)
+                    ctx.mul_plain(ev.encData.h, ev.encData.first + colIndex, pd.h, pd.first + i, t.encData.h, i, 1)
             return t
         n = self.encData.count                         # encrypted blocks x one plain constant
         t.encData = _Buf(ctx, "ct", n).view()
@@ -879,7 +904,8 @@ class AtomicSealBfvEncryptedVector:
         pl = self if self.encData is None else ev
         t.encData = _Buf(ctx, "ct", enc.count).view()
         if pl.plainDense is not None:
-            ctx.mul_plain(enc.h, enc.first, pl.plainDense.h, pl.plainDense.first, t.encData.h, 0, enc.count)
+            pd = pl._pd(ctx)
+            ctx.mul_plain(enc.h, enc.first, pd.h, pd.first, t.encData.h, 0, enc.count)
         else:
             if any(w == 0 for w in pl.plainSparse):
                 raise Exception("plain cannot be zero")
@@ -1003,11 +1029,12 @@ class AtomicSealBfvEncryptedVector:
     def _dense_plain_view(self, env):
         """Plaintexts as device polynomials: dense plaintexts as they are; sparse ones as constant polynomials."""
         if self.plainDense is not None:
-            return self.plainDense, False
-        # sparse plaintexts (biases) are constants of the network: their polynomial form is uploaded once and kept with the vector - no
-        # host upload + synchronisation in the middle of every inference (a recorded evaluation could not contain one either)
+            return self._pd(env.ctx), False
+        # sparse plaintexts (biases) are constants of the network: their polynomial form is uploaded once per context (level) and kept with
+        # the vector - no host upload + synchronisation in the middle of every inference (a recorded evaluation could not contain one either)
         key = tuple(int(x) for x in self.plainSparse)
-        cached = self.__dict__.get("_sparse_as_dense")
+        per_ctx = self.__dict__.setdefault("_sparse_as_dense", {})
+        cached = per_ctx.get(env.ctx)
         if cached is None or cached[0] != key or not cached[1].live:
             if cached is not None:
                 cached[1].release()
@@ -1015,7 +1042,7 @@ class AtomicSealBfvEncryptedVector:
             polys = np.zeros((len(self.plainSparse), env.ctx.n), dtype=np.uint64)
             polys[:, 0] = np.array(self.plainSparse, dtype=np.uint64)
             env.ctx.pt_upload(pv.h, 0, polys)
-            self._sparse_as_dense = cached = (key, pv)
+            per_ctx[env.ctx] = cached = (key, pv)
         return cached[1], False
 
     # -- decryption (client side) -------------------------------------------------------------------------------
@@ -1031,7 +1058,7 @@ class AtomicSealBfvEncryptedVector:
                 cts = ctx.ct_download(self.encData.h, self.encData.first, self.encData.count)
                 plains = np.stack([env.client.decrypt(c) for c in cts])
         elif self.plainDense is not None:
-            plains = ctx.pt_download(self.plainDense.h, self.plainDense.first, self.plainDense.count)
+            plains = self.plainDense.buf.ctx.pt_download(self.plainDense.h, self.plainDense.first, self.plainDense.count)
         else:
             plains = None
         if self.Format == EVectorFormat.dense:
@@ -1155,7 +1182,8 @@ class AtomicSealBfvEncryptedVector:
             if s.Scale != selections[first].Scale:
                 raise Exception("scales of all selection vectors should be the same")
             if s.plainDense is not None:
-                ctx.mul_plain(self.encData.h, self.encData.first, s.plainDense.h, s.plainDense.first, work.h, 1, 1)
+                pd = s._pd(ctx)
+                ctx.mul_plain(self.encData.h, self.encData.first, pd.h, pd.first, work.h, 1, 1)
             else:
                 # the reference multiplies without relinearising here (:1457) and would then fail to rotate a size-3
                 # ciphertext; encrypted selections are therefore relinearised
@@ -1242,6 +1270,7 @@ class EncryptedSealBfvVector:
         return cls._of([AtomicSealBfvEncryptedVector.Copy(x, e) for x, e in zip(v.eVectors, env.Environments)], v.Scale)
 
     Dim = property(lambda self: 0 if self.eVectors is None else self.eVectors[0].Dim)
+    Limbs = property(lambda self: None if self.eVectors is None else self.eVectors[0].Limbs)     # level of the ciphertexts, None for plaintexts
     IsEncrypted = property(lambda self: False if self.eVectors is None else self.eVectors[0].IsEncrypted)
     Format = property(lambda self: self.eVectors[0].Format)
     BlockSize = property(lambda self: None)
@@ -1350,9 +1379,11 @@ class EncryptedSealBfvVector:
         return out
 
     def DecryptFullPrecision(self, env):
+        env = _env_at(env, self.Limbs)
         return self._join([v.DecryptFullPrecision(e) for v, e in zip(self.eVectors, env.Environments)], env, self.IsSigned)
 
     def Decrypt(self, env):
+        env = _env_at(env, self.Limbs)
         ints = self._join([v._decrypt_ints(e) for v, e in zip(self.eVectors, env.Environments)], env)
         return np.array([float(x) / self.Scale for x in ints])
 
@@ -1375,6 +1406,76 @@ class EncryptedSealBfvMatrix:
     Scale = property(lambda self: self.leVectors[0].Scale)
     IsEncrypted = property(lambda self: all(v.IsEncrypted for v in self.leVectors))
 
+    @property
+    def Limbs(self):
+        """level of the matrix's ciphertexts (coefficient moduli kept), None for a plaintext matrix"""
+        for v in self.leVectors:
+            if v.IsEncrypted:
+                return v.Limbs
+        return None
+
+    def ModSwitchTo(self, limbs, env):
+        """a NEW matrix at the level q[:limbs], bound to env.Level(limbs); `env` is the environment this matrix is at.  Per plaintext prime
+        ONE cn_mod_switch over all columns: in place when they lie in one range of one array (as the batched layers produce them), otherwise
+        after one gather (cn_copy_many).  A plaintext matrix is level-free and returned as it is."""
+        if self.Limbs is None:
+            return self
+        lenv = env.Level(limbs)
+        if lenv is env:
+            return self
+        if limbs >= env.Limbs:
+            raise Exception("ModSwitchTo: level %d is not below the matrix's level %d" % (limbs, env.Limbs))
+        cols = self.leVectors
+        if not all(c.IsEncrypted for c in cols):
+            raise Exception("ModSwitchTo: a matrix with both encrypted and plaintext columns")
+
+        def one_prime(i, e):
+            views = [c.eVectors[i].encData for c in cols]
+            _check_level(e, *[c.eVectors[i] for c in cols])
+            size = views[0].buf.size
+            if any(v.buf.size != size for v in views):
+                return None                                          # mixed ciphertext sizes: column by column below
+            b0 = views[0].buf
+            idx = [v.first + j for v in views for j in range(v.count)]
+            total = len(idx)
+            tmp = None
+            if all(v.buf is b0 for v in views) and idx == list(range(idx[0], idx[0] + total)):
+                h, first = b0.h, idx[0]
+            else:
+                tmp = _Buf(e.ctx, "ct", total, size).view()
+                if hasattr(e.ctx, "copy_many"):
+                    e.ctx.copy_many([v.h for v in views for _ in range(v.count)], idx, tmp.h, 0)
+                else:
+                    pos = 0
+                    for v in views:
+                        e.ctx.copy(v.h, v.first, tmp.h, pos, v.count)
+                        pos += v.count
+                h, first = tmp.h, 0
+            out = _Buf(lenv.Environments[i].ctx, "ct", total, size)
+            try:
+                e.ctx.mod_switch(h, first, total, lenv.Environments[i].ctx, out.h, 0)
+            finally:
+                if tmp is not None:
+                    tmp.release()
+            return out
+        per_prime = _fan_out(env.Environments, one_prime)
+        r = EncryptedSealBfvMatrix(Format=self.Format)
+        if any(x is None for x in per_prime):
+            for x in per_prime:
+                if x is not None:
+                    x.view().release()
+            r.leVectors = [c.ModSwitchTo(limbs, env) for c in cols]
+            return r
+        vecs, pos = [], 0
+        for c in cols:
+            cnt = c.eVectors[0].encData.count
+            atoms = [AtomicSealBfvEncryptedVector._new(Scale=a.Scale, Dim=a.Dim, Format=a.Format, IsSigned=a.IsSigned, encData=per_prime[i].view(pos, cnt))
+                     for i, a in enumerate(c.eVectors)]
+            vecs.append(EncryptedSealBfvVector._of(atoms, c.Scale))
+            pos += cnt
+        r.leVectors = vecs
+        return r
+
     def Dispose(self):
         for cache in ("_rowpt", "_rowmask"):
             for buf in self.__dict__.pop(cache, {}).values():
@@ -1386,6 +1487,7 @@ class EncryptedSealBfvMatrix:
         self.leVectors = None
 
     def Decrypt(self, env):
+        env = _env_at(env, self.Limbs)
         vecs = [v.Decrypt(env) for v in self.leVectors]
         return np.stack(vecs, axis=0) if self.Format == EMatrixFormat.RowMajor else np.stack(vecs, axis=1)
 
@@ -1551,7 +1653,7 @@ class EncryptedSealBfvMatrix:
             ctx = e.ctx
             h, idx, tmp = _gather(ctx, [c.eVectors[i].encData for c in cols])
             res = _Buf(ctx, "ct", len(cols))
-            pd = plain.eVectors[i].plainDense
+            pd = plain.eVectors[i]._pd(ctx)
             try:
                 if idx == list(range(idx[0], idx[0] + len(idx))):
                     ctx.mul_plain(h, idx[0], pd.h, pd.first, res.h, 0, len(cols), pt_stride=0)
@@ -1574,15 +1676,20 @@ class EncryptedSealBfvMatrix:
 
     # ---- batched HOT LOOP C: every row of a RowMajor plaintext matrix against one packed ciphertext ---------------------
     def _row_plaintexts(self, i, env_i):
-        """contiguous device array with the (single-block, dense) plaintext of every row for prime i - built once"""
+        """contiguous device array with the (single-block, dense) plaintext of every row for prime i - built once per context (level)"""
         cache = self.__dict__.setdefault("_rowpt", {})
-        if i not in cache:
+        key = (i, env_i.ctx)
+        if key not in cache:
             rows = [r.eVectors[i] for r in self.leVectors]
             buf = _Buf(env_i.ctx, "pt", len(rows)).view()
-            for k, r in enumerate(rows):
-                env_i.ctx.copy(r.plainDense.h, r.plainDense.first, buf.h, k, 1)
-            cache[i] = buf
-        return cache[i]
+            if rows[0].plainDense.buf.ctx is env_i.ctx:
+                for k, r in enumerate(rows):
+                    env_i.ctx.copy(r.plainDense.h, r.plainDense.first, buf.h, k, 1)
+            else:                                                    # at a level: one upload of the rows (not a copy per row per level)
+                src = [r.plainDense for r in rows]
+                env_i.ctx.pt_upload(buf.h, 0, np.concatenate([v.buf.ctx.pt_download(v.h, v.first, 1) for v in src]))
+            cache[key] = buf
+        return cache[key]
 
     def _can_batch_rows(self, v):
         return (not LITERAL and self.Format == EMatrixFormat.RowMajor and v.IsEncrypted and v.Format == EVectorFormat.dense
@@ -1619,11 +1726,11 @@ class EncryptedSealBfvMatrix:
             fmt = EVectorFormat.sparse if ln >= slots else EVectorFormat.dense
             if ForceOutputInColumns:
                 mcache = self.__dict__.setdefault("_rowmask", {})
-                if i not in mcache:                                  # one-hot masks e_r (SumAllSlots ForceOutputInColumn, :936-945)
+                if (i, ctx) not in mcache:                           # one-hot masks e_r (SumAllSlots ForceOutputInColumn, :936-945), per context (level)
                     masks = _Buf(ctx, "pt", R).view()
                     ctx.encode_batch(np.eye(R, dtype=np.uint64), masks.h, 0)          # e_0 .. e_{R-1} in one call
-                    mcache[i] = masks
-                masks = mcache[i]
+                    mcache[(i, ctx)] = masks
+                masks = mcache[(i, ctx)]
                 ctx.mul_plain(work.h, 0, masks.h, 0, work.h, 0, R)
                 tot = _Buf(ctx, "ct", 1)
                 ctx.add_many(work.h, list(range(R)), tot.h, 0)
@@ -1669,7 +1776,7 @@ class EncryptedSealBfvMatrix:
                 raise Exception("batched PoolLayer expects single-block encrypted columns")
             h, idx, tmp = _gather(ctx, [c.encData for c in cols])
             res = _Buf(ctx, "ct", O)
-            key = (i, tuple(idx), None if bias is None else tuple(int(b) for b in bias), bias_vectors is not None)   # the bias depends on the input scale
+            key = (i, _ctx_limbs(ctx), tuple(idx), None if bias is None else tuple(int(b) for b in bias), bias_vectors is not None)   # the bias depends on the input scale; plans belong to one context (level)
             if cache is not None and key in cache and hasattr(ctx, "gemm_apply"):
                 try:
                     ctx.gemm_apply(cache[key][0], h, res.h, 0)
@@ -1684,7 +1791,7 @@ class EncryptedSealBfvMatrix:
             if bias_vectors is not None:
                 bp = _Buf(ctx, "pt", O).view()
                 for o_, bv in enumerate(bias_vectors):
-                    pd = bv.eVectors[i].plainDense
+                    pd = bv.eVectors[i]._pd(ctx)
                     ctx.copy(pd.h, pd.first, bp.h, o_, 1)
                 bh, bidx = bp.h, np.arange(O, dtype=np.int32)
             elif bias is not None:

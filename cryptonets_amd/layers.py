@@ -8,7 +8,7 @@ SquareActivation and prime).
 import numpy as np
 
 from .convolution import ConvolutionEngine
-from .hewrapper import EMatrixFormat, EVectorFormat
+from .hewrapper import EMatrixFormat, EVectorFormat, _env_at
 from .raw import Defaults, RawMatrix
 from .cryptotracker import CryptoTracker, OperationsCount
 from . import tracing
@@ -31,6 +31,8 @@ def _sync_factory(layer):
         return
     for e in getattr(env, "Environments", ()):
         e.ctx.sync()
+        for lv in getattr(e, "_levels", {}).values():          # the level contexts of a scheduled chain have streams of their own
+            lv.ctx.sync()
 
 
 class BaseLayer:
@@ -64,6 +66,11 @@ class BaseLayer:
 
     def Apply(self, m):
         raise NotImplementedError
+
+    def _env(self, m):
+        """the computation environment at the level of the input `m` (modulus switching): the factory's own environment object for a
+        top-level or plaintext input, its Level(m.Limbs) otherwise"""
+        return _env_at(self.Factory.AllocateComputationEnv(), getattr(m, "Limbs", None))
 
     Verbose = False
 
@@ -199,7 +206,7 @@ class SquareActivation(BaseLayer):
     """NeuralNetworks/SquareActivation.cs:10-19"""
 
     def Apply(self, m):
-        return m.ElementWiseMultiply(m, self.Factory.AllocateComputationEnv())
+        return m.ElementWiseMultiply(m, self._env(m))
 
     def GetOutputScale(self):
         s = self.Source.GetOutputScale()
@@ -242,7 +249,7 @@ class PoolLayer(BaseLayer):
     def Apply(self, m):
         if not self.layerPrepared:
             self.Prepare()
-        env = self.Factory.AllocateComputationEnv()
+        env = self._env(m)
         corners, maps = len(self.engine.Corners), self.engine.maps
         if self.Weights is None:
             # pool without convolve (PoolLayer.cs:122-147): sum of the window, scale multiplied by the window size
@@ -299,7 +306,7 @@ class LLDenseLayer(BaseLayer):
             self.Prepare()
         if m.ColumnCount > 1:
             raise Exception("Expecting only one column")
-        env = self.Factory.AllocateComputationEnv()
+        env = self._env(m)
         mul = self.WeightsMatrix.Mul(m.GetColumn(0), env, self.ForceDenseFormat)
         res = mul.Add(self.BiasVector, env)
         if res is not mul:
@@ -575,7 +582,7 @@ class LLPreConvLayer(BaseLayer):
             raise Exception("Expecting only a single column")
         if not self.layerPrepared:
             self.Prepare()
-        env = self.Factory.AllocateComputationEnv()
+        env = self._env(m)
         v = m.GetColumn(0)
         res = [v.Permute(self.masks[k], self.shifts[k], self.outputDim, env) for k in range(len(self.masks))]
         return self.Factory.GetMatrix(res, EMatrixFormat.ColumnMajor, CopyVectors=False)
@@ -641,6 +648,24 @@ class TimingLayer(BaseLayer):
         return m
 
 
+class ModSwitchLayer(BaseLayer):
+    """Modulus switching between layers (SEAL's Evaluator.ModSwitchTo; the reference keeps every ciphertext at the first level): the input
+    matrix switched down to `Limbs` coefficient moduli.  The layers after it run at that level (BaseLayer._env); networks.with_levels
+    inserts these layers, levels.plan_levels chooses where."""
+
+    def __init__(self, Source=None, Factory=None, Limbs=None):
+        super().__init__(Source, Factory)
+        self.Limbs = int(Limbs)
+
+    def Apply(self, m):
+        cur = getattr(m, "Limbs", None)
+        if cur is None:
+            raise Exception("ModSwitchLayer: the input is not encrypted")
+        if not 1 <= self.Limbs < cur:
+            raise Exception("ModSwitchLayer: level %d is not below the input's level %d" % (self.Limbs, cur))
+        return m.ModSwitchTo(self.Limbs, self._env(m))
+
+
 class WeightsReader:
     """NeuralNetworks/WeightsReader.cs: one array per CSV line, for the weights file and the biases file"""
 
@@ -689,7 +714,7 @@ class LLPoolLayer(BaseLayer):
     def Apply(self, m):
         if not self.layerPrepared:
             self.Prepare()
-        env = self.Factory.AllocateComputationEnv()
+        env = self._env(m)
         if self.Weights is None:
             vec = m.GetColumn(0)
             for i in range(1, m.ColumnCount):
@@ -720,7 +745,7 @@ class LLVectorizeLayer(BaseLayer):
     """NeuralNetworks/LLVectorizeLayer.cs: stack the columns into one packed vector"""
 
     def Apply(self, m):
-        vec = m.ConvertToColumnVector(self.Factory.AllocateComputationEnv())
+        vec = m.ConvertToColumnVector(self._env(m))
         return self.Factory.GetMatrix([vec], EMatrixFormat.ColumnMajor, CopyVectors=False)
 
 
@@ -732,7 +757,7 @@ class LLDuplicateLayer(BaseLayer):
         self.Count = Count
 
     def Apply(self, m):
-        env = self.Factory.AllocateComputationEnv()
+        env = self._env(m)
         return self.Factory.GetMatrix([m.GetColumn(i).Duplicate(self.Count, env) for i in range(m.ColumnCount)], m.Format, CopyVectors=False)
 
     def OutputDimension(self):
@@ -778,7 +803,7 @@ class LLPackedDenseLayer(BaseLayer):
             self.Prepare()
         if m.ColumnCount > 1:
             raise Exception("Expecting only one column")
-        env = self.Factory.AllocateComputationEnv()
+        env = self._env(m)
         vector, res = m.GetColumn(0), []
         if getattr(self.WeightsMatrix, "_can_batch_rows", lambda v: False)(vector):
             # all packed rows at once: one MultiplyPlain / rotate-and-add launch chain per plaintext prime
@@ -817,7 +842,7 @@ class LLInterleaveLayer(BaseLayer):
     def Apply(self, m):
         if not self.layerPrepared:
             self.Prepare()
-        env = self.Factory.AllocateComputationEnv()
+        env = self._env(m)
         cleanMat = m.MulColumnsByPlain(self.mask, env)               # all columns x the selection mask in one launch chain per prime
         interleaved = cleanMat.Interleave(self.Shift, env)
         cleanMat.Dispose()
@@ -864,7 +889,7 @@ class LLInterleavedDenseLayer(BaseLayer):
     def Apply(self, m):
         if not self.layerPrepared:
             self.Prepare()
-        env = self.Factory.AllocateComputationEnv()
+        env = self._env(m)
         mul = self.WeightsMatrix.Mul(m.GetColumn(0), env)
         v = mul.Add(self.BiasVector, env)
         mul.Dispose()

@@ -8,8 +8,8 @@ import numpy as np
 
 from .hewrapper import EVectorFormat
 from .layers import (BatchReader, EncryptLayer, LLConvReader, LLDenseLayer, LLDuplicateLayer, LLInterleavedDenseLayer, LLInterleaveLayer,
-                     LLPackedDenseLayer, LLPoolLayer, LLPreConvLayer, LLSingleLineReader, LLVectorizeLayer, PoolLayer, SquareActivation,
-                     TimingLayer)
+                     LLPackedDenseLayer, LLPoolLayer, LLPreConvLayer, LLSingleLineReader, LLVectorizeLayer, ModSwitchLayer, PoolLayer,
+                     SquareActivation, TimingLayer)
 
 # plaintext primes, N, decomposition bit counts, coefficient primes taken: CryptoNets.cs:17; LoLaCryptonets.cs:123,208,285,338;
 # LolaCifarCryptoNet.cs:35
@@ -180,6 +180,32 @@ def _chain(network):
         p = p.Source
 
 
+def with_levels(network, schedule):
+    """Insert modulus switches into the chain ending in `network` (SEAL users place mod_switch_to_next calls by hand; levels.plan_levels
+    plans them).  `schedule`: ordered (boundary, limbs) pairs - boundary = position in _chain(network) counted from the reader (0) of the
+    layer after which the ciphertexts are switched down to `limbs` coefficient moduli; a switch after the last layer sets the reply level.
+    Boundaries must increase, levels decrease, and every switch must come after the EncryptLayer.  The layers are rewired (each layer
+    after a boundary takes a ModSwitchLayer as its Source), never copied.  Returns the head of the new chain."""
+    layers = list(_chain(network))[::-1]
+    schedule = [(int(b), int(lv)) for b, lv in schedule]
+    enc = next((i for i, p in enumerate(layers) if isinstance(p, EncryptLayer)), 0)
+    for j, (b, lv) in enumerate(schedule):
+        if not enc <= b < len(layers):
+            raise ValueError("with_levels: boundary %d is outside the encrypted part of the chain (layers %d..%d)" % (b, enc, len(layers) - 1))
+        if lv < 1:
+            raise ValueError("with_levels: a level keeps at least one coefficient modulus (got %d)" % lv)
+        if j and (b <= schedule[j - 1][0] or lv >= schedule[j - 1][1]):
+            raise ValueError("with_levels: the schedule must have increasing boundaries and decreasing levels: %s" % (schedule,))
+    head = network
+    for b, lv in schedule:
+        ms = ModSwitchLayer(Source=layers[b], Limbs=lv)
+        if b == len(layers) - 1:
+            head = ms
+        else:
+            layers[b + 1].Source = ms
+    return head
+
+
 def evaluate_batches(network, Factory, reader, numberOfRecords, report=print):
     """CryptoNets.cs:80-109: batches until `numberOfRecords` samples are scored; prediction = arg max of the decrypted row.
     Returns (errors, count)."""
@@ -221,6 +247,8 @@ def evaluate_single_recorded(network, Factory, records, report=print):
     enc, tail = layers[k], layers[k + 1:]
     if any(isinstance(p, TimingLayer) for p in layers):
         raise Exception("a recorded evaluation cannot contain TimingLayers (they synchronise)")
+    if any(isinstance(p, ModSwitchLayer) for p in layers):
+        raise Exception("a recorded evaluation cannot contain ModSwitchLayers (cn_mod_switch is refused during a graph capture)")
     for p in layers:
         p.Factory = Factory
     network.PrepareNetwork()

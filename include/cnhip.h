@@ -77,7 +77,10 @@ int cn_ctx_create_level(cn_ctx *parent, uint32_t limbs, cn_ctx **out);
  * graph: CN_ERR_ARG and no switch is enqueued, `out` is not written.  Not deferrable: takes both context locks (more limbs first) and submits both
  * contexts' queued calls first - also when the handle or range checks then refuse the call (handles may come from the lock-free ring, "defer" = 2);
  * the context checks (chain, capture) refuse before anything is submitted.  Ordering without a host wait (events): the switch reads `in` after the work submitted to src before the call, writes `out` after
- * the work submitted to dst before it; later dst calls see the result, later src calls wait for the read. */
+ * the work submitted to dst before it; later dst calls see the result, later src calls wait for the read.
+ * Arithmetic: with "f64" on (both contexts) and every modulus of src below 2^49, the drops run in exact FP64 (k_mod_switch_f64) for the
+ * (k_src, k_dst) pairs where that form measured faster - switches of two or more primes; otherwise, and under "f64" = 0 / CN_NO_F64=1, in
+ * 64-bit integers (k_mod_switch).  Both produce the same words; cn_get_option "mod_switch_f64" tells which ran last. */
 int cn_mod_switch(cn_ctx *src, cn_handle in, uint32_t ii, uint32_t count, cn_ctx *dst, cn_handle out, uint32_t oi);
 /* Options of a context.  The tuning switches (A/B testing) all produce identical words.  cn_set_option refuses an unknown name, and a value
  * outside the range of an enumerated switch, with CN_ERR_ARG and keeps the old value; a flag takes any value, non-zero = on.  An environment
@@ -178,6 +181,7 @@ int cn_set_option(cn_ctx *ctx, const char *name, int value);
  *                              61-bit base, taken whenever log2 t + log2 N + log2 q + 2 < log2(B m_sk) does not hold for the small primes or a data
  *                              prime has 49 bits or more
  *   "behz_f64"                 the BEHZ steps run on the FP64 kernels
+ *   "mod_switch_f64"           the last cn_mod_switch this context took part in (source or target) ran the exact-FP64 kernel
  *   "aux_primes"               primes of B plus m_sk
  *   "pending_calls"            deferred calls not yet launched
  *   "ready_handles"            single-ciphertext arrays waiting for a lock-free cn_ct_alloc ("defer" = 2)
