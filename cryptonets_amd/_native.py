@@ -17,7 +17,7 @@ CSRC = os.path.join(_PKG, "csrc")
 SOURCES = [os.path.join(CSRC, f) for f in (
     "cn_api.hip", "cn_eval.hip", "cn_client.hip", "cn_defer.hip", "cn_multi.hip", "cn_host.cpp", "cn_tables.cpp", "cn_l_gemm.hip", "cn_l_behz.hip",
     "cn_l_rr_u64.hip", "cn_l_rr_f64.hip", "cn_l_rr_f64l.hip", "cn_l_ks_u64.hip", "cn_l_ks_f64.hip", "cn_l_ks_f64l.hip", "cn_level.hip", "cn_l_modswitch.hip",
-    "cn_l_modswitch_f64.hip")]
+    "cn_l_modswitch_f64.hip", "cn_l_noise.hip")]
 OBJ_DIR = os.path.join(_PKG, "lib", "obj")
 
 U64P = C.POINTER(C.c_uint64)
@@ -186,6 +186,7 @@ SIGNATURES = {
     "cn_encrypt": (C.c_int, [_CTX, _H, _u32, _u32, _H, _u32, _u32, C.c_uint64]),
     "cn_decrypt": (C.c_int, [_CTX, _H, _u32, _u32, _H, _u32]),
     "cn_noise_poly": (C.c_int, [_CTX, _H, _u32, _u32, C.POINTER(C.c_uint64)]),
+    "cn_noise_norm": (C.c_int, [_CTX, _H, _u32, _u32, C.POINTER(C.c_uint64)]),
     "cn_ntt_forward": (C.c_int, [_CTX, C.c_void_p, _u32, C.c_int]),
     "cn_ntt_inverse": (C.c_int, [_CTX, C.c_void_p, _u32, C.c_int]),
     "cn_ct_ntt": (C.c_int, [_CTX, _H, _u32, _u32, C.c_int]),
@@ -610,20 +611,23 @@ class Context:
         self._chk(self.L.cn_noise_poly(self._h, ct, ci, count, _p64(out)))
         return out
 
+    def noise_norm(self, ct, ci=0, count=1):
+        """exact centred infinity norms || t*(c0 + c1 s + c2 s^2) mod q ||_inf of `count` ciphertexts, as Python ints (cn_noise_norm: composed
+        and reduced on the device, k words per ciphertext; needs the secret key)"""
+        out = np.zeros((max(count, 1), self.k), dtype=np.uint64)
+        self._chk(self.L.cn_noise_norm(self._h, ct, ci, count, _p64(out)))
+        return [sum(int(w) << (64 * i) for i, w in enumerate(row)) for row in out[:count]]
+
     def invariant_noise_budget(self, ct, ci=0, count=1, exact_bits=False):
         """Decryptor.InvariantNoiseBudget (what CryptoTracker.TestBudget reads, CryptoTracker.cs:41-52) of `count` ciphertexts:
         log2(q) - log2(|| t (c0 + c1 s + c2 s^2) mod q ||_inf, centred) - 1, in bits (float); with `exact_bits` SEAL's integer
-        max(0, bitcount(q) - bitcount(norm) - 1).  The limbs are composed on the host with Python integers: a debugging probe."""
+        max(0, bitcount(q) - bitcount(norm) - 1).  Both from the exact norm of noise_norm."""
         import math
-        w = self.noise_poly(ct, ci, count)
         Q = 1
         for qj in self.q:
             Q *= qj
-        coef = [(Q // qj) * pow((Q // qj) % qj, -1, qj) for qj in self.q]
         out = []
-        for c in range(count):
-            x = sum(w[c, j].astype(object) * coef[j] for j in range(self.k)) % Q
-            norm = max(int(v) if 2 * int(v) <= Q else Q - int(v) for v in x)
+        for norm in self.noise_norm(ct, ci, count):
             if exact_bits:
                 out.append(max(0, Q.bit_length() - norm.bit_length() - 1))
             else:

@@ -1,8 +1,8 @@
 """HE Wrapper/CryptoTracker.cs: the noise-budget watermark.  The reference compiles the probe in only for DEBUG builds; here it is
 off until `CryptoTracker.EnableBudgetTests()` (or CN_BUDGET_TESTS=1), because every probe is a secret-key operation on the client
-context plus a host-side CRT of the N coefficients.  A client that can measure budgets offers
-`noise_budget(ct_handle, first, count) -> [bits, ...]` (SEAL's integer `Decryptor.InvariantNoiseBudget`; `DeviceClient` does, through
-`cn_noise_poly`) or, for a host-side client, `noise_budget_words(ciphertext words) -> bits`."""
+context.  A client that can measure budgets offers `noise_budget(ct_handle, first, count) -> [bits, ...]` (SEAL's integer
+`Decryptor.InvariantNoiseBudget`; `DeviceClient` does, through `cn_noise_norm`: the exact norm composed and reduced on the device, k words
+per ciphertext to the host) or, for a host-side client, `noise_budget_words(ciphertext words) -> bits` (a CRT of the N coefficients)."""
 import os
 
 import numpy as np

@@ -230,7 +230,7 @@ int gen_ksk(cn_ctx *ctx, const uint64_t *snew, int dbc, const uint32_t *dig, uin
 int adopt_ksk(cn_ctx *ctx, KsKey &slot, uint64_t *dev, size_t words);
 int encrypt_chain(cn_ctx *ctx, uint32_t cnt, const uint64_t *ptd, uint32_t pt_stride_words, uint64_t *out, uint64_t seed, const EncTab *htab);
 int encrypt_body(cn_ctx *ctx, cn_handle pt, uint32_t pi, uint32_t pt_stride, cn_handle out, uint32_t oi, uint32_t count, uint64_t seed);
-int decrypt_phase(cn_ctx *ctx, Buffer *I, uint32_t ci, uint32_t count, uint64_t *&acc);
+int decrypt_phase(cn_ctx *ctx, Buffer *I, uint32_t ci, uint32_t count, uint64_t *&acc, size_t extra = 0);
 DeferQueue *cn_defer_new();
 void cn_defer_delete(DeferQueue *q);
 bool cn_defer_pending(cn_ctx *ctx);

@@ -258,9 +258,10 @@ template <int K> static void launch_dec_scale(cn_ctx *c, const uint64_t *c0, siz
     hipLaunchKernelGGL(k_decrypt_scale<K>, dim3(cnt * c->chunks), dim3(c->bs), 0, c->stream, c0, stride, acc, plain, c->dc, c->chunks);
 }
 // acc[ct][j] <- c1 s (+ c2 s^2) in coefficient form: the part of the decryption phase that needs the secret key
-int decrypt_phase(cn_ctx *ctx, Buffer *I, uint32_t ci, uint32_t count, uint64_t *&acc) {
+// (extra: bytes of scratch the caller carves out behind it)
+int decrypt_phase(cn_ctx *ctx, Buffer *I, uint32_t ci, uint32_t count, uint64_t *&acc, size_t extra) {
     const uint32_t n = ctx->hc.n, k = ctx->hc.k; const size_t kn = (size_t)k * n;
-    CHECK(ensure_scratch(ctx, al((size_t)count * kn * 8) * 3 + al(kn * 8)));
+    CHECK(ensure_scratch(ctx, al((size_t)count * kn * 8) * 3 + al(kn * 8) + al(extra)));
     acc = salloc<uint64_t>(ctx, (size_t)count * kn);
     uint64_t *tmp = salloc<uint64_t>(ctx, (size_t)count * kn), *sp = salloc<uint64_t>(ctx, kn);
     const uint64_t *base = I->d + ci * I->item_words;
@@ -301,6 +302,29 @@ extern "C" int cn_noise_poly(cn_ctx *ctx, cn_handle ct, uint32_t ci, uint32_t co
     hipLaunchKernelGGL(k_noise_poly, dim3(count * ctx->hc.k * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, I->d + ci * I->item_words, (size_t)I->item_words, acc, ctx->dc, ctx->chunks);
     HIPCHK(hipGetLastError()); launch_count(ctx);
     HIPCHK(hipMemcpyAsync(host, acc, (size_t)count * ctx->hc.k * ctx->hc.n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return 0;
+API_END }
+// The same probe without the N k words per ciphertext on the host: k_noise_norm (cn_k_noise.hip.h) composes the limbs and reduces the centred
+// infinity norm on the device, k words per ciphertext.  At most NOISE_CHUNK_WORDS / (k N) ciphertexts per pass: decrypt_phase's scratch
+// (3 x pass x k x N words) stays below 384 MiB whatever the count.
+static const size_t NOISE_CHUNK_WORDS = (size_t)1 << 24;
+extern "C" int cn_noise_norm(cn_ctx *ctx, cn_handle ct, uint32_t ci, uint32_t count, uint64_t *host) { API_BODY
+    LOCK; NOT_CAPTURING("cn_noise_norm"); GETCT(I, ct, 0);
+    if (!ctx->sk) return fail(CN_ERR_NOKEY, "secret key not set");
+    if (!host || !range_ok(I, ci, count)) return fail(CN_ERR_ARG, "index out of range");
+    if (!count) return 0;
+    const uint32_t k = ctx->hc.k; const size_t kn = (size_t)k * ctx->hc.n;
+    const uint32_t pass = (uint32_t)std::max<size_t>(1, NOISE_CHUNK_WORDS / kn);
+    for (uint32_t c = 0; c < count; c += pass) {
+        const uint32_t m = std::min(pass, count - c);
+        uint64_t *acc = nullptr;
+        CHECK(decrypt_phase(ctx, I, ci + c, m, acc, (size_t)m * k * 8));
+        uint64_t *norm = salloc<uint64_t>(ctx, (size_t)m * k);
+        if (!norm) return fail(CN_ERR_HIP, "internal: scratch exhausted in cn_noise_norm");
+        CHECK(cn_l_noise_norm(ctx, I->d + (size_t)(ci + c) * I->item_words, I->item_words, acc, norm, m));
+        HIPCHK(hipMemcpyAsync(host + (size_t)c * k, norm, (size_t)m * k * 8, hipMemcpyDeviceToHost, ctx->stream));
+    }
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return 0;
 API_END }

@@ -77,6 +77,10 @@ struct DevConsts {
     // the same constants as exact doubles for k_mod_switch_f64 (chains whose moduli are all below 2^49): ms_invd centred in (-q_i/2, q_i/2],
     // ms_hd[p][p] = h_p itself
     double ms_invd[CN_MAXK][CN_MAXK], ms_hd[CN_MAXK][CN_MAXK];
+    // invariant noise norm (cn_noise_norm, k_noise_norm): q/q_j and q as k little-endian 64-bit words (q/q_j < 2^(61(k-1)) needs at most k - 1
+    // of them: every q_j < 2^61), and 1/q_j as a double (the estimate of the CRT quotient)
+    uint64_t nn_qhat[CN_MAXK][CN_MAXK], nn_q[CN_MAXK];
+    double nn_qinv[CN_MAXK];
 };
 
 // host-side precompute (cn_tables.cpp). tw_host must hold (k+kb+1)*4*n words; index_map (n entries) receives the

@@ -283,5 +283,8 @@ int cn_l_gemm_mfma(cn_ctx *c, const GemmLaunch &g);   // k_scalar_gemm_mfma: W =
 // modulus switching (cn_l_modswitch.hip): `items` (ciphertext, poly) pairs [items][ks][N] -> [items][kd][N] on c's stream with the constants of the source context
 int cn_l_mod_switch(cn_ctx *c, const uint64_t *src, uint64_t *dst, const DevConsts *src_consts, uint32_t ks, uint32_t kd, uint32_t items, uint32_t logn,
                     bool f64, bool *ran_f64);
+// invariant noise norm (cn_l_noise.hip): `count` ciphertexts (c0 of ciphertext i at c0 + i * ct_stride, acc [count][k][N] from decrypt_phase) ->
+// out [count][k] words on c's stream
+int cn_l_noise_norm(cn_ctx *c, const uint64_t *c0, size_t ct_stride, const uint64_t *acc, uint64_t *out, uint32_t count);
 
 inline void cn_launch_count(cn_ctx *c, int n = 1) { c->st.kernel_launches += n; }

@@ -264,6 +264,18 @@ int cn_build_consts(DevConsts *c, uint32_t n, const uint64_t *q, uint32_t k, uin
             c->ms_invd[p][i] = c->ms_inv[p][i] > q[i] / 2 ? -(double)(q[i] - c->ms_inv[p][i]) : (double)c->ms_inv[p][i]; c->ms_hd[p][i] = (double)c->ms_h[p][i];
         }
     for (uint32_t p = 1; p < k; p++) c->ms_hd[p][p] = (double)(q[p] >> 1);
+    // q (`big` above) and q/q_j as k words each
+    for (uint32_t w = 0; w < k; w++) c->nn_q[w] = w < big.size() ? big[w] : 0;
+    for (uint32_t j = 0; j < k; j++) {
+        std::vector<uint64_t> qh(k, 0); qh[0] = 1;
+        for (uint32_t i = 0; i < k; i++) {
+            if (i == j) continue;
+            uint64_t carry = 0;
+            for (auto &w : qh) { u128 p = (u128)w * q[i] + carry; w = (uint64_t)p; carry = (uint64_t)(p >> 64); }
+        }
+        for (uint32_t w = 0; w < k; w++) c->nn_qhat[j][w] = qh[w];
+        c->nn_qinv[j] = 1.0 / (double)q[j];
+    }
     return 0;
 }
 

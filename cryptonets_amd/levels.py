@@ -1,17 +1,14 @@
 """Modulus-switching schedules for the networks: where, after which layer, the ciphertexts can drop to fewer coefficient moduli.
 
 A SEAL user reads noise budgets and inserts mod_switch_to_next calls by hand.  `plan_levels` does it from measurements: it runs the chain
-on calibration records, reads the noise budget after every layer (CryptoTracker.TestVectorBudget: SEAL's integer invariant noise budget,
-on the device through cn_noise_poly), and descends greedily boundary by boundary.  Key switching costs about k^2 in the number of limbs k,
+on calibration records, reads the noise budget after every layer (the minimum CryptoTracker.TestVectorBudget reads: SEAL's integer invariant noise budget,
+on the device through cn_noise_norm), and descends greedily boundary by boundary.  Key switching costs about k^2 in the number of limbs k,
 so every limb dropped early makes the later layers cheaper; switching cannot create budget, it only spends what the later layers leave.
 
     plan = plan_levels(network, Factory, records=1)
     head = networks.with_levels(network, plan.schedule)
 """
-import contextlib
-import io
-
-from .cryptotracker import CryptoTracker
+from .cryptotracker import INT_MAX
 from .hewrapper import _env_at
 from .layers import EncryptLayer
 
@@ -106,25 +103,41 @@ def descend(oracle, boundaries, margin_bits=8):
 
 
 def min_budget(ms, Factory):
-    """the lowest noise budget (bits) over every ciphertext and plaintext prime of the matrices `ms`, each measured at its own level
-    (CryptoTracker.TestVectorBudget; the tracker's watermark is left as it was)"""
-    saved, best = CryptoTracker.MinBudgetSoFar, None
-    try:
-        for m in ms:
-            env = _env_at(Factory.AllocateComputationEnv(), m.Limbs)
-            for col in m.leVectors:
-                CryptoTracker.Reset()
-                try:
-                    with contextlib.redirect_stdout(io.StringIO()):
-                        b = CryptoTracker.TestVectorBudget(col, env)
-                except Exception as e:                         # the watermark raises at zero
-                    if "budget is zero" not in str(e):
-                        raise
-                    b = 0
-                best = b if best is None else min(best, b)
-    finally:
-        CryptoTracker.MinBudgetSoFar = saved
+    """the lowest noise budget (bits) over every ciphertext and plaintext prime of the matrices `ms`, each measured at its own level - what
+    CryptoTracker.TestVectorBudget reads column by column, but with one device probe (cn_noise_norm) per contiguous range of one handle per
+    plaintext prime instead of one per column; host-side clients are probed ciphertext by ciphertext (the tracker's watermark is untouched)"""
+    best, columns = INT_MAX, 0
+    for m in ms:
+        env = _env_at(Factory.AllocateComputationEnv(), m.Limbs)
+        ranges = {}                                                    # prime -> (environment, [(handle, first, count)])
+        for col in m.leVectors:
+            columns += 1
+            for p, (atom, e) in enumerate(zip(col.eVectors, env.Environments)):
+                d = atom.encData
+                if d is None:
+                    continue
+                if hasattr(e.client, "noise_budget"):
+                    ranges.setdefault(p, (e, []))[1].append((d.h, d.first, d.count))
+                elif hasattr(e.client, "noise_budget_words"):
+                    best = min([best] + [int(e.client.noise_budget_words(w)) for w in e.ctx.ct_download(d.h, d.first, d.count)])
+        for e, rs in ranges.values():
+            for h, first, count in _contiguous(rs):
+                best = min([best] + [int(b) for b in e.client.noise_budget(h, first, count)])
+    if not columns:
+        raise ValueError("min_budget of no ciphertexts")
     return float(best)
+
+
+def _contiguous(ranges):
+    """(handle, first, count) ranges merged where they touch or overlap within one handle"""
+    out = []
+    for h, first, count in sorted(ranges, key=lambda r: (r[0], r[1])):
+        if out and out[-1][0] == h and first <= out[-1][1] + out[-1][2]:
+            h0, f0, c0 = out[-1]
+            out[-1] = (h0, f0, max(c0, first + count - f0))
+        else:
+            out.append((h, first, count))
+    return out
 
 
 class _DeviceOracle:

@@ -373,6 +373,12 @@ int cn_decrypt(cn_ctx *ctx, cn_handle ct, uint32_t ci, uint32_t count, cn_handle
  * residues of t*(c0 + c1 s + c2 s^2) mod q_j, [count][k][N], to `host`; the caller composes the limbs (CRT) and takes
  * budget = log2(q) - log2(centred infinity norm) - 1.  Needs the secret key (client-side context); synchronises. */
 int cn_noise_poly(cn_ctx *ctx, cn_handle ct, uint32_t ci, uint32_t count, uint64_t *host);
+/* The same probe reduced on the device: writes the exact centred infinity norm of t*(c0 + c1 s [+ c2 s^2]) mod q, k little-endian 64-bit
+ * words per ciphertext, [count][k], to `host` (budget = bitcount(q) - bitcount(norm) - 1).  Size-2 and size-3 ciphertexts, any k <= 12, level
+ * contexts (their slice of the secret key).  Flushes deferred work first; CN_ERR_NOKEY without the secret key, CN_ERR_ARG for an index out of
+ * range, a null `host` or while a graph is recorded; count 0 returns 0.  Processes at most max(1, 2^24 / (k N)) ciphertexts per pass, so its
+ * scratch stays bounded; synchronises. */
+int cn_noise_norm(cn_ctx *ctx, cn_handle ct, uint32_t ci, uint32_t count, uint64_t *host /* [count][k] */);
 
 /* ---- raw transforms (kernel benchmarks / parity tests of the NTT itself) --------------- */
 /* in-place negacyclic NTT over `limbs` limbs of N words at a device pointer; limb i uses modulus
