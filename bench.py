@@ -5,11 +5,13 @@ One step = one 8192-image ciphertext batch through the five evaluated layers (th
 window, CryptoNets/CryptoNets.cs:31,74) for BOTH plaintext-prime channels, inputs resident in HBM.
 N GPUs: one process per GPU (torch.distributed, backend nccl = RCCL), every rank evaluates its own
 independent batch (weak scaling, no data-path collective); evaluation keys are broadcast once from rank 0.
-Prints ONE JSON line on rank 0 with `roofline` (the N=8192 NTT kernel, HIP-event timed), `key_switch` and `square` (the two kernel
-families that are 90 % of the batch, priced against FP64 issue with instruction counts read from the built code object) and, at N=1,
-`unchanged_caller` (the reference's per-ciphertext call pattern replayed on the C ABI), `lola` / `cifar` (BASELINE configs 4 and 5 as
-child processes: `--workload lola|cifar`, each verified inside its run; `--no-single-image` skips them) and `cpu_baseline` (the CPU
-oracle = port of the reference's SEAL path, timed on a bounded sample).  The whole default line takes about a minute.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the headline.
+`--full` adds, after the timed steps, the check of every decrypted slot against the exact integer model (`verified_against_integer_model`),
+`roofline` (the N=8192 NTT kernel, HIP-event timed), `key_switch` and `square` (the two kernel families that are 90 % of the batch, priced
+against FP64 issue with instruction counts read from the built code object), `relinearize_late` and, at N=1, `unchanged_caller` (the
+reference's per-ciphertext call pattern replayed on the C ABI), `lola` / `cifar` (BASELINE configs 4 and 5 as child processes:
+`--workload lola|cifar`, each verified inside its run; `--no-single-image` skips them) and `cpu_baseline` (the CPU oracle = port of the
+reference's SEAL path, timed on a bounded sample).  The whole --full line takes about a minute.
 """
 import argparse
 import json
@@ -412,6 +414,32 @@ def cifar_key_switch_block(g, ms_per_image, primes):
     return blk_
 
 
+def ntt_roofline(g, h):
+    """--full: the roofline of the dominant kernel - the batched N=8192 RNS NTT over the 845 ciphertexts of handle `h`, timed with HIP events
+    on the context's stream"""
+    limbs = 845 * 2 * g.k
+    ptr, _ = g.device_ptr(h)
+    g.ntt_time(ptr, limbs, 0, False, 2)
+    ms = g.ntt_time(ptr, limbs, 0, False, 20)
+    alg_bytes = limbs * g.n * 8 * 2                      # each limb read once + written once (SURVEY 8d: 128 KiB per N=8192 limb)
+    achieved = alg_bytes / (ms * 1e-3) / 1e9
+    # HBM bytes per launch: PMC counters cannot be read from inside this process (rocprofv3 wraps the command), so the figure is the one
+    # of the latest COMMITTED counter passes of this launch geometry (tools/pmc_traffic.sh: separate --pmc FETCH_SIZE / WRITE_SIZE runs) and
+    # is labelled with the file it comes from; null when no such file travels with the tree
+    traffic, traffic_source = None, None
+    try:
+        import glob
+        src = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_ntt_hbm_traffic.json")))[-1]
+        prof = json.load(open(src))
+        traffic = [v["hbm_traffic_corrected_bytes"] for kname, v in prof.items() if "k_ntt" in kname and "forward" in kname][0]
+        traffic_source = os.path.relpath(src, ROOT) + " (committed rocprofv3 --pmc passes of the same launch; not measured by this run)"
+    except Exception:
+        pass
+    return {"bound": "hbm", "kernel": "k_ntt_rr (forward, %d limbs of N=%d u64)" % (limbs, g.n), "achieved": round(achieved, 1),
+            "peak": 8000.0, "unit": "GB/s", "frac": round(achieved / 8000.0, 4), "traffic": traffic, "traffic_source": traffic_source,
+            "ms_per_launch": round(ms, 4), "bytes_per_launch": alg_bytes}
+
+
 def single_image_lines(gpu_index):
     """BASELINE configs 4 and 5 on the driver's line: `python bench.py --workload lola|cifar` run as child processes of the default
     workload (a process of their own: every plaintext-prime channel then gets a hardware queue of its own, cn_api.hip pick_stream) on the same GPU,
@@ -534,9 +562,9 @@ def stub_workload(args, rank, world, result_fd):
         shards = [None] * world                                                        # shard cover: every batch of the job on exactly one rank
         d.all_gather_object(shards, [int(b) for b in mine])
         cover = sorted(b for sh in shards for b in sh) == list(range(args.steps * world))
-    # what the real run does beside the timed region, and on which ranks: the CPU baseline, the single-image children and the unchanged caller are rank-0,
-    # world-1 work (main(): `rank == 0 and world == 1`) - at N > 1 no rank runs them, so the driver's SCALE lines time the sharded batches only
-    side = {"cpu_baseline": rank == 0 and world == 1, "single_image_children": rank == 0 and world == 1, "unchanged_caller": rank == 0 and world == 1}
+    # what the real run does beside the timed region, and on which ranks: the CPU baseline, the single-image children and the unchanged caller are --full,
+    # rank-0, world-1 work (main(): `args.full and rank == 0 and world == 1`) - at N > 1 no rank runs them, so a multi-GPU line times the sharded batches only
+    side = {k: bool(args.full) and rank == 0 and world == 1 for k in ("cpu_baseline", "single_image_children", "unchanged_caller")}
     if rank == 0:
         out = {"metric": "encrypted images/sec (CryptoNets-MNIST, N=8192)", "stub": True, "value": round(8192 * args.steps * world / dt, 1), "unit": "images/s",
                "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 2), "higher_is_better": True,
@@ -555,11 +583,15 @@ def main():
     ap.add_argument("--stub", action="store_true", help="launcher plumbing only (gloo, no device work): what the CPU test of `--gpus N` runs")
     ap.add_argument("--steps", type=_at_least(1), default=20, help="timed steps")
     ap.add_argument("--warmup", type=_at_least(0), default=3, help="untimed steps before them")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="default workload: after the timed steps also check every slot against the integer model and measure everything beside the headline "
+                         "(roofline, key_switch, square, unchanged caller, relinearize_late, CPU baseline, the lola / cifar lines); the --no-* switches below "
+                         "skip parts of it.  Off: the run sets up, warms up, times the steps, dumps (--dump-outputs) and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--weights", choices=("trained", "synthetic"), default="trained",
                     help="trained: the reference's CryptoNets/Weights.cs (shipped as package data); synthetic: random-init weights of the same shapes")
-    ap.add_argument("--no-relinearize-late", action="store_true", help="skip the opt-in program variant with Relinearize behind the dense layers")
-    ap.add_argument("--no-unchanged-caller", action="store_true", help="skip the per-ciphertext-call replay of the reference's unchanged layers")
+    ap.add_argument("--no-relinearize-late", action="store_true", help="--full: skip the opt-in program variant with Relinearize behind the dense layers")
+    ap.add_argument("--no-unchanged-caller", action="store_true", help="--full: skip the per-ciphertext-call replay of the reference's unchanged layers")
     ap.add_argument("--caller-threads", type=int, default=0, help="threads of the unchanged-caller replay; 0 = the processor count a runtime reports here "
                     "(cgroup CPU quota honoured) - the reference's Defaults.ThreadCount = Environment.ProcessorCount")
     ap.add_argument("--serialize", action="store_true", help="sync after every plaintext-prime channel (clean per-kernel profiles)")
@@ -572,7 +604,7 @@ def main():
     ap.add_argument("--shared-keys", action="store_true", help="lola / cifar, --shard images: ONE client's keys on every rank - rank 0 runs KeyGenerator, the relinearisation key, "
                     "every Galois key and the client keys are broadcast with RCCL and adopted in place (default: every rank is its own client)")
     ap.add_argument("--client-seed", type=int, default=None, help="lola / cifar: reproducible keys and encryption randomness (tests: two runs must give the same ciphertext words)")
-    ap.add_argument("--no-single-image", action="store_true", help="default workload: skip the LoLa-MNIST / LoLa-CIFAR sub-benchmarks (BASELINE configs 4 and 5) of the line")
+    ap.add_argument("--no-single-image", action="store_true", help="--full: skip the LoLa-MNIST / LoLa-CIFAR sub-benchmarks (BASELINE configs 4 and 5) of the line")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float64, rank 0): default workload - the 10 "
                          "logit ciphertexts and the decrypted logits of every plaintext prime; lola / cifar - the last image's result ciphertexts (lola: and their "
@@ -687,62 +719,45 @@ def main():
     dt = time.perf_counter() - t0
     dt = max_over_ranks(dt, torch.device("cuda", local), dist)
 
-    # ---- the measured run is checked: decrypt the logits on the device and compare ALL 8192 slots x 10 outputs per prime with the
-    # exact integer model of the network (same weights, same inputs); the digest of the final ciphertext words identifies the run
-    # (fixed key / encryption seeds: a run with the relinearisation key adopted from a broadcast buffer must give the same digest)
+    # ---- the digest of the final ciphertext words identifies the run (fixed key / encryption seeds: a run with the relinearisation key
+    # adopted from a broadcast buffer must give the same digest).  The logits are decrypted on the device only when something reads them:
+    # --dump-outputs, and the --full check of ALL 8192 slots x 10 outputs per prime against the exact integer model of the network
+    # (same weights, same inputs)
     import hashlib
     verified = True
     digest = hashlib.sha256()
     outputs = {}
+    dumping = bool(args.dump_outputs) and rank == 0
     for ch in chans:
         gg = ch.g
-        dh = gg.pt_alloc(10)
-        gg.decrypt(ch.h5, 0, 10, dh, 0)
-        got = np.ascontiguousarray(gg.decode_batch(dh, 0, 10).T)
-        gg.free(dh)
-        verified = verified and bool(np.array_equal(got, cm.model_mod_p_dense(x_int, layers, gg.t)))
         words = gg.ct_download(ch.h5, 0, 10)
         digest.update(words.tobytes())
         outputs["logit_ciphertexts_p%d" % gg.t] = words.reshape(10, 2, gg.k, gg.n)   # the 10 output ciphertexts of the batch ([poly][limb][N] words)
-        outputs["logits_mod_p%d" % gg.t] = got                    # (8192, 10): their decrypted slots, image by logit
-    if args.dump_outputs and rank == 0:                           # (before the sections below reuse the channels' buffers)
+        if args.full or dumping:
+            dh = gg.pt_alloc(10)
+            gg.decrypt(ch.h5, 0, 10, dh, 0)
+            got = np.ascontiguousarray(gg.decode_batch(dh, 0, 10).T)
+            gg.free(dh)
+            outputs["logits_mod_p%d" % gg.t] = got                # (8192, 10): their decrypted slots, image by logit
+            if args.full:
+                verified = verified and bool(np.array_equal(got, cm.model_mod_p_dense(x_int, layers, gg.t)))
+    if dumping:                                                   # (before the --full sections below reuse the channels' buffers)
         dump_outputs(args.dump_outputs, outputs)
+    g = chans[0].g
 
-    if dist is not None:                                  # every rank checked its own batch: report the conjunction
+    if args.full and dist is not None:                    # every rank checked its own batch: report the conjunction
         flag = torch.tensor([1 if verified else 0], dtype=torch.int32, device=dev)
         dist.all_reduce(flag, op=dist.ReduceOp.MIN)
         verified = bool(flag.item())
 
-    # ---- roofline of the dominant kernel: the batched N=8192 RNS NTT, timed with HIP events on the ctx stream
-    g = chans[0].g
-    limbs = 845 * 2 * g.k
-    ptr, _ = g.device_ptr(chans[0].h2)
-    g.ntt_time(ptr, limbs, 0, False, 2)
-    ms = g.ntt_time(ptr, limbs, 0, False, 20)
-    alg_bytes = limbs * g.n * 8 * 2                      # each limb read once + written once (128 KiB per N=8192 limb)
-    achieved = alg_bytes / (ms * 1e-3) / 1e9
-    # HBM bytes per launch: PMC counters cannot be read from inside this process (rocprofv3 wraps the command), so the figure is the one
-    # of the latest COMMITTED counter passes of this launch geometry (tools/visit_*.sh: separate --pmc FETCH_SIZE / WRITE_SIZE runs) and
-    # is labelled with the file it comes from; null when no such file travels with the tree
-    traffic, traffic_source = None, None
-    try:
-        import glob
-        src = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_ntt_hbm_traffic.json")))[-1]
-        prof = json.load(open(src))
-        traffic = [v["hbm_traffic_corrected_bytes"] for kname, v in prof.items() if "k_ntt" in kname and "forward" in kname][0]
-        traffic_source = os.path.relpath(src, ROOT) + " (committed rocprofv3 --pmc passes of the same launch; not measured by this run)"
-    except Exception:
-        pass
-    roofline = {"bound": "hbm", "kernel": "k_ntt_rr (forward, %d limbs of N=%d u64)" % (limbs, g.n), "achieved": round(achieved, 1),
-                "peak": 8000.0, "unit": "GB/s", "frac": round(achieved / 8000.0, 4), "traffic": traffic, "traffic_source": traffic_source,
-                "ms_per_launch": round(ms, 4), "bytes_per_launch": alg_bytes}
+    roofline = ntt_roofline(g, chans[0].h2) if args.full else None
 
     # ---- the kernel that takes the largest share of the batch (a third): the fused key switch of the first squaring layer, timed the same
     # way.  It is bound by FP64 issue, not by HBM: the ISA of the digit loop holds 1104 FP64 instructions per thread and digit (transform
     # + 2 x 16 multiply-accumulates), the two inverse transforms 1064 each, and the pipe issues one FP64 wave-instruction per 2.15 ns per
     # SIMD whatever the occupancy (profiles/r01_ubench_mulmod.txt); tools/ubench_ks.hip measures the arithmetic alone at the same 2.1 ms.
     key_switch = None
-    if rank == 0:
+    if args.full and rank == 0:
         cts = 845
         t3, t2 = g.ct_alloc(cts, 3), g.ct_alloc(cts)
         g.multiply(chans[0].h1, 0, chans[0].h1, 0, t3, 0, cts)           # the products the layer relinearises
@@ -788,7 +803,7 @@ def main():
     # kernels move by construction - extend R 2k W 2kb, squares R 2(k + kb) W 3(k + kb), floor R 3(k + kb) W 3k).  The per-kernel split of the same
     # launches is in profiles/r04_bench_kernel_trace_summary.txt.
     square = None
-    if rank == 0:
+    if args.full and rank == 0:
         try:
             cts = 845
             t3 = g.ct_alloc(cts, 3)
@@ -827,7 +842,7 @@ def main():
     # evaluator calls) - from Defaults.ThreadCount = all host cores (Defaults.cs), every decrypted slot checked against the integer model.
     # `skipped_taps`: padded taps passed as "no ciphertext" (what the batched path does): its final WORDS must equal the batched run's.
     unchanged = None
-    if rank == 0 and world == 1 and not args.no_unchanged_caller:
+    if args.full and rank == 0 and world == 1 and not args.no_unchanged_caller:
         try:
             sys.path.insert(0, os.path.join(ROOT, "tools"))
             import replay_reference_calls as rp
@@ -899,7 +914,7 @@ def main():
     # (CryptoNetsChannel.forward_relinearize_late: the squarings leave size-3 products, Evaluator.MultiplyPlain / Add run on them, 110 key
     # switches per channel instead of 945).  Same SEAL operations on the same kernels, every slot checked against the integer model.
     late = None
-    if rank == 0 and world == 1 and not args.no_relinearize_late:
+    if args.full and rank == 0 and world == 1 and not args.no_relinearize_late:
         try:
             for _ in range(2):
                 for ch in chans:
@@ -930,7 +945,7 @@ def main():
                "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 2),
                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u64",
                "data": "synthetic images" + (", the reference's trained weights (CryptoNets/Weights.cs)" if args.weights == "trained" else ", synthetic weights"),
-               "verified_against_integer_model": verified, "verified_slots": 8192 * 10 * len(chans), "logit_words_sha256": digest.hexdigest(),
+               "logit_words_sha256": digest.hexdigest(), "full": bool(args.full),
                "launcher": os.environ.get("BENCH_LAUNCHER", "external" if "WORLD_SIZE" in os.environ else "none"), "process_group": "nccl" if dist is not None else None,
                "config": {"workload": "CryptoNets-MNIST 5-layer (conv 5x5 s2 x5 maps, square, dense 845->100, square, dense 100->10), "
                                       "8192-image batch per GPU per step, N=8192, 5 RNS limbs, plaintext primes {549764251649, 549764284417}, "
@@ -944,19 +959,21 @@ def main():
                           "arithmetic": "exact modular integers over 43-49-bit RNS primes (results are u64 words, bit-identical to the integer "
                                         "oracle); products evaluated with error-free FP64 instruction sequences where the modulus is below 2^49, "
                                         "64-bit integer instructions otherwise"},
-               # the figure for the reference's LITERAL call sequence (padded taps as fresh encryptions of zero, one call per ciphertext from Defaults.ThreadCount threads), next to `value`
-               "literal_call_sequence": ({"value": unchanged.get("value"), "unit": "images/s", "ms_per_step": unchanged.get("ms_per_step"), "frac_of_value_program": unchanged.get("frac_of_batched"),
-                                          "verified_against_integer_model": unchanged.get("verified_against_integer_model")} if isinstance(unchanged, dict) and "value" in unchanged else None),
-               "roofline": roofline, "key_switch": key_switch, "square": square, "unchanged_caller": unchanged, "relinearize_late": late,
                # the WHOLE batch against HBM (inputs read once + outputs written once per layer, 640 KiB per ciphertext, per prime:
                # conv (784+845), square 845 x 2, dense (845+100), square 100 x 2, dense (100+10)): the path is FP64-issue bound, not HBM bound
                "batch_hbm": (lambda nbytes: {"algorithmic_bytes_per_step": nbytes, "achieved": round(nbytes / (dt / args.steps) / 1e9, 1), "peak": 8000.0,
                                              "unit": "GB/s", "frac": round(nbytes / (dt / args.steps) / 8e12, 4)})(
                    2 * (784 + 845 + 2 * 845 + 845 + 100 + 2 * 100 + 100 + 10) * 2 * g.k * g.n * 8)}
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(effective_cores()[0], layers)
-        if world == 1 and not args.no_single_image:
-            out["lola"], out["cifar"] = single_image_lines(local)
+        if args.full:
+            out.update({"verified_against_integer_model": verified, "verified_slots": 8192 * 10 * len(chans),
+                        # the figure for the reference's LITERAL call sequence (padded taps as fresh encryptions of zero, one call per ciphertext from Defaults.ThreadCount threads), next to `value`
+                        "literal_call_sequence": ({"value": unchanged.get("value"), "unit": "images/s", "ms_per_step": unchanged.get("ms_per_step"), "frac_of_value_program": unchanged.get("frac_of_batched"),
+                                                   "verified_against_integer_model": unchanged.get("verified_against_integer_model")} if isinstance(unchanged, dict) and "value" in unchanged else None),
+                        "roofline": roofline, "key_switch": key_switch, "square": square, "unchanged_caller": unchanged, "relinearize_late": late})
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(effective_cores()[0], layers)
+            if world == 1 and not args.no_single_image:
+                out["lola"], out["cifar"] = single_image_lines(local)
         os.write(result_fd, (json.dumps(out) + "\n").encode())
     if dist is not None:
         dist.barrier()

@@ -60,3 +60,14 @@ def test_gpus_8_stub_covers_every_shard_once():
     assert line["n_gpus"] == 8 and line["plumbing_ok"] is True and line["shard_cover_ok"] is True
     assert line["ms_per_step"] >= 79.0, line
     assert not any(line["rank0_side_work"].values())
+
+
+def test_side_work_of_the_line_runs_only_with_full():
+    """a plain run does the timed steps and nothing else: the CPU baseline, the single-image children and the unchanged caller of the N = 1 line
+    run only under --full"""
+    for extra, want in (((), False), (("--full",), True)):
+        r = subprocess.run([sys.executable, BENCH, "--steps", "1", "--warmup", "0", "--stub", *extra], env=_env(), stdout=subprocess.PIPE,
+                           stderr=subprocess.PIPE, timeout=300)
+        assert r.returncode == 0, r.stderr.decode()[-2000:]
+        side = _one_line(r.stdout)["rank0_side_work"]
+        assert set(side) == {"cpu_baseline", "single_image_children", "unchanged_caller"} and all(v is want for v in side.values()), (extra, side)

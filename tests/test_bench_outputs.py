@@ -59,7 +59,7 @@ def test_steps_below_one_are_refused(steps):
 @pytest.mark.gpu
 def test_dump_of_the_cryptonets_batch(tmp_path):
     d = str(tmp_path / "out")
-    line = _run("--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-unchanged-caller", "--no-single-image", "--no-relinearize-late",
+    line = _run("--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-unchanged-caller", "--no-single-image", "--no-relinearize-late",
                 "--dump-outputs", d)
     assert line["steps"] == 2 and line["verified_against_integer_model"] is True
     got = _load(d)
@@ -72,6 +72,23 @@ def test_dump_of_the_cryptonets_batch(tmp_path):
         assert logits.min() >= 0 and logits.max() < p and np.array_equal(logits, np.rint(logits))
         digest.update(ct.astype(np.uint64).tobytes())
     assert digest.hexdigest() == line["logit_words_sha256"]
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_what_the_full_run_verifies(tmp_path):
+    """without --full the line carries the headline alone (no check, no side measurement), and the run computes and dumps what a --full run
+    of the same arguments computes and checks against the integer model"""
+    plain = _run("--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "plain"))
+    full = _run("--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-unchanged-caller", "--no-single-image", "--no-relinearize-late",
+                "--dump-outputs", str(tmp_path / "full"))
+    assert plain["full"] is False and full["full"] is True and full["verified_against_integer_model"] is True
+    assert not {"verified_against_integer_model", "roofline", "key_switch", "square", "unchanged_caller", "relinearize_late", "cpu_baseline",
+                "lola", "cifar"} & set(plain), sorted(plain)
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup", "logit_words_sha256"):
+        assert plain[k] == full[k], k
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0
+    a, b = _load(str(tmp_path / "plain")), _load(str(tmp_path / "full"))
+    assert set(a) == set(b) and all(np.array_equal(a[k], b[k]) for k in a)
 
 
 @pytest.mark.gpu

@@ -158,8 +158,8 @@ def _bench(extra_env, *args):
 def test_bench_with_the_process_group_forced_equals_the_plain_run():
     """bench.py at world 1 with the RCCL process group created anyway: the relinearisation key travels through dist.broadcast and is adopted
     from the broadcast buffer (cn_set_relin_key(..., is_device_ptr=1)).  Same seeds -> the final ciphertext words must be the plain run's."""
-    plain = _bench({})
-    forced = _bench({"BENCH_FORCE_DIST": "1", "MASTER_PORT": "29547"})
+    plain = _bench({}, "--full")
+    forced = _bench({"BENCH_FORCE_DIST": "1", "MASTER_PORT": "29547"}, "--full")
     for line in (plain, forced):
         assert line["n_gpus"] == 1 and line["verified_against_integer_model"] is True and line["verified_slots"] == 2 * 8192 * 10
         assert line["roofline"]["frac"] > 0.2 and line["metric"].startswith("encrypted images/sec")
@@ -191,7 +191,7 @@ def test_single_image_bench_with_one_clients_keys_broadcast(workload):
 def test_bench_gpus_flag_launches_ranks_on_the_gpu_box():
     """`bench.py --gpus 1` under its own torchrun launcher (BENCH_SELF_LAUNCH=1 forces the re-exec at N = 1): the N > 1 command line, rendezvous
     and RCCL initialisation executed for real on the device that is here"""
-    line = _bench({"BENCH_SELF_LAUNCH": "1"}, "--gpus", "1")
+    line = _bench({"BENCH_SELF_LAUNCH": "1"}, "--gpus", "1", "--full")
     assert line["n_gpus"] == 1 and line["verified_against_integer_model"] is True
     assert line["launcher"] == "self (torch.distributed.run)" and line["process_group"] == "nccl"
 

@@ -4,7 +4,7 @@ OUT=gpurun_out/quick
 mkdir -p $OUT
 timeout 1500 python -m pytest tests -m gpu -x -q > $OUT/pytest.txt 2>&1
 tail -4 $OUT/pytest.txt
-python bench.py --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err
 cut -c1-230 $OUT/bench.json
 export TMPDIR=/tmp
 R=$PWD

@@ -27,6 +27,6 @@ for m in (0, 1, 2):
 PY
 find $OUT -name "*kernel_trace.csv" -delete
 for m in 0 1 2; do
-  CN_KS_XCD=$m timeout 300 python bench.py --no-cpu-baseline --no-unchanged-caller --steps 10 --warmup 2 > $OUT/bench_m$m.json 2>/dev/null
+  CN_KS_XCD=$m timeout 300 python bench.py --full --no-cpu-baseline --no-unchanged-caller --steps 10 --warmup 2 > $OUT/bench_m$m.json 2>/dev/null
   python -c "import json; d=json.load(open('$OUT/bench_m$m.json')); print('CN_KS_XCD=$m bench', d['value'], d['ms_per_step'], 'key switch', d['key_switch']['ms_per_launch'], d['verified_against_integer_model'])"
 done
