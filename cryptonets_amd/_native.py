@@ -165,6 +165,7 @@ SIGNATURES = {
     "cn_graph_begin": (C.c_int, [_CTX]),
     "cn_graph_end": (C.c_int, [_CTX, C.POINTER(_H)]),
     "cn_graph_launch": (C.c_int, [_CTX, _H]),
+    "cn_graph_begin_levels": (C.c_int, [_CTX, C.POINTER(_CTX), _u32]),
     "cn_multiply": (C.c_int, [_CTX, _H, _u32, _H, _u32, _H, _u32, _u32]),
     "cn_relinearize": (C.c_int, [_CTX, _H, _u32, _H, _u32, _u32]),
     "cn_mul_relin": (C.c_int, [_CTX, _H, _u32, _u32, _H, _u32, _u32, _H, _u32, _u32]),
@@ -306,8 +307,9 @@ class Context:
         return v.value
 
     def close(self):
+        """release the context.  A member of a live graph recorded across levels (graph_begin(levels=...)) is refused and stays open: free the graph first"""
         if self._h is not None:
-            self.L.cn_ctx_destroy(self._h)
+            self._chk(self.L.cn_ctx_destroy(self._h))
             self._h = None
 
     def __del__(self):
@@ -665,8 +667,15 @@ class Context:
         return self.L.cn_stream(self._h)
 
     # ---- captured sequences (HIP graphs): see include/cnhip.h
-    def graph_begin(self):
-        self._chk(self.L.cn_graph_begin(self._h))
+    def graph_begin(self, levels=()):
+        """start recording; `levels`: level contexts of this context's chain the recording also covers (cn_graph_begin_levels) - their calls
+        and the cn_mod_switch calls between them and this context are recorded into the one graph graph_end returns"""
+        levels = list(levels)
+        if not levels:
+            self._chk(self.L.cn_graph_begin(self._h))
+            return
+        arr = (_CTX * len(levels))(*[c._h for c in levels])
+        self._chk(self.L.cn_graph_begin_levels(self._h, arr, len(levels)))
 
     def graph_end(self):
         h = _H()

@@ -297,6 +297,11 @@ int ctx_init(cn_ctx *c, uint32_t n, uint32_t k, int device, std::vector<uint64_t
 }
 extern "C" int cn_ctx_destroy(cn_ctx *ctx) {
     if (!ctx) return 0;
+    {   // a member of a recording across levels, or of a live graph recorded so, keeps its arrays in that graph: refused, nothing freed
+        CnGuard lk(ctx->mu);
+        if ((ctx->cap_root && ctx->cap_root != ctx) || ctx->member_graphs)
+            return fail(CN_ERR_ARG, "cn_ctx_destroy: the context is a member of a recording or of a live graph of another context (cn_graph_begin_levels): free the graph first");
+    }
     {
         std::lock_guard<std::mutex> reg(g_ctx_reg_mu);
         g_ctx_reg.erase(std::remove(g_ctx_reg.begin(), g_ctx_reg.end(), ctx), g_ctx_reg.end());
@@ -311,7 +316,11 @@ void ctx_teardown(cn_ctx *ctx) {
     if (ctx->stream) {   // queued per-ciphertext calls are launched (their results die with the context, but the arrays parked behind them - cn_free while
         // calls were pending - go back to the pool and are released with it)
         CnGuard lk(ctx->mu);
-        if (ctx->capturing) { hipGraph_t g = nullptr; (void)hipStreamEndCapture(ctx->stream, &g); if (g) (void)hipGraphDestroy(g); ctx->capturing = false; }
+        if (ctx->capturing) {
+            HeldLocks members(ctx->cap_members);
+            hipGraph_t g = nullptr; (void)hipStreamEndCapture(ctx->stream, &g); if (g) (void)hipGraphDestroy(g);
+            end_recording(ctx);
+        }
         (void)ring_sync(ctx, false);
         (void)cn_defer_flush(ctx);
     }
@@ -332,6 +341,7 @@ void ctx_teardown(cn_ctx *ctx) {
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     if (ctx->ev_order) (void)hipEventDestroy(ctx->ev_order);
     if (ctx->ev_ms) (void)hipEventDestroy(ctx->ev_ms);
+    if (ctx->ev_graph) (void)hipEventDestroy(ctx->ev_graph);
     if (ctx->stream2) { (void)hipStreamSynchronize(ctx->stream2); (void)hipStreamDestroy(ctx->stream2); }
     if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
     if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
@@ -384,6 +394,7 @@ extern "C" int cn_get_option(cn_ctx *ctx, const char *name, int *value) { API_BO
     else if (!strcmp(name, "mod_switch_f64")) *value = ctx->ms_f64;                     // the last cn_mod_switch on this context ran in FP64
     else if (!strcmp(name, "aux_primes")) *value = (int)ctx->hc.kb;
     else if (!strcmp(name, "pending_calls")) *value = (int)ctx->dq->ops.size();
+    else if (!strcmp(name, "pool_arrays")) { size_t c = 0; for (auto &kv : ctx->pool) c += kv.second.size(); *value = (int)std::min<size_t>(c, 0x7fffffff); }   // cached arrays (a graph reserves its temporaries out of the pool)
     else if (!strcmp(name, "stream_tries")) *value = ctx->stream_tries;           // streams created until one had a hardware queue of its own (< 0: none had)
     else return fail(CN_ERR_ARG, "unknown option %s", name);
     return 0;
@@ -589,12 +600,46 @@ int free_many_body(cn_ctx *ctx, const cn_handle *h, uint32_t n) {
 // the handle pool and the scratch arenas have their size), nothing may synchronise (cn_sync, uploads / downloads of handles, key
 // changes) between begin and end, and the handles created while recording must stay alive as long as the graph is launched - the
 // kernels carry their addresses.  New inputs go INTO the handles the recorded sequence read (cn_copy / cn_encrypt on them).
+// ---- recording across levels (cn_graph_begin_levels, cn_level.hip): the members' calls are recorded on the root's stream (one linear graph); each member's
+// temporaries stay reserved out of its own pool, and the member counts the graph as alive (its scratch arenas must not move either)
+thread_local std::vector<const cn_ctx *> tl_held;
+HeldLocks::HeldLocks(const std::vector<cn_ctx *> &ctxs) {
+    for (cn_ctx *c : ctxs) { g.emplace_back(new CnGuard(c->mu)); tl_held.push_back(c); }
+}
+HeldLocks::~HeldLocks() {
+    for (size_t i = g.size(); i-- > 0;) tl_held.pop_back();
+    while (!g.empty()) g.pop_back();
+}
+bool HeldLocks::here(const cn_ctx *c) { return std::find(tl_held.begin(), tl_held.end(), c) != tl_held.end(); }
+// the root and its members stop recording: every member gets its stream back (caller holds every lock, the capture has ended)
+void end_recording(cn_ctx *root) {
+    for (cn_ctx *m : root->cap_members) { m->stream = m->own_stream; m->own_stream = nullptr; m->cap_root = nullptr; m->capturing = false; }
+    root->cap_members.clear(); root->cap_root = nullptr; root->capturing = false;
+}
+// arrays handed out to c while recording that are back in its pool now (temporaries): reserved for the graph
+static void reserve_temporaries(cn_ctx *c, std::vector<std::pair<uint64_t *, size_t>> &reserved) {
+    for (auto &a : c->cap_allocs) {
+        auto it = c->pool.find(a.second);
+        if (it == c->pool.end()) continue;
+        auto pos = std::find(it->second.begin(), it->second.end(), a.first);
+        if (pos == it->second.end()) continue;                  // owned by a live handle (an output of the sequence)
+        it->second.erase(pos); c->pool_bytes -= a.second;
+        reserved.push_back(a);
+    }
+    c->cap_allocs.clear();
+}
 int free_graph(cn_ctx *ctx, Buffer &b) {
     if (!b.cg) return 0;
     HIPCHK(hipStreamSynchronize(ctx->stream));
     if (b.cg->exec) (void)hipGraphExecDestroy(b.cg->exec);
     if (b.cg->graph) (void)hipGraphDestroy(b.cg->graph);
     for (auto &r : b.cg->reserved) { ctx->pool[r.second].push_back(r.first); ctx->pool_bytes += r.second; }
+    for (auto &m : b.cg->members) {                            // (the root's lock is held; a member's is taken after it, unless this thread holds it already)
+        std::unique_ptr<CnGuard> lk;
+        if (!HeldLocks::here(m.ctx)) lk.reset(new CnGuard(m.ctx->mu));
+        for (auto &r : m.reserved) { m.ctx->pool[r.second].push_back(r.first); m.ctx->pool_bytes += r.second; }
+        m.ctx->graphs_alive--; m.ctx->member_graphs--;
+    }
     b.cg.reset();
     ctx->graphs_alive--;
     return 0;
@@ -608,39 +653,67 @@ extern "C" int cn_graph_begin(cn_ctx *ctx) { API_BODY
 API_END }
 extern "C" int cn_graph_end(cn_ctx *ctx, cn_handle *graph) { API_BODY
     LOCK;
+    if (ctx->cap_root && ctx->cap_root != ctx) return fail(CN_ERR_ARG, "cn_graph_end on a member of a recording across levels: end it on its root");
     if (!ctx->capturing) return fail(CN_ERR_ARG, "cn_graph_end without cn_graph_begin");
-    ctx->capturing = false;
+    const std::vector<cn_ctx *> members = ctx->cap_members;     // (the root's lock is held: the members' are taken after it, in lock order)
+    HeldLocks locks(members);
+    std::vector<cn_ctx *> all(1, ctx);
+    all.insert(all.end(), members.begin(), members.end());
+    const auto drop = [&]() { for (cn_ctx *c : all) { c->cap_staged.clear(); c->cap_allocs.clear(); } };
     std::shared_ptr<CapturedGraph> g = std::make_shared<CapturedGraph>();
     hipError_t e = hipStreamEndCapture(ctx->stream, &g->graph);
-    if (e != hipSuccess || !g->graph) { (void)hipGetLastError(); ctx->cap_staged.clear(); ctx->cap_allocs.clear(); return fail(CN_ERR_HIP, "graph capture failed: %s", hipGetErrorString(e)); }
+    if (members.empty()) ctx->capturing = false; else end_recording(ctx);
+    if (e != hipSuccess || !g->graph) { (void)hipGetLastError(); drop(); return fail(CN_ERR_HIP, "graph capture failed: %s", hipGetErrorString(e)); }
     if (!graph) {                                              // nowhere to put the handle: drop the recording (nothing was reserved yet)
-        (void)hipGraphDestroy(g->graph); ctx->cap_staged.clear(); ctx->cap_allocs.clear();
+        (void)hipGraphDestroy(g->graph); drop();
         return fail(CN_ERR_ARG, "null argument");
     }
     e = hipGraphInstantiate(&g->exec, g->graph, nullptr, nullptr, 0);
-    if (e != hipSuccess) { (void)hipGetLastError(); (void)hipGraphDestroy(g->graph); ctx->cap_staged.clear(); ctx->cap_allocs.clear(); return fail(CN_ERR_HIP, "graph instantiation failed: %s", hipGetErrorString(e)); }
-    g->staged = std::move(ctx->cap_staged); ctx->cap_staged.clear();
-    // arrays handed out while recording that are back in the pool now (temporaries): reserve them for the graph
-    for (auto &a : ctx->cap_allocs) {
-        auto it = ctx->pool.find(a.second);
-        if (it == ctx->pool.end()) continue;
-        auto pos = std::find(it->second.begin(), it->second.end(), a.first);
-        if (pos == it->second.end()) continue;                  // owned by a live handle (an output of the sequence)
-        it->second.erase(pos); ctx->pool_bytes -= a.second;
-        g->reserved.push_back(a);
+    if (e != hipSuccess) { (void)hipGetLastError(); (void)hipGraphDestroy(g->graph); drop(); return fail(CN_ERR_HIP, "graph instantiation failed: %s", hipGetErrorString(e)); }
+    for (cn_ctx *c : all) {
+        for (auto &blk : c->cap_staged) g->staged.push_back(std::move(blk));
+        c->cap_staged.clear();
     }
-    ctx->cap_allocs.clear();
+    reserve_temporaries(ctx, g->reserved);
+    for (cn_ctx *m : members) {
+        g->members.push_back({m, {}});
+        reserve_temporaries(m, g->members.back().reserved);
+        m->graphs_alive++; m->member_graphs++;
+    }
     Buffer b; b.kind = 3; b.count = 0; b.size = 0; b.d = nullptr; b.item_words = 0; b.cg = g;
     ctx->graphs_alive++;
     *graph = ctx->bufs.insert(std::move(b));
     return 0;
 API_END }
+// A graph recorded across levels is ordered against its members' streams without a host wait: the replay starts behind the work submitted to every
+// member, and every member's later work starts behind the replay.  A graph without members launches alone.
 extern "C" int cn_graph_launch(cn_ctx *ctx, cn_handle graph) { API_BODY
     LOCK; NOT_CAPTURING("cn_graph_launch");
     Buffer *b = getbuf(ctx, graph, 3);
     if (!b || !b->cg) return fail(CN_ERR_ARG, "invalid graph handle");
+    if (b->cg->members.empty()) {
+        HIPCHK(hipGraphLaunch(b->cg->exec, ctx->stream));
+        ctx->st.kernel_launches += 1;
+        return 0;
+    }
+    std::vector<cn_ctx *> members;
+    for (const auto &m : b->cg->members) members.push_back(m.ctx);
+    HeldLocks locks(members);
+    for (cn_ctx *m : members) {
+        if (m->capturing) return fail(CN_ERR_ARG, "cn_graph_launch: a level context of this graph is recording (cn_graph_begin .. cn_graph_end)");
+        CHECK(flush_all(m));
+    }
+    CHECK(use(ctx));
+    for (cn_ctx *m : members) {
+        if (!m->ev_graph) HIPCHK(hipEventCreateWithFlags(&m->ev_graph, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(m->ev_graph, m->stream));
+        HIPCHK(hipStreamWaitEvent(ctx->stream, m->ev_graph, 0));
+    }
     HIPCHK(hipGraphLaunch(b->cg->exec, ctx->stream));
     ctx->st.kernel_launches += 1;
+    if (!ctx->ev_graph) HIPCHK(hipEventCreateWithFlags(&ctx->ev_graph, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(ctx->ev_graph, ctx->stream));
+    for (cn_ctx *m : members) HIPCHK(hipStreamWaitEvent(m->stream, ctx->ev_graph, 0));
     return 0;
 API_END }
 extern "C" int cn_live_handles(cn_ctx *ctx) { CnGuard lk(ctx->mu); (void)ring_sync(ctx, false); return (int)ctx->bufs.size() - (int)ctx->ready->size(); }   // (ready handles belong to nobody yet)

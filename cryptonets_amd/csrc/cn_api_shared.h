@@ -130,6 +130,7 @@ bool submit_async(const cn_ctx *ctx);
 int free_body(cn_ctx *ctx, cn_handle h);
 int free_many_body(cn_ctx *ctx, const cn_handle *h, uint32_t n);
 int free_graph(cn_ctx *ctx, Buffer &b);
+void end_recording(cn_ctx *root);
 int ensure_index_map(cn_ctx *ctx);
 int addsub(cn_ctx *ctx, cn_handle a, uint32_t ai, cn_handle b, uint32_t bi, cn_handle out, uint32_t oi, uint32_t count, int op);
 int addsub_body(cn_ctx *ctx, cn_handle a, uint32_t ai, cn_handle b, uint32_t bi, cn_handle out, uint32_t oi, uint32_t count, int op);
@@ -280,6 +281,19 @@ int raw_ntt(cn_ctx *ctx, void *p, uint32_t limbs, int base, int inverse);
     case 1: fn<1>(__VA_ARGS__); break; case 2: fn<2>(__VA_ARGS__); break; case 3: fn<3>(__VA_ARGS__); break; case 4: fn<4>(__VA_ARGS__); break; \
     case 5: fn<5>(__VA_ARGS__); break; case 6: fn<6>(__VA_ARGS__); break; case 7: fn<7>(__VA_ARGS__); break; case 8: fn<8>(__VA_ARGS__); break; \
     case 9: fn<9>(__VA_ARGS__); break; default: return fail(CN_ERR_ARG, "at most 9 coefficient moduli"); }
+
+// The context locks one call holds besides its own (cn_mod_switch, the recordings across levels): taken in the given order and noted per thread, so that
+// a graph released from inside such a call (a release executed from the lock-free ring) hands its members' arrays back without taking a lock twice.
+struct HeldLocks {
+    explicit HeldLocks(const std::vector<cn_ctx *> &ctxs);
+    ~HeldLocks();
+    static bool here(const cn_ctx *c);         // does this thread hold c's lock through a HeldLocks?
+    HeldLocks(const HeldLocks &) = delete;
+    HeldLocks &operator=(const HeldLocks &) = delete;
+private:
+    std::vector<std::unique_ptr<CnGuard>> g;
+};
+int flush_all(cn_ctx *ctx);
 
 template <class T> static T *salloc(cn_ctx *c, size_t count) {
     size_t b = al(count * sizeof(T));

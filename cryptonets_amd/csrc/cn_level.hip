@@ -64,18 +64,26 @@ extern "C" int cn_ctx_create_level(cn_ctx *parent, uint32_t limbs, cn_ctx **out)
 }
 
 // ---------------------------------------------------------------- cn_mod_switch
-static int flush_all(cn_ctx *ctx) { CHECK(use(ctx)); CHECK(ring_sync(ctx, true)); return cn_defer_flush(ctx); }
-static int mod_switch_locked(cn_ctx *src, cn_handle in, uint32_t ii, uint32_t count, cn_ctx *dst, cn_handle out, uint32_t oi) {
-    {   cn_ctx *ctx = src; NOT_CAPTURING("cn_mod_switch"); }
-    {   cn_ctx *ctx = dst; NOT_CAPTURING("cn_mod_switch"); }
+int flush_all(cn_ctx *ctx) { CHECK(use(ctx)); CHECK(ring_sync(ctx, true)); return cn_defer_flush(ctx); }
+// may a ciphertext of src be switched down to dst?  (cn_mod_switch; the members of a recording across levels, cn_graph_begin_levels)
+static int chain_check(const cn_ctx *src, const cn_ctx *dst, const char *what) {
     const DevConsts &a = src->hc, &b = dst->hc;
-    if (src->device != dst->device) return fail(CN_ERR_ARG, "cn_mod_switch: the target context is on another device");
-    if (a.n != b.n || a.t.q != b.t.q) return fail(CN_ERR_ARG, "cn_mod_switch: the target context has another N or t");
-    if (b.k >= a.k) return fail(CN_ERR_ARG, "cn_mod_switch: the target keeps %u of the source's %u coefficient moduli (must be fewer)", b.k, a.k);
-    for (uint32_t j = 0; j < b.k; j++) if (a.q[j].q != b.q[j].q) return fail(CN_ERR_ARG, "cn_mod_switch: the target's coefficient modulus is not a prefix of the source's");
-    if (a.ks_xi != b.ks_xi) return fail(CN_ERR_ARG, "cn_mod_switch: the contexts use different key-switch conventions (ks_xi)");
+    if (src->device != dst->device) return fail(CN_ERR_ARG, "%s: the target context is on another device", what);
+    if (a.n != b.n || a.t.q != b.t.q) return fail(CN_ERR_ARG, "%s: the target context has another N or t", what);
+    if (b.k >= a.k) return fail(CN_ERR_ARG, "%s: the target keeps %u of the source's %u coefficient moduli (must be fewer)", what, b.k, a.k);
+    for (uint32_t j = 0; j < b.k; j++) if (a.q[j].q != b.q[j].q) return fail(CN_ERR_ARG, "%s: the target's coefficient modulus is not a prefix of the source's", what);
+    if (a.ks_xi != b.ks_xi) return fail(CN_ERR_ARG, "%s: the contexts use different key-switch conventions (ks_xi)", what);
     if (a.ks_xi) for (uint32_t j = 0; j < b.k; j++) if (a.ks_inv_qhat_q[j] != b.ks_inv_qhat_q[j])
-        return fail(CN_ERR_ARG, "cn_mod_switch: under ks_xi = 1 the target must be a level of the source's chain (cn_ctx_create_level)");
+        return fail(CN_ERR_ARG, "%s: under ks_xi = 1 the target must be a level of the source's chain (cn_ctx_create_level)", what);
+    return 0;
+}
+static int mod_switch_locked(cn_ctx *src, cn_handle in, uint32_t ii, uint32_t count, cn_ctx *dst, cn_handle out, uint32_t oi) {
+    // while a graph is recorded, only a switch between two contexts of one recording across levels is possible (it is recorded like any call)
+    if ((src->capturing || dst->capturing) && !(src->cap_root && src->cap_root == dst->cap_root)) {
+        cn_ctx *ctx = src->capturing ? src : dst; NOT_CAPTURING("cn_mod_switch (other than between the contexts of one cn_graph_begin_levels)");
+    }
+    CHECK(chain_check(src, dst, "cn_mod_switch"));
+    const DevConsts &a = src->hc, &b = dst->hc;
     // not deferrable: both contexts' queued calls and published records are submitted first (a handle may come from the lock-free ring)
     {   cn_ctx *ctx = src; CHECK(flush_all(ctx)); }
     {   cn_ctx *ctx = dst; CHECK(flush_all(ctx)); }
@@ -90,15 +98,21 @@ static int mod_switch_locked(cn_ctx *src, cn_handle in, uint32_t ii, uint32_t co
     if (!count) return 0;
     // ordering without a host wait: dst's stream waits for everything submitted to src (the writers of `in`), runs the switch behind its own earlier
     // work (the readers and writers of `out`), and src's stream waits for the switch (later writers of `in`)
-    if (!src->ev_ms) HIPCHK(hipEventCreateWithFlags(&src->ev_ms, hipEventDisableTiming));
-    if (!dst->ev_ms) HIPCHK(hipEventCreateWithFlags(&dst->ev_ms, hipEventDisableTiming));
-    HIPCHK(hipEventRecord(src->ev_ms, src->stream));
-    HIPCHK(hipStreamWaitEvent(dst->stream, src->ev_ms, 0));
+    // (two contexts of one recording share the root's stream: stream order is enough, and the recorded graph stays one chain)
+    const bool one_stream = src->stream == dst->stream;
+    if (!one_stream) {
+        if (!src->ev_ms) HIPCHK(hipEventCreateWithFlags(&src->ev_ms, hipEventDisableTiming));
+        if (!dst->ev_ms) HIPCHK(hipEventCreateWithFlags(&dst->ev_ms, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(src->ev_ms, src->stream));
+        HIPCHK(hipStreamWaitEvent(dst->stream, src->ev_ms, 0));
+    }
     CHECK(cn_l_mod_switch(dst, I->d + (size_t)ii * I->item_words, O->d + (size_t)oi * O->item_words, src->dc, a.k, b.k, count * I->size, a.logn,
                           f64, &ran_f64));
     src->ms_f64 = dst->ms_f64 = ran_f64;
-    HIPCHK(hipEventRecord(dst->ev_ms, dst->stream));
-    HIPCHK(hipStreamWaitEvent(src->stream, dst->ev_ms, 0));
+    if (!one_stream) {
+        HIPCHK(hipEventRecord(dst->ev_ms, dst->stream));
+        HIPCHK(hipStreamWaitEvent(src->stream, dst->ev_ms, 0));
+    }
     return 0;
 }
 extern "C" int cn_mod_switch(cn_ctx *src, cn_handle in, uint32_t ii, uint32_t count, cn_ctx *dst, cn_handle out, uint32_t oi) {
@@ -107,7 +121,45 @@ extern "C" int cn_mod_switch(cn_ctx *src, cn_handle in, uint32_t ii, uint32_t co
     // both locks, in chain order (more limbs first): two switches along one chain cannot deadlock
     cn_ctx *first = src->hc.k >= dst->hc.k ? src : dst, *second = first == src ? dst : src;
     if (first->hc.k == second->hc.k && first > second) std::swap(first, second);
-    CnGuard g1(first->mu);
-    CnGuard g2(second->mu);
+    HeldLocks locks({first, second});
     return mod_switch_locked(src, in, ii, count, dst, out, oi);
+}
+
+// ---------------------------------------------------------------- recording across levels
+// the contexts of a recording group in lock order: more limbs first, as cn_mod_switch takes two of them (equal limbs: lower address first)
+static bool lock_order(const cn_ctx *x, const cn_ctx *y) { return x->hc.k != y->hc.k ? x->hc.k > y->hc.k : x < y; }
+static int graph_begin_levels_locked(cn_ctx *root, const std::vector<cn_ctx *> &members) {
+    {   cn_ctx *ctx = root; NOT_CAPTURING("cn_graph_begin_levels"); }
+    for (cn_ctx *m : members) {
+        if (m->capturing) return fail(CN_ERR_ARG, "cn_graph_begin_levels: a member context is already recording or a member of another recording");
+        CHECK(chain_check(root, m, "cn_graph_begin_levels"));
+    }
+    // queued calls and published records of every context are submitted first (on their own streams)
+    {   cn_ctx *ctx = root; CHECK(flush_all(ctx)); }
+    for (cn_ctx *m : members) { cn_ctx *ctx = m; CHECK(flush_all(ctx)); }
+    CHECK(use(root));
+    for (cn_ctx *c : members) { c->cap_staged.clear(); c->cap_allocs.clear(); }
+    root->cap_staged.clear(); root->cap_allocs.clear();
+    HIPCHK(hipStreamBeginCapture(root->stream, hipStreamCaptureModeRelaxed));
+    // every member launches on the root's capture stream until cn_graph_end (its own stream does not join the capture: one linear chain)
+    for (cn_ctx *m : members) { m->own_stream = m->stream; m->stream = root->stream; m->cap_root = root; m->capturing = true; }
+    root->cap_members = members; root->cap_root = root; root->capturing = true;
+    return 0;
+}
+extern "C" int cn_graph_begin_levels(cn_ctx *root, cn_ctx *const *levels, uint32_t n) {
+    if (!root || (n && !levels)) return fail(CN_ERR_ARG, "null argument");
+    if (!n) return cn_graph_begin(root);
+    std::vector<cn_ctx *> members(levels, levels + n);
+    for (uint32_t i = 0; i < n; i++) {
+        if (!members[i]) return fail(CN_ERR_ARG, "cn_graph_begin_levels: null level context at position %u", i);
+        if (members[i] == root) return fail(CN_ERR_ARG, "cn_graph_begin_levels: the root is listed as a member");
+    }
+    std::sort(members.begin(), members.end(), lock_order);
+    if (std::adjacent_find(members.begin(), members.end()) != members.end()) return fail(CN_ERR_ARG, "cn_graph_begin_levels: a level context is listed twice");
+    for (cn_ctx *m : members) if (m->hc.k >= root->hc.k) return fail(CN_ERR_ARG, "cn_graph_begin_levels: a member keeps %u of the root's %u coefficient moduli (must be fewer)", m->hc.k, root->hc.k);
+    // the root has the most limbs: root first, then the members in lock order
+    std::vector<cn_ctx *> order(1, root);
+    order.insert(order.end(), members.begin(), members.end());
+    HeldLocks locks(order);
+    return graph_begin_levels_locked(root, members);
 }

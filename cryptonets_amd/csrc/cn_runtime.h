@@ -23,10 +23,14 @@ struct GemmPlan;
 // A captured operation sequence (cn_graph_begin / cn_graph_end): the instantiated HIP graph, the host blocks its upload nodes read at
 // every launch, and the device arrays that were handed out while it was recorded and are not owned by a live handle - they stay
 // reserved for the graph (its kernels carry their addresses), out of the pool, until the graph is freed.
+// A graph recorded across levels (cn_graph_begin_levels) also carries, per member context, the arrays reserved out of that member's pool.
+struct cn_ctx;
 struct CapturedGraph {
     hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
     std::vector<std::unique_ptr<char[]>> staged;
     std::vector<std::pair<uint64_t *, size_t>> reserved;
+    struct Member { cn_ctx *ctx; std::vector<std::pair<uint64_t *, size_t>> reserved; };
+    std::vector<Member> members;           // in lock order (more limbs first); empty for cn_graph_begin
 };
 struct Buffer {
     int kind;                 // 0 = ciphertext array, 1 = dense plaintext array, 2 = scalar GEMM plan, 3 = captured graph
@@ -190,7 +194,16 @@ struct cn_ctx {
     std::atomic<bool> capturing{false};   // between cn_graph_begin and cn_graph_end: work is recorded on the stream, nothing that synchronises or allocates may run
     std::vector<std::unique_ptr<char[]>> cap_staged;                 // host blocks of the upload nodes recorded so far
     std::vector<std::pair<uint64_t *, size_t>> cap_allocs;           // arrays handed out while recording
-    int graphs_alive = 0;     // graphs carry the addresses of the scratch arenas: those must not move while one exists
+    int graphs_alive = 0;     // graphs carry the addresses of the scratch arenas: those must not move while one exists (also the graphs of a root this context is a member of)
+    // recording across levels (cn_graph_begin_levels): the root records on its stream and every member's work goes onto it.  cap_root: the root of
+    // the recording this context takes part in (the root itself included), null otherwise; cap_members: the root's members, in lock order;
+    // own_stream: a member's stream, put back at cn_graph_end; member_graphs: live graphs of other contexts that hold this one (cn_ctx_destroy refuses);
+    // ev_graph: marks a point of this context's stream a replay (or the members behind it) waits for
+    cn_ctx *cap_root = nullptr;
+    std::vector<cn_ctx *> cap_members;
+    hipStream_t own_stream = nullptr;
+    int member_graphs = 0;
+    hipEvent_t ev_graph = nullptr;
     int cus = 0;              // compute units of the device
     uint64_t folded_zero = 0;  // zero encryptions folded so far
     uint64_t mr_pipelined = 0; // cn_mul_relin chunks and flushed Multiply + Relinearize groups that ran through pipelined_halves

@@ -1839,17 +1839,25 @@ class CapturedEvaluation:
     prime.  `fn(inputs)` is the evaluation (layer `Apply` chain) on encrypted matrices; it must have run once before on data of the same
     shapes (temporaries then come out of the handle pools).  `run(new_inputs)` writes the new ciphertext words into the buffers the
     recording read, launches the graphs and returns the matrix the recording produced (same object every time: decrypt or copy it
-    before the next run).  Everything the recording created stays alive until `Dispose`."""
+    before the next run).  Everything the recording created stays alive until `Dispose`.
+    A chain that switches levels (ModSwitchLayer) is recorded across them: each prime's graph covers its context and its level contexts
+    (cn_graph_begin_levels) and replays with one launch on the first level.  `levels`: the limb counts of those level contexts (the levels the
+    rehearsal ran at); None: every level the environment has cached (`Level(limbs)`); (): none (cn_graph_begin)."""
 
-    def __init__(self, env, fn, inputs):
+    def __init__(self, env, fn, inputs, levels=None):
         self.env, self.inputs = env, list(inputs)
         ctxs = [e.ctx for e in env.Environments]
+        pick = (lambda e: sorted(e._levels)) if levels is None else (lambda e: sorted(set(int(x) for x in levels), reverse=True))
+        levels = [[e.Level(lv).ctx for lv in pick(e)] for e in env.Environments]
         import gc
         gc.collect()                                  # temporaries of the rehearsal that only the collector frees go back to the pools first
         self.graphs, begun, failure = [], [], None
         try:
-            for c in ctxs:
-                c.graph_begin()
+            for c, lv in zip(ctxs, levels):
+                if lv:
+                    c.graph_begin(levels=lv)
+                else:
+                    c.graph_begin()
                 begun.append(c)
             self.result = fn(*self.inputs)
         except BaseException as ex:                   # noqa: BLE001 - re-raised below, after every context has left capture mode
@@ -1884,6 +1892,7 @@ class CapturedEvaluation:
         return self.result
 
     def Dispose(self):
+        """frees the graphs (on the first-level contexts that own them): the level contexts they cover can be closed after this"""
         for e, g in zip(self.env.Environments, self.graphs):
             e.ctx.free(g)
         self.graphs = []

@@ -234,11 +234,28 @@ def evaluate_batches(network, Factory, reader, numberOfRecords, report=print):
     return errs, count
 
 
-def evaluate_single_recorded(network, Factory, records, report=print):
+def evaluate_single_recorded(network, Factory, records, report=print, schedule=None):
     """The loop of `evaluate_single` with the evaluation RECORDED: the first record runs layer by layer (rehearsal), the layers after the
     EncryptLayer are then recorded once as one HIP graph per plaintext prime (`hewrapper.CapturedEvaluation`) and every further record
     is encrypted, copied into the recorded input and evaluated with one launch per prime.  "Prediction-Time" covers the same window
-    as the reference's brackets (after encryption .. before decryption).  Encrypted GPU factory only.  Returns (errors, count)."""
+    as the reference's brackets (after encryption .. before decryption).  Encrypted GPU factory only.  Returns (errors, count).
+    `schedule`: a modulus-switching schedule ([(boundary, limbs), ...], as levels.plan_levels returns it) applied to the chain for this
+    evaluation (with_levels; the chain is wired back as it was afterwards): the scheduled chain is rehearsed, recorded across the levels
+    (one graph per prime covers its level contexts and the switches) and replayed."""
+    if any(isinstance(p, ModSwitchLayer) for p in _chain(network)):
+        raise Exception("a recorded evaluation takes its ModSwitchLayers from schedule=: pass the chain without them and its schedule "
+                        "(evaluate_single_recorded(..., schedule=[(boundary, limbs), ...]))")
+    wiring = [(p, p.Source) for p in _chain(network)]
+    if schedule:
+        network = with_levels(network, schedule)
+    try:
+        return _evaluate_recorded(network, Factory, records, report, [lv for _, lv in schedule or ()])
+    finally:
+        for p, src in wiring:                                     # the caller's chain as it was (with_levels rewires, never copies)
+            p.Source = src
+
+
+def _evaluate_recorded(network, Factory, records, report, levels):
     import time
     from .hewrapper import CapturedEvaluation
     layers = list(_chain(network))[::-1]                          # reader first
@@ -247,8 +264,6 @@ def evaluate_single_recorded(network, Factory, records, report=print):
     enc, tail = layers[k], layers[k + 1:]
     if any(isinstance(p, TimingLayer) for p in layers):
         raise Exception("a recorded evaluation cannot contain TimingLayers (they synchronise)")
-    if any(isinstance(p, ModSwitchLayer) for p in layers):
-        raise Exception("a recorded evaluation cannot contain ModSwitchLayers (cn_mod_switch is refused during a graph capture)")
     for p in layers:
         p.Factory = Factory
     network.PrepareNetwork()
@@ -257,6 +272,8 @@ def evaluate_single_recorded(network, Factory, records, report=print):
     def sync():
         for e in env.Environments:
             e.ctx.sync()
+            for lv in levels:                                     # (a scheduled chain: the level contexts' streams as well)
+                e.Level(lv).ctx.sync()
 
     def run_tail(x, keep):
         for L in tail:
@@ -281,7 +298,7 @@ def evaluate_single_recorded(network, Factory, records, report=print):
                     sync(); dt = time.perf_counter() - t0
                     score = np.asarray(out.Decrypt(env))[:, 0]
                     out.Dispose()
-                    cap = CapturedEvaluation(env, lambda x: run_tail(x, first), [first])
+                    cap = CapturedEvaluation(env, lambda x: run_tail(x, first), [first], levels=levels)
                 else:
                     sync(); dt = time.perf_counter() - t0
                     score = np.asarray(out.Decrypt(env))[:, 0]

@@ -28,6 +28,7 @@ def main():
     ap.add_argument("-e", "--encrypt", action="store_true")
     ap.add_argument("-v", "--verbose", action="store_true")
     ap.add_argument("--graph", action="store_true", help="with -e: record the evaluation once (one HIP graph per plaintext prime) and replay it for every further record")
+    ap.add_argument("--levels", action="store_true", help="with -e: plan a modulus-switching schedule on the first record (levels.plan_levels, margin 8 bits) and evaluate under it")
     ap.add_argument("--budget", action="store_true", help="with -e -v: probe the invariant noise budget after every layer (CryptoTracker)")
     ap.add_argument("--file", default="MNIST-28x28-test.txt")
     ap.add_argument("--synthetic", type=int, default=0, metavar="RECORDS")
@@ -48,26 +49,37 @@ def main():
         from cryptonets_amd.raw import RawFactory
         Factory = RawFactory(parms["n"])
     print("Generating keys in %.2f seconds" % (time.time() - start))
-    reader = networks.lola_reader(a.network, a.file)
-    if a.network == "LoLaLarge":
-        if a.weights:
-            from cryptonets_amd.layers import WeightsReader
-            wr = WeightsReader(a.weights, a.biases)
-            W, B = wr.Weights, wr.Biases
-        else:
-            r = np.random.default_rng(7)                         # small and sparse, so that the logits stay below the 93-bit plaintext modulus
-            pick = lambda n, p, s: r.choice([-1.0, 0.0, 1.0], size=n, p=[p / 2, 1 - p, p / 2]) / s
-            W = [np.rint(r.normal(0, 0.01, 83 * 64) * 4096) / 16, pick(163 * 83 * 36, 0.01, 64), pick(10 * 2608, 0.02, 512)]
-            B = [np.rint(r.normal(0, 0.05, 83) * 4096) / 4096, pick(163, 0.5, 64), pick(10, 0.5, 512)]
-        network = networks.LargeLoLa(Factory, reader, W, B)
-    else:
+
+    def build():
+        reader = networks.lola_reader(a.network, a.file)
+        if a.network == "LoLaLarge":
+            if a.weights:
+                from cryptonets_amd.layers import WeightsReader
+                wr = WeightsReader(a.weights, a.biases)
+                W, B = wr.Weights, wr.Biases
+            else:
+                r = np.random.default_rng(7)                         # small and sparse, so that the logits stay below the 93-bit plaintext modulus
+                pick = lambda n, p, s: r.choice([-1.0, 0.0, 1.0], size=n, p=[p / 2, 1 - p, p / 2]) / s
+                W = [np.rint(r.normal(0, 0.01, 83 * 64) * 4096) / 16, pick(163 * 83 * 36, 0.01, 64), pick(10 * 2608, 0.02, 512)]
+                B = [np.rint(r.normal(0, 0.05, 83) * 4096) / 4096, pick(163, 0.5, 64), pick(10, 0.5, 512)]
+            return networks.LargeLoLa(Factory, reader, W, B)
         weights = np.load(GOLDEN + ("/small_model_weights.npz" if a.network == "LoLaSmall" else "/cryptonets_weights.npz"))
-        network = networks.LOLA_NETWORKS[a.network](Factory, reader, weights)
+        return networks.LOLA_NETWORKS[a.network](Factory, reader, weights)
+    network = build()
+    schedule = None
+    if a.levels and a.encrypt:
+        from cryptonets_amd.levels import plan_levels
+        plan = plan_levels(network, Factory, 1, margin_bits=8)              # calibrated on the first record
+        print(plan)
+        schedule = plan.schedule
+        network = build()                                                    # the evaluation reads from the first record again
     if a.budget:
         from cryptonets_amd.cryptotracker import CryptoTracker
         CryptoTracker.EnableBudgetTests()
     if a.graph and a.encrypt:
-        errs, count = networks.evaluate_single_recorded(network, Factory, a.records)
+        errs, count = networks.evaluate_single_recorded(network, Factory, a.records, schedule=schedule)
+    elif schedule:
+        errs, count = networks.evaluate_single(networks.with_levels(network, schedule), Factory, a.records, verbose=a.verbose)
     else:
         errs, count = networks.evaluate_single(network, Factory, a.records, verbose=a.verbose)
     print("errs %d/%d accuracy %.3f%%" % (errs, count, 100 - 100.0 * errs / max(count, 1)))

@@ -48,7 +48,7 @@ int cn_device_count(void);
  * (n, coeff moduli q[k], plain modulus t, DecompositionBitCount, GaloisDecompositionBitCount). */
 int cn_ctx_create(uint32_t n, const uint64_t *q, uint32_t k, uint64_t t, int dbc, int gdbc,
                   int device, cn_ctx **out);
-int cn_ctx_destroy(cn_ctx *ctx);
+int cn_ctx_destroy(cn_ctx *ctx);      /* CN_ERR_ARG for a member of a recording or a live graph across levels (cn_graph_begin_levels) */
 int cn_sync(cn_ctx *ctx);
 /* Ordering between contexts without a host wait: everything submitted to `ctx` AFTER this call starts only when everything submitted to
  * `other` BEFORE it has finished (an event on other's stream that ctx's stream waits for; same or different device).  The plaintext-prime
@@ -73,8 +73,9 @@ int cn_ctx_create_level(cn_ctx *parent, uint32_t limbs, cn_ctx **out);
 /* out[oi + i] = ModSwitchTo(in[ii + i], level of dst), i < count: k_src - k_dst successive drops of the last prime with rounding,
  * x' = floor((x + floor(q_last / 2)) / q_last) mod Q' per coefficient (x = CRT value), as SEAL's mod_switch_to loops.  Size-2 and size-3
  * ciphertexts (both handles the same size).  dst must be on the chain of src: same device, N and t, q_dst a strict prefix of q_src, the same
- * key-switch convention (and under "ks_xi" = 1 a level of src's chain).  Otherwise, and for bad handles or ranges or while either context records a
- * graph: CN_ERR_ARG and no switch is enqueued, `out` is not written.  Not deferrable: takes both context locks (more limbs first) and submits both
+ * key-switch convention (and under "ks_xi" = 1 a level of src's chain).  Otherwise, and for bad handles or ranges, or while either context records a
+ * graph unless both belong to one recording across levels (cn_graph_begin_levels: the switch is then recorded): CN_ERR_ARG and no switch is
+ * enqueued, `out` is not written.  Not deferrable: takes both context locks (more limbs first) and submits both
  * contexts' queued calls first - also when the handle or range checks then refuse the call (handles may come from the lock-free ring, "defer" = 2);
  * the context checks (chain, capture) refuse before anything is submitted.  Ordering without a host wait (events): the switch reads `in` after the work submitted to src before the call, writes `out` after
  * the work submitted to dst before it; later dst calls see the result, later src calls wait for the read.
@@ -189,6 +190,7 @@ int cn_set_option(cn_ctx *ctx, const char *name, int value);
  *   "folded_zero_encryptions"  zero encryptions folded so far ("fold_zero")
  *   "mul_relin_pipelined"      cn_mul_relin chunks and flushed groups of queued Multiply + Relinearize calls that ran in parts over the context's two
  *                              streams ("sq_halves"; counts up)
+ *   "pool_arrays"              device arrays cached for reuse (the temporaries of a live graph are reserved out of them)
  *   "stream_tries"             streams cn_ctx_create tried until one had a hardware queue of its own (< 0: none had; CN_STREAM_PROBE=0 takes the first) */
 int cn_get_option(cn_ctx *ctx, const char *name, int *value);
 /* SEAL DefaultParams.CoeffModulus128(n) (AtomicSealBfvVector.cs:146); returns count, fills q (<=9) */
@@ -297,6 +299,19 @@ int cn_gemm_plan_apply(cn_ctx *ctx, cn_handle plan, cn_handle in, cn_handle out,
 int cn_graph_begin(cn_ctx *ctx);
 int cn_graph_end(cn_ctx *ctx, cn_handle *graph);
 int cn_graph_launch(cn_ctx *ctx, cn_handle graph);
+/* Recording across levels: cn_graph_begin_levels starts a recording on ctx, the ROOT, that also covers the n level contexts `levels`, the MEMBERS;
+ * cn_graph_end(ctx) closes it and returns one graph owned by ctx, cn_graph_launch(ctx) replays the whole chain with one launch.  Every member must be a
+ * context cn_mod_switch from ctx would accept as a target (same device, N and t, its coefficient modulus a strict prefix of ctx's, the same
+ * key-switch convention and under "ks_xi" = 1 a level of ctx's chain); the members must be distinct, none the root, none recording or a member of
+ * another recording.  Otherwise CN_ERR_ARG and nothing starts (n = 0: cn_graph_begin).  Queued calls of the root and the members are submitted first.
+ * While recording, the members' calls are recorded on the ROOT's stream (one linear graph) and every member counts as recording: the calls
+ * cn_graph_begin refuses are refused on a member too, and cn_graph_begin / cn_graph_end on a member return CN_ERR_ARG.  cn_mod_switch between two
+ * contexts of the recording is recorded; a switch to or from any other context is refused.  Each member's temporaries stay reserved out of its own
+ * pool while the graph lives.  Launch order without a host wait: the replay starts behind the work submitted to every member before
+ * cn_graph_launch, and later calls on a member start behind the replay (a graph without members launches exactly as before).
+ * Lifetime: cn_ctx_destroy of a member while the recording runs or a graph recorded with it is alive returns CN_ERR_ARG and frees nothing; free
+ * the graph (cn_free on the root) first.  Destroying the root frees its graphs and hands the members' reservations back. */
+int cn_graph_begin_levels(cn_ctx *ctx, cn_ctx *const *levels, uint32_t n);
 
 /* ---- non-linear ops ------------------------------------------------------------------ */
 /* Evaluator.Multiply (BEHZ), size2 x size2 -> size3 (AtomicSealBfvVector.cs:461,546,786,839,1457) */
