@@ -542,6 +542,13 @@ int do_keyswitch(cn_ctx *ctx, const uint64_t *target, size_t tstride, const uint
             if (!done) return fail(CN_ERR_ARG, "internal: FP64 key without FP64 kernel");
         } else if (rr) done = ks_ops[POL_U64]->launch(ctx, a);
         if (!done) {                          // radix-2 LDS fallback (N < 1024, legacy_ntt): no fused accumulator -> one element-wise add behind it
+            // The accumulator may be the result's own array (SumAllSlots adds in place): the key switch then writes into the key-switch arena
+            // (unused by this path) and the add reads it beside the untouched accumulator.  (Writing `out` first doubled the key switch there.)
+            if (extra) {
+                if (xstride != ctx->ctw2 || out_tab) return fail(CN_ERR_ARG, "internal: accumulator stride");
+                CHECK(ensure_ks_part(ctx, (size_t)cnt * ctx->ctw2 * 8));
+                a.out = (uint64_t *)ctx->ks_part;
+            }
             const uint32_t nt = std::min<uint32_t>(1024, n);
             switch (n / nt) {
                 case 1: launch_ks_legacy<1>(ctx, nt, a); break;
@@ -552,8 +559,8 @@ int do_keyswitch(cn_ctx *ctx, const uint64_t *target, size_t tstride, const uint
                 default: return fail(CN_ERR_ARG, "unsupported poly modulus degree for key switching");
             }
             if (extra) {
-                if (xstride != ctx->ctw2 || out_tab) return fail(CN_ERR_ARG, "internal: accumulator stride");
-                hipLaunchKernelGGL(k_addsub, dim3(cnt * 2 * k * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, out, extra, out, ctx->dc, ctx->chunks, 0);
+                hipLaunchKernelGGL(k_addsub, dim3(cnt * 2 * k * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, (const uint64_t *)ctx->ks_part, extra, out, ctx->dc,
+                                   ctx->chunks, 0);
                 launch_count(ctx);
             }
         }

@@ -78,7 +78,7 @@ struct DevConsts {
     // ms_hd[p][p] = h_p itself
     double ms_invd[CN_MAXK][CN_MAXK], ms_hd[CN_MAXK][CN_MAXK];
     // invariant noise norm (cn_noise_norm, k_noise_norm): q/q_j and q as k little-endian 64-bit words (q/q_j < 2^(61(k-1)) needs at most k - 1
-    // of them: every q_j < 2^61), and 1/q_j as a double (the estimate of the CRT quotient)
+    // of them: every q_j < 2^60), and 1/q_j as a double (the estimate of the CRT quotient)
     uint64_t nn_qhat[CN_MAXK][CN_MAXK], nn_q[CN_MAXK];
     double nn_qinv[CN_MAXK];
 };

@@ -110,7 +110,10 @@ int cn_build_consts(DevConsts *c, uint32_t n, const uint64_t *q, uint32_t k, uin
     c->n = n; c->k = k; c->kb = k + 1; c->dbc = dbc; c->gdbc = gdbc;
     while ((1u << c->logn) < n) c->logn++;
     for (uint32_t j = 0; j < k; j++) {
-        if (q[j] >> 61 || !is_prime_u64(q[j]) || t >= q[j]) { snprintf(err, errlen, "coeff modulus %u invalid (needs prime < 2^61, > t)", j); return -1; }
+        // SEAL 3.2 refuses coefficient moduli wider than 60 bits (SEAL_USER_MOD_BIT_COUNT_MAX); the 61-bit primes are its own: m_sk, gamma and the
+        // auxiliary base B (below), which a data prime must not be
+        if (q[j] >> 60) { snprintf(err, errlen, "coeff modulus %u has more than 60 bits (needs q < 2^60)", j); return -1; }
+        if (!is_prime_u64(q[j]) || t >= q[j]) { snprintf(err, errlen, "coeff modulus %u invalid (needs prime < 2^60, > t)", j); return -1; }
         for (uint32_t i = 0; i < j; i++) if (q[i] == q[j]) { snprintf(err, errlen, "coeff moduli must be distinct"); return -1; }
         set_mod(c->q[j], q[j]);
     }

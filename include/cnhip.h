@@ -45,7 +45,9 @@ const char *cn_last_error(void);
 int cn_device_count(void);
 
 /* ---- context = AtomicSealBfvEncryptedEnvironment (AtomicSealBfvVector.cs:19-74,140-173):
- * (n, coeff moduli q[k], plain modulus t, DecompositionBitCount, GaloisDecompositionBitCount). */
+ * (n, coeff moduli q[k], plain modulus t, DecompositionBitCount, GaloisDecompositionBitCount).  n a power of two up to 16384; every q_j a
+ * distinct prime with t < q_j < 2^60 (at most 60 bits, as SEAL 3.2 allows: the 61-bit primes are SEAL's m_sk, gamma and auxiliary base) and
+ * q_j == 1 (mod 2n); 1 <= dbc, gdbc <= 60.  Otherwise CN_ERR_ARG and no context. */
 int cn_ctx_create(uint32_t n, const uint64_t *q, uint32_t k, uint64_t t, int dbc, int gdbc,
                   int device, cn_ctx **out);
 int cn_ctx_destroy(cn_ctx *ctx);      /* CN_ERR_ARG for a member of a recording or a live graph across levels (cn_graph_begin_levels) */
@@ -376,7 +378,8 @@ int cn_set_secret_key(cn_ctx *ctx, const uint64_t *words, size_t count);   /* [k
 int cn_get_key(cn_ctx *ctx, int which /*0 relin,1 galois,2 public,3 secret*/, uint64_t galois_elt, uint64_t *host, size_t count);
 /* Encryptor.Encrypt of `count` dense plaintexts (pt = 0: encryptions of zero; pt_stride 0: the same plaintext).  With
  * cn_set_option("defer", 1) a call for up to 4 ciphertexts is queued like the evaluator calls (the unchanged PoolLayer encrypts a zero
- * vector per padded convolution tap, PoolLayer.cs:67-80: 645 calls per layer and plaintext prime become one launch chain). */
+ * vector per padded convolution tap, PoolLayer.cs:67-80: 645 calls per layer and plaintext prime become one launch chain).  Needs
+ * 1024 <= N (the samplers run on the register-radix transforms); below, CN_ERR_ARG and nothing written. */
 int cn_encrypt(cn_ctx *ctx, cn_handle pt, uint32_t pi, uint32_t pt_stride, cn_handle out, uint32_t oi, uint32_t count, uint64_t seed);
 /* AllocateCiphertext + Encryptor.Encrypt(PlainZero) as ONE call: a new one-ciphertext array holding a fresh encryption of zero (PoolLayer.ElementAt per
  * padded tap, PoolLayer.cs:67-80; the IsZero branches of AtomicSealBfvVector.cs:566,587).  Same words and - under "defer" - the same queue entry as

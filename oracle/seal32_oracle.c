@@ -251,6 +251,9 @@ uint64_t cno_compute_probe(uint64_t iters) {
 }
 cno_ctx *cno_ctx_create(uint32_t n, const uint64_t *q, uint32_t k, uint64_t t, int dbc, int gdbc) {
     if (k == 0 || k > MAXK || n < 2 || (n & (n - 1))) return NULL;
+    /* SEAL 3.2: coefficient moduli of at most 60 bits (SEAL_USER_MOD_BIT_COUNT_MAX); m_sk, gamma and the auxiliary base are 61-bit primes,
+     * and a data prime equal to one of them would make the BEHZ and decryption constants meaningless */
+    for (uint32_t j = 0; j < k; j++) if (q[j] >> 60) return NULL;
     cno_ctx *c = calloc(1, sizeof *c);
     c->n = n; c->k = k; c->kb = k + 1; c->dbc = dbc; c->gdbc = gdbc;
     while ((1u << c->logn) < n) c->logn++;

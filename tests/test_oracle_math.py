@@ -11,6 +11,9 @@ CASES = [
     (64, 257, [0xffffee001, 0xffffc4001], 16, 60),
     (128, 12289, COEFF_MODULUS_128[8192], 10, 20),
     (32, 193, COEFF_MODULUS_128[16384][:8], 60, 60),
+    (64, 257, [0xffffffffffe8001, 0xffffffffffd8001, 0xffffee001], 10, 20),   # two 60-bit primes beside a 36-bit one
+    (64, 257, [0x3fffffff000001, 0xffffffffffc0001], 59, 59),                # 54 + 60 bits, a 1-bit top digit
+    (64, 257, COEFF_MODULUS_128[2048], 10, 20),                              # k = 1: SEAL's N = 2048 default, one 54-bit prime
 ]
 
 
@@ -56,6 +59,30 @@ def test_behz_auxiliary_primes_follow_seal_rule():
         x -= 1 << 18
     bsk = o.bsk_moduli()
     assert bsk[-1] == found[0] and bsk[:3] == found[2:5]
+
+
+def test_oracle_refuses_moduli_of_61_bits_and_more():
+    """SEAL 3.2 takes coefficient moduli of at most 60 bits.  The 61-bit primes are its own - m_sk, gamma and the auxiliary base B, all of
+    them == 1 mod 2^18 and so NTT-friendly for every N - and a data prime equal to one of them gave wrong multiply words: the oracle must
+    refuse every modulus >= 2^60 rather than become the truth there.  The largest NTT-friendly prime below 2^60 is accepted."""
+    n = 64
+    aux, x = [], (1 << 61) - (1 << 18) + 1
+    while len(aux) < 4:
+        if is_prime(x):
+            aux.append(x)
+        x -= 1 << 18
+    m_sk, gamma, b0 = aux[0], aux[1], aux[2]
+    assert (m_sk, gamma, b0) == (0x1fffffffffe00001, 0x1fffffffffc80001, 0x1fffffffffb40001)
+    other = next(x for x in range((1 << 61) - 2 * n + 1, 1 << 60, -2 * n) if is_prime(x) and x % (1 << 18) != 1)   # not of SEAL's auxiliary form
+    assert other.bit_length() == 61
+    top = next(x for x in range((1 << 60) - 2 * n + 1, 1 << 59, -2 * n) if is_prime(x))
+    assert top.bit_length() == 60 and top % (2 * n) == 1
+    for wide in (m_sk, gamma, b0, other):
+        for q in ([wide, top], [top, wide], [wide]):
+            with pytest.raises(ValueError):
+                Oracle(n, 257, q=q)
+    o = Oracle(n, 257, q=[top])
+    assert o.q == [top] and pow(o.psi(0), n, top) == top - 1
 
 
 @pytest.mark.parametrize("n,t,q,dbc,gdbc", CASES)

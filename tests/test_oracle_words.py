@@ -22,6 +22,10 @@ SMALL = [
     (128, 12289, Q8192, 10, 20),                                            # CryptoNets / LoLa limbs and digit widths
     (256, 12289, Q8192[:2], 10, 20),                                        # config 2's limbs, Kronecker products in the model
     (32, 193, COEFF_MODULUS_128[16384][:8], 60, 60),                        # LoLa-CIFAR limbs (48-49 bits), dbc 60
+    # 50-60-bit moduli: the integer transforms and key switch, SEAL's 61-bit auxiliary base (the widest moduli SEAL 3.2 accepts)
+    (64, 257, [0xffffffffffe8001, 0xffffffffffd8001], 60, 60),              # two primes just below 2^60, one digit per limb
+    (64, 257, [0xffffffffffe8001, 0xffffffffffd8001, 0xffffee001], 10, 20),  # beside a 36-bit prime: six 10-bit digits per wide limb
+    (64, 257, [0x3fffffff000001, 0xffffffffffc0001], 59, 59),               # 54 and 60 bits: the top digit of the wide limb is 1 bit
 ]
 
 
