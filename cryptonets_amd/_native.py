@@ -17,7 +17,7 @@ CSRC = os.path.join(_PKG, "csrc")
 SOURCES = [os.path.join(CSRC, f) for f in (
     "cn_api.hip", "cn_eval.hip", "cn_client.hip", "cn_defer.hip", "cn_multi.hip", "cn_host.cpp", "cn_tables.cpp", "cn_l_gemm.hip", "cn_l_behz.hip",
     "cn_l_rr_u64.hip", "cn_l_rr_f64.hip", "cn_l_rr_f64l.hip", "cn_l_ks_u64.hip", "cn_l_ks_f64.hip", "cn_l_ks_f64l.hip", "cn_level.hip", "cn_l_modswitch.hip",
-    "cn_l_modswitch_f64.hip", "cn_l_noise.hip")]
+    "cn_l_modswitch_f64.hip", "cn_l_noise.hip", "cn_l_seeded.hip")]
 OBJ_DIR = os.path.join(_PKG, "lib", "obj")
 
 U64P = C.POINTER(C.c_uint64)
@@ -185,6 +185,10 @@ SIGNATURES = {
     "cn_set_secret_key": (C.c_int, [_CTX, U64P, C.c_size_t]),
     "cn_get_key": (C.c_int, [_CTX, C.c_int, C.c_uint64, U64P, C.c_size_t]),
     "cn_encrypt": (C.c_int, [_CTX, _H, _u32, _u32, _H, _u32, _u32, C.c_uint64]),
+    "cn_encrypt_symmetric": (C.c_int, [_CTX, _H, _u32, _u32, _H, _u32, _u32, C.c_uint64, C.c_char_p, C.c_uint64, C.c_uint64]),
+    "cn_ct_expand": (C.c_int, [_CTX, _H, _u32, _u32, C.c_char_p, C.c_uint64, C.c_uint64]),
+    "cn_ct_upload_compact": (C.c_int, [_CTX, _H, _u32, _u32, U64P, C.c_char_p, C.c_uint64, C.c_uint64]),
+    "cn_ct_download_compact": (C.c_int, [_CTX, _H, _u32, _u32, U64P]),
     "cn_decrypt": (C.c_int, [_CTX, _H, _u32, _u32, _H, _u32]),
     "cn_noise_poly": (C.c_int, [_CTX, _H, _u32, _u32, C.POINTER(C.c_uint64)]),
     "cn_noise_norm": (C.c_int, [_CTX, _H, _u32, _u32, C.POINTER(C.c_uint64)]),
@@ -603,6 +607,40 @@ class Context:
 
     def encrypt(self, pt, pi, out, oi, count=1, seed=1, pt_stride=1):
         self._chk(self.L.cn_encrypt(self._h, pt, pi, pt_stride, out, oi, count, seed))
+
+    # ---- seeded symmetric ciphertexts (include/cnhip.h): c1 = INTT(a), a regenerated from 32 public bytes
+    @staticmethod
+    def _seed32(a_seed):
+        a_seed = bytes(a_seed)
+        if len(a_seed) != 32:
+            raise ValueError("the public seed has 32 bytes")
+        return a_seed
+
+    def encrypt_symmetric(self, pt, pi, out, oi, count=1, *, a_seed, seed=1, a_nonce=0, a_item0=0, pt_stride=1):
+        """secret-key encryptions whose c1 is the expansion of (a_seed, a_nonce, a_item0 + i); `seed` is the nonce of the noise draw under the
+        context's own sampler key.  a_seed has no default: two ciphertexts under one (a_seed, a_nonce, item) share their a, and their difference
+        then shows the difference of the messages"""
+        self._chk(self.L.cn_encrypt_symmetric(self._h, pt, pi, pt_stride, out, oi, count, seed, self._seed32(a_seed), a_nonce, a_item0))
+
+    def ct_expand(self, h, first, count, a_seed, a_nonce=0, a_item0=0):
+        """poly 1 of h[first : first + count] from the public seed (needs no key)"""
+        self._chk(self.L.cn_ct_expand(self._h, h, first, count, self._seed32(a_seed), a_nonce, a_item0))
+
+    def ct_upload_compact(self, h, first, c0, a_seed, a_nonce=0, a_item0=0):
+        """c0 words [count, k * n] into poly 0 of h[first ..) (one strided copy), poly 1 expanded from the seed on the device"""
+        d = np.ascontiguousarray(c0, dtype=np.uint64)
+        count = d.shape[0] if d.ndim > 1 else 1
+        _, nbytes = self.device_ptr(h)                     # the library reads count * k * n words from the host pointer: check the row width here
+        size = self._ct_size.get(h)
+        if count == 0 or d.size != count * self.k * self.n or (size is not None and size != 2) or nbytes % (self.ctw * 8) or first + count > nbytes // (self.ctw * 8):
+            raise ValueError("ct_upload_compact: data of shape %s is not [count, %d] c0 words for the size-2 ciphertexts of this handle" % (d.shape, self.k * self.n))
+        self._chk(self.L.cn_ct_upload_compact(self._h, h, first, count, _p64(d), self._seed32(a_seed), a_nonce, a_item0))
+
+    def ct_download_compact(self, h, first, count):
+        """the c0 words [count, k * n] of h[first : first + count]"""
+        out = np.empty((count, self.k * self.n), dtype=np.uint64)
+        self._chk(self.L.cn_ct_download_compact(self._h, h, first, count, _p64(out)))
+        return out
 
     def decrypt(self, ct, ci, count, pt_out, pi):
         self._chk(self.L.cn_decrypt(self._h, ct, ci, count, pt_out, pi))

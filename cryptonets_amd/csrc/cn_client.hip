@@ -328,3 +328,62 @@ extern "C" int cn_noise_norm(cn_ctx *ctx, cn_handle ct, uint32_t ci, uint32_t co
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return 0;
 API_END }
+// ---------------------------------------------------------------- seeded symmetric ciphertexts (include/cnhip.h; kernel: cn_k_seeded.hip.h)
+// arguments every seeded entry point shares: size-2 ciphertexts, the transform sizes of device encryption, items inside the 40 bits of the block counter
+static int seeded_args_ok(cn_ctx *ctx, const Buffer *B, uint32_t first, uint32_t count, const uint8_t *a_seed32, uint64_t a_item0) {
+    if (!a_seed32) return fail(CN_ERR_ARG, "null seed");
+    if (!range_ok(B, first, count)) return fail(CN_ERR_ARG, "index out of range");
+    if (ctx->hc.logn < 10 || ctx->hc.logn > 14) return fail(CN_ERR_ARG, "seeded ciphertexts need 1024 <= N <= 16384");
+    if (a_item0 >> 40 || (a_item0 + count) >> 40) return fail(CN_ERR_ARG, "a_item0 + count exceeds the 40 item bits of the block counter");
+    return 0;
+}
+static int expand_body(cn_ctx *ctx, Buffer *B, uint32_t first, uint32_t count, const uint8_t *a_seed32, uint64_t a_nonce, uint64_t a_item0) {
+    SeededArgs a{B->d + (size_t)first * B->item_words, B->item_words, count, true, a_seed32, a_nonce, a_item0, nullptr, nullptr, 0};
+    return cn_l_seeded(ctx, a);
+}
+// (c0, c1) = (INTT(-a s) + e + Delta m, INTT(a)): a from the PUBLIC seed, e from the context's own sampler key (stream 1, nonce `seed`, the context's item counter)
+extern "C" int cn_encrypt_symmetric(cn_ctx *ctx, cn_handle pt, uint32_t pi, uint32_t pt_stride, cn_handle out, uint32_t oi, uint32_t count, uint64_t seed,
+                                    const uint8_t *a_seed32, uint64_t a_nonce, uint64_t a_item0) { API_BODY
+    LOCK; NOT_CAPTURING("cn_encrypt_symmetric (a replayed graph would reuse its randomness)"); GETCT(O, out, 2);
+    if (!ctx->sk) return fail(CN_ERR_NOKEY, "secret key not set");
+    CHECK(seeded_args_ok(ctx, O, oi, count, a_seed32, a_item0));
+    const uint32_t n = ctx->hc.n;
+    const uint64_t *ptd = nullptr;
+    if (pt) { Buffer *P = getbuf(ctx, pt, 1); if (!P || !range_ok(P, pi, pt_stride ? count : 1, pt_stride ? pt_stride : 1)) return fail(CN_ERR_ARG, "invalid plaintext range"); ptd = P->d + (size_t)pi * n; }
+    if (!count) return 0;
+    CHECK(ensure_scratch(ctx, al((size_t)count * n) + 1024));
+    int8_t *es = salloc<int8_t>(ctx, (size_t)count * n);
+    if (!es) return fail(CN_ERR_HIP, "internal: scratch exhausted in encrypt");
+    hipLaunchKernelGGL(k_sample_small, dim3((unsigned)(((uint64_t)count * (n / 8) + 255) / 256)), dim3(256), 0, ctx->stream, es, n, 1, 1u, count, rng_key_of(ctx), seed, 1u, ctx->rng_item,
+                       (const EncTab *)nullptr, cn_noise_table());
+    HIPCHK(hipGetLastError()); launch_count(ctx);
+    ctx->rng_item += count;
+    SeededArgs a{O->d + (size_t)oi * O->item_words, O->item_words, count, false, a_seed32, a_nonce, a_item0, es, ptd, pt_stride ? n : 0};
+    return cn_l_seeded(ctx, a);
+API_END }
+extern "C" int cn_ct_expand(cn_ctx *ctx, cn_handle h, uint32_t first, uint32_t count, const uint8_t *a_seed32, uint64_t a_nonce, uint64_t a_item0) { API_BODY
+    LOCK; NOT_CAPTURING("cn_ct_expand"); GETCT(B, h, 2);
+    CHECK(seeded_args_ok(ctx, B, first, count, a_seed32, a_item0));
+    return expand_body(ctx, B, first, count, a_seed32, a_nonce, a_item0);
+API_END }
+// c0 words [count][k][N] from the host into poly 0 (ONE strided copy), poly 1 from the seed; synchronises like cn_ct_upload (the host array may be reused)
+extern "C" int cn_ct_upload_compact(cn_ctx *ctx, cn_handle h, uint32_t first, uint32_t count, const uint64_t *host_c0, const uint8_t *a_seed32, uint64_t a_nonce, uint64_t a_item0) { API_BODY
+    LOCK; NOT_CAPTURING("cn_ct_upload_compact"); GETCT(B, h, 2);
+    if (!host_c0) return fail(CN_ERR_ARG, "null argument");
+    CHECK(seeded_args_ok(ctx, B, first, count, a_seed32, a_item0));
+    if (!count) return 0;
+    const size_t row = (size_t)ctx->hc.k * ctx->hc.n * 8;
+    HIPCHK(hipMemcpy2DAsync(B->d + (size_t)first * B->item_words, B->item_words * 8, host_c0, row, row, count, hipMemcpyHostToDevice, ctx->stream));
+    CHECK(expand_body(ctx, B, first, count, a_seed32, a_nonce, a_item0));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return 0;
+API_END }
+extern "C" int cn_ct_download_compact(cn_ctx *ctx, cn_handle h, uint32_t first, uint32_t count, uint64_t *host_c0) { API_BODY
+    LOCK; NOT_CAPTURING("cn_ct_download_compact"); GETCT(B, h, 2);
+    if (!host_c0 || !range_ok(B, first, count)) return fail(CN_ERR_ARG, "index out of range");
+    if (!count) return 0;
+    const size_t row = (size_t)ctx->hc.k * ctx->hc.n * 8;
+    HIPCHK(hipMemcpy2DAsync(host_c0, row, B->d + (size_t)first * B->item_words, B->item_words * 8, row, count, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return 0;
+API_END }

@@ -7,6 +7,7 @@
 #include "cn_submit.h"
 #include <hip/hip_runtime.h>
 #include <atomic>
+#include <cstring>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -299,5 +300,13 @@ int cn_l_mod_switch(cn_ctx *c, const uint64_t *src, uint64_t *dst, const DevCons
 // invariant noise norm (cn_l_noise.hip): `count` ciphertexts (c0 of ciphertext i at c0 + i * ct_stride, acc [count][k][N] from decrypt_phase) ->
 // out [count][k] words on c's stream
 int cn_l_noise_norm(cn_ctx *c, const uint64_t *c0, size_t ct_stride, const uint64_t *acc, uint64_t *out, uint32_t count);
+// seeded ciphertexts (cn_l_seeded.hip, k_seeded): `cnt` ciphertexts, poly 0 of ciphertext i at out + i * ct_stride.  expand_only: poly 1 = INTT(a) alone (cn_ct_expand);
+// else both components of a secret-key encryption - noise: the int8 polynomials [cnt][N] of k_sample_small, pt: plaintexts (null = zero) pt_stride_words apart
+struct SeededArgs {
+    uint64_t *out; size_t ct_stride; uint32_t cnt; bool expand_only;
+    const uint8_t *a_seed32; uint64_t a_nonce, a_item0;
+    const int8_t *noise; const uint64_t *pt; uint32_t pt_stride_words;
+};
+int cn_l_seeded(cn_ctx *c, const SeededArgs &a);
 
 inline void cn_launch_count(cn_ctx *c, int n = 1) { c->st.kernel_launches += n; }

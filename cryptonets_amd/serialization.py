@@ -26,6 +26,9 @@ Two layers, as in the reference:
                             ciphertext - the layout libcnhip keeps in HBM (include/cnhip.h).  GaloisKeys: dim1 = N, entry
                             (galois_elt - 1) / 2 holds that element's digits, absent elements have dim2 = 0.
 
+* compact batches - this library's own framing of seeded symmetric ciphertexts (c0 words and a public seed; `save_compact_batch` /
+  `load_compact_batch` below).  NOT a SEAL 3.2 stream.
+
   PARITY UNPINNED: no SEAL binary or SEAL-written file exists in this environment or in the reference repository, so byte
   compatibility with real SEAL 3.2 streams is restated, not tested.  What the tests pin is self-consistency (round trips of
   every object, rejection of foreign parameters / truncated streams) and the wrapper framing against the reference source.
@@ -187,6 +190,62 @@ def load_ciphertext_any_level(f, parms, want_ntt_form=None):
         raise BadStream("ciphertext is not valid for the encryption parameters")
     data, size = load_ciphertext(_Prefixed(pid, f), parms.level(limbs), want_ntt_form)
     return data, size, limbs
+
+
+# ------------------------------------------------------------------------------------------------ compact batches of seeded ciphertexts
+# NOT a SEAL 3.2 stream (SEAL ships seeded ciphertexts from 3.4 on, with another generator and another layout): this library's own framing of a batch
+# of fresh secret-key encryptions whose c1 is regenerated from a public seed (include/cnhip.h: cn_encrypt_symmetric, cn_ct_upload_compact).
+#     8 B magic "CNHIPSC1" | u32 version (1) | 32 B public seed | u64 nonce | u64 first item | u64 count | 32 B parms_id of the level
+#     | IntArray of count * k * N words: the c0 polynomials, [ciphertext][limb][coefficient]                       (all little-endian)
+COMPACT_MAGIC = b"CNHIPSC1"
+COMPACT_VERSION = 1
+
+
+class CompactDescriptor:
+    """what turns c0 words back into ciphertexts: the public seed (32 bytes), the nonce, the first item, the count and the parms_id of the level"""
+
+    def __init__(self, a_seed, a_nonce, a_item0, count, parms_id):
+        self.a_seed, self.a_nonce, self.a_item0, self.count, self.parms_id = bytes(a_seed), int(a_nonce), int(a_item0), int(count), bytes(parms_id)
+        if len(self.a_seed) != 32 or len(self.parms_id) != 32:
+            raise ValueError("the public seed and the parms_id have 32 bytes")
+
+    def __eq__(self, o):
+        return (self.a_seed, self.a_nonce, self.a_item0, self.count, self.parms_id) == (o.a_seed, o.a_nonce, o.a_item0, o.count, o.parms_id)
+
+
+def save_compact_batch(f, c0, desc):
+    c0 = np.ascontiguousarray(c0, dtype=np.uint64)
+    if c0.ndim != 2 or c0.shape[0] != desc.count:
+        raise ValueError("c0 words of shape %s do not belong to a descriptor of %d ciphertexts" % (c0.shape, desc.count))
+    f.write(COMPACT_MAGIC)
+    f.write(struct.pack("<I", COMPACT_VERSION))
+    f.write(desc.a_seed)
+    _w_u64(f, desc.a_nonce)
+    _w_u64(f, desc.a_item0)
+    _w_u64(f, desc.count)
+    f.write(desc.parms_id)
+    _w_array(f, c0)
+
+
+def load_compact_batch(f, parms):
+    """(c0 words [count, limbs * N], descriptor, limbs); `parms`: the Parameters of the chain's first level - a batch of any of its levels loads"""
+    if _rd(f, 8) != COMPACT_MAGIC:
+        raise BadStream("Bad stream format. (not a compact batch)")
+    version = struct.unpack("<I", _rd(f, 4))[0]
+    if version != COMPACT_VERSION:
+        raise BadStream("compact batch of version %d (this library reads %d)" % (version, COMPACT_VERSION))
+    a_seed = _rd(f, 32)
+    a_nonce, a_item0, count = _r_u64(f), _r_u64(f), _r_u64(f)
+    pid = _rd(f, 32)
+    limbs = parms.chain().get(pid)
+    if limbs is None:
+        raise BadStream("the compact batch belongs to other encryption parameters")
+    if (a_item0 + count) >> 40:
+        raise BadStream("Bad stream format. (items)")
+    words = _r_array(f)
+    if words.size != count * limbs * parms.n:
+        raise BadStream("Bad stream format. (%d words for %d ciphertexts of %d limbs)" % (words.size, count, limbs))
+    return words.reshape(count, limbs * parms.n), CompactDescriptor(a_seed, a_nonce, a_item0, count, pid), limbs
 
 
 class _Prefixed:

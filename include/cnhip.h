@@ -39,6 +39,7 @@ typedef uint64_t cn_handle;
 #define CN_ERR_NOKEY (-3)    /* relin / Galois key missing (SEAL: "Galois key not present") */
 #define CN_ERR_ZERO (-4)     /* multiply_plain by an all-zero plaintext (SEAL: "plain cannot be zero") */
 #define CN_ERR_NODEV (-5)    /* no HIP device available */
+#define CN_STREAM_A (4)      /* sampler stream of the public `a` of seeded symmetric ciphertexts (cn_encrypt_symmetric, cn_ct_expand); 0-3 are the keys' and the noise's */
 
 int cn_version(void);
 const char *cn_last_error(void);
@@ -385,6 +386,32 @@ int cn_encrypt(cn_ctx *ctx, cn_handle pt, uint32_t pi, uint32_t pt_stride, cn_ha
  * padded tap, PoolLayer.cs:67-80; the IsZero branches of AtomicSealBfvVector.cs:566,587).  Same words and - under "defer" - the same queue entry as
  * cn_ct_alloc followed by cn_encrypt(pt = 0, count = 1, seed). */
 int cn_encrypt_zero_new(cn_ctx *ctx, uint64_t seed, cn_handle *out);
+/* ---- seeded symmetric ciphertexts: a fresh secret-key encryption whose c1 is regenerated from 32 public bytes, so that only c0 travels (half the
+ * bytes of a fresh ciphertext; SEAL >= 3.4 ships the same idea, the framing here is this library's own).  Definition - part of the interface:
+ *   a_j, limb j of item i:  sample_uniform8(a_seed, a_nonce, CN_STREAM_A, a_item0 + i, j (N/8) + b, q_j) for b = 0 .. N/8 - 1 - ChaCha20 block
+ *       counter = item (40 bits) | stream (4) | redraw trial (4) | block (16), nonce words 14-15 = a_nonce, key = the 32 bytes of a_seed as eight
+ *       little-endian words; a block yields 8 consecutive words v = (w[2c] << 32) | w[2c + 1], kept as v mod q_j if v <= 2^64 - 1 - (2^64 - 1) mod q_j - 1,
+ *       else redrawn at the next trial - exactly the layout of the `a` of a key from cn_keygen.  It is read as the NTT form in the library's transform order.
+ *   c1 = INTT(a),  c0 = INTT(-a . s) + e + Delta m, with the plaintext embedding (rounding term included) of cn_encrypt: cn_decrypt needs no change.
+ *   a_seed is PUBLIC and travels with the c0 words; a does not depend on the context's sampler key or salt.  e never comes from a_seed: it is drawn
+ *   like cn_encrypt's e1 from the context's secret sampler key (cn_set_rng_key / cn_set_rng_salt), stream 1, nonce `seed`, the context's item counter.
+ *   Distinct ciphertexts under one a_seed need distinct (a_nonce, item); a_item0 + count <= 2^40.
+ * Streams of the sampler: 0 ternary (secret key, u), 1 / 2 noise, 3 the uniform component of keys, CN_STREAM_A (= 4, defined with the error codes) the public a of
+ * seeded ciphertexts. */
+/* `count` size-2 ciphertexts out[oi ..) = symmetric encryptions of the plaintexts (pt = 0: of zero; pt_stride 0: the same plaintext).  Two inverse
+ * transforms per (ciphertext, limb) against the four transforms of cn_encrypt, and fresh noise e instead of u e_pk + e1 + e2 s.  Needs the secret key
+ * (CN_ERR_NOKEY) and 1024 <= N <= 16384; CN_ERR_ARG for a bad range, a null seed or while a graph is recorded.  Flushes deferred work first and is never
+ * queued.  A level context encrypts at its own level, as it does with cn_encrypt (its slice of the secret key). */
+int cn_encrypt_symmetric(cn_ctx *ctx, cn_handle pt, uint32_t pi, uint32_t pt_stride, cn_handle out, uint32_t oi, uint32_t count, uint64_t seed,
+                         const uint8_t *a_seed32, uint64_t a_nonce, uint64_t a_item0);
+/* writes poly 1 of the size-2 ciphertexts h[first .. first + count) from the seed; poly 0 is left alone.  Needs no key; works on level contexts (limbs are
+ * independent: a level's c1 is the first limbs of its parent's).  Asynchronous on the context stream; CN_ERR_ARG while a graph is recorded. */
+int cn_ct_expand(cn_ctx *ctx, cn_handle h, uint32_t first, uint32_t count, const uint8_t *a_seed32, uint64_t a_nonce, uint64_t a_item0);
+/* host_c0 [count][k][N] -> poly 0 of h[first ..) with ONE strided copy, then the expansion of poly 1 on the context stream; synchronises like cn_ct_upload */
+int cn_ct_upload_compact(cn_ctx *ctx, cn_handle h, uint32_t first, uint32_t count, const uint64_t *host_c0, const uint8_t *a_seed32, uint64_t a_nonce,
+                         uint64_t a_item0);
+/* poly 0 of the size-2 ciphertexts h[first ..) -> host [count][k][N]; synchronises */
+int cn_ct_download_compact(cn_ctx *ctx, cn_handle h, uint32_t first, uint32_t count, uint64_t *host);
 /* Decryptor.Decrypt of size-2 or size-3 ciphertexts into dense plaintexts */
 int cn_decrypt(cn_ctx *ctx, cn_handle ct, uint32_t ci, uint32_t count, cn_handle pt_out, uint32_t pi);
 /* Decryptor.InvariantNoiseBudget as CryptoTracker.TestBudget probes it (HE Wrapper/CryptoTracker.cs:41-52, BaseLayer.cs:37): writes the
