@@ -46,6 +46,17 @@ DEV uint64_t scale_plain(const DevConsts *C, uint64_t m, uint32_t j) {       // 
 // element-wise exact-FP64 modular arithmetic (per-coefficient kernels: GEMM fold, BEHZ extend / floor)
 typedef ArF64T<1> BzF;
 DEV double bz_canon(double x, const BzF::Mod &m) { double r = BzF::center(x, m); return r < 0.0 ? __dadd_rn(r, m.q) : r; }
+// Lazy-FP64 hand-off of the tensor limbs (scratch arrays dq / db of a multiplication: producers k_square_pipe, k_square_fused, k_intt_tensor on an FP64
+// policy; only consumer k_behz_floor_f64<.., LZ = true>).  A word is the BIT PATTERN of the double the inverse transform left in its register: an exact
+// integer x with x == N d (mod p) - WITHOUT the 1/N factor, not canonical - instead of the canonical residue d.  Size and layout of the arrays are unchanged.
+// The floor's first act on every input word is mulmod(x, constant): with the constants DevConsts::bd.fl_c1n_q / fl_Tn_bsk (= the plain ones times N^-1) it
+// obtains a value congruent to the one it computed from the canonical word, and it canonicalises (q limbs: bz_canon) or only re-reduces (Bsk limbs) that
+// value exactly as before - the words it writes are the same.  What the producers no longer do per word: mulmod by N^-1 (6 FP64) and to_u64 (~8 VALU).
+// Bound chain: ntt_inverse_regs leaves |x| <= 8.5 p under ArF64T<0> and ArF64T<1> alike (its last pass starts from |x| <= p/2 and runs at most four stages:
+// the sum path doubles, 16 p/2 = 8 p, plus the lazy products on the way); mulmod(y, w) is exact for |y| <= 16 p, w < p < 2^49 (cn_ntt_core.hip.h) and returns
+// |r| <= (1/2 + 0.1875 * 8.5) p < 2.1 p - the per-term bound the floor's sums (<= 7 terms between two recentrings, 14.7 p < 2^53 / p) already assume.
+DEV uint64_t lazy_word(double v) { return (uint64_t)__double_as_longlong(v); }
+DEV double lazy_value(uint64_t w) { return __longlong_as_double((long long)w); }
 // ------------------------------------------------------------------ register-radix NTT kernels (N = 2^L, L = 10..14)
 DEV uint64_t modulus_of(const DevConsts *C, uint32_t mod) { return mod < C->k ? C->q[mod].q : (mod < C->k + C->kb ? C->bsk[mod - C->k].q : C->t.q); }
 

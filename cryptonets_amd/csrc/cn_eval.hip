@@ -380,7 +380,8 @@ API_END }
 
 // ---------------------------------------------------------------- BEHZ multiply / key switching
 // tensor product fused into the inverse transform (register-radix sizes only); returns false when the caller must fall back
-bool run_intt_tensor(cn_ctx *c, const uint64_t *A, const uint64_t *B, uint64_t *D, uint32_t cnt, uint32_t base_off, uint32_t Lm) {
+// lazy: D leaves as lazy-FP64 hand-off words for k_behz_floor_f64<.., true> (the caller checked cn_behz_lazy: every modulus takes an FP64 policy)
+bool run_intt_tensor(cn_ctx *c, const uint64_t *A, const uint64_t *B, uint64_t *D, uint32_t cnt, uint32_t base_off, uint32_t Lm, bool lazy) {
     if (c->opt.legacy_ntt || c->hc.logn < 10 || c->hc.logn > 14) return false;
     bool f64 = c->opt.f64, light = true;
     for (uint32_t m = base_off; m < base_off + Lm; m++) {
@@ -388,7 +389,8 @@ bool run_intt_tensor(cn_ctx *c, const uint64_t *A, const uint64_t *B, uint64_t *
         uint64_t q = m < c->hc.k ? c->hc.q[m].q : c->hc.bsk[m - c->hc.k].q;
         if (q >> 44) light = false;
     }
-    bool ok = rr_ops[f64 && light ? POL_F64L : (f64 ? POL_F64 : POL_U64)]->intt_tensor(c, A, B, D, cnt, base_off, Lm);
+    if (lazy && !f64) return false;
+    bool ok = rr_ops[f64 && light ? POL_F64L : (f64 ? POL_F64 : POL_U64)]->intt_tensor(c, A, B, D, cnt, base_off, Lm, lazy);
     if (ok) { launch_count(c); c->st.ntt_inverse_limbs += (uint64_t)cnt * 3 * Lm; }
     return ok;
 }
@@ -450,13 +452,17 @@ int do_multiply(cn_ctx *ctx, const uint64_t *a, uint32_t astride, const uint64_t
     if ((!fused && !aq) || !ab || (!square && (!bq || !bb)) || !dq || !db) return fail(CN_ERR_HIP, "internal: scratch exhausted in multiply");
     CHECK(cn_l_behz_extend(ctx, a, astride, atab, aq, ab, cnt));
     if (!square) CHECK(cn_l_behz_extend(ctx, b, bstride, btab, bq, bb, cnt));
+    // dq / db reach the floor as lazy-FP64 hand-off words (lazy_word, cn_dev_common.hip.h) when the tensor kernels of BOTH bases and the floor are on the
+    // FP64 policy - the fused squaring kernels always (`fused` implies it), k_intt_tensor when asked; the element-wise fall-back writes canonical words
+    bool lazy = cn_behz_lazy(ctx);
     if (fused) {
         run_square_fused(ctx, a, (size_t)astride * 2 * k * n, atab, dq, cnt, 0, k, lq);
         run_square_fused(ctx, ab, (size_t)2 * kb * n, nullptr, db, cnt, k, kb, lb);
     } else {
     CHECK(cn_run_ntt(ctx, aq, cnt * 2 * k, 0, k, 0)); CHECK(cn_run_ntt(ctx, ab, cnt * 2 * kb, k, kb, 0));
     if (!square) { CHECK(cn_run_ntt(ctx, bq, cnt * 2 * k, 0, k, 0)); CHECK(cn_run_ntt(ctx, bb, cnt * 2 * kb, k, kb, 0)); }
-    if (!run_intt_tensor(ctx, aq, bq, dq, cnt, 0, k) || !run_intt_tensor(ctx, ab, bb, db, cnt, k, kb)) {
+    if (!run_intt_tensor(ctx, aq, bq, dq, cnt, 0, k, lazy) || !run_intt_tensor(ctx, ab, bb, db, cnt, k, kb, lazy)) {
+        lazy = false;
         hipLaunchKernelGGL(k_tensor, dim3(cnt * k * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, aq, bq, dq, ctx->dc, ctx->chunks, k, 0u);
         hipLaunchKernelGGL(k_tensor, dim3(cnt * kb * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, ab, bb, db, ctx->dc, ctx->chunks, kb, k);
         HIPCHK(hipGetLastError()); launch_count(ctx, 2);
@@ -464,7 +470,7 @@ int do_multiply(cn_ctx *ctx, const uint64_t *a, uint32_t astride, const uint64_t
     }
     }
     HIPCHK(hipGetLastError());
-    CHECK(cn_l_behz_floor(ctx, dq, db, out3, cnt));
+    CHECK(cn_l_behz_floor(ctx, dq, db, out3, cnt, lazy));
     ctx->st.Multiplication += cnt;
     return 0;
 }

@@ -53,6 +53,9 @@ struct DevConsts {
         double mt_inv_qhat_q[CN_MAXK], ex_R_bsk[CN_MAXK + 1], ex_Q_bsk[CN_MAXK + 1][CN_MAXK];
         double fl_c1_q[CN_MAXK], fl_T_bsk[CN_MAXK + 1], fl_N_bsk[CN_MAXK + 1][CN_MAXK];
         double inv_bhat_b[CN_MAXK], fl_A_msk[CN_MAXK], inv_B_msk, bhat_q[CN_MAXK][CN_MAXK], B_q[CN_MAXK];
+        // the two constants the floor multiplies its INPUT words with, times N^-1: fl_c1_q[j] N^-1 mod q_j, fl_T_bsk[b] N^-1 mod b.  With them the floor
+        // takes the tensor limbs as the inverse transform leaves them (lazy doubles without the 1/N factor, see lazy_word in cn_dev_common.hip.h)
+        double fl_c1n_q[CN_MAXK], fl_Tn_bsk[CN_MAXK + 1];
     } bd;
     // decryption with the {t, gamma} BEHZ rounding (SEAL decryptor.cpp)
     DMod gamma;

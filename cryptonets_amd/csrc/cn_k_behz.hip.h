@@ -73,7 +73,9 @@ __global__ void __launch_bounds__(256) k_behz_extend_f64(const uint64_t *__restr
         ob[(size_t)b * n] = BzF::to_u64(acc, mb);
     }
 }
-template <int K, int NB = K>
+// LZ: the tensor limbs arrive in the lazy-FP64 hand-off format (lazy_word, cn_dev_common.hip.h): doubles without the 1/N factor, |x| <= 8.5 p, and the
+// two input constants carry N^-1 (bd.fl_c1n_q, bd.fl_Tn_bsk).  Every later step is the same; so are the words written.
+template <int K, int NB = K, bool LZ = false>
 __global__ void __launch_bounds__(256) k_behz_floor_f64(const uint64_t *__restrict__ dq, const uint64_t *__restrict__ db, uint64_t *__restrict__ out,
                                                         const DevConsts *__restrict__ C, uint32_t chunks) {
     const uint32_t n = C->n;
@@ -84,12 +86,14 @@ __global__ void __launch_bounds__(256) k_behz_floor_f64(const uint64_t *__restri
 #pragma unroll
     for (int j = 0; j < K; j++) {
         const BzF::Mod mq = {C->qd[j], C->qinvd[j]};
-        y[j] = bz_canon(BzF::mulmod(BzF::from_u64(xq[(size_t)j * n]), C->bd.fl_c1_q[j], mq), mq);     // [x t (q/q_j)^-1]_{q_j}, canonical
+        const double x = LZ ? lazy_value(xq[(size_t)j * n]) : BzF::from_u64(xq[(size_t)j * n]);
+        y[j] = bz_canon(BzF::mulmod(x, LZ ? C->bd.fl_c1n_q[j] : C->bd.fl_c1_q[j], mq), mq);           // [x t (q/q_j)^-1]_{q_j}, canonical
     }
 #pragma unroll
     for (int b = 0; b <= NB; b++) {
         const BzF::Mod mb = {C->qd[K + b], C->qinvd[K + b]};
-        double acc = BzF::mulmod(BzF::from_u64(xb[(size_t)b * n]), C->bd.fl_T_bsk[b], mb);          // (x_b t - conv_b) q^-1, folded
+        const double x = LZ ? lazy_value(xb[(size_t)b * n]) : BzF::from_u64(xb[(size_t)b * n]);
+        double acc = BzF::mulmod(x, LZ ? C->bd.fl_Tn_bsk[b] : C->bd.fl_T_bsk[b], mb);                 // (x_b t - conv_b) q^-1, folded
 #pragma unroll
         for (int j = 0; j < K; j++) {
             acc = __dadd_rn(acc, BzF::mulmod(y[j], C->bd.fl_N_bsk[b][j], mb));

@@ -41,7 +41,8 @@ __global__ void __launch_bounds__(NttPlan<L>::NT) k_ntt_rr(uint64_t *data, const
 // BEHZ step 2 fused into the inverse transform: block = (ciphertext, output poly p of the tensor product, limb).  The NTT-form
 // operands are read at the positions the inverse transform starts from (16 B/lane), d_p = a0*b0 | a0*b1 + a1*b0 | a1*b1 is formed
 // in registers and transformed back at once - the 3-poly NTT-form tensor never exists in HBM (saves one write + one read of
-// 3(k + k+1) limbs per ciphertext and a kernel).  A, B: [cnt][2][Lm][N]; D: [cnt][3][Lm][N] (coefficient form, canonical).
+// 3(k + k+1) limbs per ciphertext and a kernel).  A, B: [cnt][2][Lm][N]; D: [cnt][3][Lm][N] (coefficient form, canonical; `lazy`, FP64
+// policies: lazy-FP64 hand-off words for the FP64 floor instead - lazy_word, cn_dev_common.hip.h).
 // Dense MultiplyPlain on the register-radix core, two launches instead of six (lift, transform, copy, transform, dyadic, transform):
 //   k_lift_ntt:        block = (plaintext, limb j): coefficients mod t -> fast plain lift into q_j -> forward transform -> NTT form
 //   k_mul_plain_fused: block = (ciphertext, poly, limb j): forward transform, pointwise product with the plaintext's NTT form (read at
@@ -167,7 +168,7 @@ __global__ void __launch_bounds__(NttPlan<L>::NT) k_mul_plain_fused(const uint64
 
 template <int L, class AR>
 __global__ void __launch_bounds__(NttPlan<L>::NT) k_intt_tensor(const uint64_t *__restrict__ A_, const uint64_t *__restrict__ B_, uint64_t *__restrict__ D,
-                                                                const DevConsts *__restrict__ C, uint32_t base_off, uint32_t Lm) {
+                                                                const DevConsts *__restrict__ C, uint32_t base_off, uint32_t Lm, uint32_t lazy) {
     typedef typename AR::T T;
     extern __shared__ __align__(16) unsigned char smem[];
     T *s = reinterpret_cast<T *>(smem);
@@ -199,12 +200,20 @@ __global__ void __launch_bounds__(NttPlan<L>::NT) k_intt_tensor(const uint64_t *
     }
     ntt_inverse_regs<AR, L>(v, s, A.iv, A.m, tid);
     uint64_t *o = D + ((size_t)ct * 3 + p) * Ln + (size_t)l * n;
+    if constexpr (std::is_same<T, double>::value) {
+        if (lazy) {                                              // (uniform) the FP64 floor reads the registers as they are: lazy_word, cn_dev_common.hip.h
+#pragma unroll
+            for (int r = 0; r < 16; r++) o[pass_index<L, SA, 0>(tid, r)] = lazy_word(v[r]);
+            return;
+        }
+    }
 #pragma unroll
     for (int r = 0; r < 16; r++) o[pass_index<L, SA, 0>(tid, r)] = A.scaled(v[r]);
 }
 
 // BEHZ steps 2-4 of a SQUARING in one kernel (FP64 policies): block = (ciphertext, limb) of the q or the Bsk base.  The operand polys
-// a0, a1 arrive in COEFFICIENT form (k_behz_extend's output) and the tensor (a0^2, 2 a0 a1, a1^2) leaves in coefficient form:
+// a0, a1 arrive in COEFFICIENT form (k_behz_extend's output) and the tensor (a0^2, 2 a0 a1, a1^2) leaves in coefficient form, as lazy-FP64 hand-off words
+// (lazy_word, cn_dev_common.hip.h: the inverse transforms' registers, N times the coefficient - only k_behz_floor_f64<.., true> reads them):
 //     step 0:  A0 = NTT(a0) -> parked in d1's place;               d0 = INTT(A0^2)
 //     step 1:  A1 = NTT(a1) -> parked in d2's place;  A0 back;     d1 = INTT(2 A0 A1)   (overwrites the parked A0)
 //     step 2:  A1 back;                                            d2 = INTT(A1^2)      (overwrites the parked A1)
@@ -304,7 +313,7 @@ __global__ void __launch_bounds__(NttPlan<L>::NT, PLDS ? 2 : 4) k_square_fused(c
         uint32_t to = tid;
         asm volatile("" : "+v"(to));
 #pragma unroll
-        for (int r = 0; r < 16; r++) o[pass_index<L, SA, 0>(to, r)] = A.scaled(v[r]);
+        for (int r = 0; r < 16; r++) o[pass_index<L, SA, 0>(to, r)] = lazy_word(v[r]);   // no N^-1, no canonicalisation: the floor's constants carry them
     }
 }
 // The same squaring as a PIPELINED, RESIDENT kernel (round 4; N <= 8192, FP64 policies).  k_square_fused<.., PLDS> runs at 0.5 of its FP64 issue
@@ -399,7 +408,7 @@ __global__ void __launch_bounds__(NttPlan<L>::NT, 2) k_square_pipe(const uint64_
             uint32_t to = tid;
             asm volatile("" : "+v"(to));
 #pragma unroll
-            for (int r = 0; r < 16; r++) o[pass_index<L, SA, 0>(to, r)] = A.scaled(v[r]);
+            for (int r = 0; r < 16; r++) o[pass_index<L, SA, 0>(to, r)] = lazy_word(v[r]);   // no N^-1, no canonicalisation: the floor's constants carry them
         }
     }
 }

@@ -9,8 +9,9 @@ template <int K, int NB> static void launch_extend(cn_ctx *c, const uint64_t *sr
     if (c->hc.behz_f64 && c->opt.f64) hipLaunchKernelGGL((k_behz_extend_f64<K, NB>), dim3(cnt * 2 * c->chunks), dim3(c->bs), 0, c->stream, src, stride, tab, aq, ab, c->dc, c->chunks);
     else hipLaunchKernelGGL((k_behz_extend<K, NB>), dim3(cnt * 2 * c->chunks), dim3(c->bs), 0, c->stream, src, stride, tab, aq, ab, c->dc, c->chunks);
 }
-template <int K, int NB> static void launch_floor(cn_ctx *c, const uint64_t *dq, const uint64_t *db, uint64_t *out, uint32_t cnt) {
-    if (c->hc.behz_f64 && c->opt.f64) hipLaunchKernelGGL((k_behz_floor_f64<K, NB>), dim3(cnt * 3 * c->chunks), dim3(c->bs), 0, c->stream, dq, db, out, c->dc, c->chunks);
+template <int K, int NB> static void launch_floor(cn_ctx *c, const uint64_t *dq, const uint64_t *db, uint64_t *out, uint32_t cnt, bool lazy) {
+    if (lazy) hipLaunchKernelGGL((k_behz_floor_f64<K, NB, true>), dim3(cnt * 3 * c->chunks), dim3(c->bs), 0, c->stream, dq, db, out, c->dc, c->chunks);
+    else if (c->hc.behz_f64 && c->opt.f64) hipLaunchKernelGGL((k_behz_floor_f64<K, NB>), dim3(cnt * 3 * c->chunks), dim3(c->bs), 0, c->stream, dq, db, out, c->dc, c->chunks);
     else hipLaunchKernelGGL((k_behz_floor<K, NB>), dim3(cnt * 3 * c->chunks), dim3(c->bs), 0, c->stream, dq, db, out, c->dc, c->chunks);
 }
 #define DISPATCH_K(fn, ...) do { \
@@ -29,8 +30,10 @@ int cn_l_behz_extend(cn_ctx *c, const uint64_t *src, uint32_t stride, const uint
     HIPCHK(hipGetLastError()); cn_launch_count(c);
     return 0;
 }
-int cn_l_behz_floor(cn_ctx *c, const uint64_t *dq, const uint64_t *db, uint64_t *out, uint32_t cnt) {
-    DISPATCH_K(launch_floor, c, dq, db, out, cnt);
+// lazy: dq / db hold the lazy-FP64 hand-off words of an FP64 tensor kernel (cn_behz_lazy(c) must hold), else canonical residues
+int cn_l_behz_floor(cn_ctx *c, const uint64_t *dq, const uint64_t *db, uint64_t *out, uint32_t cnt, bool lazy) {
+    if (lazy && !cn_behz_lazy(c)) return cn_fail(CN_ERR_ARG, "internal: lazy tensor words without the FP64 floor");
+    DISPATCH_K(launch_floor, c, dq, db, out, cnt, lazy);
     HIPCHK(hipGetLastError()); cn_launch_count(c);
     return 0;
 }

@@ -233,13 +233,34 @@ template <class AR, int L, int S, int S0> NTT_DEV void inv_stages(typename AR::T
         }
     }
 }
+// The 16 image positions of a thread in one exchange are ONE base plus compile-time constants: pass_index composes its result from disjoint bit fields of
+// tid and r (tid < NT = 2^(L-4), so (r >> S) NT + tid has no carry either), hence pass_index(tid, r) = pass_index(tid, 0) + pass_index(0, r) without a carry
+// into any bit, and lds_pos(a + b) = lds_pos(a) + lds_pos(b) for such a sum.  Written this way the compiler emits one address register per exchange and
+// the `offset:` field of ds_read / ds_write; from lds_pos(pass_index(tid, r)) it rebuilt every address with 3 - 4 VALU instructions (or / shift / and /
+// add3: ~120 of the 253 non-FP64 VALU instructions of a key-switch digit, profiles/ks_digit_loop_valu_buckets.md).
+// FP64 policies only: the integer kernels keep the per-access form (with one base their register allocation got worse - k_mul_plain_bcast<.., ArU64> 96 -> 146
+// VGPRs, more scratch in k_mul_plain_fused<14, ArU64>).
+template <class T> struct NttBaseOffset { static constexpr bool value = false; };
+template <> struct NttBaseOffset<double> { static constexpr bool value = true; };
 template <class T, int L, int S, int S0> NTT_DEV void lds_put(const T (&x)[16], T *s, uint32_t tid) {
+    if constexpr (NttBaseOffset<T>::value) {
+        T *b = s + lds_pos(pass_index<L, S, S0>(tid, 0));
 #pragma unroll
-    for (int r = 0; r < 16; r++) s[lds_pos(pass_index<L, S, S0>(tid, r))] = x[r];
+        for (int r = 0; r < 16; r++) b[lds_pos(pass_index<L, S, S0>(0u, r))] = x[r];
+    } else {
+#pragma unroll
+        for (int r = 0; r < 16; r++) s[lds_pos(pass_index<L, S, S0>(tid, r))] = x[r];
+    }
 }
 template <class T, int L, int S, int S0> NTT_DEV void lds_get(T (&x)[16], const T *s, uint32_t tid) {
+    if constexpr (NttBaseOffset<T>::value) {
+        const T *b = s + lds_pos(pass_index<L, S, S0>(tid, 0));
 #pragma unroll
-    for (int r = 0; r < 16; r++) x[r] = s[lds_pos(pass_index<L, S, S0>(tid, r))];
+        for (int r = 0; r < 16; r++) x[r] = b[lds_pos(pass_index<L, S, S0>(0u, r))];
+    } else {
+#pragma unroll
+        for (int r = 0; r < 16; r++) x[r] = s[lds_pos(pass_index<L, S, S0>(tid, r))];
+    }
 }
 // last pass layout.  D = 2 (and NTT_TAIL_LOCAL = 0): register r holds coefficient  (c << D) + (r & (2^D - 1)),  c = tid + NT * (r >> D)
 // - consecutive lanes own consecutive 16 B across the whole limb, which needs a workgroup exchange.

@@ -254,8 +254,8 @@ struct FoldTerm { double w; uint32_t enc, pad; };                       // centr
 struct RrOps {                // register-radix kernels of one arithmetic policy; every launcher returns false when the size has no kernel
     int (*set_attrs)(uint32_t logn, size_t lds);
     bool (*ntt)(cn_ctx *c, uint64_t *data, uint32_t limbs, uint32_t base_off, uint32_t nmod, int inverse);
-    bool (*intt_tensor)(cn_ctx *c, const uint64_t *A, const uint64_t *B, uint64_t *D, uint32_t cnt, uint32_t base_off, uint32_t Lm);
-    bool (*square_fused)(cn_ctx *c, const uint64_t *A, size_t astride, const uint64_t *const *atab, uint64_t *D, uint32_t cnt, uint32_t base_off, uint32_t Lm);   // FP64 policies
+    bool (*intt_tensor)(cn_ctx *c, const uint64_t *A, const uint64_t *B, uint64_t *D, uint32_t cnt, uint32_t base_off, uint32_t Lm, bool lazy);   // lazy (FP64 policies): D as lazy-FP64 hand-off words
+    bool (*square_fused)(cn_ctx *c, const uint64_t *A, size_t astride, const uint64_t *const *atab, uint64_t *D, uint32_t cnt, uint32_t base_off, uint32_t Lm);   // FP64 policies; D: lazy-FP64 hand-off words
     bool (*mul_plain_fused)(cn_ctx *c, const uint64_t *pt, uint32_t pitch, uint32_t npt, uint64_t *lift, const uint64_t *src, size_t sstride, uint32_t pstride,
                             uint64_t *out, uint32_t count, uint32_t polys);
     bool (*enc_tail)(cn_ctx *c, const uint64_t *u, const uint64_t *pt, uint32_t pts, uint64_t *out, uint32_t cnt, const int8_t *noise, const void *tab);   // U64, F64; tab: EncTab[cnt] or null
@@ -275,7 +275,10 @@ extern const KsOps cn_ks_u64, cn_ks_f64, cn_ks_f64l;
 
 // BEHZ element-wise steps (cn_l_behz.hip); src_tab: one source address per ciphertext instead of src + ct*stride*2kN
 int cn_l_behz_extend(cn_ctx *c, const uint64_t *src, uint32_t stride, const uint64_t *const *src_tab, uint64_t *aq, uint64_t *ab, uint32_t cnt);
-int cn_l_behz_floor(cn_ctx *c, const uint64_t *dq, const uint64_t *db, uint64_t *out, uint32_t cnt);
+int cn_l_behz_floor(cn_ctx *c, const uint64_t *dq, const uint64_t *db, uint64_t *out, uint32_t cnt, bool lazy);
+// the FP64 floor runs, so FP64 tensor kernels may hand it their inverse transforms' registers (lazy_word, cn_dev_common.hip.h): both element-wise BEHZ steps
+// and - every modulus being below 2^49 - the transforms of BOTH bases are on an FP64 policy
+inline bool cn_behz_lazy(const cn_ctx *c) { return c->hc.behz_f64 && c->opt.f64; }
 
 // scalar GEMM (cn_l_gemm.hip).  Relative addressing: input / output ciphertext = base + index * ctw; absolute (ABS): the tables hold
 // device addresses (deferred per-ciphertext calls: every ciphertext is its own array), 0 = padded tap / no output.

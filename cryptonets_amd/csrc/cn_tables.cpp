@@ -312,6 +312,9 @@ void cn_build_f64_tables(DevConsts *c, const uint64_t *tw_host, double *twd_host
             for (uint32_t i = 0; i < k; i++) { c->bd.ex_Q_bsk[b][i] = (double)c->ex_Q_bsk[b][i]; c->bd.fl_N_bsk[b][i] = (double)c->fl_N_bsk[b][i]; }
         }
         c->bd.inv_B_msk = (double)c->inv_B_msk;
+        // lazy hand-off tensor -> floor: the 1/N of the inverse transforms folded into the floor's input constants (ninv[m]: m = j, k + b)
+        for (uint32_t i = 0; i < k; i++) c->bd.fl_c1n_q[i] = (double)mulm(c->fl_c1_q[i], c->ninv[i], c->q[i].q);
+        for (uint32_t b = 0; b <= nb; b++) c->bd.fl_Tn_bsk[b] = (double)mulm(c->fl_T_bsk[b], c->ninv[k + b], c->bsk[b].q);
     }
 }
 

@@ -52,10 +52,11 @@ def loops(ins):
     """{header address: [addresses of its back edges]}: backward branches, minus the compiler's out-of-line trampolines (an s_branch that
     directly follows another s_branch is the landing pad of a forward conditional branch jumping back into the body, not a loop)"""
     out = {}
+    end = min([a for a, op, _ in ins if op == "s_endpgm"] or [ins[-1][0]])      # blocks the compiler places behind the kernel's end jump back into it: no loops
     for k, (addr, op, args) in enumerate(ins):
         if op.startswith("s_cbranch") or op == "s_branch":
             m = re.search(r"(-?\d+)", args)
-            if not m or (op == "s_branch" and k and ins[k - 1][1] == "s_branch"):
+            if not m or addr > end or (op == "s_branch" and k and ins[k - 1][1] == "s_branch"):
                 continue
             nxt = ins[k + 1][0] if k + 1 < len(ins) else addr + 4
             off = int(m.group(1))
@@ -105,6 +106,104 @@ def valu_per_thread(digits_per_limb, s):
     return sum(d * s["valu_digit_loop"] + s["valu_limb_loop_only"] for d in digits_per_limb) + 2 * s["valu_tail_loop"] + s["valu_once"]
 
 
+def digit_loop(obj=None, kernel=KERNEL):
+    """the instructions of the digit loop (header .. the nearer back edge), in program order"""
+    obj = obj or os.path.join(ROOT, "cryptonets_amd", "lib", "obj", "cn_l_ks_f64l.o")
+    ins = disassemble(obj, kernel)
+    is64 = lambda op: op.startswith("v_") and "_f64" in op
+    big = sorted((h, sorted(e)) for h, e in loops(ins).items() if sum(h <= a <= max(e) and is64(op) for a, op, _ in ins) > 100)
+    h1, edges = big[1] if len(big) == 3 else big[0]
+    return [i for i in ins if h1 <= i[0] <= edges[0]]
+
+
+def _regs(tok):
+    """VGPR numbers named by one operand"""
+    m = re.match(r"^-?\|?v\[(\d+):(\d+)\]", tok)
+    if m:
+        return list(range(int(m.group(1)), int(m.group(2)) + 1))
+    m = re.match(r"^-?\|?v(\d+)\b", tok)
+    return [int(m.group(1))] if m else []
+
+
+BUCKETS = ("digit extraction", "u64 -> f64 image", "LDS address arithmetic (exchanges, LDS twiddles)", "key address arithmetic", "register moves", "other")
+
+
+def digit_loop_buckets(obj=None, kernel=KERNEL):
+    """The non-FP64 VALU instructions of one digit, by what their result is used for.  A backward slice over the loop body (one basic block but for the
+    recentring that runs every `accmax` terms): the address operands of ds_* instructions and of global loads, and the operands of FP64 instructions, are the
+    sinks; an integer instruction belongs to the sink its result reaches first (walking up from the end of the body).  Inside the FP64 slice the
+    shifts and masks are the digit extraction and the `or` with the exponent pattern 0x43300000 is the u64 -> f64 image."""
+    body = digit_loop(obj, kernel)
+    want, out = {}, {b: 0 for b in BUCKETS}
+    hist = {b: {} for b in BUCKETS}
+    for addr, op, args in reversed(body):
+        toks = [t.strip() for t in args.split(",")] if args else []
+        if op.startswith("ds_") or op.startswith("global_") or op.startswith("flat_"):
+            store = "write" in op or "store" in op
+            a = toks[0] if (store or op.startswith("ds_write")) else (toks[1] if len(toks) > 1 else "")
+            if op.startswith("global_load") or op.startswith("flat_load") or op.startswith("ds_read"):
+                a = toks[1] if len(toks) > 1 else ""
+                for r in _regs(toks[0]):
+                    want.pop(r, None)
+            for r in _regs(a):
+                want[r] = BUCKETS[2] if op.startswith("ds_") else BUCKETS[3]
+            continue
+        if not op.startswith("v_"):
+            continue
+        dst, src = _regs(toks[0]) if toks else [], [r for t in toks[1:] for r in _regs(t)]
+        if "_f64" in op:
+            for r in dst:
+                want.pop(r, None)
+            for r in src:
+                want.setdefault(r, "value")
+            continue
+        if op.startswith("v_readfirstlane"):
+            continue
+        use = next((want[r] for r in dst if r in want), None)
+        for r in dst:
+            want.pop(r, None)
+        if op.startswith("v_mov") or op.startswith("v_accvgpr"):
+            b = BUCKETS[4]
+        elif use == "value":
+            b = BUCKETS[1] if (op.startswith("v_or") and "0x4330" in args) else BUCKETS[0]
+        elif use in (BUCKETS[2], BUCKETS[3]):
+            b = use
+        else:
+            b = BUCKETS[5]
+        out[b] += 1
+        hist[b][op] = hist[b].get(op, 0) + 1
+        for r in src:
+            want.setdefault(r, use if use else "other")
+    return out, hist
+
+
+def resources(obj, pattern):
+    """{kernel symbol: (VGPRs, AGPRs, SGPRs, scratch bytes, LDS bytes)} of the kernels whose mangled name contains `pattern`, from the code object's notes"""
+    with tempfile.TemporaryDirectory() as td:
+        tmp = os.path.join(td, os.path.basename(obj))
+        os.symlink(os.path.abspath(obj), tmp)
+        subprocess.check_call([OBJDUMP, "--offloading", tmp], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+        co = [f for f in glob.glob(tmp + ".*") if "amdgcn" in f]
+        txt = subprocess.check_output([os.path.join(os.path.dirname(OBJDUMP), "llvm-readelf"), "--notes", co[0]], text=True)
+    out = {}
+    for blk in txt.split("- .agpr_count:")[1:]:
+        f = lambda key: (re.search(r"\.%s:\s*(\S+)" % key, blk) or [None, "?"])[1]
+        name = f("name")
+        if pattern in name:
+            out[name] = dict(vgpr=int(f("vgpr_count")), agpr=int(blk.split()[0]), sgpr=int(f("sgpr_count")), scratch=int(f("private_segment_fixed_size")),
+                             lds=int(f("group_segment_fixed_size")))
+    return out
+
+
+def static_counts(obj, kernel):
+    """instructions / FP64 / other VALU / v_rndne_f64 (one per modular product or recentring) in the whole kernel body, unweighted"""
+    ins = disassemble(obj, kernel)
+    return dict(instructions=len(ins), fp64=sum(op.startswith("v_") and "_f64" in op for _, op, _ in ins),
+                valu_other=sum(op.startswith("v_") and "_f64" not in op and not op.startswith("v_readfirstlane") for _, op, _ in ins),
+                rndne=sum(op.startswith("v_rndne_f64") for _, op, _ in ins))
+
+
+PIPE_KERNEL = "_Z13k_square_pipeILi13E6ArF64TILi0EEE"                 # k_square_pipe<13, ArF64T<0>>: the squaring of the CryptoNets batches
 SQUARE_KERNEL = "_Z14k_square_fusedILi13E6ArF64TILi0EELb1EE"          # k_square_fused<13, ArF64T<0>, true>: fused squaring, operand parked in LDS
 
 
@@ -174,6 +273,20 @@ def square_structure(obj=None, kernel=SQUARE_KERNEL):
 
 
 if __name__ == "__main__":
-    s = structure(sys.argv[1] if len(sys.argv) > 1 else None)
+    # python tools/ks_isa_counts.py [OBJ_DIR]: OBJ_DIR holds cn_l_ks_f64l.o / cn_l_rr_f64l.o / cn_l_behz.o of the build to read (default: the in-tree build)
+    od = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "cryptonets_amd", "lib", "obj")
+    ks, rr = os.path.join(od, "cn_l_ks_f64l.o"), os.path.join(od, "cn_l_rr_f64l.o")
+    s = structure(ks)
     print(json.dumps(s, indent=1))
-    print(json.dumps(square_structure(), indent=1))
+    print(json.dumps(square_structure(rr), indent=1))
+    print(json.dumps(dict(kernel="k_square_pipe<13, ArF64T<0>>", **static_counts(rr, PIPE_KERNEL)), indent=1))
+    b, hist = digit_loop_buckets(ks)
+    print("\nnon-FP64 VALU instructions of one digit of %s: %d" % (s["kernel"], sum(b.values())))
+    print("| bucket | instructions | opcodes |\n|---|---|---|")
+    for name in BUCKETS:
+        print("| %s | %d | %s |" % (name, b[name], ", ".join("%s x%d" % kv for kv in sorted(hist[name].items(), key=lambda kv: -kv[1]))))
+    print("\n| kernel | VGPRs | AGPRs | scratch | LDS (static) |\n|---|---|---|---|---|")
+    for obj, pat in ((ks, "k_keyswitch_rrILi13E6ArF64TILi0EE"), (rr, "k_square_pipeILi13E"), (rr, "k_square_fusedILi13E"), (rr, "k_intt_tensorILi13E"),
+                     (os.path.join(od, "cn_l_rr_f64.o"), "k_square_pipeILi13E"), (os.path.join(od, "cn_l_behz.o"), "k_behz_floor_f64ILi5ELi5E")):
+        for name, r in sorted(resources(obj, pat).items()):
+            print("| %s | %d | %d | %d | %d |" % (name, r["vgpr"], r["agpr"], r["scratch"], r["lds"]))
