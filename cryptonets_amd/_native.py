@@ -17,7 +17,7 @@ CSRC = os.path.join(_PKG, "csrc")
 SOURCES = [os.path.join(CSRC, f) for f in (
     "cn_api.hip", "cn_eval.hip", "cn_client.hip", "cn_defer.hip", "cn_multi.hip", "cn_host.cpp", "cn_tables.cpp", "cn_l_gemm.hip", "cn_l_behz.hip",
     "cn_l_rr_u64.hip", "cn_l_rr_f64.hip", "cn_l_rr_f64l.hip", "cn_l_ks_u64.hip", "cn_l_ks_f64.hip", "cn_l_ks_f64l.hip", "cn_level.hip", "cn_l_modswitch.hip",
-    "cn_l_modswitch_f64.hip", "cn_l_noise.hip", "cn_l_seeded.hip")]
+    "cn_l_modswitch_f64.hip", "cn_l_noise.hip", "cn_l_seeded.hip", "cn_l_keygen.hip")]
 OBJ_DIR = os.path.join(_PKG, "lib", "obj")
 
 U64P = C.POINTER(C.c_uint64)
@@ -181,6 +181,9 @@ SIGNATURES = {
     "cn_set_rng_key": (C.c_int, [_CTX, C.c_char_p]),
     "cn_rng_selftest": (C.c_int, [_CTX, C.c_char_p, C.c_uint64, C.c_uint64, U32P]),
     "cn_keygen": (C.c_int, [_CTX, C.c_uint64, C.c_int]),
+    "cn_keygen_galois": (C.c_int, [_CTX, C.c_uint64, U64P, _u32]),
+    "cn_galois_elts": (C.c_int, [_CTX, U64P, _u32, U32P]),
+    "cn_rotation_steps": (C.c_int, [_CTX, C.POINTER(C.c_int), _u32, U32P, C.POINTER(C.c_int)]),
     "cn_set_public_key": (C.c_int, [_CTX, U64P, C.c_size_t]),
     "cn_set_secret_key": (C.c_int, [_CTX, U64P, C.c_size_t]),
     "cn_get_key": (C.c_int, [_CTX, C.c_int, C.c_uint64, U64P, C.c_size_t]),
@@ -290,6 +293,8 @@ class Context:
             c.L, c.n, c.t, c.q, c.k = self.L, self.n, self.t, self.q[:limbs], limbs
             c.dbc, c.gdbc, c.device = self.dbc, self.gdbc, self.device
             c._adopt(h, self)
+            if self.get_option("record_steps"):                 # a level created while its parent records (networks.rotation_steps) records too, into its own list
+                c.set_option("record_steps", 1)
             self._levels[limbs] = c
         return self._levels[limbs]
 
@@ -590,6 +595,27 @@ class Context:
 
     def keygen(self, seed, galois=True):
         self._chk(self.L.cn_keygen(self._h, seed, int(galois)))
+
+    def keygen_galois(self, seed, elts):
+        """cn_keygen_galois: Galois keys for exactly the listed elements, generated by one kernel launch (needs the secret key of a keygen(...) before it)"""
+        e = np.ascontiguousarray(list(elts), dtype=np.uint64)
+        self._chk(self.L.cn_keygen_galois(self._h, seed, _p64(e), e.size))
+
+    def galois_elts(self):
+        """the Galois elements this context holds a key for, ascending (cn_galois_elts)"""
+        cnt = C.c_uint32()
+        self._chk(self.L.cn_galois_elts(self._h, None, 0, C.byref(cnt)))
+        out = np.zeros(max(1, cnt.value), dtype=np.uint64)
+        self._chk(self.L.cn_galois_elts(self._h, _p64(out), out.size, C.byref(cnt)))
+        return [int(x) for x in out[:cnt.value]]
+
+    def rotation_steps(self):
+        """(sorted distinct RotateRows steps, was a column rotation asked for) recorded since set_option("record_steps", 1) (cn_rotation_steps)"""
+        cnt, cols = C.c_uint32(), C.c_int()
+        self._chk(self.L.cn_rotation_steps(self._h, None, 0, C.byref(cnt), C.byref(cols)))
+        out = (C.c_int * max(1, cnt.value))()
+        self._chk(self.L.cn_rotation_steps(self._h, out, len(out), C.byref(cnt), C.byref(cols)))
+        return [int(out[i]) for i in range(cnt.value)], bool(cols.value)
 
     def set_public_key(self, words):
         w = np.ascontiguousarray(words, dtype=np.uint64)

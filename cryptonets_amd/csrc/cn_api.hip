@@ -375,6 +375,11 @@ extern "C" int cn_set_option(cn_ctx *ctx, const char *name, int value) { API_BOD
         HIPCHK(hipMemcpy(ctx->dc, &ctx->hc, sizeof(DevConsts), hipMemcpyHostToDevice));
         return 0;
     }
+    if (!strcmp(name, "record_steps")) {         // 1: record the RotateRows steps and column rotations asked for from now on (cn_rotation_steps); 0: stop and clear
+        ctx->rec_steps = value != 0;
+        if (!value) { ctx->rec_set.clear(); ctx->rec_cols = false; }
+        return 0;
+    }
     return fail(CN_ERR_ARG, "unknown option %s", name);
 API_END }
 // read-back of the switches and of choices the library made (tests, diagnostics)
@@ -384,6 +389,7 @@ extern "C" int cn_get_option(cn_ctx *ctx, const char *name, int *value) { API_BO
     if (const OptionSpec *o = find_option(name)) *value = ctx->opt.*o->member;
     else if (!strcmp(name, "defer")) *value = ctx->defer.load(std::memory_order_relaxed);
     else if (!strcmp(name, "ks_xi")) *value = (int)ctx->hc.ks_xi;
+    else if (!strcmp(name, "record_steps")) *value = ctx->rec_steps;
     // read-only diagnostics: choices the library made and counters (tests)
     else if (!strcmp(name, "pin_laps")) *value = (int)ctx->pin_laps;                      // laps of the pinned upload ring (each one waits for the stream)
     else if (!strcmp(name, "ready_handles")) *value = (int)ctx->ready->size();          // allocated single-ciphertext arrays waiting for a lock-free cn_ct_alloc

@@ -261,6 +261,24 @@ int ring_sync(cn_ctx *ctx, bool report);
 int ring_push(cn_ctx *ctx, uint32_t type, uint32_t count, cn_handle a, uint32_t ai, cn_handle b, uint32_t bi, cn_handle out, uint32_t oi, uint32_t x, uint64_t arg);
 int raw_ntt(cn_ctx *ctx, void *p, uint32_t limbs, int base, int inverse);
 
+// cn_set_option("record_steps", 1): the steps / column rotations a caller asks for, noted by the entry points before any NAF split (cn_rotation_steps)
+static inline void rec_rows(cn_ctx *ctx, int steps) { if (ctx->rec_steps && steps) ctx->rec_set.insert(steps); }
+static inline void rec_columns(cn_ctx *ctx) { if (ctx->rec_steps) ctx->rec_cols = true; }
+static inline void rec_sum_slots(cn_ctx *ctx, uint32_t length) {          // the chain of sum_slots_impl
+    if (!ctx->rec_steps) return;
+    const uint32_t n = ctx->hc.n, half = n / 2;
+    uint32_t len = length ? length : n;
+    if (len >= half) { ctx->rec_cols = true; len = half; }
+    for (uint32_t st = 1; st < len; st *= 2) ctx->rec_set.insert(-(int)st);
+}
+static inline void rec_galois(cn_ctx *ctx, uint64_t elt) {                // cn_apply_galois: 2N - 1 = the column swap, 3^s = RotateRows(s)
+    if (!ctx->rec_steps) return;
+    const uint64_t n = ctx->hc.n, m = 2 * n;
+    if (elt == m - 1) { ctx->rec_cols = true; return; }
+    uint64_t e = 1;
+    for (uint64_t s2 = 1; s2 < n / 2; s2++) { e = (e * 3) & (m - 1); if (e == elt) { ctx->rec_set.insert(s2 <= n / 4 ? (int)s2 : (int)s2 - (int)(n / 2)); return; } }
+}
+
 #define GETCT(var, h, sz) Buffer *var = getbuf(ctx, h, 0); if (!var) return fail(CN_ERR_ARG, "invalid ciphertext handle " #h); \
     if ((sz) && var->size != (uint32_t)(sz)) return fail(CN_ERR_ARG, "ciphertext size mismatch for " #h)
 #define GETPT(var, h) Buffer *var = getbuf(ctx, h, 1); if (!var) return fail(CN_ERR_ARG, "invalid plaintext handle " #h)

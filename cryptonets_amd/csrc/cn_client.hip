@@ -182,6 +182,104 @@ extern "C" int cn_keygen(cn_ctx *ctx, uint64_t seed, int with_galois) { API_BODY
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return 0;
 API_END }
+// KeyGenerator.GaloisKeys(dbc, galois_elts) (SEAL 3.2): keys for exactly the listed elements, all of them by ONE k_ksk_gen launch behind one noise launch
+// (cn_k_keygen.hip.h) - the words cn_keygen's loop would have produced for these elements from the context's item counter on.  One allocation pass, the
+// tables of the call in one upload each, one host wait at the end (the keys that are replaced are released behind it).
+static uint32_t brev_bits(uint32_t v, uint32_t bits) { uint32_t r = 0; for (uint32_t i = 0; i < bits; i++) r |= ((v >> i) & 1u) << (bits - 1 - i); return r; }
+extern "C" int cn_keygen_galois(cn_ctx *ctx, uint64_t seed, const uint64_t *galois_elts, uint32_t cnt) { API_BODY
+    LOCK; NOT_CAPTURING("cn_keygen_galois"); NOT_LEVEL("cn_keygen_galois");
+    if (!cnt) return 0;
+    if (!galois_elts) return fail(CN_ERR_ARG, "null argument");
+    const uint32_t n = ctx->hc.n, k = ctx->hc.k, logn = ctx->hc.logn, tot = ctx->hc.gk_tot;
+    if (logn < 10 || logn > 14) return fail(CN_ERR_ARG, "cn_keygen_galois needs 1024 <= N <= 16384");
+    for (uint32_t g = 0; g < cnt; g++) {
+        if (!(galois_elts[g] & 1) || galois_elts[g] >= 2ull * n) return fail(CN_ERR_ARG, "invalid Galois element %llu", (unsigned long long)galois_elts[g]);
+        for (uint32_t h = 0; h < g; h++) if (galois_elts[h] == galois_elts[g]) return fail(CN_ERR_ARG, "Galois element %llu is listed twice", (unsigned long long)galois_elts[g]);
+    }
+    if (!ctx->sk) return fail(CN_ERR_NOKEY, "secret key not set");
+    const uint64_t items = (uint64_t)cnt * tot, item0 = ctx->rng_item;
+    if ((item0 + 2 * items) >> 40) return fail(CN_ERR_ARG, "the sampler's item counter would exceed the 40 item bits of the block counter");
+    // host tables: NTT-domain automorphism indices per element, message factors per entry (gen_ksk), sampler items of the noise polynomials
+    std::vector<uint16_t> perm((size_t)cnt * n), br(n);
+    for (uint32_t i = 0; i < n; i++) br[i] = (uint16_t)brev_bits(i, logn);
+    for (uint32_t g = 0; g < cnt; g++) for (uint32_t i = 0; i < n; i++) {
+        const uint64_t pt = ((2ull * br[i] + 1) * galois_elts[g]) & (2ull * n - 1);
+        perm[(size_t)g * n + i] = br[(pt - 1) >> 1];
+    }
+    std::vector<KeyFactors> fac(tot);
+    {
+        uint32_t e = 0;
+        for (uint32_t l = 0; l < k; l++) for (uint32_t d = 0; d < ctx->hc.gk_dig[l]; d++, e++) {
+            KeyFactors f{};
+            for (uint32_t j = 0; j < k; j++) {
+                if (!ctx->hc.ks_xi && j != l) continue;
+                const uint64_t qj = ctx->hc.q[j].q; unsigned __int128 v = 1;
+                for (uint32_t i = 0; i < d; i++) v = (v << ctx->hc.gdbc) % qj;
+                if (ctx->hc.ks_xi) v = v * ctx->hc.qhat_q[l][j] % qj;
+                f.f[j] = (uint64_t)v;
+            }
+            fac[e] = f;
+        }
+        if (e != tot) return fail(CN_ERR_ARG, "internal: %u Galois key entries, expected %u", e, tot);
+    }
+    std::vector<EncTab> nz(items);
+    for (uint64_t i = 0; i < items; i++) nz[i] = EncTab{nullptr, nullptr, seed, item0 + 2 * i + 1};
+    const size_t gw = cn_key_words(ctx, 1);
+    std::vector<uint64_t *> keys(cnt, nullptr);
+    auto release = [&]() { for (uint64_t *p : keys) if (p) (void)hipFree(p); };
+    for (uint32_t g = 0; g < cnt; g++) if (hipMalloc((void **)&keys[g], gw * 8) != hipSuccess) { (void)hipGetLastError(); release(); return fail(CN_ERR_HIP, "hipMalloc of a Galois key failed"); }
+    const int rc = [&]() -> int {
+        CHECK(ensure_scratch(ctx, al(items * n) + al(perm.size() * 2) + al(fac.size() * sizeof(KeyFactors)) + al(nz.size() * sizeof(EncTab)) + al(cnt * sizeof(uint64_t *)) + 1024));
+        int8_t *noise = salloc<int8_t>(ctx, items * n);
+        uint16_t *dperm = nullptr; KeyFactors *dfac = nullptr; EncTab *dnz = nullptr; uint64_t **douts = nullptr;
+        if (!noise) return fail(CN_ERR_HIP, "internal: scratch exhausted in cn_keygen_galois");
+        CHECK(upload_tmp(ctx, perm.data(), perm.size(), &dperm));
+        CHECK(upload_tmp(ctx, fac.data(), fac.size(), &dfac));
+        CHECK(upload_tmp(ctx, nz.data(), nz.size(), &dnz));
+        CHECK(upload_tmp(ctx, keys.data(), keys.size(), &douts));
+        hipLaunchKernelGGL(k_sample_small, dim3((unsigned)((items * (n / 8) + 255) / 256)), dim3(256), 0, ctx->stream, noise, n, 1, 1u, (uint32_t)items, rng_key_of(ctx), seed, 1u, item0,
+                           (const EncTab *)dnz, cn_noise_table());
+        HIPCHK(hipGetLastError()); launch_count(ctx);
+        const KskGenArgs a{douts, dfac, dperm, noise, seed, item0, cnt, tot, keys_as_f64(ctx)};
+        CHECK(cn_l_ksk_gen(ctx, a));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        return 0;
+    }();
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); release(); return rc; }
+    for (uint32_t g = 0; g < cnt; g++) {
+        KsKey &slot = ctx->gk[galois_elts[g]];
+        if (slot.owned && slot.d) (void)hipFree(slot.d);
+        slot = {keys[g], true, keys_as_f64(ctx)};
+    }
+    ctx->rng_item = item0 + 2 * items;
+    return 0;
+API_END }
+// the Galois elements this context holds a key for, ascending (a level context: the keys sliced from its parent)
+extern "C" int cn_galois_elts(cn_ctx *ctx, uint64_t *elts, uint32_t cap, uint32_t *count) { API_BODY
+    LOCK_ONLY;
+    if (!count) return fail(CN_ERR_ARG, "null argument");
+    uint32_t c = 0;
+    for (auto &kv : ctx->gk) if (kv.second.d) c++;
+    *count = c;
+    if (!elts) return 0;
+    if (cap < c) return fail(CN_ERR_ARG, "the context holds %u Galois keys, room for %u", c, cap);
+    c = 0;
+    for (auto &kv : ctx->gk) if (kv.second.d) elts[c++] = kv.first;          // (std::map: ascending)
+    return 0;
+API_END }
+// the RotateRows steps recorded since cn_set_option("record_steps", 1), ascending and distinct; *columns: was a column rotation asked for
+extern "C" int cn_rotation_steps(cn_ctx *ctx, int *steps, uint32_t cap, uint32_t *count, int *columns) { API_BODY
+    LOCK_ONLY;
+    if (!count) return fail(CN_ERR_ARG, "null argument");
+    const uint32_t c = (uint32_t)ctx->rec_set.size();
+    *count = c;
+    if (columns) *columns = ctx->rec_cols ? 1 : 0;
+    if (!steps) return 0;
+    if (cap < c) return fail(CN_ERR_ARG, "%u steps recorded, room for %u", c, cap);
+    uint32_t i = 0;
+    for (int s2 : ctx->rec_set) steps[i++] = s2;
+    return 0;
+API_END }
 // Encryptor.Encrypt (AtomicSealBfvVector.cs:1211,1227): (pk0 u + e1 + Delta m [+ r_t(q)], pk1 u + e2); pt = 0 encrypts zero.
 // tab != null: `cnt` encryptions whose outputs / plaintexts / nonces / items come from the table (host copy `htab`), else dense out / ptd
 int encrypt_chain(cn_ctx *ctx, uint32_t cnt, const uint64_t *ptd, uint32_t pt_stride_words, uint64_t *out, uint64_t seed, const EncTab *htab) {

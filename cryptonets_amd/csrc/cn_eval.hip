@@ -712,7 +712,9 @@ int galois_impl(cn_ctx *ctx, Buffer *I, uint32_t ii, uint64_t elt, Buffer *O, ui
 bool galois_key_present(cn_ctx *ctx, uint64_t elt) { auto it = ctx->gk.find(elt); return it != ctx->gk.end() && it->second.d; }
 extern "C" int cn_apply_galois(cn_ctx *ctx, cn_handle in, uint32_t ii, uint64_t elt, cn_handle out, uint32_t oi, uint32_t count) { API_BODY TWO_LIMBS("cn_apply_galois");
     LOCK; GETCT(I, in, 2); GETCT(O, out, 2);
-    return galois_impl(ctx, I, ii, elt, O, oi, count);
+    CHECK(galois_impl(ctx, I, ii, elt, O, oi, count));
+    rec_galois(ctx, elt);
+    return 0;
 API_END }
 // Evaluator::rotate_internal: direct key if present, otherwise non-adjacent-form decomposition
 bool has_direct_key(cn_ctx *ctx, int steps) {
@@ -845,10 +847,13 @@ extern "C" int cn_rotate_rows(cn_ctx *ctx, cn_handle in, uint32_t ii, int steps,
     if (deferring(ctx) && count && count <= DEFER_STAGED_MAX) {
         if (!range_ok(I, ii, count) || !range_ok(O, oi, count)) return fail(CN_ERR_ARG, "index out of range");
         CHECK(rotate_check(ctx, steps));
+        rec_rows(ctx, steps);
         return defer_staged(ctx, DOP_ROT, I, ii, nullptr, 0, nullptr, 0, O, oi, count, steps);
     }
     CHECK(cn_defer_flush(ctx));
-    return rotate_rows_impl(ctx, I, ii, steps, O, oi, count);
+    CHECK(rotate_rows_impl(ctx, I, ii, steps, O, oi, count));
+    rec_rows(ctx, steps);                                   // (a refused call leaves no step behind)
+    return 0;
 API_END }
 // RotateRows of n ciphertexts by n different step counts, one launch chain (see include/cnhip.h)
 extern "C" int cn_rotate_rows_many(cn_ctx *ctx, cn_handle in, const uint32_t *ii, const int *steps, uint32_t n, cn_handle out, const uint32_t *oi) { API_BODY TWO_LIMBS("cn_rotate_rows_many");
@@ -861,6 +866,7 @@ extern "C" int cn_rotate_rows_many(cn_ctx *ctx, cn_handle in, const uint32_t *ii
         for (uint32_t j = 0; j < i; j++) if (O == I ? (oi[i] == oi[j] || oi[i] == ii[j] || ii[i] == oi[j]) : oi[i] == oi[j])
             return fail(CN_ERR_ARG, "rotate_rows_many: a result would overwrite another rotation's operand or result");
     }
+    for (uint32_t i = 0; i < n; i++) rec_rows(ctx, steps[i]);               // (every argument has been checked)
     if (deferring(ctx)) {                                   // queued like n cn_rotate_rows calls
         for (uint32_t i = 0; i < n; i++) CHECK(defer_staged(ctx, DOP_ROT, I, ii[i], nullptr, 0, nullptr, 0, O, oi[i], 1, steps[i]));
         return 0;
@@ -913,13 +919,17 @@ extern "C" int cn_rotate_rows_add(cn_ctx *ctx, cn_handle in, uint32_t ii, int st
     if (deferring(ctx) && count && count <= DEFER_STAGED_MAX) {
         if (!range_ok(I, ii, count) || !range_ok(A, ai, count) || !range_ok(O, oi, count)) return fail(CN_ERR_ARG, "index out of range");
         CHECK(rotate_check(ctx, steps));
+        rec_rows(ctx, steps);
         return defer_staged(ctx, DOP_ROTADD, I, ii, A, ai, nullptr, 0, O, oi, count, steps);
     }
     CHECK(cn_defer_flush(ctx));
-    return rotate_rows_add_impl(ctx, I, ii, steps, A, ai, O, oi, count);
+    CHECK(rotate_rows_add_impl(ctx, I, ii, steps, A, ai, O, oi, count));
+    rec_rows(ctx, steps);
+    return 0;
 API_END }
 extern "C" int cn_rotate_columns_add(cn_ctx *ctx, cn_handle in, uint32_t ii, cn_handle acc, uint32_t ai, cn_handle out, uint32_t oi, uint32_t count) { API_BODY TWO_LIMBS("cn_rotate_columns_add");
     LOCK_ONLY; GETCT(I, in, 2); GETCT(A, acc, 2); GETCT(O, out, 2);
+    if (galois_key_present(ctx, 2ull * ctx->hc.n - 1)) rec_columns(ctx);     // (without the key the call is refused below)
     if (deferring(ctx) && count && count <= DEFER_STAGED_MAX) {
         if (!range_ok(I, ii, count) || !range_ok(A, ai, count) || !range_ok(O, oi, count)) return fail(CN_ERR_ARG, "index out of range");
         if (!galois_key_present(ctx, 2ull * ctx->hc.n - 1)) return fail(CN_ERR_NOKEY, "Galois key not present");
@@ -973,10 +983,13 @@ extern "C" int cn_sum_slots(cn_ctx *ctx, cn_handle h, uint32_t first, uint32_t c
         uint32_t len = length ? length : n;
         if (len >= half) { if (!galois_key_present(ctx, 2ull * n - 1)) return fail(CN_ERR_NOKEY, "Galois key not present"); len = half; }
         for (uint32_t st = 1; st < len; st *= 2) CHECK(rotate_check(ctx, -(int)st));
+        rec_sum_slots(ctx, length);
         return defer_staged(ctx, DOP_SUMSLOTS, H, first, nullptr, 0, nullptr, 0, H, first, count, length);
     }
     CHECK(cn_defer_flush(ctx));
-    return sum_slots_impl(ctx, H, first, count, length);
+    CHECK(sum_slots_impl(ctx, H, first, count, length));
+    rec_sum_slots(ctx, length);
+    return 0;
 API_END }
 // out[r] = SumAllSlots(v * pt[r], length) for r < rows: every row of a plaintext matrix against ONE packed ciphertext
 // (EncryptedSealBfvMatrix.Mul row-major, EncryptedSealBfvMatrix.cs:79-120 -> DotProduct, AtomicSealBfvVector.cs:963-977).
@@ -984,6 +997,7 @@ extern "C" int cn_rowdot_batch(cn_ctx *ctx, cn_handle v, uint32_t vi, cn_handle 
     LOCK; GETCT(V, v, 2); GETCT(O, out, 2); GETPT(P, pt);
     if (!rows) return 0;
     if (V == O && vi >= oi && vi < oi + rows) return fail(CN_ERR_ARG, "row-dot batch cannot overwrite its input");
+    if (length != 1) rec_sum_slots(ctx, length);
     if (length != 1 && mul_plain_takes_bcast(ctx, rows)) {
         // the product kernel hands the chain its first permuted c1 (no k_galois_limbs pass over the products): one arena for the chain's two scratch arrays and the
         // transformed ciphertext, sized here and left where it is until the chain has run
@@ -1003,6 +1017,7 @@ extern "C" int cn_rowdot_batch(cn_ctx *ctx, cn_handle v, uint32_t vi, cn_handle 
 API_END }
 extern "C" int cn_rotate_columns(cn_ctx *ctx, cn_handle in, uint32_t ii, cn_handle out, uint32_t oi, uint32_t count) { API_BODY TWO_LIMBS("cn_rotate_columns");
     LOCK_ONLY; GETCT(I, in, 2); GETCT(O, out, 2);
+    if (galois_key_present(ctx, 2ull * ctx->hc.n - 1)) rec_columns(ctx);     // (without the key the call is refused below)
     if (deferring(ctx) && count && count <= DEFER_STAGED_MAX) {
         if (!range_ok(I, ii, count) || !range_ok(O, oi, count)) return fail(CN_ERR_ARG, "index out of range");
         if (!galois_key_present(ctx, 2ull * ctx->hc.n - 1)) return fail(CN_ERR_NOKEY, "Galois key not present");

@@ -11,6 +11,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <set>
 #include <string>
 #include <type_traits>
 #include <unordered_map>
@@ -221,6 +222,9 @@ struct cn_ctx {
     // uploads; ev_ms marks the point of this context's stream the other context of a cn_mod_switch waits for; ms_f64: the last cn_mod_switch
     // this context took part in ran the exact-FP64 kernel (cn_get_option "mod_switch_f64")
     bool level = false;
+    // cn_set_option("record_steps", 1): the RotateRows steps the caller asked for (before the NAF split) and whether a column rotation was asked for (cn_rotation_steps)
+    bool rec_steps = false, rec_cols = false;
+    std::set<int> rec_set;
     hipEvent_t ev_ms = nullptr;
     bool ms_f64 = false;
 };
@@ -311,5 +315,13 @@ struct SeededArgs {
     const int8_t *noise; const uint64_t *pt; uint32_t pt_stride_words;
 };
 int cn_l_seeded(cn_ctx *c, const SeededArgs &a);
+// Galois keys for `elts` elements in one launch (cn_l_keygen.hip, k_ksk_gen): outs = one key address per element, fac = [tot] x CN_MAXK message factors (gen_ksk's
+// KeyFactors per entry), perm = [elts][N] NTT-domain automorphism indices, noise = the int8 polynomials [elts * tot][N] of k_sample_small; entry e of element g draws
+// its `a` at sampler item item0 + 2 (g tot + e)
+struct KskGenArgs {
+    const void *outs, *fac; const uint16_t *perm; const int8_t *noise;
+    uint64_t seed, item0; uint32_t elts, tot; bool f64out;
+};
+int cn_l_ksk_gen(cn_ctx *c, const KskGenArgs &a);
 
 inline void cn_launch_count(cn_ctx *c, int n = 1) { c->st.kernel_launches += n; }

@@ -108,7 +108,18 @@ class BroadcastKeys:
             ctx.set_option("ks_xi", xi)
         jobs = [(0, 0, ctx.key_words(False))]
         if with_galois:
-            jobs += [(1, e, ctx.key_words(True)) for e in default_galois_elements(ctx.n)]
+            # every Galois key the source holds (cn_galois_elts): the element list travels ahead of the keys (not counted in `bytes`).  The default set goes
+            # first, in its own order, then keys for other elements (cn_keygen_galois, uploads) ascending.  A stand-in without galois_elts holds the default set.
+            elts = None
+            if rank == src:
+                held = ctx.galois_elts() if hasattr(ctx, "galois_elts") else default_galois_elements(ctx.n)
+                first = [e for e in default_galois_elements(ctx.n) if e in set(held)]
+                elts = np.array(first + sorted(set(held) - set(first)), dtype=np.uint64)
+            cnt = broadcast_words(np.array([elts.size], dtype=np.uint64) if rank == src else None, 1, src, device, dist)
+            cnt = int(cnt.cpu().numpy().view(np.uint64)[0])
+            if cnt:
+                elts = broadcast_words(elts if rank == src else None, cnt, src, device, dist).cpu().numpy().view(np.uint64)
+                jobs += [(1, int(e), ctx.key_words(True)) for e in elts]
         for which, elt, words in jobs:
             t = broadcast_words(ctx.get_key(which, elt) if rank == src else None, words, src, device, dist)
             self.bytes += words * 8

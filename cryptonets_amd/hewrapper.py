@@ -48,7 +48,10 @@ class ClientCrypto:
     """The client-side SEAL objects of AtomicSealBfvEncryptedEnvironment.SetKeys (AtomicSealBfvVector.cs:62-74):
     KeyGenerator / Encryptor / Decryptor for ONE plaintext modulus."""
 
-    def generate_keys(self, with_galois=True):
+    def generate_keys(self, with_galois=True, steps=None, columns=True):
+        """steps: None = the default Galois key set; a list of RotateRows step counts = KeyGenerator.GaloisKeys(dbc, steps) (+ the column swap when
+        `columns`).  A client that cannot generate keys for a list of its own keeps the one-argument form: GenerateEncryptionKeys(steps=...) is
+        refused for it with a message, not with a TypeError from the call."""
         raise NotImplementedError
 
     def relin_key(self):            # u64 words, layout of include/cnhip.h
@@ -283,24 +286,31 @@ class AtomicSealBfvEncryptedEnvironment:
     def Primes(self):
         return [self.plainmodulusValue]
 
-    def GenerateEncryptionKeys(self, with_galois=True):
+    def GenerateEncryptionKeys(self, with_galois=True, steps=None):
         """KeyGenerator + SetKeys (AtomicSealBfvVector.cs:62-74,163-173): keys are made by the client, the public
-        evaluation keys are uploaded to HBM."""
-        self.client.generate_keys(with_galois)
+        evaluation keys are uploaded to HBM.  steps: None = the default Galois key set (the reference's); a list of RotateRows step counts =
+        KeyGenerator.GaloisKeys(dbc, steps), keys for exactly these rotations and the column swap (client.DeviceClient.generate_keys)."""
+        if steps is None:
+            self.client.generate_keys(with_galois)
+        else:
+            import inspect
+            if "steps" not in inspect.signature(self.client.generate_keys).parameters:
+                raise Exception("%s cannot generate Galois keys for a list of steps (its generate_keys takes no `steps`)" % type(self.client).__name__)
+            self.client.generate_keys(with_galois, steps=[int(x) for x in steps])
         rk = self.client.relin_key()
         if rk is not None:                       # a device-side client has already installed its keys in the context
             self.ctx.set_relin_key(rk)
         if with_galois:
             for elt, words in self.client.galois_keys().items():
                 self.ctx.set_galois_key(elt, words)
-        self.SelfTest(with_galois)
+        self.SelfTest(with_galois, steps=steps)
 
     # what the last SelfTest found: None (not run: the client has no evaluator of its own), or a dict
     #   {"ks_xi": 0 | 1, "key_form": "ntt" | "coeff", "ops": [names compared], "tried": [(ks_xi, key_form, first failing op or None), ...],
     #    "warnings": [key-less operations whose words differ from the client's evaluator while their decrypted slots agree]}
     self_test_report = None
 
-    def SelfTest(self, with_galois=True):
+    def SelfTest(self, with_galois=True, steps=None):
         """Start-up agreement check of the drop-in with the evaluator it replaces (the C# twin does the same at the end of
         CreateDevice, integration/GpuAtomicSealBfvEncryptedVector.cs).  Two fresh ciphertexts go through the client's own evaluator and
         through the device: MultiplyPlain (dense and constant), AddPlain, Multiply - then the key-switching operations Relinearize,
@@ -309,11 +319,14 @@ class AtomicSealBfvEncryptedEnvironment:
         and whether the NTT-form key words are in this library's transform order.  So when a key-switching operation disagrees the test
         retries with the other convention, then with coefficient-form keys (cn_load_key form 1: the device transforms them itself),
         and keeps the first combination that reproduces the client's words.  Nothing matches: an exception that names the operation -
-        never rc 0 and garbage."""
+        never rc 0 and garbage.  With keys for a caller's own steps (GenerateEncryptionKeys(steps=...)) the two row rotations are by steps of
+        that list - rotations the context can serve - and RotateColumns is compared when the column-swap key exists; what is compared does not change."""
         ev = self.client.reference_evaluator() if hasattr(self.client, "reference_evaluator") else None
         if ev is None:
             return None
         ctx, n, t = self.ctx, self.ctx.n, self.ctx.t
+        rot = (1, -1) if steps is None else tuple(dict.fromkeys(int(x) for x in steps if int(x)))[:2]
+        cols = steps is None or ctx.has_galois_key(2 * n - 1)
         # deterministic operands (the encryption randomness is the client's): slot-like values over the whole range of t
         v0 = (np.arange(n, dtype=np.uint64) * np.uint64(2654435761) + np.uint64(12345)) % np.uint64(t)
         v1 = (np.arange(n, dtype=np.uint64) * np.uint64(40503) + np.uint64(7)) % np.uint64(t)
@@ -337,10 +350,8 @@ class AtomicSealBfvEncryptedEnvironment:
                 elif op == "Relinearize":
                     ctx.multiply(h2, 0, h2, 1, h3, 0)
                     ctx.relinearize(h3, 0, o2, 0)
-                elif op == "RotateRows(1)":
-                    ctx.rotate_rows(h2, 0, 1, o2, 0)
-                elif op == "RotateRows(-1)":
-                    ctx.rotate_rows(h2, 0, -1, o2, 0)
+                elif op.startswith("RotateRows("):
+                    ctx.rotate_rows(h2, 0, int(op[11:-1]), o2, 0)
                 elif op == "RotateColumns":
                     ctx.rotate_columns(h2, 0, o2, 0)
                 return ctx.ct_download(o2, 0, 1)[0]
@@ -348,8 +359,9 @@ class AtomicSealBfvEncryptedEnvironment:
             c3 = ev.multiply(ca, cb)
             want = {"MultiplyPlain": lambda: ev.multiply_plain(ca, v1), "MultiplyPlain(constant)": lambda: ev.multiply_plain(ca, np.array([const], dtype=np.uint64)),
                     "AddPlain": lambda: ev.add_plain(ca, v1), "Multiply": lambda: c3, "Relinearize": lambda: ev.relinearize(c3),
-                    "RotateRows(1)": lambda: ev.rotate_rows(ca, 1), "RotateRows(-1)": lambda: ev.rotate_rows(ca, -1),
-                    "RotateColumns": lambda: ev.rotate_columns(ca)}
+                    **{"RotateRows(%d)" % r: (lambda r=r: ev.rotate_rows(ca, r)) for r in rot}}
+            if cols:
+                want["RotateColumns"] = lambda: ev.rotate_columns(ca)
             want = {k: np.asarray(f(), dtype=np.uint64).reshape(-1) for k, f in want.items()
                     if with_galois or not k.startswith("Rotate")}
             # Operations without keys.  Equal WORDS is what the restatement of SEAL 3.2 predicts; a product whose words differ from the client's but which
@@ -373,7 +385,7 @@ class AtomicSealBfvEncryptedEnvironment:
                 # never silent: the operator sees at start-up that this device and the client's evaluator disagree on words
                 import sys as _sys
                 print("libcnhip self-test warning (plaintext modulus %d): %s" % (t, warnings[-1]), file=_sys.stderr)
-            ks_ops = [op for op in ("Relinearize", "RotateRows(1)", "RotateRows(-1)", "RotateColumns") if op in want]
+            ks_ops = [op for op in ("Relinearize", *("RotateRows(%d)" % r for r in rot), "RotateColumns") if op in want]
 
             # Key-switching operations: WORDS again - unless the product itself already differs in words (then Relinearize inherits the difference and only
             # its decrypted slots can be compared; the rotations still compare words)
@@ -1905,10 +1917,12 @@ class EncryptedSealBfvFactory:
     DefaultGaloisDecompositionBitCount = 20
 
     def __init__(self, primes=None, n=4096, DecompositionBitCount=10, GaloisDecompositionBitCount=20, SmallModulusCount=-1,
-                 client_factory=None, context_factory=None, device=0, galois=True, client_seed=None, device_client_factory=None):
+                 client_factory=None, context_factory=None, device=0, galois=True, client_seed=None, device_client_factory=None, steps=None):
         """client_seed: None (default) = keys and encryption randomness from the OS entropy source; an integer makes the default
         DeviceClient reproducible (tests only - whoever knows it can regenerate the secret key).  device_client_factory(ctx, t): a client
-        that lives on the context (e.g. client.SharedKeyDeviceClient: one rank generates, the others receive the keys by RCCL broadcast)."""
+        that lives on the context (e.g. client.SharedKeyDeviceClient: one rank generates, the others receive the keys by RCCL broadcast).
+        steps: None = the default Galois key set; a list of RotateRows step counts = keys for exactly these rotations and the column swap
+        (KeyGenerator.GaloisKeys(dbc, steps); networks.rotation_steps finds the list of a network)."""
         if primes is None:
             primes = [40961, 65537, 114689, 147457, 188417]
             n = 4096
@@ -1934,7 +1948,7 @@ class EncryptedSealBfvFactory:
                 client = DeviceClient(ctx, seed=None if client_seed is None else client_seed ^ t)
             e = AtomicSealBfvEncryptedEnvironment(ctx, client)
             if client is not None:
-                e.GenerateEncryptionKeys(with_galois=galois)
+                e.GenerateEncryptionKeys(with_galois=galois, steps=steps)
             envs.append(e)
         self.referenceEnvironment = EncryptedSealBfvEnvironment(envs, ParentFactory=self)
 

@@ -356,3 +356,46 @@ def evaluate_single(network, Factory, records, verbose=False, report=print):
             Factory.FreeComputationEnv(env)
             m.Dispose()
     return errs, count
+
+
+def rotation_steps(network, Factory, record=1):
+    """Which rotations does `network` ask for?  Evaluates `record` record(s) (one is enough: the steps depend on the layer shapes, not on the data)
+    with cn_set_option("record_steps", 1) on the context of every plaintext prime and on every level context that exists when the evaluation
+    ends (a scheduled chain creates them on the way), and returns the union as (sorted distinct RotateRows steps, was a column rotation asked
+    for) - what GenerateEncryptionKeys(steps=...) / EncryptedSealBfvFactory(steps=...) take.  The contexts need keys that can serve the network
+    already (the default set does); recording is switched off and cleared afterwards."""
+    env = Factory.AllocateComputationEnv()
+    roots = [e.ctx for e in env.Environments]
+
+    def contexts():
+        out = []
+        for c in roots:
+            out.append(c)
+            out.extend(c._levels.values())
+        return out
+    for c in roots:
+        c.set_option("record_steps", 1)
+    steps, columns = set(), False
+    try:
+        # (a level context created while the chain runs takes the recording from its parent: _native.Context.level)
+        for c in roots:
+            for lv in list(c._levels.values()):
+                lv.set_option("record_steps", 1)
+        for p in _chain(network):
+            p.Factory = Factory
+        network.PrepareNetwork()
+        for _ in range(int(record)):
+            m = network.GetNext()
+            if m is None:
+                break
+            m.Dispose()
+        for c in contexts():
+            st, cols = c.rotation_steps()
+            steps.update(st)
+            columns = columns or cols
+    finally:
+        for c in contexts():
+            c.set_option("record_steps", 0)
+        Factory.FreeComputationEnv(env)
+    return sorted(steps), columns
+

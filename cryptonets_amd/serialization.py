@@ -299,7 +299,11 @@ def digit_count(parms, dbc):
 
 # ------------------------------------------------------------------------------------------------ one environment
 def _galois_elements(ctx):
-    """elements this context holds keys for: KeyGenerator.GaloisKeys(dbc) default set = 3^(+-2^i) and 2N-1"""
+    """elements this context holds keys for, ascending (cn_galois_elts): the default set of KeyGenerator.GaloisKeys(dbc), keys generated for a
+    network's own steps (cn_keygen_galois) and uploaded ones alike.  A context stand-in that cannot enumerate its keys (the CPU test harness)
+    is asked for the default set, 3^(+-2^i) and 2N-1, element by element."""
+    if hasattr(ctx, "galois_elts"):
+        return ctx.galois_elts()
     m, n = 2 * ctx.n, ctx.n
     cand, g = {m - 1}, 3
     for _ in range(max(1, n.bit_length() - 2)):

@@ -29,6 +29,8 @@ def main():
     ap.add_argument("-v", "--verbose", action="store_true")
     ap.add_argument("--graph", action="store_true", help="with -e: record the evaluation once (one HIP graph per plaintext prime) and replay it for every further record")
     ap.add_argument("--levels", action="store_true", help="with -e: plan a modulus-switching schedule on the first record (levels.plan_levels, margin 8 bits) and evaluate under it")
+    ap.add_argument("--direct-keys", action="store_true", help="with -e: dry run of one record with the default Galois keys, then keys for exactly the recorded rotation steps "
+                    "(KeyGenerator.GaloisKeys(dbc, steps): one key switch per rotation) and the evaluation under those")
     ap.add_argument("--budget", action="store_true", help="with -e -v: probe the invariant noise budget after every layer (CryptoTracker)")
     ap.add_argument("--file", default="MNIST-28x28-test.txt")
     ap.add_argument("--synthetic", type=int, default=0, metavar="RECORDS")
@@ -66,6 +68,17 @@ def main():
         weights = np.load(GOLDEN + ("/small_model_weights.npz" if a.network == "LoLaSmall" else "/cryptonets_weights.npz"))
         return networks.LOLA_NETWORKS[a.network](Factory, reader, weights)
     network = build()
+    if a.direct_keys and a.encrypt:
+        steps, columns = networks.rotation_steps(network, Factory, 1)         # dry run with the default key set (the reference's)
+        print("rotation steps of %s: %s%s" % (a.network, steps, " + column swap" if columns else ""))
+        start = time.time()
+        for e in Factory.AllocateComputationEnv().Environments:              # the default keys (and the dry run's arrays) leave the device before the new ones arrive
+            for lv in list(e.ctx._levels.values()):
+                lv.close()
+            e.ctx.close()
+        Factory = EncryptedSealBfvFactory(**parms, steps=steps)              # (the column-swap key is always generated)
+        print("Generating keys for %d steps in %.2f seconds" % (len(steps), time.time() - start))
+        network = build()
     schedule = None
     if a.levels and a.encrypt:
         from cryptonets_amd.levels import plan_levels

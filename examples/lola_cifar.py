@@ -38,6 +38,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("-e", "--encrypt", action="store_true")
     ap.add_argument("-v", "--verbose", action="store_true")
+    ap.add_argument("--direct-keys", action="store_true", help="with -e: dry run of one record with the default Galois keys, then keys for exactly the recorded rotation steps "
+                    "(KeyGenerator.GaloisKeys(dbc, steps): one key switch per rotation) and the evaluation under those")
     ap.add_argument("--budget", action="store_true", help="with -e -v: probe the invariant noise budget after every layer (CryptoTracker)")
     ap.add_argument("--file", default="cifar-test.tsv")
     ap.add_argument("--weights", default=None)
@@ -66,6 +68,16 @@ def main():
     print("Encryption keys ready %s" % time.strftime("%X"))
     reader = networks.cifar_reader(a.file)
     network = networks.LoLaCifar(Factory, reader, W, B)
+    if a.direct_keys and a.encrypt:
+        steps, columns = networks.rotation_steps(network, Factory, 1)         # dry run with the default key set (the reference's)
+        print("rotation steps: %s%s" % (steps, " + column swap" if columns else ""))
+        for e in Factory.AllocateComputationEnv().Environments:              # the default keys (and the dry run's arrays) leave the device before the new ones arrive
+            for lv in list(e.ctx._levels.values()):
+                lv.close()
+            e.ctx.close()
+        Factory = EncryptedSealBfvFactory(**parms, steps=steps)              # (the column-swap key is always generated)
+        print("Keys for %d steps ready %s" % (len(steps), time.strftime("%X")))
+        network = networks.LoLaCifar(Factory, networks.cifar_reader(a.file), W, B)
     print("Preparing")
     if a.budget:
         from cryptonets_amd.cryptotracker import CryptoTracker

@@ -133,6 +133,7 @@ int cn_mod_switch(cn_ctx *src, cn_handle in, uint32_t ii, uint32_t count, cn_ctx
  *                                                                   product kernel; 0 = k_lift_ntt + k_mul_plain_fused
  *   "defer"          0..2    0                     -                deferred submission of per-ciphertext calls (below)
  *   "ks_xi"          flag    0                     -                decomposition convention of the key switch (below)
+ *   "record_steps"   flag    0                     -                note the rotation steps the caller asks for (cn_rotation_steps); 0 stops and clears
  *
  * Removed after their variants measured no gain: staggered squaring groups in the flush (profiles/r06_stagger_ab.txt), the q side of a batched
  * squaring on a second stream (profiles/r06_square_overlap.txt), the 128-VGPR fused key switch (profiles/HISTORY.md, round 1).
@@ -374,6 +375,29 @@ int cn_set_rng_salt(cn_ctx *ctx, uint64_t salt);
  * 64-bit nonce (state words 14-15); RFC 7539 section 2.3.2 is the case counter = 0x0900000000000001, nonce = 0x4a000000 */
 int cn_rng_selftest(cn_ctx *ctx, const uint8_t *key32, uint64_t counter, uint64_t nonce, uint32_t *out16);
 int cn_keygen(cn_ctx *ctx, uint64_t seed, int with_galois);          /* secret, public, relin (dbc) and default Galois (gdbc) keys */
+/* KeyGenerator.GaloisKeys(dbc, galois_elts) of SEAL 3.2: Galois keys for exactly the n listed elements (cn_galois_elt_from_step maps a RotateRows step),
+ * generated and installed by ONE kernel launch behind one noise launch (k_ksk_gen) with one host wait at the end.  A rotation by a step whose element has a
+ * key is ONE key switch; any other step is split into its non-adjacent form and pays one key switch per term (cn_rotate_rows).  An element the context already
+ * holds is replaced.  Layout, convention ("ks_xi", gdbc) and form (FP64 image when the context keeps its keys as doubles) are those of cn_keygen's keys:
+ * [(l,d)][2][k][N], NTT form.
+ * THE WORDS are those cn_keygen's loop would have produced for these elements, continuing from the context's item counter item0: entry e = (l, d) of the
+ * g-th listed element has  a = sample_uniform8(sampler key, seed, stream 3, item0 + 2 (g gk_tot + e), ...)  and its noise from stream 1 at the next item; the
+ * counter advances by 2 n gk_tot.  So cn_keygen(seed, 1) on one context and cn_keygen(seed, 0) followed by cn_keygen_galois(seed, the default elements in
+ * cn_keygen's order: 2N-1, then 3^(2^i), 3^-(2^i) for i = 0 .. log2(N) - 2) on another with the same sampler key hold identical keys.
+ * Needs the secret key (CN_ERR_NOKEY) and 1024 <= N <= 16384.  CN_ERR_ARG - and nothing is installed - for an even element, an element >= 2N, an element
+ * listed twice, on a level context and while a graph is recorded.  Flushes deferred work first; n = 0 returns 0. */
+int cn_keygen_galois(cn_ctx *ctx, uint64_t seed, const uint64_t *galois_elts, uint32_t n);
+/* The Galois elements this context holds a key for, ascending: *count = their number; elts (may be NULL when only the count is asked for) receives them if
+ * cap >= *count, else CN_ERR_ARG (with *count set).  A level context reports the keys sliced from its parent. */
+int cn_galois_elts(cn_ctx *ctx, uint64_t *elts, uint32_t cap, uint32_t *count);
+/* Which rotations does a caller ask for?  cn_set_option(ctx, "record_steps", 1) starts recording, 0 stops and clears (off by default; cn_get_option reads it
+ * back; a level context records into its own list and starts with recording off).  While it is on, the context notes every RotateRows step AS REQUESTED -
+ * before the split into non-adjacent-form hops - by cn_rotate_rows, cn_rotate_rows_many, cn_rotate_rows_add (immediate or queued; step 0 is a copy and is not
+ * noted), the steps -1, -2, -4, .. of cn_sum_slots and cn_rowdot_batch, the step of a cn_apply_galois element 3^s (as s or s - N/2, whichever is smaller in
+ * magnitude), and whether a column rotation was asked for (cn_rotate_columns(_add), cn_apply_galois(2N - 1), a cn_sum_slots / cn_rowdot_batch over >= N/2 slots).
+ * cn_rotation_steps returns the steps ascending and distinct: *count = their number, steps (may be NULL) receives them if cap >= *count, else CN_ERR_ARG
+ * (with *count set); *columns (may be NULL) = 1 if a column rotation was asked for. */
+int cn_rotation_steps(cn_ctx *ctx, int *steps, uint32_t cap, uint32_t *count, int *columns);
 int cn_set_public_key(cn_ctx *ctx, const uint64_t *words, size_t count);   /* [2][k][N], NTT form */
 int cn_set_secret_key(cn_ctx *ctx, const uint64_t *words, size_t count);   /* [k][N], NTT form */
 int cn_get_key(cn_ctx *ctx, int which /*0 relin,1 galois,2 public,3 secret*/, uint64_t galois_elt, uint64_t *host, size_t count);
