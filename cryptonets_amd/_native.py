@@ -169,6 +169,7 @@ SIGNATURES = {
     "cn_multiply": (C.c_int, [_CTX, _H, _u32, _H, _u32, _H, _u32, _u32]),
     "cn_relinearize": (C.c_int, [_CTX, _H, _u32, _H, _u32, _u32]),
     "cn_mul_relin": (C.c_int, [_CTX, _H, _u32, _u32, _H, _u32, _u32, _H, _u32, _u32]),
+    "cn_square_gemm": (C.c_int, [_CTX, _H, _H, _u32, _H, _u32]),
     "cn_apply_galois": (C.c_int, [_CTX, _H, _u32, C.c_uint64, _H, _u32, _u32]),
     "cn_rotate_rows": (C.c_int, [_CTX, _H, _u32, C.c_int, _H, _u32, _u32]),
     "cn_rotate_rows_many": (C.c_int, [_CTX, _H, C.POINTER(C.c_uint32), C.POINTER(C.c_int), _u32, _H, C.POINTER(C.c_uint32)]),
@@ -543,6 +544,10 @@ class Context:
 
     def mul_relin(self, a, ai, b, bi, out, oi, count=1, a_stride=1, b_stride=1):
         self._chk(self.L.cn_mul_relin(self._h, a, ai, a_stride, b, bi, b_stride, out, oi, count))
+
+    def square_gemm(self, plan, src, ii, out, oi):
+        """SquareActivation of the plan's inputs src[ii..] + the planned PoolLayer behind it: the words of mul_relin followed by gemm_apply"""
+        self._chk(self.L.cn_square_gemm(self._h, plan, src, ii, out, oi))
 
     def apply_galois(self, src, ii, elt, out, oi, count=1):
         self._chk(self.L.cn_apply_galois(self._h, src, ii, elt, out, oi, count))

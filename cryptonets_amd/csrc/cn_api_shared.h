@@ -93,6 +93,8 @@ struct GemmPlan {
     std::vector<char> host;                  // [idx | out_idx | bias_idx | weights], each 256 B aligned
     size_t off_oidx = 0, off_bidx = 0, off_w = 0;
     char *dev = nullptr;                     // persistent plans: device copy of `host`
+    // cn_square_gemm: the layer may run on the digits of the unrelinearized products (square_gemm_plan_ok) - signed weights [G][mtiles][dKw][dMT] at off_dw
+    bool dig = false; uint32_t dMT = 0, dKw = 0; size_t off_dw = 0;
 };
 // ---- rotations of n ciphertexts by n DIFFERENT step counts as one launch chain (cn_rotate_rows_many; the queued RotateRows calls of one level).
 // A single-image network rotates the 13 masked vectors of an Interleave by 13 different amounts, the 5 maps of a Vectorize by 5: one rotation
@@ -146,7 +148,7 @@ uint32_t gemm_weight_planes(cn_ctx *ctx, const uint64_t *W, size_t count);
 int free_gemm_plan(cn_ctx *ctx, Buffer &b);
 bool pair_gather_lists(uint32_t O, uint32_t &K, std::vector<int32_t> &gidx, const uint64_t *W, std::vector<uint64_t> &W2);
 int build_gemm_plan(cn_ctx *ctx, const int32_t *idx, const uint64_t *W, uint32_t O, uint32_t K, Buffer *BP, cn_handle bias_pt, const int32_t *bias_idx, GemmPlan &P);
-int run_gemm_plan(cn_ctx *ctx, const GemmPlan &P, const char *tables, Buffer *I, Buffer *OB, uint32_t oi);
+int run_gemm_plan(cn_ctx *ctx, const GemmPlan &P, const char *tables, Buffer *I, Buffer *OB, uint32_t oi, const uint64_t *in3 = nullptr);
 bool run_intt_tensor(cn_ctx *c, const uint64_t *A, const uint64_t *B, uint64_t *D, uint32_t cnt, uint32_t base_off, uint32_t Lm, bool lazy);
 bool square_fused_ok(cn_ctx *c, uint32_t base_off, uint32_t Lm, bool &light);
 void run_square_fused(cn_ctx *c, const uint64_t *A, size_t astride, const uint64_t *const *atab, uint64_t *D, uint32_t cnt, uint32_t base_off, uint32_t Lm, bool light);
@@ -206,7 +208,7 @@ static inline bool pipeline_fused_ks(cn_ctx *ctx, uint32_t c) {
     for (uint32_t i = 0; i < P; i++) if (ks_planned_mode(ctx, first[i + 1] - first[i], 0) != 0) return false;
     return P >= 2;
 }
-int do_keyswitch(cn_ctx *ctx, const uint64_t *target, size_t tstride, const uint64_t *add0, const uint64_t *add1, size_t astride, const KsKey &key, uint64_t *out, uint32_t cnt, int galois, const uint64_t *extra = nullptr, size_t xstride = 0, uint64_t *const *out_tab = nullptr, uint32_t perm_elt = 0, const KsItem *items = nullptr, uint32_t next_elt = 0, uint64_t *next_out = nullptr);
+int do_keyswitch(cn_ctx *ctx, const uint64_t *target, size_t tstride, const uint64_t *add0, const uint64_t *add1, size_t astride, const KsKey &key, uint64_t *out, uint32_t cnt, int galois, const uint64_t *extra = nullptr, size_t xstride = 0, uint64_t *const *out_tab = nullptr, uint32_t perm_elt = 0, const KsItem *items = nullptr, uint32_t next_elt = 0, uint64_t *next_out = nullptr, const double *dig = nullptr);
 bool ks_pair14_ok(cn_ctx *ctx, uint32_t cnt, int galois, const KsKey &key);
 uint32_t chunk_for(cn_ctx *ctx, size_t per_ct, uint32_t count);
 int mul_relin_body(cn_ctx *ctx, cn_handle a, uint32_t ai, uint32_t astride, cn_handle b, uint32_t bi, uint32_t bstride, cn_handle out, uint32_t oi, uint32_t count);

@@ -317,8 +317,36 @@ int build_gemm_plan(cn_ctx *ctx, const int32_t *idx, const uint64_t *W, uint32_t
         pack_gemm_weights(ctx, G, M, K, small, row, tap, P.MT, wbytes);
         P.one = gemm_one_limb(ctx, ar, G, M, K, row, tap);
     }
+    // cn_square_gemm: may this layer run on the DIGITS of unrelinearized products (k_digit_gemm)?  Small signed weights and, for every output, sum_k |w| (2^dbc - 1)
+    // below q_j / 2 for every j and below 2^52: the combined digit polynomial is then an exact double and a recentred lazy value of every limb's FP64 policy.
+    std::vector<double> dW;
+    if (small && ctx->hc.k >= 2 && ctx->hc.dbc >= 1 && ctx->hc.dbc <= 30) {
+        uint64_t qmin = ~0ull; for (uint32_t j = 0; j < ctx->hc.k; j++) qmin = std::min(qmin, ctx->hc.q[j].q);
+        const uint64_t dmax = (1ull << ctx->hc.dbc) - 1, lim = std::min<uint64_t>((qmin - 1) / 2, (1ull << 52) - 1) / dmax;      // sum |w| <= lim
+        bool ok = true;
+        for (uint32_t g = 0; g < G && ok; g++) for (uint32_t m = 0; m < M && ok; m++) {
+            const uint64_t *wr = row(g, m);
+            if (!wr) continue;
+            uint64_t sum = 0;
+            for (uint32_t kk = 0; kk < K; kk++) if (hidx[(size_t)g * Kp + kk] >= 0) { const uint64_t w = wr[kk]; sum += w >= ctx->hc.t_half ? t - w : w; }
+            ok = sum <= lim;
+        }
+        if (ok) {
+            P.dig = true; P.dMT = digit_gemm_tile(M); P.dKw = digit_gemm_rows(K);
+            const uint32_t mtd = (M + P.dMT - 1) / P.dMT;
+            dW.assign((size_t)G * mtd * P.dKw * P.dMT, 0.0);
+            for (uint32_t g = 0; g < G; g++) for (uint32_t m = 0; m < M; m++) {
+                const uint64_t *wr = row(g, m);
+                if (!wr) continue;
+                double *dst = &dW[(((size_t)g * mtd + m / P.dMT) * P.dKw) * P.dMT + m % P.dMT];
+                for (uint32_t kk = 0; kk < K; kk++) { const uint64_t w = hidx[(size_t)g * Kp + kk] >= 0 ? wr[kk] : 0; dst[(size_t)kk * P.dMT] = w >= ctx->hc.t_half ? -(double)(t - w) : (double)w; }
+            }
+        }
+    }
     P.off_oidx = al(hidx.size() * 4); P.off_bidx = P.off_oidx + al(hoidx.size() * 4); P.off_w = P.off_bidx + al(hbidx.size() * 4);
-    P.host.assign(P.off_w + al(wbytes.size()), 0);
+    P.off_dw = P.off_w + al(wbytes.size());
+    P.host.assign(P.off_dw + al(dW.size() * 8), 0);
+    memcpy(P.host.data() + P.off_dw, dW.data(), dW.size() * 8);
     memcpy(P.host.data(), hidx.data(), hidx.size() * 4);
     memcpy(P.host.data() + P.off_oidx, hoidx.data(), hoidx.size() * 4);
     memcpy(P.host.data() + P.off_bidx, hbidx.data(), hbidx.size() * 4);
@@ -326,21 +354,25 @@ int build_gemm_plan(cn_ctx *ctx, const int32_t *idx, const uint64_t *W, uint32_t
     return 0;
 }
 // tables: device image of P.host (scratch or the plan's own allocation)
-int run_gemm_plan(cn_ctx *ctx, const GemmPlan &P, const char *tables, Buffer *I, Buffer *OB, uint32_t oi) {
+// in3 (cn_square_gemm): the inputs are the first TWO components of the size-3 products at in3 (P.max_in of them, checked by the caller) instead of the ciphertexts of I
+int run_gemm_plan(cn_ctx *ctx, const GemmPlan &P, const char *tables, Buffer *I, Buffer *OB, uint32_t oi, const uint64_t *in3) {
     if (!range_ok(OB, oi, P.O)) return fail(CN_ERR_ARG, "output index out of range");
+    if (!in3) {
     if (I == OB) return fail(CN_ERR_ARG, "scalar GEMM cannot run in place");
     if (P.max_in > I->count) return fail(CN_ERR_ARG, "input index out of range");
     // Evaluator::multiply_plain / add take ciphertexts of any size: size 3 = products that have not been relinearized yet (the sum of weighted
     // products is then relinearized once per OUTPUT instead of once per input)
     if (I->size != OB->size || I->size < 2 || I->size > 3) return fail(CN_ERR_ARG, "scalar GEMM: input and output ciphertext sizes must match (2 or 3)");
+    } else if (OB->size != 2) return fail(CN_ERR_ARG, "scalar GEMM: output ciphertext size must be 2");
     const uint64_t *bias = nullptr;
     if (P.has_bias) {
         Buffer *BP = getbuf(ctx, P.bias_pt, 1);
         if (!BP || BP->count < P.bias_count) return fail(CN_ERR_ARG, "invalid bias plaintext handle");
         bias = BP->d;
     }
-    GemmLaunch gl{P.small, P.two, false, P.MT, I->d, tables, tables + P.off_w, tables + P.off_oidx, bias, tables + P.off_bidx, OB->d,
-                  P.G, P.M, P.K, P.lazy, P.Kp, oi, P.P, P.mtiles, P.ksteps, I->size, (uint32_t)ctx->opt.gemm_order, P.one};
+    GemmLaunch gl{P.small, P.two, false, P.MT, in3 ? in3 : I->d, tables, tables + P.off_w, tables + P.off_oidx, bias, tables + P.off_bidx, OB->d,
+                  P.G, P.M, P.K, P.lazy, P.Kp, oi, P.P, P.mtiles, P.ksteps, in3 ? 2u : I->size, (uint32_t)ctx->opt.gemm_order, P.one};
+    if (in3) gl.in_unit = 3 * ctx->hc.k * ctx->hc.n;              // two components of every product, three apart
     CHECK(P.mfma ? cn_l_gemm_mfma(ctx, gl) : cn_l_gemm(ctx, gl));
     ctx->st.PlainMultiplication += P.nnz; ctx->st.Addition += P.nnz - P.O;
     if (P.has_bias) ctx->st.PlainAddition += P.O;
@@ -515,7 +547,7 @@ int ks_planned_mode(cn_ctx *ctx, uint32_t cnt, int galois) {
 // previous link of a rotate-and-add chain), add0 = the unpermuted c0 and perm_elt; next_elt / next_out ask for sigma_next of the new c1 on the side.
 int do_keyswitch(cn_ctx *ctx, const uint64_t *target, size_t tstride, const uint64_t *add0, const uint64_t *add1, size_t astride,
                         const KsKey &key, uint64_t *out, uint32_t cnt, int galois, const uint64_t *extra, size_t xstride,
-                        uint64_t *const *out_tab, uint32_t perm_elt, const KsItem *items, uint32_t next_elt, uint64_t *next_out) {
+                        uint64_t *const *out_tab, uint32_t perm_elt, const KsItem *items, uint32_t next_elt, uint64_t *next_out, const double *dig) {
     const uint32_t n = ctx->hc.n, k = ctx->hc.k, tot_dig = galois ? ctx->hc.gk_tot : ctx->hc.rl_tot;
     uint64_t qmax = 0; for (uint32_t j = 0; j < k; j++) qmax = std::max(qmax, ctx->hc.q[j].q);
     const int bits = 64 - __builtin_clzll(qmax);
@@ -529,6 +561,8 @@ int do_keyswitch(cn_ctx *ctx, const uint64_t *target, size_t tstride, const uint
     if (a.mode) CHECK(ensure_ks_part(ctx, (size_t)cnt * (a.mode == 2 ? k : tot_dig) * ctx->ctw2 * 8));
     a.perm_elt = perm_elt; a.items = items;
     a.next_elt = next_elt; a.next_out = next_out;
+    a.dig = dig;
+    if (dig && !(rr && key.f64 && ctx->hc.logn <= 13 && !galois && !ctx->hc.ks_xi)) return fail(CN_ERR_ARG, "internal: ready-made digits outside the FP64 register-radix key switch");
     const bool pair = ks_pair14_ok(ctx, cnt, galois, key);
     if ((perm_elt || items || next_elt) && !a.mode && !(pair && !items)) return fail(CN_ERR_ARG, "internal: automorphism inside the fused key switch");
     if (pair) {                                                                                      // N = 16384: both 8192-point halves of a limb in one workgroup, one launch
@@ -653,6 +687,64 @@ int mul_relin_body(cn_ctx *ctx, cn_handle a, uint32_t ai, uint32_t astride, cn_h
     ctx->st.Relinarization += count;
     return 0;
 }
+
+// ---------------------------------------------------------------- squaring layer + dense layer in one call
+// SquareActivation relinearizes every product, ct_k = (d0_k + KS0(d2_k), d1_k + KS1(d2_k)), and the PoolLayer behind it forms out_o = sum_k w_ok ct_k.  A key switch is
+// linear over Z_{q_j} in the DIGITS of its operand - digit extraction is its only non-linear step and comes first - and so is the scalar GEMM, hence word for word
+//   sum_k w_ok KSc(d2_k)[j] = INTT_j( sum_{l,d} NTT_j(S_{o,l,d}) K^c_{l,d,j} ),   S_{o,l,d} = sum_k w_ok dig_{k,l,d}   (a plain integer, the same for every j).
+// The pair therefore needs one key switch per dense OUTPUT, fed with the weight-combined digit polynomials S (k_digit_gemm), not one per input: 100 + 10 instead of
+// 845 + 100 for CryptoNets, the same ciphertext words.  (Not forward_relinearize_late's "relinearize the sum": there the digits are those of the sum.)
+// Runs when the plan allows it (GemmPlan::dig: small weights, |S| below every q_j / 2 and 2^52), every modulus and the key are on an FP64 policy, the ring has the
+// register-radix kernels up to N = 8192 and the decomposition is the plain one; anything else takes the two separate steps inside the same call.
+static bool square_gemm_fused_ok(cn_ctx *ctx, const GemmPlan &P) {
+    if (!P.dig || !ctx->opt.f64 || ctx->opt.legacy_ntt || ctx->hc.logn < 10 || ctx->hc.logn > 13 || ctx->hc.ks_xi || !ctx->rlk.f64) return false;
+    for (uint32_t m = 0; m < ctx->hc.k; m++) if (!ctx->hc.f64ok[m]) return false;
+    return true;
+}
+extern "C" int cn_square_gemm(cn_ctx *ctx, cn_handle plan, cn_handle in, uint32_t ii, cn_handle out, uint32_t oi) { TWO_LIMBS("cn_square_gemm"); API_BODY
+    LOCK; GETCT(I, in, 2); GETCT(OB, out, 2);
+    Buffer *PB = getbuf(ctx, plan, 2);
+    if (!PB || !PB->plan) return fail(CN_ERR_ARG, "invalid scalar GEMM plan handle");
+    const GemmPlan &P = *PB->plan;
+    const uint32_t cnt = P.max_in;
+    if (!range_ok(I, ii, cnt)) return fail(CN_ERR_ARG, "input index out of range");
+    if (!range_ok(OB, oi, P.O)) return fail(CN_ERR_ARG, "output index out of range");
+    if (I == OB) return fail(CN_ERR_ARG, "cn_square_gemm cannot run in place");
+    if (!ctx->rlk.d) return fail(CN_ERR_NOKEY, "relinearization keys not set");
+    const uint32_t n = ctx->hc.n, k = ctx->hc.k, tot = ctx->hc.rl_tot;
+    const size_t kn = (size_t)k * n;
+    const size_t per = mul_scratch_per_ct(ctx, true);
+    const size_t fixed = al((size_t)cnt * 3 * kn * 8) + al((size_t)P.O * tot * n * 8) + 8192;
+    if (!square_gemm_fused_ok(ctx, P) || fixed + per > ctx->smax) {               // the two steps as they are: square + relinearize into a temporary, the GEMM from it
+        cn_handle tmp = 0;
+        CHECK(alloc_buf(ctx, 0, cnt, 2, &tmp));
+        int rc = mul_relin_body(ctx, in, ii, 1, in, ii, 1, tmp, 0, cnt);
+        if (!rc) rc = cn_defer_flush(ctx);                                        // (a context that queues its calls has queued this one)
+        OB = getbuf(ctx, out, 0);                                                 // the handle table may have moved
+        if (!rc) rc = run_gemm_plan(ctx, P, P.dev, getbuf(ctx, tmp, 0), OB, oi);
+        const int rf = free_body(ctx, tmp);
+        return rc ? rc : rf;
+    }
+    const uint32_t ch = (uint32_t)std::min<size_t>(cnt, (ctx->smax - fixed) / per);
+    CHECK(ensure_scratch(ctx, fixed + per * ch + 4096));
+    uint64_t *t3 = salloc<uint64_t>(ctx, (size_t)cnt * 3 * kn);
+    double *S = salloc<double>(ctx, (size_t)P.O * tot * n);
+    if (!t3 || !S) return fail(CN_ERR_HIP, "internal: scratch exhausted in cn_square_gemm");
+    const size_t mark = ctx->soff;
+    const uint64_t *pa = I->d + ii * I->item_words;
+    for (uint32_t s = 0; s < cnt; s += ch) {                                      // the products, all of them, before the first sum
+        const uint32_t c = std::min(ch, cnt - s);
+        ctx->soff = mark;
+        CHECK(do_multiply(ctx, pa + (size_t)s * I->item_words, 1, pa + (size_t)s * I->item_words, 1, t3 + (size_t)s * 3 * kn, c));
+    }
+    CHECK(run_gemm_plan(ctx, P, P.dev, nullptr, OB, oi, t3));                     // components 0 and 1 (+ bias) straight into the outputs
+    DigitGemmLaunch dg{t3 + 2 * kn, 3 * kn, P.dev, P.dev + P.off_dw, P.dev + P.off_oidx, S, P.G, P.M, P.K, P.Kp, P.dKw, P.dMT};
+    CHECK(cn_l_digit_gemm(ctx, dg));
+    uint64_t *o = OB->d + oi * OB->item_words;
+    CHECK(do_keyswitch(ctx, nullptr, 0, o, o + kn, 2 * kn, ctx->rlk, o, P.O, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, S));
+    ctx->st.Relinarization += cnt; ctx->sg_fused++;
+    return 0;
+API_END }
 
 // ---------------------------------------------------------------- rotations
 // in/out device pointers to size-2 ciphertext arrays; tmp holds count size-2 ciphertexts

@@ -495,3 +495,87 @@ __global__ void __launch_bounds__(256, 2) k_scalar_gemm_mfma(const uint64_t *__r
         }
     }
 }
+
+// ------------------------------------------------------------------ digit GEMM (cn_square_gemm)
+// The dense layer behind a squaring layer, applied to the DIGITS of the unrelinearized component: S[o][g][i] = sum_k w[o][k] * dig_g(in[idx[k]][l][i]) for the
+// digit g = (source limb l, digit d) of the key-switch decomposition, dig = (word >> dbc d) & (2^dbc - 1).  Digit extraction is the only step of a key switch that
+// is not linear, and it happens here, per input, before the weights: everything behind it (transforms, key products, inverse transforms, the mod q_j reductions)
+// commutes with the weighted sum, so ONE key switch per output fed with S gives the words of one key switch per input followed by the scalar GEMM.  S is a plain
+// signed integer (|S| <= max_o sum_k |w_ok| (2^dbc - 1) < 2^52, checked when the plan is built), the same for every output limb j: exact in one FMA per term.
+// Workgroup = (256 coefficients, source limb l, group of DG digits, output tile mt, gather list g); in = component 2 of product 0, products in_unit words apart.
+// Weights [g][mt][kk < Kw][MT] signed doubles, zero rows behind the K terms and zero for padded taps (which read a valid word: product 0); gather rows as in
+// k_scalar_gemm_f64.  The output tiles of a slice take block ids 8 apart: one XCD, adjacent in time, the slice is re-read from that L2 (gemm_block_coords).
+template <int MT, int DG>
+__global__ void __launch_bounds__(256) k_digit_gemm(const uint64_t *__restrict__ in, size_t in_unit, const int32_t *__restrict__ idx, const double *__restrict__ Wd,
+                                                    const int32_t *__restrict__ out_idx, double *__restrict__ S, const DevConsts *__restrict__ C, uint32_t G, uint32_t M,
+                                                    uint32_t K, uint32_t mtiles, uint32_t Kp, uint32_t Kw, uint32_t ndg) {
+    const uint32_t n = C->n, k = C->k, chunks = n >> 8;
+    uint32_t chunk, lj, mt, g;
+    gemm_block_coords(blockIdx.x, 0, chunks, k * ndg, mtiles, G, chunk, lj, mt, g);
+    const uint32_t l = lj % k, d0 = (lj / k) * DG, nd = C->rl_dig[l];
+    if (d0 >= nd) return;
+    uint32_t g0 = 0;                                           // index of the first digit of limb l in the key
+    for (uint32_t x = 0; x < l; x++) g0 += C->rl_dig[x];
+    const uint32_t i = chunk * 256 + threadIdx.x, dbc = (uint32_t)C->dbc, mask = (1u << dbc) - 1;
+    const size_t e = (size_t)l * n + i;
+    uint32_t sh[DG];
+#pragma unroll
+    for (int d = 0; d < DG; d++) sh[d] = min(dbc * (d0 + (uint32_t)d), 63u);
+    double acc[DG][MT];
+#pragma unroll
+    for (int d = 0; d < DG; d++)
+#pragma unroll
+        for (int m = 0; m < MT; m++) acc[d][m] = 0.0;
+    const int32_t *gi = idx + (size_t)g * Kp;
+    const double *gw = Wd + ((size_t)g * mtiles + mt) * (size_t)Kw * MT;
+    constexpr int PF = 4, WB = MT > 10 ? 1 : 2;
+    auto fetch = [&](uint64_t (&x)[PF], uint32_t kk) {         // branch-free: terms past K and padded taps carry the weight 0
+        const int4 ids = *reinterpret_cast<const int4 *>(__builtin_assume_aligned(gi + min(kk, Kp - PF), 16));
+        const int32_t id[4] = {ids.x, ids.y, ids.z, ids.w};
+#pragma unroll
+        for (int p = 0; p < PF; p++) x[p] = in[(size_t)max(id[p], 0) * in_unit + e];
+    };
+    auto terms = [&](const uint64_t (&x)[PF], uint32_t kk) {
+#pragma unroll
+        for (int p0 = 0; p0 < PF; p0 += WB) {
+            double w[WB * MT];
+            const double *wp = gw + (size_t)(kk + p0) * MT;
+#pragma unroll
+            for (int q = 0; q < WB * MT; q++) w[q] = wp[q];
+#pragma unroll
+            for (int p = p0; p < p0 + WB; p++) {
+                double dg[DG];
+#pragma unroll
+                for (int d = 0; d < DG; d++) dg[d] = (double)((uint32_t)(x[p] >> sh[d]) & mask);
+#pragma unroll
+                for (int m = 0; m < MT; m++)
+#pragma unroll
+                    for (int d = 0; d < DG; d++) acc[d][m] = __fma_rn(dg[d], w[(p - p0) * MT + m], acc[d][m]);
+            }
+        }
+    };
+    {   // sets of PF terms in pairs, two register sets ping-pong (k_scalar_gemm_f64); ONE exit at the end of the pair loop
+        const uint32_t sets = (K + PF - 1) / PF;
+        uint32_t kk = 0;
+        uint64_t xa[PF], xb[PF];
+        fetch(xa, 0);
+        for (uint32_t it = sets >> 1; it; it--, kk += 2 * PF) {
+            fetch(xb, kk + PF);
+            terms(xa, kk);
+            fetch(xa, kk + 2 * PF);
+            terms(xb, kk + PF);
+        }
+        if (sets & 1) terms(xa, kk);
+    }
+    const uint32_t tot = C->rl_tot;
+#pragma unroll
+    for (int m = 0; m < MT; m++) {
+        const uint32_t mm = mt * MT + (uint32_t)m;
+        if (mm >= M) break;
+        const int32_t o = out_idx[g * M + mm];
+        if (o < 0) continue;                                   // padding member of a smaller group
+#pragma unroll
+        for (int d = 0; d < DG; d++)
+            if (d0 + (uint32_t)d < nd) S[((size_t)o * tot + g0 + d0 + (uint32_t)d) * n + i] = acc[d][m];
+    }
+}

@@ -59,13 +59,23 @@ template <class FW0> struct KsPassA<FW0, true> { typedef ArPassA<FW0> P; };
 // uses, read back behind it.  Bit-exact; 3.37 vs 3.33 ms: the key stream costs bandwidth on the vector memory path, not exposed latency.)
 // XI: the "ks_xi" decomposition (digits of [c_l (q/q_l)^-1]_{q_l}) as a separate instantiation - the default kernel is instruction for instruction the one
 // that is profiled and priced (tools/ks_isa_counts.py)
-template <int L, class AR, int MINW = 1, bool TWL = false, bool XI = false>
+// DIG: the digit polynomials arrive ready-made (cn_square_gemm: S[ct][g][N], the weight-combined digits of a dense layer's inputs, exact signed doubles with
+// |S| < q_j / 2 for every j - a recentred lazy value of the FP64 policies) instead of being cut out of a source limb: `target` is that array, tgt_stride = digits * N.
+// Again a separate instantiation, selected by wrapping the policy - k_keyswitch_rr<L, KsDigits<AR>, ..> - so that the default instantiations keep their names;
+// everything behind the digit load is the same code.
+template <class AR> struct KsDigits {};
+template <class AR> struct KsSrc { typedef AR P; static constexpr bool dig = false; };
+template <class AR> struct KsSrc<KsDigits<AR>> { typedef AR P; static constexpr bool dig = true; };
+template <int L, class AR_, int MINW = 1, bool TWL = false, bool XI = false>
 __global__ void __launch_bounds__(NttPlan<L>::NT, MINW) k_keyswitch_rr(const uint64_t *__restrict__ target, size_t tgt_stride, const uint64_t *__restrict__ add0,
                                                                  const uint64_t *__restrict__ add1, size_t add_stride, const void *__restrict__ key_,
                                                                  uint64_t *out, const DevConsts *__restrict__ C, int galois, uint32_t accmax,
                                                                  const uint64_t *extra, size_t ex_stride, uint64_t *const *__restrict__ out_tab,
                                                                  uint32_t xcd_cts) {
+    typedef typename KsSrc<AR_>::P AR;
+    constexpr bool DIG = KsSrc<AR_>::dig;
     typedef typename AR::T T;
+    static_assert(!DIG || (std::is_same<T, double>::value && !XI), "ready-made digits: FP64 policies, plain decomposition");
     extern __shared__ __align__(16) unsigned char smem[];
     T *s = reinterpret_cast<T *>(smem);
     constexpr uint32_t n = 1u << L;
@@ -121,9 +131,11 @@ __global__ void __launch_bounds__(NttPlan<L>::NT, MINW) k_keyswitch_rr(const uin
         for (int r = 0; r < 16; r++) w[r] = src[pass_index<L, SA, 0>(t0, r)];
     };
     if constexpr (AHEAD) request(nraw, 0);
+    const double *dsrc = reinterpret_cast<const double *>(target) + (size_t)ct * tgt_stride;      // DIG: digit polynomial g of this ciphertext at dsrc + g N
     for (uint32_t l = 0; l < k; l++) {
         const uint32_t nd = galois ? C->gk_dig[l] : C->rl_dig[l];
-        if constexpr (AHEAD) {
+        if constexpr (DIG) {
+        } else if constexpr (AHEAD) {
 #pragma unroll
             for (int r = 0; r < 16; r++) raw[r] = nraw[r];
             request(nraw, min(l + 1, k - 1));
@@ -139,6 +151,11 @@ __global__ void __launch_bounds__(NttPlan<L>::NT, MINW) k_keyswitch_rr(const uin
             asm volatile("" : "+v"(tl));           // opaque copy of tid: keeps LDS/twiddle address math and twiddle loads inside the
                                                    // loop (hoisted as loop invariants they cost >150 VGPRs and spill)
             T v[16];
+            if constexpr (DIG) {
+#pragma unroll
+                for (int r = 0; r < 16; r++) v[r] = (T)dsrc[pass_index<L, SA, 0>(tl, r)];
+                dsrc += n;
+            } else {
 #pragma unroll
             for (int r = 0; r < 16; r++) {
                 uint64_t t = (raw[r] >> sh) & mask;
@@ -146,6 +163,7 @@ __global__ void __launch_bounds__(NttPlan<L>::NT, MINW) k_keyswitch_rr(const uin
                 v[r] = A.load(t);                  // F64: the first recentring of the transform reduces digits >= q_j
             }
             if constexpr (std::is_same<T, double>::value) { if (mask >= q) AR::renorm(v, A.m); }     // digits below q_j need no recentring (uniform branch)
+            }
             ntt_forward_regs<FW, L, KS_PRE_SYNC != 0>(v, s, fwt, A.m, tl);
             const T *k0 = kp + (size_t)j * n, *k1 = kp + kn + (size_t)j * n;
 #pragma unroll
@@ -525,10 +543,13 @@ template <int L> NTT_DEV void ks_gather_automorphism(uint64_t (&raw)[16], const 
 //                    part[ct][g][2][k][N] (transform order, same 16 B/lane pattern as the key reads)
 //   k_ks_sum_intt  : block = (ct, j, component p): sum of the partials over g -> inverse transform -> (+ add_p) -> out
 // Same residues as the fused kernel (exact arithmetic in both), HBM traffic 2 * tot * 2kN words per ciphertext more.
-template <int L, class AR>
+// KsDigits<AR> (both k_ks_digit_mac and k_ks_limb_mac): ready-made digit polynomials, see k_keyswitch_rr
+template <int L, class AR_>
 __global__ void __launch_bounds__(NttPlan<L>::NT) k_ks_digit_mac(const uint64_t *__restrict__ target, size_t tgt_stride, const void *__restrict__ key_,
                                                                   void *__restrict__ part_, const DevConsts *__restrict__ C, int galois, uint32_t tot, uint32_t perm_elt,
                                                                   const KsItem *__restrict__ items) {
+    typedef typename KsSrc<AR_>::P AR;
+    constexpr bool DIG = KsSrc<AR_>::dig;
     typedef typename AR::T T;
     extern __shared__ __align__(16) unsigned char smem[];
     T *s = reinterpret_cast<T *>(smem);
@@ -552,6 +573,12 @@ __global__ void __launch_bounds__(NttPlan<L>::NT) k_ks_digit_mac(const uint64_t 
         src = (const NTT_GLOBAL uint64_t *)it.in + kn + (size_t)l * n; keyp = (const NTT_GLOBAL T *)it.key; perm_elt = it.elt;
     }
     T v[16];
+    if constexpr (DIG) {
+        static_assert(std::is_same<T, double>::value, "ready-made digits: FP64 policies");
+        const double *dsrc = reinterpret_cast<const double *>(target) + (size_t)ct * tgt_stride + (size_t)g * n;
+#pragma unroll
+        for (int r = 0; r < 16; r++) v[r] = (T)dsrc[pass_index<L, SA, 0>(tid, r)];
+    } else {
     uint64_t raw[16];
     if (perm_elt) ks_gather_automorphism<L>(raw, src, perm_elt, C->q[l].q, s, tid);
     else {
@@ -566,6 +593,7 @@ __global__ void __launch_bounds__(NttPlan<L>::NT) k_ks_digit_mac(const uint64_t 
         v[r] = A.load(t);
     }
     if constexpr (std::is_same<T, double>::value) { if (mask >= q) AR::renorm(v, A.m); }
+    }
     ntt_forward_regs<AR, L>(v, s, A.fw, A.m, tid);
     const NTT_GLOBAL T *k0 = keyp + (size_t)g * 2 * kn + (size_t)j * n, *k1 = k0 + kn;
     T *o0 = reinterpret_cast<T *>(part_) + (((size_t)ct * tot + g) * 2) * kn + (size_t)j * n, *o1 = o0 + kn;
@@ -584,10 +612,12 @@ __global__ void __launch_bounds__(NttPlan<L>::NT) k_ks_digit_mac(const uint64_t 
 // Middle ground for batches of ~7-32 ciphertexts: block = (ct, source limb l, output limb j) runs the digits of ONE source limb
 // through the fused loop (accumulators in registers) and leaves one partial pair per (ct, l): k*k workgroups per ciphertext
 // instead of k (fused) or digits*k (k_ks_digit_mac), and k_ks_sum_intt adds k partials instead of all digits.
-template <int L, class AR>
+template <int L, class AR_>
 __global__ void __launch_bounds__(NttPlan<L>::NT) k_ks_limb_mac(const uint64_t *__restrict__ target, size_t tgt_stride, const void *__restrict__ key_,
                                                                  void *__restrict__ part_, const DevConsts *__restrict__ C, int galois, uint32_t accmax, uint32_t perm_elt,
                                                                  const KsItem *__restrict__ items) {
+    typedef typename KsSrc<AR_>::P AR;
+    constexpr bool DIG = KsSrc<AR_>::dig;
     typedef typename AR::T T;
     extern __shared__ __align__(16) unsigned char smem[];
     T *s = reinterpret_cast<T *>(smem);
@@ -611,6 +641,8 @@ __global__ void __launch_bounds__(NttPlan<L>::NT) k_ks_limb_mac(const uint64_t *
         src = (const NTT_GLOBAL uint64_t *)it.in + kn + (size_t)l * n; keyp = (const NTT_GLOBAL T *)it.key; perm_elt = it.elt;
     }
     uint64_t raw[16];
+    if constexpr (DIG) static_assert(std::is_same<T, double>::value, "ready-made digits: FP64 policies");
+    else {
     if (perm_elt) ks_gather_automorphism<L>(raw, src, perm_elt, C->q[l].q, s, tid);
     else {
         uint32_t t0 = tid;
@@ -619,6 +651,8 @@ __global__ void __launch_bounds__(NttPlan<L>::NT) k_ks_limb_mac(const uint64_t *
         for (int r = 0; r < 16; r++) raw[r] = src[pass_index<L, SA, 0>(t0, r)];
     }
     ks_premultiply(raw, C, l);
+    }
+    const double *dsrc = reinterpret_cast<const double *>(target) + (size_t)ct * tgt_stride + (size_t)g0 * n;      // DIG: the digits of limb l
     T acc0[16], acc1[16];
 #pragma unroll
     for (int r = 0; r < 16; r++) { acc0[r] = 0; acc1[r] = 0; }
@@ -629,6 +663,11 @@ __global__ void __launch_bounds__(NttPlan<L>::NT) k_ks_limb_mac(const uint64_t *
         uint32_t tl = tid;
         asm volatile("" : "+v"(tl));
         T v[16];
+        if constexpr (DIG) {
+#pragma unroll
+            for (int r = 0; r < 16; r++) v[r] = (T)dsrc[pass_index<L, SA, 0>(tl, r)];
+            dsrc += n;
+        } else {
 #pragma unroll
         for (int r = 0; r < 16; r++) {
             uint64_t t = (raw[r] >> sh) & mask;
@@ -636,6 +675,7 @@ __global__ void __launch_bounds__(NttPlan<L>::NT) k_ks_limb_mac(const uint64_t *
             v[r] = A.load(t);
         }
         if constexpr (std::is_same<T, double>::value) { if (mask >= q) AR::renorm(v, A.m); }
+        }
         ntt_forward_regs<AR, L, KS_PRE_SYNC != 0>(v, s, A.fw, A.m, tl);
         const NTT_GLOBAL T *k0 = kp + (size_t)j * n, *k1 = kp + kn + (size_t)j * n;
 #pragma unroll

@@ -68,3 +68,23 @@ template <bool ABS> static int launch_mfma_p(cn_ctx *c, const GemmLaunch &g) {
     return 0;
 }
 int cn_l_gemm_mfma(cn_ctx *c, const GemmLaunch &g) { return g.abs ? launch_mfma_p<true>(c, g) : launch_mfma_p<false>(c, g); }
+
+// digit GEMM (cn_square_gemm): DG = 5 digits of a source limb per workgroup (a 50-bit limb at dbc 10), more digits per limb in further groups
+template <int MT> static void launch_digit(cn_ctx *c, const DigitGemmLaunch &g, uint32_t ndg, uint32_t mtiles) {
+    const size_t blocks = (size_t)(c->hc.n >> 8) * c->hc.k * ndg * mtiles * g.G;
+    hipLaunchKernelGGL((k_digit_gemm<MT, 5>), dim3((uint32_t)blocks), dim3(256), 0, c->stream, g.in, g.in_unit, (const int32_t *)g.idx, (const double *)g.W,
+                       (const int32_t *)g.oidx, g.S, c->dc, g.G, g.M, g.K, mtiles, g.Kp, g.Kw, ndg);
+}
+int cn_l_digit_gemm(cn_ctx *c, const DigitGemmLaunch &g) {
+    uint32_t ndmax = 0; for (uint32_t l = 0; l < c->hc.k; l++) ndmax = std::max(ndmax, c->hc.rl_dig[l]);
+    const uint32_t ndg = (ndmax + 4) / 5, mtiles = (g.M + g.MT - 1) / g.MT;
+    if ((c->hc.n & 255) || (uint64_t)(c->hc.n >> 8) * c->hc.k * ndg * mtiles * g.G >= (1ull << 31)) return cn_fail(CN_ERR_ARG, "internal: digit GEMM grid");
+    switch (g.MT) {
+        case 10: launch_digit<10>(c, g, ndg, mtiles); break;
+        case 2: launch_digit<2>(c, g, ndg, mtiles); break;
+        default: return cn_fail(CN_ERR_ARG, "internal: digit GEMM tile %u", g.MT);
+    }
+    HIPCHK(hipGetLastError());
+    cn_launch_count(c);
+    return 0;
+}

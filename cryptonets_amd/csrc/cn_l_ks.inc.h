@@ -17,10 +17,16 @@ template <int L> static int set_attrs_l(size_t bytes) {
     CHECK(big_lds(k_keyswitch_rr<L, AR>, bytes)); CHECK(big_lds(k_keyswitch_rr<L, AR, 1, false, true>, bytes));
     if constexpr (KsFwd<AR, L>::lds) { CHECK(big_lds(k_keyswitch_rr<L, AR, 1, true>, ks_twl_lds<L>())); CHECK(big_lds(k_keyswitch_rr<L, AR, 1, true, true>, ks_twl_lds<L>())); }
     CHECK(big_lds(k_ks_digit_mac<L, AR>, bytes)); CHECK(big_lds(k_ks_limb_mac<L, AR>, bytes)); CHECK(big_lds(k_ks_sum_intt<L, AR>, bytes));
+    if constexpr (kF64) {               // the instantiations that read ready-made digits (KsArgs::dig)
+        CHECK(big_lds(k_keyswitch_rr<L, KsDigits<AR>, 1, false, false>, bytes));
+        if constexpr (KsFwd<AR, L>::lds) CHECK(big_lds(k_keyswitch_rr<L, KsDigits<AR>, 1, true, false>, ks_twl_lds<L>()));
+        CHECK(big_lds(k_ks_digit_mac<L, KsDigits<AR>>, bytes)); CHECK(big_lds(k_ks_limb_mac<L, KsDigits<AR>>, bytes));
+    }
     return 0;
 }
 static int set_attrs(uint32_t logn, size_t bytes) {
-    if constexpr (kF64) { if (logn == 12) { CHECK(big_lds(k_keyswitch_rr<12, AR, 1, true>, ks_twl_lds<12>())); CHECK(big_lds(k_keyswitch_rr<12, AR, 1, true, true>, ks_twl_lds<12>())); } }   // N = 4096: image + LDS twiddle table = 66.5 KiB
+    if constexpr (kF64) { if (logn == 12) { CHECK(big_lds(k_keyswitch_rr<12, AR, 1, true>, ks_twl_lds<12>())); CHECK(big_lds(k_keyswitch_rr<12, AR, 1, true, true>, ks_twl_lds<12>()));
+                                           CHECK(big_lds(k_keyswitch_rr<12, KsDigits<AR>, 1, true, false>, ks_twl_lds<12>())); } }   // N = 4096: image + LDS twiddle table = 66.5 KiB
     if (logn == 13) CHECK(set_attrs_l<13>(bytes));
     if (logn == 14) {
         CHECK(set_attrs_l<14>(bytes));
@@ -34,26 +40,41 @@ static int set_attrs(uint32_t logn, size_t bytes) {
 }
 // the LDS copy of the twiddle table pays once a workgroup runs enough digit transforms of its modulus
 static const uint32_t KS_TWL_MIN_DIGITS = 12;
-template <int L, bool XI> static void launch_fused_x(cn_ctx *c, const KsArgs &a) {
+template <int L, bool XI, bool DIG = false> static void launch_fused_x(cn_ctx *c, const KsArgs &a) {
     const uint32_t tot = a.galois ? c->hc.gk_tot : c->hc.rl_tot;
+    typedef typename std::conditional<DIG, KsDigits<AR>, AR>::type ARS;
+    const uint64_t *tgt = DIG ? (const uint64_t *)a.dig : a.target;
+    const size_t tstride = DIG ? (size_t)tot * c->hc.n : a.tstride;
     if constexpr (KsFwd<AR, L>::lds) {
         if (tot >= KS_TWL_MIN_DIGITS) {
-            hipLaunchKernelGGL((k_keyswitch_rr<L, AR, 1, true, XI>), dim3(a.cnt * c->hc.k), dim3(NttPlan<L>::NT), ks_twl_lds<L>(), c->stream, a.target, a.tstride, a.add0, a.add1,
+            hipLaunchKernelGGL((k_keyswitch_rr<L, ARS, 1, true, XI>), dim3(a.cnt * c->hc.k), dim3(NttPlan<L>::NT), ks_twl_lds<L>(), c->stream, tgt, tstride, a.add0, a.add1,
                                a.astride, (const void *)a.key, a.out, c->dc, a.galois, a.accmax, a.extra, a.xstride, a.out_tab, a.xcd_cts);
             return;
         }
     }
-    hipLaunchKernelGGL((k_keyswitch_rr<L, AR, 1, false, XI>), dim3(a.cnt * c->hc.k), dim3(NttPlan<L>::NT), (size_t)ntt_lds_words(1u << L) * 8, c->stream, a.target, a.tstride,
+    hipLaunchKernelGGL((k_keyswitch_rr<L, ARS, 1, false, XI>), dim3(a.cnt * c->hc.k), dim3(NttPlan<L>::NT), (size_t)ntt_lds_words(1u << L) * 8, c->stream, tgt, tstride,
                        a.add0, a.add1, a.astride, (const void *)a.key, a.out, c->dc, a.galois, a.accmax, a.extra, a.xstride, a.out_tab, a.xcd_cts);
 }
 template <int L> static void launch_fused(cn_ctx *c, const KsArgs &a) {
+    if constexpr (kF64) { if (a.dig) { launch_fused_x<L, false, true>(c, a); return; } }
     if (c->hc.ks_xi) launch_fused_x<L, true>(c, a);
     else launch_fused_x<L, false>(c, a);
 }
 template <int L> static void launch_two_phase(cn_ctx *c, const KsArgs &a) {
     const uint32_t tot = a.galois ? c->hc.gk_tot : c->hc.rl_tot, k = c->hc.k;
     const size_t lds = (size_t)ntt_lds_words(1u << L) * 8;
-    if (a.mode == 2) {              // one partial per (ct, source limb): k*k workgroups per ciphertext, k partials to sum
+    bool dig = false;
+    if constexpr (kF64) dig = a.dig != nullptr;
+    if (dig) {                      // ready-made digit polynomials: the same two forms, first launch from KsArgs::dig
+        if constexpr (kF64) {
+            if (a.mode == 2) hipLaunchKernelGGL((k_ks_limb_mac<L, KsDigits<AR>>), dim3(a.cnt * k * k), dim3(NttPlan<L>::NT), lds, c->stream, (const uint64_t *)a.dig, (size_t)tot * c->hc.n,
+                                                (const void *)a.key, c->ks_part, c->dc, a.galois, a.accmax, 0u, (const KsItem *)nullptr);
+            else hipLaunchKernelGGL((k_ks_digit_mac<L, KsDigits<AR>>), dim3(a.cnt * tot * k), dim3(NttPlan<L>::NT), lds, c->stream, (const uint64_t *)a.dig, (size_t)tot * c->hc.n,
+                                    (const void *)a.key, c->ks_part, c->dc, a.galois, tot, 0u, (const KsItem *)nullptr);
+        }
+        hipLaunchKernelGGL((k_ks_sum_intt<L, AR>), dim3(a.cnt * k * 2), dim3(NttPlan<L>::NT), lds, c->stream, (const void *)c->ks_part, a.add0, a.add1, a.astride,
+                           a.out, c->dc, a.mode == 2 ? k : tot, a.mode == 2 ? 0xffffffffu : a.accmax, a.extra, a.xstride, a.out_tab, a.perm_elt, a.items);
+    } else if (a.mode == 2) {       // one partial per (ct, source limb): k*k workgroups per ciphertext, k partials to sum
         hipLaunchKernelGGL((k_ks_limb_mac<L, AR>), dim3(a.cnt * k * k), dim3(NttPlan<L>::NT), lds, c->stream, a.target, a.tstride, (const void *)a.key, c->ks_part,
                            c->dc, a.galois, a.accmax, a.perm_elt, a.items);
         hipLaunchKernelGGL((k_ks_sum_intt<L, AR>), dim3(a.cnt * k * 2), dim3(NttPlan<L>::NT), lds, c->stream, (const void *)c->ks_part, a.add0, a.add1, a.astride,

@@ -209,6 +209,7 @@ struct cn_ctx {
     int cus = 0;              // compute units of the device
     uint64_t folded_zero = 0;  // zero encryptions folded so far
     uint64_t mr_pipelined = 0; // cn_mul_relin chunks and flushed Multiply + Relinearize groups that ran through pipelined_halves
+    uint64_t sg_fused = 0;     // cn_square_gemm calls that ran the one-key-switch-per-output form
     uint64_t uid = 0;         // creation order within the process (cn_ctx_create)
     hipStream_t stream2 = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr; bool stream2_failed = false;   // second stream of pipelined_halves (aux_stream_ready)
     // deferred submission (cn_set_option("defer", 1)): per-ciphertext calls are queued and flushed as batched launches; 2: ... and submitted without the
@@ -251,6 +252,8 @@ struct KsArgs {
     uint32_t perm_elt = 0;    // two-launch variants: Galois element of a rotation whose automorphism the kernels apply while loading (target / add0 = the UNPERMUTED c1 / c0)
                               // k_keyswitch_pair14: target = sigma(c1) already, add0 = the UNPERMUTED c0 (permuted through LDS by the workgroup that owns the limb)
     uint32_t next_elt = 0; uint64_t *next_out = nullptr;   // k_keyswitch_pair14: the new c1 leaves a second time as sigma_next(c1) -> next_out[ct][k][N] (rotate-and-add chains)
+    const double *dig = nullptr;     // register-radix kernels, FP64 policies, relinearisation: ready-made digit polynomials [cnt][rl_tot][N] (exact signed doubles, |S| < q_j / 2)
+                                     // instead of `target` (cn_square_gemm: the weight-combined digits of a dense layer's inputs)
 };
 // k_encrypt_fold (cn_k_rr.hip.h): a scalar-product output that receives the weighted sum of `count` folded zero encryptions, and the terms of all outputs
 struct FoldOut { uint64_t *out; uint32_t first, count; };               // terms [first, first + count) of the term table
@@ -301,6 +304,15 @@ struct GemmLaunch {
 inline uint32_t gemm_f64_rows(uint32_t K) { return ((K + 15) & ~15u) + 16; }
 int cn_l_gemm(cn_ctx *c, const GemmLaunch &g);
 int cn_l_gemm_mfma(cn_ctx *c, const GemmLaunch &g);   // k_scalar_gemm_mfma: W = weight digit fragments, idx rows of ksteps * 32 entries
+// digit GEMM of cn_square_gemm (k_digit_gemm): in = component 2 of product 0 (products in_unit words apart), S [outputs][rl_tot][N] doubles; W = signed doubles
+// [G][mtiles][Kw][MT], MT = 10 or 2
+struct DigitGemmLaunch {
+    const uint64_t *in; size_t in_unit; const void *idx; const void *W; const void *oidx; double *S;
+    uint32_t G, M, K, Kp, Kw, MT;
+};
+inline uint32_t digit_gemm_tile(uint32_t M) { return M > 2 ? 10u : 2u; }
+inline uint32_t digit_gemm_rows(uint32_t K) { return ((K + 7) & ~7u) + 8; }        // K terms + zero rows: the kernel's sets of four terms run past K
+int cn_l_digit_gemm(cn_ctx *c, const DigitGemmLaunch &g);
 // modulus switching (cn_l_modswitch.hip): `items` (ciphertext, poly) pairs [items][ks][N] -> [items][kd][N] on c's stream with the constants of the source context
 int cn_l_mod_switch(cn_ctx *c, const uint64_t *src, uint64_t *dst, const DevConsts *src_consts, uint32_t ks, uint32_t kd, uint32_t items, uint32_t logn,
                     bool f64, bool *ran_f64);

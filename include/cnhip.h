@@ -194,6 +194,7 @@ int cn_set_option(cn_ctx *ctx, const char *name, int value);
  *   "folded_zero_encryptions"  zero encryptions folded so far ("fold_zero")
  *   "mul_relin_pipelined"      cn_mul_relin chunks and flushed groups of queued Multiply + Relinearize calls that ran in parts over the context's two
  *                              streams ("sq_halves"; counts up)
+ *   "square_gemm_fused"        cn_square_gemm calls that ran one key switch per output (counts up; the others took the two separate steps)
  *   "pool_arrays"              device arrays cached for reuse (the temporaries of a live graph are reserved out of them)
  *   "stream_tries"             streams cn_ctx_create tried until one had a hardware queue of its own (< 0: none had; CN_STREAM_PROBE=0 takes the first) */
 int cn_get_option(cn_ctx *ctx, const char *name, int *value);
@@ -331,6 +332,15 @@ int cn_relinearize(cn_ctx *ctx, cn_handle in3, uint32_t ii, cn_handle out, uint3
  * published without the lock (defer = 2). */
 int cn_mul_relin(cn_ctx *ctx, cn_handle a, uint32_t ai, uint32_t a_stride, cn_handle b, uint32_t bi, uint32_t b_stride,
                  cn_handle out, uint32_t oi, uint32_t count);
+/* SquareActivation followed by the PoolLayer behind it, as one call: squares the ciphertexts in[ii .. ii + n_in) (n_in = the largest input index of the plan + 1)
+ * and writes the O outputs that cn_mul_relin(in, ii -> tmp) followed by cn_gemm_plan_apply(plan, tmp, out, oi) would write - the same words, bias included; the
+ * counters of cn_stats that mirror OperationsCount advance as for those two calls.  The relinearized squares themselves are not produced: a key switch is linear in
+ * the digits of its operand, so the layer pair needs one key switch per OUTPUT, fed with the weight-combined digit polynomials S = sum_k w_ok digit(d2_k) - digits
+ * taken per input, before the sum, hence the reference's words (unlike relinearizing the sum of size-3 products).  That form runs when the plan's weights are small
+ * (|w| < 2^20 centred), max_o sum_k |w_ok| (2^dbc - 1) is below every q_j / 2 and below 2^52, every coefficient modulus and the relinearization key are on the exact-FP64
+ * path, 1024 <= N <= 8192 and "ks_xi" is 0; otherwise the call runs the two steps through a temporary - same result, no error.  `in` and `out` must be different
+ * handles; with "defer" on, queued calls are submitted first and the call runs at once; under cn_graph_begin it is recorded like its two parts. */
+int cn_square_gemm(cn_ctx *ctx, cn_handle plan, cn_handle in, uint32_t ii, cn_handle out, uint32_t oi);
 
 /* ---- rotations (HOT LOOP C) ----------------------------------------------------------- */
 /* Evaluator.ApplyGalois: automorphism + key switch of c1 */
