@@ -94,7 +94,8 @@ struct GemmPlan {
     size_t off_oidx = 0, off_bidx = 0, off_w = 0;
     char *dev = nullptr;                     // persistent plans: device copy of `host`
     // cn_square_gemm: the layer may run on the digits of the unrelinearized products (square_gemm_plan_ok) - signed weights [G][mtiles][dKw][dMT] at off_dw
-    bool dig = false; uint32_t dMT = 0, dKw = 0; size_t off_dw = 0;
+    // dig_mfma: the digit GEMM runs on the matrix cores from the fragments at off_w (no table at off_dw)
+    bool dig = false, dig_mfma = false; uint32_t dMT = 0, dKw = 0; size_t off_dw = 0;
 };
 // ---- rotations of n ciphertexts by n DIFFERENT step counts as one launch chain (cn_rotate_rows_many; the queued RotateRows calls of one level).
 // A single-image network rotates the 13 masked vectors of an Interleave by 13 different amounts, the 5 maps of a Vectorize by 5: one rotation

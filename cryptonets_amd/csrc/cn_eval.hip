@@ -331,8 +331,14 @@ int build_gemm_plan(cn_ctx *ctx, const int32_t *idx, const uint64_t *W, uint32_t
             for (uint32_t kk = 0; kk < K; kk++) if (hidx[(size_t)g * Kp + kk] >= 0) { const uint64_t w = wr[kk]; sum += w >= ctx->hc.t_half ? t - w : w; }
             ok = sum <= lim;
         }
-        if (ok) {
-            P.dig = true; P.dMT = digit_gemm_tile(M); P.dKw = digit_gemm_rows(K);
+        // Matrix-core form (k_digit_gemm_mfma) where the plan's own GEMM takes the matrix cores (P.mfma: small weights in P <= 3 signed byte digits |w_p| <= 128, M >= 16,
+        // 3 K < 2^17, rows of 32 K gather entries, fragments at off_w) and a digit splits into two int8 pieces: dg + 128 = (lo + 128) + 256 hi with hi <= 127 needs
+        // 2^dbc - 1 + 128 < 2^15, dbc <= 14 (then hi <= 64).  i32 head-room: a diagonal receives per term one lo x w_p product (<= 128 * 128) and one hi x w_(p-1) product
+        // (<= 64 * 128), K <= 43690 terms: 43690 * 24576 = 1 073 725 440 < 2^31.  N a multiple of 256: the column tiles of a slice are dealt to the 8 XCDs.
+        // Otherwise the FP64 form k_digit_gemm with its own table of signed doubles.
+        if (ok) { P.dig = true; P.dig_mfma = mfma && ctx->digit_mfma && ctx->hc.dbc <= 14 && !(ctx->hc.n & 255); }
+        if (ok && !P.dig_mfma) {
+            P.dMT = digit_gemm_tile(M); P.dKw = digit_gemm_rows(K);
             const uint32_t mtd = (M + P.dMT - 1) / P.dMT;
             dW.assign((size_t)G * mtd * P.dKw * P.dMT, 0.0);
             for (uint32_t g = 0; g < G; g++) for (uint32_t m = 0; m < M; m++) {
@@ -739,6 +745,7 @@ extern "C" int cn_square_gemm(cn_ctx *ctx, cn_handle plan, cn_handle in, uint32_
     }
     CHECK(run_gemm_plan(ctx, P, P.dev, nullptr, OB, oi, t3));                     // components 0 and 1 (+ bias) straight into the outputs
     DigitGemmLaunch dg{t3 + 2 * kn, 3 * kn, P.dev, P.dev + P.off_dw, P.dev + P.off_oidx, S, P.G, P.M, P.K, P.Kp, P.dKw, P.dMT};
+    if (P.dig_mfma) { dg.W = P.dev + P.off_w; dg.mfma = true; dg.P = P.P; dg.mtiles = P.mtiles; dg.ksteps = P.ksteps; }
     CHECK(cn_l_digit_gemm(ctx, dg));
     uint64_t *o = OB->d + oi * OB->item_words;
     CHECK(do_keyswitch(ctx, nullptr, 0, o, o + kn, 2 * kn, ctx->rlk, o, P.O, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, S));

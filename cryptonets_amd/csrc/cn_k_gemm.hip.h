@@ -579,3 +579,138 @@ __global__ void __launch_bounds__(256) k_digit_gemm(const uint64_t *__restrict__
             if (d0 + (uint32_t)d < nd) S[((size_t)o * tot + g0 + d0 + (uint32_t)d) * n + i] = acc[d][m];
     }
 }
+
+// ------------------------------------------------------------------ digit GEMM on the int8 matrix cores (exact)
+// The same sums S[o][(l, d)][i] = sum_k w[o][k] * dig_d(in[idx[k]][l][i]) as k_digit_gemm, as an integer contraction on v_mfma_i32_32x32x32_i8 with the structure of
+// k_scalar_gemm_mfma: workgroup = 4 waves = 32 coefficient columns of one source limb l x up to four 32-row output tiles (wave w: tile 4 mg + w) x a group of DG digits;
+// the waves build the B operand together through LDS (one barrier per K step, ring of three register sets, gather-table entries as scalar loads - see there for why).
+// A operand: the plan's weight fragments as they are (pack_gemm_mfma: P signed base-256 digits w_p of every weight, zero for padded taps / rows / terms).
+// B operand: a digit dg < 2^dbc, dbc <= 14, is split as dg = lo + 256 hi with t = dg + 128, lo = (t & 255) - 128 in -128..127 (the byte (t & 255) ^ 0x80 read as int8)
+// and hi = t >> 8 in 0..64 - exact by construction, both int8.  Products lo w_p have weight 256^p, hi w_p weight 256^(p + 1): P + 1 diagonals per digit,
+//   S = sum_j 256^j acc_j,   acc_j = sum_k (lo_k w_(k,j) + hi_k w_(k,j-1)).
+// A diagonal receives at most two products per term, together at most 128 * 128 + 64 * 128 = 24576 in magnitude; the plan takes this form only with 3 K < 2^17
+// (gemm_mfma_ok), K <= 43690 terms: |acc_j| <= 1 073 725 440 < 2^31 (the bound is enforced where the plan is built, cn_eval.hip).
+// Fold in FP64, lowest diagonal first: every partial sum is an integer below 2^53 in magnitude - acc_0 + 256 acc_1 + 65536 acc_2 < 2^47.1 for any i32 values, and the top
+// diagonal of P = 3 holds only hi w_2 products (|w_2| <= 128: |acc_3| < 2^28.5, 2^24 |acc_3| < 2^52.5) - so each FMA is exact and the result is the S of k_digit_gemm
+// (|S| < 2^52 by the plan's digit check), stored where that kernel stores it.  An accumulator register holds 32 consecutive coefficients per half-wave: 256 B per store.
+// Digit groups: 16 (P + 1) DG accumulator registers per wave; all five digits of a CryptoNets limb (240 at P = 2) do not fit two workgroups per CU, so a workgroup takes
+// DG of them and the groups of a slice take block ids 8 apart - one XCD, adjacent in time: the second group reads the slice from that L2.  Limbs with fewer digits
+// skip the absent ones (rl_dig), a group without any digit leaves at once.
+template <int P, int DG>
+__global__ void __launch_bounds__(256, 2) k_digit_gemm_mfma(const uint64_t *__restrict__ in, size_t in_unit, const int32_t *__restrict__ idx, const int8_t *__restrict__ Wf,
+                                                            const int32_t *__restrict__ out_idx, double *__restrict__ S, const DevConsts *__restrict__ C, uint32_t G,
+                                                            uint32_t M, uint32_t mtiles, uint32_t ksteps, uint32_t ndg) {
+    constexpr int NP = 2 * DG, D = P + 1, NB = GEMM_MFMA_DEPTH + 1;
+    __shared__ __align__(16) uint32_t frag[NB][NP][64][4];         // [buffer][digit, piece][lane][slot group q]
+    const uint32_t n = C->n, k = C->k, ctiles = n >> 5;            // n is a multiple of 256 (launcher)
+    const uint32_t lane = threadIdx.x & 63, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), half = lane >> 5, col = lane & 31;
+    uint32_t b = blockIdx.x;
+    const uint32_t x8 = b & 7; b >>= 3;
+    const uint32_t dgi = b % ndg; b /= ndg;
+    const uint32_t ctile = (b % (ctiles >> 3)) * 8 + x8; b /= ctiles >> 3;
+    const uint32_t l = b % k; b /= k;
+    const uint32_t mgroups = (mtiles + 3) >> 2, mg = b % mgroups, g = b / mgroups;
+    const uint32_t d0 = dgi * DG, nd = C->rl_dig[l];
+    if (d0 >= nd) return;
+    const uint32_t cnt = min((uint32_t)DG, nd - d0);
+    uint32_t g0 = 0;                                           // index of the first digit of limb l in the key
+    for (uint32_t x = 0; x < l; x++) g0 += C->rl_dig[x];
+    const uint32_t mt = mg * 4 + wave;
+    const bool active = mt < mtiles;                           // a wave without an output tile still loads its share of the B operand
+    const uint32_t dbc = (uint32_t)C->dbc, mask = (1u << dbc) - 1;
+    uint32_t sh[DG];
+#pragma unroll
+    for (int d = 0; d < DG; d++) sh[d] = min(dbc * (d0 + (uint32_t)d), 63u);
+    const size_t e = (size_t)l * n + (size_t)ctile * 32 + col;
+    const uint32_t Kp = ksteps * 32;
+    const int32_t *gi = idx + (size_t)g * Kp + 4 * wave;       // + 32 ks + 16 half + u
+    const int8_t *wf = Wf + ((((size_t)g * P) * mtiles + (active ? mt : 0)) * ksteps) * 1024 + (size_t)lane * 16;       // + (p * mtiles * ksteps + ks) * 1024
+    v16i_t acc[DG][D];
+#pragma unroll
+    for (int d = 0; d < DG; d++)
+#pragma unroll
+        for (int j = 0; j < D; j++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc[d][j][r] = 0;
+    // requests behind the last step repeat the last step, as in k_scalar_gemm_mfma (no branch around loads in flight)
+    const uint32_t klast = ksteps - 1;
+    auto load_idx = [&](int32_t (&s)[8], uint32_t ks) {
+        const int32_t *t = gi + (size_t)min(ks, klast) * 32;
+#pragma unroll
+        for (int u = 0; u < 4; u++) { s[u] = t[u]; s[4 + u] = t[16 + u]; }
+    };
+    auto load_x = [&](uint64_t (&x)[4], const int32_t (&s)[8]) {   // a padded tap reads product 0 (its weight digits are 0)
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            size_t o0 = (size_t)max(s[u], 0) * in_unit, o1 = (size_t)max(s[4 + u], 0) * in_unit;
+            asm volatile("" : "+s"(o0), "+s"(o1));
+            x[u] = in[(half ? o1 : o0) + e];
+        }
+    };
+    auto load_a = [&](v4i_t (&af)[P], uint32_t ks) {
+#pragma unroll
+        for (int p = 0; p < P; p++) af[p] = *reinterpret_cast<const v4i_t *>(wf + ((size_t)p * mtiles * ksteps + min(ks, klast)) * 1024);
+    };
+    uint64_t xs[NB][4];
+    v4i_t afs[NB][P];
+    int32_t nidx[8];
+    load_idx(nidx, 0);
+#pragma unroll
+    for (int s = 0; s < GEMM_MFMA_DEPTH; s++) { load_x(xs[s], nidx); load_a(afs[s], s); load_idx(nidx, s + 1); }
+    auto step = [&](uint64_t (&x)[4], v4i_t (&af)[P], uint64_t (&xn)[4], v4i_t (&afn)[P], uint32_t ks, uint32_t (*fb)[64][4]) {
+        // digits of the 4 words, + 128: byte 0 = lo + 128, byte 1 = hi; transposed into one dword per (digit, piece); published
+#pragma unroll
+        for (int d = 0; d < DG; d++) {
+            uint32_t t[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) t[u] = ((uint32_t)(x[u] >> sh[d]) & mask) + 128u;
+            const uint32_t ab = byte_perm(t[1], t[0], 0x05010400u), cd = byte_perm(t[3], t[2], 0x05010400u);      // (a.lo b.lo a.hi b.hi), (c.lo d.lo c.hi d.hi)
+            fb[2 * d][lane][wave] = byte_perm(cd, ab, 0x05040100u) ^ 0x80808080u;
+            fb[2 * d + 1][lane][wave] = byte_perm(cd, ab, 0x07060302u);
+        }
+        load_x(xn, nidx); load_a(afn, ks + GEMM_MFMA_DEPTH);
+        load_idx(nidx, ks + GEMM_MFMA_DEPTH + 1);
+        __syncthreads();
+        if (active) {
+#pragma unroll
+            for (int d = 0; d < DG; d++) {
+                if ((uint32_t)d >= cnt) continue;
+                const v4i_t blo = *reinterpret_cast<const v4i_t *>(&fb[2 * d][lane][0]), bhi = *reinterpret_cast<const v4i_t *>(&fb[2 * d + 1][lane][0]);
+#pragma unroll
+                for (int p = 0; p < P; p++) acc[d][p] = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[p], blo, acc[d][p], 0, 0, 0);
+#pragma unroll
+                for (int p = 0; p < P; p++) acc[d][p + 1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[p], bhi, acc[d][p + 1], 0, 0, 0);
+            }
+        }
+    };
+    uint32_t ks = 0;
+    for (; ks + NB <= ksteps; ks += NB) {
+#pragma unroll
+        for (int s = 0; s < NB; s++) step(xs[s], afs[s], xs[(s + GEMM_MFMA_DEPTH) % NB], afs[(s + GEMM_MFMA_DEPTH) % NB], ks + s, frag[s]);
+    }
+#pragma unroll
+    for (int s = 0; s < NB - 1; s++)
+        if (ks + s < ksteps) step(xs[s], afs[s], xs[(s + GEMM_MFMA_DEPTH) % NB], afs[(s + GEMM_MFMA_DEPTH) % NB], ks + s, frag[s]);
+    if (!active) return;
+    // ---- fold the diagonals of every digit to one exact double and store it: the table entries of the 16 rows first (one round trip)
+    const uint32_t tot = C->rl_tot, olast = G * M - 1;
+    int32_t oo[16];
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const uint32_t mm = mt * 32 + (uint32_t)(r & 3) + 8u * (uint32_t)(r >> 2) + 4u * half;
+        oo[r] = out_idx[min(g * M + mm, olast)];
+        if (mm >= M) oo[r] = -1;
+    }
+#pragma unroll
+    for (int d = 0; d < DG; d++) {
+        if ((uint32_t)d >= cnt) continue;
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            if (oo[r] < 0) continue;                               // row past M, or padding member of a smaller group
+            double v = (double)acc[d][0][r];
+#pragma unroll
+            for (int j = 1; j < D; j++) v = __fma_rn((double)acc[d][j][r], (double)(1u << (8 * j)), v);
+            S[((size_t)oo[r] * tot + g0 + d0 + (uint32_t)d) * n + (size_t)ctile * 32 + col] = v;
+        }
+    }
+}

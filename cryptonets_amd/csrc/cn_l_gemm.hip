@@ -75,8 +75,29 @@ template <int MT> static void launch_digit(cn_ctx *c, const DigitGemmLaunch &g, 
     hipLaunchKernelGGL((k_digit_gemm<MT, 5>), dim3((uint32_t)blocks), dim3(256), 0, c->stream, g.in, g.in_unit, (const int32_t *)g.idx, (const double *)g.W,
                        (const int32_t *)g.oidx, g.S, c->dc, g.G, g.M, g.K, mtiles, g.Kp, g.Kw, ndg);
 }
+// matrix-core form: DG = digit_gemm_mfma_group(P) digits per workgroup; the digit groups of a (column tile, limb) take block ids 8 apart (k_digit_gemm_mfma)
+template <int P, int DG> static void launch_digit_mfma(cn_ctx *c, const DigitGemmLaunch &g, uint32_t ndg, size_t blocks) {
+    hipLaunchKernelGGL((k_digit_gemm_mfma<P, DG>), dim3((uint32_t)blocks), dim3(256), 0, c->stream, g.in, g.in_unit, (const int32_t *)g.idx, (const int8_t *)g.W,
+                       (const int32_t *)g.oidx, g.S, c->dc, g.G, g.M, g.mtiles, g.ksteps, ndg);
+}
+static int digit_gemm_mfma(cn_ctx *c, const DigitGemmLaunch &g, uint32_t ndmax) {
+    const uint32_t DG = digit_gemm_mfma_group(g.P), ndg = (ndmax + DG - 1) / DG, mgroups = (g.mtiles + 3) / 4;
+    const uint64_t blocks = (uint64_t)g.G * mgroups * c->hc.k * (c->hc.n / 32) * ndg;
+    if ((c->hc.n & 255) || !g.ksteps || blocks >= (1ull << 31)) return cn_fail(CN_ERR_ARG, "internal: digit GEMM grid");
+    switch (g.P) {
+        case 1: launch_digit_mfma<1, 3>(c, g, ndg, blocks); break;
+        case 2: launch_digit_mfma<2, 3>(c, g, ndg, blocks); break;
+        case 3: launch_digit_mfma<3, 2>(c, g, ndg, blocks); break;
+        default: return cn_fail(CN_ERR_ARG, "internal: %u weight digit planes", g.P);
+    }
+    HIPCHK(hipGetLastError());
+    cn_launch_count(c);
+    c->dg_mfma++;
+    return 0;
+}
 int cn_l_digit_gemm(cn_ctx *c, const DigitGemmLaunch &g) {
     uint32_t ndmax = 0; for (uint32_t l = 0; l < c->hc.k; l++) ndmax = std::max(ndmax, c->hc.rl_dig[l]);
+    if (g.mfma) return digit_gemm_mfma(c, g, ndmax);
     const uint32_t ndg = (ndmax + 4) / 5, mtiles = (g.M + g.MT - 1) / g.MT;
     if ((c->hc.n & 255) || (uint64_t)(c->hc.n >> 8) * c->hc.k * ndg * mtiles * g.G >= (1ull << 31)) return cn_fail(CN_ERR_ARG, "internal: digit GEMM grid");
     switch (g.MT) {

@@ -210,6 +210,9 @@ struct cn_ctx {
     uint64_t folded_zero = 0;  // zero encryptions folded so far
     uint64_t mr_pipelined = 0; // cn_mul_relin chunks and flushed Multiply + Relinearize groups that ran through pipelined_halves
     uint64_t sg_fused = 0;     // cn_square_gemm calls that ran the one-key-switch-per-output form
+    uint64_t dg_mfma = 0;      // digit GEMMs launched in the matrix-core form
+    bool digit_mfma = true;    // cn_set_option "digit_mfma": plans made from now on run their digit GEMM on the int8 matrix cores where they can (k_digit_gemm_mfma, exact); false: always
+                               // the FP64 kernel k_digit_gemm.  A switch between two live forms of one step of cn_square_gemm, set by name like "ks_xi" (no environment override)
     uint64_t uid = 0;         // creation order within the process (cn_ctx_create)
     hipStream_t stream2 = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr; bool stream2_failed = false;   // second stream of pipelined_halves (aux_stream_ready)
     // deferred submission (cn_set_option("defer", 1)): per-ciphertext calls are queued and flushed as batched launches; 2: ... and submitted without the
@@ -305,11 +308,13 @@ inline uint32_t gemm_f64_rows(uint32_t K) { return ((K + 15) & ~15u) + 16; }
 int cn_l_gemm(cn_ctx *c, const GemmLaunch &g);
 int cn_l_gemm_mfma(cn_ctx *c, const GemmLaunch &g);   // k_scalar_gemm_mfma: W = weight digit fragments, idx rows of ksteps * 32 entries
 // digit GEMM of cn_square_gemm (k_digit_gemm): in = component 2 of product 0 (products in_unit words apart), S [outputs][rl_tot][N] doubles; W = signed doubles
-// [G][mtiles][Kw][MT], MT = 10 or 2
+// [G][mtiles][Kw][MT], MT = 10 or 2.  mfma (k_digit_gemm_mfma): W = the plan's weight digit fragments (pack_gemm_mfma), idx rows of ksteps * 32 entries
 struct DigitGemmLaunch {
     const uint64_t *in; size_t in_unit; const void *idx; const void *W; const void *oidx; double *S;
     uint32_t G, M, K, Kp, Kw, MT;
+    bool mfma = false; uint32_t P = 0, mtiles = 0, ksteps = 0;
 };
+inline uint32_t digit_gemm_mfma_group(uint32_t P) { return P <= 2 ? 3u : 2u; }     // digits per workgroup: 16 (P + 1) DG accumulator registers per wave
 inline uint32_t digit_gemm_tile(uint32_t M) { return M > 2 ? 10u : 2u; }
 inline uint32_t digit_gemm_rows(uint32_t K) { return ((K + 7) & ~7u) + 8; }        // K terms + zero rows: the kernel's sets of four terms run past K
 int cn_l_digit_gemm(cn_ctx *c, const DigitGemmLaunch &g);

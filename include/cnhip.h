@@ -115,6 +115,9 @@ int cn_mod_switch(cn_ctx *src, cn_handle in, uint32_t ii, uint32_t count, cn_ctx
  *   "fold_zero"      flag    1                     CN_FOLD_ZERO     queued zero encryptions folded into the scalar product that reads them (below)
  *   "gemm_mfma"      flag    1                     CN_GEMM_MFMA     wide scalar GEMMs (>= 16 outputs per gather list) on the int8 matrix cores; 0 = the
  *                                                                   FP64 kernel.  Affects GEMMs planned after the call
+ *   "digit_mfma"     flag    1                     -                the digit GEMM of cn_square_gemm on the int8 matrix cores where the plan's own GEMM
+ *                                                                   takes them and a key-switch digit has at most 14 bits; 0 = the FP64 kernel (which
+ *                                                                   also serves every other plan).  The same words.  Affects GEMMs planned after the call
  *   "gemm_pair"      flag    1                     CN_GEMM_PAIR     cn_scalar_gemm / cn_gemm_plan_create merge gather lists that share at least half of
  *                                                                   their inputs in pairs (small signed weights, lists of <= 64 entries and <= 5
  *                                                                   outputs); 0 = the caller's lists.  Affects GEMMs planned after the call
@@ -195,6 +198,7 @@ int cn_set_option(cn_ctx *ctx, const char *name, int value);
  *   "mul_relin_pipelined"      cn_mul_relin chunks and flushed groups of queued Multiply + Relinearize calls that ran in parts over the context's two
  *                              streams ("sq_halves"; counts up)
  *   "square_gemm_fused"        cn_square_gemm calls that ran one key switch per output (counts up; the others took the two separate steps)
+ *   "digit_gemm_mfma"          digit GEMMs of cn_square_gemm launched in the matrix-core form ("digit_mfma"; counts up)
  *   "pool_arrays"              device arrays cached for reuse (the temporaries of a live graph are reserved out of them)
  *   "stream_tries"             streams cn_ctx_create tried until one had a hardware queue of its own (< 0: none had; CN_STREAM_PROBE=0 takes the first) */
 int cn_get_option(cn_ctx *ctx, const char *name, int *value);
