@@ -17,7 +17,7 @@ CSRC = os.path.join(_PKG, "csrc")
 SOURCES = [os.path.join(CSRC, f) for f in (
     "cn_api.hip", "cn_eval.hip", "cn_client.hip", "cn_defer.hip", "cn_multi.hip", "cn_host.cpp", "cn_tables.cpp", "cn_l_gemm.hip", "cn_l_behz.hip",
     "cn_l_rr_u64.hip", "cn_l_rr_f64.hip", "cn_l_rr_f64l.hip", "cn_l_ks_u64.hip", "cn_l_ks_f64.hip", "cn_l_ks_f64l.hip", "cn_level.hip", "cn_l_modswitch.hip",
-    "cn_l_modswitch_f64.hip", "cn_l_noise.hip", "cn_l_seeded.hip", "cn_l_keygen.hip")]
+    "cn_l_modswitch_f64.hip", "cn_l_noise.hip", "cn_l_seeded.hip", "cn_l_keygen.hip", "cn_l_packed.hip")]
 OBJ_DIR = os.path.join(_PKG, "lib", "obj")
 
 U64P = C.POINTER(C.c_uint64)
@@ -193,6 +193,9 @@ SIGNATURES = {
     "cn_ct_expand": (C.c_int, [_CTX, _H, _u32, _u32, C.c_char_p, C.c_uint64, C.c_uint64]),
     "cn_ct_upload_compact": (C.c_int, [_CTX, _H, _u32, _u32, U64P, C.c_char_p, C.c_uint64, C.c_uint64]),
     "cn_ct_download_compact": (C.c_int, [_CTX, _H, _u32, _u32, U64P]),
+    "cn_packed_words": (C.c_size_t, [_CTX, _u32]),
+    "cn_ct_download_packed": (C.c_int, [_CTX, _H, _u32, _u32, _u32, U64P]),
+    "cn_ct_upload_packed": (C.c_int, [_CTX, _H, _u32, _u32, _u32, U64P, C.c_char_p, C.c_uint64, C.c_uint64]),
     "cn_decrypt": (C.c_int, [_CTX, _H, _u32, _u32, _H, _u32]),
     "cn_noise_poly": (C.c_int, [_CTX, _H, _u32, _u32, C.POINTER(C.c_uint64)]),
     "cn_noise_norm": (C.c_int, [_CTX, _H, _u32, _u32, C.POINTER(C.c_uint64)]),
@@ -673,6 +676,38 @@ class Context:
         self._chk(self.L.cn_ct_download_compact(self._h, h, first, count, _p64(out)))
         return out
 
+    # ---- packed rows (include/cnhip.h): residues in bit_length(q_j) bits each
+    def packed_words(self, polys=1):
+        """words of one packed ciphertext of `polys` polynomials: polys * (n / 64) * sum of the moduli's bit lengths"""
+        return int(self.L.cn_packed_words(self._h, polys))
+
+    def ct_download_packed(self, h, first, count, polys=1, size=None):
+        """packed rows [count, words] of h[first : first + count]: poly 0 alone (polys = 1) or every polynomial of the handle (polys = 0; `size`: its
+        polynomials per ciphertext when the handle was not allocated through this object)"""
+        if polys not in (0, 1):
+            raise ValueError("polys: 0 (every polynomial of the handle) or 1 (c0 only)")
+        size = 1 if polys else (size or self._ct_size.get(h))
+        if size is None:
+            raise ValueError("ct_download_packed(polys=0): pass `size`, the handle was not allocated through this object")
+        out = np.empty((count, self.packed_words(size)), dtype=np.uint64)
+        self._chk(self.L.cn_ct_download_packed(self._h, h, first, count, polys, _p64(out)))
+        return out
+
+    def ct_upload_packed(self, h, first, packed, polys=1, a_seed=None, a_nonce=0, a_item0=0, size=None):
+        """packed rows [count, words] into h[first ..): polys = 1 - c0 rows, poly 1 expanded from the seed (ct_upload_compact's arguments); polys = 0 - every
+        polynomial of the handle, no seed; `size`: its polynomials per ciphertext when the handle was not allocated through this object.  Raises CnError (CN_ERR_ARG) when a row held a residue that is not below its modulus"""
+        if polys not in (0, 1):
+            raise ValueError("polys: 0 (every polynomial of the handle) or 1 (c0 only)")
+        d = np.ascontiguousarray(packed, dtype=np.uint64)
+        count = d.shape[0] if d.ndim > 1 else 1
+        size = self._ct_size.get(h) or size
+        _, nbytes = self.device_ptr(h)                     # the library reads count * packed words from the host pointer: check the row width here
+        if size is None or (polys == 1 and size != 2) or count == 0 or d.size != count * self.packed_words(1 if polys else size) \
+                or first + count > nbytes // (size * self.k * self.n * 8):
+            raise ValueError("ct_upload_packed: data of shape %s does not fit the ciphertexts of this handle" % (d.shape,))
+        seed = self._seed32(a_seed) if polys == 1 else None
+        self._chk(self.L.cn_ct_upload_packed(self._h, h, first, count, polys, _p64(d), seed, a_nonce, a_item0))
+
     def decrypt(self, ct, ci, count, pt_out, pi):
         self._chk(self.L.cn_decrypt(self._h, ct, ci, count, pt_out, pi))
 
@@ -766,3 +801,4 @@ class Context:
         s = CnStats()
         self._chk(self.L.cn_stats_get(self._h, C.byref(s), int(reset)))
         return {n: int(getattr(s, n)) for n, _ in CnStats._fields_}
+

@@ -485,3 +485,50 @@ extern "C" int cn_ct_download_compact(cn_ctx *ctx, cn_handle h, uint32_t first, 
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return 0;
 API_END }
+// ---------------------------------------------------------------- packed rows (include/cnhip.h; kernels: cn_k_packed.hip.h)
+extern "C" size_t cn_packed_words(cn_ctx *ctx, uint32_t polys) { return ctx ? (size_t)polys * cn_packed_row_words(ctx) : 0; }
+// polynomials of a packed call on B: `polys` = 0 every polynomial of B, 1 poly 0 alone; 0 = refused
+static uint32_t packed_polys(const Buffer *B, uint32_t polys) { return polys == 0 ? B->size : (polys == 1 ? 1u : 0u); }
+extern "C" int cn_ct_download_packed(cn_ctx *ctx, cn_handle h, uint32_t first, uint32_t count, uint32_t polys, uint64_t *host) { API_BODY
+    LOCK; NOT_CAPTURING("cn_ct_download_packed"); GETCT(B, h, 0);
+    const uint32_t P = packed_polys(B, polys);
+    const size_t pw = cn_packed_row_words(ctx);
+    if (!P) return fail(CN_ERR_ARG, "polys: 0 (every polynomial) or 1 (c0 only)");
+    if (!pw) return fail(CN_ERR_ARG, "packed rows need N >= 1024");
+    if (!host || !range_ok(B, first, count)) return fail(CN_ERR_ARG, "index out of range");
+    if (!count) return 0;
+    const size_t words = (size_t)count * P * pw;
+    CHECK(ensure_scratch(ctx, al(words * 8)));
+    uint64_t *stage = salloc<uint64_t>(ctx, words);
+    if (!stage) return fail(CN_ERR_HIP, "internal: scratch exhausted in cn_ct_download_packed");
+    CHECK(cn_l_pack_rows(ctx, B->d + (size_t)first * B->item_words, B->item_words, stage, count, P));
+    HIPCHK(hipMemcpyAsync(host, stage, words * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return 0;
+API_END }
+extern "C" int cn_ct_upload_packed(cn_ctx *ctx, cn_handle h, uint32_t first, uint32_t count, uint32_t polys, const uint64_t *host,
+                                   const uint8_t *a_seed32, uint64_t a_nonce, uint64_t a_item0) { API_BODY
+    LOCK; NOT_CAPTURING("cn_ct_upload_packed"); GETCT(B, h, polys == 1 ? 2 : 0);
+    const uint32_t P = packed_polys(B, polys);
+    const size_t pw = cn_packed_row_words(ctx);
+    if (!P) return fail(CN_ERR_ARG, "polys: 0 (every polynomial) or 1 (c0 only, c1 from the seed)");
+    if (!pw) return fail(CN_ERR_ARG, "packed rows need N >= 1024");
+    if (!host) return fail(CN_ERR_ARG, "null argument");
+    if (polys == 1) CHECK(seeded_args_ok(ctx, B, first, count, a_seed32, a_item0));
+    else if (!range_ok(B, first, count)) return fail(CN_ERR_ARG, "index out of range");
+    if (!count) return 0;
+    const size_t words = (size_t)count * P * pw;
+    CHECK(ensure_scratch(ctx, al(words * 8) + 256));
+    uint64_t *stage = salloc<uint64_t>(ctx, words);
+    uint32_t *flag = salloc<uint32_t>(ctx, 1);
+    if (!stage || !flag) return fail(CN_ERR_HIP, "internal: scratch exhausted in cn_ct_upload_packed");
+    HIPCHK(hipMemcpyAsync(stage, host, words * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemsetAsync(flag, 0, 4, ctx->stream));
+    CHECK(cn_l_unpack_rows(ctx, stage, B->d + (size_t)first * B->item_words, B->item_words, count, P, flag));
+    if (polys == 1) CHECK(expand_body(ctx, B, first, count, a_seed32, a_nonce, a_item0));
+    uint32_t seen = 0;
+    HIPCHK(hipMemcpyAsync(&seen, flag, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (seen) { ctx->packed_bad++; return fail(CN_ERR_ARG, "residue not below its modulus"); }
+    return 0;
+API_END }

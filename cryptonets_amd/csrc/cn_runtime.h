@@ -211,6 +211,7 @@ struct cn_ctx {
     uint64_t mr_pipelined = 0; // cn_mul_relin chunks and flushed Multiply + Relinearize groups that ran through pipelined_halves
     uint64_t sg_fused = 0;     // cn_square_gemm calls that ran the one-key-switch-per-output form
     uint64_t dg_mfma = 0;      // digit GEMMs launched in the matrix-core form
+    std::atomic<uint64_t> packed_bad{0};       // packed uploads whose rows held a residue >= its modulus (counted where the flag is read)
     bool digit_mfma = true;    // cn_set_option "digit_mfma": plans made from now on run their digit GEMM on the int8 matrix cores where they can (k_digit_gemm_mfma, exact); false: always
                                // the FP64 kernel k_digit_gemm.  A switch between two live forms of one step of cn_square_gemm, set by name like "ks_xi" (no environment override)
     uint64_t uid = 0;         // creation order within the process (cn_ctx_create)
@@ -332,6 +333,11 @@ struct SeededArgs {
     const int8_t *noise; const uint64_t *pt; uint32_t pt_stride_words;
 };
 int cn_l_seeded(cn_ctx *c, const SeededArgs &a);
+// packed rows (cn_l_packed.hip, cn_k_packed.hip.h): `cnt` ciphertexts of `polys` polynomials, packed [cnt][polys][limb] rows <-> poly 0 .. polys - 1 of the items at
+// arr + i * item_words; flag: one device word the unpack ORs 1 into when it saw a residue >= q_j (stored reduced).  stream null: the context's
+size_t cn_packed_row_words(const cn_ctx *c);
+int cn_l_unpack_rows(cn_ctx *c, const uint64_t *packed, uint64_t *arr, size_t item_words, uint32_t cnt, uint32_t polys, uint32_t *flag, hipStream_t stream = nullptr);
+int cn_l_pack_rows(cn_ctx *c, const uint64_t *arr, size_t item_words, uint64_t *packed, uint32_t cnt, uint32_t polys, hipStream_t stream = nullptr);
 // Galois keys for `elts` elements in one launch (cn_l_keygen.hip, k_ksk_gen): outs = one key address per element, fac = [tot] x CN_MAXK message factors (gen_ksk's
 // KeyFactors per entry), perm = [elts][N] NTT-domain automorphism indices, noise = the int8 polynomials [elts * tot][N] of k_sample_small; entry e of element g draws
 // its `a` at sampler item item0 + 2 (g tot + e)

@@ -28,6 +28,7 @@ Two layers, as in the reference:
 
 * compact batches - this library's own framing of seeded symmetric ciphertexts (c0 words and a public seed; `save_compact_batch` /
   `load_compact_batch` below).  NOT a SEAL 3.2 stream.
+* packed rows and packed batches - the same batches with every residue in bit_length(q_j) bits (`pack_rows`, `save_packed_batch` below).
 
   PARITY UNPINNED: no SEAL binary or SEAL-written file exists in this environment or in the reference repository, so byte
   compatibility with real SEAL 3.2 streams is restated, not tested.  What the tests pin is self-consistency (round trips of
@@ -246,6 +247,136 @@ def load_compact_batch(f, parms):
     if words.size != count * limbs * parms.n:
         raise BadStream("Bad stream format. (%d words for %d ciphertexts of %d limbs)" % (words.size, count, limbs))
     return words.reshape(count, limbs * parms.n), CompactDescriptor(a_seed, a_nonce, a_item0, count, pid), limbs
+
+
+# ------------------------------------------------------------------------------------------------ packed rows and packed batches
+# The library's own wire form without padding bits (include/cnhip.h: cn_packed_words, cn_ct_upload_packed; NOT a SEAL stream): the residues of one
+# polynomial limb in bits = bit_length(q_j) bits each.  The row is the integer sum_i v_i 2^(i bits), cut into little-endian 64-bit words: coefficient i
+# occupies bits [i bits, (i + 1) bits) of the row, bit p of the row is bit p % 64 of word p / 64.  n * bits is a multiple of 64 (n is a multiple of 64).
+def pack_rows(words, bits):
+    """uint64 [..., n] residues below 2^bits (2 <= bits <= 60) -> uint64 [..., n * bits / 64] packed rows"""
+    w = np.ascontiguousarray(words, dtype=np.uint64)
+    bits, n = int(bits), w.shape[-1]
+    if not 2 <= bits <= 60 or (n * bits) % 64:
+        raise ValueError("pack_rows: 2 <= bits <= 60 and n * bits a multiple of 64 (got bits %d, n %d)" % (bits, n))
+    if w.size and int(w.max()) >> bits:
+        raise ValueError("pack_rows: a residue does not fit %d bits" % bits)
+    pos = np.arange(n, dtype=np.uint64) * np.uint64(bits)
+    wd, sh = (pos >> np.uint64(6)).astype(np.intp), pos & np.uint64(63)
+    nw = n * bits // 64
+    flat = w.reshape(-1, n)
+    # bits < 64: a coefficient starts in every word, so the coefficients that start in word w are a run [start[w], start[w + 1]).  Their fields are disjoint
+    # (the sums are ORs): word w = their low parts + what the last coefficient that starts in word w - 1 spills over
+    start = np.searchsorted(wd, np.arange(nw))
+    low = np.add.reduceat(flat << sh, start, axis=1)
+    spill = np.add.reduceat((flat >> (np.uint64(63) - sh)) >> np.uint64(1), start, axis=1)       # v >> (64 - sh), 0 for sh = 0
+    low[:, 1:] += spill[:, :-1]
+    return low.reshape(w.shape[:-1] + (nw,))
+
+
+def unpack_rows(packed, bits, n):
+    """uint64 [..., n * bits / 64] packed rows -> uint64 [..., n] values below 2^bits (NOT reduced: a value may be >= the modulus, the device checks)"""
+    p = np.ascontiguousarray(packed, dtype=np.uint64)
+    bits, n = int(bits), int(n)
+    if not 2 <= bits <= 60 or (n * bits) % 64 or p.shape[-1] != n * bits // 64:
+        raise ValueError("unpack_rows: rows of %d words are not %d coefficients of %d bits" % (p.shape[-1], n, bits))
+    pos = np.arange(n, dtype=np.uint64) * np.uint64(bits)
+    wd, sh = (pos >> np.uint64(6)).astype(np.intp), pos & np.uint64(63)
+    flat = np.concatenate([p.reshape(-1, p.shape[-1]), np.zeros((p.size // p.shape[-1], 1), dtype=np.uint64)], axis=1)
+    lo = flat[:, wd] >> sh
+    hi = (flat[:, wd + 1] << (np.uint64(63) - sh)) << np.uint64(1)                # word << (64 - sh), 0 for sh = 0
+    return ((lo | hi) & np.uint64((1 << bits) - 1)).reshape(p.shape[:-1] + (n,))
+
+
+def packed_bits(q):
+    """bit widths of the packed rows of the moduli q"""
+    return [int(x).bit_length() for x in q]
+
+
+def pack_ciphertexts(words, q, n):
+    """uint64 [count, polys * k * n] ciphertext words -> packed [count, polys * (n / 64) * sum bits] in [poly][limb] row order"""
+    w = np.ascontiguousarray(words, dtype=np.uint64)
+    k = len(q)
+    w = w.reshape(w.shape[0], -1, k, n)
+    return np.concatenate([pack_rows(w[:, p, j], b) for p in range(w.shape[1]) for j, b in enumerate(packed_bits(q))], axis=1)
+
+
+def unpack_ciphertexts(packed, q, n, polys):
+    """the inverse of pack_ciphertexts (values are not reduced)"""
+    p = np.ascontiguousarray(packed, dtype=np.uint64)
+    out, off = [], 0
+    for _ in range(polys):
+        for b in packed_bits(q):
+            out.append(unpack_rows(p[:, off:off + n * b // 64], b, n))
+            off += n * b // 64
+    if off != p.shape[1]:
+        raise ValueError("unpack_ciphertexts: %d words per ciphertext, expected %d" % (p.shape[1], off))
+    return np.concatenate(out, axis=1)
+
+
+# A packed batch: the compact batch with its c0 polynomials as packed rows.
+#     8 B magic "CNHIPPK1" | u32 version (1) | 32 B public seed | u64 nonce | u64 first item | u64 count | 32 B parms_id of the level
+#     | u32 limbs | limbs x u8 bit widths | IntArray of count * (N / 64) * sum(widths) words: [ciphertext][limb] rows        (all little-endian)
+PACKED_MAGIC = b"CNHIPPK1"
+PACKED_VERSION = 1
+
+
+class PackedDescriptor(CompactDescriptor):
+    """a CompactDescriptor and the bit widths of the rows (one per limb of the level): what turns packed c0 rows back into ciphertexts"""
+
+    def __init__(self, a_seed, a_nonce, a_item0, count, parms_id, bits):
+        super().__init__(a_seed, a_nonce, a_item0, count, parms_id)
+        self.bits = [int(b) for b in bits]
+        if not self.bits or min(self.bits) < 2 or max(self.bits) > 60:
+            raise ValueError("packed rows have 2 .. 60 bits per coefficient")
+
+    def __eq__(self, o):
+        return super().__eq__(o) and self.bits == getattr(o, "bits", None)
+
+
+def save_packed_batch(f, packed, desc):
+    """packed c0 rows [count, (n / 64) * sum(desc.bits)] with their PackedDescriptor"""
+    packed = np.ascontiguousarray(packed, dtype=np.uint64)
+    bits = desc.bits
+    if packed.ndim != 2 or packed.shape[0] != desc.count or packed.shape[1] % sum(bits):
+        raise ValueError("packed words of shape %s do not belong to a descriptor of %d ciphertexts" % (packed.shape, desc.count))
+    f.write(PACKED_MAGIC)
+    f.write(struct.pack("<I", PACKED_VERSION))
+    f.write(desc.a_seed)
+    _w_u64(f, desc.a_nonce)
+    _w_u64(f, desc.a_item0)
+    _w_u64(f, desc.count)
+    f.write(desc.parms_id)
+    f.write(struct.pack("<I", len(bits)))
+    f.write(bytes(bits))
+    _w_array(f, packed)
+
+
+def load_packed_batch(f, parms):
+    """(packed c0 rows [count, words], descriptor, limbs); `parms`: the Parameters of the chain's first level - a batch of any of its levels loads.  The
+    widths are checked against the level's moduli, the word count against them and the item range; the rows are NOT unpacked (the device reduces and
+    reports a residue that is not below its modulus: Context.ct_upload_packed)"""
+    if _rd(f, 8) != PACKED_MAGIC:
+        raise BadStream("Bad stream format. (not a packed batch)")
+    version = struct.unpack("<I", _rd(f, 4))[0]
+    if version != PACKED_VERSION:
+        raise BadStream("packed batch of version %d (this library reads %d)" % (version, PACKED_VERSION))
+    a_seed = _rd(f, 32)
+    a_nonce, a_item0, count = _r_u64(f), _r_u64(f), _r_u64(f)
+    pid = _rd(f, 32)
+    limbs = parms.chain().get(pid)
+    if limbs is None:
+        raise BadStream("the packed batch belongs to other encryption parameters")
+    if (a_item0 + count) >> 40:
+        raise BadStream("Bad stream format. (items)")
+    nl = struct.unpack("<I", _rd(f, 4))[0]
+    if nl != limbs or list(_rd(f, nl)) != packed_bits(parms.q[:limbs]):
+        raise BadStream("Bad stream format. (bit widths of the packed rows)")
+    row = parms.n // 64 * sum(packed_bits(parms.q[:limbs]))
+    words = _r_array(f)
+    if words.size != count * row:
+        raise BadStream("Bad stream format. (%d words for %d packed ciphertexts of %d limbs)" % (words.size, count, limbs))
+    return words.reshape(count, row), PackedDescriptor(a_seed, a_nonce, a_item0, count, pid, packed_bits(parms.q[:limbs])), limbs
 
 
 class _Prefixed:

@@ -450,6 +450,19 @@ int cn_ct_upload_compact(cn_ctx *ctx, cn_handle h, uint32_t first, uint32_t coun
                          uint64_t a_item0);
 /* poly 0 of the size-2 ciphertexts h[first ..) -> host [count][k][N]; synchronises */
 int cn_ct_download_compact(cn_ctx *ctx, cn_handle h, uint32_t first, uint32_t count, uint64_t *host);
+/* Packed rows - the library's own wire form of residues without padding bits (not a SEAL stream).  b_j = bit_length(q_j); the N residues of limb j are one
+ * little-endian bit stream, coefficient i in bits [i b_j, (i + 1) b_j) of the row, bit p of the row = bit p % 64 of word p / 64; a row is N b_j / 64 words, a
+ * packed ciphertext its rows in [poly][limb] order, a batch [ciphertext][poly][limb].  Needs N >= 1024; works on level contexts with that level's limbs.
+ * words of a packed ciphertext of `polys` polynomials: polys * (N / 64) * sum_j b_j (0 when the context has no packed form) */
+size_t cn_packed_words(cn_ctx *ctx, uint32_t polys);
+/* h[first .. first + count) -> host as packed rows, polys = 1: poly 0 only, 0: every polynomial of h (size 2 or 3); staged through scratch, synchronises */
+int cn_ct_download_packed(cn_ctx *ctx, cn_handle h, uint32_t first, uint32_t count, uint32_t polys, uint64_t *host);
+/* packed rows -> h[first ..).  polys = 1: h of size 2, host holds c0 rows, poly 1 is expanded from the seed as in cn_ct_upload_compact; polys = 0: every
+ * polynomial of h, the seed arguments are ignored.  Staged through scratch, synchronises like cn_ct_upload_compact.  A row can carry v >= q_j (q_j < 2^b_j):
+ * the device stores v - q_j, so the array holds canonical words, and the call returns CN_ERR_ARG ("residue not below its modulus"); the destination is
+ * otherwise unspecified then.  cn_get_option "packed_bad_residues" counts such calls. */
+int cn_ct_upload_packed(cn_ctx *ctx, cn_handle h, uint32_t first, uint32_t count, uint32_t polys, const uint64_t *host, const uint8_t *a_seed32, uint64_t a_nonce,
+                        uint64_t a_item0);
 /* Decryptor.Decrypt of size-2 or size-3 ciphertexts into dense plaintexts */
 int cn_decrypt(cn_ctx *ctx, cn_handle ct, uint32_t ci, uint32_t count, cn_handle pt_out, uint32_t pi);
 /* Decryptor.InvariantNoiseBudget as CryptoTracker.TestBudget probes it (HE Wrapper/CryptoTracker.cs:41-52, BaseLayer.cs:37): writes the
