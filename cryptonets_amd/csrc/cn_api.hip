@@ -335,6 +335,7 @@ void ctx_teardown(cn_ctx *ctx) {
     delete &slabs_of(ctx);
     if (ctx->rlk.owned) (void)hipFree(ctx->rlk.d);
     for (auto &kv : ctx->gk) if (kv.second.owned) (void)hipFree(kv.second.d);
+    defer_square_release(ctx);
     (void)hipFree(ctx->sk); (void)hipFree(ctx->pk); (void)hipFree(ctx->ks_part); (void)hipFree(ctx->d_index_map); (void)hipFree(ctx->stage); if (ctx->pin) (void)hipHostFree(ctx->pin);
     (void)hipFree(ctx->scratch); (void)hipFree(ctx->tw); (void)hipFree(ctx->twd); (void)hipFree(ctx->twdh); (void)hipFree(ctx->dc);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
@@ -356,6 +357,7 @@ extern "C" int cn_set_option(cn_ctx *ctx, const char *name, int value) { API_BOD
     if (const OptionSpec *o = find_option(name)) {
         if (!o->flag && (value < o->lo || value > o->hi)) return fail(CN_ERR_ARG, "%s: %d .. %d", name, o->lo, o->hi);
         ctx->opt.*o->member = o->flag ? value != 0 : value;
+        if (o->member == &CnTunables::f64 || o->member == &CnTunables::gemm_mfma || o->member == &CnTunables::gemm_pair) defer_square_drop_plans(ctx);   // (the switches build_gemm_plan reads)
         return 0;
     }
     if (!strcmp(name, "defer")) {                // 0 immediate, 1 queued under the context lock, 2 queued through the lock-free submission ring; the queue was drained by LOCK
@@ -375,7 +377,8 @@ extern "C" int cn_set_option(cn_ctx *ctx, const char *name, int value) { API_BOD
         HIPCHK(hipMemcpy(ctx->dc, &ctx->hc, sizeof(DevConsts), hipMemcpyHostToDevice));
         return 0;
     }
-    if (!strcmp(name, "digit_mfma")) { ctx->digit_mfma = value != 0; return 0; }     // the digit GEMM of plans made AFTER the call: matrix cores where eligible / FP64 (cn_eval.hip)
+    if (!strcmp(name, "defer_square_gemm")) { ctx->defer_square_gemm = value != 0; return 0; }     // (LOCK has settled what the queue held back under the old value)
+    if (!strcmp(name, "digit_mfma")) { ctx->digit_mfma = value != 0; defer_square_drop_plans(ctx); return 0; }     // the digit GEMM of plans made AFTER the call: matrix cores where eligible / FP64 (cn_eval.hip)
     if (!strcmp(name, "record_steps")) {         // 1: record the RotateRows steps and column rotations asked for from now on (cn_rotation_steps); 0: stop and clear
         ctx->rec_steps = value != 0;
         if (!value) { ctx->rec_set.clear(); ctx->rec_cols = false; }
@@ -392,11 +395,14 @@ extern "C" int cn_get_option(cn_ctx *ctx, const char *name, int *value) { API_BO
     else if (!strcmp(name, "ks_xi")) *value = (int)ctx->hc.ks_xi;
     else if (!strcmp(name, "record_steps")) *value = ctx->rec_steps;
     else if (!strcmp(name, "digit_mfma")) *value = ctx->digit_mfma;
+    else if (!strcmp(name, "defer_square_gemm")) *value = ctx->defer_square_gemm;
     // read-only diagnostics: choices the library made and counters (tests)
     else if (!strcmp(name, "pin_laps")) *value = (int)ctx->pin_laps;                      // laps of the pinned upload ring (each one waits for the stream)
     else if (!strcmp(name, "ready_handles")) *value = (int)ctx->ready->size();          // allocated single-ciphertext arrays waiting for a lock-free cn_ct_alloc
     else if (!strcmp(name, "folded_zero_encryptions")) *value = (int)std::min<uint64_t>(ctx->folded_zero, 0x7fffffff);    // zero encryptions folded so far
     else if (!strcmp(name, "square_gemm_fused")) *value = (int)std::min<uint64_t>(ctx->sg_fused, 0x7fffffff);
+    else if (!strcmp(name, "defer_square_gemm_fused")) *value = (int)std::min<uint64_t>(ctx->dsg_fused, 0x7fffffff);       // groups of queued scalar products run on deferred squarings
+    else if (!strcmp(name, "defer_pending_products")) *value = (int)ctx->dq->sq->out.size();                             // squarings whose relinearisation is held back right now
     else if (!strcmp(name, "digit_gemm_mfma")) *value = (int)std::min<uint64_t>(ctx->dg_mfma, 0x7fffffff);                 // digit GEMMs launched in the matrix-core form
     else if (!strcmp(name, "packed_bad_residues")) *value = (int)std::min<uint64_t>(ctx->packed_bad.load(), 0x7fffffff);      // packed uploads that held a residue >= its modulus
     else if (!strcmp(name, "mul_relin_pipelined")) *value = (int)std::min<uint64_t>(ctx->mr_pipelined, 0x7fffffff);      // Multiply + Relinearize batches run in parts over two streams

@@ -13,6 +13,8 @@
 #include <algorithm>
 #include <chrono>
 #include <mutex>
+#include <map>
+#include <unordered_map>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -68,6 +70,7 @@ struct DeferQueue {
     std::vector<std::pair<uint64_t *, size_t>> frees;      // arrays released by the caller while calls were pending: back to the pool after the flush
     struct Fold { int32_t enc; uint64_t w; };               // a zero encryption (index of its DOp) folded into a scalar product with weight w (residue mod t)
     std::vector<Fold> folds;
+    struct DeferSquare *sq = nullptr;                       // squarings whose relinearisation is held back for the next dense layer (below; cn_defer.hip)
 };
 // Small arrays (a per-ciphertext caller allocates every Ciphertext on its own: thousands of 640 KiB arrays per layer) are carved out of
 // slabs - one hipMalloc per SLAB_PIECES arrays, neighbours in the address space - and only ever travel between the handles and the pool;
@@ -97,6 +100,26 @@ struct GemmPlan {
     // dig_mfma: the digit GEMM runs on the matrix cores from the fragments at off_w (no table at off_dw)
     bool dig = false, dig_mfma = false; uint32_t dMT = 0, dKw = 0; size_t off_dw = 0;
 };
+// ---- deferred squarings that feed the next dense layer (cn_set_option "defer_square_gemm", cn_defer.hip).  A layer-boundary flush runs only the Multiply half of the
+// squarings it launches: the size-3 products stay in `arr` ([slot][3][k][N], owned by the context, grown on demand and never while a graph is alive), the callers'
+// output arrays are not written, `slot` remembers output array -> slot.  The next flush either runs the scalar products that read them in cn_square_gemm's second half
+// (GEMM over components 0 and 1, digit GEMM, one KsDigits key switch per OUTPUT) or relinearises every product into its own array first and goes on as ever.
+// SgPlan: the plan of one such dense layer, built once and found again by memcmp - the rows sorted by their weights and the slots renumbered in order of first
+// appearance, so that the order in which the caller's threads issued the calls does not change the key; the tables that hold slots, biases and output addresses
+// are made per flush (idx / oidx: the plan's gather rows and output members on the host).
+struct SgPlan {
+    bool ok = false, bias = false; uint32_t O = 0, K = 0;
+    std::vector<uint64_t> W; std::vector<int32_t> cidx;      // the key: weights [O][K], renumbered slots [O][K] (-1: padded tap)
+    GemmPlan P; std::vector<int32_t> idx, oidx;              // P.dev: weights on the device; idx [G][Kp], oidx [G][M]
+    uint64_t used = 0;
+};
+struct DeferSquare {
+    uint64_t *arr = nullptr; size_t cap = 0;                 // bytes
+    std::vector<uint64_t *> out;                             // slot -> the output array its product is relinearised into
+    std::unordered_map<const uint64_t *, uint32_t> slot;
+    std::vector<std::unique_ptr<SgPlan>> plans; uint64_t tick = 0;
+};
+static const size_t DEFER_SQ_PLANS = 8;
 // ---- rotations of n ciphertexts by n DIFFERENT step counts as one launch chain (cn_rotate_rows_many; the queued RotateRows calls of one level).
 // A single-image network rotates the 13 masked vectors of an Interleave by 13 different amounts, the 5 maps of a Vectorize by 5: one rotation
 // is 2 dependent dispatches per hop, and dependent dispatches are what the latency of such a chain is made of.  The hops of a
@@ -150,6 +173,10 @@ int free_gemm_plan(cn_ctx *ctx, Buffer &b);
 bool pair_gather_lists(uint32_t O, uint32_t &K, std::vector<int32_t> &gidx, const uint64_t *W, std::vector<uint64_t> &W2);
 int build_gemm_plan(cn_ctx *ctx, const int32_t *idx, const uint64_t *W, uint32_t O, uint32_t K, Buffer *BP, cn_handle bias_pt, const int32_t *bias_idx, GemmPlan &P);
 int run_gemm_plan(cn_ctx *ctx, const GemmPlan &P, const char *tables, Buffer *I, Buffer *OB, uint32_t oi, const uint64_t *in3 = nullptr);
+int launch_gemm_plan(cn_ctx *ctx, const GemmPlan &P, const char *tables, const void *idx, const uint64_t *in, uint32_t in_unit, uint32_t polys, const uint64_t *bias, const void *bidx,
+                     uint32_t bias_unit, uint64_t *out, uint32_t obase);
+bool square_gemm_ctx_ok(cn_ctx *ctx);
+bool square_gemm_fused_ok(cn_ctx *ctx, const GemmPlan &P);
 bool run_intt_tensor(cn_ctx *c, const uint64_t *A, const uint64_t *B, uint64_t *D, uint32_t cnt, uint32_t base_off, uint32_t Lm, bool lazy);
 bool square_fused_ok(cn_ctx *c, uint32_t base_off, uint32_t Lm, bool &light);
 void run_square_fused(cn_ctx *c, const uint64_t *A, size_t astride, const uint64_t *const *atab, uint64_t *D, uint32_t cnt, uint32_t base_off, uint32_t Lm, bool light);
@@ -242,7 +269,7 @@ int32_t defer_level(DeferQueue *q, const uint64_t *const *ins, uint32_t nin, con
 int defer_push(cn_ctx *ctx, DOp op, const uint64_t *const *ins, uint32_t nin);
 int flush_gemm_group(cn_ctx *ctx, DeferQueue *q, const std::vector<const DOp *> &ops, uint32_t K);
 int flush_elementwise_group(cn_ctx *ctx, const std::vector<const DOp *> &ops, int type);
-int flush_mulrelin_group(cn_ctx *ctx, const std::vector<const DOp *> &all);
+int flush_mulrelin_group(cn_ctx *ctx, const std::vector<const DOp *> &all, const std::map<const uint64_t *, size_t> *park = nullptr, int32_t level = 0);
 int ensure_stage(cn_ctx *ctx, size_t bytes);
 int copy_by_table(cn_ctx *ctx, const std::vector<Tab2> &tab, Tab2 *dtab, uint32_t words_per_item);
 int flush_staged_group(cn_ctx *ctx, const std::vector<const DOp *> &all, int type);
@@ -251,7 +278,9 @@ int flush_encrypt_group(cn_ctx *ctx, const std::vector<const DOp *> &ops);
 bool zero_fold_ok(cn_ctx *ctx);
 int flush_zero_folds(cn_ctx *ctx, DeferQueue *q, const std::vector<const DOp *> &gemms);
 int defer_encrypt(cn_ctx *ctx, const uint64_t *ptd, uint32_t pt_stride_words, Buffer *O, uint32_t oi, uint32_t count, uint64_t seed);
-int cn_defer_flush(cn_ctx *ctx);
+int cn_defer_flush(cn_ctx *ctx, bool boundary = false);      // boundary: the layer-boundary trigger of defer_push; every other flush is a demand flush
+void defer_square_drop_plans(cn_ctx *ctx);                   // the cached plans of deferred square + dense layers (changes of the switches build_gemm_plan reads)
+void defer_square_release(cn_ctx *ctx);                      // ... and the product array (ctx_teardown)
 bool deferring(cn_ctx *ctx);
 int scalar_dot_body(cn_ctx *ctx, const cn_handle *in, const uint32_t *in_idx, const uint64_t *w, uint32_t K, cn_handle out, uint32_t oi);
 int defer_addsub(cn_ctx *ctx, cn_handle a, uint32_t ai, cn_handle b, uint32_t bi, cn_handle out, uint32_t oi, uint32_t count, int op);

@@ -25,9 +25,10 @@
 // into dozens of small launches: 0.47 of the batched rate at 4-32 threads against 0.84 at one.  Flushing whenever the stream had run dry
 // instead cut the first layers into 256-call pieces and lost the bias folding: 0.85 against 0.93.)
 static const size_t DEFER_FLUSH_MIN = 64, DEFER_MAX_OPS = 32768;
-DeferQueue *cn_defer_new() { return new DeferQueue(); }
-void cn_defer_delete(DeferQueue *q) { delete q; }
-bool cn_defer_pending(cn_ctx *ctx) { return ctx->dq && !ctx->dq->ops.empty(); }
+DeferQueue *cn_defer_new() { DeferQueue *q = new DeferQueue(); q->sq = new DeferSquare(); return q; }
+void cn_defer_delete(DeferQueue *q) { if (q) delete q->sq; delete q; }
+// (products whose relinearisation is held back count as pending work: an array released meanwhile waits in DeferQueue::frees for the flush that settles them)
+bool cn_defer_pending(cn_ctx *ctx) { return ctx->dq && (!ctx->dq->ops.empty() || !ctx->dq->sq->out.empty()); }
 
 int32_t defer_level(DeferQueue *q, const uint64_t *const *ins, uint32_t nin, const uint64_t *out) {
     int32_t lv = 0;
@@ -49,14 +50,15 @@ int defer_push(cn_ctx *ctx, DOp op, const uint64_t *const *ins, uint32_t nin) {
     int32_t hd = 0;
     for (uint32_t i = 0; i < nin; i++) if (ins[i]) { const DeferQueue::Haz *h = q->haz.find(ins[i]); if (h) hd = std::max(hd, h->hd); }
     hd += heavy ? 1 : 0;
-    if (q->ops.size() >= DEFER_MAX_OPS || (heavy && hd >= 2 && q->ops.size() >= DEFER_FLUSH_MIN)) {
+    const bool full = q->ops.size() >= DEFER_MAX_OPS;
+    if (full || (heavy && hd >= 2 && q->ops.size() >= DEFER_FLUSH_MIN)) {
         // a layer boundary (or a full queue): launch what is queued, the callers go on queueing the next layer behind it
         std::vector<uint64_t> ta, tw;
         if (op.type == DOP_GEMM1) {                     // the terms of this call sit at the end of the term arrays: keep them over the flush
             ta.assign(q->addr.begin() + op.terms, q->addr.end()); tw.assign(q->wt.begin() + op.terms, q->wt.end());
             q->addr.resize(op.terms); q->wt.resize(op.terms);
         }
-        CHECK(cn_defer_flush(ctx));
+        CHECK(cn_defer_flush(ctx, !full));
         if (op.type == DOP_GEMM1) { op.terms = 0; q->addr = ta; q->wt = tw; }
         lv = 0; hd = heavy ? 1 : 0;
     }
@@ -206,13 +208,230 @@ int flush_elementwise_group(cn_ctx *ctx, const std::vector<const DOp *> &ops, in
     HIPCHK(hipGetLastError()); launch_count(ctx);
     return 0;
 }
+// ---- deferred squarings that feed the next dense layer (DeferSquare, cn_api_shared.h)
+static bool defer_trace() { static const bool on = getenv("CN_DEFER_TRACE") && atoi(getenv("CN_DEFER_TRACE")); return on; }
+void defer_square_drop_plans(cn_ctx *ctx) {
+    if (!ctx->dq || ctx->dq->sq->plans.empty()) return;
+    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+    for (auto &p : ctx->dq->sq->plans) if (p->P.dev) (void)hipFree(p->P.dev);
+    ctx->dq->sq->plans.clear();
+}
+void defer_square_release(cn_ctx *ctx) {
+    if (!ctx->dq) return;
+    defer_square_drop_plans(ctx);
+    DeferSquare &sq = *ctx->dq->sq;
+    if (sq.arr) (void)hipFree(sq.arr);
+    sq.arr = nullptr; sq.cap = 0; sq.out.clear(); sq.slot.clear();
+}
+// The squarings of one level at a layer-boundary flush keep their relinearisation back if every one of them is the last writer of its output array, nothing queued
+// reads that array, the caller has not released it, and the products fit the context's product array (a quarter of the scratch limit at most; the array is not grown
+// while a graph is alive).  Only the Multiply half runs: products into slots 0 .. n - 1, output array -> slot noted.  False: the caller relinearises them at once.
+// has the caller released the buffer that holds p?  (DeferQueue::frees lists whole buffers: an output may be an element of a handle of several ciphertexts)
+static bool in_freed(const std::map<const uint64_t *, size_t> &freed, const uint64_t *p) {
+    auto it = freed.upper_bound(p);
+    if (it == freed.begin()) return false;
+    --it;
+    return (const char *)p < (const char *)it->first + it->second;
+}
+static bool park_squarings(cn_ctx *ctx, DeferQueue *q, const std::vector<const DOp *> &ops, const std::map<const uint64_t *, size_t> &freed, int32_t level, int *rc) {
+    DeferSquare &sq = *q->sq;
+    const size_t kn = (size_t)ctx->hc.k * ctx->hc.n, need = ops.size() * 3 * kn * 8;
+    if (!sq.out.empty() || need > ctx->smax / 4) return false;
+    std::unordered_map<const uint64_t *, int> seen;
+    for (const DOp *op : ops) {
+        const DeferQueue::Haz *h = q->haz.find(op->out);
+        if (!h || h->wop != (int32_t)(op - q->ops.data()) || h->readers || in_freed(freed, op->out) || seen[op->out]++) return false;
+    }
+    if (need > sq.cap) {
+        if (ctx->capturing || ctx->graphs_alive) return false;
+        if (hipStreamSynchronize(ctx->stream) != hipSuccess) { *rc = fail(CN_ERR_HIP, "hipStreamSynchronize failed"); return true; }
+        if (sq.arr) (void)hipFree(sq.arr);
+        sq.arr = nullptr; sq.cap = 0;
+        const size_t want = need + (need >> 3);
+        if (hipMalloc((void **)&sq.arr, want) != hipSuccess) { (void)hipGetLastError(); sq.arr = nullptr; return false; }
+        sq.cap = want;
+    }
+    const uint32_t n = (uint32_t)ops.size();
+    const size_t per = mul_scratch_per_ct(ctx, true) + 8 + 64;
+    const uint32_t ch = chunk_for(ctx, per, n);
+    for (uint32_t s0 = 0; s0 < n && !*rc; s0 += ch) {
+        const uint32_t c = std::min<uint32_t>(ch, n - s0);
+        if ((*rc = ensure_scratch(ctx, per * c + al((size_t)c * 8) + 8192))) break;
+        std::vector<const uint64_t *> ha(c);
+        for (uint32_t i = 0; i < c; i++) ha[i] = ops[s0 + i]->a;
+        const uint64_t **da;
+        if ((*rc = upload_tmp(ctx, ha.data(), c, &da))) break;
+        *rc = do_multiply(ctx, nullptr, 1, nullptr, 1, sq.arr + (size_t)s0 * 3 * kn, c, da, da);
+    }
+    if (*rc) return true;
+    sq.out.resize(n);
+    for (uint32_t i = 0; i < n; i++) { sq.out[i] = ops[i]->out; sq.slot[ops[i]->out] = i; }
+    if (defer_trace()) fprintf(stderr, "defer %p level %d: parks %u squarings (Multiply only, %zu MB of products)\n", (void *)ctx, level, n, need >> 20);
+    return true;
+}
+// every product with need[slot] set is relinearised into its own output array (do_keyswitch from its slot, as flush_mulrelin_group would have), runs of slots per launch
+static int pending_materialise(cn_ctx *ctx, DeferSquare &sq, const std::vector<uint8_t> &need) {
+    const uint32_t n = (uint32_t)sq.out.size();
+    const size_t kn = (size_t)ctx->hc.k * ctx->hc.n;
+    CHECK(ensure_scratch(ctx, al((size_t)n * 8) + 4096));
+    uint64_t **dout; CHECK(upload_tmp(ctx, sq.out.data(), n, &dout));
+    uint32_t done = 0;
+    for (uint32_t s = 0; s < n;) {
+        if (!need[s]) { s++; continue; }
+        uint32_t e = s; while (e < n && need[e]) e++;
+        uint64_t *t = sq.arr + (size_t)s * 3 * kn;
+        CHECK(do_keyswitch(ctx, t + 2 * kn, 3 * kn, t, t + kn, 3 * kn, ctx->rlk, nullptr, e - s, 0, nullptr, 0, dout + s));
+        done += e - s; s = e;
+    }
+    if (defer_trace()) fprintf(stderr, "defer %p: materialises %u of %u pending products (one key switch each)\n", (void *)ctx, done, n);
+    return 0;
+}
+struct SgGroup { int32_t level; SgPlan *plan; std::vector<const DOp *> rows; std::vector<int32_t> slot_of; };       // rows: the scalar products in the plan's output order; slot_of: renumbered slot -> slot
+// the plan of a dense layer on deferred squarings: found by (O, K, weights, renumbered slot pattern) or built (build_gemm_plan: validation, grouping, weight tiles,
+// GemmPlan::dig) and kept, its weights on the device.  `keep`: entries used since this tick belong to the flush at hand and are not evicted
+static SgPlan *sg_plan(cn_ctx *ctx, DeferSquare &sq, uint32_t O, uint32_t K, std::vector<uint64_t> &W, std::vector<int32_t> &cidx, uint64_t keep) {
+    for (auto &p : sq.plans)
+        if (p->O == O && p->K == K && !memcmp(p->W.data(), W.data(), W.size() * 8) && !memcmp(p->cidx.data(), cidx.data(), cidx.size() * 4)) { p->used = ++sq.tick; return p.get(); }
+    if (sq.plans.size() >= DEFER_SQ_PLANS) {
+        size_t v = sq.plans.size();
+        for (size_t i = 0; i < sq.plans.size(); i++) if (sq.plans[i]->used <= keep && (v == sq.plans.size() || sq.plans[i]->used < sq.plans[v]->used)) v = i;
+        if (v < sq.plans.size()) {
+            if (sq.plans[v]->P.dev) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(sq.plans[v]->P.dev); }
+            sq.plans.erase(sq.plans.begin() + v);
+        }
+    }
+    std::unique_ptr<SgPlan> p(new SgPlan());
+    p->O = O; p->K = K; p->W.swap(W); p->cidx.swap(cidx); p->used = ++sq.tick;
+    GemmPlan &P = p->P;
+    if (build_gemm_plan(ctx, p->cidx.data(), p->W.data(), O, K, nullptr, 0, nullptr, P)) return nullptr;     // (unreachable for queued calls: their weights and rows were checked when they were queued)
+    p->ok = P.dig;                                                // (a layer outside the digit bound stays cached as such: it is not planned again every batch)
+    if (p->ok) {
+        p->idx.assign((const int32_t *)P.host.data(), (const int32_t *)P.host.data() + (size_t)P.G * P.Kp);
+        p->oidx.assign((const int32_t *)(P.host.data() + P.off_oidx), (const int32_t *)(P.host.data() + P.off_oidx) + (size_t)P.G * P.M);
+        if (hipMalloc((void **)&P.dev, P.host.size()) != hipSuccess || hipMemcpy(P.dev, P.host.data(), P.host.size(), hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipGetLastError();
+            if (P.dev) (void)hipFree(P.dev);
+            P.dev = nullptr; p->ok = false;
+        }
+    }
+    P.host.clear(); P.host.shrink_to_fit();
+    sq.plans.push_back(std::move(p));
+    return sq.plans.back().get();
+}
+static size_t sg_scratch(cn_ctx *ctx, const GemmPlan &P) {
+    const size_t kn = (size_t)ctx->hc.k * ctx->hc.n;
+    return al((size_t)P.O * 2 * kn * 8) + al((size_t)P.O * ctx->hc.rl_tot * ctx->hc.n * 8) + al((size_t)P.G * P.Kp * 4) + al((size_t)P.G * P.M * 4) + al((size_t)P.O * 8) + 8192;
+}
+// The decision of a flush that finds products pending (once, all or nothing): may every queued reader of a pending array run in cn_square_gemm's second half?
+//   (a) the caller has released every pending output array, (b) only scalar products read pending arrays - and those form groups (one level, one term count)
+//   whose plan passes square_gemm_fused_ok, with a bias on every output or on none, (c) every gathered term of such a scalar product is a pending array (and no zero
+//   encryption was folded onto it), (d) no queued call writes a pending array.
+// need[slot]: the product has to be relinearised if the answer is no - somebody reads its array or the caller still holds it.
+static bool sg_prepare(cn_ctx *ctx, DeferQueue *q, const std::vector<uint8_t> &dead, const std::map<const uint64_t *, size_t> &freed, std::vector<SgGroup> &groups,
+                       std::vector<int32_t> &sg_of, std::vector<uint8_t> &need) {
+    DeferSquare &sq = *q->sq;
+    const std::vector<DOp> &ops = q->ops;
+    const uint32_t n = (uint32_t)sq.out.size();
+    need.assign(n, 0);
+    bool ok = ctx->defer_square_gemm && square_gemm_ctx_ok(ctx) && ctx->rlk.d;
+    auto slot_of = [&](const uint64_t *p) -> int32_t { if (!p) return -1; auto it = sq.slot.find(p); return it == sq.slot.end() ? -1 : (int32_t)it->second; };
+    std::map<std::pair<int32_t, uint32_t>, std::vector<size_t>> cand;            // (level, term count) -> scalar products that read pending arrays
+    for (size_t x = 0; x < ops.size(); x++) {
+        if (dead[x]) continue;
+        const DOp &X = ops[x];
+        if (slot_of(X.out) >= 0) ok = false;                                         // (d)
+        if (X.type == DOP_GEMM1) {
+            uint32_t np = 0, other = 0;
+            for (uint32_t kk = 0; kk < X.K; kk++) {
+                const uint64_t *a = (const uint64_t *)q->addr[X.terms + kk];
+                if (!a) continue;
+                const int32_t s = slot_of(a);
+                if (s >= 0) { need[s] = 1; np++; } else other++;
+            }
+            if (!np) continue;
+            if (other || X.fold_count) ok = false;                                   // (c)
+            cand[{X.level, X.K}].push_back(x);
+            continue;
+        }
+        if (X.type == DOP_ENCRYPT) continue;                                         // (a = plaintext polynomial)
+        const bool b_plain = X.type == DOP_ADDPLAIN || X.type == DOP_SUBPLAIN || X.type == DOP_MULPLAIN;
+        for (const uint64_t *p : {X.a, b_plain ? nullptr : X.b}) { const int32_t s = slot_of(p); if (s >= 0) { need[s] = 1; ok = false; } }      // (b)
+    }
+    for (uint32_t s = 0; s < n; s++) if (!in_freed(freed, sq.out[s])) { need[s] = 1; ok = false; }      // (a)
+    if (!ok) return false;
+    const uint64_t keep = sq.tick;
+    for (auto &kv : cand) {
+        const uint32_t K = kv.first.second, O = (uint32_t)kv.second.size();
+        SgGroup g; g.level = kv.first.first;
+        for (size_t x : kv.second) g.rows.push_back(&ops[x]);
+        // the key must not depend on the order in which the caller's threads issued the calls: rows by their weights, slots by first appearance
+        std::stable_sort(g.rows.begin(), g.rows.end(), [&](const DOp *x, const DOp *y) {
+            return std::lexicographical_compare(&q->wt[x->terms], &q->wt[x->terms] + K, &q->wt[y->terms], &q->wt[y->terms] + K); });
+        std::vector<uint64_t> W((size_t)O * K); std::vector<int32_t> cidx((size_t)O * K, -1), canon(n, -1);
+        for (uint32_t o = 0; o < O; o++) {
+            memcpy(&W[(size_t)o * K], &q->wt[g.rows[o]->terms], (size_t)K * 8);
+            for (uint32_t kk = 0; kk < K; kk++) {
+                const int32_t s = slot_of((const uint64_t *)q->addr[g.rows[o]->terms + kk]);
+                if (s < 0) continue;
+                if (canon[s] < 0) { canon[s] = (int32_t)g.slot_of.size(); g.slot_of.push_back(s); }
+                cidx[(size_t)o * K + kk] = canon[s];
+            }
+        }
+        g.plan = sg_plan(ctx, sq, O, K, W, cidx, keep);
+        if (!g.plan || !g.plan->ok || !square_gemm_fused_ok(ctx, g.plan->P) || sg_scratch(ctx, g.plan->P) > ctx->smax) return false;
+        if (sg_scratch(ctx, g.plan->P) > ctx->scap && ctx->graphs_alive) return false;       // (the scratch arena does not grow while a graph is alive)
+        uint64_t bbase = ~0ull;
+        for (const DOp *r : g.rows) { if ((r->bias != nullptr) != (g.rows[0]->bias != nullptr)) return false; if (r->bias) bbase = std::min(bbase, (uint64_t)r->bias); }
+        for (const DOp *r : g.rows) if (r->bias && ((((uint64_t)r->bias - bbase) & 255) || (((uint64_t)r->bias - bbase) >> 8) >= 0x7fffffffull)) return false;
+        for (size_t x : kv.second) sg_of[x] = (int32_t)groups.size();
+        groups.push_back(std::move(g));
+    }
+    return true;
+}
+// one group in cn_square_gemm's second half: the GEMM over components 0 and 1 of the products (+ the folded bias) into a contiguous temporary, the digit GEMM into S,
+// one KsDigits key switch per output that adds the temporary and writes the callers' arrays through its output table (no scatter copy)
+static int sg_run(cn_ctx *ctx, DeferQueue *q, const SgGroup &g) {
+    const SgPlan &sp = *g.plan; const GemmPlan &P = sp.P;
+    const uint32_t n = ctx->hc.n, k = ctx->hc.k, tot = ctx->hc.rl_tot;
+    const size_t kn = (size_t)k * n;
+    std::vector<int32_t> pidx(sp.idx.size()), bidx(sp.oidx.size(), 0);
+    std::vector<uint64_t *> outs(P.O);
+    for (size_t x = 0; x < pidx.size(); x++) pidx[x] = sp.idx[x] >= 0 ? g.slot_of[sp.idx[x]] : -1;
+    const bool bias = g.rows[0]->bias != nullptr;
+    uint64_t bbase = ~0ull;
+    if (bias) {
+        for (const DOp *r : g.rows) bbase = std::min(bbase, (uint64_t)r->bias);
+        for (size_t x = 0; x < bidx.size(); x++) if (sp.oidx[x] >= 0) bidx[x] = (int32_t)(((uint64_t)g.rows[sp.oidx[x]]->bias - bbase) >> 8);
+    }
+    for (uint32_t o = 0; o < P.O; o++) outs[o] = g.rows[o]->out;
+    CHECK(ensure_scratch(ctx, sg_scratch(ctx, P)));
+    uint64_t *T = salloc<uint64_t>(ctx, (size_t)P.O * 2 * kn);
+    double *S = salloc<double>(ctx, (size_t)P.O * tot * n);
+    if (!T || !S) return fail(CN_ERR_HIP, "internal: scratch exhausted in the deferred square + dense form");
+    int32_t *dpidx, *dbidx; uint64_t **douts;
+    CHECK(upload_tmp(ctx, pidx.data(), pidx.size(), &dpidx)); CHECK(upload_tmp(ctx, bidx.data(), bidx.size(), &dbidx)); CHECK(upload_tmp(ctx, outs.data(), outs.size(), &douts));
+    const uint64_t *arr = q->sq->arr;
+    // two components of every product, three apart; bias polynomials as 256-byte offsets from the lowest one (as flush_gemm_group)
+    CHECK(launch_gemm_plan(ctx, P, P.dev, dpidx, arr, (uint32_t)(3 * kn), 2u, bias ? (const uint64_t *)bbase : nullptr, dbidx, 32, T, 0));
+    DigitGemmLaunch dg{arr + 2 * kn, 3 * kn, dpidx, P.dev + P.off_dw, P.dev + P.off_oidx, S, P.G, P.M, P.K, P.Kp, P.dKw, P.dMT};
+    if (P.dig_mfma) { dg.W = P.dev + P.off_w; dg.mfma = true; dg.P = P.P; dg.mtiles = P.mtiles; dg.ksteps = P.ksteps; }
+    CHECK(cn_l_digit_gemm(ctx, dg));
+    CHECK(do_keyswitch(ctx, nullptr, 0, T, T + kn, 2 * kn, ctx->rlk, nullptr, P.O, 0, nullptr, 0, douts, 0, nullptr, 0, nullptr, S));
+    ctx->dsg_fused++;
+    if (defer_trace()) fprintf(stderr, "defer %p level %d: fuses %u scalar products over %zu pending products (GEMM, digit GEMM%s, %u key switches)\n", (void *)ctx, g.level, P.O,
+                               g.slot_of.size(), P.dig_mfma ? " on the matrix cores" : "", P.O);
+    return 0;
+}
+
 // all queued Multiply + Relinearize calls of one level: the batched BEHZ pipeline + ONE key switch, operands and results through tables
-int flush_mulrelin_group(cn_ctx *ctx, const std::vector<const DOp *> &all) {
+// park (a layer-boundary flush, cn_set_option "defer_square_gemm"): the squarings may keep their relinearisation back (park_squarings)
+int flush_mulrelin_group(cn_ctx *ctx, const std::vector<const DOp *> &all, const std::map<const uint64_t *, size_t> *park, int32_t level) {
     const size_t kn = (size_t)ctx->hc.k * ctx->hc.n;
     for (int sq = 1; sq >= 0; sq--) {                    // squarings (SquareActivation) take the fused kernel; general products the separate launches
         std::vector<const DOp *> ops;
         for (const DOp *op : all) if ((op->a == op->b) == (sq == 1)) ops.push_back(op);
         if (ops.empty()) continue;
+        if (sq && park) { int rc = 0; if (park_squarings(ctx, ctx->dq, ops, *park, level, &rc)) { CHECK(rc); continue; } }
         const size_t per = mul_scratch_per_ct(ctx, sq == 1) + al(3 * kn * 8) + 3 * 8 + 64;
         const uint32_t ch = chunk_for(ctx, per, (uint32_t)ops.size());
         for (uint32_t s0 = 0; s0 < ops.size(); s0 += ch) {
@@ -447,10 +666,11 @@ int defer_encrypt(cn_ctx *ctx, const uint64_t *ptd, uint32_t pt_stride_words, Bu
     return 0;
 }
 
-int cn_defer_flush(cn_ctx *ctx) {
+int cn_defer_flush(cn_ctx *ctx, bool boundary) {
     DeferQueue *q = ctx->dq;
     if (!q) return 0;
     int rc = 0;
+    DeferSquare &sqs = *q->sq;
     // CN_DEFER_TRACE=2: host time of every flush (the flush runs on the thread of the call that triggered it, under the context lock: every other caller of the
     // context waits for it, and so does the device if it has run dry)
     static const bool timing = getenv("CN_DEFER_TRACE") && atoi(getenv("CN_DEFER_TRACE")) >= 2;
@@ -458,7 +678,7 @@ int cn_defer_flush(cn_ctx *ctx) {
         if (on && nops) fprintf(stderr, "defer %p flush of %zu calls: %.0f us of host time\n", (void *)c, nops,
                                 1e6 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()); } }
         ft{timing, q->ops.size(), ctx, std::chrono::steady_clock::now()};
-    if (!q->ops.empty()) {
+    if (!q->ops.empty() || !sqs.out.empty()) {
         std::vector<DOp> &ops = q->ops;
         // ---- an AddPlain that only adds the bias to a DenseMatrixBySparseVectorMultiply result the caller has already released
         // (PoolLayer.cs:184-186: `using (conv = ConvolveOnce(..)) res[k] = conv.Add(bias)`) is folded into the GEMM's epilogue - the GEMM
@@ -577,6 +797,19 @@ int cn_defer_flush(cn_ctx *ctx) {
                 }
             }
         }
+        // ---- products whose relinearisation an earlier layer-boundary flush held back: the scalar products that read them run in cn_square_gemm's second half (at their
+        // level, below), or every product is relinearised into its own array first and the flush proceeds as ever
+        std::vector<int32_t> sg_of(ops.size(), -1);
+        std::vector<SgGroup> sgs;
+        std::map<const uint64_t *, size_t> freed_rng;            // released buffers as address ranges
+        for (auto &f : q->frees) freed_rng[f.first] = f.second;
+        int32_t sg_deepest = -1;
+        if (!sqs.out.empty()) {
+            std::vector<uint8_t> need;
+            if (sg_prepare(ctx, q, dead, freed_rng, sgs, sg_of, need)) { for (const SgGroup &g : sgs) sg_deepest = std::max(sg_deepest, g.level); }
+            else { sgs.clear(); std::fill(sg_of.begin(), sg_of.end(), -1); rc = pending_materialise(ctx, sqs, need); }
+            sqs.out.clear(); sqs.slot.clear();              // (the groups carry the slots they read; released arrays without a reader just give their slots back)
+        }
         // ---- launches: level by level, one batched launch per kind (and per term count for the GEMMs)
         const int32_t levels = q->maxlevel + 1;
         static const bool trace = getenv("CN_DEFER_TRACE") && atoi(getenv("CN_DEFER_TRACE"));       // one line per (flush, level): calls per kind, launches
@@ -594,8 +827,9 @@ int cn_defer_flush(cn_ctx *ctx) {
                 fprintf(stderr, "%s -> %llu launches\n", line, (unsigned long long)(c->st.kernel_launches - l0)); } } tr{ctx, lv, l0, by_type, trace};
             if (!by_type[DOP_GEMM1].empty()) {
                 std::map<uint32_t, std::vector<const DOp *>> byK;
-                for (const DOp *op : by_type[DOP_GEMM1]) byK[op->K].push_back(op);
+                for (const DOp *op : by_type[DOP_GEMM1]) if (sg_of[op - ops.data()] < 0) byK[op->K].push_back(op);
                 for (auto &kv : byK) if (!rc) rc = flush_gemm_group(ctx, q, kv.second, kv.first);
+                for (const SgGroup &g : sgs) if (!rc && g.level == lv) rc = sg_run(ctx, q, g);
                 std::vector<const DOp *> folded;
                 for (const DOp *op : by_type[DOP_GEMM1]) if (op->fold_count) folded.push_back(op);
                 if (!rc && !folded.empty()) rc = flush_zero_folds(ctx, q, folded);
@@ -603,9 +837,12 @@ int cn_defer_flush(cn_ctx *ctx) {
             for (int t : {DOP_ADD, DOP_SUB, DOP_ADDPLAIN, DOP_SUBPLAIN}) if (!rc && !by_type[t].empty()) rc = flush_elementwise_group(ctx, by_type[t], t);
             if (!rc && !by_type[DOP_ENCRYPT].empty()) rc = flush_encrypt_group(ctx, by_type[DOP_ENCRYPT]);
             for (int t = DOP_COPY; t <= DOP_SUMSLOTS; t++) if (!rc && !by_type[t].empty()) rc = flush_staged_group(ctx, by_type[t], t);
-            if (!rc && !by_type[DOP_MULRELIN].empty()) rc = flush_mulrelin_group(ctx, by_type[DOP_MULRELIN]);
+            // (new products take the slots from 0: only behind the last group that still reads the old ones)
+            const bool park = boundary && ctx->defer_square_gemm && lv > sg_deepest && square_gemm_ctx_ok(ctx);
+            if (!rc && !by_type[DOP_MULRELIN].empty()) rc = flush_mulrelin_group(ctx, by_type[DOP_MULRELIN], park ? &freed_rng : nullptr, lv);
         }
     }
+    if (rc) { sqs.out.clear(); sqs.slot.clear(); }          // an error drops the pending state with the queue
     q->ops.clear(); q->addr.clear(); q->wt.clear(); q->haz.clear(); q->maxlevel = -1; q->folds.clear();
     for (auto &f : q->frees) { int r2 = dev_release(ctx, f.first, f.second); if (!rc) rc = r2; }
     q->frees.clear();

@@ -359,6 +359,15 @@ int build_gemm_plan(cn_ctx *ctx, const int32_t *idx, const uint64_t *W, uint32_t
     memcpy(P.host.data() + P.off_w, wbytes.data(), wbytes.size());
     return 0;
 }
+// the launch of a plan from raw pointers: weights and output members at `tables`, gather rows at idx, inputs in_unit words apart (0: one ciphertext of `polys` polynomials; the
+// size-3 products of cn_square_gemm: 3 k N with polys = 2), bias polynomials bias_unit words apart (0: one plaintext; the deferred queue: 32 = 256-byte offsets), outputs from obase
+int launch_gemm_plan(cn_ctx *ctx, const GemmPlan &P, const char *tables, const void *idx, const uint64_t *in, uint32_t in_unit, uint32_t polys, const uint64_t *bias, const void *bidx,
+                     uint32_t bias_unit, uint64_t *out, uint32_t obase) {
+    GemmLaunch gl{P.small, P.two, false, P.MT, in, idx, tables + P.off_w, tables + P.off_oidx, bias, bidx, out,
+                  P.G, P.M, P.K, P.lazy, P.Kp, obase, P.P, P.mtiles, P.ksteps, polys, (uint32_t)ctx->opt.gemm_order, P.one};
+    gl.in_unit = in_unit; gl.bias_unit = bias_unit;
+    return P.mfma ? cn_l_gemm_mfma(ctx, gl) : cn_l_gemm(ctx, gl);
+}
 // tables: device image of P.host (scratch or the plan's own allocation)
 // in3 (cn_square_gemm): the inputs are the first TWO components of the size-3 products at in3 (P.max_in of them, checked by the caller) instead of the ciphertexts of I
 int run_gemm_plan(cn_ctx *ctx, const GemmPlan &P, const char *tables, Buffer *I, Buffer *OB, uint32_t oi, const uint64_t *in3) {
@@ -376,10 +385,7 @@ int run_gemm_plan(cn_ctx *ctx, const GemmPlan &P, const char *tables, Buffer *I,
         if (!BP || BP->count < P.bias_count) return fail(CN_ERR_ARG, "invalid bias plaintext handle");
         bias = BP->d;
     }
-    GemmLaunch gl{P.small, P.two, false, P.MT, in3 ? in3 : I->d, tables, tables + P.off_w, tables + P.off_oidx, bias, tables + P.off_bidx, OB->d,
-                  P.G, P.M, P.K, P.lazy, P.Kp, oi, P.P, P.mtiles, P.ksteps, in3 ? 2u : I->size, (uint32_t)ctx->opt.gemm_order, P.one};
-    if (in3) gl.in_unit = 3 * ctx->hc.k * ctx->hc.n;              // two components of every product, three apart
-    CHECK(P.mfma ? cn_l_gemm_mfma(ctx, gl) : cn_l_gemm(ctx, gl));
+    CHECK(launch_gemm_plan(ctx, P, tables, tables, in3 ? in3 : I->d, in3 ? (uint32_t)(3 * ctx->hc.k * ctx->hc.n) : 0u, in3 ? 2u : I->size, bias, tables + P.off_bidx, 0, OB->d, oi));
     ctx->st.PlainMultiplication += P.nnz; ctx->st.Addition += P.nnz - P.O;
     if (P.has_bias) ctx->st.PlainAddition += P.O;
     return 0;
@@ -702,11 +708,13 @@ int mul_relin_body(cn_ctx *ctx, cn_handle a, uint32_t ai, uint32_t astride, cn_h
 // 845 + 100 for CryptoNets, the same ciphertext words.  (Not forward_relinearize_late's "relinearize the sum": there the digits are those of the sum.)
 // Runs when the plan allows it (GemmPlan::dig: small weights, |S| below every q_j / 2 and 2^52), every modulus and the key are on an FP64 policy, the ring has the
 // register-radix kernels up to N = 8192 and the decomposition is the plain one; anything else takes the two separate steps inside the same call.
-static bool square_gemm_fused_ok(cn_ctx *ctx, const GemmPlan &P) {
-    if (!P.dig || !ctx->opt.f64 || ctx->opt.legacy_ntt || ctx->hc.logn < 10 || ctx->hc.logn > 13 || ctx->hc.ks_xi || !ctx->rlk.f64) return false;
+// (square_gemm_ctx_ok: everything but the plan - the deferred queue asks it before it holds the relinearisation of queued squarings back, cn_defer.hip)
+bool square_gemm_ctx_ok(cn_ctx *ctx) {
+    if (!ctx->opt.f64 || ctx->opt.legacy_ntt || ctx->hc.logn < 10 || ctx->hc.logn > 13 || ctx->hc.ks_xi || !ctx->rlk.f64) return false;
     for (uint32_t m = 0; m < ctx->hc.k; m++) if (!ctx->hc.f64ok[m]) return false;
     return true;
 }
+bool square_gemm_fused_ok(cn_ctx *ctx, const GemmPlan &P) { return P.dig && square_gemm_ctx_ok(ctx); }
 extern "C" int cn_square_gemm(cn_ctx *ctx, cn_handle plan, cn_handle in, uint32_t ii, cn_handle out, uint32_t oi) { TWO_LIMBS("cn_square_gemm"); API_BODY
     LOCK; GETCT(I, in, 2); GETCT(OB, out, 2);
     Buffer *PB = getbuf(ctx, plan, 2);

@@ -210,10 +210,14 @@ struct cn_ctx {
     uint64_t folded_zero = 0;  // zero encryptions folded so far
     uint64_t mr_pipelined = 0; // cn_mul_relin chunks and flushed Multiply + Relinearize groups that ran through pipelined_halves
     uint64_t sg_fused = 0;     // cn_square_gemm calls that ran the one-key-switch-per-output form
+    uint64_t dsg_fused = 0;    // groups of queued scalar products that ran on deferred squarings in the one-key-switch-per-output form ("defer_square_gemm_fused")
     uint64_t dg_mfma = 0;      // digit GEMMs launched in the matrix-core form
     std::atomic<uint64_t> packed_bad{0};       // packed uploads whose rows held a residue >= its modulus (counted where the flag is read)
     bool digit_mfma = true;    // cn_set_option "digit_mfma": plans made from now on run their digit GEMM on the int8 matrix cores where they can (k_digit_gemm_mfma, exact); false: always
                                // the FP64 kernel k_digit_gemm.  A switch between two live forms of one step of cn_square_gemm, set by name like "ks_xi" (no environment override)
+    bool defer_square_gemm = false;  // cn_set_option "defer_square_gemm" (default 0: its effect on the literal call sequence has not been measured, profiles/deferred_square_gemm.md): queued squarings launched by a layer-boundary flush keep their relinearisation back; scalar products that read
+                               // nothing else run as cn_square_gemm's second half - one key switch per dense OUTPUT (cn_defer.hip); false: every queued squaring relinearises at once.
+                               // Set by name like "digit_mfma" (no environment override)
     uint64_t uid = 0;         // creation order within the process (cn_ctx_create)
     hipStream_t stream2 = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr; bool stream2_failed = false;   // second stream of pipelined_halves (aux_stream_ready)
     // deferred submission (cn_set_option("defer", 1)): per-ciphertext calls are queued and flushed as batched launches; 2: ... and submitted without the

@@ -135,6 +135,9 @@ int cn_mod_switch(cn_ctx *src, cn_handle in, uint32_t ii, uint32_t count, cn_ctx
  *   "mp_bcast"       flag    1                     -                cn_rowdot_batch transforms its ONE ciphertext once and the row plaintexts inside the
  *                                                                   product kernel; 0 = k_lift_ntt + k_mul_plain_fused
  *   "defer"          0..2    0                     -                deferred submission of per-ciphertext calls (below)
+ *   "defer_square_gemm" flag 0                     -                queued squarings keep their relinearisation back for the dense layer that
+ *                                                                   reads them: one key switch per dense output (below); 0 = every squaring relinearises
+ *                                                                   at once.  A context flag like "digit_mfma"
  *   "ks_xi"          flag    0                     -                decomposition convention of the key switch (below)
  *   "record_steps"   flag    0                     -                note the rotation steps the caller asks for (cn_rotation_steps); 0 stops and clears
  *
@@ -164,6 +167,16 @@ int cn_mod_switch(cn_ctx *src, cn_handle in, uint32_t ii, uint32_t count, cn_ctx
  * product and has been released by the caller (PoolLayer.ElementAt / ReleaseTemp, PoolLayer.cs:67-90) is not materialised: sum_t w_t Enc_t(0) is
  * added onto the scalar product's output by linearity - exact modular arithmetic on the same sampler draws (nonce, item), the SAME words as with
  * "fold_zero" = 0, a fifth of the transforms.  All or nothing per flush (every queued zero encryption must qualify).
+ * "defer_square_gemm" = 1 (off by default until it has been measured, profiles/deferred_square_gemm.md): the queue runs the reference's SquareActivation + PoolLayer call sequence (one cn_mul_relin(a, a) per column, then one cn_scalar_dot +
+ * cn_add_plain + cn_free per output) in the form of cn_square_gemm.  A flush at a layer boundary runs only the Multiply half of the squarings it launches and keeps
+ * the size-3 products in an array of the context (at most a quarter of the scratch limit; the callers' output arrays are not written yet).  The next flush decides
+ * once, all or nothing: if the caller has released every such output array (BaseLayer.GetNext disposes a layer's input), only scalar products read them, every
+ * gathered term of those scalar products is such an array, no queued call writes one, and the weights pass the test of cn_square_gemm (small signed weights, row sums
+ * within the digit bound, FP64 moduli and key, 1024 <= N <= 8192, "ks_xi" = 0), the scalar products run as GEMM + digit GEMM + ONE key switch per OUTPUT - the SAME
+ * words.  Otherwise every held-back product is relinearised into its own array first and the flush goes on as with "defer_square_gemm" = 0.  Every flush that is not a
+ * layer boundary (cn_sync, downloads, cn_stats_get, any non-deferrable entry point, a full queue, cn_ctx_destroy) settles what is held back and relinearises its own
+ * squarings at once: afterwards every array holds its words and the OperationsCount counters read as for the literal calls.  The plan of such a layer is built once
+ * and found again by its weights (a handful are kept per context).
  * "sq_halves": cn_mul_relin of >= 512 ciphertexts at N <= 8192 runs in parts software-pipelined over two streams of the context - the Multiply of a part
  * beside the key switch of the part before (its HBM-bound base extension / floor fill what the FP64-bound key switch leaves).  Same words; every later call
  * on the context is ordered behind all parts.  A caller that issues its plaintext primes one after the other (or from parallel tasks) gets what bench.py's
@@ -182,7 +195,7 @@ int cn_mod_switch(cn_ctx *src, cn_handle in, uint32_t ii, uint32_t count, cn_ctx
  * limb) blocks up to which a key switch runs as two launches: 160 / with one workgroup per digit: 10), CN_GEMM_ONE_LIMB=0 (the small-weight GEMM kernel
  * keeps its two-limb form), CN_DEFER_MERGE_GEMM=0 (deferred scalar products of one flush keep their levels: one launch per level instead of one per term
  * count), CN_PIN_RING_MIB (size of the pinned upload ring, 32 MiB), CN_DEFER_TRACE=1 (one stderr line per flushed queue level: calls per kind,
- * launches), CN_LOCK_GRACE_NS / CN_LOCK_COMBINE (the two context-lock experiments that are kept but off, cn_host.cpp). */
+ * launches; one per flush that holds squarings back, runs a dense layer on them or relinearises them after all), CN_LOCK_GRACE_NS / CN_LOCK_COMBINE (the two context-lock experiments that are kept but off, cn_host.cpp). */
 int cn_set_option(cn_ctx *ctx, const char *name, int value);
 /* reads back every option of cn_set_option's list, or one of these read-only values:
  *   "behz_small_base"          1: auxiliary primes below 2^49 - the FP64 kernels - k+1 of them, or k+2 where k+1 are too few (N = 16384); 0: SEAL's
@@ -198,6 +211,8 @@ int cn_set_option(cn_ctx *ctx, const char *name, int value);
  *   "mul_relin_pipelined"      cn_mul_relin chunks and flushed groups of queued Multiply + Relinearize calls that ran in parts over the context's two
  *                              streams ("sq_halves"; counts up)
  *   "square_gemm_fused"        cn_square_gemm calls that ran one key switch per output (counts up; the others took the two separate steps)
+ *   "defer_square_gemm_fused"  groups of queued scalar products that ran on held-back squarings with one key switch per output ("defer_square_gemm"; counts up)
+ *   "defer_pending_products"   squarings whose relinearisation is held back right now (0 after every flush that is not a layer boundary)
  *   "digit_gemm_mfma"          digit GEMMs of cn_square_gemm launched in the matrix-core form ("digit_mfma"; counts up)
  *   "pool_arrays"              device arrays cached for reuse (the temporaries of a live graph are reserved out of them)
  *   "stream_tries"             streams cn_ctx_create tried until one had a hardware queue of its own (< 0: none had; CN_STREAM_PROBE=0 takes the first) */
