@@ -170,6 +170,7 @@ SIGNATURES = {
     "cn_relinearize": (C.c_int, [_CTX, _H, _u32, _H, _u32, _u32]),
     "cn_mul_relin": (C.c_int, [_CTX, _H, _u32, _u32, _H, _u32, _u32, _H, _u32, _u32]),
     "cn_square_gemm": (C.c_int, [_CTX, _H, _H, _u32, _H, _u32]),
+    "cn_mul_relin_sum": (C.c_int, [_CTX, C.POINTER(_H), U32P, C.POINTER(_H), U32P, _u32, _u32, _H, _u32, _u32]),
     "cn_apply_galois": (C.c_int, [_CTX, _H, _u32, C.c_uint64, _H, _u32, _u32]),
     "cn_rotate_rows": (C.c_int, [_CTX, _H, _u32, C.c_int, _H, _u32, _u32]),
     "cn_rotate_rows_many": (C.c_int, [_CTX, _H, C.POINTER(C.c_uint32), C.POINTER(C.c_int), _u32, _H, C.POINTER(C.c_uint32)]),
@@ -551,6 +552,25 @@ class Context:
     def square_gemm(self, plan, src, ii, out, oi):
         """SquareActivation of the plan's inputs src[ii..] + the planned PoolLayer behind it: the words of mul_relin followed by gemm_apply"""
         self._chk(self.L.cn_square_gemm(self._h, plan, src, ii, out, oi))
+
+    def mul_relin_sum(self, a_handles, a_idx, b_handles, b_idx, b_stride, out, oi, count=1):
+        """out[oi + i] = sum_k Relinearize(Multiply(a_handles[k][a_idx[k] + i], b_handles[k][b_idx[k] + i * b_stride])), i < count: the words of mul_relin per
+        term followed by add_many, with one key switch per output where the context allows it (a_idx / b_idx None = all zero)"""
+        ha = np.ascontiguousarray(a_handles, dtype=np.uint64)
+        hb = np.ascontiguousarray(b_handles, dtype=np.uint64)
+        if ha.ndim != 1 or ha.shape != hb.shape:
+            raise ValueError("mul_relin_sum: one handle per term on either side")
+        ia = ib = None
+        if a_idx is not None:
+            ia = np.ascontiguousarray(a_idx, dtype=np.uint32)
+            if ia.shape != ha.shape:
+                raise ValueError("mul_relin_sum: one index per term expected")
+        if b_idx is not None:
+            ib = np.ascontiguousarray(b_idx, dtype=np.uint32)
+            if ib.shape != hb.shape:
+                raise ValueError("mul_relin_sum: one index per term expected")
+        self._chk(self.L.cn_mul_relin_sum(self._h, ha.ctypes.data_as(C.POINTER(_H)), ia.ctypes.data_as(U32P) if ia is not None else None,
+                                          hb.ctypes.data_as(C.POINTER(_H)), ib.ctypes.data_as(U32P) if ib is not None else None, ha.size, b_stride, out, oi, count))
 
     def apply_galois(self, src, ii, elt, out, oi, count=1):
         self._chk(self.L.cn_apply_galois(self._h, src, ii, elt, out, oi, count))

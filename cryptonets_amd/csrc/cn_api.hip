@@ -379,6 +379,7 @@ extern "C" int cn_set_option(cn_ctx *ctx, const char *name, int value) { API_BOD
     }
     if (!strcmp(name, "defer_square_gemm")) { ctx->defer_square_gemm = value != 0; return 0; }     // (LOCK has settled what the queue held back under the old value)
     if (!strcmp(name, "digit_mfma")) { ctx->digit_mfma = value != 0; defer_square_drop_plans(ctx); return 0; }     // the digit GEMM of plans made AFTER the call: matrix cores where eligible / FP64 (cn_eval.hip)
+    if (!strcmp(name, "mul_sum")) { ctx->mul_sum = value != 0; return 0; }       // cn_mul_relin_sum: one key switch per output where it can / always the literal sequence (cn_eval.hip)
     if (!strcmp(name, "record_steps")) {         // 1: record the RotateRows steps and column rotations asked for from now on (cn_rotation_steps); 0: stop and clear
         ctx->rec_steps = value != 0;
         if (!value) { ctx->rec_set.clear(); ctx->rec_cols = false; }
@@ -396,12 +397,16 @@ extern "C" int cn_get_option(cn_ctx *ctx, const char *name, int *value) { API_BO
     else if (!strcmp(name, "record_steps")) *value = ctx->rec_steps;
     else if (!strcmp(name, "digit_mfma")) *value = ctx->digit_mfma;
     else if (!strcmp(name, "defer_square_gemm")) *value = ctx->defer_square_gemm;
+    else if (!strcmp(name, "mul_sum")) *value = ctx->mul_sum;
     // read-only diagnostics: choices the library made and counters (tests)
     else if (!strcmp(name, "pin_laps")) *value = (int)ctx->pin_laps;                      // laps of the pinned upload ring (each one waits for the stream)
     else if (!strcmp(name, "ready_handles")) *value = (int)ctx->ready->size();          // allocated single-ciphertext arrays waiting for a lock-free cn_ct_alloc
     else if (!strcmp(name, "folded_zero_encryptions")) *value = (int)std::min<uint64_t>(ctx->folded_zero, 0x7fffffff);    // zero encryptions folded so far
     else if (!strcmp(name, "square_gemm_fused")) *value = (int)std::min<uint64_t>(ctx->sg_fused, 0x7fffffff);
     else if (!strcmp(name, "defer_square_gemm_fused")) *value = (int)std::min<uint64_t>(ctx->dsg_fused, 0x7fffffff);       // groups of queued scalar products run on deferred squarings
+    else if (!strcmp(name, "mul_sum_fused")) *value = (int)std::min<uint64_t>(ctx->ms_fused, 0x7fffffff);                 // cn_mul_relin_sum calls that ran one key switch per output
+    else if (!strcmp(name, "mul_sum_groups")) *value = (int)ctx->ms_groups;                                                // output groups of the last cn_mul_relin_sum (0: the literal sequence)
+    else if (!strcmp(name, "mul_sum_min_k")) *value = (int)MUL_SUM_MIN_K;                                                   // smallest K that takes that form
     else if (!strcmp(name, "defer_pending_products")) *value = (int)ctx->dq->sq->out.size();                             // squarings whose relinearisation is held back right now
     else if (!strcmp(name, "digit_gemm_mfma")) *value = (int)std::min<uint64_t>(ctx->dg_mfma, 0x7fffffff);                 // digit GEMMs launched in the matrix-core form
     else if (!strcmp(name, "packed_bad_residues")) *value = (int)std::min<uint64_t>(ctx->packed_bad.load(), 0x7fffffff);      // packed uploads that held a residue >= its modulus

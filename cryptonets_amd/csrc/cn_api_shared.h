@@ -188,6 +188,9 @@ bool aux_stream_ready(cn_ctx *ctx);
 // stagger of the primes 12.2-12.6; two parts 12.4-12.5, four 12.7, five 12.4).
 // mul(first, count), ks(first, count) launch on ctx->stream.
 static const uint32_t SQ_HALVES_MIN = 512;       // (the 100-ciphertext layer of CryptoNets pipelined as well: 12.35 -> 13.4 ms per batch, visit AY)
+// cn_mul_relin_sum: the smallest K that takes the one-key-switch-per-output form (cn_get_option "mul_sum_min_k").  2 = every sum of products: at C3, K = 2 takes
+// 0.53 (one output) and 0.69 (eight outputs) of the literal sequence's time, the spreads of the two sides apart (profiles/mul_relin_sum.md, tools/mul_sum_probe.py)
+static const uint32_t MUL_SUM_MIN_K = 2;
 // the parts of a pipelined batch of c ciphertexts: part i = [first[i], first[i + 1]); returns the number of parts P = min(3, max(1, c / 128)) (first[] holds P + 1
 // entries).  Three parts are cut at 30 and 70 %, two at the half; every cut is rounded up to a multiple of 8.
 static inline uint32_t pipeline_cuts(uint32_t c, uint32_t first[4]) {

@@ -761,6 +761,119 @@ extern "C" int cn_square_gemm(cn_ctx *ctx, cn_handle plan, cn_handle in, uint32_
     return 0;
 API_END }
 
+// ---------------------------------------------------------------- sum of encrypted x encrypted products in one call
+// DenseMatrixBySparseVectorMultiply with both operands encrypted (AtomicSealBfvVector.cs:459-465,502) and DotProduct of two encrypted dense vectors (:839-840,
+// 888-900) form out = sum_k Relinearize(Multiply(a_k, b_k)).  With ct_k = (d0_k + KS0(d2_k), d1_k + KS1(d2_k)) this is the identity above with unit weights:
+//   out = (sum_k d0_k, sum_k d1_k) + KS(S),   S_(l,d) = sum_k digit_(l,d)(d2_k)   - the digits cut per product, before the sum: the reference's words,
+// K multiplies and ONE key switch per output instead of K.  k_product_sum forms the three sums in one pass over the products.
+// The fused form runs when square_gemm_ctx_ok holds, "mul_sum" is on, K >= MUL_SUM_MIN_K, S is a lazy value the KsDigits kernels take (K (2^dbc - 1) below every
+// q_j / 2 and below 2^52), the kernel's 64-bit accumulators hold the sums of components 0 and 1 exactly (K (q_max - 1) < 2^64), its digit registers hold every limb's
+// digits (at most PRODUCT_SUM_MAX_DIGITS of at most 31 bits) and the scratch limit leaves room for the products of one output; anything else takes the literal
+// sequence - cn_mul_relin per term into a temporary, AddMany per output - inside the same call.
+static bool mul_sum_fused_ok(cn_ctx *ctx, uint32_t K) {
+    if (!ctx->mul_sum || K < MUL_SUM_MIN_K || !square_gemm_ctx_ok(ctx)) return false;
+    const int dbc = ctx->hc.dbc;
+    if (dbc < 1 || dbc > 31) return false;
+    const unsigned __int128 s = (unsigned __int128)K * ((1ull << dbc) - 1);
+    if (s >= ((unsigned __int128)1 << 52)) return false;
+    uint64_t qmax = 0;
+    for (uint32_t j = 0; j < ctx->hc.k; j++) {
+        qmax = std::max(qmax, ctx->hc.q[j].q);
+        if (s >= ctx->hc.q[j].q / 2) return false;
+        if (ctx->hc.rl_dig[j] > PRODUCT_SUM_MAX_DIGITS) return false;
+    }
+    return (unsigned __int128)K * (qmax - 1) < ((unsigned __int128)1 << 64) && !(ctx->hc.n & 511);      // PRODUCT_SUM_MAX_TERMS: floor((2^64 - 1) / (q_max - 1))
+}
+// AddMany of the K terms of every output out of the temporary of the literal sequence (term k of output i at k * count + i): one table, one launch per output
+static int add_many_terms(cn_ctx *ctx, Buffer *T, uint32_t K, Buffer *O, uint32_t oi, uint32_t count) {
+    std::vector<uint32_t> idx((size_t)count * K);
+    for (uint32_t i = 0; i < count; i++) for (uint32_t kk = 0; kk < K; kk++) idx[(size_t)i * K + kk] = kk * count + i;
+    CHECK(ensure_scratch(ctx, al(idx.size() * 4) + 4096));
+    uint32_t *didx; CHECK(upload_tmp(ctx, idx.data(), idx.size(), &didx));
+    const uint32_t limbs = T->size * ctx->hc.k;
+    for (uint32_t i = 0; i < count; i++) {
+        hipLaunchKernelGGL(k_add_many, dim3(limbs * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, T->d, didx + (size_t)i * K, K, T->item_words,
+                           O->d + (oi + i) * O->item_words, ctx->dc, ctx->chunks);
+        HIPCHK(hipGetLastError()); launch_count(ctx);
+    }
+    return 0;
+}
+extern "C" int cn_mul_relin_sum(cn_ctx *ctx, const cn_handle *a, const uint32_t *a_idx, const cn_handle *b, const uint32_t *b_idx, uint32_t K, uint32_t b_stride,
+                                cn_handle out, uint32_t oi, uint32_t count) { TWO_LIMBS("cn_mul_relin_sum"); API_BODY
+    LOCK;
+    if (!a || !b) return fail(CN_ERR_ARG, "null argument");
+    if (!K || !count) return fail(CN_ERR_ARG, "cn_mul_relin_sum of an empty list");
+    if (b_stride > 1) return fail(CN_ERR_ARG, "cn_mul_relin_sum: b_stride is 0 (one ciphertext for every output) or 1");
+    if ((uint64_t)K * count > 0x7fffffffull) return fail(CN_ERR_ARG, "cn_mul_relin_sum: too many products");
+    GETCT(O, out, 2);
+    if (!range_ok(O, oi, count)) return fail(CN_ERR_ARG, "output index out of range");
+    auto ai = [&](uint32_t kk) { return a_idx ? a_idx[kk] : 0u; };
+    auto bi = [&](uint32_t kk) { return b_idx ? b_idx[kk] : 0u; };
+    for (uint32_t kk = 0; kk < K; kk++) {
+        if (a[kk] == out || b[kk] == out) return fail(CN_ERR_ARG, "cn_mul_relin_sum cannot run in place (out is an operand handle)");
+        Buffer *A = getbuf(ctx, a[kk], 0), *B = getbuf(ctx, b[kk], 0);
+        if (!A || !B) return fail(CN_ERR_ARG, "invalid ciphertext handle in term %u", kk);
+        if (A->size != 2 || B->size != 2) return fail(CN_ERR_ARG, "ciphertext size mismatch in term %u", kk);
+        if (!range_ok(A, ai(kk), count) || !range_ok(B, bi(kk), b_stride ? count : 1)) return fail(CN_ERR_ARG, "index out of range in term %u", kk);
+    }
+    if (!ctx->rlk.d) return fail(CN_ERR_NOKEY, "relinearization keys not set");
+    ctx->ms_groups = 0;
+    const uint32_t n = ctx->hc.n, k = ctx->hc.k, tot = ctx->hc.rl_tot;
+    const size_t kn = (size_t)k * n;
+    if (K == 1) {                                                                 // one term per output: Multiply + Relinearize straight into the outputs
+        int rc = mul_relin_body(ctx, a[0], ai(0), 1, b[0], bi(0), b_stride, out, oi, count);
+        if (!rc) rc = cn_defer_flush(ctx);                                        // (a context that queues its calls has queued this one)
+        if (!rc) { ctx->st.AddMany += count; ctx->st.AddManyItemCount += count; }
+        return rc;
+    }
+    // outputs per group: the products [output][term][3][k][N], S [output][rl_tot][N] and the two address tables of a group beside the scratch of one product
+    const size_t per = mul_scratch_per_ct(ctx, false);
+    const size_t per_out = (size_t)K * 3 * kn * 8 + (size_t)tot * n * 8 + (size_t)K * 16, slack = 4 * 256 + 8192;
+    const size_t g_fit = ctx->smax > per + slack ? (ctx->smax - per - slack) / per_out : 0;
+    if (!mul_sum_fused_ok(ctx, K) || !g_fit) {                                    // the literal sequence: Multiply + Relinearize per term into a temporary, AddMany per output
+        cn_handle tmp = 0;
+        CHECK(alloc_buf(ctx, 0, K * count, 2, &tmp));
+        int rc = 0;
+        for (uint32_t kk = 0; kk < K && !rc; kk++) rc = mul_relin_body(ctx, a[kk], ai(kk), 1, b[kk], bi(kk), b_stride, tmp, kk * count, count);
+        if (!rc) rc = cn_defer_flush(ctx);
+        if (!rc) rc = add_many_terms(ctx, getbuf(ctx, tmp, 0), K, getbuf(ctx, out, 0), oi, count);      // (the handle table may have moved)
+        if (!rc) { ctx->st.AddMany += count; ctx->st.AddManyItemCount += (uint64_t)count * K; }
+        const int rf = free_body(ctx, tmp);
+        return rc ? rc : rf;
+    }
+    const uint32_t g = (uint32_t)std::min<size_t>(count, g_fit);
+    std::vector<const uint64_t *> ha((size_t)g * K), hb((size_t)g * K);
+    for (uint32_t o0 = 0; o0 < count; o0 += g) {                                  // the groups, one after the other
+        const uint32_t go = std::min(g, count - o0), np = go * K;
+        const size_t fixed = al((size_t)np * 3 * kn * 8) + al((size_t)go * tot * n * 8) + 2 * al((size_t)np * 8) + 8192;
+        const uint32_t ch = (uint32_t)std::min<size_t>(np, std::max<size_t>(1, (ctx->smax - std::min(ctx->smax, fixed)) / per));
+        CHECK(ensure_scratch(ctx, fixed + per * ch + 4096));
+        uint64_t *t3 = salloc<uint64_t>(ctx, (size_t)np * 3 * kn);
+        double *S = salloc<double>(ctx, (size_t)go * tot * n);
+        if (!t3 || !S) return fail(CN_ERR_HIP, "internal: scratch exhausted in cn_mul_relin_sum");
+        for (uint32_t i = 0; i < go; i++) for (uint32_t kk = 0; kk < K; kk++) {
+            const Buffer *A = getbuf(ctx, a[kk], 0), *B = getbuf(ctx, b[kk], 0);
+            ha[(size_t)i * K + kk] = A->d + (size_t)(ai(kk) + o0 + i) * A->item_words;
+            hb[(size_t)i * K + kk] = B->d + (size_t)(bi(kk) + (o0 + i) * b_stride) * B->item_words;
+        }
+        const uint64_t **da, **db;
+        CHECK(upload_tmp(ctx, ha.data(), np, &da)); CHECK(upload_tmp(ctx, hb.data(), np, &db));
+        const size_t mark = ctx->soff;
+        for (uint32_t s = 0; s < np; s += ch) {                                   // the products, all of them, before the sum
+            const uint32_t c = std::min(ch, np - s);
+            ctx->soff = mark;
+            CHECK(do_multiply(ctx, nullptr, 1, nullptr, 1, t3 + (size_t)s * 3 * kn, c, da + s, db + s));
+        }
+        uint64_t *o = O->d + (size_t)(oi + o0) * O->item_words;
+        CHECK(cn_l_product_sum(ctx, ProductSumLaunch{t3, K, o, S, go}));          // (sum d0, sum d1) straight into the outputs, the digit sums into S
+        CHECK(do_keyswitch(ctx, nullptr, 0, o, o + kn, 2 * kn, ctx->rlk, o, go, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, S));
+        ctx->ms_groups++;
+    }
+    ctx->st.Relinarization += (uint64_t)K * count; ctx->st.AddMany += count; ctx->st.AddManyItemCount += (uint64_t)count * K;
+    ctx->ms_fused++;
+    return 0;
+API_END }
+
 // ---------------------------------------------------------------- rotations
 // in/out device pointers to size-2 ciphertext arrays; tmp holds count size-2 ciphertexts
 // acc != nullptr: out = acc + galois(in) in the same launches (acc may alias out and/or in)

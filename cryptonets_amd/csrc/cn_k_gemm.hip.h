@@ -714,3 +714,93 @@ __global__ void __launch_bounds__(256, 2) k_digit_gemm_mfma(const uint64_t *__re
         }
     }
 }
+
+// ------------------------------------------------------------------ sum of K unrelinearized products (cn_mul_relin_sum)
+// out = sum_k Relinearize(Multiply(a_k, b_k)) needs ONE key switch, by the identity of k_digit_gemm with unit weights: this kernel is the sum in front of it.  A
+// streaming reduction over the K size-3 products of one output, prod[o][term][3][k][N] (canonical words, cn_l_behz_floor):
+//   out[o][c][l] = sum_k prod[o][k][c][l] mod q_l (c = 0, 1: canonical words - the add0 / add1 of the key switch, which reads them where it then writes the result),
+//   S[o][g0(l) + d] = sum_k dig_d(prod[o][k][2][l]),   dig_d(w) = (w >> dbc d) & (2^dbc - 1)   (exact doubles, where k_digit_gemm stores them).
+// Workgroup = (512 coefficients, source limb l, output o); a thread owns two consecutive coefficients and reads them with 16-byte global loads (k_mod_switch), the
+// limb-l words of all three components of a term: every product word comes from HBM exactly once - 3 K k N 8 bytes per output, the kernel's whole cost.  All ND
+// digits of the limb live in the thread (ND >= every rl_dig[l], chosen by the launcher; <= 8).  A wider decomposition has to loop digit groups in here, not split
+// them over workgroups: components 0 and 1 would be summed twice.  Terms in sets of four, two register sets ping-pong (k_digit_gemm): twelve 16-byte loads per
+// thread in flight before the first use; whole pairs of sets run without a branch, the at most seven terms behind them in a tail; a load behind the last term repeats it.
+// Accumulators are plain 64-bit integers: the host admits K (q_l - 1) < 2^64 for every l (components 0 and 1, one reduction mod q_l per stored word) and
+// K (2^dbc - 1) < 2^52 (digit sums: exact as doubles, lazy values the KsDigits kernels take) - PRODUCT_SUM_MAX_TERMS / mul_sum_fused_ok, cn_eval.hip.
+typedef uint64_t ps_u64x2 __attribute__((ext_vector_type(2)));
+typedef double ps_f64x2 __attribute__((ext_vector_type(2)));
+DEV uint64_t ps_reduce(uint64_t x, const DMod &m) {              // x mod q for any 64-bit x: r1 = floor(2^64 / q), the quotient estimate is low by at most one
+    const uint64_t r = x - __umul64hi(x, m.r1) * m.q;
+    return r >= m.q ? r - m.q : r;
+}
+template <int ND>
+__global__ void __launch_bounds__(256) k_product_sum(const uint64_t *__restrict__ prod_, uint32_t K, uint64_t *__restrict__ out_, double *__restrict__ S_,
+                                                     const DevConsts *__restrict__ C) {
+    typedef const NTT_GLOBAL ps_u64x2 *In;
+    constexpr int PF = 4;
+    const uint32_t n = C->n, k = C->k, n2 = n >> 1, tiles = n >> 9;
+    uint32_t b = blockIdx.x;
+    const uint32_t tile = b % tiles; b /= tiles;
+    const uint32_t l = b % k, o = b / k;
+    const uint32_t p = tile * 256 + threadIdx.x;                 // pair of coefficients
+    const uint32_t dbc = (uint32_t)C->dbc, mask = (1u << dbc) - 1, nd = C->rl_dig[l];
+    uint32_t g0 = 0;                                             // index of the first digit of limb l in the key
+    for (uint32_t x = 0; x < l; x++) g0 += C->rl_dig[x];
+    uint32_t sh[ND];
+#pragma unroll
+    for (int d = 0; d < ND; d++) sh[d] = min(dbc * (uint32_t)d, 63u);
+    const size_t comp = (size_t)k * n2, unit = 3 * comp;         // in 16-byte pairs
+    // a wave-uniform base per (term, component) and ONE 32-bit lane offset: the loads take the scalar-base form and need no address registers of their own
+    const NTT_GLOBAL char *src = (const NTT_GLOBAL char *)prod_ + (size_t)o * K * unit * 16;
+    const uint32_t lane_off = (l * n2 + p) * 16;                 // < 8 k N bytes
+    uint64_t c0x = 0, c0y = 0, c1x = 0, c1y = 0, dx[ND], dy[ND];
+#pragma unroll
+    for (int d = 0; d < ND; d++) { dx[d] = 0; dy[d] = 0; }
+    auto fetch = [&](ps_u64x2 (&x)[PF][3], uint32_t kk) {
+#pragma unroll
+        for (int t = 0; t < PF; t++) {
+            const NTT_GLOBAL char *s = src + (size_t)min(kk + (uint32_t)t, K - 1) * unit * 16;
+#pragma unroll
+            for (int c = 0; c < 3; c++) x[t][c] = *(In)(s + (size_t)c * comp * 16 + lane_off);
+        }
+    };
+    auto term = [&](const ps_u64x2 (&x)[3]) {
+        c0x += x[0].x; c0y += x[0].y; c1x += x[1].x; c1y += x[1].y;
+#pragma unroll
+        for (int d = 0; d < ND; d++) { dx[d] += (uint32_t)(x[2].x >> sh[d]) & mask; dy[d] += (uint32_t)(x[2].y >> sh[d]) & mask; }
+    };
+    auto terms = [&](const ps_u64x2 (&x)[PF][3]) {                 // a whole set: no branch
+#pragma unroll
+        for (int t = 0; t < PF; t++) term(x[t]);
+    };
+    auto tail = [&](const ps_u64x2 (&x)[PF][3], uint32_t nv) {     // the first nv terms of a set (wave-uniform)
+#pragma unroll
+        for (int t = 0; t < PF; t++) if ((uint32_t)t < nv) term(x[t]);
+    };
+    {   // whole sets in pairs, two register sets ping-pong (k_digit_gemm); the at most seven terms behind the last pair in a tail of their own
+        uint32_t kk = 0;
+        ps_u64x2 xa[PF][3], xb[PF][3];
+        fetch(xa, 0);
+        for (uint32_t it = K / (2 * PF); it; it--, kk += 2 * PF) {
+            fetch(xb, kk + PF);
+            terms(xa);
+            fetch(xa, kk + 2 * PF);
+            terms(xb);
+        }
+        const uint32_t r = K - kk;                                   // 0 .. 7
+        if (r > PF) fetch(xb, kk + PF);
+        tail(xa, min(r, (uint32_t)PF));
+        if (r > PF) tail(xb, r - PF);
+    }
+    const DMod m = C->q[l];
+    typedef NTT_GLOBAL ps_u64x2 *Out;
+    Out dst = (Out)out_ + (size_t)o * 2 * comp + (size_t)l * n2 + p;
+    ps_u64x2 v;
+    v.x = ps_reduce(c0x, m); v.y = ps_reduce(c0y, m); dst[0] = v;
+    v.x = ps_reduce(c1x, m); v.y = ps_reduce(c1y, m); dst[comp] = v;
+    typedef NTT_GLOBAL ps_f64x2 *OutS;
+    OutS sd = (OutS)S_ + ((size_t)o * C->rl_tot + g0) * n2 + p;
+#pragma unroll
+    for (int d = 0; d < ND; d++)
+        if ((uint32_t)d < nd) { ps_f64x2 w; w.x = (double)dx[d]; w.y = (double)dy[d]; sd[(size_t)d * n2] = w; }
+}

@@ -109,3 +109,20 @@ int cn_l_digit_gemm(cn_ctx *c, const DigitGemmLaunch &g) {
     cn_launch_count(c);
     return 0;
 }
+
+// sum of the K products of every output (cn_mul_relin_sum): ND = the smallest instantiation that holds all digits of every source limb
+template <int ND> static void launch_product_sum(cn_ctx *c, const ProductSumLaunch &g, uint32_t blocks) {
+    hipLaunchKernelGGL((k_product_sum<ND>), dim3(blocks), dim3(256), 0, c->stream, g.prod, g.K, g.out, g.S, c->dc);
+}
+int cn_l_product_sum(cn_ctx *c, const ProductSumLaunch &g) {
+    uint32_t ndmax = 0; for (uint32_t l = 0; l < c->hc.k; l++) ndmax = std::max(ndmax, c->hc.rl_dig[l]);
+    const uint64_t blocks = (uint64_t)(c->hc.n >> 9) * c->hc.k * g.outputs;
+    if ((c->hc.n & 511) || !g.K || !g.outputs || ndmax > PRODUCT_SUM_MAX_DIGITS || c->hc.dbc > 31 || blocks >= (1ull << 31)) return cn_fail(CN_ERR_ARG, "internal: product sum grid");
+    if (ndmax <= 2) launch_product_sum<2>(c, g, (uint32_t)blocks);
+    else if (ndmax <= 4) launch_product_sum<4>(c, g, (uint32_t)blocks);
+    else if (ndmax <= 5) launch_product_sum<5>(c, g, (uint32_t)blocks);
+    else launch_product_sum<8>(c, g, (uint32_t)blocks);
+    HIPCHK(hipGetLastError());
+    cn_launch_count(c);
+    return 0;
+}

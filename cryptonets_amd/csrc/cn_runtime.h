@@ -213,6 +213,10 @@ struct cn_ctx {
     uint64_t dsg_fused = 0;    // groups of queued scalar products that ran on deferred squarings in the one-key-switch-per-output form ("defer_square_gemm_fused")
     uint64_t dg_mfma = 0;      // digit GEMMs launched in the matrix-core form
     std::atomic<uint64_t> packed_bad{0};       // packed uploads whose rows held a residue >= its modulus (counted where the flag is read)
+    uint64_t ms_fused = 0;     // cn_mul_relin_sum calls that ran one key switch per output ("mul_sum_fused")
+    uint32_t ms_groups = 0;    // output groups of the last cn_mul_relin_sum call ("mul_sum_groups"; 0: it took the literal sequence)
+    bool mul_sum = true;       // cn_set_option "mul_sum": cn_mul_relin_sum sums the unrelinearized products and runs one key switch per output where it can (k_product_sum, the
+                               // same words); false: always Multiply + Relinearize per term and AddMany.  A switch between two live forms of one call, set by name like "digit_mfma"
     bool digit_mfma = true;    // cn_set_option "digit_mfma": plans made from now on run their digit GEMM on the int8 matrix cores where they can (k_digit_gemm_mfma, exact); false: always
                                // the FP64 kernel k_digit_gemm.  A switch between two live forms of one step of cn_square_gemm, set by name like "ks_xi" (no environment override)
     bool defer_square_gemm = false;  // cn_set_option "defer_square_gemm" (default 0: its effect on the literal call sequence has not been measured, profiles/deferred_square_gemm.md): queued squarings launched by a layer-boundary flush keep their relinearisation back; scalar products that read
@@ -323,6 +327,11 @@ inline uint32_t digit_gemm_mfma_group(uint32_t P) { return P <= 2 ? 3u : 2u; }  
 inline uint32_t digit_gemm_tile(uint32_t M) { return M > 2 ? 10u : 2u; }
 inline uint32_t digit_gemm_rows(uint32_t K) { return ((K + 7) & ~7u) + 8; }        // K terms + zero rows: the kernel's sets of four terms run past K
 int cn_l_digit_gemm(cn_ctx *c, const DigitGemmLaunch &g);
+// sum of unrelinearized products (cn_mul_relin_sum, k_product_sum): prod [outputs][K][3][k][N] -> components 0 and 1 summed mod q_l into out [outputs][2][k][N],
+// the digit sums of component 2 into S [outputs][rl_tot][N] doubles.  Every source limb has at most PRODUCT_SUM_MAX_DIGITS digits of at most 31 bits
+struct ProductSumLaunch { const uint64_t *prod; uint32_t K; uint64_t *out; double *S; uint32_t outputs; };
+static const uint32_t PRODUCT_SUM_MAX_DIGITS = 8;
+int cn_l_product_sum(cn_ctx *c, const ProductSumLaunch &g);
 // modulus switching (cn_l_modswitch.hip): `items` (ciphertext, poly) pairs [items][ks][N] -> [items][kd][N] on c's stream with the constants of the source context
 int cn_l_mod_switch(cn_ctx *c, const uint64_t *src, uint64_t *dst, const DevConsts *src_consts, uint32_t ks, uint32_t kd, uint32_t items, uint32_t logn,
                     bool f64, bool *ran_f64);

@@ -648,7 +648,14 @@ class AtomicSealBfvEncryptedVector:
         K = len(denses)
         res = _Buf(ctx, "ct", l).view()
         if denses[0].IsEncrypted and sparse.IsEncrypted:
-            # Multiply + Relinearize per term, then AddMany (:459-465,502)
+            # Multiply + Relinearize per term, then AddMany (:459-465,502).  The twin's form: ONE cn_mul_relin_sum over the K columns where they lie - the same
+            # words and counters, one key switch per output block where the context allows it
+            if hasattr(ctx, "mul_relin_sum"):
+                ctx.mul_relin_sum([d.encData.h for d in denses], [d.encData.first for d in denses], [sparse.encData.h] * K,
+                                  [sparse.encData.first + k for k in range(K)], 0, res.h, 0, l)
+                return AtomicSealBfvEncryptedVector._new(Format=EVectorFormat.dense, Scale=denses[0].Scale * sparse.Scale, IsSigned=sparse.IsSigned,
+                                                         encData=res, Dim=denses[0].Dim)
+            # (backends without cn_mul_relin_sum - the CPU test harness): the literal loop
             terms = _Buf(ctx, "ct", K * l).view()
             for k in range(K):
                 ctx.mul_relin(denses[k].encData.h, denses[k].encData.first, sparse.encData.h, sparse.encData.first + k,
@@ -969,6 +976,18 @@ class AtomicSealBfvEncryptedVector:
 
     def DotProduct(self, v, env, length=None, ForceOutputInColumn=None):
         """AtomicSealBfvVector.cs:963-977"""
+        full = length is None or length > 1
+        if (full and self.encData is not None and v.encData is not None and self.Format == v.Format == EVectorFormat.dense and self.Dim == v.Dim
+                and self.IsSigned == v.IsSigned and v.encData.count > 1 and self.encData.count == v.encData.count and hasattr(env.ctx, "mul_relin_sum")):
+            # two encrypted dense vectors of several blocks: PointwiseMultiply (:839-840) and the AddMany at the head of SumAllSlots (:888-900) as ONE
+            # cn_mul_relin_sum - the same words and counters - into the array the slot sum is then built in
+            _check_level(env, self, v)
+            n = v.encData.count
+            mul = AtomicSealBfvEncryptedVector._new(Scale=self.Scale * v.Scale, Dim=self.Dim, Format=self.Format, IsSigned=self.IsSigned)
+            mul.encData = _Buf(env.ctx, "ct", 1).view()
+            env.ctx.mul_relin_sum([v.encData.h] * n, [v.encData.first + i for i in range(n)], [self.encData.h] * n,
+                                  [self.encData.first + i for i in range(n)], 1, mul.encData.h, 0, 1)
+            return mul.SumAllSlots(env, length, ForceOutputInColumn, _consume=True)
         mul = self.PointwiseMultiply(v, env)
         if (length is None or length > 1) and mul.encData is not None and mul.Format == EVectorFormat.dense:
             return mul.SumAllSlots(env, length, ForceOutputInColumn, _consume=True)       # the product is a temporary: summed in its own array

@@ -118,6 +118,8 @@ int cn_mod_switch(cn_ctx *src, cn_handle in, uint32_t ii, uint32_t count, cn_ctx
  *   "digit_mfma"     flag    1                     -                the digit GEMM of cn_square_gemm on the int8 matrix cores where the plan's own GEMM
  *                                                                   takes them and a key-switch digit has at most 14 bits; 0 = the FP64 kernel (which
  *                                                                   also serves every other plan).  The same words.  Affects GEMMs planned after the call
+ *   "mul_sum"        flag    1                     -                cn_mul_relin_sum sums the unrelinearized products and runs one key switch per output
+ *                                                                   where it can; 0 = always Multiply + Relinearize per term, then AddMany.  The same words
  *   "gemm_pair"      flag    1                     CN_GEMM_PAIR     cn_scalar_gemm / cn_gemm_plan_create merge gather lists that share at least half of
  *                                                                   their inputs in pairs (small signed weights, lists of <= 64 entries and <= 5
  *                                                                   outputs); 0 = the caller's lists.  Affects GEMMs planned after the call
@@ -213,6 +215,9 @@ int cn_set_option(cn_ctx *ctx, const char *name, int value);
  *   "square_gemm_fused"        cn_square_gemm calls that ran one key switch per output (counts up; the others took the two separate steps)
  *   "defer_square_gemm_fused"  groups of queued scalar products that ran on held-back squarings with one key switch per output ("defer_square_gemm"; counts up)
  *   "defer_pending_products"   squarings whose relinearisation is held back right now (0 after every flush that is not a layer boundary)
+ *   "mul_sum_fused"            cn_mul_relin_sum calls that ran one key switch per output (counts up; the others took the literal sequence)
+ *   "mul_sum_groups"           output groups of the last cn_mul_relin_sum call (0: it took the literal sequence or had K = 1)
+ *   "mul_sum_min_k"            the smallest K for which cn_mul_relin_sum takes the one-key-switch form
  *   "digit_gemm_mfma"          digit GEMMs of cn_square_gemm launched in the matrix-core form ("digit_mfma"; counts up)
  *   "pool_arrays"              device arrays cached for reuse (the temporaries of a live graph are reserved out of them)
  *   "stream_tries"             streams cn_ctx_create tried until one had a hardware queue of its own (< 0: none had; CN_STREAM_PROBE=0 takes the first) */
@@ -360,6 +365,24 @@ int cn_mul_relin(cn_ctx *ctx, cn_handle a, uint32_t ai, uint32_t a_stride, cn_ha
  * path, 1024 <= N <= 8192 and "ks_xi" is 0; otherwise the call runs the two steps through a temporary - same result, no error.  `in` and `out` must be different
  * handles; with "defer" on, queued calls are submitted first and the call runs at once; under cn_graph_begin it is recorded like its two parts. */
 int cn_square_gemm(cn_ctx *ctx, cn_handle plan, cn_handle in, uint32_t ii, cn_handle out, uint32_t oi);
+/* Encrypted x encrypted sums of products, as one call: out[oi + i] = sum_{k < K} Relinearize(Multiply(a[k][a_idx[k] + i], b[k][b_idx[k] + i * b_stride])), i < count.
+ * DenseMatrixBySparseVectorMultiply with both operands encrypted (AtomicSealBfvVector.cs:459-465,502: Multiply + Relinearize per term, then AddMany - a[k] the dense
+ * column k, b[k] the sparse vector's entry k, b_stride 0) and DotProduct of two encrypted dense vectors of several blocks (:963-977: PointwiseMultiply :839-840 and the
+ * AddMany at the head of SumAllSlots :888-900 - K = blocks, count 1).  K operand handles on either side, in the form of cn_scalar_dot (a caller's columns are separate
+ * arrays; handles may repeat); a_idx / b_idx may be NULL (all zero); b_stride is 0 (one ciphertext of b[k] for every output) or 1.
+ * The words, and the counters of cn_stats that mirror OperationsCount, are those of the literal sequence: K calls of cn_mul_relin into a temporary, then cn_add_many
+ * per output.  A key switch is linear in the digits of its operand, so the sum needs ONE key switch per output, fed with S = sum_k digit(d2_k) - digits cut per
+ * product, before the sum, hence the reference's words (cn_square_gemm with unit weights): K multiplies, one pass that sums the unrelinearized products
+ * (components 0 and 1 mod q, the digits of component 2 as integers), one key switch.  That form runs when every coefficient modulus and the relinearization key are on
+ * the exact-FP64 path, 1024 <= N <= 8192, "ks_xi" is 0, K (2^dbc - 1) is below every q_j / 2 and below 2^52, K (q_max - 1) < 2^64, a digit has at most 31 bits and a limb at
+ * most 8 digits, K >= "mul_sum_min_k", "mul_sum" is 1 and the scratch limit (CN_SCRATCH_GB) leaves room for the K products of one output; the outputs run in groups
+ * whose products fit that limit ("mul_sum_groups").  Otherwise the call runs the literal sequence through a temporary - same result, no error.  K = 1 is cn_mul_relin
+ * into the outputs.  Level contexts are eligible (their sliced keys are the prefix's key set under "ks_xi" = 0).
+ * Refused with CN_ERR_ARG / CN_ERR_NOKEY, nothing written: K = 0, count = 0, b_stride > 1, an index range outside its handle, `out` among the operand handles,
+ * operands or outputs not of size 2, no relinearization key, a context with one coefficient modulus.  With "defer" on, queued calls are submitted first and the call
+ * runs at once; under cn_graph_begin it is recorded like its parts. */
+int cn_mul_relin_sum(cn_ctx *ctx, const cn_handle *a, const uint32_t *a_idx, const cn_handle *b, const uint32_t *b_idx, uint32_t K, uint32_t b_stride,
+                     cn_handle out, uint32_t oi, uint32_t count);
 
 /* ---- rotations (HOT LOOP C) ----------------------------------------------------------- */
 /* Evaluator.ApplyGalois: automorphism + key switch of c1 */

@@ -641,14 +641,12 @@ namespace HEWrapper
             var res = Result(env, (uint)l);
             res.Format = EVectorFormat.dense; res.Scale = denses[0].Scale * sparse.Scale; res.IsSigned = sparse.IsSigned; res.Dim = denses[0].Dim;
             if (denses[0].IsEncrypted && sparse.IsEncrypted)
-            {   // Multiply + Relinearize per term (:459-465), then AddMany (:502)
-                using (var terms = new CnBuffer(env.device, (uint)(K * l)))
-                {
-                    for (int k = 0; k < K; k++)
-                        CnHip.Check(CnHip.cn_mul_relin(ctx, denses[k].enc.Handle, 0, 1, sparse.enc.Handle, (uint)k, 0, terms.Handle, (uint)(k * l), (uint)l));
-                    for (int i = 0; i < l; i++)
-                        CnHip.Check(CnHip.cn_add_many(ctx, terms.Handle, Enumerable.Range(0, K).Select(k => (uint)(k * l + i)).ToArray(), (uint)K, res.enc.Handle, (uint)i));
-                }
+            {   // Multiply + Relinearize per term (:459-465), then AddMany (:502): ONE cn_mul_relin_sum over the K columns where they lie - the same words,
+                // one key switch per output block where the context allows it
+                var columns = denses.Select(d => d.enc.Handle).ToArray();
+                var entries = Enumerable.Repeat(sparse.enc.Handle, K).ToArray();
+                var entryIndex = Enumerable.Range(0, K).Select(k => (uint)k).ToArray();
+                CnHip.Check(CnHip.cn_mul_relin_sum(ctx, columns, null, entries, entryIndex, (uint)K, 0, res.enc.Handle, 0, (uint)l));
                 OperationsCount.Add(ref OperationsCount.Multiplication, K * l); OperationsCount.Add(ref OperationsCount.Relinarization, K * l);
             }
             else if (denses[0].IsEncrypted)
