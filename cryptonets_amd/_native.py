@@ -17,7 +17,7 @@ CSRC = os.path.join(_PKG, "csrc")
 SOURCES = [os.path.join(CSRC, f) for f in (
     "cn_api.hip", "cn_eval.hip", "cn_client.hip", "cn_defer.hip", "cn_multi.hip", "cn_host.cpp", "cn_tables.cpp", "cn_l_gemm.hip", "cn_l_behz.hip",
     "cn_l_rr_u64.hip", "cn_l_rr_f64.hip", "cn_l_rr_f64l.hip", "cn_l_ks_u64.hip", "cn_l_ks_f64.hip", "cn_l_ks_f64l.hip", "cn_level.hip", "cn_l_modswitch.hip",
-    "cn_l_modswitch_f64.hip", "cn_l_noise.hip", "cn_l_seeded.hip", "cn_l_keygen.hip", "cn_l_packed.hip")]
+    "cn_l_modswitch_f64.hip", "cn_l_noise.hip", "cn_l_seeded.hip", "cn_l_keygen.hip", "cn_l_packed.hip", "cn_l_join.hip")]
 OBJ_DIR = os.path.join(_PKG, "lib", "obj")
 
 U64P = C.POINTER(C.c_uint64)
@@ -200,6 +200,8 @@ SIGNATURES = {
     "cn_decrypt": (C.c_int, [_CTX, _H, _u32, _u32, _H, _u32]),
     "cn_noise_poly": (C.c_int, [_CTX, _H, _u32, _u32, C.POINTER(C.c_uint64)]),
     "cn_noise_norm": (C.c_int, [_CTX, _H, _u32, _u32, C.POINTER(C.c_uint64)]),
+    "cn_join_words": (C.c_int, [C.POINTER(_CTX), _u32]),
+    "cn_decrypt_join": (C.c_int, [C.POINTER(_CTX), _u32, C.POINTER(_H), U32P, _u32, _u32, _u32, C.c_double, C.POINTER(C.c_double), U64P, I32P]),
     "cn_ntt_forward": (C.c_int, [_CTX, C.c_void_p, _u32, C.c_int]),
     "cn_ntt_inverse": (C.c_int, [_CTX, C.c_void_p, _u32, C.c_int]),
     "cn_ct_ntt": (C.c_int, [_CTX, _H, _u32, _u32, C.c_int]),
@@ -243,6 +245,62 @@ def broadcast_keys(contexts):
     rc = lib().cn_ctx_broadcast_keys(arr, len(contexts))
     if rc:
         raise CnError(rc, lib().cn_last_error().decode())
+
+
+def join_words(contexts):
+    """64-bit words of one joined integer of these plaintext-prime contexts: ceil((bit_length(prod t_i) + 1) / 64) (cn_join_words)"""
+    arr = (_CTX * len(contexts))(*[c._h for c in contexts])
+    w = lib().cn_join_words(arr, len(contexts))
+    if w <= 0:
+        raise CnError(w, lib().cn_last_error().decode())
+    return w
+
+
+class JoinResult:
+    """what decrypt_join returns: values [count, nslots] float64, words [count, nslots, W] uint64 (two's complement, little-endian) or None,
+    argmax [nslots] int32 or None"""
+
+    def __init__(self, values, words, argmax):
+        self.values, self.words, self.argmax = values, words, argmax
+
+    def ints(self):
+        """the joined integers as Python ints, [count][nslots]"""
+        W = self.words.shape[2]
+        out = []
+        for row in self.words.reshape(self.words.shape[0], -1).tolist():
+            r = []
+            for i in range(0, len(row), W):
+                x = 0
+                for w in range(W - 1, -1, -1):
+                    x = (x << 64) | row[i + w]
+                r.append(x - (1 << (64 * W)) if x >> (64 * W - 1) else x)
+            out.append(r)
+        return out
+
+
+def decrypt_join(contexts, handles, firsts, count, nslots, signed=True, scale=1.0, coeff0=False, words=False, argmax=False, values=True):
+    """Decrypt + BatchEncoder.Decode + JoinSplitNumbers of `count` ciphertexts per plaintext prime in one call (cn_decrypt_join): contexts[i] holds
+    the ciphertexts handles[i][firsts[i] : firsts[i] + count] of prime t_i (firsts None = 0).  Dense form: the first `nslots` slots of every
+    ciphertext; coeff0: coefficient 0 of every plaintext (nslots = 1, the wrapper's sparse format).  Joined value x in [0, M), or centred under
+    `signed`; values = float(x) / scale."""
+    L = lib()
+    P = len(contexts)
+    arr = (_CTX * P)(*[c._h for c in contexts])
+    hs = (_H * P)(*[int(h) for h in handles])
+    fs = None if firsts is None else (_u32 * P)(*[int(f) for f in firsts])
+    flags = (1 if signed else 0) | (2 if coeff0 else 0)
+    out_v = np.empty((count, nslots), dtype=np.float64) if values else None
+    out_w = None
+    if words:
+        out_w = np.empty((count, nslots, join_words(contexts)), dtype=np.uint64)
+    out_a = np.empty(nslots, dtype=np.int32) if argmax else None
+    rc = L.cn_decrypt_join(arr, P, hs, fs, count, nslots, flags, float(scale),
+                           None if out_v is None else out_v.ctypes.data_as(C.POINTER(C.c_double)),
+                           None if out_w is None else out_w.ctypes.data_as(U64P),
+                           None if out_a is None else out_a.ctypes.data_as(I32P))
+    if rc:
+        raise CnError(rc, L.cn_last_error().decode())
+    return JoinResult(out_v, out_w, out_a)
 
 
 def default_coeff_modulus(n):

@@ -210,6 +210,16 @@ class CryptoNetsChannel:
         g.relinearize(self.w3, 0, self.h5, 0, 10)
 
 
+def predict(channels, nslots=None):
+    """The predicted class of every image of the batch: the arg max over the 10 logit ciphertexts (h5) of the plaintext-prime channels, decrypted, decoded,
+    CRT-joined and compared as exact signed integers on the device in ONE call (cn_decrypt_join with `argmax`) - [nslots] int32, nslots = N by default.
+    The contexts hold the secret key (the data owner's side: client.DeviceClient)."""
+    from . import _native
+    ctxs = [c.g for c in channels]
+    n = ctxs[0].n if nslots is None else int(nslots)
+    return _native.decrypt_join(ctxs, [c.h5 for c in channels], None, 10, n, signed=True, values=False, argmax=True).argmax
+
+
 def constant_plaintext(n):
     def enc(v):
         p = np.zeros(n, dtype=np.uint64)

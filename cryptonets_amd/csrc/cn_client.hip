@@ -1,5 +1,6 @@
 // libcnhip.so host runtime (3/5): the data owner's side on the device - keys, ChaCha20 sampler, keygen, encrypt, decrypt, noise.
 #include "cn_api_shared.h"
+#include "cn_k_join.hip.h"
 
 // ---------------------------------------------------------------- client side on the device
 int set_plain_key(cn_ctx *ctx, uint64_t **slot, const uint64_t *words, size_t count, size_t expect, bool is_dev, bool coeff_form) {
@@ -532,3 +533,102 @@ extern "C" int cn_ct_upload_packed(cn_ctx *ctx, cn_handle h, uint32_t first, uin
     if (seen) { ctx->packed_bad++; return fail(CN_ERR_ARG, "residue not below its modulus"); }
     return 0;
 API_END }
+// ---------------------------------------------------------------- the reply path (include/cnhip.h: cn_decrypt_join; kernels: cn_k_join.hip.h)
+// The constants of a list of contexts: CN_ERR_ARG unless cn_decrypt_join accepts the list (the checks that need no lock: N, device, t are fixed at creation)
+static int join_tab_of(cn_ctx *const *ctxs, uint32_t P, uint32_t flags, double scale, JoinTab &T) {
+    if (!ctxs || P < 1 || P > CNJ_MAXP) return fail(CN_ERR_ARG, "cn_decrypt_join takes 1 .. %d contexts", CNJ_MAXP);
+    uint64_t t[CNJ_MAXP];
+    for (uint32_t i = 0; i < P; i++) {
+        if (!ctxs[i]) return fail(CN_ERR_ARG, "null context at position %u", i);
+        if (ctxs[i]->hc.n != ctxs[0]->hc.n || ctxs[i]->device != ctxs[0]->device) return fail(CN_ERR_ARG, "cn_decrypt_join: context %u has another N or device", i);
+        if (!ctxs[i]->hc.inv_g_t) return fail(CN_ERR_ARG, "device decryption needs a prime plain modulus");
+        t[i] = ctxs[i]->hc.t.q;
+        for (uint32_t h = 0; h < i; h++) if (t[h] == t[i]) return fail(CN_ERR_ARG, "cn_decrypt_join: contexts %u and %u have the same plain modulus", h, i);
+    }
+    if (cnj_build_tab(t, P, flags, scale, &T)) return fail(CN_ERR_ARG, "cn_decrypt_join: the product of the plain moduli must stay below 2^255");
+    return 0;
+}
+extern "C" int cn_join_words(cn_ctx *const *ctxs, uint32_t P) {
+    JoinTab T;
+    CHECK(join_tab_of(ctxs, P, 0, 1.0, T));
+    return (int)T.W;
+}
+static bool join_lock_order(const cn_ctx *x, const cn_ctx *y) { return x->hc.k != y->hc.k ? x->hc.k > y->hc.k : x < y; }      // as cn_mod_switch takes two (cn_level.hip)
+static int decrypt_join_locked(cn_ctx *const *ctxs, const JoinTab &T, const cn_handle *ct, const uint32_t *ci, uint32_t count, uint32_t nslots,
+                               double *values, uint64_t *words, int32_t *argmax) {
+    const uint32_t P = T.P, W = T.W, n = ctxs[0]->hc.n;
+    const bool dense = !(T.flags & CNJ_COEFF0);
+    for (uint32_t i = 0; i < P; i++) { cn_ctx *ctx = ctxs[i]; NOT_CAPTURING("cn_decrypt_join"); }
+    // not deferrable: every context's queued calls and published records are submitted first (a handle may come from the lock-free ring)
+    for (uint32_t i = 0; i < P; i++) CHECK(flush_all(ctxs[i]));
+    Buffer *I[CNJ_MAXP];
+    for (uint32_t i = 0; i < P; i++) {
+        cn_ctx *ctx = ctxs[i];
+        GETCT(B, ct[i], 0);
+        if (B->size != 2 && B->size != 3) return fail(CN_ERR_ARG, "cn_decrypt_join: ciphertexts of size 2 or 3");
+        if (!range_ok(B, ci ? ci[i] : 0, count)) return fail(CN_ERR_ARG, "index out of range");
+        if (!ctx->sk) return fail(CN_ERR_NOKEY, "secret key not set");
+        I[i] = B;
+    }
+    if (!count) return 0;
+    cn_ctx *c0 = ctxs[0];
+    for (uint32_t i = 0; i < P; i++) if (!ctxs[i]->ev_ms) { CHECK(use(ctxs[i])); HIPCHK(hipEventCreateWithFlags(&ctxs[i]->ev_ms, hipEventDisableTiming)); }
+    CHECK(use(c0));
+    if (dense) CHECK(ensure_index_map(c0));                   // (the slot order depends on N alone)
+    // the arena of the call, in ctxs[0]'s scratch behind the arrays of its own decryption: plaintexts [P][count][N], the constants, the outputs.
+    // The other contexts write their slice from their own streams: they start behind whatever ctxs[0]'s stream still runs on that memory.
+    HIPCHK(hipEventRecord(c0->ev_ms, c0->stream));
+    const size_t slice = (size_t)count * n, total = (size_t)count * nslots;
+    const bool want_words = words || argmax;
+    const size_t vbytes = values ? total * 8 : 0, wbytes = want_words ? total * W * 8 : 0, abytes = argmax ? (size_t)nslots * 4 : 0;
+    uint64_t *plain = nullptr, *dwords = nullptr; JoinTab *dtab = nullptr; double *dvalues = nullptr; int32_t *dargmax = nullptr;
+    for (uint32_t i = 0; i < P; i++) {
+        cn_ctx *ctx = ctxs[i];
+        CHECK(use(ctx));
+        if (i && ctx->stream != c0->stream) HIPCHK(hipStreamWaitEvent(ctx->stream, c0->ev_ms, 0));
+        uint64_t *acc = nullptr;
+        const uint32_t first = ci ? ci[i] : 0;
+        CHECK(decrypt_phase(ctx, I[i], first, count, acc, i ? 0 : al(P * slice * 8) + al(sizeof(JoinTab)) + al(vbytes) + al(wbytes) + al(abytes)));
+        if (!i) {
+            plain = salloc<uint64_t>(ctx, P * slice);
+            CHECK(upload_tmp(ctx, &T, 1, &dtab));
+            if (vbytes) dvalues = (double *)salloc<char>(ctx, vbytes);
+            if (wbytes) dwords = (uint64_t *)salloc<char>(ctx, wbytes);
+            if (abytes) dargmax = (int32_t *)salloc<char>(ctx, abytes);
+            if (!plain || (vbytes && !dvalues) || (wbytes && !dwords) || (abytes && !dargmax)) return fail(CN_ERR_HIP, "internal: scratch exhausted in cn_decrypt_join");
+        }
+        uint64_t *mine = plain + (size_t)i * slice;
+        DISPATCH_K2(launch_dec_scale, ctx, I[i]->d + first * I[i]->item_words, I[i]->item_words, acc, mine, count);
+        HIPCHK(hipGetLastError()); launch_count(ctx);
+        if (dense) CHECK(cn_run_ntt(ctx, mine, count, ctx->hc.k + ctx->hc.kb, 1, 0));     // the forward transform mod t of cn_decode_batch
+        if (i && ctx->stream != c0->stream) {                                             // ctxs[0]'s stream waits for this slice
+            HIPCHK(hipEventRecord(ctx->ev_ms, ctx->stream));
+            HIPCHK(hipStreamWaitEvent(c0->stream, ctx->ev_ms, 0));
+        }
+    }
+    CHECK(use(c0));
+    CHECK(cn_l_crt_join(c0, plain, c0->d_index_map, dtab, P, W, dvalues, dwords, count, nslots));
+    if (argmax) CHECK(cn_l_join_argmax(c0, dwords, W, dargmax, count, nslots));
+    if (values) HIPCHK(hipMemcpyAsync(values, dvalues, vbytes, hipMemcpyDeviceToHost, c0->stream));
+    if (words) HIPCHK(hipMemcpyAsync(words, dwords, wbytes, hipMemcpyDeviceToHost, c0->stream));
+    if (argmax) HIPCHK(hipMemcpyAsync(argmax, dargmax, abytes, hipMemcpyDeviceToHost, c0->stream));
+    // the one host wait of the call: ctxs[0]'s stream has waited for every other stream's slice, so nothing of the call is in flight on any of them afterwards
+    HIPCHK(hipStreamSynchronize(c0->stream));
+    return 0;
+}
+extern "C" int cn_decrypt_join(cn_ctx *const *ctxs, uint32_t P, const cn_handle *ct, const uint32_t *ci, uint32_t count, uint32_t nslots, uint32_t flags, double scale,
+                               double *values, uint64_t *words, int32_t *argmax) {
+    JoinTab T;
+    CHECK(join_tab_of(ctxs, P, flags, scale, T));
+    if (flags & ~(CNJ_SIGNED | CNJ_COEFF0)) return fail(CN_ERR_ARG, "cn_decrypt_join: unknown flag");
+    if (!ct) return fail(CN_ERR_ARG, "null argument");
+    if (!values && !words && !argmax) return fail(CN_ERR_ARG, "cn_decrypt_join: no output asked for");
+    if (nslots == 0 || nslots > ctxs[0]->hc.n) return fail(CN_ERR_ARG, "cn_decrypt_join: 1 .. N slots");
+    if ((flags & CNJ_COEFF0) && nslots != 1) return fail(CN_ERR_ARG, "cn_decrypt_join: CN_JOIN_COEFF0 reads one coefficient (nslots = 1)");
+    if (!(flags & CNJ_COEFF0)) for (uint32_t i = 0; i < P; i++) if (!ctxs[i]->hc.batching) return fail(CN_ERR_ARG, "plain modulus does not support batching");
+    // every lock, in the order cn_mod_switch takes two (more limbs first): calls over one set of contexts cannot deadlock
+    std::vector<cn_ctx *> order(ctxs, ctxs + P);
+    std::sort(order.begin(), order.end(), join_lock_order);
+    HeldLocks locks(order);
+    return decrypt_join_locked(ctxs, T, ct, ci, count, nslots, values, words, argmax);
+}

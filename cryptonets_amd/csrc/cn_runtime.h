@@ -338,6 +338,10 @@ int cn_l_mod_switch(cn_ctx *c, const uint64_t *src, uint64_t *dst, const DevCons
 // invariant noise norm (cn_l_noise.hip): `count` ciphertexts (c0 of ciphertext i at c0 + i * ct_stride, acc [count][k][N] from decrypt_phase) ->
 // out [count][k] words on c's stream
 int cn_l_noise_norm(cn_ctx *c, const uint64_t *c0, size_t ct_stride, const uint64_t *acc, uint64_t *out, uint32_t count);
+// reply path (cn_l_join.hip, cn_k_join.hip.h): the CRT join of `count` x `nslots` values out of the transformed plaintexts plain [P][count][N] on c's stream (tab: the call's
+// JoinTab on the device; values [count][nslots] doubles and words [count][nslots][W] may be null), and the arg max per slot over the ciphertexts from those words
+int cn_l_crt_join(cn_ctx *c, const uint64_t *plain, const uint32_t *index_map, const void *tab, uint32_t P, uint32_t W, double *values, uint64_t *words, uint32_t count, uint32_t nslots);
+int cn_l_join_argmax(cn_ctx *c, const uint64_t *words, uint32_t W, int32_t *argmax, uint32_t count, uint32_t nslots);
 // seeded ciphertexts (cn_l_seeded.hip, k_seeded): `cnt` ciphertexts, poly 0 of ciphertext i at out + i * ct_stride.  expand_only: poly 1 = INTT(a) alone (cn_ct_expand);
 // else both components of a secret-key encryption - noise: the int8 polynomials [cnt][N] of k_sample_small, pt: plaintexts (null = zero) pt_stride_words apart
 struct SeededArgs {

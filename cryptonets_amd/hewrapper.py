@@ -44,6 +44,22 @@ def set_literal(on):
     global LITERAL
     LITERAL = bool(on)
 
+
+# The reply path: EncryptedSealBfvVector.Decrypt / DecryptFullPrecision and EncryptedSealBfvMatrix.Decrypt decrypt, decode and CRT-join on the device with one
+# cn_decrypt_join call when every environment's client is a device client (profiles/reply_probe.txt).  False: always the per-prime path (decrypt, download, decode,
+# join slot by slot with Python integers) - which host clients, the oracle backends and plaintext vectors take in either case.
+DEVICE_JOIN = True
+
+
+def _device_join_ok(env):
+    """may cn_decrypt_join serve this CRT environment?  Device clients on library contexts, at most 8 primes, their product below 2^255"""
+    if not DEVICE_JOIN:
+        return False
+    envs = getattr(env, "Environments", None)
+    if not envs or len(envs) > 8 or env.bigFactor >> 255:
+        return False
+    return all(hasattr(e.client, "decrypt_device") and hasattr(e.ctx, "_h") and hasattr(e.ctx, "L") for e in envs)
+
 class ClientCrypto:
     """The client-side SEAL objects of AtomicSealBfvEncryptedEnvironment.SetKeys (AtomicSealBfvVector.cs:62-74):
     KeyGenerator / Encryptor / Decryptor for ONE plaintext modulus."""
@@ -1409,12 +1425,41 @@ class EncryptedSealBfvVector:
             out.append(x)
         return out
 
+    def _device_join(self, env, signed, scale=1.0, words=False):
+        """Decrypt + Decode + JoinSplitNumbers of this vector as ONE cn_decrypt_join call (dense: every block, cut to Dim; sparse: coefficient 0 of every
+        entry), or None when the present path has to run: DEVICE_JOIN off, a plaintext vector, a host client or an oracle backend, a prime set
+        cn_decrypt_join does not take."""
+        if not self.IsEncrypted or not _device_join_ok(env):
+            return None
+        views = [v.encData for v in self.eVectors]
+        count = views[0].count
+        if any(v.count != count for v in views):
+            return None
+        from . import _native
+        dim = int(self.Dim)
+        if self.Format == EVectorFormat.dense:
+            nslots = env.Environments[0].ctx.n if count > 1 else max(1, min(dim, env.Environments[0].ctx.n))
+            coeff0 = False
+        else:
+            nslots, coeff0 = 1, True
+        r = _native.decrypt_join([e.ctx for e in env.Environments], [v.h for v in views], [v.first for v in views], count, nslots,
+                                 signed=signed, scale=scale, coeff0=coeff0, words=words, values=not words)
+        if words:
+            return [x for row in r.ints() for x in row][:dim if self.Format == EVectorFormat.dense else count]
+        return r.values.reshape(-1)[:dim if self.Format == EVectorFormat.dense else count].copy()
+
     def DecryptFullPrecision(self, env):
         env = _env_at(env, self.Limbs)
+        joined = self._device_join(env, self.IsSigned, words=True)
+        if joined is not None:
+            return joined
         return self._join([v.DecryptFullPrecision(e) for v, e in zip(self.eVectors, env.Environments)], env, self.IsSigned)
 
     def Decrypt(self, env):
         env = _env_at(env, self.Limbs)
+        joined = self._device_join(env, True, scale=self.Scale)
+        if joined is not None:
+            return joined
         ints = self._join([v._decrypt_ints(e) for v, e in zip(self.eVectors, env.Environments)], env)
         return np.array([float(x) / self.Scale for x in ints])
 
@@ -1517,9 +1562,34 @@ class EncryptedSealBfvMatrix:
                     v.Dispose()
         self.leVectors = None
 
+    def _device_join(self, env):
+        """every column decrypted, decoded and joined by ONE cn_decrypt_join call - when the columns are dense, encrypted and lie in one range of one
+        array per plaintext prime (the batched layers' form) - as the list of the columns' value arrays; else None (column by column)"""
+        cols = self.leVectors
+        if not cols or not all(c.IsEncrypted and c.Format == EVectorFormat.dense for c in cols) or not _device_join_ok(env):
+            return None
+        if any(c.Scale != cols[0].Scale or c.Dim != cols[0].Dim for c in cols):
+            return None
+        P = len(env.Environments)
+        blocks = cols[0].eVectors[0].encData.count
+        firsts = []
+        for i in range(P):
+            views = [c.eVectors[i].encData for c in cols]
+            if any(v.buf is not views[0].buf or v.count != blocks for v in views) or [v.first for v in views] != [views[0].first + j * blocks for j in range(len(cols))]:
+                return None
+            firsts.append(views[0].first)
+        from . import _native
+        n, dim = env.Environments[0].ctx.n, int(cols[0].Dim)
+        nslots = n if blocks > 1 else max(1, min(dim, n))
+        r = _native.decrypt_join([e.ctx for e in env.Environments], [cols[0].eVectors[i].encData.h for i in range(P)], firsts, blocks * len(cols), nslots,
+                                 signed=True, scale=cols[0].Scale)
+        return [v[:dim] for v in r.values.reshape(len(cols), blocks * nslots)]
+
     def Decrypt(self, env):
         env = _env_at(env, self.Limbs)
-        vecs = [v.Decrypt(env) for v in self.leVectors]
+        vecs = self._device_join(env)
+        if vecs is None:
+            vecs = [v.Decrypt(env) for v in self.leVectors]
         return np.stack(vecs, axis=0) if self.Format == EMatrixFormat.RowMajor else np.stack(vecs, axis=1)
 
     def Mul(self, v, env, ForceDenseFormat=False):

@@ -513,6 +513,27 @@ int cn_noise_poly(cn_ctx *ctx, cn_handle ct, uint32_t ci, uint32_t count, uint64
  * range, a null `host` or while a graph is recorded; count 0 returns 0.  Processes at most max(1, 2^24 / (k N)) ciphertexts per pass, so its
  * scratch stays bounded; synchronises. */
 int cn_noise_norm(cn_ctx *ctx, cn_handle ct, uint32_t ci, uint32_t count, uint64_t *host /* [count][k] */);
+/* ---- the reply path on the device: Decryptor.Decrypt + BatchEncoder.Decode + JoinSplitNumbers (EncryptedSealBfvVector.cs:381-411) of `count` ciphertexts per
+ * plaintext prime in ONE call - no plaintext and no per-prime slot array reaches the host.  ctxs[i]: the context of plaintext prime t_i, ct[i] / ci[i]: handle and
+ * first index in ctxs[i] (ci NULL = 0).
+ *   v_i[c][s]  slot s of Decode(Decrypt(ct_i[c])) in the slot order of cn_decode_batch; with CN_JOIN_COEFF0 coefficient 0 of the decrypted plaintext (the wrapper's sparse
+ *              format: nslots must be 1, no transform runs)
+ *   x          the unique integer in [0, M), M = prod t_i, with x == v_i (mod t_i) for every i; with CN_JOIN_SIGNED, x - M when 2x > M
+ *   words      x as W = cn_join_words little-endian 64-bit words, two's complement: [count][nslots][W]
+ *   values     double(x) / scale: round-to-nearest-even of the exact integer (up to 255 bits), then the IEEE division - Python's float(x) / scale: [count][nslots]
+ *   argmax[s]  the lowest c whose integer x[c][s] is largest (compared as integers, not as doubles): [nslots]
+ * Accepted: 1 <= P <= 8 contexts of one device and one N, level contexts included (their slice of the secret key), with pairwise different prime t_i and M < 2^255;
+ * size-2 and size-3 ciphertexts.  Refused with CN_ERR_ARG (a missing secret key: CN_ERR_NOKEY), nothing written: P = 0 or P > 8, equal moduli, a different N or device,
+ * nslots = 0 or > N, CN_JOIN_COEFF0 with nslots != 1, the dense form on a context without batching, all three outputs NULL, an index range outside its handle, a
+ * recording in progress on any context.  count = 0 returns 0.  Takes every context's lock (more limbs first, as cn_mod_switch), submits every context's deferred work
+ * first, runs each prime's decryption on its own context's stream into a join buffer of ctxs[0] (ordered by events, no host wait in between), the join on ctxs[0]'s
+ * stream, and synchronises once.  cn_join_words: W = ceil((bit_length(M) + 1) / 64), or CN_ERR_ARG for a list cn_decrypt_join refuses. */
+#define CN_JOIN_SIGNED (1u)
+#define CN_JOIN_COEFF0 (2u)
+int cn_join_words(cn_ctx *const *ctxs, uint32_t P);
+int cn_decrypt_join(cn_ctx *const *ctxs, uint32_t P, const cn_handle *ct, const uint32_t *ci, uint32_t count, uint32_t nslots, uint32_t flags,
+                    double scale, double *values /* [count][nslots] or NULL */, uint64_t *words /* [count][nslots][W] or NULL */,
+                    int32_t *argmax /* [nslots] or NULL */);
 
 /* ---- raw transforms (kernel benchmarks / parity tests of the NTT itself) --------------- */
 /* in-place negacyclic NTT over `limbs` limbs of N words at a device pointer; limb i uses modulus
