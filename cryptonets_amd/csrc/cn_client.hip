@@ -1,6 +1,7 @@
 // libcnhip.so host runtime (3/5): the data owner's side on the device - keys, ChaCha20 sampler, keygen, encrypt, decrypt, noise.
 #include "cn_api_shared.h"
 #include "cn_k_join.hip.h"
+#include "cn_noise_table.h"
 
 // ---------------------------------------------------------------- client side on the device
 int set_plain_key(cn_ctx *ctx, uint64_t **slot, const uint64_t *words, size_t count, size_t expect, bool is_dev, bool coeff_form) {
@@ -43,17 +44,9 @@ extern "C" int cn_get_key(cn_ctx *ctx, int which, uint64_t elt, uint64_t *host, 
     return 0;
 API_END }
 RngKey rng_key_of(const cn_ctx *ctx) { RngKey k; memcpy(k.k, ctx->rng_key, sizeof k.k); return k; }
-// thresholds of sample_noise8 (cn_dev_common.hip.h): cumulative distribution of |x|, x ~ N(0, 3.2^2) conditioned on |x| <= 19.2 (SEAL 3.2: noise_standard_deviation 3.20, noise_max_deviation 6 sigma)
+// thresholds of sample_noise8 (cn_dev_common.hip.h), computed once per process: the formula is in cn_noise_table.h
 const NoiseTab &cn_noise_table() {
-    static const NoiseTab tab = [] {
-        NoiseTab t;
-        const long double sigma = 3.2L, root2 = 1.41421356237309504880168872420969808L, norm = erfl(19.2L / (sigma * root2));
-        for (int i = 0; i < 19; i++) {
-            const long double c = erfl((long double)(i + 1) / (sigma * root2)) / norm;             // P(|x| < i + 1 | clipped)
-            t.thr[i] = c >= 1.0L ? 0x7fffffffffffffffull : (uint64_t)floorl(c * 9223372036854775808.0L);
-        }
-        return t;
-    }();
+    static const NoiseTab tab = cn_noise_table_compute();
     return tab;
 }
 // `polys` polynomials [polys][k][N] of residues: kind 0 ternary, 1 clipped normal (both drawn ONCE per coefficient into an int8 array in

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include "cn_internal.h"
 #include "cn_ntt_core.hip.h"
+#include "cn_noise_table.h"
 #include <type_traits>
 
 typedef unsigned __int128 u128;
@@ -109,8 +110,8 @@ template <int RN> struct TensorOps<ArF64T<RN>> {
 // block function, 20 rounds) as a counter-mode DRBG - 256-bit key per context (cn_set_rng_key: the data owner draws it from the OS
 // entropy source), 64-bit nonce per call (the `seed` argument of cn_keygen / cn_encrypt), 64-bit block counter made of
 // (polynomial item, stream, redraw trial, block index inside the polynomial): every block of every polynomial of every call is distinct.
-// One block (512 bits) yields 16 ternary coefficients (32 bits each: 16 two-bit rejection trials), 8 clipped-normal coefficients (four
-// Box-Muller pairs, both branches used) or 8 uniform 64-bit words; secrets and noise are drawn ONCE per coefficient into int8 arrays
+// One block (512 bits) yields 16 ternary coefficients (32 bits each: 16 two-bit rejection trials), 8 clipped-normal coefficients (one 64-bit
+// word each: sign bit + 63 bits against the thresholds of cn_noise_table.h) or 8 uniform 64-bit words; secrets and noise are drawn ONCE per coefficient into int8 arrays
 // and expanded to the k residues afterwards.
 struct RngKey { uint32_t k[8]; };
 // EncTab: per-ciphertext parameters of an encryption whose outputs are separate arrays and whose calls carried their own nonce (deferred
@@ -134,8 +135,9 @@ DEV void chacha20_block(const RngKey &key, uint64_t counter, uint64_t nonce, uin
 }
 // block counter: item (40 bits) | stream (4) | trial (4) | block index inside the polynomial (16)
 DEV uint64_t rng_counter(uint64_t item, uint32_t stream, uint32_t trial, uint32_t blk) { return (item << 24) | ((uint64_t)(stream & 15) << 20) | ((uint64_t)(trial & 15) << 16) | (blk & 0xffffu); }
-// streams: 0 = ternary (secret key, u), 1 / 2 = noise polynomials e1 / e2 (and key noise), 3 = uniform (the `a` component of keys)
-// 16 ternary coefficients {-1, 0, 1} from one block: coefficient c takes word c, two bits at a time, the first pair that is not 3
+// streams: 0 = ternary (secret key, u), 1 / 2 = noise polynomials e1 / e2 (1: key noise, the noise of cn_encrypt_symmetric), 3 = uniform (the `a` component of keys),
+// 4 = CN_STREAM_A (include/cnhip.h: the public `a` of seeded ciphertexts, under the PUBLIC seed of the call, never the context's sampler key)
+// 16 ternary coefficients {-1, 0, 1} from one block: coefficient c takes word c, two bits at a time: the LOWEST pair that is not 3, minus 1
 DEV void sample_ternary16(const RngKey &key, uint64_t nonce, uint32_t stream, uint64_t item, uint32_t blk, int8_t (&out)[16]) {
     uint32_t w[16];
     chacha20_block(key, rng_counter(item, stream, 0, blk), nonce, w);
@@ -159,7 +161,7 @@ DEV void sample_ternary16(const RngKey &key, uint64_t nonce, uint32_t stream, ui
 // noise sampler took 100 us per 1 290 polynomials, a fifth of an encryption).  One 64-bit word per coefficient: the top bit is the sign, the other 63 bits are compared with the 19
 // thresholds thr[i] = floor(2^63 P(|x| < i + 1 | |x| <= 19.2)) (cn_noise_table(), long double erf): |value| = the number of thresholds at or below it.  The same distribution
 // (P(0) = P(|x| < 1), P(+-k) = P(k <= |x| < k + 1) / 2, P(+-19) = P(19 <= |x| <= 19.2) / 2) to 2^-63, no rejection loop; a different stream than rounds 1-5 for the same seed.
-struct NoiseTab { uint64_t thr[19]; };
+// struct NoiseTab { uint64_t thr[19]; } and the formula of the table: cn_noise_table.h (host code only)
 DEV void sample_noise8(const RngKey &key, uint64_t nonce, uint32_t stream, uint64_t item, uint32_t blk, const NoiseTab &nt, int8_t (&out)[8]) {
     uint32_t w[16];
     chacha20_block(key, rng_counter(item, stream, 0, blk), nonce, w);

@@ -420,7 +420,12 @@ int cn_rowdot_batch(cn_ctx *ctx, cn_handle v, uint32_t vi, cn_handle pt, uint32_
 /* Sampler: ChaCha20 (RFC 7539 block function) in counter mode.  cn_set_rng_key installs the 256-bit key of the context (the data owner draws
  * it from the OS entropy source; default all zero = reproducible, for tests); the `seed` argument of cn_keygen / cn_encrypt is the 64-bit
  * nonce of the call - distinct calls under one key need distinct nonces (a counter or fresh entropy).  cn_set_rng_salt sets only the first
- * 64 key bits (kept for callers of the round-1 interface). */
+ * 64 key bits (kept for callers of the round-1 interface).
+ * Every polynomial drawn takes the next value of the context's item counter (block counter = item | stream | redraw trial | block, as for CN_STREAM_A
+ * below): cn_keygen RESETS it to 0 (item 0 = the secret key, 1 / 2 = the public a / noise, then two items per key entry), every other call goes on from it,
+ * and a level context has a counter of its own that starts at 0.  Calls that share a nonce are distinct only through the counter: wherever it starts again
+ * (a second cn_keygen, a level context) the nonce of an earlier call under the same key must not be used again - item 0 of stream 0 under the nonce of
+ * cn_keygen IS the secret key.  tests/sampler_model.py restates every draw; tests/test_gpu_sampler_kat.py holds the device's words to it. */
 int cn_set_rng_key(cn_ctx *ctx, const uint8_t *key32);
 int cn_set_rng_salt(cn_ctx *ctx, uint64_t salt);
 /* known-answer self-test of the generator: one raw block (16 words) for a key, the 64-bit block counter (state words 12-13) and the
