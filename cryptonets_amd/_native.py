@@ -17,7 +17,8 @@ CSRC = os.path.join(_PKG, "csrc")
 SOURCES = [os.path.join(CSRC, f) for f in (
     "cn_api.hip", "cn_eval.hip", "cn_client.hip", "cn_defer.hip", "cn_multi.hip", "cn_host.cpp", "cn_tables.cpp", "cn_l_gemm.hip", "cn_l_behz.hip",
     "cn_l_rr_u64.hip", "cn_l_rr_f64.hip", "cn_l_rr_f64l.hip", "cn_l_ks_u64.hip", "cn_l_ks_f64.hip", "cn_l_ks_f64l.hip", "cn_level.hip", "cn_l_modswitch.hip",
-    "cn_l_modswitch_f64.hip", "cn_l_noise.hip", "cn_l_seeded.hip", "cn_l_keygen.hip", "cn_l_packed.hip", "cn_l_join.hip")]
+    "cn_l_modswitch_f64.hip", "cn_l_noise.hip", "cn_l_seeded.hip", "cn_l_keygen.hip", "cn_l_packed.hip", "cn_l_join.hip",
+    "cn_l_split.hip")]
 OBJ_DIR = os.path.join(_PKG, "lib", "obj")
 
 U64P = C.POINTER(C.c_uint64)
@@ -202,6 +203,8 @@ SIGNATURES = {
     "cn_noise_norm": (C.c_int, [_CTX, _H, _u32, _u32, C.POINTER(C.c_uint64)]),
     "cn_join_words": (C.c_int, [C.POINTER(_CTX), _u32]),
     "cn_decrypt_join": (C.c_int, [C.POINTER(_CTX), _u32, C.POINTER(_H), U32P, _u32, _u32, _u32, C.c_double, C.POINTER(C.c_double), U64P, I32P]),
+    "cn_split_encode": (C.c_int, [C.POINTER(_CTX), _u32, C.c_void_p, C.c_int64, C.c_int64, _u32, _u32, _u32, C.c_double, C.POINTER(_H), U32P, C.POINTER(C.c_uint8)]),
+    "cn_split_encrypt": (C.c_int, [C.POINTER(_CTX), _u32, C.c_void_p, C.c_int64, C.c_int64, _u32, _u32, _u32, C.c_double, C.POINTER(_H), U32P, U64P]),
     "cn_ntt_forward": (C.c_int, [_CTX, C.c_void_p, _u32, C.c_int]),
     "cn_ntt_inverse": (C.c_int, [_CTX, C.c_void_p, _u32, C.c_int]),
     "cn_ct_ntt": (C.c_int, [_CTX, _H, _u32, _u32, C.c_int]),
@@ -301,6 +304,53 @@ def decrypt_join(contexts, handles, firsts, count, nslots, signed=True, scale=1.
     if rc:
         raise CnError(rc, L.cn_last_error().decode())
     return JoinResult(out_v, out_w, out_a)
+
+
+def _split_args(contexts, values, handles, firsts, transpose, coeff0):
+    """the arguments cn_split_encode and cn_split_encrypt share: values[c, s] (after `transpose`: values[s, c]) is slot s of plaintext c; float64 or int64 with any
+    numpy strides that are whole elements - the strides are passed on, no host copy is made"""
+    v = values if isinstance(values, np.ndarray) else np.asarray(values)
+    if v.dtype not in (np.float64, np.int64):
+        v = v.astype(np.float64)
+    if v.ndim == 1:
+        v = v.reshape(1, -1)
+    if transpose:
+        v = v.T
+    if v.ndim != 2 or v.strides[0] % 8 or v.strides[1] % 8:
+        raise ValueError("expected a 2-D float64 / int64 array with element-aligned strides")
+    P = len(contexts)
+    arr = (_CTX * P)(*[c._h for c in contexts])
+    hs = (_H * P)(*[int(h) for h in handles])
+    fs = None if firsts is None else (_u32 * P)(*[int(f) for f in firsts])
+    flags = (1 if v.dtype == np.int64 else 0) | (2 if coeff0 else 0)
+    return v, P, arr, hs, fs, flags
+
+
+def split_encode(contexts, values, handles, firsts=None, scale=1.0, coeff0=False, transpose=False):
+    """SplitBigNumbers + BatchEncoder.Encode of values.shape[0] plaintexts of values.shape[1] slots per plaintext prime in one call (cn_split_encode) into the plaintext
+    handles handles[i][firsts[i] : ...] of contexts[i].  float64: rint(x * scale); int64: taken as they are.  coeff0: one value per plaintext, the constant
+    polynomial (the wrapper's sparse format).  Returns the zero flags, [P, count] bool."""
+    L = lib()
+    v, P, arr, hs, fs, flags = _split_args(contexts, values, handles, firsts, transpose, coeff0)
+    count, nvalues = v.shape
+    zero = np.zeros((P, count), dtype=np.uint8)
+    rc = L.cn_split_encode(arr, P, C.c_void_p(v.ctypes.data), v.strides[0] // 8, v.strides[1] // 8, count, nvalues, flags, float(scale), hs, fs,
+                           zero.ctypes.data_as(C.POINTER(C.c_uint8)))
+    if rc:
+        raise CnError(rc, L.cn_last_error().decode())
+    return zero.astype(bool)
+
+
+def split_encrypt(contexts, values, handles, firsts, seeds, scale=1.0, coeff0=False, transpose=False):
+    """the same split and encoding followed by the public-key encryption of every plaintext under the nonce seeds[i] (cn_split_encrypt) into the size-2 ciphertext
+    handles handles[i][firsts[i] : ...] of contexts[i]"""
+    L = lib()
+    v, P, arr, hs, fs, flags = _split_args(contexts, values, handles, firsts, transpose, coeff0)
+    count, nvalues = v.shape
+    sd = (C.c_uint64 * P)(*[int(x) & (2 ** 64 - 1) for x in seeds])
+    rc = L.cn_split_encrypt(arr, P, C.c_void_p(v.ctypes.data), v.strides[0] // 8, v.strides[1] // 8, count, nvalues, flags, float(scale), hs, fs, sd)
+    if rc:
+        raise CnError(rc, L.cn_last_error().decode())
 
 
 def default_coeff_modulus(n):

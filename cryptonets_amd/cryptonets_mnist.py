@@ -220,6 +220,22 @@ def predict(channels, nslots=None):
     return _native.decrypt_join(ctxs, [c.h5 for c in channels], None, 10, n, signed=True, values=False, argmax=True).argmax
 
 
+def encrypt_images(channels, images, scale, seeds=None):
+    """The request of a batch, the mirror of predict: images [batch <= N][784], already normalised (pixel / 256), slot = image.  Feature f of every image
+    becomes ciphertext f of every channel's h_in - round(x * scale) split over the plaintext primes, encoded and encrypted on the device in ONE call
+    (cn_split_encrypt) that reads the image-major matrix as it lies.  seeds: one nonce per channel (default: the OS entropy source).  The contexts hold
+    the public key (the data owner's side: client.DeviceClient)."""
+    from . import _native
+    from .client import _entropy64
+    ctxs = [c.g for c in channels]
+    x = np.asarray(images, dtype=np.float64)
+    if x.ndim != 2 or x.shape[1] != 784 or not 1 <= x.shape[0] <= ctxs[0].n:
+        raise ValueError("images: [batch <= N][784]")
+    if seeds is None:
+        seeds = [_entropy64() for _ in channels]
+    _native.split_encrypt(ctxs, x, [c.h_in for c in channels], None, seeds, scale=scale, transpose=True)
+
+
 def constant_plaintext(n):
     def enc(v):
         p = np.zeros(n, dtype=np.uint64)

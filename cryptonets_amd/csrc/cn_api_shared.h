@@ -262,7 +262,8 @@ RngKey rng_key_of(const cn_ctx *ctx);
 int sample_poly(cn_ctx *ctx, uint64_t *dst, uint32_t polys, int kind, uint64_t seed, uint64_t stream);
 int gen_ksk(cn_ctx *ctx, const uint64_t *snew, int dbc, const uint32_t *dig, uint32_t tot, uint64_t seed, uint64_t *key, uint64_t *e);
 int adopt_ksk(cn_ctx *ctx, KsKey &slot, uint64_t *dev, size_t words);
-int encrypt_chain(cn_ctx *ctx, uint32_t cnt, const uint64_t *ptd, uint32_t pt_stride_words, uint64_t *out, uint64_t seed, const EncTab *htab);
+int encrypt_chain(cn_ctx *ctx, uint32_t cnt, const uint64_t *ptd, uint32_t pt_stride_words, uint64_t *out, uint64_t seed, const EncTab *htab, bool in_arena = false);
+size_t encrypt_scratch_bytes(const cn_ctx *ctx, uint32_t cnt, bool tab);
 int encrypt_body(cn_ctx *ctx, cn_handle pt, uint32_t pi, uint32_t pt_stride, cn_handle out, uint32_t oi, uint32_t count, uint64_t seed);
 int decrypt_phase(cn_ctx *ctx, Buffer *I, uint32_t ci, uint32_t count, uint64_t *&acc, size_t extra = 0);
 DeferQueue *cn_defer_new();

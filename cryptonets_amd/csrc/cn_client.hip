@@ -1,6 +1,6 @@
 // libcnhip.so host runtime (3/5): the data owner's side on the device - keys, ChaCha20 sampler, keygen, encrypt, decrypt, noise.
 #include "cn_api_shared.h"
-#include "cn_k_join.hip.h"
+#include "cn_k_split.hip.h"          // (includes cn_k_join.hip.h)
 #include "cn_noise_table.h"
 
 // ---------------------------------------------------------------- client side on the device
@@ -276,9 +276,14 @@ extern "C" int cn_rotation_steps(cn_ctx *ctx, int *steps, uint32_t cap, uint32_t
 API_END }
 // Encryptor.Encrypt (AtomicSealBfvVector.cs:1211,1227): (pk0 u + e1 + Delta m [+ r_t(q)], pk1 u + e2); pt = 0 encrypts zero.
 // tab != null: `cnt` encryptions whose outputs / plaintexts / nonces / items come from the table (host copy `htab`), else dense out / ptd
-int encrypt_chain(cn_ctx *ctx, uint32_t cnt, const uint64_t *ptd, uint32_t pt_stride_words, uint64_t *out, uint64_t seed, const EncTab *htab) {
+// in_arena: the caller has sized the scratch arena for the whole call (encrypt_scratch_bytes) and carved its own arrays out of it: the arena is neither reset nor grown
+size_t encrypt_scratch_bytes(const cn_ctx *ctx, uint32_t cnt, bool tab) {
+    const size_t n = ctx->hc.n, kn = (size_t)ctx->hc.k * n;
+    return al((size_t)cnt * kn * 8) + al((size_t)cnt * n) + al((size_t)cnt * 2 * n) + (tab ? al(cnt * sizeof(EncTab)) : 0) + 1024;
+}
+int encrypt_chain(cn_ctx *ctx, uint32_t cnt, const uint64_t *ptd, uint32_t pt_stride_words, uint64_t *out, uint64_t seed, const EncTab *htab, bool in_arena) {
     const uint32_t n = ctx->hc.n, k = ctx->hc.k; const size_t kn = (size_t)k * n;
-    CHECK(ensure_scratch(ctx, al((size_t)cnt * kn * 8) + al((size_t)cnt * n) + al((size_t)cnt * 2 * n) + (htab ? al(cnt * sizeof(EncTab)) : 0) + 1024));
+    if (!in_arena) CHECK(ensure_scratch(ctx, encrypt_scratch_bytes(ctx, cnt, htab != nullptr)));
     uint64_t *u = salloc<uint64_t>(ctx, (size_t)cnt * kn);
     int8_t *us = salloc<int8_t>(ctx, (size_t)cnt * n), *es = salloc<int8_t>(ctx, (size_t)cnt * 2 * n);
     EncTab *dtab = nullptr;
@@ -624,4 +629,143 @@ extern "C" int cn_decrypt_join(cn_ctx *const *ctxs, uint32_t P, const cn_handle 
     std::sort(order.begin(), order.end(), join_lock_order);
     HeldLocks locks(order);
     return decrypt_join_locked(ctxs, T, ct, ci, count, nslots, values, words, argmax);
+}
+// ---------------------------------------------------------------- the request path (include/cnhip.h: cn_split_encode / cn_split_encrypt; kernel: cn_k_split.hip.h)
+struct SplitCall {
+    const char *what; const void *values; int64_t stride_ct, stride_slot; uint32_t count, nvalues, flags; double scale;
+    const cn_handle *h; const uint32_t *first; const uint64_t *seeds; uint8_t *zero; bool encrypt;
+};
+// the checks that need no lock (N, device and t are fixed at creation)
+static int split_args_ok(cn_ctx *const *ctxs, uint32_t P, const SplitCall &a) {
+    if (!ctxs || P < 1 || P > CNJ_MAXP) return fail(CN_ERR_ARG, "%s takes 1 .. %d contexts", a.what, CNJ_MAXP);
+    for (uint32_t i = 0; i < P; i++) {
+        if (!ctxs[i]) return fail(CN_ERR_ARG, "null context at position %u", i);
+        if (ctxs[i]->hc.n != ctxs[0]->hc.n || ctxs[i]->device != ctxs[0]->device) return fail(CN_ERR_ARG, "%s: context %u has another N or device", a.what, i);
+        for (uint32_t h = 0; h < i; h++) if (ctxs[h] == ctxs[i]) return fail(CN_ERR_ARG, "%s: context %u is listed twice", a.what, i);
+        if (ctxs[i]->hc.t.q < 2 || (ctxs[i]->hc.t.q >> 62)) return fail(CN_ERR_ARG, "%s: plain modulus outside [2, 2^62)", a.what);
+    }
+    if (a.flags & ~(CSP_I64 | CSP_COEFF0)) return fail(CN_ERR_ARG, "%s: unknown flag", a.what);
+    if (!a.values || !a.h || (a.encrypt && !a.seeds)) return fail(CN_ERR_ARG, "null argument");
+    const uint32_t n = ctxs[0]->hc.n;
+    if (a.flags & CSP_COEFF0) { if (a.nvalues != 1) return fail(CN_ERR_ARG, "%s: CN_SPLIT_COEFF0 writes one coefficient (nvalues = 1)", a.what); }
+    else {
+        if (a.nvalues == 0 || a.nvalues > n) return fail(CN_ERR_ARG, "%s: 1 .. N values per plaintext", a.what);
+        for (uint32_t i = 0; i < P; i++) if (!ctxs[i]->hc.batching) return fail(CN_ERR_ARG, "plain modulus does not support batching");
+    }
+    if (a.encrypt && (ctxs[0]->hc.logn < 10 || ctxs[0]->hc.logn > 14)) return fail(CN_ERR_ARG, "device encryption needs 1024 <= N <= 16384");
+    return 0;
+}
+// elements [lo, hi] of `values` that the plaintexts [cb, cb + m) read
+static void split_extent(const SplitCall &a, uint32_t cb, uint32_t m, __int128 &lo, __int128 &hi) {
+    const __int128 c0 = (__int128)cb * a.stride_ct, c1 = (__int128)(cb + m - 1) * a.stride_ct, s1 = (__int128)(a.nvalues - 1) * a.stride_slot;
+    lo = std::min(c0, c1) + std::min<__int128>(0, s1);
+    hi = std::max(c0, c1) + std::max<__int128>(0, s1);
+}
+static int split_locked(cn_ctx *const *ctxs, uint32_t P, const SplitCall &a) {
+    const uint32_t n = ctxs[0]->hc.n, count = a.count;
+    const bool dense = !(a.flags & CSP_COEFF0);
+    for (uint32_t i = 0; i < P; i++) { cn_ctx *ctx = ctxs[i]; NOT_CAPTURING("cn_split_encode / cn_split_encrypt"); }
+    // not deferrable: every context's queued calls and published records are submitted first (a handle may come from the lock-free ring)
+    for (uint32_t i = 0; i < P; i++) CHECK(flush_all(ctxs[i]));
+    Buffer *B[CNJ_MAXP]; uint32_t first[CNJ_MAXP]; uint64_t t[CNJ_MAXP];
+    for (uint32_t i = 0; i < P; i++) {
+        cn_ctx *ctx = ctxs[i];
+        Buffer *b = getbuf(ctx, a.h[i], a.encrypt ? 0 : 1);
+        if (!b) return fail(CN_ERR_ARG, "%s: invalid handle at position %u", a.what, i);
+        if (a.encrypt && b->size != 2) return fail(CN_ERR_ARG, "%s: fresh ciphertexts have size 2", a.what);
+        first[i] = a.first ? a.first[i] : 0;
+        if (!range_ok(b, first[i], count)) return fail(CN_ERR_ARG, "index out of range");
+        B[i] = b; t[i] = ctx->hc.t.q;
+    }
+    if (a.encrypt) for (uint32_t i = 0; i < P; i++) if (!ctxs[i]->pk) return fail(CN_ERR_NOKEY, "public key not set");
+    if (!count) return 0;
+    // passes of at most max(1, 2^24 / N) plaintexts (and of one launch's grid): the arenas stay bounded whatever the count
+    const uint32_t pass = (uint32_t)std::min<size_t>(std::max<size_t>(1, NOISE_CHUNK_WORDS / n), 65536), mp = std::min(pass, count);
+    size_t stage_bytes = 0;
+    for (uint32_t cb = 0; cb < count; cb += pass) {
+        __int128 lo, hi; split_extent(a, cb, std::min(pass, count - cb), lo, hi);
+        if (hi - lo >= ((__int128)1 << 40)) return fail(CN_ERR_ARG, "%s: the strides span more than 2^40 elements in one pass", a.what);
+        stage_bytes = std::max(stage_bytes, (size_t)(hi - lo + 1) * 8);
+    }
+    cn_ctx *c0 = ctxs[0];
+    for (uint32_t i = 0; i < P; i++) if (!ctxs[i]->ev_ms) { CHECK(use(ctxs[i])); HIPCHK(hipEventCreateWithFlags(&ctxs[i]->ev_ms, hipEventDisableTiming)); }
+    CHECK(use(c0));
+    if (dense) CHECK(ensure_index_map(c0));                   // (the slot order depends on N alone)
+    // the arenas of the call.  ctxs[0]: the flags of every pass, then per pass the staged values; every context of cn_split_encrypt: per pass its plaintexts and the
+    // arrays of its own encryption.  Sized once for the largest pass, so no arena moves while another stream works in it.
+    const size_t flag_words = (size_t)P * count + 1;
+    size_t mark[CNJ_MAXP];
+    for (uint32_t i = 0; i < P; i++) {
+        const size_t own = a.encrypt ? al((size_t)mp * n * 8) + encrypt_scratch_bytes(ctxs[i], mp, false) : 0;
+        if (i == 0 || own) { CHECK(use(ctxs[i])); CHECK(ensure_scratch(ctxs[i], own + (i ? 0 : al(flag_words * 4) + al(stage_bytes) + 256))); }
+        mark[i] = ctxs[i]->soff;
+    }
+    uint32_t *dflags = salloc<uint32_t>(c0, flag_words);      // nz [P][count], then the range flag
+    if (!dflags) return fail(CN_ERR_HIP, "internal: scratch exhausted in %s", a.what);
+    mark[0] = c0->soff;
+    uint32_t *dbad = dflags + (size_t)P * count;
+    std::vector<uint32_t> hflags(flag_words);
+    const int rc = [&]() -> int {
+        CHECK(use(c0));
+        HIPCHK(hipMemsetAsync(dflags, 0, flag_words * 4, c0->stream));
+        for (uint32_t cb = 0; cb < count; cb += pass) {
+            const uint32_t m = std::min(pass, count - cb);
+            __int128 lo, hi; split_extent(a, cb, m, lo, hi);
+            uint64_t *plain[CNJ_MAXP];
+            for (uint32_t i = 0; i < P; i++) {
+                cn_ctx *ctx = ctxs[i];
+                ctx->soff = mark[i];
+                plain[i] = a.encrypt ? salloc<uint64_t>(ctx, (size_t)m * n) : B[i]->d + (size_t)(first[i] + cb) * n;
+                if (!plain[i]) return fail(CN_ERR_HIP, "internal: scratch exhausted in %s", a.what);
+                // ctxs[0]'s stream writes this context's rows: behind whatever the context's own stream still runs on them
+                if (i && ctx->stream != c0->stream) { CHECK(use(ctx)); HIPCHK(hipEventRecord(ctx->ev_ms, ctx->stream)); HIPCHK(hipStreamWaitEvent(c0->stream, ctx->ev_ms, 0)); }
+            }
+            CHECK(use(c0));
+            const size_t bytes = (size_t)(hi - lo + 1) * 8;
+            char *stage = salloc<char>(c0, bytes);
+            if (!stage) return fail(CN_ERR_HIP, "internal: scratch exhausted in %s", a.what);
+            HIPCHK(hipMemcpyAsync(stage, (const char *)a.values + (int64_t)lo * 8, bytes, hipMemcpyHostToDevice, c0->stream));
+            const void *dvalues = (const void *)((intptr_t)stage - (intptr_t)((int64_t)lo * 8));          // element (c, s) at dvalues[c stride_ct + s stride_slot]
+            CHECK(cn_l_crt_split(c0, (const char *)dvalues + (int64_t)cb * a.stride_ct * 8, a.stride_ct, a.stride_slot, m, a.nvalues, a.flags, a.scale, t, plain, P,
+                                 dense ? c0->d_index_map : nullptr, dflags + cb, count, dbad));
+            HIPCHK(hipEventRecord(c0->ev_ms, c0->stream));
+            for (uint32_t i = 0; i < P; i++) {
+                cn_ctx *ctx = ctxs[i];
+                const bool other = i && ctx->stream != c0->stream;
+                CHECK(use(ctx));
+                if (other) HIPCHK(hipStreamWaitEvent(ctx->stream, c0->ev_ms, 0));
+                if (dense) CHECK(cn_run_ntt(ctx, plain[i], m, ctx->hc.k + ctx->hc.kb, 1, 1));          // the inverse transform mod t of cn_encode_batch
+                if (a.encrypt) CHECK(encrypt_chain(ctx, m, plain[i], n, B[i]->d + (size_t)(first[i] + cb) * B[i]->item_words, a.seeds[i], nullptr, true));
+                // ctxs[0]'s stream waits for this context: the next pass reuses the arenas, and the call ends with one wait on that stream
+                if (other) { HIPCHK(hipEventRecord(ctx->ev_ms, ctx->stream)); HIPCHK(hipStreamWaitEvent(c0->stream, ctx->ev_ms, 0)); }
+            }
+        }
+        CHECK(use(c0));
+        HIPCHK(hipMemcpyAsync(hflags.data(), dflags, flag_words * 4, hipMemcpyDeviceToHost, c0->stream));
+        HIPCHK(hipStreamSynchronize(c0->stream));              // the one host wait of the call
+        return 0;
+    }();
+    if (rc) { for (uint32_t i = 0; i < P; i++) (void)hipStreamSynchronize(ctxs[i]->stream); return rc; }          // nothing of the call stays in flight on any stream
+    for (uint32_t i = 0; i < P; i++) for (uint32_t c = 0; c < count; c++) {
+        const uint8_t z = hflags[(size_t)i * count + c] ? 0 : 1;
+        if (!a.encrypt) B[i]->pt_zero[first[i] + c] = z;
+        if (a.zero) a.zero[(size_t)i * count + c] = z;
+    }
+    if (hflags[(size_t)P * count]) return fail(CN_ERR_ARG, "%s: value does not fit (NaN, infinite or 2^62 and beyond after scaling)", a.what);
+    return 0;
+}
+static int split_call(cn_ctx *const *ctxs, uint32_t P, const SplitCall &a) {
+    CHECK(split_args_ok(ctxs, P, a));
+    std::vector<cn_ctx *> order(ctxs, ctxs + P);
+    std::sort(order.begin(), order.end(), join_lock_order);      // every lock, in cn_decrypt_join's order
+    HeldLocks locks(order);
+    return split_locked(ctxs, P, a);
+}
+extern "C" int cn_split_encode(cn_ctx *const *ctxs, uint32_t P, const void *values, int64_t stride_ct, int64_t stride_slot, uint32_t count, uint32_t nvalues, uint32_t flags,
+                               double scale, const cn_handle *pt, const uint32_t *pi, uint8_t *zero) {
+    return split_call(ctxs, P, SplitCall{"cn_split_encode", values, stride_ct, stride_slot, count, nvalues, flags, scale, pt, pi, nullptr, zero, false});
+}
+extern "C" int cn_split_encrypt(cn_ctx *const *ctxs, uint32_t P, const void *values, int64_t stride_ct, int64_t stride_slot, uint32_t count, uint32_t nvalues, uint32_t flags,
+                                double scale, const cn_handle *ct, const uint32_t *ci, const uint64_t *seeds) {
+    return split_call(ctxs, P, SplitCall{"cn_split_encrypt", values, stride_ct, stride_slot, count, nvalues, flags, scale, ct, ci, seeds, nullptr, true});
 }

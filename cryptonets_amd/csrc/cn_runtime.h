@@ -342,6 +342,12 @@ int cn_l_noise_norm(cn_ctx *c, const uint64_t *c0, size_t ct_stride, const uint6
 // JoinTab on the device; values [count][nslots] doubles and words [count][nslots][W] may be null), and the arg max per slot over the ciphertexts from those words
 int cn_l_crt_join(cn_ctx *c, const uint64_t *plain, const uint32_t *index_map, const void *tab, uint32_t P, uint32_t W, double *values, uint64_t *words, uint32_t count, uint32_t nslots);
 int cn_l_join_argmax(cn_ctx *c, const uint64_t *words, uint32_t W, int32_t *argmax, uint32_t count, uint32_t nslots);
+// request path (cn_l_split.hip, cn_k_split.hip.h): `count` plaintexts of `nvalues` values each, split modulo t[0 .. P) on c's stream - element (ct, s) at
+// values[ct stride_ct + s stride_slot] (device memory, 8 bytes each: doubles, or int64 under CN_SPLIT_I64), row ct of prime i at dst[i] + ct N in the slot order of
+// index_map (position 0 under CN_SPLIT_COEFF0), zero beyond nvalues.  nz [P][nz_stride] and bad [1]: device words zeroed by the caller, OR-ed with 1 for a plaintext with
+// a non-zero coefficient / when a value does not fit.  At most 65535 x 16 plaintexts per launch.
+int cn_l_crt_split(cn_ctx *c, const void *values, int64_t stride_ct, int64_t stride_slot, uint32_t count, uint32_t nvalues, uint32_t flags, double scale,
+                   const uint64_t *t, uint64_t *const *dst, uint32_t P, const uint32_t *index_map, uint32_t *nz, uint32_t nz_stride, uint32_t *bad);
 // seeded ciphertexts (cn_l_seeded.hip, k_seeded): `cnt` ciphertexts, poly 0 of ciphertext i at out + i * ct_stride.  expand_only: poly 1 = INTT(a) alone (cn_ct_expand);
 // else both components of a secret-key encryption - noise: the int8 polynomials [cnt][N] of k_sample_small, pt: plaintexts (null = zero) pt_stride_words apart
 struct SeededArgs {

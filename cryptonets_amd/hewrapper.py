@@ -60,6 +60,50 @@ def _device_join_ok(env):
         return False
     return all(hasattr(e.client, "decrypt_device") and hasattr(e.ctx, "_h") and hasattr(e.ctx, "L") for e in envs)
 
+
+# The request path: EncryptedSealBfvVector(...) and EncryptedSealBfvFactory.GetEncryptedMatrix / GetPlainMatrix scale, round, split, encode and encrypt on the
+# device with one cn_split_encrypt / cn_split_encode call for all blocks (columns) and plaintext primes when every environment's client is a device client on a
+# library context (profiles/request_probe.txt).  False: always the host path (np.rint, one np.mod per prime, then one encode + encrypt per vector and prime) -
+# which host clients, the oracle backends, Python integers beyond int64, values of 2^62 and beyond after scaling and sparse plaintext vectors (host lists of
+# integers) take in either case.
+DEVICE_SPLIT = True
+
+
+def _device_split_ok(env, encrypt):
+    """may cn_split_encode / cn_split_encrypt serve this CRT environment?  Device clients on library contexts, at most 8 primes; encryption on the ring
+    sizes cn_encrypt takes"""
+    if not DEVICE_SPLIT:
+        return False
+    envs = getattr(env, "Environments", None)
+    if not envs or len(envs) > 8:
+        return False
+    if not all(hasattr(e.client, "encrypt_device") and hasattr(e.client, "_call_seed") and hasattr(e.ctx, "_h") and hasattr(e.ctx, "L") for e in envs):
+        return False
+    if any("encode_batch" in vars(e.ctx) for e in envs):          # a call-trace recorder wraps the context's methods (tools/call_trace.py): it records the per-context calls
+        return False
+    return not encrypt or 1024 <= envs[0].ctx.n <= 16384
+
+
+def _device_split(env, values, encrypt, coeff0, scale):
+    """values [count][nvalues] (float64 or int64, any strides) -> per environment a view of ONE fresh array of `count` ciphertexts (or plaintexts) and the zero
+    flags [P][count] (None for ciphertexts); None when a value does not fit (2^62 and beyond after scaling, NaN): the caller's host path reports or handles it"""
+    from . import _native
+    envs = env.Environments
+    ctxs = [e.ctx for e in envs]
+    views = [_Buf(c, "ct" if encrypt else "pt", values.shape[0]).view() for c in ctxs]
+    try:
+        if encrypt:
+            _native.split_encrypt(ctxs, values, [v.h for v in views], None, [e.client._call_seed() for e in envs], scale=scale, coeff0=coeff0)
+            return views, None
+        return views, _native.split_encode(ctxs, values, [v.h for v in views], None, scale=scale, coeff0=coeff0)
+    except BaseException as ex:
+        for v in views:
+            v.release()
+        if isinstance(ex, _native.CnError) and ex.code == -1 and "does not fit" in str(ex):
+            return None
+        raise
+
+
 class ClientCrypto:
     """The client-side SEAL objects of AtomicSealBfvEncryptedEnvironment.SetKeys (AtomicSealBfvVector.cs:62-74):
     KeyGenerator / Encryptor / Decryptor for ONE plaintext modulus."""
@@ -1291,6 +1335,8 @@ class EncryptedSealBfvVector:
         self.Scale = Scale
         self.IsSigned = True
         if v is not None or integers is not None:
+            if self._device_split(v, env, Scale, EncryptData, Format, integers):
+                return
             primes = [e.plainmodulusValue for e in env.Environments]
             res = None
             if integers is None:
@@ -1305,6 +1351,35 @@ class EncryptedSealBfvVector:
                 res = [np.array([x % p for x in z], dtype=np.uint64) for p in primes]
             self.eVectors = [AtomicSealBfvEncryptedVector(res[i], e, Scale=1, SignedNumbers=False, EncryptData=EncryptData, Format=Format)
                              for i, e in enumerate(env.Environments)]
+
+    def _device_split(self, v, env, Scale, EncryptData, Format, integers):
+        """the constructor's work as ONE cn_split_encrypt / cn_split_encode call for all blocks and primes (DEVICE_SPLIT); False: the host path has to do it"""
+        sparse = Format != EVectorFormat.dense
+        if not _device_split_ok(env, EncryptData) or (sparse and not EncryptData):       # (a sparse plaintext vector is a host list of integers)
+            return False
+        try:
+            x = np.asarray(v, dtype=np.float64) if integers is None else np.array([int(i) for i in integers], dtype=np.int64)
+        except OverflowError:                                                             # Python integers beyond int64
+            return False
+        if x.ndim != 1 or x.size == 0:
+            return False
+        slots = env.Environments[0].SlotCount
+        if sparse:
+            x2 = x.reshape(-1, 1)
+        elif x.size <= slots or x.size % slots == 0:
+            x2 = x.reshape(-1, min(x.size, slots))
+        else:                                                                             # a partial last block: zero padded, like the host path's blocks
+            x2 = np.zeros(-(-x.size // slots) * slots, dtype=x.dtype)
+            x2[:x.size] = x
+            x2 = x2.reshape(-1, slots)
+        done = _device_split(env, x2, EncryptData, sparse, Scale)
+        if done is None:
+            return False
+        views, zero = done
+        self.eVectors = [AtomicSealBfvEncryptedVector._new(Scale=1, IsSigned=False, Format=Format, Dim=int(x.size), encData=vw if EncryptData else None,
+                                                           plainDense=None if EncryptData else vw, plainZero=None if EncryptData else [bool(z) for z in zero[i]])
+                         for i, vw in enumerate(views)]
+        return True
 
     @classmethod
     def _of(cls, vecs, Scale=1.0):
@@ -2096,7 +2171,23 @@ class EncryptedSealBfvFactory:
 
     def _matrix(self, m, format, scale, encrypt):
         m = np.asarray(m, dtype=np.float64)
-        rows = m.T if format == EMatrixFormat.ColumnMajor else m
+        rows = m.T if format == EMatrixFormat.ColumnMajor else m                 # (a view: the column-major request reaches the device as transposed strides)
+        env = self.referenceEnvironment
+        if rows.ndim == 2 and rows.shape[0] and 0 < rows.shape[1] <= env.Environments[0].SlotCount and _device_split_ok(env, encrypt):
+            # ONE call for the whole matrix: all vectors of a prime lie in one array, in order, each a view of it - the form the batched layers produce and
+            # EncryptedSealBfvMatrix.ModSwitchTo / Decrypt take without a gather
+            done = _device_split(env, rows, encrypt, False, scale)
+            if done is not None:
+                views, zero = done
+                vecs = []
+                for j in range(rows.shape[0]):
+                    atoms = [AtomicSealBfvEncryptedVector._new(Scale=1, IsSigned=False, Format=EVectorFormat.dense, Dim=int(rows.shape[1]),
+                                                               encData=vw.sub(j) if encrypt else None, plainDense=None if encrypt else vw.sub(j),
+                                                               plainZero=None if encrypt else [bool(zero[i][j])]) for i, vw in enumerate(views)]
+                    vecs.append(EncryptedSealBfvVector._of(atoms, scale))
+                for vw in views:
+                    vw.release()                                                 # (the columns' views keep the arrays alive)
+                return EncryptedSealBfvMatrix(vecs, env, CopyVectors=False, Format=format)
         vecs = [EncryptedSealBfvVector(r, self.referenceEnvironment, scale, EncryptData=encrypt, Format=EVectorFormat.dense) for r in rows]
         return EncryptedSealBfvMatrix(vecs, self.referenceEnvironment, CopyVectors=False, Format=format)
 

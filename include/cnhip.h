@@ -539,6 +539,34 @@ int cn_join_words(cn_ctx *const *ctxs, uint32_t P);
 int cn_decrypt_join(cn_ctx *const *ctxs, uint32_t P, const cn_handle *ct, const uint32_t *ci, uint32_t count, uint32_t nslots, uint32_t flags,
                     double scale, double *values /* [count][nslots] or NULL */, uint64_t *words /* [count][nslots][W] or NULL */,
                     int32_t *argmax /* [nslots] or NULL */);
+/* ---- the request path on the device: SplitBigNumbers (EncryptedSealBfvVector.cs:352-365) + BatchEncoder.Encode [+ Encryptor.Encrypt] (AtomicSealBfvVector.cs:1114-1232) of
+ * `count` plaintexts per plaintext prime in ONE call - one upload of the values, no per-prime residue array on the host.  ctxs[i]: the context of plaintext prime t_i,
+ * pt[i] / pi[i] (ct[i] / ci[i]): handle and first index in ctxs[i] (pi / ci NULL = 0).  For plaintext c < count and slot s < nvalues the input element is
+ * values[c * stride_ct + s * stride_slot]; the strides count elements of 8 bytes (a row-major [image][feature] matrix is read as it lies, no host transpose).
+ *   w          doubles (the default): r = rint(x * scale) - one IEEE double multiply, then round to nearest even; the call is refused when any r is NaN, infinite or
+ *              |r| >= 2^62; w = (int64) r.  CN_SPLIT_I64: the elements are int64_t and w is the element (every int64, INT64_MIN included; scale is ignored)
+ *   v_i[c][s]  w mod t_i as the representative in [0, t_i)
+ *   plaintext  c of context i: BatchEncoder.Encode of the slots v_i[c][0 .. nvalues), zero beyond, in the slot order and with the transform of cn_encode_batch (equal
+ *              words); with CN_SPLIT_COEFF0 the constant polynomial v_i[c][0] (the wrapper's sparse format: nvalues must be 1, no transform runs)
+ *   zero       zero[i * count + c] = 1 when every coefficient of that plaintext is zero; cn_split_encode sets the handles' zero flags (what cn_mul_plain refuses
+ *              by) to the same exact values
+ *   cn_split_encrypt   ct[i][ci[i] + c] = cn_encrypt of that plaintext under the nonce seeds[i]: the words of cn_encode_batch + cn_encrypt(pt, 0, 1, ct[i], ci[i], count,
+ *              seeds[i]) on a context in the same sampler state, and the item counter advances as in that call.  Public-key encryption only: the symmetric, compact
+ *              and packed forms take cn_split_encode and then their own per-context call.  The plaintexts live in each context's scratch.
+ * Accepted: 1 <= P <= 8 different contexts of one device and one N, level contexts included; the t_i need not differ.  Refused with CN_ERR_ARG before anything is
+ * enqueued: P = 0 or P > 8, a different N or device, nvalues > N, nvalues = 0 in the dense form, CN_SPLIT_COEFF0 with nvalues != 1, the dense form on a context without
+ * batching, a null values / pt / ct / seeds, an index range outside its handle, a ciphertext array of size 3, a recording in progress on any context, cn_split_encrypt
+ * with N < 1024 (cn_encrypt's own limit).  cn_split_encrypt without a public key: CN_ERR_NOKEY.  count = 0 returns 0.  A value out of range is found on the device:
+ * the call returns CN_ERR_ARG ("value does not fit") and the destinations are unspecified, as for cn_ct_upload_packed's bad residues.
+ * Takes every context's lock (the order of cn_decrypt_join), submits every context's deferred work first, uploads the strided extent of the values once into ctxs[0]'s
+ * scratch, splits on ctxs[0]'s stream into all P destinations, runs each prime's inverse transform mod t and encryption on its own context's stream (ordered by events,
+ * no host wait in between), in passes of at most max(1, 2^24 / N) plaintexts, and synchronises once. */
+#define CN_SPLIT_I64    (1u)   /* values are int64_t and are taken as they are; scale is ignored */
+#define CN_SPLIT_COEFF0 (2u)   /* the wrapper's sparse format: the value becomes coefficient 0 of a constant plaintext; nvalues must be 1, no transform runs */
+int cn_split_encode(cn_ctx *const *ctxs, uint32_t P, const void *values, int64_t stride_ct, int64_t stride_slot, uint32_t count, uint32_t nvalues, uint32_t flags,
+                    double scale, const cn_handle *pt, const uint32_t *pi /* NULL = 0 */, uint8_t *zero /* [P][count] or NULL */);
+int cn_split_encrypt(cn_ctx *const *ctxs, uint32_t P, const void *values, int64_t stride_ct, int64_t stride_slot, uint32_t count, uint32_t nvalues, uint32_t flags,
+                     double scale, const cn_handle *ct, const uint32_t *ci /* NULL = 0 */, const uint64_t *seeds /* [P] */);
 
 /* ---- raw transforms (kernel benchmarks / parity tests of the NTT itself) --------------- */
 /* in-place negacyclic NTT over `limbs` limbs of N words at a device pointer; limb i uses modulus
