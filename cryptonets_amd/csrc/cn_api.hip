@@ -95,14 +95,7 @@ int range_ok(const Buffer *b, uint32_t first, uint32_t count, uint32_t stride) {
 int cn_run_ntt(cn_ctx *c, uint64_t *data, uint32_t limbs, uint32_t base_off, uint32_t nmod, int inverse) {
     if (!limbs) return 0;
     uint32_t n = c->hc.n;
-    bool f64 = c->opt.f64;
-    for (uint32_t m = base_off; m < base_off + nmod; m++) f64 = f64 && c->hc.f64ok[m];
-    bool light = f64;
-    for (uint32_t m = base_off; m < base_off + nmod && light; m++) {
-        uint64_t q = m < c->hc.k ? c->hc.q[m].q : (m < c->hc.k + c->hc.kb ? c->hc.bsk[m - c->hc.k].q : c->hc.t.q);
-        if (q >> 44) light = false;
-    }
-    bool done = !c->opt.legacy_ntt && rr_ops[light ? POL_F64L : (f64 ? POL_F64 : POL_U64)]->ntt(c, data, limbs, base_off, nmod, inverse);
+    bool done = !c->opt.legacy_ntt && rr_ops[cn_policy(cn_mod_range(c->hc, base_off, nmod), c->opt.f64)]->ntt(c, data, limbs, base_off, nmod, inverse);
     if (!done) {
         uint32_t nt = std::min<uint32_t>(512, n / 2);
         hipLaunchKernelGGL(k_ntt, dim3(limbs), dim3(nt), (size_t)n * 8, c->stream, data, c->dc, base_off, nmod, inverse);
@@ -448,7 +441,7 @@ extern "C" int cn_ctx_wait_for(cn_ctx *ctx_, cn_ctx *other) {
 extern "C" size_t cn_key_words(cn_ctx *ctx, int which) { return (size_t)(which ? ctx->hc.gk_tot : ctx->hc.rl_tot) * ctx->ctw2; }
 
 // does this context keep its key-switch keys as FP64 images (the FP64 key-switch kernels read doubles)?
-bool keys_as_f64(const cn_ctx *ctx) { return ctx->opt.f64 && ctx->hc.q_f64 && !ctx->opt.legacy_ntt && ctx->hc.logn >= 10 && ctx->hc.logn <= 14; }
+bool keys_as_f64(const cn_ctx *ctx) { return ctx->opt.f64 && cn_mod_range(ctx->hc, 0, ctx->hc.k).f64ok && rr_kernels(ctx); }
 // coeff_form: the words are coefficient-form polynomials [..][k][N]; the device transforms them with its own tables (cn_load_key, form 1)
 int set_key(cn_ctx *ctx, KsKey &slot, const uint64_t *words, size_t count, size_t expect, int is_dev, bool coeff_form) {
     if (!words || count != expect) return fail(CN_ERR_ARG, "key has %zu words, expected %zu", count, expect);

@@ -4,6 +4,7 @@
 //   cn_client.hip  the data owner's side on the device: keys, sampler, keygen, encrypt, decrypt, noise
 //   cn_defer.hip   deferred submission of per-ciphertext calls (queue, hazards, flush) and the consumer side of the lock-free submission ring
 //   cn_multi.hip   the key broadcast between contexts (RCCL)
+// Which arithmetic policy a modulus range takes and which ring sizes have the register-radix kernels is decided in cn_policy.h (cn_mod_range, cn_policy, cn_rr_size).
 // Everything here is internal: the C ABI is include/cnhip.h.  The element-wise kernels (cn_k_elem.hip.h) have internal linkage - every unit that launches one
 // carries its own copy.
 #pragma once
@@ -24,6 +25,7 @@ struct DOp; struct DeferQueue; struct GemmPlan; struct GemmArith; struct Tab2; s
 
 static const RrOps *const rr_ops[3] = {&cn_rr_u64, &cn_rr_f64, &cn_rr_f64l};
 static const KsOps *const ks_ops[3] = {&cn_ks_u64, &cn_ks_f64, &cn_ks_f64l};
+inline bool rr_kernels(const cn_ctx *c, uint32_t max_logn = 14) { return !c->opt.legacy_ntt && cn_rr_size(c->hc.logn, max_logn); }   // the context runs register-radix kernels
 enum { DOP_GEMM1 = 0, DOP_ADD, DOP_SUB, DOP_ADDPLAIN, DOP_SUBPLAIN, DOP_MULRELIN, DOP_ENCRYPT,
        DOP_COPY, DOP_MULPLAIN, DOP_ROT, DOP_ROTADD, DOP_COLS, DOP_COLSADD, DOP_SUMSLOTS, DOP_TYPES };      // DOP_COPY .. : staged (gather / batched call / scatter) at flush time
 struct DOp {
@@ -178,8 +180,8 @@ int launch_gemm_plan(cn_ctx *ctx, const GemmPlan &P, const char *tables, const v
 bool square_gemm_ctx_ok(cn_ctx *ctx);
 bool square_gemm_fused_ok(cn_ctx *ctx, const GemmPlan &P);
 bool run_intt_tensor(cn_ctx *c, const uint64_t *A, const uint64_t *B, uint64_t *D, uint32_t cnt, uint32_t base_off, uint32_t Lm, bool lazy);
-bool square_fused_ok(cn_ctx *c, uint32_t base_off, uint32_t Lm, bool &light);
-void run_square_fused(cn_ctx *c, const uint64_t *A, size_t astride, const uint64_t *const *atab, uint64_t *D, uint32_t cnt, uint32_t base_off, uint32_t Lm, bool light);
+bool square_fused_ok(cn_ctx *c, uint32_t base_off, uint32_t Lm);
+void run_square_fused(cn_ctx *c, const uint64_t *A, size_t astride, const uint64_t *const *atab, uint64_t *D, uint32_t cnt, uint32_t base_off, uint32_t Lm);
 bool aux_stream_ready(cn_ctx *ctx);
 // "sq_halves": Multiply + Relinearize of a batch software-pipelined in parts over the context's two streams (round 6): part i on stream i % 2, its Multiply behind the Multiply
 // of the part before it (event), its key switch behind its own Multiply (stream order) - [mul 0][ks 0 | mul 1][ks 1 | mul 2][ks 2]: the HBM-bound base extension / floor and
@@ -408,8 +410,7 @@ template <class ROW, class TAP> static void pack_gemm_weights(cn_ctx *ctx, uint3
 template <class ROW, class TAP> static bool gemm_one_limb(cn_ctx *ctx, const GemmArith &ar, uint32_t G, uint32_t M, uint32_t K, ROW row, TAP tap_ok) {
     static const bool on = !(getenv("CN_GEMM_ONE_LIMB") && !atoi(getenv("CN_GEMM_ONE_LIMB")));
     if (!on || !ar.small || ar.bits > 49 || K > ar.lazy) return false;
-    uint64_t qmax = 0; for (uint32_t j = 0; j < ctx->hc.k; j++) qmax = std::max(qmax, ctx->hc.q[j].q);
-    const uint64_t room = (1ull << 53) / qmax;                 // sum |w| + 1 <= room
+    const uint64_t room = (1ull << 53) / cn_mod_range(ctx->hc, 0, ctx->hc.k).qmax;   // sum |w| + 1 <= room
     const uint64_t t = ctx->hc.t.q;
     for (uint32_t g = 0; g < G; g++) for (uint32_t m = 0; m < M; m++) {
         const uint64_t *wr = row(g, m);

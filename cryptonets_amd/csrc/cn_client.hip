@@ -185,7 +185,7 @@ extern "C" int cn_keygen_galois(cn_ctx *ctx, uint64_t seed, const uint64_t *galo
     if (!cnt) return 0;
     if (!galois_elts) return fail(CN_ERR_ARG, "null argument");
     const uint32_t n = ctx->hc.n, k = ctx->hc.k, logn = ctx->hc.logn, tot = ctx->hc.gk_tot;
-    if (logn < 10 || logn > 14) return fail(CN_ERR_ARG, "cn_keygen_galois needs 1024 <= N <= 16384");
+    if (!cn_rr_size(logn)) return fail(CN_ERR_ARG, "cn_keygen_galois needs 1024 <= N <= 16384");
     for (uint32_t g = 0; g < cnt; g++) {
         if (!(galois_elts[g] & 1) || galois_elts[g] >= 2ull * n) return fail(CN_ERR_ARG, "invalid Galois element %llu", (unsigned long long)galois_elts[g]);
         for (uint32_t h = 0; h < g; h++) if (galois_elts[h] == galois_elts[g]) return fail(CN_ERR_ARG, "Galois element %llu is listed twice", (unsigned long long)galois_elts[g]);
@@ -294,11 +294,9 @@ int encrypt_chain(cn_ctx *ctx, uint32_t cnt, const uint64_t *ptd, uint32_t pt_st
     hipLaunchKernelGGL(k_sample_small, dim3((unsigned)(((uint64_t)cnt * (n / 16) + 255) / 256)), dim3(256), 0, ctx->stream, us, n, 0, 1u, cnt, key, seed, 0u, item0, (const EncTab *)dtab, cn_noise_table());
     hipLaunchKernelGGL(k_sample_small, dim3((unsigned)(((uint64_t)cnt * 2 * (n / 8) + 255) / 256)), dim3(256), 0, ctx->stream, es, n, 1, 2u, cnt, key, seed, 1u, item0, (const EncTab *)dtab, cn_noise_table());
     if (!htab) ctx->rng_item += cnt;
-    const bool f64 = ctx->opt.f64 && ctx->hc.q_f64;
+    CnModRange qr = cn_mod_range(ctx->hc, 0, k);
     if (ctx->opt.enc_fused && !ctx->opt.legacy_ntt) {                 // one kernel behind the samplers: u stays in registers between its transform and the two components
-        uint64_t qmax = 0; for (uint32_t j = 0; j < k; j++) qmax = std::max(qmax, ctx->hc.q[j].q);
-        const int pol = f64 ? ((qmax >> 44) ? POL_F64 : POL_F64L) : POL_U64;
-        if (rr_ops[pol]->enc_fused(ctx, us, ptd, pt_stride_words, out, cnt, es, dtab)) {
+        if (rr_ops[cn_policy(qr, ctx->opt.f64)]->enc_fused(ctx, us, ptd, pt_stride_words, out, cnt, es, dtab)) {
             HIPCHK(hipGetLastError()); launch_count(ctx, 3);
             ctx->st.ntt_forward_limbs += (uint64_t)cnt * k;          // (counted like the three-launch chain)
             return 0;
@@ -307,7 +305,8 @@ int encrypt_chain(cn_ctx *ctx, uint32_t cnt, const uint64_t *ptd, uint32_t pt_st
     hipLaunchKernelGGL(k_expand_small, dim3(cnt * k * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, us, u, ctx->dc, ctx->chunks);
     HIPCHK(hipGetLastError()); launch_count(ctx, 3);
     CHECK(cn_run_ntt(ctx, u, cnt * k, 0, k, 0));
-    if (!rr_ops[f64 ? POL_F64 : POL_U64]->enc_tail(ctx, u, ptd, pt_stride_words, out, cnt, es, dtab)) return fail(CN_ERR_ARG, "unsupported size");
+    qr.light = false;                         // k_encrypt_tail exists for ArU64 and ArF64 only (RR_ENC_TAIL is not defined for the f64l unit): a light range takes ArF64 here
+    if (!rr_ops[cn_policy(qr, ctx->opt.f64)]->enc_tail(ctx, u, ptd, pt_stride_words, out, cnt, es, dtab)) return fail(CN_ERR_ARG, "unsupported size");
     HIPCHK(hipGetLastError()); launch_count(ctx);
     return 0;
 }
@@ -319,7 +318,7 @@ int encrypt_body(cn_ctx *ctx, cn_handle pt, uint32_t pi, uint32_t pt_stride, cn_
     NOT_CAPTURING("cn_encrypt (a replayed graph would reuse its randomness)"); GETCT(O, out, 2);
     if (!ctx->pk) return fail(CN_ERR_NOKEY, "public key not set");
     if (!range_ok(O, oi, count)) return fail(CN_ERR_ARG, "index out of range");
-    if (ctx->hc.logn < 10 || ctx->hc.logn > 14) return fail(CN_ERR_ARG, "device encryption needs 1024 <= N <= 16384");
+    if (!cn_rr_size(ctx->hc.logn)) return fail(CN_ERR_ARG, "device encryption needs 1024 <= N <= 16384");
     const uint64_t *ptd = nullptr;
     if (pt) { Buffer *P = getbuf(ctx, pt, 1); if (!P || !range_ok(P, pi, pt_stride ? count : 1, pt_stride ? pt_stride : 1)) return fail(CN_ERR_ARG, "invalid plaintext range"); ptd = P->d + (size_t)pi * ctx->hc.n; }
     if (!count) return 0;
@@ -339,7 +338,7 @@ extern "C" int cn_encrypt_zero_new(cn_ctx *ctx, uint64_t seed, cn_handle *out) {
     LOCK_ONLY; NOT_CAPTURING("cn_encrypt_zero_new (a replayed graph would reuse its randomness)");
     if (!out) return fail(CN_ERR_ARG, "null argument");
     if (!ctx->pk) return fail(CN_ERR_NOKEY, "public key not set");
-    if (ctx->hc.logn < 10 || ctx->hc.logn > 14) return fail(CN_ERR_ARG, "device encryption needs 1024 <= N <= 16384");
+    if (!cn_rr_size(ctx->hc.logn)) return fail(CN_ERR_ARG, "device encryption needs 1024 <= N <= 16384");
     cn_handle h = 0;
     CHECK(alloc_buf(ctx, 0, 1, 2, &h));
     if (ctx->defer.load(std::memory_order_relaxed) == 2) ready_refill(ctx);          // (the ring of ready handles had run dry)
@@ -430,7 +429,7 @@ API_END }
 static int seeded_args_ok(cn_ctx *ctx, const Buffer *B, uint32_t first, uint32_t count, const uint8_t *a_seed32, uint64_t a_item0) {
     if (!a_seed32) return fail(CN_ERR_ARG, "null seed");
     if (!range_ok(B, first, count)) return fail(CN_ERR_ARG, "index out of range");
-    if (ctx->hc.logn < 10 || ctx->hc.logn > 14) return fail(CN_ERR_ARG, "seeded ciphertexts need 1024 <= N <= 16384");
+    if (!cn_rr_size(ctx->hc.logn)) return fail(CN_ERR_ARG, "seeded ciphertexts need 1024 <= N <= 16384");
     if (a_item0 >> 40 || (a_item0 + count) >> 40) return fail(CN_ERR_ARG, "a_item0 + count exceeds the 40 item bits of the block counter");
     return 0;
 }
@@ -652,7 +651,7 @@ static int split_args_ok(cn_ctx *const *ctxs, uint32_t P, const SplitCall &a) {
         if (a.nvalues == 0 || a.nvalues > n) return fail(CN_ERR_ARG, "%s: 1 .. N values per plaintext", a.what);
         for (uint32_t i = 0; i < P; i++) if (!ctxs[i]->hc.batching) return fail(CN_ERR_ARG, "plain modulus does not support batching");
     }
-    if (a.encrypt && (ctxs[0]->hc.logn < 10 || ctxs[0]->hc.logn > 14)) return fail(CN_ERR_ARG, "device encryption needs 1024 <= N <= 16384");
+    if (a.encrypt && !cn_rr_size(ctxs[0]->hc.logn)) return fail(CN_ERR_ARG, "device encryption needs 1024 <= N <= 16384");
     return 0;
 }
 // elements [lo, hi] of `values` that the plaintexts [cb, cb + m) read

@@ -627,7 +627,7 @@ int flush_encrypt_group(cn_ctx *ctx, const std::vector<const DOp *> &ops) {
 // the weighted sums of folded zero encryptions (cn_defer_flush), added onto the outputs of the scalar products `gemms` (launched just before): the samplers draw
 // u, e1, e2 of every folded encryption exactly as flush_encrypt_group would have (its nonce, its item), k_encrypt_fold does the rest
 bool zero_fold_ok(cn_ctx *ctx) {
-    return ctx->pk && ctx->opt.enc_fused && !ctx->opt.legacy_ntt && ctx->opt.f64 && ctx->hc.q_f64 && ctx->hc.logn >= 10 && ctx->hc.logn <= 13;
+    return ctx->pk && ctx->opt.enc_fused && rr_kernels(ctx, 13) && ctx->opt.f64 && cn_mod_range(ctx->hc, 0, ctx->hc.k).f64ok;
 }
 int flush_zero_folds(cn_ctx *ctx, DeferQueue *q, const std::vector<const DOp *> &gemms) {
     const uint32_t n = ctx->hc.n;
@@ -651,8 +651,8 @@ int flush_zero_folds(cn_ctx *ctx, DeferQueue *q, const std::vector<const DOp *> 
     const RngKey key = rng_key_of(ctx);
     hipLaunchKernelGGL(k_sample_small, dim3((unsigned)(((uint64_t)cnt * (n / 16) + 255) / 256)), dim3(256), 0, ctx->stream, us, n, 0, 1u, cnt, key, 0ull, 0u, 0ull, (const EncTab *)dtab, cn_noise_table());
     hipLaunchKernelGGL(k_sample_small, dim3((unsigned)(((uint64_t)cnt * 2 * (n / 8) + 255) / 256)), dim3(256), 0, ctx->stream, es, n, 1, 2u, cnt, key, 0ull, 1u, 0ull, (const EncTab *)dtab, cn_noise_table());
-    uint64_t qmax = 0; for (uint32_t j = 0; j < ctx->hc.k; j++) qmax = std::max(qmax, ctx->hc.q[j].q);
-    if (!rr_ops[(qmax >> 44) ? POL_F64 : POL_F64L]->enc_fold(ctx, us, es, dfo, dft, (uint32_t)fo.size())) return fail(CN_ERR_ARG, "internal: zero-encryption fold without a kernel");
+    const int pol = cn_policy(cn_mod_range(ctx->hc, 0, ctx->hc.k), true);       // zero_fold_ok held when the folds were queued: the pick is between the two FP64 policies
+    if (!rr_ops[pol]->enc_fold(ctx, us, es, dfo, dft, (uint32_t)fo.size())) return fail(CN_ERR_ARG, "internal: zero-encryption fold without a kernel");
     HIPCHK(hipGetLastError()); launch_count(ctx, 3);
     ctx->st.ntt_forward_limbs += (uint64_t)fo.size() * ctx->hc.k; ctx->st.ntt_inverse_limbs += (uint64_t)fo.size() * 2 * ctx->hc.k;
     return 0;
@@ -972,7 +972,7 @@ int ring_exec(cn_ctx *ctx, const SubRec &r) {
         Buffer *O = ctx->bufs.find(r.out);
         if (!O || O->kind != 0 || O->size != 2) return fail(CN_ERR_ARG, "invalid ciphertext handle");
         if (!ctx->pk) return fail(CN_ERR_NOKEY, "public key not set");
-        if (ctx->hc.logn < 10 || ctx->hc.logn > 14) return fail(CN_ERR_ARG, "device encryption needs 1024 <= N <= 16384");
+        if (!cn_rr_size(ctx->hc.logn)) return fail(CN_ERR_ARG, "device encryption needs 1024 <= N <= 16384");
         return defer_encrypt(ctx, nullptr, 0, O, 0, 1, r.arg);
     }
     default: return fail(CN_ERR_ARG, "internal: submission record of type %u", r.type);

@@ -68,9 +68,7 @@ int mul_plain_fused(cn_ctx *ctx, Buffer *A, uint32_t ai, bool a_bcast, Buffer *P
     uint64_t *o = O->d + oi * O->item_words;
     const uint64_t *src = A->d + ai * A->item_words;
     // one input ciphertext broadcast over the outputs: it must survive until the last block has read it
-    bool f64 = ctx->opt.f64, light = true;
-    for (uint32_t m = 0; m < k; m++) { f64 = f64 && ctx->hc.f64ok[m]; if (ctx->hc.q[m].q >> 44) light = false; }
-    const int pol = f64 && light ? POL_F64L : (f64 ? POL_F64 : POL_U64);
+    const int pol = cn_policy(cn_mod_range(ctx->hc, 0, k), ctx->opt.f64);
     if (a_bcast && pstride && count >= 4 && ctx->opt.mp_bcast) {      // one ciphertext x many plaintexts: transform the ciphertext once, the plaintexts inside the product kernel
         uint64_t *ctn = nx ? nx->ctn : nullptr;
         if (!nx) { CHECK(ensure_scratch(ctx, al(A->item_words * 8))); ctn = salloc<uint64_t>(ctx, A->item_words); }
@@ -102,7 +100,7 @@ int mul_plain_fused(cn_ctx *ctx, Buffer *A, uint32_t ai, bool a_bcast, Buffer *P
     ctx->st.PlainMultiplication += count;
     return 0;
 }
-bool mul_plain_takes_bcast(cn_ctx *ctx, uint32_t count) { return ctx->opt.mp_fused && ctx->opt.mp_bcast && !ctx->opt.legacy_ntt && ctx->hc.logn >= 10 && ctx->hc.logn <= 14 && count >= 4; }
+bool mul_plain_takes_bcast(cn_ctx *ctx, uint32_t count) { return ctx->opt.mp_fused && ctx->opt.mp_bcast && rr_kernels(ctx) && count >= 4; }
 int mul_plain_impl(cn_ctx *ctx, Buffer *A, uint32_t ai, bool a_bcast, Buffer *P, uint32_t pi, uint32_t pstride, Buffer *O, uint32_t oi, uint32_t count,
                           const BcastNext *nx) {
     if (!range_ok(A, ai, a_bcast ? 1 : count) || !range_ok(O, oi, count) || !range_ok(P, pi, pstride ? count : 1, pstride ? pstride : 1))
@@ -112,7 +110,7 @@ int mul_plain_impl(cn_ctx *ctx, Buffer *A, uint32_t ai, bool a_bcast, Buffer *P,
         return fail(CN_ERR_ARG, "multiply_plain: input and output ranges overlap partially (use the same range or disjoint ranges)");
     const uint32_t n = ctx->hc.n, k = ctx->hc.k, npt = pstride ? count : 1;
     for (uint32_t c = 0; c < npt; c++) if (P->pt_zero[pi + c * pstride]) return fail(CN_ERR_ZERO, "plain cannot be zero");
-    if (ctx->opt.mp_fused && !ctx->opt.legacy_ntt && ctx->hc.logn >= 10 && ctx->hc.logn <= 14) return mul_plain_fused(ctx, A, ai, a_bcast, P, pi, pstride, O, oi, count, nx);
+    if (ctx->opt.mp_fused && rr_kernels(ctx)) return mul_plain_fused(ctx, A, ai, a_bcast, P, pi, pstride, O, oi, count, nx);
     if (nx) return fail(CN_ERR_ARG, "internal: chained row-dot batch outside the fused product");
     CHECK(ensure_scratch(ctx, al((size_t)npt * k * n * 8)));
     uint64_t *lift = salloc<uint64_t>(ctx, (size_t)npt * k * n);
@@ -176,12 +174,12 @@ bool gemm_weights_small(cn_ctx *ctx, const uint64_t *W, size_t count) {
     return true;
 }
 GemmArith gemm_arith(cn_ctx *ctx, bool weights_small) {
-    uint64_t qmax = 0; for (uint32_t j = 0; j < ctx->hc.k; j++) qmax = std::max(qmax, ctx->hc.q[j].q);
-    const int bits = 64 - __builtin_clzll(qmax);
+    const CnModRange qr = cn_mod_range(ctx->hc, 0, ctx->hc.k);
+    const int bits = qr.bits;
     GemmArith g;
     g.bits = bits;
     g.small = weights_small && ctx->opt.f64 && bits <= 49;       // the kernel folds its limb sums with exact-FP64 modular arithmetic (q < 2^49.4)
-    g.two = bits <= 44;                                          // 2 limbs of 22 bits, else 3 limbs of 17 bits
+    g.two = qr.light;                                            // 2 limbs of 22 bits, else 3 limbs of 17 bits
     if (g.small) g.lazy = g.two ? 1024u : 32768u;                // terms whose limb products (< 2^42 / 2^37) still sum exactly below 2^52
     else g.lazy = (2 * bits >= 127) ? 1u : (uint32_t)std::min<uint64_t>(1u << 20, 1ull << (127 - 2 * bits));   // products of two values < q_max in 128 bits
     return g;
@@ -426,31 +424,20 @@ API_END }
 // tensor product fused into the inverse transform (register-radix sizes only); returns false when the caller must fall back
 // lazy: D leaves as lazy-FP64 hand-off words for k_behz_floor_f64<.., true> (the caller checked cn_behz_lazy: every modulus takes an FP64 policy)
 bool run_intt_tensor(cn_ctx *c, const uint64_t *A, const uint64_t *B, uint64_t *D, uint32_t cnt, uint32_t base_off, uint32_t Lm, bool lazy) {
-    if (c->opt.legacy_ntt || c->hc.logn < 10 || c->hc.logn > 14) return false;
-    bool f64 = c->opt.f64, light = true;
-    for (uint32_t m = base_off; m < base_off + Lm; m++) {
-        f64 = f64 && c->hc.f64ok[m];
-        uint64_t q = m < c->hc.k ? c->hc.q[m].q : c->hc.bsk[m - c->hc.k].q;
-        if (q >> 44) light = false;
-    }
-    if (lazy && !f64) return false;
-    bool ok = rr_ops[f64 && light ? POL_F64L : (f64 ? POL_F64 : POL_U64)]->intt_tensor(c, A, B, D, cnt, base_off, Lm, lazy);
+    if (!rr_kernels(c)) return false;
+    const int pol = cn_policy(cn_mod_range(c->hc, base_off, Lm), c->opt.f64);
+    if (lazy && pol == POL_U64) return false;
+    bool ok = rr_ops[pol]->intt_tensor(c, A, B, D, cnt, base_off, Lm, lazy);
     if (ok) { launch_count(c); c->st.ntt_inverse_limbs += (uint64_t)cnt * 3 * Lm; }
     return ok;
 }
 // squaring: forward transforms, tensor and inverse transforms of one (ciphertext, limb) in ONE kernel (FP64 policies)
-bool square_fused_ok(cn_ctx *c, uint32_t base_off, uint32_t Lm, bool &light) {
-    if (!c->opt.sq_fused || c->opt.legacy_ntt || !c->opt.f64 || c->hc.logn < 10 || c->hc.logn > 14) return false;
-    light = true;
-    for (uint32_t m = base_off; m < base_off + Lm; m++) {
-        if (!c->hc.f64ok[m]) return false;
-        uint64_t q = m < c->hc.k ? c->hc.q[m].q : c->hc.bsk[m - c->hc.k].q;
-        if (q >> 44) light = false;
-    }
-    return true;
+bool square_fused_ok(cn_ctx *c, uint32_t base_off, uint32_t Lm) {
+    return c->opt.sq_fused && c->opt.f64 && rr_kernels(c) && cn_mod_range(c->hc, base_off, Lm).f64ok;
 }
-void run_square_fused(cn_ctx *c, const uint64_t *A, size_t astride, const uint64_t *const *atab, uint64_t *D, uint32_t cnt, uint32_t base_off, uint32_t Lm, bool light) {
-    rr_ops[light ? POL_F64L : POL_F64]->square_fused(c, A, astride, atab, D, cnt, base_off, Lm);
+// (the caller asked square_fused_ok: the range is on an FP64 policy, the pick here is between the two)
+void run_square_fused(cn_ctx *c, const uint64_t *A, size_t astride, const uint64_t *const *atab, uint64_t *D, uint32_t cnt, uint32_t base_off, uint32_t Lm) {
+    rr_ops[cn_policy(cn_mod_range(c->hc, base_off, Lm), true)]->square_fused(c, A, astride, atab, D, cnt, base_off, Lm);
     launch_count(c);
     c->st.ntt_forward_limbs += (uint64_t)cnt * 2 * Lm; c->st.ntt_inverse_limbs += (uint64_t)cnt * 3 * Lm;
 }
@@ -487,8 +474,7 @@ int do_multiply(cn_ctx *ctx, const uint64_t *a, uint32_t astride, const uint64_t
     const bool square = atab ? atab == btab : (a == b && astride == bstride);
     // squarings on the FP64 path: one fused kernel per base does forward transforms, tensor and inverse transforms; its q side reads the
     // input ciphertexts in place, so k_behz_extend only has to produce the Bsk limbs
-    bool lq = false, lb = false;
-    const bool fused = square && ctx->hc.behz_f64 && square_fused_ok(ctx, 0, k, lq) && square_fused_ok(ctx, k, kb, lb);
+    const bool fused = square && ctx->hc.behz_f64 && square_fused_ok(ctx, 0, k) && square_fused_ok(ctx, k, kb);
     uint64_t *aq = fused ? nullptr : salloc<uint64_t>(ctx, (size_t)cnt * 2 * k * n), *ab = salloc<uint64_t>(ctx, (size_t)cnt * 2 * kb * n);
     uint64_t *bq = aq, *bb = ab;
     if (!square) { bq = salloc<uint64_t>(ctx, (size_t)cnt * 2 * k * n); bb = salloc<uint64_t>(ctx, (size_t)cnt * 2 * kb * n); }
@@ -500,8 +486,8 @@ int do_multiply(cn_ctx *ctx, const uint64_t *a, uint32_t astride, const uint64_t
     // FP64 policy - the fused squaring kernels always (`fused` implies it), k_intt_tensor when asked; the element-wise fall-back writes canonical words
     bool lazy = cn_behz_lazy(ctx);
     if (fused) {
-        run_square_fused(ctx, a, (size_t)astride * 2 * k * n, atab, dq, cnt, 0, k, lq);
-        run_square_fused(ctx, ab, (size_t)2 * kb * n, nullptr, db, cnt, k, kb, lb);
+        run_square_fused(ctx, a, (size_t)astride * 2 * k * n, atab, dq, cnt, 0, k);
+        run_square_fused(ctx, ab, (size_t)2 * kb * n, nullptr, db, cnt, k, kb);
     } else {
     CHECK(cn_run_ntt(ctx, aq, cnt * 2 * k, 0, k, 0)); CHECK(cn_run_ntt(ctx, ab, cnt * 2 * kb, k, kb, 0));
     if (!square) { CHECK(cn_run_ntt(ctx, bq, cnt * 2 * k, 0, k, 0)); CHECK(cn_run_ntt(ctx, bb, cnt * 2 * kb, k, kb, 0)); }
@@ -547,8 +533,7 @@ uint32_t ks_wide_max_blocks() {               // (ciphertext, limb) blocks up to
 // the variant do_keyswitch takes for `cnt` ciphertexts: 0 = the fused kernel, 1 / 2 = two launches (KsArgs::mode)
 int ks_planned_mode(cn_ctx *ctx, uint32_t cnt, int galois) {
     const uint32_t k = ctx->hc.k, tot_dig = galois ? ctx->hc.gk_tot : ctx->hc.rl_tot;
-    const bool rr = !ctx->opt.legacy_ntt && ctx->hc.logn >= 10 && ctx->hc.logn <= 14;
-    if (!(rr && (ctx->opt.ks_wide > 0 || (ctx->opt.ks_wide < 0 && cnt * k <= KS_WIDE_MAX_BLOCKS)))) return 0;
+    if (!(rr_kernels(ctx) && (ctx->opt.ks_wide > 0 || (ctx->opt.ks_wide < 0 && cnt * k <= KS_WIDE_MAX_BLOCKS)))) return 0;
     // N = 16384: 1024-thread workgroups cannot hold two accumulator sets without spilling -> per-digit only
     const int mode = ctx->opt.ks_wide == 2 || (ctx->opt.ks_wide < 0 && cnt * k > KS_DIGIT_MAX_BLOCKS && ctx->hc.logn < 14) ? 2 : 1;
     return (size_t)cnt * (mode == 2 ? k : tot_dig) * ctx->ctw2 * 8 > ctx->smax ? 0 : mode;
@@ -561,14 +546,14 @@ int do_keyswitch(cn_ctx *ctx, const uint64_t *target, size_t tstride, const uint
                         const KsKey &key, uint64_t *out, uint32_t cnt, int galois, const uint64_t *extra, size_t xstride,
                         uint64_t *const *out_tab, uint32_t perm_elt, const KsItem *items, uint32_t next_elt, uint64_t *next_out, const double *dig) {
     const uint32_t n = ctx->hc.n, k = ctx->hc.k, tot_dig = galois ? ctx->hc.gk_tot : ctx->hc.rl_tot;
-    uint64_t qmax = 0; for (uint32_t j = 0; j < k; j++) qmax = std::max(qmax, ctx->hc.q[j].q);
-    const int bits = 64 - __builtin_clzll(qmax);
+    const CnModRange qr = cn_mod_range(ctx->hc, 0, k);
+    const int bits = qr.bits, pol = cn_policy(qr, key.f64);          // by the form the key was loaded in (keys_as_f64 then), not by the "f64" option now
     KsArgs a{target, tstride, add0, add1, astride, key.d, out, cnt, galois, extra, xstride,
              key.f64 ? (bits >= 50 ? 1u : (1u << std::min(10, 50 - bits))) : 0xffffffffu,     // lazy FP64 accumulators: |term| <= 2.1 q, sum below 2^52
              0, out_tab};
     if (ctx->opt.ks_xcd == 1) a.xcd_cts = cnt & ~7u;
     else if (ctx->opt.ks_xcd == 2) a.xcd_cts = 0x80000000u;
-    const bool rr = !ctx->opt.legacy_ntt && ctx->hc.logn >= 10 && ctx->hc.logn <= 14;                // register-radix kernels available
+    const bool rr = rr_kernels(ctx);
     a.mode = ks_planned_mode(ctx, cnt, galois);
     if (a.mode) CHECK(ensure_ks_part(ctx, (size_t)cnt * (a.mode == 2 ? k : tot_dig) * ctx->ctw2 * 8));
     a.perm_elt = perm_elt; a.items = items;
@@ -580,20 +565,17 @@ int do_keyswitch(cn_ctx *ctx, const uint64_t *target, size_t tstride, const uint
     if (pair) {                                                                                      // N = 16384: both 8192-point halves of a limb in one workgroup, one launch
         CHECK(ensure_ks_part(ctx, (size_t)cnt * ctx->ctw2 * 8));
         a.xcd_cts = ctx->opt.ks_xcd == 1 ? (cnt & ~7u) : 0u;
-        ks_ops[bits <= 44 ? POL_F64L : POL_F64]->pair14(ctx, a);
+        ks_ops[pol]->pair14(ctx, a);
     } else if (a.mode == 0 && rr && key.f64 && ctx->hc.logn == 14 && ctx->hc.twdh && ctx->opt.ks_split14) {   // ... as two workgroups per limb + a combining pass (rounds 1-4; A/B)
         CHECK(ensure_ks_part(ctx, (size_t)cnt * ctx->ctw2 * 8));
-        ks_ops[bits <= 44 ? POL_F64L : POL_F64]->split14(ctx, a);
+        ks_ops[pol]->split14(ctx, a);
         hipLaunchKernelGGL(k_ks_combine14, dim3(cnt * 2 * k * (n / 512)), dim3(256), 0, ctx->stream, (const uint64_t *)ctx->ks_part, add0, add1, astride, out, ctx->dc,
                            extra, xstride, out_tab);
         launch_count(ctx);
     } else {
-        bool done = false;
-        if (key.f64) {
-            done = rr && ks_ops[bits <= 44 ? POL_F64L : POL_F64]->launch(ctx, a);
-            if (!done) return fail(CN_ERR_ARG, "internal: FP64 key without FP64 kernel");
-        } else if (rr) done = ks_ops[POL_U64]->launch(ctx, a);
-        if (!done) {                          // radix-2 LDS fallback (N < 1024, legacy_ntt): no fused accumulator -> one element-wise add behind it
+        const bool done = rr && ks_ops[pol]->launch(ctx, a);
+        if (!done && key.f64) return fail(CN_ERR_ARG, "internal: FP64 key without FP64 kernel");
+        if (!done) {                        // radix-2 LDS fallback (N < 1024, legacy_ntt): no fused accumulator -> one element-wise add behind it
             // The accumulator may be the result's own array (SumAllSlots adds in place): the key switch then writes into the key-switch arena
             // (unused by this path) and the add reads it beside the untouched accumulator.  (Writing `out` first doubled the key switch there.)
             if (extra) {
@@ -622,7 +604,7 @@ int do_keyswitch(cn_ctx *ctx, const uint64_t *target, size_t tstride, const uint
     return 0;
 }
 bool ks_pair14_ok(cn_ctx *ctx, uint32_t cnt, int galois, const KsKey &key) {
-    return ctx->opt.ks_pair14 && ctx->opt.ks_split14 && !ctx->opt.legacy_ntt && ctx->hc.logn == 14 && ctx->hc.twdh && key.f64 && ks_planned_mode(ctx, cnt, galois) == 0;
+    return ctx->opt.ks_pair14 && ctx->opt.ks_split14 && rr_kernels(ctx) && ctx->hc.logn == 14 && ctx->hc.twdh && key.f64 && ks_planned_mode(ctx, cnt, galois) == 0;
 }
 uint32_t chunk_for(cn_ctx *ctx, size_t per_ct, uint32_t count) {
     size_t c = std::max<size_t>(1, ctx->smax / per_ct);
@@ -710,9 +692,7 @@ int mul_relin_body(cn_ctx *ctx, cn_handle a, uint32_t ai, uint32_t astride, cn_h
 // register-radix kernels up to N = 8192 and the decomposition is the plain one; anything else takes the two separate steps inside the same call.
 // (square_gemm_ctx_ok: everything but the plan - the deferred queue asks it before it holds the relinearisation of queued squarings back, cn_defer.hip)
 bool square_gemm_ctx_ok(cn_ctx *ctx) {
-    if (!ctx->opt.f64 || ctx->opt.legacy_ntt || ctx->hc.logn < 10 || ctx->hc.logn > 13 || ctx->hc.ks_xi || !ctx->rlk.f64) return false;
-    for (uint32_t m = 0; m < ctx->hc.k; m++) if (!ctx->hc.f64ok[m]) return false;
-    return true;
+    return ctx->opt.f64 && rr_kernels(ctx, 13) && !ctx->hc.ks_xi && ctx->rlk.f64 && cn_mod_range(ctx->hc, 0, ctx->hc.k).f64ok;
 }
 bool square_gemm_fused_ok(cn_ctx *ctx, const GemmPlan &P) { return P.dig && square_gemm_ctx_ok(ctx); }
 extern "C" int cn_square_gemm(cn_ctx *ctx, cn_handle plan, cn_handle in, uint32_t ii, cn_handle out, uint32_t oi) { TWO_LIMBS("cn_square_gemm"); API_BODY
@@ -776,9 +756,8 @@ static bool mul_sum_fused_ok(cn_ctx *ctx, uint32_t K) {
     if (dbc < 1 || dbc > 31) return false;
     const unsigned __int128 s = (unsigned __int128)K * ((1ull << dbc) - 1);
     if (s >= ((unsigned __int128)1 << 52)) return false;
-    uint64_t qmax = 0;
+    const uint64_t qmax = cn_mod_range(ctx->hc, 0, ctx->hc.k).qmax;
     for (uint32_t j = 0; j < ctx->hc.k; j++) {
-        qmax = std::max(qmax, ctx->hc.q[j].q);
         if (s >= ctx->hc.q[j].q / 2) return false;
         if (ctx->hc.rl_dig[j] > PRODUCT_SUM_MAX_DIGITS) return false;
     }

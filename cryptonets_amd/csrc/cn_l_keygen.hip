@@ -23,9 +23,9 @@ template <class AR> static int by_size(cn_ctx *c, const KskGenArgs &a) {
 // the policy of the context's coefficient moduli, chosen like the encryption's (encrypt_chain)
 int cn_l_ksk_gen(cn_ctx *c, const KskGenArgs &a) {
     if (!a.elts || !a.tot) return 0;
-    if (c->opt.f64 && c->hc.q_f64) {
-        uint64_t qmax = 0; for (uint32_t j = 0; j < c->hc.k; j++) qmax = qmax > c->hc.q[j].q ? qmax : c->hc.q[j].q;
-        return (qmax >> 44) ? by_size<ArF64>(c, a) : by_size<ArF64L>(c, a);
+    switch (cn_policy(cn_mod_range(c->hc, 0, c->hc.k), c->opt.f64)) {
+        case POL_F64L: return by_size<ArF64L>(c, a);
+        case POL_F64: return by_size<ArF64>(c, a);
     }
     return by_size<ArU64>(c, a);
 }

@@ -127,15 +127,11 @@ static bool pair14(cn_ctx *c, const KsArgs &a0) {
         // accumulator starts from) stay below 11.8 q.  The generic bound of do_keyswitch (2.1 q per term, sum below 2^52) allows 2 at 49 bits: a recentring of
         // both accumulator sets every other digit, 2 % of the kernel's FP64 instructions at the reference's N = 16384 parameters.
         KsArgs a = a0;
-        {
-            uint64_t qm = 0; for (uint32_t j = 0; j < c->hc.k; j++) qm = std::max(qm, c->hc.q[j].q);
-            const int bits = 64 - __builtin_clzll(qm);
-            if (bits >= 45 && bits <= 49) a.accmax = std::max(a.accmax, 1u << (52 - bits));
-        }
+        const CnModRange qr = cn_mod_range(c->hc, 0, c->hc.k);
+        if (!qr.light && qr.bits <= 49) a.accmax = std::max(a.accmax, 1u << (52 - qr.bits));
         // one digit per source limb that covers the limb (the reference's N = 16384 parameter sets, dbc 60): the digit is the word itself
         const int dbc = a.galois ? c->hc.gdbc : c->hc.dbc;
-        uint64_t qmax = 0; for (uint32_t j = 0; j < c->hc.k; j++) qmax = std::max(qmax, c->hc.q[j].q);
-        const bool whole = (a.galois ? c->hc.gk_tot : c->hc.rl_tot) == c->hc.k && dbc < 64 && (qmax >> dbc) == 0;
+        const bool whole = (a.galois ? c->hc.gk_tot : c->hc.rl_tot) == c->hc.k && dbc < 64 && (qr.qmax >> dbc) == 0;
         if (c->hc.ks_xi) { if (whole) launch_pair14<true, true>(c, a); else launch_pair14<true, false>(c, a); }
         else { if (whole) launch_pair14<false, true>(c, a); else launch_pair14<false, false>(c, a); }
         return true;

@@ -119,7 +119,7 @@ template <int L> static void l_enc_fused(cn_ctx *c, const int8_t *us, const uint
     }
 }
 static bool enc_fused(cn_ctx *c, const int8_t *us, const uint64_t *pt, uint32_t pts, uint64_t *out, uint32_t cnt, const int8_t *noise, const void *tab) {
-    if (c->hc.logn > 13) return false;
+    if (!cn_rr_size(c->hc.logn, 13)) return false;
     BY_SIZE(l_enc_fused, c, us, pt, pts, out, cnt, noise, tab)
 }
 // weighted sums of fresh zero encryptions folded onto scalar-product outputs (k_encrypt_fold; FP64 policies, N <= 8192)
@@ -129,7 +129,7 @@ template <int L> static void l_enc_fold(cn_ctx *c, const int8_t *us, const int8_
                            (const FoldOut *)fout, (const FoldTerm *)terms);
 }
 static bool enc_fold(cn_ctx *c, const int8_t *us, const int8_t *noise, const void *fout, const void *terms, uint32_t outputs) {
-    if (!kF64 || c->hc.logn > 13) return false;
+    if (!kF64 || !cn_rr_size(c->hc.logn, 13)) return false;
     BY_SIZE(l_enc_fold, c, us, noise, fout, terms, outputs)
 }
 #ifndef __HIP_DEVICE_COMPILE__      // host-side table (in the device pass a const global would be emitted as device data)

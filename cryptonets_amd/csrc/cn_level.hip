@@ -93,8 +93,7 @@ static int mod_switch_locked(cn_ctx *src, cn_handle in, uint32_t ii, uint32_t co
     if (I->size != O->size || (I->size != 2 && I->size != 3)) return fail(CN_ERR_ARG, "cn_mod_switch: ciphertext sizes %u and %u (both 2 or both 3)", I->size, O->size);
     if (!range_ok(I, ii, count) || !range_ok(O, oi, count)) return fail(CN_ERR_ARG, "index out of range");
     // the FP64 form needs the "f64" option and every modulus of the source chain below 2^49 (the target's are a prefix)
-    bool f64 = src->opt.f64 && dst->opt.f64, ran_f64 = false;
-    for (uint32_t j = 0; j < a.k; j++) f64 = f64 && a.f64ok[j];
+    bool f64 = src->opt.f64 && dst->opt.f64 && cn_mod_range(a, 0, a.k).f64ok, ran_f64 = false;
     if (!count) return 0;
     // ordering without a host wait: dst's stream waits for everything submitted to src (the writers of `in`), runs the switch behind its own earlier
     // work (the readers and writers of `out`), and src's stream waits for the switch (later writers of `in`)

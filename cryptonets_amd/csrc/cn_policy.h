@@ -1,0 +1,30 @@
+// The two decisions every launch starts from, taken here and nowhere else: the arithmetic policy of a modulus range and whether a ring size has the
+// register-radix kernels.  Host-only and free of HIP: a plain C++ compiler builds it (tests/cpp/policy_table.cpp).
+#pragma once
+#include "cn_internal.h"
+
+enum { POL_U64 = 0, POL_F64 = 1, POL_F64L = 2 };       // ArU64 (Shoup, any modulus), ArF64 (< 2^49.4), ArF64L (<= 44 bits: no forward recentring)
+
+// Moduli [base_off, base_off + nmod) in the order of the twiddle tables: m < k is q_m, k <= m < k + kb is bsk_(m-k), k + kb is the plain modulus t.  The unit of
+// decision is the range, not the context: c3 takes ArF64L for its q limbs and for t, ArF64 for its 49-bit BEHZ auxiliary base
+struct CnModRange {
+    bool f64ok;        // every modulus has its FP64 tables (DevConsts::f64ok: below 2^49, and t only when batching)
+    bool light;        // no modulus has a bit at or above bit 44
+    int bits;          // bit length of qmax (0: empty range)
+    uint64_t qmax;     // the largest modulus
+};
+inline CnModRange cn_mod_range(const DevConsts &hc, uint32_t base_off, uint32_t nmod) {
+    CnModRange r{true, true, 0, 0};
+    for (uint32_t m = base_off; m < base_off + nmod; m++) {
+        const uint64_t q = m < hc.k ? hc.q[m].q : (m < hc.k + hc.kb ? hc.bsk[m - hc.k].q : hc.t.q);
+        r.f64ok = r.f64ok && hc.f64ok[m];
+        if (q > r.qmax) r.qmax = q;
+    }
+    r.light = !(r.qmax >> 44);
+    r.bits = r.qmax ? 64 - __builtin_clzll(r.qmax) : 0;
+    return r;
+}
+// use_f64: the "f64" option as it stands now - or, for a key switch, the form its key was loaded in (KsKey::f64)
+inline int cn_policy(const CnModRange &r, bool use_f64) { return !(use_f64 && r.f64ok) ? POL_U64 : (r.light ? POL_F64L : POL_F64); }
+// the ring sizes of the register-radix kernels: 1024 <= N <= 16384, or N <= 8192 (max_logn = 13) for the kernels that stop there
+inline bool cn_rr_size(uint32_t logn, uint32_t max_logn = 14) { return logn >= 10 && logn <= max_logn; }

@@ -3,7 +3,7 @@
 // register-radix kernels alone are ~180 instantiations (5 transform sizes x 3 arithmetic policies x 12 kernels).
 #pragma once
 #include "../../include/cnhip.h"
-#include "cn_internal.h"
+#include "cn_policy.h"
 #include "cn_submit.h"
 #include <hip/hip_runtime.h>
 #include <atomic>
@@ -242,9 +242,7 @@ struct cn_ctx {
     bool ms_f64 = false;
 };
 
-// ---------------------------------------------------------------- kernel launchers (cn_l_*.hip)
-enum { POL_U64 = 0, POL_F64 = 1, POL_F64L = 2 };       // ArU64 (Shoup, any modulus), ArF64 (< 2^49.4), ArF64L (<= 44 bits: no forward recentring)
-
+// ---------------------------------------------------------------- kernel launchers (cn_l_*.hip); the tables of RrOps / KsOps are indexed by cn_policy (cn_policy.h)
 // One key switch of `cnt` ciphertexts: out[ct] = (add0[ct], add1[ct]) + KeySwitch(target[ct]) (+ extra[ct] - the fused accumulator of
 // the cn_*_add entry points).  target / add0 / add1 / extra are strided per ciphertext (in words); out is dense size-2, or - out_tab -
 // one address per ciphertext (deferred per-ciphertext calls whose results live in separate arrays).
