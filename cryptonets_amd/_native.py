@@ -18,7 +18,7 @@ SOURCES = [os.path.join(CSRC, f) for f in (
     "cn_api.hip", "cn_eval.hip", "cn_client.hip", "cn_defer.hip", "cn_multi.hip", "cn_host.cpp", "cn_tables.cpp", "cn_l_gemm.hip", "cn_l_behz.hip",
     "cn_l_rr_u64.hip", "cn_l_rr_f64.hip", "cn_l_rr_f64l.hip", "cn_l_ks_u64.hip", "cn_l_ks_f64.hip", "cn_l_ks_f64l.hip", "cn_level.hip", "cn_l_modswitch.hip",
     "cn_l_modswitch_f64.hip", "cn_l_noise.hip", "cn_l_seeded.hip", "cn_l_keygen.hip", "cn_l_packed.hip", "cn_l_join.hip",
-    "cn_l_split.hip")]
+    "cn_l_split.hip", "cn_l_diag.hip")]
 OBJ_DIR = os.path.join(_PKG, "lib", "obj")
 
 U64P = C.POINTER(C.c_uint64)
@@ -180,6 +180,7 @@ SIGNATURES = {
     "cn_rotate_columns_add": (C.c_int, [_CTX, _H, _u32, _H, _u32, _H, _u32, _u32]),
     "cn_sum_slots": (C.c_int, [_CTX, _H, _u32, _u32, _u32]),
     "cn_rowdot_batch": (C.c_int, [_CTX, _H, _u32, _H, _u32, _u32, _u32, _H, _u32]),
+    "cn_mul_plain_sum": (C.c_int, [_CTX, _H, _u32, _H, _u32, U32P, U32P, _u32, _H, _u32]),
     "cn_set_rng_salt": (C.c_int, [_CTX, C.c_uint64]),
     "cn_set_rng_key": (C.c_int, [_CTX, C.c_char_p]),
     "cn_rng_selftest": (C.c_int, [_CTX, C.c_char_p, C.c_uint64, C.c_uint64, U32P]),
@@ -705,6 +706,15 @@ class Context:
     def rowdot_batch(self, v, vi, pt, pi, rows, length, out, oi):
         """out[oi + r] = SumAllSlots(v[vi] * pt[pi + r], length) for r < rows"""
         self._chk(self.L.cn_rowdot_batch(self._h, v, vi, pt, pi, rows, length, out, oi))
+
+    def mul_plain_sum(self, ct, ci, pt, pi, grp_off, ct_idx, out, oi):
+        """out[oi + g] = sum_{e in [grp_off[g], grp_off[g + 1])} MultiplyPlain(ct[ci + ct_idx[e]], pt[pi + e]) for g < len(grp_off) - 1: the words of mul_plain per
+        term followed by add_many, in one kernel on the register-radix sizes (cn_mul_plain_sum)"""
+        go = np.ascontiguousarray(grp_off, dtype=np.uint32).reshape(-1)
+        ix = np.ascontiguousarray(ct_idx, dtype=np.uint32).reshape(-1)
+        if go.size < 1 or int(go[-1]) != ix.size:
+            raise ValueError("mul_plain_sum: grp_off has one entry per group plus one and ends at len(ct_idx)")
+        self._chk(self.L.cn_mul_plain_sum(self._h, ct, ci, pt, pi, go.ctypes.data_as(U32P), ix.ctypes.data_as(U32P), go.size - 1, out, oi))
 
     def rotate_columns_add(self, src, ii, acc, ai, out, oi, count=1):
         self._chk(self.L.cn_rotate_columns_add(self._h, src, ii, acc, ai, out, oi, count))

@@ -286,6 +286,7 @@ int ctx_init(cn_ctx *c, uint32_t n, uint32_t k, int device, std::vector<uint64_t
         CHECK(set_ks_attr<8>(lds)); CHECK(set_ks_attr<16>(lds));
     }
     for (int pol = 0; pol < 3; pol++) { CHECK(rr_ops[pol]->set_attrs(c->hc.logn, lds)); CHECK(ks_ops[pol]->set_attrs(c->hc.logn, lds)); }
+    CHECK(cn_l_diag_set_attrs(c->hc.logn, lds));
     return 0;
 }
 extern "C" int cn_ctx_destroy(cn_ctx *ctx) {

@@ -1214,6 +1214,83 @@ extern "C" int cn_rowdot_batch(cn_ctx *ctx, cn_handle v, uint32_t vi, cn_handle 
     if (length == 1) return 0;
     return sum_slots_impl(ctx, O, oi, rows, length);
 API_END }
+// out[oi + g] = sum over the terms e of group g of MultiplyPlain(ct[ci + ct_idx[e]], pt[pi + e]) (include/cnhip.h).  Register-radix sizes: the distinct
+// ciphertexts transformed once into scratch (like `ctn` of the row-dot batch), then ONE launch of k_mul_plain_sum; other sizes: cn_mul_plain per term into a temporary
+// and AddMany per group.
+extern "C" int cn_mul_plain_sum(cn_ctx *ctx, cn_handle ct, uint32_t ci, cn_handle pt, uint32_t pi, const uint32_t *grp_off, const uint32_t *ct_idx, uint32_t G,
+                                cn_handle out, uint32_t oi) { API_BODY
+    LOCK; GETCT(A, ct, 2); GETCT(O, out, 2); GETPT(P, pt);
+    if (!grp_off || !ct_idx) return fail(CN_ERR_ARG, "null argument");
+    if (!G) return fail(CN_ERR_ARG, "cn_mul_plain_sum of an empty list");
+    if (grp_off[0]) return fail(CN_ERR_ARG, "cn_mul_plain_sum: grp_off[0] must be 0");
+    uint32_t maxlen = 0;
+    for (uint32_t g = 0; g < G; g++) {
+        if (grp_off[g + 1] <= grp_off[g]) return fail(CN_ERR_ARG, "cn_mul_plain_sum: group %u is empty", g);
+        maxlen = std::max(maxlen, grp_off[g + 1] - grp_off[g]);
+    }
+    const uint32_t E = grp_off[G];
+    if (!range_ok(O, oi, G) || !range_ok(P, pi, E) || ci >= A->count) return fail(CN_ERR_ARG, "index out of range");
+    for (uint32_t e = 0; e < E; e++) {
+        if (ct_idx[e] >= A->count - ci) return fail(CN_ERR_ARG, "ciphertext index out of range in term %u", e);
+        if (A == O && ci + ct_idx[e] >= oi && ci + ct_idx[e] < oi + G) return fail(CN_ERR_ARG, "cn_mul_plain_sum cannot overwrite a ciphertext it reads");
+    }
+    for (uint32_t e = 0; e < E; e++) if (P->pt_zero[pi + e]) return fail(CN_ERR_ZERO, "plain cannot be zero");
+    const uint32_t n = ctx->hc.n, k = ctx->hc.k;
+    const CnModRange qr = cn_mod_range(ctx->hc, 0, k);
+    const int pol = cn_policy(qr, ctx->opt.f64);
+    if (!(ctx->opt.mp_fused && rr_kernels(ctx) && cn_l_mul_plain_sum_kernel(pol, ctx->hc.logn))) {      // compose the existing calls
+        cn_handle tmp = 0;
+        CHECK(alloc_buf(ctx, 0, maxlen, 2, &tmp));
+        int rc = 0;
+        std::vector<uint32_t> ident(maxlen);
+        for (uint32_t i = 0; i < maxlen; i++) ident[i] = i;
+        for (uint32_t g = 0; g < G && !rc; g++) {
+            const uint32_t len = grp_off[g + 1] - grp_off[g];
+            Buffer *T = getbuf(ctx, tmp, 0);                                      // (the handle table may have moved)
+            A = getbuf(ctx, ct, 0); O = getbuf(ctx, out, 0); P = getbuf(ctx, pt, 1);
+            for (uint32_t i = 0; i < len && !rc; i++) rc = mul_plain_impl(ctx, A, ci + ct_idx[grp_off[g] + i], false, P, pi + grp_off[g] + i, 1, T, i, 1);
+            if (rc) break;
+            if ((rc = ensure_scratch(ctx, al((size_t)len * 4)))) break;
+            uint32_t *didx;
+            if ((rc = upload_tmp(ctx, ident.data(), len, &didx))) break;
+            hipLaunchKernelGGL(k_add_many, dim3(2 * k * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, T->d, didx, len, T->item_words, O->d + (size_t)(oi + g) * O->item_words, ctx->dc,
+                               ctx->chunks);
+            if (hipGetLastError() != hipSuccess) rc = fail(CN_ERR_HIP, "launch of k_add_many failed");
+            launch_count(ctx);
+        }
+        if (!rc) { ctx->st.AddMany += G; ctx->st.AddManyItemCount += E; }
+        const int rf = free_body(ctx, tmp);
+        return rc ? rc : rf;
+    }
+    // the distinct ciphertexts, in order of first appearance -> slots of the NTT-form scratch copy
+    std::vector<uint32_t> slot(E), src;
+    {
+        std::unordered_map<uint32_t, uint32_t> seen;
+        for (uint32_t e = 0; e < E; e++) {
+            auto it = seen.find(ct_idx[e]);
+            if (it == seen.end()) { it = seen.emplace(ct_idx[e], (uint32_t)src.size()).first; src.push_back(ct_idx[e]); }
+            slot[e] = it->second;
+        }
+    }
+    const uint32_t D = (uint32_t)src.size();
+    CHECK(ensure_scratch(ctx, al((size_t)D * A->item_words * 8) + al((size_t)(G + 1) * 4) + al((size_t)E * 4)));
+    uint64_t *ctn = salloc<uint64_t>(ctx, (size_t)D * A->item_words);
+    if (!ctn) return fail(CN_ERR_HIP, "internal: scratch exhausted in cn_mul_plain_sum");
+    uint32_t *dgo, *dslot;
+    CHECK(upload_tmp(ctx, grp_off, (size_t)G + 1, &dgo)); CHECK(upload_tmp(ctx, slot.data(), E, &dslot));
+    for (uint32_t s = 0; s < D;) {                                                // runs of neighbouring ciphertexts travel in one copy (baby steps: one run)
+        uint32_t r = 1;
+        while (s + r < D && src[s + r] == src[s] + r) r++;
+        HIPCHK(hipMemcpyAsync(ctn + (size_t)s * A->item_words, A->d + (size_t)(ci + src[s]) * A->item_words, (size_t)r * A->item_words * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        s += r;
+    }
+    CHECK(cn_run_ntt(ctx, ctn, D * 2 * k, 0, k, 0));
+    const uint32_t accmax = pol == POL_U64 ? 0xffffffffu : (qr.bits >= 50 ? 1u : (1u << std::min(10, 50 - qr.bits)));      // lazy FP64 accumulators: |term| <= 2.1 q, sum below 2^52
+    CHECK(cn_l_mul_plain_sum(ctx, pol, MulPlainSumLaunch{P->d + (size_t)pi * n, ctn, dgo, dslot, O->d + (size_t)oi * O->item_words, G, accmax}));
+    ctx->st.ntt_forward_limbs += (uint64_t)D * 2 * k + (uint64_t)E * 2 * k; ctx->st.ntt_inverse_limbs += (uint64_t)G * 2 * k;
+    ctx->st.PlainMultiplication += E; ctx->st.AddMany += G; ctx->st.AddManyItemCount += E;
+    return 0;
+API_END }
 extern "C" int cn_rotate_columns(cn_ctx *ctx, cn_handle in, uint32_t ii, cn_handle out, uint32_t oi, uint32_t count) { API_BODY TWO_LIMBS("cn_rotate_columns");
     LOCK_ONLY; GETCT(I, in, 2); GETCT(O, out, 2);
     if (galois_key_present(ctx, 2ull * ctx->hc.n - 1)) rec_columns(ctx);     // (without the key the call is refused below)

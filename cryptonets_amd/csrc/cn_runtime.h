@@ -330,6 +330,12 @@ int cn_l_digit_gemm(cn_ctx *c, const DigitGemmLaunch &g);
 struct ProductSumLaunch { const uint64_t *prod; uint32_t K; uint64_t *out; double *S; uint32_t outputs; };
 static const uint32_t PRODUCT_SUM_MAX_DIGITS = 8;
 int cn_l_product_sum(cn_ctx *c, const ProductSumLaunch &g);
+// sums of plaintext x ciphertext products (cn_mul_plain_sum; cn_l_diag.hip, k_mul_plain_sum): group g < groups = terms [grp_off[g], grp_off[g + 1]), term e = plaintext
+// pt + e N (coefficients mod t) times the NTT-form ciphertext ctn + slot[e] 2kN; out [groups][2][k][N].  grp_off / slot: device memory.  policy: cn_policy of the q limbs
+struct MulPlainSumLaunch { const uint64_t *pt, *ctn; const uint32_t *grp_off, *slot; uint64_t *out; uint32_t groups, accmax; };
+int cn_l_mul_plain_sum(cn_ctx *c, int policy, const MulPlainSumLaunch &a);
+bool cn_l_mul_plain_sum_kernel(int policy, uint32_t logn);      // is there a kernel?  Every register-radix size but N = 16384 under the integer policy
+int cn_l_diag_set_attrs(uint32_t logn, size_t lds);
 // modulus switching (cn_l_modswitch.hip): `items` (ciphertext, poly) pairs [items][ks][N] -> [items][kd][N] on c's stream with the constants of the source context
 int cn_l_mod_switch(cn_ctx *c, const uint64_t *src, uint64_t *dst, const DevConsts *src_consts, uint32_t ks, uint32_t kd, uint32_t items, uint32_t logn,
                     bool f64, bool *ran_f64);

@@ -69,6 +69,15 @@ def _device_join_ok(env):
 DEVICE_SPLIT = True
 
 
+# The dense layers: EncryptedSealBfvMatrix.Mul(..., ForceDenseFormat=True) on a batchable row-major plaintext matrix as a generalized-diagonal product with
+# baby-step giant-step rotations (diagonal.py): the input vector is rotated, ONE cn_mul_plain_sum multiplies the rotations by the matrix's diagonals
+# and sums them, the sums are rotated and added - instead of one product per row, a SumAllSlots chain on each and a one-hot mask.  Taken if and only if
+# diagonal.dense_path_counts counts fewer limb transforms for it (a 10 x 5488 layer keeps the default path).  The decrypted slots are those of the default path
+# (the same integer linear map mod t); the ciphertext words and the noise differ.  False (default): the calls and words of the default path, always.
+# profiles/diag_dense.md: what was measured.
+DIAGONAL_DENSE = False
+
+
 def _device_split_ok(env, encrypt):
     """may cn_split_encode / cn_split_encrypt serve this CRT environment?  Device clients on library contexts, at most 8 primes; encryption on the ring
     sizes cn_encrypt takes"""
@@ -1631,6 +1640,8 @@ class EncryptedSealBfvMatrix:
         for cache in ("_rowpt", "_rowmask"):
             for buf in self.__dict__.pop(cache, {}).values():
                 buf.release()
+        for (_, pts) in self.__dict__.pop("_diagplan", {}).values():
+            pts.release()
         if self.leVectors is not None and not self.DataDisposedExternaly:
             for v in self.leVectors:
                 if v is not None:
@@ -1675,6 +1686,8 @@ class EncryptedSealBfvMatrix:
             return EncryptedSealBfvVector.DenseMatrixBySparseVectorMultiply(self.leVectors, v, env)
         if self._can_batch_rows(v):
             if ForceDenseFormat:
+                if DIAGONAL_DENSE and self.DiagonalDenseWins(v, env):
+                    return self.DiagonalDense(v, env)
                 return self.RowsDotProduct(v, env, ForceOutputInColumns=True)
             temp = self.RowsDotProduct(v, env)
             res = EncryptedSealBfvVector.GenerateSpareOfArray(temp, env)
@@ -1932,6 +1945,114 @@ class EncryptedSealBfvMatrix:
         for (_, wv) in per_prime:
             wv.release()
         return res
+
+    # ---- the dense product by generalized diagonals (DIAGONAL_DENSE; diagonal.py) ---------------------------
+    def DiagonalDenseCounts(self, v, env):
+        """diagonal.dense_path_counts for this matrix against the packed vector v in `env` (None: the matrix has more rows than a ciphertext has slots)"""
+        from . import diagonal
+        ctx = env.Environments[0].ctx
+        R, n = len(self.leVectors), ctx.n
+        if R > n or v.Dim > n:
+            return None
+        return diagonal.dense_path_counts(R, int(v.Dim), n, len(ctx.q), diagonal.ks_digits(ctx.q, ctx.gdbc))
+
+    def DiagonalDenseWins(self, v, env):
+        c = self.DiagonalDenseCounts(v, env)
+        return c is not None and c["choice"] == "diagonal"
+
+    def _diagonal_plan(self, i, env_i, B=None):
+        """(plan, device array of its pre-rotated diagonal plaintexts) for prime i - built once per context (level), like _row_plaintexts: the weights are the
+        integers the row plaintexts hold, rotated in slot space on the host and encoded in chunks"""
+        from . import diagonal
+        cache = self.__dict__.setdefault("_diagplan", {})
+        key = (i, env_i.ctx, B)
+        if key not in cache:
+            ctx = env_i.ctx
+            R, dim = len(self.leVectors), int(self.leVectors[0].Dim)
+            rows = self._row_plaintexts(i, env_i)
+            W = np.ascontiguousarray(ctx.decode_batch(rows.h, rows.first, R)[:, :dim])
+            bound = int(diagonal.structural_diagonals(R, dim, ctx.n).sum())
+            pts = _Buf(ctx, "pt", bound).view()
+
+            def emit(first, slots):
+                ctx.encode_batch(slots, pts.h, pts.first + first)
+            try:
+                plan = diagonal.build_plan(W, ctx.n, emit, B=B)
+            except BaseException:
+                pts.release()
+                raise
+            cache[key] = (plan, pts)
+        return cache[key]
+
+    def DiagonalDense(self, v, env, B=None):
+        """Mul(v, ForceDenseFormat=True) by generalized diagonals: per plaintext prime the baby steps rho_b(v) (by doubling: log2 B cn_rotate_rows calls), ONE
+        cn_mul_plain_sum for the 2 Gs sums of diagonal x rotation products (contexts without it: mul_plain + add_many per group), the giant steps by folding (log2 Gs
+        cn_rotate_rows_add calls over both column groups) and one cn_rotate_columns_add; cn_rotate_rows_many / cn_add_many where zero diagonals leave gaps.  The result
+        is the vector RowsDotProduct(ForceOutputInColumns=True) returns: row r in slot r, zero elsewhere, same Scale, Dim, format and sign."""
+        R = len(self.leVectors)
+
+        def one_prime(i, e):
+            ctx = e.ctx
+            plan, pts = self._diagonal_plan(i, e, B)
+            src = v.eVectors[i].encData
+            nb, ng, Bs, Gs = len(plan.babies), len(plan.groups), plan.B, plan.Gs
+            bab, u = _Buf(ctx, "ct", nb), _Buf(ctx, "ct", ng)
+            bv, uv = bab.view(), u.view()
+            ctx.copy(src.h, src.first, bab.h, 0, 1)
+            if plan.babies_by_doubling:
+                s = 1
+                while s < Bs:                                        # rho_(b + s)(v) = rho_s(rho_b(v)) for all b < s at once
+                    ctx.rotate_rows(bab.h, 0, s, bab.h, s, s)
+                    s *= 2
+            elif nb > 1:
+                ctx.rotate_rows_many(bab.h, [0] * (nb - 1), plan.babies[1:], bab.h, list(range(1, nb)))
+            if hasattr(ctx, "mul_plain_sum"):
+                ctx.mul_plain_sum(bab.h, 0, pts.h, pts.first, plan.grp_off, plan.ct_idx, u.h, 0)
+            else:                                                    # (the CPU backend): the composed loop
+                for g in range(ng):
+                    e0, e1 = plan.grp_off[g], plan.grp_off[g + 1]
+                    tmp = _Buf(ctx, "ct", e1 - e0)
+                    tv = tmp.view()
+                    for x in range(e0, e1):
+                        ctx.mul_plain(bab.h, plan.ct_idx[x], pts.h, pts.first + x, tmp.h, x - e0, 1)
+                    ctx.add_many(tmp.h, list(range(e1 - e0)), u.h, g)
+                    tv.release()
+            bv.release()
+            res = _Buf(ctx, "ct", 1)
+            if plan.giants_by_folding:                               # u[nc j + x] += rho_(half B)(u[nc (j + half) + x]) for j < half, every column class at once
+                nc, half = len(plan.classes), Gs // 2
+                while half >= 1:
+                    ctx.rotate_rows_add(u.h, nc * half, half * Bs, u.h, 0, u.h, 0, nc * half)
+                    half //= 2
+                if nc == 2:
+                    ctx.rotate_columns_add(u.h, 1, u.h, 0, res.h, 0, 1)
+                elif plan.classes == [1]:
+                    ctx.rotate_columns(u.h, 0, res.h, 0, 1)
+                else:
+                    ctx.copy(u.h, 0, res.h, 0, 1)
+            else:
+                far = [g for g, (j, _) in enumerate(plan.groups) if j]
+                if far:
+                    ctx.rotate_rows_many(u.h, far, [plan.groups[g][0] * Bs for g in far], u.h, far)
+                tot = _Buf(ctx, "ct", 2)
+                tv = tot.view()
+                members = [[g for g, (_, c) in enumerate(plan.groups) if c == cc] for cc in (0, 1)]
+                for cc in (0, 1):
+                    if members[cc]:
+                        ctx.add_many(u.h, members[cc], tot.h, cc)
+                if members[0] and members[1]:
+                    ctx.rotate_columns_add(tot.h, 1, tot.h, 0, res.h, 0, 1)
+                elif members[1]:
+                    ctx.rotate_columns(tot.h, 1, res.h, 0, 1)
+                else:
+                    ctx.copy(tot.h, 0, res.h, 0, 1)
+                tv.release()
+            uv.release()
+            return res.view()
+        views = _fan_out(env.Environments, one_prime)
+        signed = v.eVectors[0].IsSigned
+        atoms = [AtomicSealBfvEncryptedVector._new(Scale=1, Dim=R, Format=EVectorFormat.dense, IsSigned=signed, encData=wv) for wv in views]
+        return EncryptedSealBfvVector._of(atoms, self.leVectors[0].Scale * v.Scale)
 
     # ---- batched HOT LOOP A for a whole PoolLayer (PoolLayer.cs:149-229 issues one Mul per output) -----------------
     def MulManySparse(self, gather, weights, bias, out_scale, env, cache=None, bias_vectors=None):

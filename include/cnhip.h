@@ -413,6 +413,22 @@ int cn_rotate_columns_add(cn_ctx *ctx, cn_handle in, uint32_t ii, cn_handle acc,
  * LLInterleavedDenseLayer).  Same words as the per-row MultiplyPlain / RotateRows / Add sequence of the reference. */
 int cn_sum_slots(cn_ctx *ctx, cn_handle h, uint32_t first, uint32_t count, uint32_t length);
 int cn_rowdot_batch(cn_ctx *ctx, cn_handle v, uint32_t vi, cn_handle pt, uint32_t pi, uint32_t rows, uint32_t length, cn_handle out, uint32_t oi);
+/* Sums of plaintext x ciphertext products, as one call: for g < G
+ *     out[oi + g] = sum_{e in [grp_off[g], grp_off[g + 1])} MultiplyPlain(ct[ci + ct_idx[e]], pt[pi + e])
+ * - the inner loop of a generalized-diagonal (baby-step giant-step) matrix-vector product: the rotated copies of ONE packed input vector against the diagonals of
+ * a plaintext matrix (hewrapper.DIAGONAL_DENSE); the encrypted x plaintext sibling of cn_mul_relin_sum.  grp_off has G + 1 entries, starts at 0 and
+ * increases strictly (no empty group); ct_idx has grp_off[G] entries, which may repeat inside and across groups; term e takes plaintext pi + e.  Every plaintext is
+ * a dense N-coefficient plaintext and none may be zero (CN_ERR_ZERO, like cn_mul_plain).
+ * The results are size-2 ciphertexts in coefficient form with canonical words: modular arithmetic is exact, so they are the words of cn_mul_plain per term followed
+ * by cn_add in any order.  With the register-radix kernels (1024 <= N <= 16384, every arithmetic policy, level contexts included) the distinct ciphertexts are
+ * transformed once and ONE kernel per call lifts and transforms each plaintext, multiplies, accumulates in registers and transforms each sum back once: neither a
+ * lifted plaintext nor a product exists in memory.  Other ring sizes, N = 16384 under the integer policy (moduli of 50 bits and more, or "f64" = 0: transform and
+ * accumulators do not fit the registers of a 1024-thread workgroup) and "mp_fused" = 0 compose cn_mul_plain and cn_add_many through a temporary - same words.
+ * Refused with CN_ERR_ARG, nothing written: G = 0, grp_off[0] != 0, an empty group, an index outside its handle, operands or outputs not of size 2, and an output
+ * range that contains one of the ciphertexts the call reads.  Queued calls ("defer") are submitted first; under cn_graph_begin the index lists are captured by
+ * value, like those of cn_add_many and cn_copy_many. */
+int cn_mul_plain_sum(cn_ctx *ctx, cn_handle ct, uint32_t ci, cn_handle pt, uint32_t pi, const uint32_t *grp_off, const uint32_t *ct_idx, uint32_t G,
+                     cn_handle out, uint32_t oi);
 
 /* ---- client side on the device (what SEAL's KeyGenerator / Encryptor / Decryptor do for
  * AtomicSealBfvEncryptedEnvironment.SetKeys / Encrypt / Decrypt, AtomicSealBfvVector.cs:62-74,1030-1110,1202-1232), for data

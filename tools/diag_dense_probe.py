@@ -1,0 +1,241 @@
+"""The dense layer of one image on the default path (cn_rowdot_batch + one-hot masks) and on the diagonal path (hewrapper.DIAGONAL_DENSE: cn_mul_plain_sum between
+baby and giant steps), in one process on the same input ciphertext: wall-clock time of Mul(..., ForceDenseFormat=True) with the plans and plaintexts resident,
+equality of all N decrypted slots, and the invariant noise budget (cn_noise_norm) of both outputs per plaintext prime.
+
+Shapes: the test shape 37 x 700 at N = 1024 (two primes, three 36-37-bit limbs), the LoLa-CIFAR layer 5488 x 16268 (N = 16384, 8 limbs, dbc 60) and the LargeLoLa
+layer 2608 x 11952 (N = 16384, 7 limbs).  Weights are synthetic small integers (the reference's blobs are not available); the input is a FRESH encryption of small
+integers - in the networks it arrives behind a squaring with most of its budget spent, so the budgets below compare the two paths, they are not the networks'.
+
+"network": the LoLa-CIFAR network of the reference's parameters (8 limbs, two primes, synthetic full-range weights of the reference's shapes) evaluated to the logits
+with the flag off and on - time of the 5488 x 16268 layer inside the network (bias add included), the budgets behind the layers that follow, and whether the
+decrypted outputs equal the integer model (networks.lola_cifar_dense_model).
+
+    python tools/diag_dense_probe.py [--shapes tiny,cifar,large,network] [--primes 1] [--rounds 3] [--out profiles/diag_dense.md]
+"""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np
+
+from cryptonets_amd import diagonal, hewrapper, networks
+from cryptonets_amd.hewrapper import EMatrixFormat, EncryptedSealBfvFactory, EVectorFormat
+
+TINY_Q = [0xffffee001, 0xffffc4001, 0x1ffffe0001]
+
+
+class TinyContexts:
+    """context factory of the N = 1024 test ring (the library's default modulus at 1024 is a single prime: no rotations)"""
+
+    def default_coeff_modulus(self, n):
+        return list(TINY_Q)
+
+    def __call__(self, n, t, q, dbc, gdbc):
+        from cryptonets_amd._native import Context
+        return Context(n, t, q=q, dbc=dbc, gdbc=gdbc, device=0)
+
+
+def device_client(ctx, t):
+    from cryptonets_amd.client import DeviceClient
+    return DeviceClient(ctx, seed=1234 ^ t)
+
+
+SHAPES = {
+    "tiny": dict(R=37, Dim=700, parms=dict(primes=(12289, 40961), n=1024, context_factory=TinyContexts(), device_client_factory=device_client), wmax=3, vmax=3),
+    "cifar": dict(R=5488, Dim=16268, parms=dict(networks.FACTORY_PARAMETERS["LoLaCifar"], client_seed=7), wmax=10, vmax=50),
+    "large": dict(R=2608, Dim=11952, parms=dict(networks.FACTORY_PARAMETERS["LoLaLarge"], client_seed=7), wmax=10, vmax=50),
+}
+
+
+def sync(env):
+    for e in env.Environments:
+        e.ctx.sync()
+
+
+def slots_and_budgets(vec, env):
+    slots, budgets = [], []
+    for a, e in zip(vec.eVectors, env.Environments):
+        d, ctx = a.encData, e.ctx
+        budgets.append(float(ctx.invariant_noise_budget(d.h, d.first, 1)[0]))
+        plain = e.client.decrypt(ctx.ct_download(d.h, d.first, 1)[0])
+        pt = ctx.pt_alloc(1)
+        ctx.pt_upload(pt, 0, plain)
+        slots.append(ctx.decode_batch(pt, 0, 1)[0])
+        ctx.free(pt)
+    return slots, budgets
+
+
+def timed(fn, env, rounds):
+    out, ms = None, []
+    for _ in range(rounds):
+        if out is not None:
+            out.Dispose()
+        sync(env)
+        t0 = time.perf_counter()
+        out = fn()
+        sync(env)
+        ms.append((time.perf_counter() - t0) * 1e3)
+    return out, ms
+
+
+def probe(name, nprimes, rounds, say):
+    s = SHAPES[name]
+    parms = dict(s["parms"])
+    parms["primes"] = tuple(parms["primes"])[:nprimes]
+    R, Dim = s["R"], s["Dim"]
+    rng = np.random.default_rng(11)
+    W = rng.integers(-s["wmax"], s["wmax"] + 1, size=(R, Dim)).astype(float)
+    W[:, 0] = np.where(W.any(axis=1), W[:, 0], 1)
+    v = rng.integers(-s["vmax"], s["vmax"] + 1, size=Dim).astype(float)
+    F = EncryptedSealBfvFactory(**parms)
+    env = F.AllocateComputationEnv()
+    ctx0 = env.Environments[0].ctx
+    mat = F.GetPlainMatrix(W, EMatrixFormat.RowMajor, 1.0)
+    vec = F.GetEncryptedVector(v, EVectorFormat.dense, 1.0)
+    counts = mat.DiagonalDenseCounts(vec, env)
+    say("### %s: %d x %d, N = %d, k = %d, %d plaintext prime(s) %s" % (name, R, Dim, ctx0.n, len(ctx0.q), len(parms["primes"]), list(parms["primes"])))
+    say("")
+    say("limb transforms counted (`diagonal.dense_path_counts`): default %d (%d key switches), diagonal %d (%d key switches, %d diagonals, B = %d) -> %s"
+        % (counts["default"], counts["default_key_switches"], counts["diagonal"], counts["diagonal_key_switches"], counts["diagonals"], counts["B"], counts["choice"]))
+    _, in_budget = slots_and_budgets(vec, env)
+    hewrapper.DIAGONAL_DENSE = False
+    mat.Mul(vec, env, ForceDenseFormat=True).Dispose()               # untimed: row plaintexts and masks become resident
+    base, ms_default = timed(lambda: mat.Mul(vec, env, ForceDenseFormat=True), env, rounds)
+    t0 = time.perf_counter()
+    plans = [mat._diagonal_plan(i, e)[0] for i, e in enumerate(env.Environments)]
+    sync(env)
+    plan_s = time.perf_counter() - t0
+    mat.DiagonalDense(vec, env).Dispose()                            # untimed: the scratch arena takes its size
+    out, ms_diag = timed(lambda: mat.DiagonalDense(vec, env), env, rounds)
+    a, ba = slots_and_budgets(base, env)
+    b, bb = slots_and_budgets(out, env)
+    equal = all(np.array_equal(x, y) for x, y in zip(a, b))
+    t = [int(e.ctx.t) for e in env.Environments]
+    want = (W.astype(np.int64) @ v.astype(np.int64))
+    model = all(np.array_equal(x[:R].astype(np.int64), np.mod(want, ti)) and not x[R:].any() for x, ti in zip(b, t))
+    p = plans[0]
+    say("")
+    say("| | default path | diagonal path |")
+    say("|---|---|---|")
+    say("| time per layer, ms (min / median of %d) | %.2f / %.2f | %.2f / %.2f |" % (rounds, min(ms_default), statistics.median(ms_default), min(ms_diag), statistics.median(ms_diag)))
+    say("| invariant noise budget of the output, bits, per prime (input: %s) | %s | %s |" % (", ".join("%.1f" % x for x in in_budget), ", ".join("%.1f" % x for x in ba),
+                                                                                             ", ".join("%.1f" % x for x in bb)))
+    say("")
+    say("ratio default / diagonal (medians): %.2f.  All %d decrypted slots equal on both paths: %s; equal to W v mod t with zeros at %d and above: %s."
+        % (statistics.median(ms_default) / statistics.median(ms_diag), ctx0.n, equal, R, model))
+    say("Plan: B = %d, Gs = %d, %d diagonals in %d groups, %d rotated inputs, %d key switches (baby steps by doubling: %s, giant steps by folding: %s); built and encoded once in %.1f s "
+        "(host, untimed above); resident diagonal plaintexts %.1f MiB per prime against %.1f MiB of row plaintexts."
+        % (p.B, p.Gs, p.terms, len(p.groups), len(p.babies), p.key_switches(), p.babies_by_doubling, p.giants_by_folding, plan_s, p.terms * ctx0.n * 8 / 2 ** 20,
+           R * ctx0.n * 8 / 2 ** 20))
+    say("")
+    for x in (base, out, vec):
+        x.Dispose()
+    mat.Dispose()
+    for e in env.Environments:
+        e.ctx.close()
+    return equal and model
+
+
+def mulmod(a, b, p):
+    b = np.asarray(b, dtype=np.uint64)
+    hi = (a * (b >> np.uint64(20))) % p
+    return (hi * np.uint64(1 << 20) + a * (b & np.uint64(0xFFFFF))) % p
+
+
+def network(say):
+    """LoLa-CIFAR, 8 limbs (LolaCifarCryptoNet.cs:35,58-131), one image, flag off and on"""
+    say("### network: LoLa-CIFAR at the reference's parameters (N = 16384, 8 limbs, two primes), one image, synthetic weights of the reference's shapes")
+    say("")
+    say("| `DIAGONAL_DENSE` | dense 5488 x 16268 layer in the network, ms (three runs) | its outputs exact | budget per prime, bits: input of the layer / its output / behind the second square / logits | logits exact |")
+    say("|---|---|---|---|---|")
+    ok = True
+    for flag in (False, True):
+        hewrapper.DIAGONAL_DENSE = flag
+        rng = np.random.default_rng(5)
+        F = EncryptedSealBfvFactory(**dict(networks.FACTORY_PARAMETERS["LoLaCifar"], client_seed=7))
+        env = F.AllocateComputationEnv()
+        img = rng.integers(0, 256, size=3 * 32 * 32).astype(float)
+        q = lambda a, sc: np.rint(a * sc) / sc
+        w = [q(rng.normal(0, 0.05, 83 * 192), 256), q(rng.normal(0, 0.02, 112 * 8300), 512), q(rng.normal(0, 0.05, 10 * 5488), 512)]
+        b = [q(rng.normal(0, 0.05, 83), 256), q(rng.normal(0, 0.05, 112), 512), q(rng.normal(0, 0.05, 10), 512)]
+        reader = networks.cifar_reader(Factory=F)
+        reader.Features = img / 256.0
+        d6 = networks.LoLaCifar(F, reader, w, b, timing=False)
+        a5 = d6.Source
+        d4 = a5.Source
+        a3 = d4.Source
+        c1 = a3.Source.Source
+        d6.PrepareNetwork()
+        x3 = a3.GetNext()
+        d4.Apply(x3).Dispose()                                       # untimed: plans and plaintexts become resident
+        ms, out4 = [], None
+        for _ in range(3):
+            if out4 is not None:
+                out4.Dispose()
+            sync(env)
+            t0 = time.perf_counter()
+            out4 = d4.Apply(x3)
+            sync(env)
+            ms.append((time.perf_counter() - t0) * 1e3)
+
+        def budgets(m):
+            return ", ".join("%.1f" % float(e.ctx.invariant_noise_budget(a.encData.h, a.encData.first, 1)[0]) for a, e in zip(m.GetColumn(0).eVectors, env.Environments))
+        a5v = a5.Apply(out4)
+        out = d6.Apply(a5v)
+        trail = " / ".join(budgets(m) for m in (x3, out4, a5v, out))
+        W2i = np.rint(w[2].reshape(10, 5488) * 512).astype(np.int64)
+        s2 = ((8 * 256) ** 2 * 512) ** 2
+        B2i = [int(round(float(x) * s2 * 512)) for x in b[2]]
+        ok4, ok6 = True, True
+        for i, e in enumerate(env.Environments):
+            p = np.uint64(e.plainmodulusValue)
+            a2 = networks.lola_cifar_dense_model(reader, c1, w, b, img, int(p))
+            ok4 = ok4 and [int(v) for v in out4.GetColumn(0).eVectors[i]._decrypt_ints(e)] == [int(v) for v in a2]
+            a2 = mulmod(a2, a2, p)
+            W2p = np.mod(W2i, int(p)).astype(np.uint64)
+            lg = np.zeros(10, dtype=np.uint64)
+            for c0 in range(0, 5488, 512):
+                lg = (lg + (mulmod(W2p[:, c0:c0 + 512], a2[None, c0:c0 + 512], p) % p).sum(axis=1) % p) % p
+            lg = (lg + np.array([x % int(p) for x in B2i], dtype=np.uint64)) % p
+            ok6 = ok6 and [int(v) for v in out.GetColumn(0).eVectors[i]._decrypt_ints(e)] == [int(v) for v in lg]
+        say("| %s | %s | %s | %s | %s |" % (flag, ", ".join("%.1f" % x for x in ms), ok4, trail, ok6))
+        ok = ok and ok4
+        for e in env.Environments:
+            e.ctx.close()
+    hewrapper.DIAGONAL_DENSE = False
+    say("")
+    return ok
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", default="tiny,cifar,large")
+    ap.add_argument("--primes", type=int, default=1, help="plaintext primes of the N = 16384 shapes (the tiny shape always takes its two)")
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "diag_dense.md"))
+    a = ap.parse_args()
+    lines = []
+
+    def say(x):
+        print(x, flush=True)
+        lines.append(x)
+    say("# Dense layers by generalized diagonals: `tools/diag_dense_probe.py`")
+    say("")
+    say("One MI355X, one process, one image; both paths on the same input ciphertext, plans and plaintexts resident, wall clock around `Mul(..., ForceDenseFormat=True)` and a")
+    say("host wait on every context.  Synthetic integer weights, a fresh input encryption (see the tool's docstring).")
+    say("")
+    ok = True
+    for name in a.shapes.split(","):
+        ok = (network(say) if name == "network" else probe(name, 2 if name == "tiny" else a.primes, a.rounds, say)) and ok
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    return 0 if ok else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
