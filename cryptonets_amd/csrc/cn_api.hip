@@ -474,15 +474,7 @@ extern "C" int cn_set_galois_key(cn_ctx *ctx, uint64_t elt, const uint64_t *word
     return set_key(ctx, ctx->gk[elt], words, count, cn_key_words(ctx, 1), is_dev);
 API_END }
 extern "C" int cn_has_galois_key(cn_ctx *ctx, uint64_t elt) { CnGuard lk(ctx->mu); auto it = ctx->gk.find(elt); return it != ctx->gk.end() && it->second.d; }
-extern "C" uint64_t cn_galois_elt_from_step(cn_ctx *ctx, int steps) {
-    uint64_t n = ctx->hc.n, m = 2 * n;
-    if (steps == 0) return m - 1;
-    uint64_t pos = (uint64_t)std::abs((long)steps);
-    if (pos >= n / 2) return 0;
-    uint64_t s = steps < 0 ? n / 2 - pos : pos, e = 1;
-    while (s--) e = (e * 3) & (m - 1);
-    return e;
-}
+extern "C" uint64_t cn_galois_elt_from_step(cn_ctx *ctx, int steps) { return cn_elt_of_step(ctx->hc.n, steps); }
 
 // ---------------------------------------------------------------- buffers
 void pool_flush(cn_ctx *ctx) {
@@ -840,7 +832,7 @@ extern "C" int cn_copy(cn_ctx *ctx, cn_handle src, uint32_t sfirst, cn_handle ds
     Buffer *s = ctx->bufs.find(src), *d = ctx->bufs.find(dst);
     if (deferring(ctx) && s && d && s->kind == 0 && d->kind == 0 && s->size == 2 && d->size == 2 && count && count <= DEFER_STAGED_MAX &&
         range_ok(s, sfirst, count) && range_ok(d, dfirst, count) && !(s == d && sfirst < dfirst + count && dfirst < sfirst + count))
-        return defer_staged(ctx, DOP_COPY, s, sfirst, nullptr, 0, nullptr, 0, d, dfirst, count, 0);
+        return defer_staged(ctx, DOP_COPY, CtSpan{s->d + sfirst * ctx->ctw2, count}, CtSpan{}, CtSpan{d->d + dfirst * ctx->ctw2, count}, 0);
     CHECK(cn_defer_flush(ctx));
     if (!s || !d) return fail(CN_ERR_ARG, "invalid handle");
     if (s->kind != d->kind || s->item_words != d->item_words) return fail(CN_ERR_ARG, "copy between different buffer shapes");

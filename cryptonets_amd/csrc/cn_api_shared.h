@@ -9,6 +9,7 @@
 // carries its own copy.
 #pragma once
 #include "cn_runtime.h"
+#include "cn_rotation.h"
 #include <thread>
 #include "cn_k_elem.hip.h"
 #include <algorithm>
@@ -80,8 +81,18 @@ struct DeferQueue {
 static const size_t SLAB_MAX_ITEM = 8u << 20, SLAB_BYTES = 64u << 20;
 struct Slab { char *base; size_t bytes; };
 static const uint32_t DEFER_STAGED_MAX = 4;       // per-ciphertext callers: calls on up to this many ciphertexts are queued, larger ones run at once
-// out[c] = a[c * (a_bcast ? 0 : 1)] * pt[c * pstride]; a_bcast: ONE ciphertext against `count` plaintexts (row-dot batches)
-// Dense MultiplyPlain in two launches (k_lift_ntt, k_mul_plain_fused); ranges / zero plaintexts were checked by the caller
+// What the batched implementations (*_impl) work on: the entry points check handles and ranges and hand over spans, the deferred flush builds them from its staging
+// pointers.  CtSpan: `count` ciphertexts from d on, one after the other (size 2 - ctx->ctw2 words each - wherever no `polys` says otherwise).  PtSpan: plaintexts of N
+// coefficients from d on, `stride` plaintexts apart (0: one for every ciphertext); zero: their all-zero flags, or null when the caller has refused zero plaintexts already
+struct CtSpan { uint64_t *d; uint32_t count; };
+struct PtSpan { const uint64_t *d; uint32_t stride; const uint8_t *zero; };
+// do_galois: in / out / tmp hold `count` size-2 ciphertexts; acc, pre, next_elt / next_out: see cn_eval.hip
+struct GaloisCall {
+    const uint64_t *in; uint64_t elt; uint64_t *out, *tmp; uint32_t count;
+    const uint64_t *acc = nullptr, *pre = nullptr; uint64_t next_elt = 0; uint64_t *next_out = nullptr;
+};
+// out[c] = a[c * (a_bcast ? 0 : 1)] * pt[c * stride]; a_bcast: ONE ciphertext against `count` plaintexts (row-dot batches)
+// Dense MultiplyPlain in two launches (k_lift_ntt, k_mul_plain_fused); ranges were checked by the caller
 // A row-dot batch whose SumAllSlots chain follows: the product kernel leaves sigma_elt(c1) of every product in `out` ([row][k][N], the chain's first scratch array) and takes
 // its transformed ciphertext from `ctn` - both inside the scratch arena the caller has sized for the whole call (no ensure_scratch in between: the arena must not move)
 struct BcastNext { uint64_t elt; uint64_t *out, *ctn; };
@@ -125,11 +136,11 @@ static const size_t DEFER_SQ_PLANS = 8;
 // ---- rotations of n ciphertexts by n DIFFERENT step counts as one launch chain (cn_rotate_rows_many; the queued RotateRows calls of one level).
 // A single-image network rotates the 13 masked vectors of an Interleave by 13 different amounts, the 5 maps of a Vectorize by 5: one rotation
 // is 2 dependent dispatches per hop, and dependent dispatches are what the latency of such a chain is made of.  The hops of a
-// rotation (the element of its step count if the key exists, else its NAF terms - the same decomposition rotate_rec walks, so the words are the
+// rotation (the element of its step count if the key exists, else its NAF terms - the plan of cn_rotation.h that every rotation walks, so the words are the
 // same) are taken in rounds: round r is ONE two-launch key switch over every ciphertext that has an r-th hop, each with its own key and element
 // from a table (KsItem); round 0 reads the source and writes the destination, later rounds work on the destination in place.
 struct Tab2 { const NTT_GLOBAL uint64_t *src; NTT_GLOBAL uint64_t *dst; };          // one (source, destination) pair of k_copy_tab
-struct RotJob { const uint64_t *src; uint64_t *dst; int steps; std::vector<uint64_t> elts; };
+struct RotJob { const uint64_t *src; uint64_t *dst; int steps; CnRotPlan plan; };
 
 // ---- functions defined in one unit and used by the others
 int cn_run_ntt(cn_ctx *c, uint64_t *data, uint32_t limbs, uint32_t base_off, uint32_t nmod, int inverse);
@@ -163,9 +174,9 @@ int ensure_index_map(cn_ctx *ctx);
 int addsub(cn_ctx *ctx, cn_handle a, uint32_t ai, cn_handle b, uint32_t bi, cn_handle out, uint32_t oi, uint32_t count, int op);
 int addsub_body(cn_ctx *ctx, cn_handle a, uint32_t ai, cn_handle b, uint32_t bi, cn_handle out, uint32_t oi, uint32_t count, int op);
 int add_plain_body(cn_ctx *ctx, cn_handle a, uint32_t ai, cn_handle pt, uint32_t pi, int subtract, cn_handle out, uint32_t oi, uint32_t count);
-int mul_plain_fused(cn_ctx *ctx, Buffer *A, uint32_t ai, bool a_bcast, Buffer *P, uint32_t pi, uint32_t pstride, Buffer *O, uint32_t oi, uint32_t count, const BcastNext *nx = nullptr);
+bool shifted_overlap(const uint64_t *a, const uint64_t *o, size_t words);
 bool mul_plain_takes_bcast(cn_ctx *ctx, uint32_t count);
-int mul_plain_impl(cn_ctx *ctx, Buffer *A, uint32_t ai, bool a_bcast, Buffer *P, uint32_t pi, uint32_t pstride, Buffer *O, uint32_t oi, uint32_t count, const BcastNext *nx = nullptr);
+int mul_plain_impl(cn_ctx *ctx, CtSpan A, bool a_bcast, PtSpan P, CtSpan O, uint32_t polys, const BcastNext *nx = nullptr);
 uint64_t lift_scalar(const DevConsts &hc, uint64_t w, uint32_t j);
 bool gemm_weights_small(cn_ctx *ctx, const uint64_t *W, size_t count);
 GemmArith gemm_arith(cn_ctx *ctx, bool weights_small);
@@ -241,24 +252,19 @@ static inline bool pipeline_fused_ks(cn_ctx *ctx, uint32_t c) {
     for (uint32_t i = 0; i < P; i++) if (ks_planned_mode(ctx, first[i + 1] - first[i], 0) != 0) return false;
     return P >= 2;
 }
-int do_keyswitch(cn_ctx *ctx, const uint64_t *target, size_t tstride, const uint64_t *add0, const uint64_t *add1, size_t astride, const KsKey &key, uint64_t *out, uint32_t cnt, int galois, const uint64_t *extra = nullptr, size_t xstride = 0, uint64_t *const *out_tab = nullptr, uint32_t perm_elt = 0, const KsItem *items = nullptr, uint32_t next_elt = 0, uint64_t *next_out = nullptr, const double *dig = nullptr);
+int do_keyswitch(cn_ctx *ctx, const KsKey &key, const KsCall &call);
 bool ks_pair14_ok(cn_ctx *ctx, uint32_t cnt, int galois, const KsKey &key);
 uint32_t chunk_for(cn_ctx *ctx, size_t per_ct, uint32_t count);
 int mul_relin_body(cn_ctx *ctx, cn_handle a, uint32_t ai, uint32_t astride, cn_handle b, uint32_t bi, uint32_t bstride, cn_handle out, uint32_t oi, uint32_t count);
-int do_galois(cn_ctx *ctx, const uint64_t *in, uint64_t elt, uint64_t *out, uint64_t *tmp, uint32_t count, const uint64_t *acc = nullptr, const uint64_t *pre = nullptr, uint64_t next_elt = 0, uint64_t *next_out = nullptr);
-bool shifted_overlap(const Buffer *I, uint32_t ii, const Buffer *O, uint32_t oi, uint32_t count);
-int galois_impl(cn_ctx *ctx, Buffer *I, uint32_t ii, uint64_t elt, Buffer *O, uint32_t oi, uint32_t count);
-bool galois_key_present(cn_ctx *ctx, uint64_t elt);
-bool has_direct_key(cn_ctx *ctx, int steps);
-int rotate_rec(cn_ctx *ctx, uint64_t *cur, int steps, uint64_t *tmp, uint32_t count);
-int rotate_rows_impl(cn_ctx *ctx, Buffer *I, uint32_t ii, int steps, Buffer *O, uint32_t oi, uint32_t count);
-int rotate_check(cn_ctx *ctx, int steps);
-int rotation_hops(cn_ctx *ctx, int steps, std::vector<uint64_t> &elts);
+const KsKey *galois_key(cn_ctx *ctx, uint64_t elt);          // null: not present
+int do_galois(cn_ctx *ctx, const GaloisCall &g);
+int galois_impl(cn_ctx *ctx, CtSpan in, uint64_t elt, CtSpan acc, CtSpan out);
+int plan_rotation(cn_ctx *ctx, int steps, CnRotPlan *plan = nullptr);      // null: the check alone
+int rotate_rows_impl(cn_ctx *ctx, CtSpan in, int steps, CtSpan out);
 int rotate_jobs(cn_ctx *ctx, std::vector<RotJob> &jobs);
-int rotate_rows_add_impl(cn_ctx *ctx, Buffer *I, uint32_t ii, int steps, Buffer *A, uint32_t ai, Buffer *O, uint32_t oi, uint32_t count);
-int rotate_columns_add_impl(cn_ctx *ctx, Buffer *I, uint32_t ii, Buffer *A, uint32_t ai, Buffer *O, uint32_t oi, uint32_t count);
+int rotate_rows_add_impl(cn_ctx *ctx, CtSpan in, int steps, CtSpan acc, CtSpan out);
 std::vector<uint64_t> sum_slots_chain_elts(cn_ctx *ctx, uint32_t count, uint32_t length);
-int sum_slots_impl(cn_ctx *ctx, Buffer *H, uint32_t first, uint32_t count, uint32_t length, bool first_ready = false);
+int sum_slots_impl(cn_ctx *ctx, CtSpan h, uint32_t length, bool first_ready = false);
 int set_plain_key(cn_ctx *ctx, uint64_t **slot, const uint64_t *words, size_t count, size_t expect, bool is_dev = false, bool coeff_form = false);
 RngKey rng_key_of(const cn_ctx *ctx);
 int sample_poly(cn_ctx *ctx, uint64_t *dst, uint32_t polys, int kind, uint64_t seed, uint64_t stream);
@@ -279,7 +285,7 @@ int flush_mulrelin_group(cn_ctx *ctx, const std::vector<const DOp *> &all, const
 int ensure_stage(cn_ctx *ctx, size_t bytes);
 int copy_by_table(cn_ctx *ctx, const std::vector<Tab2> &tab, Tab2 *dtab, uint32_t words_per_item);
 int flush_staged_group(cn_ctx *ctx, const std::vector<const DOp *> &all, int type);
-int defer_staged(cn_ctx *ctx, int type, Buffer *A, uint32_t ai, Buffer *B, uint32_t bi, const uint64_t *plain, uint32_t pstride_words, Buffer *O, uint32_t oi, uint32_t count, int64_t arg);
+int defer_staged(cn_ctx *ctx, int type, CtSpan a, CtSpan b, CtSpan o, int64_t arg, const uint64_t *plain = nullptr, uint32_t pstride_words = 0);
 int flush_encrypt_group(cn_ctx *ctx, const std::vector<const DOp *> &ops);
 bool zero_fold_ok(cn_ctx *ctx);
 int flush_zero_folds(cn_ctx *ctx, DeferQueue *q, const std::vector<const DOp *> &gemms);
@@ -288,6 +294,8 @@ int cn_defer_flush(cn_ctx *ctx, bool boundary = false);      // boundary: the la
 void defer_square_drop_plans(cn_ctx *ctx);                   // the cached plans of deferred square + dense layers (changes of the switches build_gemm_plan reads)
 void defer_square_release(cn_ctx *ctx);                      // ... and the product array (ctx_teardown)
 bool deferring(cn_ctx *ctx);
+// per-ciphertext callers: does a staged call (cn_mul_plain, the rotations) on `count` ciphertexts join the queue?  Larger ones run at once
+static inline bool queues(cn_ctx *ctx, uint32_t count) { return deferring(ctx) && count && count <= DEFER_STAGED_MAX; }
 int scalar_dot_body(cn_ctx *ctx, const cn_handle *in, const uint32_t *in_idx, const uint64_t *w, uint32_t K, cn_handle out, uint32_t oi);
 int defer_addsub(cn_ctx *ctx, cn_handle a, uint32_t ai, cn_handle b, uint32_t bi, cn_handle out, uint32_t oi, uint32_t count, int op);
 int defer_add_plain(cn_ctx *ctx, cn_handle a, uint32_t ai, cn_handle pt, uint32_t pi, int subtract, cn_handle out, uint32_t oi, uint32_t count);
@@ -320,6 +328,10 @@ static inline void rec_galois(cn_ctx *ctx, uint64_t elt) {                // cn_
 #define GETCT(var, h, sz) Buffer *var = getbuf(ctx, h, 0); if (!var) return fail(CN_ERR_ARG, "invalid ciphertext handle " #h); \
     if ((sz) && var->size != (uint32_t)(sz)) return fail(CN_ERR_ARG, "ciphertext size mismatch for " #h)
 #define GETPT(var, h) Buffer *var = getbuf(ctx, h, 1); if (!var) return fail(CN_ERR_ARG, "invalid plaintext handle " #h)
+#define SPAN(var, b, first, count) if (!range_ok(b, first, count)) return fail(CN_ERR_ARG, "index out of range"); \
+    const CtSpan var{b->d + (size_t)(first) * b->item_words, count}
+#define PTSPAN(var, b, first, count, stride) if (!range_ok(b, first, (stride) ? count : 1, (stride) ? (stride) : 1)) return fail(CN_ERR_ARG, "index out of range"); \
+    const PtSpan var{b->d + (size_t)(first) * ctx->hc.n, stride, b->pt_zero.data() + (first)}
 #define LOCK_ONLY CHECK(use(ctx)); CHECK(ring_sync(ctx, false))
 #define API_BODY return ctx->mu.run([&]() -> int {
 #define API_END });

@@ -279,8 +279,7 @@ static int pending_materialise(cn_ctx *ctx, DeferSquare &sq, const std::vector<u
     for (uint32_t s = 0; s < n;) {
         if (!need[s]) { s++; continue; }
         uint32_t e = s; while (e < n && need[e]) e++;
-        uint64_t *t = sq.arr + (size_t)s * 3 * kn;
-        CHECK(do_keyswitch(ctx, t + 2 * kn, 3 * kn, t, t + kn, 3 * kn, ctx->rlk, nullptr, e - s, 0, nullptr, 0, dout + s));
+        CHECK(do_keyswitch(ctx, ctx->rlk, KsCall::relin(sq.arr + (size_t)s * 3 * kn, kn, e - s).to_table(dout + s)));
         done += e - s; s = e;
     }
     if (defer_trace()) fprintf(stderr, "defer %p: materialises %u of %u pending products (one key switch each)\n", (void *)ctx, done, n);
@@ -416,7 +415,7 @@ static int sg_run(cn_ctx *ctx, DeferQueue *q, const SgGroup &g) {
     DigitGemmLaunch dg{arr + 2 * kn, 3 * kn, dpidx, P.dev + P.off_dw, P.dev + P.off_oidx, S, P.G, P.M, P.K, P.Kp, P.dKw, P.dMT};
     if (P.dig_mfma) { dg.W = P.dev + P.off_w; dg.mfma = true; dg.P = P.P; dg.mtiles = P.mtiles; dg.ksteps = P.ksteps; }
     CHECK(cn_l_digit_gemm(ctx, dg));
-    CHECK(do_keyswitch(ctx, nullptr, 0, T, T + kn, 2 * kn, ctx->rlk, nullptr, P.O, 0, nullptr, 0, douts, 0, nullptr, 0, nullptr, S));
+    CHECK(do_keyswitch(ctx, ctx->rlk, KsCall::relin_digits(S, T, kn, P.O).to_table(douts)));
     ctx->dsg_fused++;
     if (defer_trace()) fprintf(stderr, "defer %p level %d: fuses %u scalar products over %zu pending products (GEMM, digit GEMM%s, %u key switches)\n", (void *)ctx, g.level, P.O,
                                g.slot_of.size(), P.dig_mfma ? " on the matrix cores" : "", P.O);
@@ -446,7 +445,7 @@ int flush_mulrelin_group(cn_ctx *ctx, const std::vector<const DOp *> &all, const
             uint64_t *t3 = salloc<uint64_t>(ctx, (size_t)c * 3 * kn);
             if (!t3) return fail(CN_ERR_HIP, "internal: scratch exhausted in deferred multiply");
             auto mul = [&](uint32_t f, uint32_t n_) { return do_multiply(ctx, nullptr, 1, nullptr, 1, t3 + (size_t)f * 3 * kn, n_, da + f, (sq ? da : db) + f); };
-            auto ksw = [&](uint32_t f, uint32_t n_) { uint64_t *t = t3 + (size_t)f * 3 * kn; return do_keyswitch(ctx, t + 2 * kn, 3 * kn, t, t + kn, 3 * kn, ctx->rlk, nullptr, n_, 0, nullptr, 0, dout + f); };
+            auto ksw = [&](uint32_t f, uint32_t n_) { return do_keyswitch(ctx, ctx->rlk, KsCall::relin(t3 + (size_t)f * 3 * kn, kn, n_).to_table(dout + f)); };
             if (ctx->opt.sq_halves >= 2 && ctx->hc.logn <= 13 && c >= SQ_HALVES_MIN && !ctx->capturing && pipeline_fused_ks(ctx, c) && aux_stream_ready(ctx)) {
                 CHECK(pipelined_halves(ctx, c, mul, ksw)); continue;
             }
@@ -503,7 +502,7 @@ int flush_staged_group(cn_ctx *ctx, const std::vector<const DOp *> &all, int typ
     }
     if (type == DOP_ROT && all.size() * ctx->hc.k <= KS_WIDE_MAX_BLOCKS) {     // few rotations, any step counts: one launch chain per hop round
         std::vector<RotJob> jobs(all.size());
-        for (size_t i = 0; i < all.size(); i++) jobs[i] = {all[i]->a, all[i]->out, (int)all[i]->arg, {}};
+        for (size_t i = 0; i < all.size(); i++) jobs[i] = {all[i]->a, all[i]->out, (int)all[i]->arg};
         return rotate_jobs(ctx, jobs);
     }
     std::map<int64_t, std::vector<const DOp *>> by_arg;      // one batched call per parameter value (rotation steps, slot count)
@@ -543,18 +542,14 @@ int flush_staged_group(cn_ctx *ctx, const std::vector<const DOp *> &all, int typ
         if (dout) O = ops[0]->out;
         if (!gin.empty()) CHECK(copy_by_table(ctx, gin, t_in, (uint32_t)ctw));
         if (!gpt.empty()) CHECK(copy_by_table(ctx, gpt, t_pt, n));
-        Buffer fa, fb, fo, fp;
-        auto fake = [&](Buffer &b, int kind, uint64_t *d, size_t item) { b.kind = kind; b.count = cnt; b.size = kind == 0 ? 2 : 1; b.d = d; b.item_words = item; };
-        fake(fa, 0, A, ctw); fake(fb, 0, B, ctw); fake(fo, 0, O, ctw); fake(fp, 1, P, n);
-        if (has_p) fp.pt_zero.assign(cnt, 0);                 // zero plaintexts were refused when the calls were queued
+        const CtSpan sa{A, same_a ? 1u : cnt}, sb{B, cnt}, so{O, cnt};
         int rc = 0;
         switch (type) {
-        case DOP_MULPLAIN: if (same_a) fa.count = 1; rc = mul_plain_impl(ctx, &fa, 0, same_a, &fp, 0, 1, &fo, 0, cnt); break;
-        case DOP_ROT: rc = rotate_rows_impl(ctx, &fa, 0, (int)kv.first, &fo, 0, cnt); break;
-        case DOP_ROTADD: rc = rotate_rows_add_impl(ctx, &fa, 0, (int)kv.first, &fb, 0, &fo, 0, cnt); break;
-        case DOP_COLS: rc = galois_impl(ctx, &fa, 0, 2ull * n - 1, &fo, 0, cnt); break;
-        case DOP_COLSADD: rc = rotate_columns_add_impl(ctx, &fa, 0, &fb, 0, &fo, 0, cnt); break;
-        case DOP_SUMSLOTS: rc = sum_slots_impl(ctx, &fa, 0, cnt, (uint32_t)kv.first); break;
+        case DOP_MULPLAIN: rc = mul_plain_impl(ctx, sa, same_a, PtSpan{P, 1, nullptr}, so, 2); break;      // (zero plaintexts were refused when the calls were queued)
+        case DOP_ROT: rc = rotate_rows_impl(ctx, sa, (int)kv.first, so); break;
+        case DOP_ROTADD: rc = rotate_rows_add_impl(ctx, sa, (int)kv.first, sb, so); break;
+        case DOP_COLS: case DOP_COLSADD: rc = galois_impl(ctx, sa, 2ull * n - 1, sb, so); break;
+        case DOP_SUMSLOTS: rc = sum_slots_impl(ctx, sa, (uint32_t)kv.first); break;
         default: rc = fail(CN_ERR_ARG, "internal: staged kind %d", type);
         }
         CHECK(rc);
@@ -563,18 +558,13 @@ int flush_staged_group(cn_ctx *ctx, const std::vector<const DOp *> &all, int typ
     return 0;
 }
 // queue `count` per-ciphertext operations of a staged kind (arguments were checked by the caller)
-int defer_staged(cn_ctx *ctx, int type, Buffer *A, uint32_t ai, Buffer *B, uint32_t bi, const uint64_t *plain, uint32_t pstride_words, Buffer *O, uint32_t oi,
-                        uint32_t count, int64_t arg) {
-    for (uint32_t c = 0; c < count; c++) {
-        const uint64_t *pa = A->d + (size_t)(ai + c) * A->item_words, *pb = B ? B->d + (size_t)(bi + c) * B->item_words : nullptr;
-        DOp op{type, 0, O->d + (size_t)(oi + c) * O->item_words, pa, plain ? plain + (size_t)c * pstride_words : pb, 0, 0, nullptr};
+int defer_staged(cn_ctx *ctx, int type, CtSpan a, CtSpan b, CtSpan o, int64_t arg, const uint64_t *plain, uint32_t pstride_words) {
+    for (uint32_t c = 0; c < o.count; c++) {
+        const uint64_t *pa = a.d + c * ctx->ctw2, *pb = b.d ? b.d + c * ctx->ctw2 : nullptr;
+        DOp op{type, 0, o.d + c * ctx->ctw2, pa, plain ? plain + (size_t)c * pstride_words : pb, 0, 0, nullptr};
         op.arg = arg;
         const uint64_t *ins[2] = {pa, pb};
         CHECK(defer_push(ctx, op, ins, 2));
-    }
-    switch (type) {
-    case DOP_MULPLAIN: ctx->st.PlainMultiplication += 0; break;          // (counted by the batched implementation at flush time)
-    default: break;
     }
     return 0;
 }
@@ -598,7 +588,8 @@ extern "C" int cn_copy_many(cn_ctx *ctx, const cn_handle *src, const uint32_t *s
         sb[i] = b;
     }
     if (deferring(ctx) && d->kind == 0 && d->size == 2) {          // queued like n cn_copy calls
-        for (uint32_t i = 0; i < n; i++) CHECK(defer_staged(ctx, DOP_COPY, sb[i], sfirst ? sfirst[i] : 0, nullptr, 0, nullptr, 0, d, dfirst + i, 1, 0));
+        for (uint32_t i = 0; i < n; i++)
+            CHECK(defer_staged(ctx, DOP_COPY, CtSpan{sb[i]->d + (sfirst ? sfirst[i] : 0) * ctx->ctw2, 1}, CtSpan{}, CtSpan{d->d + (dfirst + i) * ctx->ctw2, 1}, 0));
         return 0;
     }
     CHECK(cn_defer_flush(ctx));

@@ -62,71 +62,77 @@ int add_plain_body(cn_ctx *ctx, cn_handle a, uint32_t ai, cn_handle pt, uint32_t
     if (subtract) ctx->st.PlainSubtraction += count; else ctx->st.PlainAddition += count;
     return 0;
 }
-int mul_plain_fused(cn_ctx *ctx, Buffer *A, uint32_t ai, bool a_bcast, Buffer *P, uint32_t pi, uint32_t pstride, Buffer *O, uint32_t oi, uint32_t count,
-                           const BcastNext *nx) {
-    const uint32_t n = ctx->hc.n, k = ctx->hc.k, npt = pstride ? count : 1;
-    uint64_t *o = O->d + oi * O->item_words;
-    const uint64_t *src = A->d + ai * A->item_words;
+int mul_plain_fused(cn_ctx *ctx, CtSpan A, bool a_bcast, PtSpan P, CtSpan O, uint32_t polys, const BcastNext *nx) {
+    const uint32_t n = ctx->hc.n, k = ctx->hc.k, count = O.count, pstride = P.stride, npt = pstride ? count : 1;
+    const size_t item_words = (size_t)polys * k * n;
+    uint64_t *o = O.d;
+    const uint64_t *src = A.d;
     // one input ciphertext broadcast over the outputs: it must survive until the last block has read it
     const int pol = cn_policy(cn_mod_range(ctx->hc, 0, k), ctx->opt.f64);
     if (a_bcast && pstride && count >= 4 && ctx->opt.mp_bcast) {      // one ciphertext x many plaintexts: transform the ciphertext once, the plaintexts inside the product kernel
         uint64_t *ctn = nx ? nx->ctn : nullptr;
-        if (!nx) { CHECK(ensure_scratch(ctx, al(A->item_words * 8))); ctn = salloc<uint64_t>(ctx, A->item_words); }
+        if (!nx) { CHECK(ensure_scratch(ctx, al(item_words * 8))); ctn = salloc<uint64_t>(ctx, item_words); }
         if (!ctn) return fail(CN_ERR_HIP, "internal: scratch exhausted in multiply_plain");
-        HIPCHK(hipMemcpyAsync(ctn, src, A->item_words * 8, hipMemcpyDeviceToDevice, ctx->stream));
-        CHECK(cn_run_ntt(ctx, ctn, A->size * k, 0, k, 0));
-        rr_ops[pol]->mul_plain_bcast(ctx, P->d + (size_t)pi * n, pstride, ctn, o, count, A->size, nx ? (uint32_t)nx->elt : 0u, nx ? nx->out : nullptr);
+        HIPCHK(hipMemcpyAsync(ctn, src, item_words * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        CHECK(cn_run_ntt(ctx, ctn, polys * k, 0, k, 0));
+        rr_ops[pol]->mul_plain_bcast(ctx, P.d, pstride, ctn, o, count, polys, nx ? (uint32_t)nx->elt : 0u, nx ? nx->out : nullptr);
         HIPCHK(hipGetLastError()); launch_count(ctx);
-        ctx->st.ntt_forward_limbs += (uint64_t)A->size * k + (uint64_t)count * A->size * k; ctx->st.ntt_inverse_limbs += (uint64_t)count * A->size * k;
+        ctx->st.ntt_forward_limbs += (uint64_t)polys * k + (uint64_t)count * polys * k; ctx->st.ntt_inverse_limbs += (uint64_t)count * polys * k;
         ctx->st.PlainMultiplication += count;
         return 0;
     }
-    const bool alias = a_bcast && src >= o && src < o + (size_t)count * A->item_words;
-    CHECK(ensure_scratch(ctx, al((size_t)npt * k * n * 8) + (alias ? al(A->item_words * 8) : 0)));
+    const bool alias = a_bcast && src >= o && src < o + (size_t)count * item_words;
+    CHECK(ensure_scratch(ctx, al((size_t)npt * k * n * 8) + (alias ? al(item_words * 8) : 0)));
     uint64_t *lift = salloc<uint64_t>(ctx, (size_t)npt * k * n);
     if (alias) {
-        uint64_t *keep = salloc<uint64_t>(ctx, A->item_words);
+        uint64_t *keep = salloc<uint64_t>(ctx, item_words);
         if (!keep) return fail(CN_ERR_HIP, "internal: scratch exhausted in multiply_plain");
-        HIPCHK(hipMemcpyAsync(keep, src, A->item_words * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(keep, src, item_words * 8, hipMemcpyDeviceToDevice, ctx->stream));
         src = keep;
     }
     if (!lift) return fail(CN_ERR_HIP, "internal: scratch exhausted in multiply_plain");
-    const uint64_t *pt = P->d + (size_t)pi * n;
-    const size_t sstride = a_bcast ? 0 : A->item_words;
+    const size_t sstride = a_bcast ? 0 : item_words;
     const uint32_t pitch = pstride ? pstride : 1u, ps = pstride ? 1u : 0u;
-    rr_ops[pol]->mul_plain_fused(ctx, pt, pitch, npt, lift, src, sstride, ps, o, count, A->size);
+    rr_ops[pol]->mul_plain_fused(ctx, P.d, pitch, npt, lift, src, sstride, ps, o, count, polys);
     HIPCHK(hipGetLastError()); launch_count(ctx, 2);
-    ctx->st.ntt_forward_limbs += (uint64_t)npt * k + (uint64_t)count * A->size * k; ctx->st.ntt_inverse_limbs += (uint64_t)count * A->size * k;
+    ctx->st.ntt_forward_limbs += (uint64_t)npt * k + (uint64_t)count * polys * k; ctx->st.ntt_inverse_limbs += (uint64_t)count * polys * k;
     ctx->st.PlainMultiplication += count;
     return 0;
 }
 bool mul_plain_takes_bcast(cn_ctx *ctx, uint32_t count) { return ctx->opt.mp_fused && ctx->opt.mp_bcast && rr_kernels(ctx) && count >= 4; }
-int mul_plain_impl(cn_ctx *ctx, Buffer *A, uint32_t ai, bool a_bcast, Buffer *P, uint32_t pi, uint32_t pstride, Buffer *O, uint32_t oi, uint32_t count,
-                          const BcastNext *nx) {
-    if (!range_ok(A, ai, a_bcast ? 1 : count) || !range_ok(O, oi, count) || !range_ok(P, pi, pstride ? count : 1, pstride ? pstride : 1))
-        return fail(CN_ERR_ARG, "index out of range");
+// neither the same range nor disjoint: `words` words at a and at o overlap with a shift (a null operand overlaps nothing)
+bool shifted_overlap(const uint64_t *a, const uint64_t *o, size_t words) { return a && a != o && a < o + words && o < a + words; }
+static int mul_plain_overlap(const CtSpan &A, const CtSpan &O, size_t item_words) {      // block c writes out[c] while another block still reads in[c']
+    if (!shifted_overlap(A.d, O.d, O.count * item_words)) return 0;
+    return fail(CN_ERR_ARG, "multiply_plain: input and output ranges overlap partially (use the same range or disjoint ranges)");
+}
+static int plain_not_zero(const PtSpan &P, uint32_t count) {
+    for (uint32_t c = 0; P.zero && c < (P.stride ? count : 1u); c++) if (P.zero[c * P.stride]) return fail(CN_ERR_ZERO, "plain cannot be zero");
+    return 0;
+}
+int mul_plain_impl(cn_ctx *ctx, CtSpan A, bool a_bcast, PtSpan P, CtSpan O, uint32_t polys, const BcastNext *nx) {
+    const uint32_t n = ctx->hc.n, k = ctx->hc.k, count = O.count, pstride = P.stride, npt = pstride ? count : 1;
+    const size_t item_words = (size_t)polys * k * n;
     if (!count) return 0;
-    if (A == O && !a_bcast && ai != oi && ai < oi + count && oi < ai + count)          // block c writes out[c] while another block still reads in[c']
-        return fail(CN_ERR_ARG, "multiply_plain: input and output ranges overlap partially (use the same range or disjoint ranges)");
-    const uint32_t n = ctx->hc.n, k = ctx->hc.k, npt = pstride ? count : 1;
-    for (uint32_t c = 0; c < npt; c++) if (P->pt_zero[pi + c * pstride]) return fail(CN_ERR_ZERO, "plain cannot be zero");
-    if (ctx->opt.mp_fused && rr_kernels(ctx)) return mul_plain_fused(ctx, A, ai, a_bcast, P, pi, pstride, O, oi, count, nx);
+    if (!a_bcast) CHECK(mul_plain_overlap(A, O, item_words));
+    CHECK(plain_not_zero(P, count));
+    if (ctx->opt.mp_fused && rr_kernels(ctx)) return mul_plain_fused(ctx, A, a_bcast, P, O, polys, nx);
     if (nx) return fail(CN_ERR_ARG, "internal: chained row-dot batch outside the fused product");
     CHECK(ensure_scratch(ctx, al((size_t)npt * k * n * 8)));
     uint64_t *lift = salloc<uint64_t>(ctx, (size_t)npt * k * n);
     // lift every referenced plaintext into the k limbs (one launch), NTT them
-    hipLaunchKernelGGL(k_lift_plain, dim3(npt * k * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, P->d + (size_t)pi * n, lift, ctx->dc, ctx->chunks, pstride ? pstride : 1u);
+    hipLaunchKernelGGL(k_lift_plain, dim3(npt * k * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, P.d, lift, ctx->dc, ctx->chunks, pstride ? pstride : 1u);
     HIPCHK(hipGetLastError()); launch_count(ctx);
     CHECK(cn_run_ntt(ctx, lift, npt * k, 0, k, 0));
-    uint64_t *o = O->d + oi * O->item_words;
-    const uint64_t *src = A->d + ai * A->item_words;
+    uint64_t *o = O.d;
+    const uint64_t *src = A.d;
     if (a_bcast) {
         for (uint32_t c = 0; c < count; c++)
-            if (o + c * A->item_words != src) HIPCHK(hipMemcpyAsync(o + c * A->item_words, src, A->item_words * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    } else if (o != src) HIPCHK(hipMemcpyAsync(o, src, count * A->item_words * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    uint32_t limbs = count * A->size * k;
+            if (o + c * item_words != src) HIPCHK(hipMemcpyAsync(o + c * item_words, src, item_words * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    } else if (o != src) HIPCHK(hipMemcpyAsync(o, src, count * item_words * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    uint32_t limbs = count * polys * k;
     CHECK(cn_run_ntt(ctx, o, limbs, 0, k, 0));
-    hipLaunchKernelGGL(k_dyadic_pt, dim3(limbs * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, o, lift, pstride ? 1u : 0u, ctx->dc, ctx->chunks, A->size);
+    hipLaunchKernelGGL(k_dyadic_pt, dim3(limbs * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, o, lift, pstride ? 1u : 0u, ctx->dc, ctx->chunks, polys);
     HIPCHK(hipGetLastError()); launch_count(ctx);
     CHECK(cn_run_ntt(ctx, o, limbs, 0, k, 1));
     ctx->st.PlainMultiplication += count;
@@ -134,14 +140,13 @@ int mul_plain_impl(cn_ctx *ctx, Buffer *A, uint32_t ai, bool a_bcast, Buffer *P,
 }
 extern "C" int cn_mul_plain(cn_ctx *ctx, cn_handle a, uint32_t ai, cn_handle pt, uint32_t pi, uint32_t pstride, cn_handle out, uint32_t oi, uint32_t count) { API_BODY
     LOCK_ONLY; GETCT(A, a, 0); GETCT(O, out, A->size); GETPT(P, pt);
-    if (deferring(ctx) && count && count <= DEFER_STAGED_MAX && A->size == 2) {       // the per-row MultiplyPlain of an unchanged caller: queued, rows merged at flush
-        if (!range_ok(A, ai, count) || !range_ok(O, oi, count) || !range_ok(P, pi, pstride ? count : 1, pstride ? pstride : 1)) return fail(CN_ERR_ARG, "index out of range");
-        for (uint32_t c = 0; c < (pstride ? count : 1u); c++) if (P->pt_zero[pi + c * pstride]) return fail(CN_ERR_ZERO, "plain cannot be zero");
-        if (A == O && ai != oi && ai < oi + count && oi < ai + count) return fail(CN_ERR_ARG, "multiply_plain: input and output ranges overlap partially (use the same range or disjoint ranges)");
-        return defer_staged(ctx, DOP_MULPLAIN, A, ai, nullptr, 0, P->d + (size_t)pi * ctx->hc.n, pstride * ctx->hc.n, O, oi, count, 0);
+    SPAN(sa, A, ai, count); SPAN(so, O, oi, count); PTSPAN(sp, P, pi, count, pstride);
+    if (queues(ctx, count) && A->size == 2) {                   // the per-row MultiplyPlain of an unchanged caller: queued, rows merged at flush
+        CHECK(plain_not_zero(sp, count)); CHECK(mul_plain_overlap(sa, so, A->item_words));
+        return defer_staged(ctx, DOP_MULPLAIN, sa, CtSpan{}, so, 0, sp.d, pstride * ctx->hc.n);
     }
     CHECK(cn_defer_flush(ctx));
-    return mul_plain_impl(ctx, A, ai, false, P, pi, pstride, O, oi, count);
+    return mul_plain_impl(ctx, sa, false, sp, so, A->size);
 API_END }
 uint64_t lift_scalar(const DevConsts &hc, uint64_t w, uint32_t j) { return w >= hc.t_half ? w + hc.lift_inc[j] : w; }
 extern "C" int cn_mul_scalar(cn_ctx *ctx, cn_handle a, uint32_t ai, const uint64_t *scalars, uint32_t sstride, cn_handle out, uint32_t oi, uint32_t count) { API_BODY
@@ -538,30 +543,25 @@ int ks_planned_mode(cn_ctx *ctx, uint32_t cnt, int galois) {
     const int mode = ctx->opt.ks_wide == 2 || (ctx->opt.ks_wide < 0 && cnt * k > KS_DIGIT_MAX_BLOCKS && ctx->hc.logn < 14) ? 2 : 1;
     return (size_t)cnt * (mode == 2 ? k : tot_dig) * ctx->ctw2 * 8 > ctx->smax ? 0 : mode;
 }
+// One key switch.  call: the operands by name (KsCall, cn_runtime.h); the key words, accmax, mode, xcd_cts and the arena sizes are derived here.
 // perm_elt != 0 (two-launch variants only - the caller asks ks_planned_mode first): target / add0 are the c1 / c0 of the ciphertext a rotation
 // READS and the kernels apply the automorphism x -> x^perm_elt while loading them
 // N = 16384, fused path: one launch per key switch (k_keyswitch_pair14).  A rotation then hands in target = sigma(c1) (permuted ahead of time: k_galois_limbs, or the
 // previous link of a rotate-and-add chain), add0 = the unpermuted c0 and perm_elt; next_elt / next_out ask for sigma_next of the new c1 on the side.
-int do_keyswitch(cn_ctx *ctx, const uint64_t *target, size_t tstride, const uint64_t *add0, const uint64_t *add1, size_t astride,
-                        const KsKey &key, uint64_t *out, uint32_t cnt, int galois, const uint64_t *extra, size_t xstride,
-                        uint64_t *const *out_tab, uint32_t perm_elt, const KsItem *items, uint32_t next_elt, uint64_t *next_out, const double *dig) {
-    const uint32_t n = ctx->hc.n, k = ctx->hc.k, tot_dig = galois ? ctx->hc.gk_tot : ctx->hc.rl_tot;
+int do_keyswitch(cn_ctx *ctx, const KsKey &key, const KsCall &call) {
+    const uint32_t n = ctx->hc.n, k = ctx->hc.k, cnt = call.cnt, tot_dig = call.galois ? ctx->hc.gk_tot : ctx->hc.rl_tot;
     const CnModRange qr = cn_mod_range(ctx->hc, 0, k);
     const int bits = qr.bits, pol = cn_policy(qr, key.f64);          // by the form the key was loaded in (keys_as_f64 then), not by the "f64" option now
-    KsArgs a{target, tstride, add0, add1, astride, key.d, out, cnt, galois, extra, xstride,
+    KsArgs a{call, key.d,
              key.f64 ? (bits >= 50 ? 1u : (1u << std::min(10, 50 - bits))) : 0xffffffffu,     // lazy FP64 accumulators: |term| <= 2.1 q, sum below 2^52
-             0, out_tab};
+             ks_planned_mode(ctx, cnt, call.galois)};
     if (ctx->opt.ks_xcd == 1) a.xcd_cts = cnt & ~7u;
     else if (ctx->opt.ks_xcd == 2) a.xcd_cts = 0x80000000u;
     const bool rr = rr_kernels(ctx);
-    a.mode = ks_planned_mode(ctx, cnt, galois);
     if (a.mode) CHECK(ensure_ks_part(ctx, (size_t)cnt * (a.mode == 2 ? k : tot_dig) * ctx->ctw2 * 8));
-    a.perm_elt = perm_elt; a.items = items;
-    a.next_elt = next_elt; a.next_out = next_out;
-    a.dig = dig;
-    if (dig && !(rr && key.f64 && ctx->hc.logn <= 13 && !galois && !ctx->hc.ks_xi)) return fail(CN_ERR_ARG, "internal: ready-made digits outside the FP64 register-radix key switch");
-    const bool pair = ks_pair14_ok(ctx, cnt, galois, key);
-    if ((perm_elt || items || next_elt) && !a.mode && !(pair && !items)) return fail(CN_ERR_ARG, "internal: automorphism inside the fused key switch");
+    if (a.dig && !(rr && key.f64 && ctx->hc.logn <= 13 && !a.galois && !ctx->hc.ks_xi)) return fail(CN_ERR_ARG, "internal: ready-made digits outside the FP64 register-radix key switch");
+    const bool pair = ks_pair14_ok(ctx, cnt, a.galois, key);
+    if ((a.perm_elt || a.items || a.next_elt) && !a.mode && !(pair && !a.items)) return fail(CN_ERR_ARG, "internal: automorphism inside the fused key switch");
     if (pair) {                                                                                      // N = 16384: both 8192-point halves of a limb in one workgroup, one launch
         CHECK(ensure_ks_part(ctx, (size_t)cnt * ctx->ctw2 * 8));
         a.xcd_cts = ctx->opt.ks_xcd == 1 ? (cnt & ~7u) : 0u;
@@ -569,8 +569,8 @@ int do_keyswitch(cn_ctx *ctx, const uint64_t *target, size_t tstride, const uint
     } else if (a.mode == 0 && rr && key.f64 && ctx->hc.logn == 14 && ctx->hc.twdh && ctx->opt.ks_split14) {   // ... as two workgroups per limb + a combining pass (rounds 1-4; A/B)
         CHECK(ensure_ks_part(ctx, (size_t)cnt * ctx->ctw2 * 8));
         ks_ops[pol]->split14(ctx, a);
-        hipLaunchKernelGGL(k_ks_combine14, dim3(cnt * 2 * k * (n / 512)), dim3(256), 0, ctx->stream, (const uint64_t *)ctx->ks_part, add0, add1, astride, out, ctx->dc,
-                           extra, xstride, out_tab);
+        hipLaunchKernelGGL(k_ks_combine14, dim3(cnt * 2 * k * (n / 512)), dim3(256), 0, ctx->stream, (const uint64_t *)ctx->ks_part, a.add0, a.add1, a.astride, a.out, ctx->dc,
+                           a.extra, a.xstride, a.out_tab);
         launch_count(ctx);
     } else {
         const bool done = rr && ks_ops[pol]->launch(ctx, a);
@@ -578,8 +578,9 @@ int do_keyswitch(cn_ctx *ctx, const uint64_t *target, size_t tstride, const uint
         if (!done) {                        // radix-2 LDS fallback (N < 1024, legacy_ntt): no fused accumulator -> one element-wise add behind it
             // The accumulator may be the result's own array (SumAllSlots adds in place): the key switch then writes into the key-switch arena
             // (unused by this path) and the add reads it beside the untouched accumulator.  (Writing `out` first doubled the key switch there.)
-            if (extra) {
-                if (xstride != ctx->ctw2 || out_tab) return fail(CN_ERR_ARG, "internal: accumulator stride");
+            uint64_t *const out = a.out;
+            if (a.extra) {
+                if (a.xstride != ctx->ctw2 || a.out_tab) return fail(CN_ERR_ARG, "internal: accumulator stride");
                 CHECK(ensure_ks_part(ctx, (size_t)cnt * ctx->ctw2 * 8));
                 a.out = (uint64_t *)ctx->ks_part;
             }
@@ -592,8 +593,8 @@ int do_keyswitch(cn_ctx *ctx, const uint64_t *target, size_t tstride, const uint
                 case 16: launch_ks_legacy<16>(ctx, nt, a); break;
                 default: return fail(CN_ERR_ARG, "unsupported poly modulus degree for key switching");
             }
-            if (extra) {
-                hipLaunchKernelGGL(k_addsub, dim3(cnt * 2 * k * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, (const uint64_t *)ctx->ks_part, extra, out, ctx->dc,
+            if (a.extra) {
+                hipLaunchKernelGGL(k_addsub, dim3(cnt * 2 * k * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, (const uint64_t *)ctx->ks_part, a.extra, out, ctx->dc,
                                    ctx->chunks, 0);
                 launch_count(ctx);
             }
@@ -632,7 +633,7 @@ extern "C" int cn_relinearize(cn_ctx *ctx, cn_handle in3, uint32_t ii, cn_handle
     if (!count) return 0;
     const size_t kn = (size_t)ctx->hc.k * ctx->hc.n;
     const uint64_t *p = I->d + ii * I->item_words;
-    CHECK(do_keyswitch(ctx, p + 2 * kn, 3 * kn, p, p + kn, 3 * kn, ctx->rlk, O->d + oi * O->item_words, count, 0));
+    CHECK(do_keyswitch(ctx, ctx->rlk, KsCall::relin(p, kn, count).to(O->d + oi * O->item_words)));
     ctx->st.Relinarization += count;
     return 0;
 API_END }
@@ -671,7 +672,7 @@ int mul_relin_body(cn_ctx *ctx, cn_handle a, uint32_t ai, uint32_t astride, cn_h
         CHECK(ensure_scratch(ctx, per * c + 8192));
         uint64_t *t3 = salloc<uint64_t>(ctx, (size_t)c * 3 * kn);
         auto mul = [&](uint32_t f, uint32_t n_) { return do_multiply(ctx, pa + (size_t)(s + f) * astride * A->item_words, astride, pb + (size_t)(s + f) * bstride * B->item_words, bstride, t3 + (size_t)f * 3 * kn, n_); };
-        auto ksw = [&](uint32_t f, uint32_t n_) { uint64_t *t = t3 + (size_t)f * 3 * kn; return do_keyswitch(ctx, t + 2 * kn, 3 * kn, t, t + kn, 3 * kn, ctx->rlk, O->d + (oi + s + f) * O->item_words, n_, 0); };
+        auto ksw = [&](uint32_t f, uint32_t n_) { return do_keyswitch(ctx, ctx->rlk, KsCall::relin(t3 + (size_t)f * 3 * kn, kn, n_).to(O->d + (oi + s + f) * O->item_words)); };
         if (ctx->opt.sq_halves && ctx->hc.logn <= 13 && c >= SQ_HALVES_MIN && !ctx->capturing && pipeline_fused_ks(ctx, c) && aux_stream_ready(ctx)) {
             CHECK(pipelined_halves(ctx, c, mul, ksw)); continue;
         }
@@ -736,7 +737,7 @@ extern "C" int cn_square_gemm(cn_ctx *ctx, cn_handle plan, cn_handle in, uint32_
     if (P.dig_mfma) { dg.W = P.dev + P.off_w; dg.mfma = true; dg.P = P.P; dg.mtiles = P.mtiles; dg.ksteps = P.ksteps; }
     CHECK(cn_l_digit_gemm(ctx, dg));
     uint64_t *o = OB->d + oi * OB->item_words;
-    CHECK(do_keyswitch(ctx, nullptr, 0, o, o + kn, 2 * kn, ctx->rlk, o, P.O, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, S));
+    CHECK(do_keyswitch(ctx, ctx->rlk, KsCall::relin_digits(S, o, kn, P.O).to(o)));
     ctx->st.Relinarization += cnt; ctx->sg_fused++;
     return 0;
 API_END }
@@ -845,7 +846,7 @@ extern "C" int cn_mul_relin_sum(cn_ctx *ctx, const cn_handle *a, const uint32_t 
         }
         uint64_t *o = O->d + (size_t)(oi + o0) * O->item_words;
         CHECK(cn_l_product_sum(ctx, ProductSumLaunch{t3, K, o, S, go}));          // (sum d0, sum d1) straight into the outputs, the digit sums into S
-        CHECK(do_keyswitch(ctx, nullptr, 0, o, o + kn, 2 * kn, ctx->rlk, o, go, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, S));
+        CHECK(do_keyswitch(ctx, ctx->rlk, KsCall::relin_digits(S, o, kn, go).to(o)));
         ctx->ms_groups++;
     }
     ctx->st.Relinarization += (uint64_t)K * count; ctx->st.AddMany += count; ctx->st.AddManyItemCount += (uint64_t)count * K;
@@ -854,135 +855,97 @@ extern "C" int cn_mul_relin_sum(cn_ctx *ctx, const cn_handle *a, const uint32_t 
 API_END }
 
 // ---------------------------------------------------------------- rotations
-// in/out device pointers to size-2 ciphertext arrays; tmp holds count size-2 ciphertexts
-// acc != nullptr: out = acc + galois(in) in the same launches (acc may alias out and/or in)
-// pre: sigma_elt(c1) of `in` if somebody has produced it already ([ct][k][N]); next_elt / next_out: see do_keyswitch (both only on the one-launch N = 16384 path)
-int do_galois(cn_ctx *ctx, const uint64_t *in, uint64_t elt, uint64_t *out, uint64_t *tmp, uint32_t count, const uint64_t *acc,
-                     const uint64_t *pre, uint64_t next_elt, uint64_t *next_out) {
-    auto it = ctx->gk.find(elt);
-    if (it == ctx->gk.end() || !it->second.d) return fail(CN_ERR_NOKEY, "Galois key not present");
-
+const KsKey *galois_key(cn_ctx *ctx, uint64_t elt) { auto it = ctx->gk.find(elt); return it != ctx->gk.end() && it->second.d ? &it->second : nullptr; }
+static int columns_key(cn_ctx *ctx) { return galois_key(ctx, 2ull * ctx->hc.n - 1) ? 0 : fail(CN_ERR_NOKEY, "Galois key not present"); }
+// The rotate-and-ADD forms refuse an operand or accumulator that overlaps the result with a shift: the fused accumulator is read where the result is stored, no path
+// reads it ahead of the stores
+static int add_overlap(cn_ctx *ctx, const uint64_t *in, const uint64_t *acc, const uint64_t *out, uint32_t count) {
+    if (!shifted_overlap(in, out, count * ctx->ctw2) && !shifted_overlap(acc, out, count * ctx->ctw2)) return 0;
+    return fail(CN_ERR_ARG, "rotate-and-add: operand / accumulator and result ranges overlap partially (use the same range or disjoint ranges)");
+}
+// in / out: `count` size-2 ciphertexts each, tmp holds as many; acc: out = acc + galois(in) in the same launches (acc may alias out and/or in)
+// pre: sigma_elt(c1) of `in` if somebody has produced it already ([ct][k][N]); next_elt / next_out: see KsCall (both only on the one-launch N = 16384 path)
+int do_galois(cn_ctx *ctx, const GaloisCall &g) {
+    const KsKey *key = galois_key(ctx, g.elt);
+    if (!key) return fail(CN_ERR_NOKEY, "Galois key not present");
     const size_t kn = (size_t)ctx->hc.k * ctx->hc.n;
-    uint32_t limbs = count * 2 * ctx->hc.k;
-    // (the one-launch kernel reads c0 of `in` while other workgroups already write `out`: safe when the two arrays are the same or disjoint - a workgroup only touches
-    // its own (ciphertext, limb) - not when they overlap with a shift: those calls keep the permutation pass, which has read all of `in` before anything is written)
-    const bool shifted = in != out && in < out + (size_t)count * ctx->ctw2 && out < in + (size_t)count * ctx->ctw2;
-    const bool acc_shifted = acc && acc != out && acc < out + (size_t)count * ctx->ctw2 && out < acc + (size_t)count * ctx->ctw2;
-    if (acc_shifted) return fail(CN_ERR_ARG, "rotate-and-add: accumulator and result ranges overlap partially (use the same range or disjoint ranges)");
-    if (!shifted && ks_pair14_ok(ctx, count, 1, it->second)) {           // N = 16384, batch: c1 is permuted once (here unless the caller brings it), c0 inside the key switch
-        if (!pre) {
-            hipLaunchKernelGGL(k_galois_limbs, dim3(count * ctx->hc.k), dim3(1024), (size_t)ctx->hc.n * 8, ctx->stream, in + kn, 2 * kn, tmp, kn, ctx->dc, elt);
+    const uint32_t count = g.count, limbs = count * 2 * ctx->hc.k, elt = (uint32_t)g.elt;
+    // A result range that overlaps the operand range with a SHIFT (the same handle, different first indices): the kernels that apply the automorphism while they
+    // load (one-launch N = 16384 kernel, two-launch small-batch kernels) would read ciphertext c after another workgroup has written c' over it - safe when the two
+    // arrays are the same or disjoint, a workgroup only touches its own (ciphertext, limb).  Shifted calls keep the permutation pass, which has read all of `in`
+    // before anything is written (they used to be refused on every path).
+    const bool shifted = shifted_overlap(g.in, g.out, count * ctx->ctw2);
+    CHECK(add_overlap(ctx, nullptr, g.acc, g.out, count));
+    KsCall ks;
+    if (!shifted && ks_pair14_ok(ctx, count, 1, *key)) {                 // N = 16384, batch: c1 is permuted once (here unless the caller brings it), c0 inside the key switch
+        if (!g.pre) {
+            hipLaunchKernelGGL(k_galois_limbs, dim3(count * ctx->hc.k), dim3(1024), (size_t)ctx->hc.n * 8, ctx->stream, g.in + kn, 2 * kn, g.tmp, kn, ctx->dc, g.elt);
             HIPCHK(hipGetLastError()); launch_count(ctx);
-            pre = tmp;
         }
-        CHECK(do_keyswitch(ctx, pre, kn, in, nullptr, 2 * kn, it->second, out, count, 1, acc, ctx->ctw2, nullptr, (uint32_t)elt, nullptr, (uint32_t)next_elt, next_out));
-        ctx->st.Rotation += count;
-        if (acc) ctx->st.Addition += count;
-        return 0;
+        ks = KsCall::galois_of(g.pre ? g.pre : g.tmp, kn, g.in, kn, count).perm(elt).next((uint32_t)g.next_elt, g.next_out);
+    } else if (g.pre || g.next_elt) return fail(CN_ERR_ARG, "internal: rotation chain outside the one-launch key switch");
+    else if (!shifted && ctx->opt.ks_perm_fused && ks_planned_mode(ctx, count, 1) != 0)      // small batches (two-launch key switch): no permutation pass - the
+        ks = KsCall::galois_of(g.in + kn, 2 * kn, g.in, kn, count).perm(elt);                // key-switch kernels apply the automorphism while they load c1 and c0
+    else {
+        if (ctx->hc.n >= 1024) hipLaunchKernelGGL(k_galois_lds, dim3(limbs), dim3(std::min<uint32_t>(1024, ctx->hc.n / 4)), (size_t)ctx->hc.n * 8, ctx->stream, g.in, g.tmp, ctx->dc, g.elt);
+        else hipLaunchKernelGGL(k_galois, dim3(limbs * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, g.in, g.tmp, ctx->dc, ctx->chunks, g.elt);
+        HIPCHK(hipGetLastError()); launch_count(ctx);
+        ks = KsCall::galois_of(g.tmp + kn, 2 * kn, g.tmp, kn, count);
     }
-    if (pre || next_elt) return fail(CN_ERR_ARG, "internal: rotation chain outside the one-launch key switch");
-    // small batches (two-launch key switch): no permutation pass - the key-switch kernels apply the automorphism while they load c1 and c0
-    if (!shifted && ctx->opt.ks_perm_fused && ks_planned_mode(ctx, count, 1) != 0) {
-        CHECK(do_keyswitch(ctx, in + kn, 2 * kn, in, nullptr, 2 * kn, it->second, out, count, 1, acc, ctx->ctw2, nullptr, (uint32_t)elt));
-        ctx->st.Rotation += count;
-        if (acc) ctx->st.Addition += count;
-        return 0;
-    }
-    if (ctx->hc.n >= 1024) hipLaunchKernelGGL(k_galois_lds, dim3(limbs), dim3(std::min<uint32_t>(1024, ctx->hc.n / 4)), (size_t)ctx->hc.n * 8, ctx->stream, in, tmp, ctx->dc, elt);
-    else hipLaunchKernelGGL(k_galois, dim3(limbs * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, in, tmp, ctx->dc, ctx->chunks, elt);
-    HIPCHK(hipGetLastError()); launch_count(ctx);
-    CHECK(do_keyswitch(ctx, tmp + kn, 2 * kn, tmp, nullptr, 2 * kn, it->second, out, count, 1, acc, ctx->ctw2));
+    CHECK(do_keyswitch(ctx, *key, ks.to(g.out).plus(g.acc, ctx->ctw2)));
     ctx->st.Rotation += count;
-    if (acc) ctx->st.Addition += count;
+    if (g.acc) ctx->st.Addition += count;
     return 0;
 }
-// A rotation whose result range overlaps its operand range with a SHIFT (the same handle, different first indices): the kernels that apply the automorphism while they
-// load (one-launch N = 16384 kernel, two-launch small-batch kernels) would read ciphertext c after another workgroup has written c' over it - such calls take the
-// permutation pass (do_galois: `shifted`), which has read the whole operand before anything is written (they used to be refused on every path).  Only the
-// rotate-and-ADD forms still refuse a partially overlapping ACCUMULATOR: no path reads it ahead of the stores.
-bool shifted_overlap(const Buffer *I, uint32_t ii, const Buffer *O, uint32_t oi, uint32_t count) { return I == O && ii != oi && ii < oi + count && oi < ii + count; }
-int galois_impl(cn_ctx *ctx, Buffer *I, uint32_t ii, uint64_t elt, Buffer *O, uint32_t oi, uint32_t count) {
-    if (!range_ok(I, ii, count) || !range_ok(O, oi, count)) return fail(CN_ERR_ARG, "index out of range");
-    if (!count) return 0;
-    CHECK(ensure_scratch(ctx, al(count * ctx->ctw2 * 8)));
-    uint64_t *tmp = salloc<uint64_t>(ctx, count * ctx->ctw2);
-    return do_galois(ctx, I->d + ii * I->item_words, elt, O->d + oi * O->item_words, tmp, count);
+// scratch for `arrays` arrays of `count` size-2 ciphertexts; returns the first
+static int ct_scratch(cn_ctx *ctx, uint32_t count, uint32_t arrays, uint64_t **first) {
+    CHECK(ensure_scratch(ctx, al(count * ctx->ctw2 * 8) * arrays));
+    *first = salloc<uint64_t>(ctx, count * ctx->ctw2);
+    return 0;
 }
-bool galois_key_present(cn_ctx *ctx, uint64_t elt) { auto it = ctx->gk.find(elt); return it != ctx->gk.end() && it->second.d; }
+int galois_impl(cn_ctx *ctx, CtSpan in, uint64_t elt, CtSpan acc, CtSpan out) {      // acc.d: out = acc + galois(in)
+    if (acc.d) CHECK(add_overlap(ctx, in.d, acc.d, out.d, out.count));
+    if (!out.count) return 0;
+    uint64_t *tmp; CHECK(ct_scratch(ctx, out.count, 1, &tmp));
+    return do_galois(ctx, {.in = in.d, .elt = elt, .out = out.d, .tmp = tmp, .count = out.count, .acc = acc.d});
+}
 extern "C" int cn_apply_galois(cn_ctx *ctx, cn_handle in, uint32_t ii, uint64_t elt, cn_handle out, uint32_t oi, uint32_t count) { API_BODY TWO_LIMBS("cn_apply_galois");
-    LOCK; GETCT(I, in, 2); GETCT(O, out, 2);
-    CHECK(galois_impl(ctx, I, ii, elt, O, oi, count));
+    LOCK; GETCT(I, in, 2); GETCT(O, out, 2); SPAN(si, I, ii, count); SPAN(so, O, oi, count);
+    CHECK(galois_impl(ctx, si, elt, CtSpan{}, so));
     rec_galois(ctx, elt);
     return 0;
 API_END }
-// Evaluator::rotate_internal: direct key if present, otherwise non-adjacent-form decomposition
-bool has_direct_key(cn_ctx *ctx, int steps) {
-    uint64_t elt = cn_galois_elt_from_step(ctx, steps);
-    auto it = ctx->gk.find(elt);
-    return elt && it != ctx->gk.end() && it->second.d;
+// Evaluator::rotate_internal with the keys this context holds (cn_rotation.h): the hops of RotateRows(steps), or the refusal.  Queued rotations are checked with it
+// when they are queued, like every other argument
+int plan_rotation(cn_ctx *ctx, int steps, CnRotPlan *plan) {
+    const CnRotPlan p = cn_rotation_plan(ctx->hc.n, steps, [ctx](uint64_t e) { return galois_key(ctx, e) != nullptr; });
+    if (plan) *plan = p;
+    return p.rc ? fail(p.rc, "%s", p.msg) : 0;
 }
-int rotate_rec(cn_ctx *ctx, uint64_t *cur, int steps, uint64_t *tmp, uint32_t count) {
-    if (steps == 0) return 0;
-    uint64_t elt = cn_galois_elt_from_step(ctx, steps);
-    if (!elt) return fail(CN_ERR_ARG, "step count too large");
-    auto it = ctx->gk.find(elt);
-    if (it != ctx->gk.end() && it->second.d) return do_galois(ctx, cur, elt, cur, tmp, count);
-    std::vector<int> naf;
-    bool sign = steps < 0; int v = std::abs(steps);
-    for (int i = 0; v; i++) { int zi = (v & 1) ? 2 - (v & 3) : 0; v = (v - zi) >> 1; if (zi) naf.push_back((sign ? -zi : zi) * (1 << i)); }
-    if (naf.size() == 1) return fail(CN_ERR_NOKEY, "Galois key not present");
-    for (int s : naf) {
-        if ((uint32_t)std::abs(s) == ctx->hc.n / 2) continue;
-        CHECK(rotate_rec(ctx, cur, s, tmp, count));
-    }
+// the hops of a plan one after the other, in place
+static int rotate_hops(cn_ctx *ctx, const CnRotPlan &p, uint64_t *cur, uint64_t *tmp, uint32_t count) {
+    for (uint32_t h = 0; h < p.hops; h++) CHECK(do_galois(ctx, {.in = cur, .elt = p.elt[h], .out = cur, .tmp = tmp, .count = count}));
     return 0;
 }
-int rotate_rows_impl(cn_ctx *ctx, Buffer *I, uint32_t ii, int steps, Buffer *O, uint32_t oi, uint32_t count) {
-    if (!range_ok(I, ii, count) || !range_ok(O, oi, count)) return fail(CN_ERR_ARG, "index out of range");
+int rotate_rows_impl(cn_ctx *ctx, CtSpan in, int steps, CtSpan out) {
+    const uint32_t count = out.count;
     if (!count) return 0;
-    const bool shifted = shifted_overlap(I, ii, O, oi, count);
-    CHECK(ensure_scratch(ctx, al(count * ctx->ctw2 * 8) * (shifted ? 2 : 1)));
-    uint64_t *tmp = salloc<uint64_t>(ctx, count * ctx->ctw2);
-    uint64_t *o = O->d + oi * O->item_words; const uint64_t *i = I->d + ii * I->item_words;
-    if (steps != 0 && has_direct_key(ctx, steps)) return do_galois(ctx, i, cn_galois_elt_from_step(ctx, steps), o, tmp, count);   // one hop: no staging copy
+    CnRotPlan p; CHECK(plan_rotation(ctx, steps, &p));                   // (a refused rotation enqueues nothing and leaves `out` as it is)
+    const bool shifted = shifted_overlap(in.d, out.d, count * ctx->ctw2);
+    uint64_t *tmp; CHECK(ct_scratch(ctx, count, shifted ? 2 : 1, &tmp));
+    if (p.hops == 1) return do_galois(ctx, {.in = in.d, .elt = p.elt[0], .out = out.d, .tmp = tmp, .count = count});   // one hop: no staging copy
     if (shifted) {                                    // overlapping ranges: through a staging array (a device-to-device copy between overlapping ranges is undefined)
         uint64_t *stage = salloc<uint64_t>(ctx, count * ctx->ctw2);
-        HIPCHK(hipMemcpyAsync(stage, i, count * ctx->ctw2 * 8, hipMemcpyDeviceToDevice, ctx->stream));
-        HIPCHK(hipMemcpyAsync(o, stage, count * ctx->ctw2 * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    } else if (o != i) HIPCHK(hipMemcpyAsync(o, i, count * ctx->ctw2 * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    return rotate_rec(ctx, o, steps, tmp, count);
-}
-// can RotateRows(steps) run with the keys this context holds (direct key, or every hop of the NAF decomposition)?  Queued rotations are
-// checked when they are queued, like every other argument.
-int rotate_check(cn_ctx *ctx, int steps) {
-    if (steps == 0) return 0;
-    const uint64_t elt = cn_galois_elt_from_step(ctx, steps);
-    if (!elt) return fail(CN_ERR_ARG, "step count too large");
-    if (galois_key_present(ctx, elt)) return 0;
-    std::vector<int> naf;
-    bool sign = steps < 0; int v = std::abs(steps);
-    for (int i = 0; v; i++) { int zi = (v & 1) ? 2 - (v & 3) : 0; v = (v - zi) >> 1; if (zi) naf.push_back((sign ? -zi : zi) * (1 << i)); }
-    if (naf.size() == 1) return fail(CN_ERR_NOKEY, "Galois key not present");
-    for (int s2 : naf) { if ((uint32_t)std::abs(s2) == ctx->hc.n / 2) continue; CHECK(rotate_check(ctx, s2)); }
-    return 0;
-}
-int rotation_hops(cn_ctx *ctx, int steps, std::vector<uint64_t> &elts) {
-    if (steps == 0) return 0;
-    const uint64_t elt = cn_galois_elt_from_step(ctx, steps);
-    if (!elt) return fail(CN_ERR_ARG, "step count too large");
-    if (galois_key_present(ctx, elt)) { elts.push_back(elt); return 0; }
-    std::vector<int> naf;
-    bool sign = steps < 0; int v = std::abs(steps);
-    for (int i = 0; v; i++) { int zi = (v & 1) ? 2 - (v & 3) : 0; v = (v - zi) >> 1; if (zi) naf.push_back((sign ? -zi : zi) * (1 << i)); }
-    if (naf.size() == 1) return fail(CN_ERR_NOKEY, "Galois key not present");
-    for (int s2 : naf) { if ((uint32_t)std::abs(s2) == ctx->hc.n / 2) continue; CHECK(rotation_hops(ctx, s2, elts)); }
-    return 0;
+        HIPCHK(hipMemcpyAsync(stage, in.d, count * ctx->ctw2 * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(out.d, stage, count * ctx->ctw2 * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    } else if (out.d != in.d) HIPCHK(hipMemcpyAsync(out.d, in.d, count * ctx->ctw2 * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    return rotate_hops(ctx, p, out.d, tmp, count);
 }
 int rotate_jobs(cn_ctx *ctx, std::vector<RotJob> &jobs) {
     const uint32_t n = (uint32_t)jobs.size();
     if (!n) return 0;
-    size_t rounds = 0;
-    for (RotJob &j : jobs) { CHECK(rotation_hops(ctx, j.steps, j.elts)); rounds = std::max(rounds, j.elts.size()); }
+    uint32_t rounds = 0;
+    for (RotJob &j : jobs) { CHECK(plan_rotation(ctx, j.steps, &j.plan)); rounds = std::max(rounds, j.plan.hops); }
     bool aliased = false;
     for (uint32_t a = 0; a < n && !aliased; a++) for (uint32_t b = 0; b < n; b++) if (a != b && (jobs[a].dst == jobs[b].src || jobs[a].dst == jobs[b].dst)) { aliased = true; break; }
     bool tables_ok = ctx->opt.ks_perm_fused && !aliased && ks_planned_mode(ctx, n, 1) != 0;
@@ -995,7 +958,6 @@ int rotate_jobs(cn_ctx *ctx, std::vector<RotJob> &jobs) {
         if (piece) {
             for (uint32_t s0 = 0; s0 < n; s0 += piece) {
                 std::vector<RotJob> part(jobs.begin() + s0, jobs.begin() + std::min<uint32_t>(n, s0 + piece));
-                for (RotJob &j : part) j.elts.clear();
                 CHECK(rotate_jobs(ctx, part));
             }
             return 0;
@@ -1006,25 +968,25 @@ int rotate_jobs(cn_ctx *ctx, std::vector<RotJob> &jobs) {
         for (RotJob &j : jobs) {
             ctx->soff = 0;
             uint64_t *tmp = salloc<uint64_t>(ctx, ctx->ctw2);
-            if (j.elts.size() == 1) { CHECK(do_galois(ctx, j.src, j.elts[0], j.dst, tmp, 1)); continue; }
+            if (j.plan.hops == 1) { CHECK(do_galois(ctx, {.in = j.src, .elt = j.plan.elt[0], .out = j.dst, .tmp = tmp, .count = 1})); continue; }
             if (j.dst != j.src) HIPCHK(hipMemcpyAsync(j.dst, j.src, ctx->ctw2 * 8, hipMemcpyDeviceToDevice, ctx->stream));
-            for (uint64_t e : j.elts) CHECK(do_galois(ctx, j.dst, e, j.dst, tmp, 1));
+            CHECK(rotate_hops(ctx, j.plan, j.dst, tmp, 1));
         }
         return 0;
     }
     {   // rotations by 0 steps: copies
         std::vector<Tab2> cp;
-        for (RotJob &j : jobs) if (j.elts.empty() && j.dst != j.src) cp.push_back({(const NTT_GLOBAL uint64_t *)j.src, (NTT_GLOBAL uint64_t *)j.dst});
+        for (RotJob &j : jobs) if (!j.plan.hops && j.dst != j.src) cp.push_back({(const NTT_GLOBAL uint64_t *)j.src, (NTT_GLOBAL uint64_t *)j.dst});
         if (!cp.empty()) { CHECK(ensure_stage(ctx, al(cp.size() * sizeof(Tab2)))); CHECK(copy_by_table(ctx, cp, (Tab2 *)ctx->stage, (uint32_t)ctx->ctw2)); }
     }
-    for (size_t r = 0; r < rounds; r++) {
+    for (uint32_t r = 0; r < rounds; r++) {
         std::vector<KsItem> items; std::vector<uint64_t *> outs;
         const KsKey *any = nullptr;
         for (RotJob &j : jobs) {
-            if (j.elts.size() <= r) continue;
-            const KsKey &key = ctx->gk.find(j.elts[r])->second;
+            if (j.plan.hops <= r) continue;
+            const KsKey &key = *galois_key(ctx, j.plan.elt[r]);
             any = &key;
-            items.push_back({r == 0 ? j.src : j.dst, key.d, (uint32_t)j.elts[r], 0u});
+            items.push_back({r == 0 ? j.src : j.dst, key.d, (uint32_t)j.plan.elt[r], 0u});
             outs.push_back(j.dst);
         }
         const uint32_t cnt = (uint32_t)items.size();
@@ -1035,107 +997,84 @@ int rotate_jobs(cn_ctx *ctx, std::vector<RotJob> &jobs) {
         const void *p_items, *p_outs;
         CHECK(place_table(ctx, items.data(), cnt * sizeof(KsItem), d_items, &p_items));
         CHECK(place_table(ctx, outs.data(), cnt * sizeof(uint64_t *), d_outs, &p_outs));
-        CHECK(do_keyswitch(ctx, nullptr, 0, nullptr, nullptr, 0, *any, nullptr, cnt, 1, nullptr, 0, (uint64_t *const *)p_outs, 0, (const KsItem *)p_items));
+        CHECK(do_keyswitch(ctx, *any, KsCall::galois_items((const KsItem *)p_items, cnt).to_table((uint64_t *const *)p_outs)));
         ctx->st.Rotation += cnt;
     }
     return 0;
 }
 
-extern "C" int cn_rotate_rows(cn_ctx *ctx, cn_handle in, uint32_t ii, int steps, cn_handle out, uint32_t oi, uint32_t count) { API_BODY TWO_LIMBS("cn_rotate_rows");
-    LOCK_ONLY; GETCT(I, in, 2); GETCT(O, out, 2);
-    if (deferring(ctx) && count && count <= DEFER_STAGED_MAX) {
-        if (!range_ok(I, ii, count) || !range_ok(O, oi, count)) return fail(CN_ERR_ARG, "index out of range");
-        CHECK(rotate_check(ctx, steps));
-        rec_rows(ctx, steps);
-        return defer_staged(ctx, DOP_ROT, I, ii, nullptr, 0, nullptr, 0, O, oi, count, steps);
-    }
-    CHECK(cn_defer_flush(ctx));
-    CHECK(rotate_rows_impl(ctx, I, ii, steps, O, oi, count));
-    rec_rows(ctx, steps);                                   // (a refused call leaves no step behind)
-    return 0;
-API_END }
 // RotateRows of n ciphertexts by n different step counts, one launch chain (see include/cnhip.h)
 extern "C" int cn_rotate_rows_many(cn_ctx *ctx, cn_handle in, const uint32_t *ii, const int *steps, uint32_t n, cn_handle out, const uint32_t *oi) { API_BODY TWO_LIMBS("cn_rotate_rows_many");
     LOCK_ONLY; GETCT(I, in, 2); GETCT(O, out, 2);
     if (!n) return 0;
     if (!ii || !steps || !oi) return fail(CN_ERR_ARG, "null argument");
+    std::vector<RotJob> jobs(n);
     for (uint32_t i = 0; i < n; i++) {
-        if (!range_ok(I, ii[i], 1) || !range_ok(O, oi[i], 1)) return fail(CN_ERR_ARG, "index out of range");
-        CHECK(rotate_check(ctx, steps[i]));
+        SPAN(si, I, ii[i], 1); SPAN(so, O, oi[i], 1);
+        CHECK(plan_rotation(ctx, steps[i]));
         for (uint32_t j = 0; j < i; j++) if (O == I ? (oi[i] == oi[j] || oi[i] == ii[j] || ii[i] == oi[j]) : oi[i] == oi[j])
             return fail(CN_ERR_ARG, "rotate_rows_many: a result would overwrite another rotation's operand or result");
+        jobs[i] = {si.d, so.d, steps[i]};
     }
     for (uint32_t i = 0; i < n; i++) rec_rows(ctx, steps[i]);               // (every argument has been checked)
     if (deferring(ctx)) {                                   // queued like n cn_rotate_rows calls
-        for (uint32_t i = 0; i < n; i++) CHECK(defer_staged(ctx, DOP_ROT, I, ii[i], nullptr, 0, nullptr, 0, O, oi[i], 1, steps[i]));
+        for (const RotJob &j : jobs) CHECK(defer_staged(ctx, DOP_ROT, CtSpan{const_cast<uint64_t *>(j.src), 1}, CtSpan{}, CtSpan{j.dst, 1}, j.steps));
         return 0;
     }
     CHECK(cn_defer_flush(ctx));
-    std::vector<RotJob> jobs(n);
-    for (uint32_t i = 0; i < n; i++) jobs[i] = {I->d + (size_t)ii[i] * I->item_words, O->d + (size_t)oi[i] * O->item_words, steps[i], {}};
     return rotate_jobs(ctx, jobs);
 API_END }
-// out = acc + RotateRows(in, steps): the rotate-and-add step of SumAllSlots (AtomicSealBfvVector.cs:862-868) with the addition
-// fused into the last kernel of the key switch.  Same words as cn_rotate_rows followed by cn_add.
-int rotate_rows_add_impl(cn_ctx *ctx, Buffer *I, uint32_t ii, int steps, Buffer *A, uint32_t ai, Buffer *O, uint32_t oi, uint32_t count) {
-    if (!range_ok(I, ii, count) || !range_ok(A, ai, count) || !range_ok(O, oi, count)) return fail(CN_ERR_ARG, "index out of range");
-    if (shifted_overlap(I, ii, O, oi, count) || shifted_overlap(A, ai, O, oi, count))          // (the fused accumulator is read where the result is stored: no path reads it ahead)
-        return fail(CN_ERR_ARG, "rotate-and-add: operand / accumulator and result ranges overlap partially (use the same range or disjoint ranges)");
-    if (!count) return 0;
-    const uint64_t *i = I->d + ii * I->item_words, *a = A->d + ai * A->item_words; uint64_t *o = O->d + oi * O->item_words;
-    if (steps == 0) {
-        hipLaunchKernelGGL(k_addsub, dim3(count * 2 * ctx->hc.k * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, i, a, o, ctx->dc, ctx->chunks, 0);
-        HIPCHK(hipGetLastError()); launch_count(ctx);
-        ctx->st.Addition += count;
-        return 0;
-    }
-    if (has_direct_key(ctx, steps)) {
-        CHECK(ensure_scratch(ctx, al(count * ctx->ctw2 * 8)));
-        uint64_t *tmp = salloc<uint64_t>(ctx, count * ctx->ctw2);
-        return do_galois(ctx, i, cn_galois_elt_from_step(ctx, steps), o, tmp, count, a);
-    }
-    // multi-hop (NAF) rotation: rotate into a staging array, then one element-wise add
-    CHECK(ensure_scratch(ctx, al(count * ctx->ctw2 * 8) * 2));
-    uint64_t *tmp = salloc<uint64_t>(ctx, count * ctx->ctw2), *stage = salloc<uint64_t>(ctx, count * ctx->ctw2);
-    HIPCHK(hipMemcpyAsync(stage, i, count * ctx->ctw2 * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    CHECK(rotate_rec(ctx, stage, steps, tmp, count));
-    hipLaunchKernelGGL(k_addsub, dim3(count * 2 * ctx->hc.k * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, a, stage, o, ctx->dc, ctx->chunks, 0);
+static int add_kernel(cn_ctx *ctx, const uint64_t *a, const uint64_t *b, uint64_t *out, uint32_t count) {
+    hipLaunchKernelGGL(k_addsub, dim3(count * 2 * ctx->hc.k * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, a, b, out, ctx->dc, ctx->chunks, 0);
     HIPCHK(hipGetLastError()); launch_count(ctx);
     ctx->st.Addition += count;
     return 0;
 }
-int rotate_columns_add_impl(cn_ctx *ctx, Buffer *I, uint32_t ii, Buffer *A, uint32_t ai, Buffer *O, uint32_t oi, uint32_t count) {
-    if (!range_ok(I, ii, count) || !range_ok(A, ai, count) || !range_ok(O, oi, count)) return fail(CN_ERR_ARG, "index out of range");
-    if (shifted_overlap(I, ii, O, oi, count) || shifted_overlap(A, ai, O, oi, count))          // (the fused accumulator is read where the result is stored: no path reads it ahead)
-        return fail(CN_ERR_ARG, "rotate-and-add: operand / accumulator and result ranges overlap partially (use the same range or disjoint ranges)");
+// out = acc + RotateRows(in, steps): the rotate-and-add step of SumAllSlots (AtomicSealBfvVector.cs:862-868) with the addition
+// fused into the last kernel of the key switch.  Same words as cn_rotate_rows followed by cn_add.
+int rotate_rows_add_impl(cn_ctx *ctx, CtSpan in, int steps, CtSpan acc, CtSpan out) {
+    const uint32_t count = out.count;
+    CHECK(add_overlap(ctx, in.d, acc.d, out.d, count));
     if (!count) return 0;
-    CHECK(ensure_scratch(ctx, al(count * ctx->ctw2 * 8)));
-    uint64_t *tmp = salloc<uint64_t>(ctx, count * ctx->ctw2);
-    return do_galois(ctx, I->d + ii * I->item_words, 2ull * ctx->hc.n - 1, O->d + oi * O->item_words, tmp, count, A->d + ai * A->item_words);
+    CnRotPlan p; CHECK(plan_rotation(ctx, steps, &p));                   // (a refused rotation enqueues nothing)
+    if (!p.hops) return add_kernel(ctx, in.d, acc.d, out.d, count);
+    uint64_t *tmp; CHECK(ct_scratch(ctx, count, p.hops > 1 ? 2 : 1, &tmp));
+    if (p.hops == 1) return do_galois(ctx, {.in = in.d, .elt = p.elt[0], .out = out.d, .tmp = tmp, .count = count, .acc = acc.d});
+    // multi-hop (NAF) rotation: rotate into a staging array, then one element-wise add
+    uint64_t *stage = salloc<uint64_t>(ctx, count * ctx->ctw2);
+    HIPCHK(hipMemcpyAsync(stage, in.d, count * ctx->ctw2 * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    CHECK(rotate_hops(ctx, p, stage, tmp, count));
+    return add_kernel(ctx, acc.d, stage, out.d, count);
 }
-extern "C" int cn_rotate_rows_add(cn_ctx *ctx, cn_handle in, uint32_t ii, int steps, cn_handle acc, uint32_t ai, cn_handle out, uint32_t oi, uint32_t count) { API_BODY TWO_LIMBS("cn_rotate_rows_add");
-    LOCK_ONLY; GETCT(I, in, 2); GETCT(A, acc, 2); GETCT(O, out, 2);
-    if (deferring(ctx) && count && count <= DEFER_STAGED_MAX) {
-        if (!range_ok(I, ii, count) || !range_ok(A, ai, count) || !range_ok(O, oi, count)) return fail(CN_ERR_ARG, "index out of range");
-        CHECK(rotate_check(ctx, steps));
-        rec_rows(ctx, steps);
-        return defer_staged(ctx, DOP_ROTADD, I, ii, A, ai, nullptr, 0, O, oi, count, steps);
-    }
+// cn_rotate_rows and cn_rotate_rows_add (acc.d null: no accumulator) behind their range checks.  Queued (defer = 1, up to DEFER_STAGED_MAX ciphertexts): the keys are
+// asked through the planner now, like every other argument; else everything pending is flushed and the call runs at once.  A refused call records no step.
+static int rotate_rows_call(cn_ctx *ctx, CtSpan in, int steps, CtSpan acc, CtSpan out) {
+    if (queues(ctx, out.count)) { CHECK(plan_rotation(ctx, steps)); rec_rows(ctx, steps); return defer_staged(ctx, acc.d ? DOP_ROTADD : DOP_ROT, in, acc, out, steps); }
     CHECK(cn_defer_flush(ctx));
-    CHECK(rotate_rows_add_impl(ctx, I, ii, steps, A, ai, O, oi, count));
+    CHECK(acc.d ? rotate_rows_add_impl(ctx, in, steps, acc, out) : rotate_rows_impl(ctx, in, steps, out));
     rec_rows(ctx, steps);
     return 0;
+}
+// ... and the column swap the same way; it is recorded only when its key is present (an empty call asks for no key)
+static int rotate_columns_call(cn_ctx *ctx, CtSpan in, CtSpan acc, CtSpan out) {
+    const uint64_t elt = 2ull * ctx->hc.n - 1;
+    if (queues(ctx, out.count)) { CHECK(columns_key(ctx)); rec_columns(ctx); return defer_staged(ctx, acc.d ? DOP_COLSADD : DOP_COLS, in, acc, out, 0); }
+    CHECK(cn_defer_flush(ctx));
+    CHECK(galois_impl(ctx, in, elt, acc, out));
+    if (galois_key(ctx, elt)) rec_columns(ctx);
+    return 0;
+}
+extern "C" int cn_rotate_rows(cn_ctx *ctx, cn_handle in, uint32_t ii, int steps, cn_handle out, uint32_t oi, uint32_t count) { API_BODY TWO_LIMBS("cn_rotate_rows");
+    LOCK_ONLY; GETCT(I, in, 2); GETCT(O, out, 2); SPAN(si, I, ii, count); SPAN(so, O, oi, count);
+    return rotate_rows_call(ctx, si, steps, CtSpan{}, so);
+API_END }
+extern "C" int cn_rotate_rows_add(cn_ctx *ctx, cn_handle in, uint32_t ii, int steps, cn_handle acc, uint32_t ai, cn_handle out, uint32_t oi, uint32_t count) { API_BODY TWO_LIMBS("cn_rotate_rows_add");
+    LOCK_ONLY; GETCT(I, in, 2); GETCT(A, acc, 2); GETCT(O, out, 2); SPAN(si, I, ii, count); SPAN(sa, A, ai, count); SPAN(so, O, oi, count);
+    return rotate_rows_call(ctx, si, steps, sa, so);
 API_END }
 extern "C" int cn_rotate_columns_add(cn_ctx *ctx, cn_handle in, uint32_t ii, cn_handle acc, uint32_t ai, cn_handle out, uint32_t oi, uint32_t count) { API_BODY TWO_LIMBS("cn_rotate_columns_add");
-    LOCK_ONLY; GETCT(I, in, 2); GETCT(A, acc, 2); GETCT(O, out, 2);
-    if (galois_key_present(ctx, 2ull * ctx->hc.n - 1)) rec_columns(ctx);     // (without the key the call is refused below)
-    if (deferring(ctx) && count && count <= DEFER_STAGED_MAX) {
-        if (!range_ok(I, ii, count) || !range_ok(A, ai, count) || !range_ok(O, oi, count)) return fail(CN_ERR_ARG, "index out of range");
-        if (!galois_key_present(ctx, 2ull * ctx->hc.n - 1)) return fail(CN_ERR_NOKEY, "Galois key not present");
-        return defer_staged(ctx, DOP_COLSADD, I, ii, A, ai, nullptr, 0, O, oi, count, 0);
-    }
-    CHECK(cn_defer_flush(ctx));
-    return rotate_columns_add_impl(ctx, I, ii, A, ai, O, oi, count);
+    LOCK_ONLY; GETCT(I, in, 2); GETCT(A, acc, 2); GETCT(O, out, 2); SPAN(si, I, ii, count); SPAN(sa, A, ai, count); SPAN(so, O, oi, count);
+    return rotate_columns_call(ctx, si, sa, so);
 API_END }
 // SumAllSlots(length) of AtomicSealBfvVector.cs:888-935 on `count` single-block ciphertexts at once, in place: the column swap when
 // length >= N/2, then log2 rotate-and-add steps (RotateRows(-2^s) + AddInplace).  length 0 = all N slots.
@@ -1146,14 +1085,14 @@ std::vector<uint64_t> sum_slots_chain_elts(cn_ctx *ctx, uint32_t count, uint32_t
     bool ok = ctx->opt.ks_chain && count > 0;
     uint32_t l2 = length ? length : n;
     if (l2 >= half) { elts.push_back(2ull * n - 1); l2 = half; }
-    for (uint32_t steps = 1; steps < l2 && ok; steps *= 2) { if (has_direct_key(ctx, -(int)steps)) elts.push_back(cn_galois_elt_from_step(ctx, -(int)steps)); else ok = false; }
-    for (uint64_t e : elts) { auto it = ctx->gk.find(e); if (it == ctx->gk.end() || !it->second.d || !ks_pair14_ok(ctx, count, 1, it->second)) { ok = false; break; } }
+    for (uint32_t steps = 1; steps < l2 && ok; steps *= 2) elts.push_back(cn_elt_of_step(n, -(int)steps));
+    for (uint64_t e : elts) { const KsKey *key = galois_key(ctx, e); if (!key || !ks_pair14_ok(ctx, count, 1, *key)) { ok = false; break; } }
     if (!ok || elts.size() < 2) elts.clear();
     return elts;
 }
-// first_ready: the scratch arena already holds sigma_(elts[0])(c1) of every ciphertext at its start (written by the producer of H: k_mul_plain_bcast) and is large enough
-int sum_slots_impl(cn_ctx *ctx, Buffer *H, uint32_t first, uint32_t count, uint32_t length, bool first_ready) {
-    const uint32_t n = ctx->hc.n, half = n / 2;
+// first_ready: the scratch arena already holds sigma_(elts[0])(c1) of every ciphertext at its start (written by the producer of h: k_mul_plain_bcast) and is large enough
+int sum_slots_impl(cn_ctx *ctx, CtSpan h, uint32_t length, bool first_ready) {
+    const uint32_t n = ctx->hc.n, half = n / 2, count = h.count;
     uint32_t len = length ? length : n;
     {   // N = 16384, batch: the links of the chain as ONE launch each - link s leaves sigma_(s+1) of its new c1 beside its result (k_keyswitch_pair14), so only the
         // first link needs a permutation pass (none when the producer has left it).  Same words as the loop below (the same key switches on the same operands).
@@ -1163,30 +1102,31 @@ int sum_slots_impl(cn_ctx *ctx, Buffer *H, uint32_t first, uint32_t count, uint3
             const size_t kn = (size_t)ctx->hc.k * n;
             if (first_ready) ctx->soff = 0; else CHECK(ensure_scratch(ctx, al(count * ctx->ctw2 * 8)));
             uint64_t *pp[2]; pp[0] = salloc<uint64_t>(ctx, count * ctx->ctw2); pp[1] = pp[0] + (size_t)count * kn;
-            uint64_t *h = H->d + first * H->item_words;
-            for (size_t s = 0; s < elts.size(); s++)
-                CHECK(do_galois(ctx, h, elts[s], h, pp[s & 1], count, h, (s || first_ready) ? pp[s & 1] : nullptr, s + 1 < elts.size() ? elts[s + 1] : 0, pp[(s + 1) & 1]));
+            for (size_t s = 0; s < elts.size(); s++) {
+                const bool last = s + 1 == elts.size();
+                CHECK(do_galois(ctx, {.in = h.d, .elt = elts[s], .out = h.d, .tmp = pp[s & 1], .count = count, .acc = h.d, .pre = (s || first_ready) ? pp[s & 1] : nullptr,
+                                      .next_elt = last ? 0 : elts[s + 1], .next_out = pp[(s + 1) & 1]}));
+            }
             return 0;
         }
     }
-    if (len >= half) { CHECK(rotate_columns_add_impl(ctx, H, first, H, first, H, first, count)); len = half; }
-    for (uint32_t steps = 1; steps < len; steps *= 2) CHECK(rotate_rows_add_impl(ctx, H, first, -(int)steps, H, first, H, first, count));
+    if (len >= half) { CHECK(galois_impl(ctx, h, 2ull * n - 1, h, h)); len = half; }
+    for (uint32_t steps = 1; steps < len; steps *= 2) CHECK(rotate_rows_add_impl(ctx, h, -(int)steps, h, h));
     return 0;
 }
 extern "C" int cn_sum_slots(cn_ctx *ctx, cn_handle h, uint32_t first, uint32_t count, uint32_t length) { API_BODY TWO_LIMBS("cn_sum_slots");
-    LOCK_ONLY; GETCT(H, h, 2);
-    if (!range_ok(H, first, count)) return fail(CN_ERR_ARG, "index out of range");
+    LOCK_ONLY; GETCT(H, h, 2); SPAN(sh, H, first, count);
     if (!count) return 0;
-    if (deferring(ctx) && count <= DEFER_STAGED_MAX) {
+    if (queues(ctx, count)) {
         const uint32_t n = ctx->hc.n, half = n / 2;
         uint32_t len = length ? length : n;
-        if (len >= half) { if (!galois_key_present(ctx, 2ull * n - 1)) return fail(CN_ERR_NOKEY, "Galois key not present"); len = half; }
-        for (uint32_t st = 1; st < len; st *= 2) CHECK(rotate_check(ctx, -(int)st));
+        if (len >= half) { CHECK(columns_key(ctx)); len = half; }
+        for (uint32_t st = 1; st < len; st *= 2) CHECK(plan_rotation(ctx, -(int)st));
         rec_sum_slots(ctx, length);
-        return defer_staged(ctx, DOP_SUMSLOTS, H, first, nullptr, 0, nullptr, 0, H, first, count, length);
+        return defer_staged(ctx, DOP_SUMSLOTS, sh, CtSpan{}, sh, length);
     }
     CHECK(cn_defer_flush(ctx));
-    CHECK(sum_slots_impl(ctx, H, first, count, length));
+    CHECK(sum_slots_impl(ctx, sh, length));
     rec_sum_slots(ctx, length);
     return 0;
 API_END }
@@ -1196,23 +1136,24 @@ extern "C" int cn_rowdot_batch(cn_ctx *ctx, cn_handle v, uint32_t vi, cn_handle 
     LOCK; GETCT(V, v, 2); GETCT(O, out, 2); GETPT(P, pt);
     if (!rows) return 0;
     if (V == O && vi >= oi && vi < oi + rows) return fail(CN_ERR_ARG, "row-dot batch cannot overwrite its input");
+    SPAN(sv, V, vi, 1); SPAN(so, O, oi, rows); PTSPAN(sp, P, pi, rows, 1u);
     if (length != 1) rec_sum_slots(ctx, length);
     if (length != 1 && mul_plain_takes_bcast(ctx, rows)) {
         // the product kernel hands the chain its first permuted c1 (no k_galois_limbs pass over the products): one arena for the chain's two scratch arrays and the
         // transformed ciphertext, sized here and left where it is until the chain has run
         const std::vector<uint64_t> elts = sum_slots_chain_elts(ctx, rows, length);
         if (!elts.empty()) {
-            CHECK(ensure_scratch(ctx, al(rows * ctx->ctw2 * 8) + al(V->item_words * 8)));
-            uint64_t *p0 = salloc<uint64_t>(ctx, rows * ctx->ctw2), *ctn = salloc<uint64_t>(ctx, V->item_words);
+            CHECK(ensure_scratch(ctx, al(rows * ctx->ctw2 * 8) + al(ctx->ctw2 * 8)));
+            uint64_t *p0 = salloc<uint64_t>(ctx, rows * ctx->ctw2), *ctn = salloc<uint64_t>(ctx, ctx->ctw2);
             if (!p0 || !ctn) return fail(CN_ERR_HIP, "internal: scratch exhausted in the row-dot batch");
             const BcastNext nx{elts[0], p0, ctn};
-            CHECK(mul_plain_impl(ctx, V, vi, true, P, pi, 1, O, oi, rows, &nx));
-            return sum_slots_impl(ctx, O, oi, rows, length, true);
+            CHECK(mul_plain_impl(ctx, sv, true, sp, so, 2, &nx));
+            return sum_slots_impl(ctx, so, length, true);
         }
     }
-    CHECK(mul_plain_impl(ctx, V, vi, true, P, pi, 1, O, oi, rows));
+    CHECK(mul_plain_impl(ctx, sv, true, sp, so, 2));
     if (length == 1) return 0;
-    return sum_slots_impl(ctx, O, oi, rows, length);
+    return sum_slots_impl(ctx, so, length);
 API_END }
 // out[oi + g] = sum over the terms e of group g of MultiplyPlain(ct[ci + ct_idx[e]], pt[pi + e]) (include/cnhip.h).  Register-radix sizes: the distinct
 // ciphertexts transformed once into scratch (like `ctn` of the row-dot batch), then ONE launch of k_mul_plain_sum; other sizes: cn_mul_plain per term into a temporary
@@ -1248,7 +1189,8 @@ extern "C" int cn_mul_plain_sum(cn_ctx *ctx, cn_handle ct, uint32_t ci, cn_handl
             const uint32_t len = grp_off[g + 1] - grp_off[g];
             Buffer *T = getbuf(ctx, tmp, 0);                                      // (the handle table may have moved)
             A = getbuf(ctx, ct, 0); O = getbuf(ctx, out, 0); P = getbuf(ctx, pt, 1);
-            for (uint32_t i = 0; i < len && !rc; i++) rc = mul_plain_impl(ctx, A, ci + ct_idx[grp_off[g] + i], false, P, pi + grp_off[g] + i, 1, T, i, 1);
+            for (uint32_t i = 0, e = grp_off[g]; i < len && !rc; i++, e++)      // (ranges and zero plaintexts were checked above)
+                rc = mul_plain_impl(ctx, CtSpan{A->d + (ci + ct_idx[e]) * ctx->ctw2, 1}, false, PtSpan{P->d + (size_t)(pi + e) * n, 1, nullptr}, CtSpan{T->d + i * ctx->ctw2, 1}, 2);
             if (rc) break;
             if ((rc = ensure_scratch(ctx, al((size_t)len * 4)))) break;
             uint32_t *didx;
@@ -1292,13 +1234,6 @@ extern "C" int cn_mul_plain_sum(cn_ctx *ctx, cn_handle ct, uint32_t ci, cn_handl
     return 0;
 API_END }
 extern "C" int cn_rotate_columns(cn_ctx *ctx, cn_handle in, uint32_t ii, cn_handle out, uint32_t oi, uint32_t count) { API_BODY TWO_LIMBS("cn_rotate_columns");
-    LOCK_ONLY; GETCT(I, in, 2); GETCT(O, out, 2);
-    if (galois_key_present(ctx, 2ull * ctx->hc.n - 1)) rec_columns(ctx);     // (without the key the call is refused below)
-    if (deferring(ctx) && count && count <= DEFER_STAGED_MAX) {
-        if (!range_ok(I, ii, count) || !range_ok(O, oi, count)) return fail(CN_ERR_ARG, "index out of range");
-        if (!galois_key_present(ctx, 2ull * ctx->hc.n - 1)) return fail(CN_ERR_NOKEY, "Galois key not present");
-        return defer_staged(ctx, DOP_COLS, I, ii, nullptr, 0, nullptr, 0, O, oi, count, 0);
-    }
-    CHECK(cn_defer_flush(ctx));
-    return galois_impl(ctx, I, ii, 2ull * ctx->hc.n - 1, O, oi, count);
+    LOCK_ONLY; GETCT(I, in, 2); GETCT(O, out, 2); SPAN(si, I, ii, count); SPAN(so, O, oi, count);
+    return rotate_columns_call(ctx, si, CtSpan{}, so);
 API_END }

@@ -249,21 +249,41 @@ struct cn_ctx {
 // per-ciphertext operands of a two-launch key switch that rotates every ciphertext by its own step count (cn_rotate_rows_many): the ciphertext it reads
 // (c0 at in, c1 behind it), the Galois key of its element, the element
 struct KsItem { const uint64_t *in; const void *key; uint32_t elt, pad; };
-struct KsArgs {
-    const uint64_t *target; size_t tstride;
-    const uint64_t *add0, *add1; size_t astride;
-    const uint64_t *key; uint64_t *out; uint32_t cnt; int galois;
-    const uint64_t *extra; size_t xstride;
-    uint32_t accmax;          // FP64 accumulators: terms between recentrings
-    int mode;                 // 0 fused, 1 two launches / workgroup per digit, 2 two launches / workgroup per source limb
-    uint64_t *const *out_tab;
-    uint32_t xcd_cts = 0;     // fused kernel: ciphertexts (a multiple of 8) placed XCD-aware, see k_keyswitch_rr
+// KsCall: the operands a caller of do_keyswitch names - by designated initialisers or through the constructors of the three shapes that occur; do_keyswitch
+// derives the rest of KsArgs (key words, accmax, mode, xcd_cts) and the launchers read both parts
+struct KsCall {
+    const uint64_t *target = nullptr; size_t tstride = 0;
+    const uint64_t *add0 = nullptr, *add1 = nullptr; size_t astride = 0;
+    uint64_t *out = nullptr; uint32_t cnt = 0; int galois = 0;
+    const uint64_t *extra = nullptr; size_t xstride = 0;
+    uint64_t *const *out_tab = nullptr;
     const KsItem *items = nullptr;   // two-launch variants: per-ciphertext (operand, key, element) table instead of target / add0 / key / perm_elt
     uint32_t perm_elt = 0;    // two-launch variants: Galois element of a rotation whose automorphism the kernels apply while loading (target / add0 = the UNPERMUTED c1 / c0)
                               // k_keyswitch_pair14: target = sigma(c1) already, add0 = the UNPERMUTED c0 (permuted through LDS by the workgroup that owns the limb)
     uint32_t next_elt = 0; uint64_t *next_out = nullptr;   // k_keyswitch_pair14: the new c1 leaves a second time as sigma_next(c1) -> next_out[ct][k][N] (rotate-and-add chains)
     const double *dig = nullptr;     // register-radix kernels, FP64 policies, relinearisation: ready-made digit polynomials [cnt][rl_tot][N] (exact signed doubles, |S| < q_j / 2)
                                      // instead of `target` (cn_square_gemm: the weight-combined digits of a dense layer's inputs)
+    // The shapes (kn = k N words per polynomial): relinearise the products prod [cnt][3][kn]; relinearise from the digit polynomials S on top of the size-2
+    // ciphertexts base [cnt][2][kn]; Galois switch of c1 (c1_stride apart) with c0 [cnt][2][kn] added, or of every ciphertext with its own operand, key and element
+    static KsCall relin(const uint64_t *prod, size_t kn, uint32_t cnt) {
+        return {.target = prod + 2 * kn, .tstride = 3 * kn, .add0 = prod, .add1 = prod + kn, .astride = 3 * kn, .cnt = cnt};
+    }
+    static KsCall relin_digits(const double *S, const uint64_t *base, size_t kn, uint32_t cnt) { return {.add0 = base, .add1 = base + kn, .astride = 2 * kn, .cnt = cnt, .dig = S}; }
+    static KsCall galois_of(const uint64_t *c1, size_t c1_stride, const uint64_t *c0, size_t kn, uint32_t cnt) {
+        return {.target = c1, .tstride = c1_stride, .add0 = c0, .astride = 2 * kn, .cnt = cnt, .galois = 1};
+    }
+    static KsCall galois_items(const KsItem *items, uint32_t cnt) { return {.cnt = cnt, .galois = 1, .items = items}; }
+    KsCall &to(uint64_t *dense) { out = dense; return *this; }                       // results: a dense size-2 array, or one address per ciphertext
+    KsCall &to_table(uint64_t *const *tab) { out_tab = tab; return *this; }
+    KsCall &plus(const uint64_t *acc, size_t stride) { extra = acc; xstride = stride; return *this; }      // the fused accumulator (may be null)
+    KsCall &perm(uint32_t elt) { perm_elt = elt; return *this; }
+    KsCall &next(uint32_t elt, uint64_t *nout) { next_elt = elt; next_out = nout; return *this; }
+};
+struct KsArgs : KsCall {
+    const uint64_t *key;
+    uint32_t accmax;          // FP64 accumulators: terms between recentrings
+    int mode;                 // 0 fused, 1 two launches / workgroup per digit, 2 two launches / workgroup per source limb
+    uint32_t xcd_cts = 0;     // fused kernel: ciphertexts (a multiple of 8) placed XCD-aware, see k_keyswitch_rr
 };
 // k_encrypt_fold (cn_k_rr.hip.h): a scalar-product output that receives the weighted sum of `count` folded zero encryptions, and the terms of all outputs
 struct FoldOut { uint64_t *out; uint32_t first, count; };               // terms [first, first + count) of the term table

@@ -391,7 +391,8 @@ int cn_apply_galois(cn_ctx *ctx, cn_handle in, uint32_t ii, uint64_t galois_elt,
  * (AtomicSealBfvVector.cs:625,631,637,660,864,1420,1458).  Operand and result ranges of ONE handle may be the same range (in place), disjoint, or
  * overlap with a shift (cn_rotate_rows, cn_apply_galois, cn_rotate_columns: such a call takes the permutation pass / a staging copy, which reads the whole
  * operand before anything is written).  The _add forms refuse a partial overlap of operand or accumulator with the result (CN_ERR_ARG): their fused
- * accumulator is read where the result is stored. */
+ * accumulator is read where the result is stored.  The hops are planned before anything is copied or launched: a rotation that is refused for a missing
+ * key (CN_ERR_NOKEY) or a step count of N/2 or more (CN_ERR_ARG) enqueues nothing and leaves the result range untouched. */
 int cn_rotate_rows(cn_ctx *ctx, cn_handle in, uint32_t ii, int steps, cn_handle out, uint32_t oi, uint32_t count);
 /* RotateRows of n ciphertexts by n DIFFERENT step counts: out[oi[i]] = RotateRows(in[ii[i]], steps[i]), same words as n cn_rotate_rows calls.
  * The reference rotates the vectors of an Interleave / a Vectorize one Evaluator.RotateRows at a time (AtomicSealBfvVector.cs:628-688); here the

@@ -68,7 +68,7 @@ def test_ntt_domain_automorphism_is_the_gather(n):
 
 # ---------------------------------------------------------------- hop counts
 def naf_hops(n, steps, have):
-    """key switches of RotateRows(steps) with keys for the elements `have`: rotation_hops of cn_eval.hip - one if the step's own key exists, else the sum
+    """key switches of RotateRows(steps) with keys for the elements `have`: cn_rotation_plan of cn_rotation.h - one if the step's own key exists, else the sum
     over the terms of its non-adjacent form (a term of N/2 is skipped); None if a term has no key"""
     if steps == 0:
         return 0

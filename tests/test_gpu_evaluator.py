@@ -1449,3 +1449,38 @@ def test_rotate_rows_many(name, rng):
     assert g.stats()["kernel_launches"] - l0 < 40
     for x in (h, out, w, hb):
         g.free(x)
+
+
+def test_refused_multi_hop_rotation_leaves_no_trace(rng):
+    """A context with the Galois keys of the steps 1 and 4 only.  RotateRows(7) = (-1) + 8 in non-adjacent form has no key for either hop: the call is refused with
+    CN_ERR_NOKEY when it is planned - nothing launched, the result range as uploaded, no step recorded - and under deferred submission at the call, not at the flush.
+    RotateRows(5) = 1 + 4 runs both hops and gives the oracle's words."""
+    from cryptonets_amd._native import CnError, Context
+    p, o = PARAMS["tiny"], get_oracle("tiny", galois=True)
+    g = Context(p["n"], p["t"], q=p["q"], dbc=p["dbc"], gdbc=p["gdbc"], device=0)
+    have = {o.galois_elt_from_step(1), o.galois_elt_from_step(4)}
+    for i, e in enumerate(o.galois_elts()):
+        if e in have:
+            g.set_galois_key(e, o.galois_key(i))
+    assert sorted(g.galois_elts()) == sorted(have)
+    vals, cts = enc_batch(o, rng, 4)
+    h, out = up(g, cts[:2]), up(g, cts[2:])
+    g.set_option("record_steps", 1)
+    for defer in (0, 1):
+        g.set_option("defer", defer)
+        try:
+            l0 = g.stats()["kernel_launches"]
+            with pytest.raises(CnError) as err:
+                g.rotate_rows(h, 0, 7, out, 0, 2)
+            assert err.value.code == -3, err.value
+            assert g.stats()["kernel_launches"] == l0
+            assert np.array_equal(g.ct_download(out, 0, 2), cts[2:])              # (a download flushes the queue: nothing was queued)
+            assert g.stats()["kernel_launches"] == l0
+            assert g.rotation_steps() == ([], False)
+        finally:
+            g.set_option("defer", 0)
+    g.rotate_rows(h, 0, 5, out, 0, 2)
+    assert np.array_equal(g.ct_download(out, 0, 2), np.stack([o.rotate_rows(c, 5) for c in cts[:2]]))
+    assert g.rotation_steps() == ([5], False)
+    g.close()
+
