@@ -373,6 +373,7 @@ extern "C" int cn_set_option(cn_ctx *ctx, const char *name, int value) { API_BOD
     }
     if (!strcmp(name, "defer_square_gemm")) { ctx->defer_square_gemm = value != 0; return 0; }     // (LOCK has settled what the queue held back under the old value)
     if (!strcmp(name, "digit_mfma")) { ctx->digit_mfma = value != 0; defer_square_drop_plans(ctx); return 0; }     // the digit GEMM of plans made AFTER the call: matrix cores where eligible / FP64 (cn_eval.hip)
+    if (!strcmp(name, "digit_i32")) { ctx->digit_i32 = value != 0; defer_square_drop_plans(ctx); return 0; }       // the digit sums of plans made AFTER the call (and of cn_mul_relin_sum): int32 words where they fit / doubles
     if (!strcmp(name, "mul_sum")) { ctx->mul_sum = value != 0; return 0; }       // cn_mul_relin_sum: one key switch per output where it can / always the literal sequence (cn_eval.hip)
     if (!strcmp(name, "record_steps")) {         // 1: record the RotateRows steps and column rotations asked for from now on (cn_rotation_steps); 0: stop and clear
         ctx->rec_steps = value != 0;
@@ -390,6 +391,7 @@ extern "C" int cn_get_option(cn_ctx *ctx, const char *name, int *value) { API_BO
     else if (!strcmp(name, "ks_xi")) *value = (int)ctx->hc.ks_xi;
     else if (!strcmp(name, "record_steps")) *value = ctx->rec_steps;
     else if (!strcmp(name, "digit_mfma")) *value = ctx->digit_mfma;
+    else if (!strcmp(name, "digit_i32")) *value = ctx->digit_i32;
     else if (!strcmp(name, "defer_square_gemm")) *value = ctx->defer_square_gemm;
     else if (!strcmp(name, "mul_sum")) *value = ctx->mul_sum;
     // read-only diagnostics: choices the library made and counters (tests)
@@ -403,6 +405,7 @@ extern "C" int cn_get_option(cn_ctx *ctx, const char *name, int *value) { API_BO
     else if (!strcmp(name, "mul_sum_min_k")) *value = (int)MUL_SUM_MIN_K;                                                   // smallest K that takes that form
     else if (!strcmp(name, "defer_pending_products")) *value = (int)ctx->dq->sq->out.size();                             // squarings whose relinearisation is held back right now
     else if (!strcmp(name, "digit_gemm_mfma")) *value = (int)std::min<uint64_t>(ctx->dg_mfma, 0x7fffffff);                 // digit GEMMs launched in the matrix-core form
+    else if (!strcmp(name, "ks_digits_i32")) *value = (int)std::min<uint64_t>(ctx->ks_dig_i32, 0x7fffffff);                // key switches launched on int32 digit sums
     else if (!strcmp(name, "packed_bad_residues")) *value = (int)std::min<uint64_t>(ctx->packed_bad.load(), 0x7fffffff);      // packed uploads that held a residue >= its modulus
     else if (!strcmp(name, "mul_relin_pipelined")) *value = (int)std::min<uint64_t>(ctx->mr_pipelined, 0x7fffffff);      // Multiply + Relinearize batches run in parts over two streams
     else if (!strcmp(name, "behz_small_base")) *value = ctx->hc.bsk[ctx->hc.kb - 1].q < (1ull << 49);     // auxiliary primes below 2^49 (FP64 kernels) instead of SEAL's 61-bit ones

@@ -111,7 +111,8 @@ struct GemmPlan {
     char *dev = nullptr;                     // persistent plans: device copy of `host`
     // cn_square_gemm: the layer may run on the digits of the unrelinearized products (square_gemm_plan_ok) - signed weights [G][mtiles][dKw][dMT] at off_dw
     // dig_mfma: the digit GEMM runs on the matrix cores from the fragments at off_w (no table at off_dw)
-    bool dig = false, dig_mfma = false; uint32_t dMT = 0, dKw = 0; size_t off_dw = 0;
+    // dig_i32: every digit sum fits a signed 32-bit word (cn_digit_sum_fits_i32 of the largest row, "digit_i32" on): S is stored and read as int32 words
+    bool dig = false, dig_mfma = false, dig_i32 = false; uint32_t dMT = 0, dKw = 0; size_t off_dw = 0;
 };
 // ---- deferred squarings that feed the next dense layer (cn_set_option "defer_square_gemm", cn_defer.hip).  A layer-boundary flush runs only the Multiply half of the
 // squarings it launches: the size-3 products stay in `arr` ([slot][3][k][N], owned by the context, grown on demand and never while a graph is alive), the callers'

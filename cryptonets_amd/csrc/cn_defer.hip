@@ -319,7 +319,7 @@ static SgPlan *sg_plan(cn_ctx *ctx, DeferSquare &sq, uint32_t O, uint32_t K, std
 }
 static size_t sg_scratch(cn_ctx *ctx, const GemmPlan &P) {
     const size_t kn = (size_t)ctx->hc.k * ctx->hc.n;
-    return al((size_t)P.O * 2 * kn * 8) + al((size_t)P.O * ctx->hc.rl_tot * ctx->hc.n * 8) + al((size_t)P.G * P.Kp * 4) + al((size_t)P.G * P.M * 4) + al((size_t)P.O * 8) + 8192;
+    return al((size_t)P.O * 2 * kn * 8) + al((size_t)P.O * ctx->hc.rl_tot * ctx->hc.n * (P.dig_i32 ? 4 : 8)) + al((size_t)P.G * P.Kp * 4) + al((size_t)P.G * P.M * 4) + al((size_t)P.O * 8) + 8192;
 }
 // The decision of a flush that finds products pending (once, all or nothing): may every queued reader of a pending array run in cn_square_gemm's second half?
 //   (a) the caller has released every pending output array, (b) only scalar products read pending arrays - and those form groups (one level, one term count)
@@ -405,7 +405,7 @@ static int sg_run(cn_ctx *ctx, DeferQueue *q, const SgGroup &g) {
     for (uint32_t o = 0; o < P.O; o++) outs[o] = g.rows[o]->out;
     CHECK(ensure_scratch(ctx, sg_scratch(ctx, P)));
     uint64_t *T = salloc<uint64_t>(ctx, (size_t)P.O * 2 * kn);
-    double *S = salloc<double>(ctx, (size_t)P.O * tot * n);
+    void *S = salloc<char>(ctx, (size_t)P.O * tot * n * (P.dig_i32 ? 4 : 8));       // int32 words where the plan's digit bound allows (GemmPlan::dig_i32)
     if (!T || !S) return fail(CN_ERR_HIP, "internal: scratch exhausted in the deferred square + dense form");
     int32_t *dpidx, *dbidx; uint64_t **douts;
     CHECK(upload_tmp(ctx, pidx.data(), pidx.size(), &dpidx)); CHECK(upload_tmp(ctx, bidx.data(), bidx.size(), &dbidx)); CHECK(upload_tmp(ctx, outs.data(), outs.size(), &douts));
@@ -414,8 +414,9 @@ static int sg_run(cn_ctx *ctx, DeferQueue *q, const SgGroup &g) {
     CHECK(launch_gemm_plan(ctx, P, P.dev, dpidx, arr, (uint32_t)(3 * kn), 2u, bias ? (const uint64_t *)bbase : nullptr, dbidx, 32, T, 0));
     DigitGemmLaunch dg{arr + 2 * kn, 3 * kn, dpidx, P.dev + P.off_dw, P.dev + P.off_oidx, S, P.G, P.M, P.K, P.Kp, P.dKw, P.dMT};
     if (P.dig_mfma) { dg.W = P.dev + P.off_w; dg.mfma = true; dg.P = P.P; dg.mtiles = P.mtiles; dg.ksteps = P.ksteps; }
+    dg.i32 = P.dig_i32;
     CHECK(cn_l_digit_gemm(ctx, dg));
-    CHECK(do_keyswitch(ctx, ctx->rlk, KsCall::relin_digits(S, T, kn, P.O).to_table(douts)));
+    CHECK(do_keyswitch(ctx, ctx->rlk, KsCall::relin_digits(S, P.dig_i32, T, kn, P.O).to_table(douts)));
     ctx->dsg_fused++;
     if (defer_trace()) fprintf(stderr, "defer %p level %d: fuses %u scalar products over %zu pending products (GEMM, digit GEMM%s, %u key switches)\n", (void *)ctx, g.level, P.O,
                                g.slot_of.size(), P.dig_mfma ? " on the matrix cores" : "", P.O);

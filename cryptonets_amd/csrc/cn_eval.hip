@@ -327,19 +327,22 @@ int build_gemm_plan(cn_ctx *ctx, const int32_t *idx, const uint64_t *W, uint32_t
         uint64_t qmin = ~0ull; for (uint32_t j = 0; j < ctx->hc.k; j++) qmin = std::min(qmin, ctx->hc.q[j].q);
         const uint64_t dmax = (1ull << ctx->hc.dbc) - 1, lim = std::min<uint64_t>((qmin - 1) / 2, (1ull << 52) - 1) / dmax;      // sum |w| <= lim
         bool ok = true;
+        uint64_t sum_max = 0;                                     // the largest sum_k |w_ok| of any output: the plan's digit bound is sum_max (2^dbc - 1)
         for (uint32_t g = 0; g < G && ok; g++) for (uint32_t m = 0; m < M && ok; m++) {
             const uint64_t *wr = row(g, m);
             if (!wr) continue;
             uint64_t sum = 0;
             for (uint32_t kk = 0; kk < K; kk++) if (hidx[(size_t)g * Kp + kk] >= 0) { const uint64_t w = wr[kk]; sum += w >= ctx->hc.t_half ? t - w : w; }
             ok = sum <= lim;
+            sum_max = std::max(sum_max, sum);
         }
         // Matrix-core form (k_digit_gemm_mfma) where the plan's own GEMM takes the matrix cores (P.mfma: small weights in P <= 3 signed byte digits |w_p| <= 128, M >= 16,
         // 3 K < 2^17, rows of 32 K gather entries, fragments at off_w) and a digit splits into two int8 pieces: dg + 128 = (lo + 128) + 256 hi with hi <= 127 needs
         // 2^dbc - 1 + 128 < 2^15, dbc <= 14 (then hi <= 64).  i32 head-room: a diagonal receives per term one lo x w_p product (<= 128 * 128) and one hi x w_(p-1) product
         // (<= 64 * 128), K <= 43690 terms: 43690 * 24576 = 1 073 725 440 < 2^31.  N a multiple of 256: the column tiles of a slice are dealt to the 8 XCDs.
         // Otherwise the FP64 form k_digit_gemm with its own table of signed doubles.
-        if (ok) { P.dig = true; P.dig_mfma = mfma && ctx->digit_mfma && ctx->hc.dbc <= 14 && !(ctx->hc.n & 255); }
+        // int32 words for S ("digit_i32"): the plan's digit bound sum_max (2^dbc - 1) is at most 2^31 - 1; anything larger keeps doubles
+        if (ok) { P.dig = true; P.dig_mfma = mfma && ctx->digit_mfma && ctx->hc.dbc <= 14 && !(ctx->hc.n & 255); P.dig_i32 = ctx->digit_i32 && cn_digit_sum_fits_i32(sum_max, ctx->hc.dbc); }
         if (ok && !P.dig_mfma) {
             P.dMT = digit_gemm_tile(M); P.dKw = digit_gemm_rows(K);
             const uint32_t mtd = (M + P.dMT - 1) / P.dMT;
@@ -601,6 +604,7 @@ int do_keyswitch(cn_ctx *ctx, const KsKey &key, const KsCall &call) {
         }
     }
     HIPCHK(hipGetLastError()); launch_count(ctx);
+    if (a.dig && a.dig_i32) ctx->ks_dig_i32++;
     ctx->st.ntt_forward_limbs += (uint64_t)cnt * tot_dig * k; ctx->st.ntt_inverse_limbs += (uint64_t)cnt * 2 * k;
     return 0;
 }
@@ -709,7 +713,8 @@ extern "C" int cn_square_gemm(cn_ctx *ctx, cn_handle plan, cn_handle in, uint32_
     const uint32_t n = ctx->hc.n, k = ctx->hc.k, tot = ctx->hc.rl_tot;
     const size_t kn = (size_t)k * n;
     const size_t per = mul_scratch_per_ct(ctx, true);
-    const size_t fixed = al((size_t)cnt * 3 * kn * 8) + al((size_t)P.O * tot * n * 8) + 8192;
+    const size_t sw = P.dig_i32 ? 4 : 8;                                          // bytes per word of S
+    const size_t fixed = al((size_t)cnt * 3 * kn * 8) + al((size_t)P.O * tot * n * sw) + 8192;
     if (!square_gemm_fused_ok(ctx, P) || fixed + per > ctx->smax) {               // the two steps as they are: square + relinearize into a temporary, the GEMM from it
         cn_handle tmp = 0;
         CHECK(alloc_buf(ctx, 0, cnt, 2, &tmp));
@@ -723,7 +728,7 @@ extern "C" int cn_square_gemm(cn_ctx *ctx, cn_handle plan, cn_handle in, uint32_
     const uint32_t ch = (uint32_t)std::min<size_t>(cnt, (ctx->smax - fixed) / per);
     CHECK(ensure_scratch(ctx, fixed + per * ch + 4096));
     uint64_t *t3 = salloc<uint64_t>(ctx, (size_t)cnt * 3 * kn);
-    double *S = salloc<double>(ctx, (size_t)P.O * tot * n);
+    void *S = salloc<char>(ctx, (size_t)P.O * tot * n * sw);
     if (!t3 || !S) return fail(CN_ERR_HIP, "internal: scratch exhausted in cn_square_gemm");
     const size_t mark = ctx->soff;
     const uint64_t *pa = I->d + ii * I->item_words;
@@ -735,9 +740,10 @@ extern "C" int cn_square_gemm(cn_ctx *ctx, cn_handle plan, cn_handle in, uint32_
     CHECK(run_gemm_plan(ctx, P, P.dev, nullptr, OB, oi, t3));                     // components 0 and 1 (+ bias) straight into the outputs
     DigitGemmLaunch dg{t3 + 2 * kn, 3 * kn, P.dev, P.dev + P.off_dw, P.dev + P.off_oidx, S, P.G, P.M, P.K, P.Kp, P.dKw, P.dMT};
     if (P.dig_mfma) { dg.W = P.dev + P.off_w; dg.mfma = true; dg.P = P.P; dg.mtiles = P.mtiles; dg.ksteps = P.ksteps; }
+    dg.i32 = P.dig_i32;
     CHECK(cn_l_digit_gemm(ctx, dg));
     uint64_t *o = OB->d + oi * OB->item_words;
-    CHECK(do_keyswitch(ctx, ctx->rlk, KsCall::relin_digits(S, o, kn, P.O).to(o)));
+    CHECK(do_keyswitch(ctx, ctx->rlk, KsCall::relin_digits(S, P.dig_i32, o, kn, P.O).to(o)));
     ctx->st.Relinarization += cnt; ctx->sg_fused++;
     return 0;
 API_END }
@@ -808,7 +814,9 @@ extern "C" int cn_mul_relin_sum(cn_ctx *ctx, const cn_handle *a, const uint32_t 
     }
     // outputs per group: the products [output][term][3][k][N], S [output][rl_tot][N] and the two address tables of a group beside the scratch of one product
     const size_t per = mul_scratch_per_ct(ctx, false);
-    const size_t per_out = (size_t)K * 3 * kn * 8 + (size_t)tot * n * 8 + (size_t)K * 16, slack = 4 * 256 + 8192;
+    const bool s32 = ctx->digit_i32 && cn_digit_sum_fits_i32(K, ctx->hc.dbc);      // unit weights: K (2^dbc - 1) <= 2^31 - 1 - S as int32 words
+    const size_t sw = s32 ? 4 : 8;
+    const size_t per_out = (size_t)K * 3 * kn * 8 + (size_t)tot * n * sw + (size_t)K * 16, slack = 4 * 256 + 8192;
     const size_t g_fit = ctx->smax > per + slack ? (ctx->smax - per - slack) / per_out : 0;
     if (!mul_sum_fused_ok(ctx, K) || !g_fit) {                                    // the literal sequence: Multiply + Relinearize per term into a temporary, AddMany per output
         cn_handle tmp = 0;
@@ -825,11 +833,11 @@ extern "C" int cn_mul_relin_sum(cn_ctx *ctx, const cn_handle *a, const uint32_t 
     std::vector<const uint64_t *> ha((size_t)g * K), hb((size_t)g * K);
     for (uint32_t o0 = 0; o0 < count; o0 += g) {                                  // the groups, one after the other
         const uint32_t go = std::min(g, count - o0), np = go * K;
-        const size_t fixed = al((size_t)np * 3 * kn * 8) + al((size_t)go * tot * n * 8) + 2 * al((size_t)np * 8) + 8192;
+        const size_t fixed = al((size_t)np * 3 * kn * 8) + al((size_t)go * tot * n * sw) + 2 * al((size_t)np * 8) + 8192;
         const uint32_t ch = (uint32_t)std::min<size_t>(np, std::max<size_t>(1, (ctx->smax - std::min(ctx->smax, fixed)) / per));
         CHECK(ensure_scratch(ctx, fixed + per * ch + 4096));
         uint64_t *t3 = salloc<uint64_t>(ctx, (size_t)np * 3 * kn);
-        double *S = salloc<double>(ctx, (size_t)go * tot * n);
+        void *S = salloc<char>(ctx, (size_t)go * tot * n * sw);
         if (!t3 || !S) return fail(CN_ERR_HIP, "internal: scratch exhausted in cn_mul_relin_sum");
         for (uint32_t i = 0; i < go; i++) for (uint32_t kk = 0; kk < K; kk++) {
             const Buffer *A = getbuf(ctx, a[kk], 0), *B = getbuf(ctx, b[kk], 0);
@@ -845,8 +853,8 @@ extern "C" int cn_mul_relin_sum(cn_ctx *ctx, const cn_handle *a, const uint32_t 
             CHECK(do_multiply(ctx, nullptr, 1, nullptr, 1, t3 + (size_t)s * 3 * kn, c, da + s, db + s));
         }
         uint64_t *o = O->d + (size_t)(oi + o0) * O->item_words;
-        CHECK(cn_l_product_sum(ctx, ProductSumLaunch{t3, K, o, S, go}));          // (sum d0, sum d1) straight into the outputs, the digit sums into S
-        CHECK(do_keyswitch(ctx, ctx->rlk, KsCall::relin_digits(S, o, kn, go).to(o)));
+        CHECK(cn_l_product_sum(ctx, ProductSumLaunch{t3, K, o, S, go, s32}));     // (sum d0, sum d1) straight into the outputs, the digit sums into S
+        CHECK(do_keyswitch(ctx, ctx->rlk, KsCall::relin_digits(S, s32, o, kn, go).to(o)));
         ctx->ms_groups++;
     }
     ctx->st.Relinarization += (uint64_t)K * count; ctx->st.AddMany += count; ctx->st.AddManyItemCount += (uint64_t)count * K;

@@ -505,9 +505,13 @@ __global__ void __launch_bounds__(256, 2) k_scalar_gemm_mfma(const uint64_t *__r
 // Workgroup = (256 coefficients, source limb l, group of DG digits, output tile mt, gather list g); in = component 2 of product 0, products in_unit words apart.
 // Weights [g][mt][kk < Kw][MT] signed doubles, zero rows behind the K terms and zero for padded taps (which read a valid word: product 0); gather rows as in
 // k_scalar_gemm_f64.  The output tiles of a slice take block ids 8 apart: one XCD, adjacent in time, the slice is re-read from that L2 (gemm_block_coords).
-template <int MT, int DG>
+// Element type of S (all three producers): doubles - k_digit_gemm<MT, DG> - or, where the plan's digit bound is at most 2^31 - 1 (GemmPlan::dig_i32), int32 words -
+// k_digit_gemm<MT, DG, int32_t>: the same exact integer in half the bytes, read by the KsDigits<AR, int32_t> key switch.  (A parameter pack: the double forms keep their names.)
+template <class... E> struct DigitWord { typedef double type; };
+template <> struct DigitWord<int32_t> { typedef int32_t type; };
+template <int MT, int DG, class... E>
 __global__ void __launch_bounds__(256) k_digit_gemm(const uint64_t *__restrict__ in, size_t in_unit, const int32_t *__restrict__ idx, const double *__restrict__ Wd,
-                                                    const int32_t *__restrict__ out_idx, double *__restrict__ S, const DevConsts *__restrict__ C, uint32_t G, uint32_t M,
+                                                    const int32_t *__restrict__ out_idx, typename DigitWord<E...>::type *__restrict__ S, const DevConsts *__restrict__ C, uint32_t G, uint32_t M,
                                                     uint32_t K, uint32_t mtiles, uint32_t Kp, uint32_t Kw, uint32_t ndg) {
     const uint32_t n = C->n, k = C->k, chunks = n >> 8;
     uint32_t chunk, lj, mt, g;
@@ -576,7 +580,7 @@ __global__ void __launch_bounds__(256) k_digit_gemm(const uint64_t *__restrict__
         if (o < 0) continue;                                   // padding member of a smaller group
 #pragma unroll
         for (int d = 0; d < DG; d++)
-            if (d0 + (uint32_t)d < nd) S[((size_t)o * tot + g0 + d0 + (uint32_t)d) * n + i] = acc[d][m];
+            if (d0 + (uint32_t)d < nd) S[((size_t)o * tot + g0 + d0 + (uint32_t)d) * n + i] = (typename DigitWord<E...>::type)acc[d][m];
     }
 }
 
@@ -596,9 +600,11 @@ __global__ void __launch_bounds__(256) k_digit_gemm(const uint64_t *__restrict__
 // Digit groups: 16 (P + 1) DG accumulator registers per wave; all five digits of a CryptoNets limb (240 at P = 2) do not fit two workgroups per CU, so a workgroup takes
 // DG of them and the groups of a slice take block ids 8 apart - one XCD, adjacent in time: the second group reads the slice from that L2.  Limbs with fewer digits
 // skip the absent ones (rl_dig), a group without any digit leaves at once.
-template <int P, int DG>
+// int32 words (k_digit_gemm_mfma<P, DG, int32_t>): |S| <= 2^31 - 1, so the fold runs in 32-bit integers - exact modulo 2^32 whatever the partial sums do - and
+// the word is stored as it is: no conversion, half the bytes (an accumulator register then stores 128 B per half-wave).
+template <int P, int DG, class... E>
 __global__ void __launch_bounds__(256, 2) k_digit_gemm_mfma(const uint64_t *__restrict__ in, size_t in_unit, const int32_t *__restrict__ idx, const int8_t *__restrict__ Wf,
-                                                            const int32_t *__restrict__ out_idx, double *__restrict__ S, const DevConsts *__restrict__ C, uint32_t G,
+                                                            const int32_t *__restrict__ out_idx, typename DigitWord<E...>::type *__restrict__ S, const DevConsts *__restrict__ C, uint32_t G,
                                                             uint32_t M, uint32_t mtiles, uint32_t ksteps, uint32_t ndg) {
     constexpr int NP = 2 * DG, D = P + 1, NB = GEMM_MFMA_DEPTH + 1;
     __shared__ __align__(16) uint32_t frag[NB][NP][64][4];         // [buffer][digit, piece][lane][slot group q]
@@ -707,10 +713,18 @@ __global__ void __launch_bounds__(256, 2) k_digit_gemm_mfma(const uint64_t *__re
 #pragma unroll
         for (int r = 0; r < 16; r++) {
             if (oo[r] < 0) continue;                               // row past M, or padding member of a smaller group
-            double v = (double)acc[d][0][r];
+            typename DigitWord<E...>::type *dst = S + ((size_t)oo[r] * tot + g0 + d0 + (uint32_t)d) * n + (size_t)ctile * 32 + col;
+            if constexpr (std::is_same<typename DigitWord<E...>::type, int32_t>::value) {
+                uint32_t v = (uint32_t)acc[d][D - 1][r];
 #pragma unroll
-            for (int j = 1; j < D; j++) v = __fma_rn((double)acc[d][j][r], (double)(1u << (8 * j)), v);
-            S[((size_t)oo[r] * tot + g0 + d0 + (uint32_t)d) * n + (size_t)ctile * 32 + col] = v;
+                for (int j = D - 2; j >= 0; j--) v = (v << 8) + (uint32_t)acc[d][j][r];
+                *dst = (int32_t)v;
+            } else {
+                double v = (double)acc[d][0][r];
+#pragma unroll
+                for (int j = 1; j < D; j++) v = __fma_rn((double)acc[d][j][r], (double)(1u << (8 * j)), v);
+                *dst = v;
+            }
         }
     }
 }
@@ -733,8 +747,10 @@ DEV uint64_t ps_reduce(uint64_t x, const DMod &m) {              // x mod q for 
     const uint64_t r = x - __umul64hi(x, m.r1) * m.q;
     return r >= m.q ? r - m.q : r;
 }
-template <int ND>
-__global__ void __launch_bounds__(256) k_product_sum(const uint64_t *__restrict__ prod_, uint32_t K, uint64_t *__restrict__ out_, double *__restrict__ S_,
+// int32 words (k_product_sum<ND, int32_t>, K (2^dbc - 1) <= 2^31 - 1): the two sums of a thread leave as one 8-byte store.
+typedef int32_t ps_i32x2 __attribute__((ext_vector_type(2)));
+template <int ND, class... E>
+__global__ void __launch_bounds__(256) k_product_sum(const uint64_t *__restrict__ prod_, uint32_t K, uint64_t *__restrict__ out_, typename DigitWord<E...>::type *__restrict__ S_,
                                                      const DevConsts *__restrict__ C) {
     typedef const NTT_GLOBAL ps_u64x2 *In;
     constexpr int PF = 4;
@@ -798,9 +814,11 @@ __global__ void __launch_bounds__(256) k_product_sum(const uint64_t *__restrict_
     ps_u64x2 v;
     v.x = ps_reduce(c0x, m); v.y = ps_reduce(c0y, m); dst[0] = v;
     v.x = ps_reduce(c1x, m); v.y = ps_reduce(c1y, m); dst[comp] = v;
-    typedef NTT_GLOBAL ps_f64x2 *OutS;
+    typedef typename DigitWord<E...>::type SE;
+    typedef typename std::conditional<std::is_same<SE, int32_t>::value, ps_i32x2, ps_f64x2>::type SV;
+    typedef NTT_GLOBAL SV *OutS;
     OutS sd = (OutS)S_ + ((size_t)o * C->rl_tot + g0) * n2 + p;
 #pragma unroll
     for (int d = 0; d < ND; d++)
-        if ((uint32_t)d < nd) { ps_f64x2 w; w.x = (double)dx[d]; w.y = (double)dy[d]; sd[(size_t)d * n2] = w; }
+        if ((uint32_t)d < nd) { SV w; w.x = (SE)dx[d]; w.y = (SE)dy[d]; sd[(size_t)d * n2] = w; }
 }

@@ -59,13 +59,20 @@ template <class FW0> struct KsPassA<FW0, true> { typedef ArPassA<FW0> P; };
 // uses, read back behind it.  Bit-exact; 3.37 vs 3.33 ms: the key stream costs bandwidth on the vector memory path, not exposed latency.)
 // XI: the "ks_xi" decomposition (digits of [c_l (q/q_l)^-1]_{q_l}) as a separate instantiation - the default kernel is instruction for instruction the one
 // that is profiled and priced (tools/ks_isa_counts.py)
-// DIG: the digit polynomials arrive ready-made (cn_square_gemm: S[ct][g][N], the weight-combined digits of a dense layer's inputs, exact signed doubles with
-// |S| < q_j / 2 for every j - a recentred lazy value of the FP64 policies) instead of being cut out of a source limb: `target` is that array, tgt_stride = digits * N.
+// DIG: the digit polynomials arrive ready-made (cn_square_gemm: S[ct][g][N], the weight-combined digits of a dense layer's inputs, exact signed integers with
+// |S| < q_j / 2 for every j - a recentred lazy value of the FP64 policies - stored as doubles or, where they fit, as int32 words) instead of being cut out of a source limb: `target` is that array, tgt_stride = digits * N.
 // Again a separate instantiation, selected by wrapping the policy - k_keyswitch_rr<L, KsDigits<AR>, ..> - so that the default instantiations keep their names;
 // everything behind the digit load is the same code.
-template <class AR> struct KsDigits {};
-template <class AR> struct KsSrc { typedef AR P; static constexpr bool dig = false; };
-template <class AR> struct KsSrc<KsDigits<AR>> { typedef AR P; static constexpr bool dig = true; };
+// Element type of S: KsDigits<AR> reads doubles, KsDigits<AR, int32_t> reads 32-bit words (GemmPlan::dig_i32: |S| <= 2^31 - 1, half the bytes) and makes
+// the transform's double with one conversion.  (A parameter pack, so that KsDigits<AR> keeps its name in traces.)
+template <class AR, class... E> struct KsDigits {};
+template <class AR> struct KsSrc { typedef AR P; typedef double E; static constexpr bool dig = false; };
+template <class AR> struct KsSrc<KsDigits<AR>> { typedef AR P; typedef double E; static constexpr bool dig = true; };
+template <class AR> struct KsSrc<KsDigits<AR, int32_t>> { typedef AR P; typedef int32_t E; static constexpr bool dig = true; };
+// (Measured, not kept: the 16 int32 words of digit g + 1 requested right behind the forward transform of digit g and taken at the top of the next iteration, in
+// k_keyswitch_rr and k_ks_limb_mac.  Bit-exact, 242 instead of 208 VGPRs; 500.1 / 500.0 against 500.4 / 504.2 us per 100-output launch and 70.7 against 71.5 - 72.0 us
+// per 10-output launch, the first inside the run-to-run spread of the averages: with int32 words a workgroup of this kernel already takes what one of the plain kernel
+// takes.  profiles/digit_sums_i32.md)
 template <int L, class AR_, int MINW = 1, bool TWL = false, bool XI = false>
 __global__ void __launch_bounds__(NttPlan<L>::NT, MINW) k_keyswitch_rr(const uint64_t *__restrict__ target, size_t tgt_stride, const uint64_t *__restrict__ add0,
                                                                  const uint64_t *__restrict__ add1, size_t add_stride, const void *__restrict__ key_,
@@ -131,7 +138,8 @@ __global__ void __launch_bounds__(NttPlan<L>::NT, MINW) k_keyswitch_rr(const uin
         for (int r = 0; r < 16; r++) w[r] = src[pass_index<L, SA, 0>(t0, r)];
     };
     if constexpr (AHEAD) request(nraw, 0);
-    const double *dsrc = reinterpret_cast<const double *>(target) + (size_t)ct * tgt_stride;      // DIG: digit polynomial g of this ciphertext at dsrc + g N
+    typedef typename KsSrc<AR_>::E E;
+    const E *dsrc = reinterpret_cast<const E *>(target) + (size_t)ct * tgt_stride;      // DIG: digit polynomial g of this ciphertext at dsrc + g N
     for (uint32_t l = 0; l < k; l++) {
         const uint32_t nd = galois ? C->gk_dig[l] : C->rl_dig[l];
         if constexpr (DIG) {
@@ -575,7 +583,8 @@ __global__ void __launch_bounds__(NttPlan<L>::NT) k_ks_digit_mac(const uint64_t 
     T v[16];
     if constexpr (DIG) {
         static_assert(std::is_same<T, double>::value, "ready-made digits: FP64 policies");
-        const double *dsrc = reinterpret_cast<const double *>(target) + (size_t)ct * tgt_stride + (size_t)g * n;
+        typedef typename KsSrc<AR_>::E E;
+        const E *dsrc = reinterpret_cast<const E *>(target) + (size_t)ct * tgt_stride + (size_t)g * n;
 #pragma unroll
         for (int r = 0; r < 16; r++) v[r] = (T)dsrc[pass_index<L, SA, 0>(tid, r)];
     } else {
@@ -652,7 +661,8 @@ __global__ void __launch_bounds__(NttPlan<L>::NT) k_ks_limb_mac(const uint64_t *
     }
     ks_premultiply(raw, C, l);
     }
-    const double *dsrc = reinterpret_cast<const double *>(target) + (size_t)ct * tgt_stride + (size_t)g0 * n;      // DIG: the digits of limb l
+    typedef typename KsSrc<AR_>::E E;
+    const E *dsrc = reinterpret_cast<const E *>(target) + (size_t)ct * tgt_stride + (size_t)g0 * n;      // DIG: the digits of limb l
     T acc0[16], acc1[16];
 #pragma unroll
     for (int r = 0; r < 16; r++) { acc0[r] = 0; acc1[r] = 0; }

@@ -70,15 +70,20 @@ template <bool ABS> static int launch_mfma_p(cn_ctx *c, const GemmLaunch &g) {
 int cn_l_gemm_mfma(cn_ctx *c, const GemmLaunch &g) { return g.abs ? launch_mfma_p<true>(c, g) : launch_mfma_p<false>(c, g); }
 
 // digit GEMM (cn_square_gemm): DG = 5 digits of a source limb per workgroup (a 50-bit limb at dbc 10), more digits per limb in further groups
+// (g.i32: S as int32 words - the <.., int32_t> instantiations of the three producers)
 template <int MT> static void launch_digit(cn_ctx *c, const DigitGemmLaunch &g, uint32_t ndg, uint32_t mtiles) {
     const size_t blocks = (size_t)(c->hc.n >> 8) * c->hc.k * ndg * mtiles * g.G;
-    hipLaunchKernelGGL((k_digit_gemm<MT, 5>), dim3((uint32_t)blocks), dim3(256), 0, c->stream, g.in, g.in_unit, (const int32_t *)g.idx, (const double *)g.W,
-                       (const int32_t *)g.oidx, g.S, c->dc, g.G, g.M, g.K, mtiles, g.Kp, g.Kw, ndg);
+    if (g.i32) hipLaunchKernelGGL((k_digit_gemm<MT, 5, int32_t>), dim3((uint32_t)blocks), dim3(256), 0, c->stream, g.in, g.in_unit, (const int32_t *)g.idx, (const double *)g.W,
+                                  (const int32_t *)g.oidx, (int32_t *)g.S, c->dc, g.G, g.M, g.K, mtiles, g.Kp, g.Kw, ndg);
+    else hipLaunchKernelGGL((k_digit_gemm<MT, 5>), dim3((uint32_t)blocks), dim3(256), 0, c->stream, g.in, g.in_unit, (const int32_t *)g.idx, (const double *)g.W,
+                            (const int32_t *)g.oidx, (double *)g.S, c->dc, g.G, g.M, g.K, mtiles, g.Kp, g.Kw, ndg);
 }
 // matrix-core form: DG = digit_gemm_mfma_group(P) digits per workgroup; the digit groups of a (column tile, limb) take block ids 8 apart (k_digit_gemm_mfma)
 template <int P, int DG> static void launch_digit_mfma(cn_ctx *c, const DigitGemmLaunch &g, uint32_t ndg, size_t blocks) {
-    hipLaunchKernelGGL((k_digit_gemm_mfma<P, DG>), dim3((uint32_t)blocks), dim3(256), 0, c->stream, g.in, g.in_unit, (const int32_t *)g.idx, (const int8_t *)g.W,
-                       (const int32_t *)g.oidx, g.S, c->dc, g.G, g.M, g.mtiles, g.ksteps, ndg);
+    if (g.i32) hipLaunchKernelGGL((k_digit_gemm_mfma<P, DG, int32_t>), dim3((uint32_t)blocks), dim3(256), 0, c->stream, g.in, g.in_unit, (const int32_t *)g.idx, (const int8_t *)g.W,
+                                  (const int32_t *)g.oidx, (int32_t *)g.S, c->dc, g.G, g.M, g.mtiles, g.ksteps, ndg);
+    else hipLaunchKernelGGL((k_digit_gemm_mfma<P, DG>), dim3((uint32_t)blocks), dim3(256), 0, c->stream, g.in, g.in_unit, (const int32_t *)g.idx, (const int8_t *)g.W,
+                            (const int32_t *)g.oidx, (double *)g.S, c->dc, g.G, g.M, g.mtiles, g.ksteps, ndg);
 }
 static int digit_gemm_mfma(cn_ctx *c, const DigitGemmLaunch &g, uint32_t ndmax) {
     const uint32_t DG = digit_gemm_mfma_group(g.P), ndg = (ndmax + DG - 1) / DG, mgroups = (g.mtiles + 3) / 4;
@@ -112,7 +117,8 @@ int cn_l_digit_gemm(cn_ctx *c, const DigitGemmLaunch &g) {
 
 // sum of the K products of every output (cn_mul_relin_sum): ND = the smallest instantiation that holds all digits of every source limb
 template <int ND> static void launch_product_sum(cn_ctx *c, const ProductSumLaunch &g, uint32_t blocks) {
-    hipLaunchKernelGGL((k_product_sum<ND>), dim3(blocks), dim3(256), 0, c->stream, g.prod, g.K, g.out, g.S, c->dc);
+    if (g.i32) hipLaunchKernelGGL((k_product_sum<ND, int32_t>), dim3(blocks), dim3(256), 0, c->stream, g.prod, g.K, g.out, (int32_t *)g.S, c->dc);
+    else hipLaunchKernelGGL((k_product_sum<ND>), dim3(blocks), dim3(256), 0, c->stream, g.prod, g.K, g.out, (double *)g.S, c->dc);
 }
 int cn_l_product_sum(cn_ctx *c, const ProductSumLaunch &g) {
     uint32_t ndmax = 0; for (uint32_t l = 0; l < c->hc.k; l++) ndmax = std::max(ndmax, c->hc.rl_dig[l]);

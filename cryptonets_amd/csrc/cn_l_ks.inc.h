@@ -13,20 +13,26 @@ template <class K> static int big_lds(K kern, size_t bytes) {
 }
 // dynamic LDS of the fused key switch with LDS-resident forward twiddles: exchange image + table
 template <int L> static size_t ks_twl_lds() { return ((size_t)ntt_lds_words(1u << L) + (1u << L)) * 8; }
+// int32 digit sums: the rings do_keyswitch admits ready-made digits for (N <= 8192) - no instantiation of the 1024-thread kernels, which nobody launches
+template <int L> static constexpr bool kDig32 = kF64 && L <= 13;
+// the instantiations that read ready-made digits (KsArgs::dig), as doubles (DS = KsDigits<AR>) or int32 words (KsDigits<AR, int32_t>)
+template <int L, class DS> static int set_attrs_dig(size_t bytes) {
+    CHECK(big_lds(k_keyswitch_rr<L, DS, 1, false, false>, bytes));
+    if constexpr (KsFwd<AR, L>::lds) CHECK(big_lds(k_keyswitch_rr<L, DS, 1, true, false>, ks_twl_lds<L>()));
+    CHECK(big_lds(k_ks_digit_mac<L, DS>, bytes)); CHECK(big_lds(k_ks_limb_mac<L, DS>, bytes));
+    return 0;
+}
 template <int L> static int set_attrs_l(size_t bytes) {
     CHECK(big_lds(k_keyswitch_rr<L, AR>, bytes)); CHECK(big_lds(k_keyswitch_rr<L, AR, 1, false, true>, bytes));
     if constexpr (KsFwd<AR, L>::lds) { CHECK(big_lds(k_keyswitch_rr<L, AR, 1, true>, ks_twl_lds<L>())); CHECK(big_lds(k_keyswitch_rr<L, AR, 1, true, true>, ks_twl_lds<L>())); }
     CHECK(big_lds(k_ks_digit_mac<L, AR>, bytes)); CHECK(big_lds(k_ks_limb_mac<L, AR>, bytes)); CHECK(big_lds(k_ks_sum_intt<L, AR>, bytes));
-    if constexpr (kF64) {               // the instantiations that read ready-made digits (KsArgs::dig)
-        CHECK(big_lds(k_keyswitch_rr<L, KsDigits<AR>, 1, false, false>, bytes));
-        if constexpr (KsFwd<AR, L>::lds) CHECK(big_lds(k_keyswitch_rr<L, KsDigits<AR>, 1, true, false>, ks_twl_lds<L>()));
-        CHECK(big_lds(k_ks_digit_mac<L, KsDigits<AR>>, bytes)); CHECK(big_lds(k_ks_limb_mac<L, KsDigits<AR>>, bytes));
-    }
+    if constexpr (kF64) { CHECK((set_attrs_dig<L, KsDigits<AR>>(bytes))); if constexpr (kDig32<L>) CHECK((set_attrs_dig<L, KsDigits<AR, int32_t>>(bytes))); }
     return 0;
 }
 static int set_attrs(uint32_t logn, size_t bytes) {
     if constexpr (kF64) { if (logn == 12) { CHECK(big_lds(k_keyswitch_rr<12, AR, 1, true>, ks_twl_lds<12>())); CHECK(big_lds(k_keyswitch_rr<12, AR, 1, true, true>, ks_twl_lds<12>()));
-                                           CHECK(big_lds(k_keyswitch_rr<12, KsDigits<AR>, 1, true, false>, ks_twl_lds<12>())); } }   // N = 4096: image + LDS twiddle table = 66.5 KiB
+                                           CHECK(big_lds(k_keyswitch_rr<12, KsDigits<AR>, 1, true, false>, ks_twl_lds<12>()));
+                                           CHECK(big_lds(k_keyswitch_rr<12, KsDigits<AR, int32_t>, 1, true, false>, ks_twl_lds<12>())); } }   // N = 4096: image + LDS twiddle table = 66.5 KiB
     if (logn == 13) CHECK(set_attrs_l<13>(bytes));
     if (logn == 14) {
         CHECK(set_attrs_l<14>(bytes));
@@ -40,9 +46,9 @@ static int set_attrs(uint32_t logn, size_t bytes) {
 }
 // the LDS copy of the twiddle table pays once a workgroup runs enough digit transforms of its modulus
 static const uint32_t KS_TWL_MIN_DIGITS = 12;
-template <int L, bool XI, bool DIG = false> static void launch_fused_x(cn_ctx *c, const KsArgs &a) {
+template <int L, bool XI, class ARS = AR> static void launch_fused_x(cn_ctx *c, const KsArgs &a) {
     const uint32_t tot = a.galois ? c->hc.gk_tot : c->hc.rl_tot;
-    typedef typename std::conditional<DIG, KsDigits<AR>, AR>::type ARS;
+    constexpr bool DIG = KsSrc<ARS>::dig;
     const uint64_t *tgt = DIG ? (const uint64_t *)a.dig : a.target;
     const size_t tstride = DIG ? (size_t)tot * c->hc.n : a.tstride;
     if constexpr (KsFwd<AR, L>::lds) {
@@ -56,9 +62,22 @@ template <int L, bool XI, bool DIG = false> static void launch_fused_x(cn_ctx *c
                        a.add0, a.add1, a.astride, (const void *)a.key, a.out, c->dc, a.galois, a.accmax, a.extra, a.xstride, a.out_tab, a.xcd_cts);
 }
 template <int L> static void launch_fused(cn_ctx *c, const KsArgs &a) {
-    if constexpr (kF64) { if (a.dig) { launch_fused_x<L, false, true>(c, a); return; } }
+    if constexpr (kF64) {
+        if (a.dig) {
+            if constexpr (kDig32<L>) { if (a.dig_i32) { launch_fused_x<L, false, KsDigits<AR, int32_t>>(c, a); return; } }
+            launch_fused_x<L, false, KsDigits<AR>>(c, a); return;
+        }
+    }
     if (c->hc.ks_xi) launch_fused_x<L, true>(c, a);
     else launch_fused_x<L, false>(c, a);
+}
+// first launch of the two-launch forms from ready-made digit polynomials (DS: KsDigits<AR> or KsDigits<AR, int32_t>)
+template <int L, class DS> static void launch_dig_mac(cn_ctx *c, const KsArgs &a, uint32_t tot, size_t lds) {
+    const uint32_t k = c->hc.k;
+    if (a.mode == 2) hipLaunchKernelGGL((k_ks_limb_mac<L, DS>), dim3(a.cnt * k * k), dim3(NttPlan<L>::NT), lds, c->stream, (const uint64_t *)a.dig, (size_t)tot * c->hc.n,
+                                        (const void *)a.key, c->ks_part, c->dc, a.galois, a.accmax, 0u, (const KsItem *)nullptr);
+    else hipLaunchKernelGGL((k_ks_digit_mac<L, DS>), dim3(a.cnt * tot * k), dim3(NttPlan<L>::NT), lds, c->stream, (const uint64_t *)a.dig, (size_t)tot * c->hc.n,
+                            (const void *)a.key, c->ks_part, c->dc, a.galois, tot, 0u, (const KsItem *)nullptr);
 }
 template <int L> static void launch_two_phase(cn_ctx *c, const KsArgs &a) {
     const uint32_t tot = a.galois ? c->hc.gk_tot : c->hc.rl_tot, k = c->hc.k;
@@ -67,10 +86,10 @@ template <int L> static void launch_two_phase(cn_ctx *c, const KsArgs &a) {
     if constexpr (kF64) dig = a.dig != nullptr;
     if (dig) {                      // ready-made digit polynomials: the same two forms, first launch from KsArgs::dig
         if constexpr (kF64) {
-            if (a.mode == 2) hipLaunchKernelGGL((k_ks_limb_mac<L, KsDigits<AR>>), dim3(a.cnt * k * k), dim3(NttPlan<L>::NT), lds, c->stream, (const uint64_t *)a.dig, (size_t)tot * c->hc.n,
-                                                (const void *)a.key, c->ks_part, c->dc, a.galois, a.accmax, 0u, (const KsItem *)nullptr);
-            else hipLaunchKernelGGL((k_ks_digit_mac<L, KsDigits<AR>>), dim3(a.cnt * tot * k), dim3(NttPlan<L>::NT), lds, c->stream, (const uint64_t *)a.dig, (size_t)tot * c->hc.n,
-                                    (const void *)a.key, c->ks_part, c->dc, a.galois, tot, 0u, (const KsItem *)nullptr);
+            bool i32 = false;
+            if constexpr (kDig32<L>) i32 = a.dig_i32;
+            if constexpr (kDig32<L>) { if (i32) launch_dig_mac<L, KsDigits<AR, int32_t>>(c, a, tot, lds); }
+            if (!i32) launch_dig_mac<L, KsDigits<AR>>(c, a, tot, lds);
         }
         hipLaunchKernelGGL((k_ks_sum_intt<L, AR>), dim3(a.cnt * k * 2), dim3(NttPlan<L>::NT), lds, c->stream, (const void *)c->ks_part, a.add0, a.add1, a.astride,
                            a.out, c->dc, a.mode == 2 ? k : tot, a.mode == 2 ? 0xffffffffu : a.accmax, a.extra, a.xstride, a.out_tab, a.perm_elt, a.items);

@@ -26,5 +26,11 @@ inline CnModRange cn_mod_range(const DevConsts &hc, uint32_t base_off, uint32_t 
 }
 // use_f64: the "f64" option as it stands now - or, for a key switch, the form its key was loaded in (KsKey::f64)
 inline int cn_policy(const CnModRange &r, bool use_f64) { return !(use_f64 && r.f64ok) ? POL_U64 : (r.light ? POL_F64L : POL_F64); }
+// Digit sums S = sum_k w_k dig_k of cn_square_gemm / cn_mul_relin_sum (|dig| <= 2^dbc - 1, sum_abs_w = the largest sum_k |w_k| of any output; K for unit
+// weights): do they fit a signed 32-bit word, sum_abs_w (2^dbc - 1) <= 2^31 - 1?  Then the producers store int32 words and the key switch reads half the bytes
+inline bool cn_digit_sum_fits_i32(uint64_t sum_abs_w, int dbc) {
+    if (dbc < 1 || dbc > 31) return false;
+    return (unsigned __int128)sum_abs_w * ((1ull << dbc) - 1) <= 0x7fffffffull;
+}
 // the ring sizes of the register-radix kernels: 1024 <= N <= 16384, or N <= 8192 (max_logn = 13) for the kernels that stop there
 inline bool cn_rr_size(uint32_t logn, uint32_t max_logn = 14) { return logn >= 10 && logn <= max_logn; }

@@ -219,6 +219,9 @@ struct cn_ctx {
                                // same words); false: always Multiply + Relinearize per term and AddMany.  A switch between two live forms of one call, set by name like "digit_mfma"
     bool digit_mfma = true;    // cn_set_option "digit_mfma": plans made from now on run their digit GEMM on the int8 matrix cores where they can (k_digit_gemm_mfma, exact); false: always
                                // the FP64 kernel k_digit_gemm.  A switch between two live forms of one step of cn_square_gemm, set by name like "ks_xi" (no environment override)
+    bool digit_i32 = true;     // cn_set_option "digit_i32": plans made from now on (and cn_mul_relin_sum calls) hand their digit sums S to the key switch as int32 words where the bound
+                               // allows it (cn_digit_sum_fits_i32, cn_policy.h: half the bytes of S); false: always doubles.  Set by name like "digit_mfma" (no environment override)
+    uint64_t ks_dig_i32 = 0;   // key switches launched on int32 digit sums ("ks_digits_i32")
     bool defer_square_gemm = false;  // cn_set_option "defer_square_gemm" (default 0: its effect on the literal call sequence has not been measured, profiles/deferred_square_gemm.md): queued squarings launched by a layer-boundary flush keep their relinearisation back; scalar products that read
                                // nothing else run as cn_square_gemm's second half - one key switch per dense OUTPUT (cn_defer.hip); false: every queued squaring relinearises at once.
                                // Set by name like "digit_mfma" (no environment override)
@@ -261,14 +264,17 @@ struct KsCall {
     uint32_t perm_elt = 0;    // two-launch variants: Galois element of a rotation whose automorphism the kernels apply while loading (target / add0 = the UNPERMUTED c1 / c0)
                               // k_keyswitch_pair14: target = sigma(c1) already, add0 = the UNPERMUTED c0 (permuted through LDS by the workgroup that owns the limb)
     uint32_t next_elt = 0; uint64_t *next_out = nullptr;   // k_keyswitch_pair14: the new c1 leaves a second time as sigma_next(c1) -> next_out[ct][k][N] (rotate-and-add chains)
-    const double *dig = nullptr;     // register-radix kernels, FP64 policies, relinearisation: ready-made digit polynomials [cnt][rl_tot][N] (exact signed doubles, |S| < q_j / 2)
+    const void *dig = nullptr;       // register-radix kernels, FP64 policies, relinearisation: ready-made digit polynomials [cnt][rl_tot][N] (exact signed integers, |S| < q_j / 2)
                                      // instead of `target` (cn_square_gemm: the weight-combined digits of a dense layer's inputs)
+    bool dig_i32 = false;            // ... stored as int32 words (|S| <= 2^31 - 1: GemmPlan::dig_i32) instead of doubles
     // The shapes (kn = k N words per polynomial): relinearise the products prod [cnt][3][kn]; relinearise from the digit polynomials S on top of the size-2
     // ciphertexts base [cnt][2][kn]; Galois switch of c1 (c1_stride apart) with c0 [cnt][2][kn] added, or of every ciphertext with its own operand, key and element
     static KsCall relin(const uint64_t *prod, size_t kn, uint32_t cnt) {
         return {.target = prod + 2 * kn, .tstride = 3 * kn, .add0 = prod, .add1 = prod + kn, .astride = 3 * kn, .cnt = cnt};
     }
-    static KsCall relin_digits(const double *S, const uint64_t *base, size_t kn, uint32_t cnt) { return {.add0 = base, .add1 = base + kn, .astride = 2 * kn, .cnt = cnt, .dig = S}; }
+    static KsCall relin_digits(const void *S, bool i32, const uint64_t *base, size_t kn, uint32_t cnt) {
+        return {.add0 = base, .add1 = base + kn, .astride = 2 * kn, .cnt = cnt, .dig = S, .dig_i32 = i32};
+    }
     static KsCall galois_of(const uint64_t *c1, size_t c1_stride, const uint64_t *c0, size_t kn, uint32_t cnt) {
         return {.target = c1, .tstride = c1_stride, .add0 = c0, .astride = 2 * kn, .cnt = cnt, .galois = 1};
     }
@@ -334,20 +340,21 @@ struct GemmLaunch {
 inline uint32_t gemm_f64_rows(uint32_t K) { return ((K + 15) & ~15u) + 16; }
 int cn_l_gemm(cn_ctx *c, const GemmLaunch &g);
 int cn_l_gemm_mfma(cn_ctx *c, const GemmLaunch &g);   // k_scalar_gemm_mfma: W = weight digit fragments, idx rows of ksteps * 32 entries
-// digit GEMM of cn_square_gemm (k_digit_gemm): in = component 2 of product 0 (products in_unit words apart), S [outputs][rl_tot][N] doubles; W = signed doubles
+// digit GEMM of cn_square_gemm (k_digit_gemm): in = component 2 of product 0 (products in_unit words apart), S [outputs][rl_tot][N] doubles (i32: int32 words); W = signed doubles
 // [G][mtiles][Kw][MT], MT = 10 or 2.  mfma (k_digit_gemm_mfma): W = the plan's weight digit fragments (pack_gemm_mfma), idx rows of ksteps * 32 entries
 struct DigitGemmLaunch {
-    const uint64_t *in; size_t in_unit; const void *idx; const void *W; const void *oidx; double *S;
+    const uint64_t *in; size_t in_unit; const void *idx; const void *W; const void *oidx; void *S;
     uint32_t G, M, K, Kp, Kw, MT;
     bool mfma = false; uint32_t P = 0, mtiles = 0, ksteps = 0;
+    bool i32 = false;
 };
 inline uint32_t digit_gemm_mfma_group(uint32_t P) { return P <= 2 ? 3u : 2u; }     // digits per workgroup: 16 (P + 1) DG accumulator registers per wave
 inline uint32_t digit_gemm_tile(uint32_t M) { return M > 2 ? 10u : 2u; }
 inline uint32_t digit_gemm_rows(uint32_t K) { return ((K + 7) & ~7u) + 8; }        // K terms + zero rows: the kernel's sets of four terms run past K
 int cn_l_digit_gemm(cn_ctx *c, const DigitGemmLaunch &g);
 // sum of unrelinearized products (cn_mul_relin_sum, k_product_sum): prod [outputs][K][3][k][N] -> components 0 and 1 summed mod q_l into out [outputs][2][k][N],
-// the digit sums of component 2 into S [outputs][rl_tot][N] doubles.  Every source limb has at most PRODUCT_SUM_MAX_DIGITS digits of at most 31 bits
-struct ProductSumLaunch { const uint64_t *prod; uint32_t K; uint64_t *out; double *S; uint32_t outputs; };
+// the digit sums of component 2 into S [outputs][rl_tot][N] doubles (i32: int32 words).  Every source limb has at most PRODUCT_SUM_MAX_DIGITS digits of at most 31 bits
+struct ProductSumLaunch { const uint64_t *prod; uint32_t K; uint64_t *out; void *S; uint32_t outputs; bool i32 = false; };
 static const uint32_t PRODUCT_SUM_MAX_DIGITS = 8;
 int cn_l_product_sum(cn_ctx *c, const ProductSumLaunch &g);
 // sums of plaintext x ciphertext products (cn_mul_plain_sum; cn_l_diag.hip, k_mul_plain_sum): group g < groups = terms [grp_off[g], grp_off[g + 1]), term e = plaintext

@@ -118,6 +118,9 @@ int cn_mod_switch(cn_ctx *src, cn_handle in, uint32_t ii, uint32_t count, cn_ctx
  *   "digit_mfma"     flag    1                     -                the digit GEMM of cn_square_gemm on the int8 matrix cores where the plan's own GEMM
  *                                                                   takes them and a key-switch digit has at most 14 bits; 0 = the FP64 kernel (which
  *                                                                   also serves every other plan).  The same words.  Affects GEMMs planned after the call
+ *   "digit_i32"      flag    1                     -                the digit sums cn_square_gemm and cn_mul_relin_sum hand to their key switch are stored
+ *                                                                   as int32 words where sum |w| (2^dbc - 1) <= 2^31 - 1; 0 = always doubles.  The same
+ *                                                                   words.  Affects GEMMs planned after the call
  *   "mul_sum"        flag    1                     -                cn_mul_relin_sum sums the unrelinearized products and runs one key switch per output
  *                                                                   where it can; 0 = always Multiply + Relinearize per term, then AddMany.  The same words
  *   "gemm_pair"      flag    1                     CN_GEMM_PAIR     cn_scalar_gemm / cn_gemm_plan_create merge gather lists that share at least half of
@@ -219,6 +222,7 @@ int cn_set_option(cn_ctx *ctx, const char *name, int value);
  *   "mul_sum_groups"           output groups of the last cn_mul_relin_sum call (0: it took the literal sequence or had K = 1)
  *   "mul_sum_min_k"            the smallest K for which cn_mul_relin_sum takes the one-key-switch form
  *   "digit_gemm_mfma"          digit GEMMs of cn_square_gemm launched in the matrix-core form ("digit_mfma"; counts up)
+ *   "ks_digits_i32"            key switches launched on int32 digit sums ("digit_i32"; counts up)
  *   "pool_arrays"              device arrays cached for reuse (the temporaries of a live graph are reserved out of them)
  *   "stream_tries"             streams cn_ctx_create tried until one had a hardware queue of its own (< 0: none had; CN_STREAM_PROBE=0 takes the first) */
 int cn_get_option(cn_ctx *ctx, const char *name, int *value);
