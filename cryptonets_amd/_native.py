@@ -18,7 +18,7 @@ SOURCES = [os.path.join(CSRC, f) for f in (
     "cn_api.hip", "cn_eval.hip", "cn_client.hip", "cn_defer.hip", "cn_multi.hip", "cn_host.cpp", "cn_tables.cpp", "cn_l_gemm.hip", "cn_l_behz.hip",
     "cn_l_rr_u64.hip", "cn_l_rr_f64.hip", "cn_l_rr_f64l.hip", "cn_l_ks_u64.hip", "cn_l_ks_f64.hip", "cn_l_ks_f64l.hip", "cn_level.hip", "cn_l_modswitch.hip",
     "cn_l_modswitch_f64.hip", "cn_l_noise.hip", "cn_l_seeded.hip", "cn_l_keygen.hip", "cn_l_packed.hip", "cn_l_join.hip",
-    "cn_l_split.hip", "cn_l_diag.hip")]
+    "cn_l_split.hip", "cn_l_diag.hip", "cn_l_ptn.hip")]
 OBJ_DIR = os.path.join(_PKG, "lib", "obj")
 
 U64P = C.POINTER(C.c_uint64)
@@ -181,6 +181,10 @@ SIGNATURES = {
     "cn_sum_slots": (C.c_int, [_CTX, _H, _u32, _u32, _u32]),
     "cn_rowdot_batch": (C.c_int, [_CTX, _H, _u32, _H, _u32, _u32, _u32, _H, _u32]),
     "cn_mul_plain_sum": (C.c_int, [_CTX, _H, _u32, _H, _u32, U32P, U32P, _u32, _H, _u32]),
+    "cn_ptn_alloc": (C.c_int, [_CTX, _u32, C.POINTER(_H)]),
+    "cn_pt_transform": (C.c_int, [_CTX, _H, _u32, _u32, _H, _u32]),
+    "cn_ptn_upload": (C.c_int, [_CTX, _H, _u32, _u32, U64P]),
+    "cn_ptn_download": (C.c_int, [_CTX, _H, _u32, _u32, U64P]),
     "cn_set_rng_salt": (C.c_int, [_CTX, C.c_uint64]),
     "cn_set_rng_key": (C.c_int, [_CTX, C.c_char_p]),
     "cn_rng_selftest": (C.c_int, [_CTX, C.c_char_p, C.c_uint64, C.c_uint64, U32P]),
@@ -527,6 +531,26 @@ class Context:
     def pt_download(self, h, first, count):
         out = np.empty((count, self.n), dtype=np.uint64)
         self._chk(self.L.cn_pt_download(self._h, h, first, count, _p64(out)))
+        return out
+
+    def ptn_alloc(self, count):
+        """an array of `count` NTT-form plaintexts, [count][k][N] words (Evaluator.TransformToNtt): the operand mul_plain, rowdot_batch and mul_plain_sum take
+        in place of a coefficient-form handle, k times its size"""
+        h = _H()
+        self._chk(self.L.cn_ptn_alloc(self._h, count, C.byref(h)))
+        return h.value
+
+    def pt_transform(self, pt, pi, count, ptn, oi):
+        """ptn[oi + i] = NTT form of pt[pi + i], i < count (cn_pt_transform)"""
+        self._chk(self.L.cn_pt_transform(self._h, pt, pi, count, ptn, oi))
+
+    def ptn_upload(self, h, first, data):
+        d = np.ascontiguousarray(data, dtype=np.uint64).reshape(-1, self.k * self.n)
+        self._chk(self.L.cn_ptn_upload(self._h, h, first, d.shape[0], _p64(d)))
+
+    def ptn_download(self, h, first, count):
+        out = np.empty((count, self.k, self.n), dtype=np.uint64)
+        self._chk(self.L.cn_ptn_download(self._h, h, first, count, _p64(out)))
         return out
 
     def encode(self, values, pt, pi):

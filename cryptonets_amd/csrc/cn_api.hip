@@ -273,6 +273,7 @@ int ctx_init(cn_ctx *c, uint32_t n, uint32_t k, int device, std::vector<uint64_t
     env = getenv("CN_POOL_GB");
     c->pool_max = (size_t)((env ? atof(env) : 8.0) * (double)(1ull << 30));
     c->opt.f64 = !(getenv("CN_NO_F64") && atoi(getenv("CN_NO_F64")));
+    c->ptn_order = getenv("CN_PTN_ORDER") && atoi(getenv("CN_PTN_ORDER")) == 1;
     // fused key switch, workgroup order: limb-major up to N = 8192 (one key slice per XCD L2 at a time: 2.34 GiB fetched per 845-ciphertext launch
     // against 3.99 GiB in (ciphertext, limb) order and 3.0 GiB with the limbs of a ciphertext on one XCD, same kernel time -
     // profiles/r03_pmc_keyswitch_orders.txt); (ciphertext, limb) order at N = 16384, where limb-major measured 30 % slower in round 1
@@ -286,7 +287,7 @@ int ctx_init(cn_ctx *c, uint32_t n, uint32_t k, int device, std::vector<uint64_t
         CHECK(set_ks_attr<8>(lds)); CHECK(set_ks_attr<16>(lds));
     }
     for (int pol = 0; pol < 3; pol++) { CHECK(rr_ops[pol]->set_attrs(c->hc.logn, lds)); CHECK(ks_ops[pol]->set_attrs(c->hc.logn, lds)); }
-    CHECK(cn_l_diag_set_attrs(c->hc.logn, lds));
+    CHECK(cn_l_diag_set_attrs(c->hc.logn, lds)); CHECK(cn_l_ptn_set_attrs(c->hc.logn, lds));
     return 0;
 }
 extern "C" int cn_ctx_destroy(cn_ctx *ctx) {
@@ -375,6 +376,11 @@ extern "C" int cn_set_option(cn_ctx *ctx, const char *name, int value) { API_BOD
     if (!strcmp(name, "digit_mfma")) { ctx->digit_mfma = value != 0; defer_square_drop_plans(ctx); return 0; }     // the digit GEMM of plans made AFTER the call: matrix cores where eligible / FP64 (cn_eval.hip)
     if (!strcmp(name, "digit_i32")) { ctx->digit_i32 = value != 0; defer_square_drop_plans(ctx); return 0; }       // the digit sums of plans made AFTER the call (and of cn_mul_relin_sum): int32 words where they fit / doubles
     if (!strcmp(name, "mul_sum")) { ctx->mul_sum = value != 0; return 0; }       // cn_mul_relin_sum: one key switch per output where it can / always the literal sequence (cn_eval.hip)
+    if (!strcmp(name, "ptn_order")) {            // k_mul_ptn_sum, workgroup order: 0 limb-major, 1 limb = workgroup index mod k (cn_l_ptn.hip)
+        if (value < 0 || value > 1) return fail(CN_ERR_ARG, "ptn_order: 0 or 1");
+        ctx->ptn_order = value;
+        return 0;
+    }
     if (!strcmp(name, "record_steps")) {         // 1: record the RotateRows steps and column rotations asked for from now on (cn_rotation_steps); 0: stop and clear
         ctx->rec_steps = value != 0;
         if (!value) { ctx->rec_set.clear(); ctx->rec_cols = false; }
@@ -406,6 +412,10 @@ extern "C" int cn_get_option(cn_ctx *ctx, const char *name, int *value) { API_BO
     else if (!strcmp(name, "defer_pending_products")) *value = (int)ctx->dq->sq->out.size();                             // squarings whose relinearisation is held back right now
     else if (!strcmp(name, "digit_gemm_mfma")) *value = (int)std::min<uint64_t>(ctx->dg_mfma, 0x7fffffff);                 // digit GEMMs launched in the matrix-core form
     else if (!strcmp(name, "ks_digits_i32")) *value = (int)std::min<uint64_t>(ctx->ks_dig_i32, 0x7fffffff);                // key switches launched on int32 digit sums
+    else if (!strcmp(name, "ptn_order")) *value = ctx->ptn_order;
+    else if (!strcmp(name, "ptn_sum")) *value = (int)std::min<uint64_t>(ctx->ptn_sum, 0x7fffffff);                        // launches of k_mul_ptn_sum (cn_mul_plain_sum on NTT-form plaintexts)
+    else if (!strcmp(name, "ptn_bcast")) *value = (int)std::min<uint64_t>(ctx->ptn_bcast, 0x7fffffff);                    // launches of k_mul_plain_bcast on NTT-form plaintexts
+    else if (!strcmp(name, "ptn_sum_interval")) *value = (int)cn_ptn_sum_interval(cn_mod_range(ctx->hc, 0, ctx->hc.k).qmax);   // terms between two recentrings of its FP64 accumulators
     else if (!strcmp(name, "packed_bad_residues")) *value = (int)std::min<uint64_t>(ctx->packed_bad.load(), 0x7fffffff);      // packed uploads that held a residue >= its modulus
     else if (!strcmp(name, "mul_relin_pipelined")) *value = (int)std::min<uint64_t>(ctx->mr_pipelined, 0x7fffffff);      // Multiply + Relinearize batches run in parts over two streams
     else if (!strcmp(name, "behz_small_base")) *value = ctx->hc.bsk[ctx->hc.kb - 1].q < (1ull << 49);     // auxiliary primes below 2^49 (FP64 kernels) instead of SEAL's 61-bit ones
@@ -532,9 +542,9 @@ int dev_release(cn_ctx *ctx, uint64_t *p, size_t bytes) {
 int alloc_buf(cn_ctx *ctx, int kind, uint32_t count, uint32_t size, cn_handle *out) {
     if (!out || !count) return fail(CN_ERR_ARG, "bad allocation request");
     Buffer b; b.kind = kind; b.count = count; b.size = size;
-    b.item_words = kind == 0 ? (size_t)size * ctx->hc.k * ctx->hc.n : ctx->hc.n;
+    b.item_words = kind == 0 ? (size_t)size * ctx->hc.k * ctx->hc.n : (kind == 4 ? (size_t)ctx->hc.k * ctx->hc.n : ctx->hc.n);
     CHECK(dev_alloc(ctx, b.item_words * 8 * count, &b.d));
-    if (kind == 1) b.pt_zero.assign(count, 1);
+    if (kind == 1 || kind == 4) b.pt_zero.assign(count, 1);
     *out = ctx->bufs.insert(std::move(b));
     return 0;
 }
@@ -762,6 +772,31 @@ extern "C" int cn_pt_download(cn_ctx *ctx, cn_handle h, uint32_t first, uint32_t
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return 0;
 API_END }
+// NTT-form plaintext arrays (Buffer::kind 4, include/cnhip.h): [count][k][N] canonical words, limb j of plaintext p = NTT_j(lift_j(m_p)) - what
+// Evaluator.TransformToNtt(Plaintext, parms_id) leaves (SEAL 3.2 evaluator.cpp; the reference multiplies coefficient-form plaintexts only, EncryptedSealBfvMatrix.cs:79-120)
+extern "C" int cn_ptn_alloc(cn_ctx *ctx, uint32_t count, cn_handle *out) { API_BODY LOCK_ONLY; return alloc_buf(ctx, 4, count, 1, out); API_END }
+extern "C" int cn_ptn_upload(cn_ctx *ctx, cn_handle h, uint32_t first, uint32_t count, const uint64_t *host) { API_BODY
+    LOCK; NOT_CAPTURING("cn_ptn_upload"); GETPTN(b, h);
+    if (!range_ok(b, first, count) || !host) return fail(CN_ERR_ARG, "index out of range");
+    const uint32_t n = ctx->hc.n, k = ctx->hc.k;
+    std::vector<uint8_t> zero(count, 1);
+    for (uint32_t p = 0; p < count; p++)
+        for (uint32_t j = 0; j < k; j++) {
+            const uint64_t q = ctx->hc.q[j].q, *w = host + ((size_t)p * k + j) * n;
+            for (uint32_t i = 0; i < n; i++) { if (w[i] >= q) return fail(CN_ERR_ARG, "NTT-form plaintext word >= its coefficient modulus"); if (w[i]) zero[p] = 0; }
+        }
+    for (uint32_t p = 0; p < count; p++) b->pt_zero[first + p] = zero[p];
+    HIPCHK(hipMemcpyAsync(b->d + (size_t)first * b->item_words, host, (size_t)count * b->item_words * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return 0;
+API_END }
+extern "C" int cn_ptn_download(cn_ctx *ctx, cn_handle h, uint32_t first, uint32_t count, uint64_t *host) { API_BODY
+    LOCK; NOT_CAPTURING("cn_ptn_download"); GETPTN(b, h);
+    if (!range_ok(b, first, count) || !host) return fail(CN_ERR_ARG, "index out of range");
+    HIPCHK(hipMemcpyAsync(host, b->d + (size_t)first * b->item_words, (size_t)count * b->item_words * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return 0;
+API_END }
 // BatchEncoder.Encode / Decode of `count` plaintexts with ONE upload, one scatter launch and one batched (I)NTT mod t: the slot order is
 // SEAL's index map (matrix rows -> bit-reversed coefficient positions), kept on the device
 __global__ void k_encode_scatter(const uint64_t *__restrict__ values, uint32_t nvalues, const uint32_t *__restrict__ index_map, uint64_t *__restrict__ out, uint32_t n) {
@@ -841,7 +876,7 @@ extern "C" int cn_copy(cn_ctx *ctx, cn_handle src, uint32_t sfirst, cn_handle ds
     if (s->kind != d->kind || s->item_words != d->item_words) return fail(CN_ERR_ARG, "copy between different buffer shapes");
     if (!range_ok(s, sfirst, count) || !range_ok(d, dfirst, count)) return fail(CN_ERR_ARG, "index out of range");
     HIPCHK(hipMemcpyAsync(d->d + dfirst * d->item_words, s->d + sfirst * s->item_words, count * s->item_words * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    if (s->kind == 1) for (uint32_t i = 0; i < count; i++) d->pt_zero[dfirst + i] = s->pt_zero[sfirst + i];
+    if (s->kind == 1 || s->kind == 4) for (uint32_t i = 0; i < count; i++) d->pt_zero[dfirst + i] = s->pt_zero[sfirst + i];
     return 0;
 API_END }
 extern "C" int cn_device_ptr(cn_ctx *ctx, cn_handle h, void **ptr, size_t *bytes) {

@@ -85,7 +85,7 @@ static const uint32_t DEFER_STAGED_MAX = 4;       // per-ciphertext callers: cal
 // pointers.  CtSpan: `count` ciphertexts from d on, one after the other (size 2 - ctx->ctw2 words each - wherever no `polys` says otherwise).  PtSpan: plaintexts of N
 // coefficients from d on, `stride` plaintexts apart (0: one for every ciphertext); zero: their all-zero flags, or null when the caller has refused zero plaintexts already
 struct CtSpan { uint64_t *d; uint32_t count; };
-struct PtSpan { const uint64_t *d; uint32_t stride; const uint8_t *zero; };
+struct PtSpan { const uint64_t *d; uint32_t stride; const uint8_t *zero; bool ntt; };   // ntt: the plaintexts of an NTT-form array (Buffer::kind 4: k N words each, stride in plaintexts)
 // do_galois: in / out / tmp hold `count` size-2 ciphertexts; acc, pre, next_elt / next_out: see cn_eval.hip
 struct GaloisCall {
     const uint64_t *in; uint64_t elt; uint64_t *out, *tmp; uint32_t count;
@@ -329,10 +329,13 @@ static inline void rec_galois(cn_ctx *ctx, uint64_t elt) {                // cn_
 #define GETCT(var, h, sz) Buffer *var = getbuf(ctx, h, 0); if (!var) return fail(CN_ERR_ARG, "invalid ciphertext handle " #h); \
     if ((sz) && var->size != (uint32_t)(sz)) return fail(CN_ERR_ARG, "ciphertext size mismatch for " #h)
 #define GETPT(var, h) Buffer *var = getbuf(ctx, h, 1); if (!var) return fail(CN_ERR_ARG, "invalid plaintext handle " #h)
+// the operand of a plaintext product (cn_mul_plain, cn_rowdot_batch, cn_mul_plain_sum): a coefficient-form array or an NTT-form one (cn_pt_transform)
+#define GETPT_OR_PTN(var, h) Buffer *var = getbuf(ctx, h, 1); if (!var) var = getbuf(ctx, h, 4); if (!var) return fail(CN_ERR_ARG, "invalid plaintext handle " #h)
+#define GETPTN(var, h) Buffer *var = getbuf(ctx, h, 4); if (!var) return fail(CN_ERR_ARG, "invalid NTT-form plaintext handle " #h)
 #define SPAN(var, b, first, count) if (!range_ok(b, first, count)) return fail(CN_ERR_ARG, "index out of range"); \
     const CtSpan var{b->d + (size_t)(first) * b->item_words, count}
 #define PTSPAN(var, b, first, count, stride) if (!range_ok(b, first, (stride) ? count : 1, (stride) ? (stride) : 1)) return fail(CN_ERR_ARG, "index out of range"); \
-    const PtSpan var{b->d + (size_t)(first) * ctx->hc.n, stride, b->pt_zero.data() + (first)}
+    const PtSpan var{b->d + (size_t)(first) * b->item_words, stride, b->pt_zero.data() + (first), b->kind == 4}
 #define LOCK_ONLY CHECK(use(ctx)); CHECK(ring_sync(ctx, false))
 #define API_BODY return ctx->mu.run([&]() -> int {
 #define API_END });

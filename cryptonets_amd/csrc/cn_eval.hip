@@ -69,19 +69,36 @@ int mul_plain_fused(cn_ctx *ctx, CtSpan A, bool a_bcast, PtSpan P, CtSpan O, uin
     const uint64_t *src = A.d;
     // one input ciphertext broadcast over the outputs: it must survive until the last block has read it
     const int pol = cn_policy(cn_mod_range(ctx->hc, 0, k), ctx->opt.f64);
-    if (a_bcast && pstride && count >= 4 && ctx->opt.mp_bcast) {      // one ciphertext x many plaintexts: transform the ciphertext once, the plaintexts inside the product kernel
+    if (a_bcast && pstride && count >= 4 && ctx->opt.mp_bcast && !(P.ntt && !cn_rr_ptn_bcast(pol, ctx->hc.logn))) {      // one ciphertext x many plaintexts: transform the ciphertext once, the plaintexts inside the product kernel
         uint64_t *ctn = nx ? nx->ctn : nullptr;
         if (!nx) { CHECK(ensure_scratch(ctx, al(item_words * 8))); ctn = salloc<uint64_t>(ctx, item_words); }
         if (!ctn) return fail(CN_ERR_HIP, "internal: scratch exhausted in multiply_plain");
         HIPCHK(hipMemcpyAsync(ctn, src, item_words * 8, hipMemcpyDeviceToDevice, ctx->stream));
         CHECK(cn_run_ntt(ctx, ctn, polys * k, 0, k, 0));
-        rr_ops[pol]->mul_plain_bcast(ctx, P.d, pstride, ctn, o, count, polys, nx ? (uint32_t)nx->elt : 0u, nx ? nx->out : nullptr);
+        rr_ops[pol]->mul_plain_bcast(ctx, P.d, pstride, ctn, o, count, polys, nx ? (uint32_t)nx->elt : 0u, nx ? nx->out : nullptr, P.ntt);
         HIPCHK(hipGetLastError()); launch_count(ctx);
-        ctx->st.ntt_forward_limbs += (uint64_t)polys * k + (uint64_t)count * polys * k; ctx->st.ntt_inverse_limbs += (uint64_t)count * polys * k;
+        if (P.ntt) ctx->ptn_bcast++;                               // (NTT-form rows: no transform of the plaintexts ran)
+        if (!P.ntt) ctx->st.ntt_forward_limbs += (uint64_t)polys * k + (uint64_t)count * polys * k;      // (NTT-form rows: the polys k limbs cn_run_ntt counted are all that ran)
+        ctx->st.ntt_inverse_limbs += (uint64_t)count * polys * k;
         ctx->st.PlainMultiplication += count;
         return 0;
     }
     const bool alias = a_bcast && src >= o && src < o + (size_t)count * item_words;
+    if (P.ntt) {                                                   // NTT-form plaintexts: k_mul_plain_fused alone, reading the array where it lies (pstride as given)
+        if (nx) return fail(CN_ERR_ARG, "internal: chained row-dot batch outside the broadcast product");
+        if (alias) {
+            CHECK(ensure_scratch(ctx, al(item_words * 8)));
+            uint64_t *keep = salloc<uint64_t>(ctx, item_words);
+            if (!keep) return fail(CN_ERR_HIP, "internal: scratch exhausted in multiply_plain");
+            HIPCHK(hipMemcpyAsync(keep, src, item_words * 8, hipMemcpyDeviceToDevice, ctx->stream));
+            src = keep;
+        }
+        rr_ops[pol]->mul_plain_fused(ctx, nullptr, 0, 0, const_cast<uint64_t *>(P.d), src, a_bcast ? 0 : item_words, pstride, o, count, polys);
+        HIPCHK(hipGetLastError()); launch_count(ctx);
+        ctx->st.ntt_forward_limbs += (uint64_t)count * polys * k; ctx->st.ntt_inverse_limbs += (uint64_t)count * polys * k;
+        ctx->st.PlainMultiplication += count;
+        return 0;
+    }
     CHECK(ensure_scratch(ctx, al((size_t)npt * k * n * 8) + (alias ? al(item_words * 8) : 0)));
     uint64_t *lift = salloc<uint64_t>(ctx, (size_t)npt * k * n);
     if (alias) {
@@ -118,12 +135,17 @@ int mul_plain_impl(cn_ctx *ctx, CtSpan A, bool a_bcast, PtSpan P, CtSpan O, uint
     CHECK(plain_not_zero(P, count));
     if (ctx->opt.mp_fused && rr_kernels(ctx)) return mul_plain_fused(ctx, A, a_bcast, P, O, polys, nx);
     if (nx) return fail(CN_ERR_ARG, "internal: chained row-dot batch outside the fused product");
-    CHECK(ensure_scratch(ctx, al((size_t)npt * k * n * 8)));
-    uint64_t *lift = salloc<uint64_t>(ctx, (size_t)npt * k * n);
-    // lift every referenced plaintext into the k limbs (one launch), NTT them
-    hipLaunchKernelGGL(k_lift_plain, dim3(npt * k * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, P.d, lift, ctx->dc, ctx->chunks, pstride ? pstride : 1u);
-    HIPCHK(hipGetLastError()); launch_count(ctx);
-    CHECK(cn_run_ntt(ctx, lift, npt * k, 0, k, 0));
+    const uint64_t *lift = P.d;                                    // NTT-form plaintexts are multiplied where they lie: no lift, no transform of theirs
+    uint32_t dstride = pstride;
+    if (!P.ntt) {
+        CHECK(ensure_scratch(ctx, al((size_t)npt * k * n * 8)));
+        uint64_t *lf = salloc<uint64_t>(ctx, (size_t)npt * k * n);
+        // lift every referenced plaintext into the k limbs (one launch), NTT them
+        hipLaunchKernelGGL(k_lift_plain, dim3(npt * k * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, P.d, lf, ctx->dc, ctx->chunks, pstride ? pstride : 1u);
+        HIPCHK(hipGetLastError()); launch_count(ctx);
+        CHECK(cn_run_ntt(ctx, lf, npt * k, 0, k, 0));
+        lift = lf; dstride = pstride ? 1u : 0u;
+    }
     uint64_t *o = O.d;
     const uint64_t *src = A.d;
     if (a_bcast) {
@@ -132,21 +154,45 @@ int mul_plain_impl(cn_ctx *ctx, CtSpan A, bool a_bcast, PtSpan P, CtSpan O, uint
     } else if (o != src) HIPCHK(hipMemcpyAsync(o, src, count * item_words * 8, hipMemcpyDeviceToDevice, ctx->stream));
     uint32_t limbs = count * polys * k;
     CHECK(cn_run_ntt(ctx, o, limbs, 0, k, 0));
-    hipLaunchKernelGGL(k_dyadic_pt, dim3(limbs * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, o, lift, pstride ? 1u : 0u, ctx->dc, ctx->chunks, polys);
+    hipLaunchKernelGGL(k_dyadic_pt, dim3(limbs * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, o, lift, dstride, ctx->dc, ctx->chunks, polys);
     HIPCHK(hipGetLastError()); launch_count(ctx);
     CHECK(cn_run_ntt(ctx, o, limbs, 0, k, 1));
     ctx->st.PlainMultiplication += count;
     return 0;
 }
 extern "C" int cn_mul_plain(cn_ctx *ctx, cn_handle a, uint32_t ai, cn_handle pt, uint32_t pi, uint32_t pstride, cn_handle out, uint32_t oi, uint32_t count) { API_BODY
-    LOCK_ONLY; GETCT(A, a, 0); GETCT(O, out, A->size); GETPT(P, pt);
+    LOCK_ONLY; GETCT(A, a, 0); GETCT(O, out, A->size); GETPT_OR_PTN(P, pt);
     SPAN(sa, A, ai, count); SPAN(so, O, oi, count); PTSPAN(sp, P, pi, count, pstride);
-    if (queues(ctx, count) && A->size == 2) {                   // the per-row MultiplyPlain of an unchanged caller: queued, rows merged at flush
+    if (queues(ctx, count) && A->size == 2 && !sp.ntt) {       // (an NTT-form operand is never queued: the queue is flushed and the call runs at once)                 // the per-row MultiplyPlain of an unchanged caller: queued, rows merged at flush
         CHECK(plain_not_zero(sp, count)); CHECK(mul_plain_overlap(sa, so, A->item_words));
         return defer_staged(ctx, DOP_MULPLAIN, sa, CtSpan{}, so, 0, sp.d, pstride * ctx->hc.n);
     }
     CHECK(cn_defer_flush(ctx));
     return mul_plain_impl(ctx, sa, false, sp, so, A->size);
+API_END }
+// ptn[oi + i] = NTT-form of pt[pi + i], i < count: Evaluator.TransformToNtt(plain, parms_id) of SEAL (evaluator.cpp; the reference never calls it - its plaintext
+// products transform their operand on every call, EncryptedSealBfvMatrix.cs:79-120).  The words the product kernels read: limb j = NTT_j(lift_j(m)), canonical.
+// Register-radix sizes: ONE launch of k_lift_ntt into the array; other sizes and "legacy_ntt": k_lift_plain + the generic transform.  Only kernel launches: allowed
+// while a graph is recorded; the zero flags travel at call time.
+extern "C" int cn_pt_transform(cn_ctx *ctx, cn_handle pt, uint32_t pi, uint32_t count, cn_handle ptn, uint32_t oi) { API_BODY
+    LOCK; GETPT(P, pt); GETPTN(O, ptn);
+    if (!range_ok(P, pi, count) || !range_ok(O, oi, count)) return fail(CN_ERR_ARG, "index out of range");
+    if (!count) return 0;
+    const uint32_t n = ctx->hc.n, k = ctx->hc.k;
+    const uint64_t *src = P->d + (size_t)pi * n;
+    uint64_t *dst = O->d + (size_t)oi * O->item_words;
+    if (rr_kernels(ctx)) {
+        const int pol = cn_policy(cn_mod_range(ctx->hc, 0, k), ctx->opt.f64);
+        rr_ops[pol]->mul_plain_fused(ctx, src, 1, count, dst, nullptr, 0, 0, nullptr, 0, 0);
+        HIPCHK(hipGetLastError()); launch_count(ctx);
+        ctx->st.ntt_forward_limbs += (uint64_t)count * k;
+    } else {
+        hipLaunchKernelGGL(k_lift_plain, dim3(count * k * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, src, dst, ctx->dc, ctx->chunks, 1u);
+        HIPCHK(hipGetLastError()); launch_count(ctx);
+        CHECK(cn_run_ntt(ctx, dst, count * k, 0, k, 0));
+    }
+    for (uint32_t c = 0; c < count; c++) O->pt_zero[oi + c] = P->pt_zero[pi + c];
+    return 0;
 API_END }
 uint64_t lift_scalar(const DevConsts &hc, uint64_t w, uint32_t j) { return w >= hc.t_half ? w + hc.lift_inc[j] : w; }
 extern "C" int cn_mul_scalar(cn_ctx *ctx, cn_handle a, uint32_t ai, const uint64_t *scalars, uint32_t sstride, cn_handle out, uint32_t oi, uint32_t count) { API_BODY
@@ -1141,12 +1187,13 @@ API_END }
 // out[r] = SumAllSlots(v * pt[r], length) for r < rows: every row of a plaintext matrix against ONE packed ciphertext
 // (EncryptedSealBfvMatrix.Mul row-major, EncryptedSealBfvMatrix.cs:79-120 -> DotProduct, AtomicSealBfvVector.cs:963-977).
 extern "C" int cn_rowdot_batch(cn_ctx *ctx, cn_handle v, uint32_t vi, cn_handle pt, uint32_t pi, uint32_t rows, uint32_t length, cn_handle out, uint32_t oi) { API_BODY TWO_LIMBS("cn_rowdot_batch");
-    LOCK; GETCT(V, v, 2); GETCT(O, out, 2); GETPT(P, pt);
+    LOCK; GETCT(V, v, 2); GETCT(O, out, 2); GETPT_OR_PTN(P, pt);
     if (!rows) return 0;
     if (V == O && vi >= oi && vi < oi + rows) return fail(CN_ERR_ARG, "row-dot batch cannot overwrite its input");
     SPAN(sv, V, vi, 1); SPAN(so, O, oi, rows); PTSPAN(sp, P, pi, rows, 1u);
     if (length != 1) rec_sum_slots(ctx, length);
-    if (length != 1 && mul_plain_takes_bcast(ctx, rows)) {
+    const bool ptn_fused = sp.ntt && !cn_rr_ptn_bcast(cn_policy(cn_mod_range(ctx->hc, 0, ctx->hc.k), ctx->opt.f64), ctx->hc.logn);   // NTT-form rows without a broadcast kernel
+    if (length != 1 && mul_plain_takes_bcast(ctx, rows) && !ptn_fused) {
         // the product kernel hands the chain its first permuted c1 (no k_galois_limbs pass over the products): one arena for the chain's two scratch arrays and the
         // transformed ciphertext, sized here and left where it is until the chain has run
         const std::vector<uint64_t> elts = sum_slots_chain_elts(ctx, rows, length);
@@ -1168,7 +1215,8 @@ API_END }
 // and AddMany per group.
 extern "C" int cn_mul_plain_sum(cn_ctx *ctx, cn_handle ct, uint32_t ci, cn_handle pt, uint32_t pi, const uint32_t *grp_off, const uint32_t *ct_idx, uint32_t G,
                                 cn_handle out, uint32_t oi) { API_BODY
-    LOCK; GETCT(A, ct, 2); GETCT(O, out, 2); GETPT(P, pt);
+    LOCK; GETCT(A, ct, 2); GETCT(O, out, 2); GETPT_OR_PTN(P, pt);
+    const bool ptn = P->kind == 4;                                   // NTT-form plaintexts (cn_pt_transform): k_mul_ptn_sum, no transform of theirs
     if (!grp_off || !ct_idx) return fail(CN_ERR_ARG, "null argument");
     if (!G) return fail(CN_ERR_ARG, "cn_mul_plain_sum of an empty list");
     if (grp_off[0]) return fail(CN_ERR_ARG, "cn_mul_plain_sum: grp_off[0] must be 0");
@@ -1187,7 +1235,7 @@ extern "C" int cn_mul_plain_sum(cn_ctx *ctx, cn_handle ct, uint32_t ci, cn_handl
     const uint32_t n = ctx->hc.n, k = ctx->hc.k;
     const CnModRange qr = cn_mod_range(ctx->hc, 0, k);
     const int pol = cn_policy(qr, ctx->opt.f64);
-    if (!(ctx->opt.mp_fused && rr_kernels(ctx) && cn_l_mul_plain_sum_kernel(pol, ctx->hc.logn))) {      // compose the existing calls
+    if (!(ctx->opt.mp_fused && rr_kernels(ctx) && (ptn ? cn_l_mul_ptn_sum_kernel(pol, ctx->hc.logn) : cn_l_mul_plain_sum_kernel(pol, ctx->hc.logn)))) {      // compose the existing calls
         cn_handle tmp = 0;
         CHECK(alloc_buf(ctx, 0, maxlen, 2, &tmp));
         int rc = 0;
@@ -1196,9 +1244,9 @@ extern "C" int cn_mul_plain_sum(cn_ctx *ctx, cn_handle ct, uint32_t ci, cn_handl
         for (uint32_t g = 0; g < G && !rc; g++) {
             const uint32_t len = grp_off[g + 1] - grp_off[g];
             Buffer *T = getbuf(ctx, tmp, 0);                                      // (the handle table may have moved)
-            A = getbuf(ctx, ct, 0); O = getbuf(ctx, out, 0); P = getbuf(ctx, pt, 1);
+            A = getbuf(ctx, ct, 0); O = getbuf(ctx, out, 0); P = getbuf(ctx, pt, ptn ? 4 : 1);
             for (uint32_t i = 0, e = grp_off[g]; i < len && !rc; i++, e++)      // (ranges and zero plaintexts were checked above)
-                rc = mul_plain_impl(ctx, CtSpan{A->d + (ci + ct_idx[e]) * ctx->ctw2, 1}, false, PtSpan{P->d + (size_t)(pi + e) * n, 1, nullptr}, CtSpan{T->d + i * ctx->ctw2, 1}, 2);
+                rc = mul_plain_impl(ctx, CtSpan{A->d + (ci + ct_idx[e]) * ctx->ctw2, 1}, false, PtSpan{P->d + (size_t)(pi + e) * P->item_words, 1, nullptr, ptn}, CtSpan{T->d + i * ctx->ctw2, 1}, 2);
             if (rc) break;
             if ((rc = ensure_scratch(ctx, al((size_t)len * 4)))) break;
             uint32_t *didx;
@@ -1236,8 +1284,11 @@ extern "C" int cn_mul_plain_sum(cn_ctx *ctx, cn_handle ct, uint32_t ci, cn_handl
     }
     CHECK(cn_run_ntt(ctx, ctn, D * 2 * k, 0, k, 0));
     const uint32_t accmax = pol == POL_U64 ? 0xffffffffu : (qr.bits >= 50 ? 1u : (1u << std::min(10, 50 - qr.bits)));      // lazy FP64 accumulators: |term| <= 2.1 q, sum below 2^52
-    CHECK(cn_l_mul_plain_sum(ctx, pol, MulPlainSumLaunch{P->d + (size_t)pi * n, ctn, dgo, dslot, O->d + (size_t)oi * O->item_words, G, accmax}));
-    ctx->st.ntt_forward_limbs += (uint64_t)D * 2 * k + (uint64_t)E * 2 * k; ctx->st.ntt_inverse_limbs += (uint64_t)G * 2 * k;
+    if (ptn) CHECK(cn_l_mul_ptn_sum(ctx, pol, MulPlainSumLaunch{P->d + (size_t)pi * P->item_words, ctn, dgo, dslot, O->d + (size_t)oi * O->item_words, G,
+                                                                pol == POL_U64 ? 0xffffffffu : cn_ptn_sum_interval(qr.qmax)}));
+    else CHECK(cn_l_mul_plain_sum(ctx, pol, MulPlainSumLaunch{P->d + (size_t)pi * n, ctn, dgo, dslot, O->d + (size_t)oi * O->item_words, G, accmax}));
+    if (!ptn) ctx->st.ntt_forward_limbs += (uint64_t)D * 2 * k + (uint64_t)E * 2 * k;      // (NTT-form plaintexts: the D 2k limbs cn_run_ntt counted are all that ran)
+    ctx->st.ntt_inverse_limbs += (uint64_t)G * 2 * k;
     ctx->st.PlainMultiplication += E; ctx->st.AddMany += G; ctx->st.AddManyItemCount += E;
     return 0;
 API_END }

@@ -79,7 +79,9 @@ __global__ void __launch_bounds__(NttPlan<L>::NT) k_lift_ntt(const uint64_t *__r
 // shapes) - a launch, a fifth of the transforms and that round trip less.
 // next_elt != 0: the c1 limbs (poly 1) leave a second time, permuted by the Galois element of the rotation that follows (the first link of the row-dot batch's
 // SumAllSlots chain, k_keyswitch_pair14): next_out[row][k][N] - staged through the exchange image (coalesced stores), no permutation pass in front of the chain.
-template <int L, class AR>
+// PTN: the rows are NTT-form plaintexts (cn_pt_transform: pt [row][k][N], canonical words at the positions k_lift_ntt stored them) - load, lift and forward
+// transform become 16-byte loads of the row's words at the positions the thread multiplies at; everything behind is the same code.
+template <int L, class AR, bool PTN = false>
 __global__ void __launch_bounds__(NttPlan<L>::NT) k_mul_plain_bcast(const uint64_t *__restrict__ pt, uint32_t pitch, const uint64_t *__restrict__ ctn, uint64_t *__restrict__ out,
                                                                     const DevConsts *__restrict__ C, uint32_t polys, uint32_t next_elt, uint64_t *__restrict__ next_out) {
     typedef typename AR::T T;
@@ -90,24 +92,35 @@ __global__ void __launch_bounds__(NttPlan<L>::NT) k_mul_plain_bcast(const uint64
     const uint32_t tid = threadIdx.x, k = C->k, j = blockIdx.x % k, cp = blockIdx.x / k, row = cp / polys, p = cp % polys;
     const ArCtx<AR> A(C, j);
     const TensorOps<AR> ops(C, j);
-    const uint64_t *x = pt + (size_t)row * pitch * n, th = C->t_half, inc = C->lift_inc[j];
     const uint64_t *w = ctn + ((size_t)p * k + j) * n;
     T v[16];
-#pragma unroll
-    for (int r = 0; r < 16; r++) { const uint64_t m = x[pass_index<L, SA, 0>(tid, r)]; v[r] = A.load(m >= th ? m + inc : m); }
-    ntt_forward_regs<AR, L>(v, s, A.fw, A.m, tid);
     uint32_t tm = tid;
-    asm volatile("" : "+v"(tm));
+    if constexpr (PTN) {
+        const uint64_t *x = pt + (((size_t)row * pitch) * k + j) * n;
+#pragma unroll
+        for (int r = 0; r < 16; r += 2) {
+            const ulonglong2 m = *reinterpret_cast<const ulonglong2 *>(x + tail_index<L>(tm, r));
+            v[r] = A.load(m.x); v[r + 1] = A.load(m.y);
+        }
+    } else {
+        const uint64_t *x = pt + (size_t)row * pitch * n, th = C->t_half, inc = C->lift_inc[j];
+#pragma unroll
+        for (int r = 0; r < 16; r++) { const uint64_t m = x[pass_index<L, SA, 0>(tid, r)]; v[r] = A.load(m >= th ? m + inc : m); }
+        ntt_forward_regs<AR, L>(v, s, A.fw, A.m, tid);
+        asm volatile("" : "+v"(tm));
+    }
 #pragma unroll
     for (int r = 0; r < 16; r += 2) {
         const ulonglong2 y = *reinterpret_cast<const ulonglong2 *>(w + tail_index<L>(tm, r));
-        if constexpr (std::is_same<T, double>::value) {                   // lazy transform output x canonical word: exact (see KsMac)
+        if constexpr (std::is_same<T, double>::value) {                   // lazy transform output (PTN: canonical word) x canonical word: exact (see KsMac)
             v[r] = ops.mul(v[r], A.load(y.x), A); v[r + 1] = ops.mul(v[r + 1], A.load(y.y), A);
+        } else if constexpr (PTN) {
+            v[r] = ops.mul(v[r], y.x, A); v[r + 1] = ops.mul(v[r + 1], y.y, A);
         } else {
             v[r] = ops.mul(A.canon(v[r]), y.x, A); v[r + 1] = ops.mul(A.canon(v[r + 1]), y.y, A);
         }
     }
-    if (!ntt_tail_local<L>()) __syncthreads();
+    if (!PTN && !ntt_tail_local<L>()) __syncthreads();                   // (PTN: nobody has touched the image yet)
     uint32_t ti = tid;
     asm volatile("" : "+v"(ti));
     ntt_inverse_regs<AR, L>(v, s, A.iv, A.m, ti);

@@ -18,6 +18,7 @@ template <int L> static int set_attrs_l(size_t bytes) {
         if constexpr (L <= 13) { CHECK(big_lds(k_square_fused<L, AR, true>, bytes + ((size_t)8 << L))); CHECK(big_lds(k_square_pipe<L, AR>, bytes + ((size_t)8 << L))); }
     }
     CHECK(big_lds(k_lift_ntt<L, AR>, bytes)); CHECK(big_lds(k_mul_plain_fused<L, AR>, bytes)); CHECK(big_lds(k_mul_plain_bcast<L, AR>, bytes));
+    if constexpr (kF64 || L <= 13) CHECK(big_lds(k_mul_plain_bcast<L, AR, true>, bytes));
 #ifdef RR_ENC_TAIL
     CHECK(big_lds(k_encrypt_tail<L, AR>, bytes));
 #endif
@@ -75,24 +76,31 @@ static bool square_fused(cn_ctx *c, const uint64_t *A, size_t astride, const uin
     BY_SIZE(l_square_fused, c, A, astride, atab, D, cnt, base_off, Lm)
 }
 
-// dense MultiplyPlain in two launches (k_lift_ntt, k_mul_plain_fused)
+// dense MultiplyPlain in two launches (k_lift_ntt, k_mul_plain_fused).  pt null: `lift` holds the NTT form already (an NTT-form plaintext array: the product
+// kernel alone); src null: the lift alone, into `lift` (cn_pt_transform)
 template <int L> static void l_mul_plain_fused(cn_ctx *c, const uint64_t *pt, uint32_t pitch, uint32_t npt, uint64_t *lift, const uint64_t *src, size_t sstride,
                                                uint32_t pstride, uint64_t *out, uint32_t count, uint32_t polys) {
     const size_t lds = (size_t)ntt_lds_words(1u << L) * 8;
-    hipLaunchKernelGGL((k_lift_ntt<L, AR>), dim3(npt * c->hc.k), dim3(NttPlan<L>::NT), lds, c->stream, pt, pitch, lift, c->dc);
-    hipLaunchKernelGGL((k_mul_plain_fused<L, AR>), dim3(count * polys * c->hc.k), dim3(NttPlan<L>::NT), lds, c->stream, src, sstride, lift, pstride, out, c->dc, polys);
+    if (pt) hipLaunchKernelGGL((k_lift_ntt<L, AR>), dim3(npt * c->hc.k), dim3(NttPlan<L>::NT), lds, c->stream, pt, pitch, lift, c->dc);
+    if (src) hipLaunchKernelGGL((k_mul_plain_fused<L, AR>), dim3(count * polys * c->hc.k), dim3(NttPlan<L>::NT), lds, c->stream, src, sstride, lift, pstride, out, c->dc, polys);
 }
 static bool mul_plain_fused(cn_ctx *c, const uint64_t *pt, uint32_t pitch, uint32_t npt, uint64_t *lift, const uint64_t *src, size_t sstride, uint32_t pstride,
                             uint64_t *out, uint32_t count, uint32_t polys) { BY_SIZE(l_mul_plain_fused, c, pt, pitch, npt, lift, src, sstride, pstride, out, count, polys) }
 
-// one ciphertext (NTT form in ctn) times `count` plaintexts: one launch
+// one ciphertext (NTT form in ctn) times `count` plaintexts: one launch.  ptn: the plaintexts are rows of an NTT-form array ([row][k][N], pitch in rows)
 template <int L> static void l_mul_plain_bcast(cn_ctx *c, const uint64_t *pt, uint32_t pitch, const uint64_t *ctn, uint64_t *out, uint32_t count, uint32_t polys, uint32_t next_elt,
-                                               uint64_t *next_out) {
-    hipLaunchKernelGGL((k_mul_plain_bcast<L, AR>), dim3(count * polys * c->hc.k), dim3(NttPlan<L>::NT), (size_t)ntt_lds_words(1u << L) * 8, c->stream, pt, pitch, ctn, out, c->dc, polys,
+                                               uint64_t *next_out, bool ptn) {
+    // (no NTT-form instantiation under the integer policy at N = 16384, where it spills like the default form does: cn_rr_ptn_bcast, the caller runs k_mul_plain_fused alone)
+    if (ptn) {
+        if constexpr (kF64 || L <= 13)
+            hipLaunchKernelGGL((k_mul_plain_bcast<L, AR, true>), dim3(count * polys * c->hc.k), dim3(NttPlan<L>::NT), (size_t)ntt_lds_words(1u << L) * 8, c->stream, pt, pitch, ctn, out,
+                               c->dc, polys, next_elt, next_out);
+    } else hipLaunchKernelGGL((k_mul_plain_bcast<L, AR>), dim3(count * polys * c->hc.k), dim3(NttPlan<L>::NT), (size_t)ntt_lds_words(1u << L) * 8, c->stream, pt, pitch, ctn, out, c->dc, polys,
                        next_elt, next_out);
 }
-static bool mul_plain_bcast(cn_ctx *c, const uint64_t *pt, uint32_t pitch, const uint64_t *ctn, uint64_t *out, uint32_t count, uint32_t polys, uint32_t next_elt, uint64_t *next_out) {
-    BY_SIZE(l_mul_plain_bcast, c, pt, pitch, ctn, out, count, polys, next_elt, next_out)
+static bool mul_plain_bcast(cn_ctx *c, const uint64_t *pt, uint32_t pitch, const uint64_t *ctn, uint64_t *out, uint32_t count, uint32_t polys, uint32_t next_elt, uint64_t *next_out,
+                            bool ptn) {
+    BY_SIZE(l_mul_plain_bcast, c, pt, pitch, ctn, out, count, polys, next_elt, next_out, ptn)
 }
 
 #ifdef RR_ENC_TAIL

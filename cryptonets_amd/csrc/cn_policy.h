@@ -32,5 +32,21 @@ inline bool cn_digit_sum_fits_i32(uint64_t sum_abs_w, int dbc) {
     if (dbc < 1 || dbc > 31) return false;
     return (unsigned __int128)sum_abs_w * ((1ull << dbc) - 1) <= 0x7fffffffull;
 }
+// Sums over NTT-form plaintexts on the FP64 policies (k_mul_ptn_sum, cn_k_ptn.hip.h): a term is ArF64T::mulmod of two canonical words below q < 2^50, exact with
+// |term| <= q/2 + 3 q^2 / 2^53 (the quotient is rint of a product rounded three times).  cn_ptn_term_bound rounds that up to an integer; cn_ptn_sum_interval is how
+// many terms the lazy accumulators take between two recentrings: the largest count with count x bound < 2^52 (a recentred accumulator adds at most q/2 + 1 < 2^49:
+// every partial sum stays below 2^53), capped at CN_PTN_INTERVAL_CAP, which *capped reports (the counter is a 32-bit word; small moduli would allow millions).
+static const uint32_t CN_PTN_INTERVAL_CAP = 1u << 16;
+inline uint64_t cn_ptn_term_bound(uint64_t q) {
+    const unsigned __int128 sq = (unsigned __int128)3 * q * q;
+    return q / 2 + 1 + (uint64_t)((sq + (((unsigned __int128)1 << 53) - 1)) >> 53);
+}
+inline uint32_t cn_ptn_sum_interval(uint64_t qmax, bool *capped = nullptr) {
+    const uint64_t fit = ((1ull << 52) - 1) / cn_ptn_term_bound(qmax);
+    if (capped) *capped = fit > CN_PTN_INTERVAL_CAP;
+    return fit > CN_PTN_INTERVAL_CAP ? CN_PTN_INTERVAL_CAP : (fit ? (uint32_t)fit : 1u);
+}
+// k_mul_plain_bcast on NTT-form rows: every register-radix size but N = 16384 under the integer policy (spills; the product kernel alone runs there)
+inline bool cn_rr_ptn_bcast(int policy, uint32_t logn) { return !(policy == POL_U64 && logn == 14); }
 // the ring sizes of the register-radix kernels: 1024 <= N <= 16384, or N <= 8192 (max_logn = 13) for the kernels that stop there
 inline bool cn_rr_size(uint32_t logn, uint32_t max_logn = 14) { return logn >= 10 && logn <= max_logn; }

@@ -35,7 +35,7 @@ struct CapturedGraph {
     std::vector<Member> members;           // in lock order (more limbs first); empty for cn_graph_begin
 };
 struct Buffer {
-    int kind;                 // 0 = ciphertext array, 1 = dense plaintext array, 2 = scalar GEMM plan, 3 = captured graph
+    int kind;                 // 0 = ciphertext array, 1 = dense plaintext array, 2 = scalar GEMM plan, 3 = captured graph, 4 = NTT-form plaintext array [pt][k][N]
     std::shared_ptr<GemmPlan> plan;
     std::shared_ptr<CapturedGraph> cg;
     uint32_t count, size;     // size = polys per ciphertext
@@ -222,6 +222,8 @@ struct cn_ctx {
     bool digit_i32 = true;     // cn_set_option "digit_i32": plans made from now on (and cn_mul_relin_sum calls) hand their digit sums S to the key switch as int32 words where the bound
                                // allows it (cn_digit_sum_fits_i32, cn_policy.h: half the bytes of S); false: always doubles.  Set by name like "digit_mfma" (no environment override)
     uint64_t ks_dig_i32 = 0;   // key switches launched on int32 digit sums ("ks_digits_i32")
+    int ptn_order = 0;         // k_mul_ptn_sum, workgroup order ("ptn_order", CN_PTN_ORDER): 0 limb-major, 1 limb = workgroup index mod k (a limb per XCD at k = 8)
+    uint64_t ptn_sum = 0, ptn_bcast = 0;   // launches of k_mul_ptn_sum / of k_mul_plain_bcast on NTT-form plaintexts ("ptn_sum", "ptn_bcast")
     bool defer_square_gemm = false;  // cn_set_option "defer_square_gemm" (default 0: its effect on the literal call sequence has not been measured, profiles/deferred_square_gemm.md): queued squarings launched by a layer-boundary flush keep their relinearisation back; scalar products that read
                                // nothing else run as cn_square_gemm's second half - one key switch per dense OUTPUT (cn_defer.hip); false: every queued squaring relinearises at once.
                                // Set by name like "digit_mfma" (no environment override)
@@ -300,11 +302,11 @@ struct RrOps {                // register-radix kernels of one arithmetic policy
     bool (*intt_tensor)(cn_ctx *c, const uint64_t *A, const uint64_t *B, uint64_t *D, uint32_t cnt, uint32_t base_off, uint32_t Lm, bool lazy);   // lazy (FP64 policies): D as lazy-FP64 hand-off words
     bool (*square_fused)(cn_ctx *c, const uint64_t *A, size_t astride, const uint64_t *const *atab, uint64_t *D, uint32_t cnt, uint32_t base_off, uint32_t Lm);   // FP64 policies; D: lazy-FP64 hand-off words
     bool (*mul_plain_fused)(cn_ctx *c, const uint64_t *pt, uint32_t pitch, uint32_t npt, uint64_t *lift, const uint64_t *src, size_t sstride, uint32_t pstride,
-                            uint64_t *out, uint32_t count, uint32_t polys);
+                            uint64_t *out, uint32_t count, uint32_t polys);            // pt null: `lift` is the NTT form already; src null: the lift alone
     bool (*enc_tail)(cn_ctx *c, const uint64_t *u, const uint64_t *pt, uint32_t pts, uint64_t *out, uint32_t cnt, const int8_t *noise, const void *tab);   // U64, F64; tab: EncTab[cnt] or null
     bool (*enc_fused)(cn_ctx *c, const int8_t *us, const uint64_t *pt, uint32_t pts, uint64_t *out, uint32_t cnt, const int8_t *noise, const void *tab);  // all policies, N <= 8192: u (int8) -> transform -> both components in one kernel
     bool (*mul_plain_bcast)(cn_ctx *c, const uint64_t *pt, uint32_t pitch, const uint64_t *ctn, uint64_t *out, uint32_t count, uint32_t polys, uint32_t next_elt,
-                            uint64_t *next_out);                                       // ONE ciphertext (NTT form) x count plaintexts (+ sigma_next(c1) of every product on the side)
+                            uint64_t *next_out, bool ptn);                             // ONE ciphertext (NTT form) x count plaintexts (+ sigma_next(c1) of every product on the side); ptn: NTT-form plaintexts
     bool (*enc_fold)(cn_ctx *c, const int8_t *us, const int8_t *noise, const void *fout, const void *terms, uint32_t outputs);   // FP64 policies, N <= 8192: k_encrypt_fold
 };
 struct KsOps {
@@ -363,6 +365,11 @@ struct MulPlainSumLaunch { const uint64_t *pt, *ctn; const uint32_t *grp_off, *s
 int cn_l_mul_plain_sum(cn_ctx *c, int policy, const MulPlainSumLaunch &a);
 bool cn_l_mul_plain_sum_kernel(int policy, uint32_t logn);      // is there a kernel?  Every register-radix size but N = 16384 under the integer policy
 int cn_l_diag_set_attrs(uint32_t logn, size_t lds);
+// the same sums over an NTT-form plaintext array (cn_l_ptn.hip, k_mul_ptn_sum): a.pt = the NTT-form words of term 0 ([term][k][N], cn_pt_transform), a.accmax = the
+// recentring interval of the lazy FP64 accumulators (cn_ptn_sum_interval, cn_policy.h).  A kernel at every register-radix size but N = 16384 under the integer policy
+int cn_l_mul_ptn_sum(cn_ctx *c, int policy, const MulPlainSumLaunch &a);
+bool cn_l_mul_ptn_sum_kernel(int policy, uint32_t logn);
+int cn_l_ptn_set_attrs(uint32_t logn, size_t lds);
 // modulus switching (cn_l_modswitch.hip): `items` (ciphertext, poly) pairs [items][ks][N] -> [items][kd][N] on c's stream with the constants of the source context
 int cn_l_mod_switch(cn_ctx *c, const uint64_t *src, uint64_t *dst, const DevConsts *src_consts, uint32_t ks, uint32_t kd, uint32_t items, uint32_t logn,
                     bool f64, bool *ran_f64);

@@ -71,7 +71,7 @@ def choose_baby_steps(mask):
     return best[1]
 
 
-def dense_path_counts(R, Dim, n, k, digits, length=None, B=None):
+def dense_path_counts(R, Dim, n, k, digits, length=None, B=None, ntt_weights=False):
     """Limb transforms (one N-point transform of one limb) of the two ways to compute the dense product of an R x Dim plaintext matrix with one packed ciphertext on a
     ring of n slots with k coefficient moduli and `digits` digit polynomials per key switch (ks_digits of the Galois decomposition bit count):
 
@@ -83,6 +83,9 @@ def dense_path_counts(R, Dim, n, k, digits, length=None, B=None):
                                 the key switches of _rotation_counts, 2 k forward per distinct rotated input, 2 k forward per diagonal (a workgroup per polynomial
                                 transforms the plaintext itself) and 2 k inverse per group
 
+    ntt_weights: the row plaintexts / the diagonals are resident in NTT form (hewrapper.NTT_WEIGHTS, cn_pt_transform) - their transforms drop out of both counts:
+    2 k per row on the default path, 2 k per diagonal on the diagonal path.
+
     Weights are taken as dense inside R x Dim (structural_diagonals).  Returns a dict with the two totals, their parts and "choice": "diagonal" if and only if its
     total is lower."""
     m = n // 2
@@ -93,13 +96,13 @@ def dense_path_counts(R, Dim, n, k, digits, length=None, B=None):
         links, ln = 1, m
     links += max(ln - 1, 0).bit_length()
     d_ks = R * links
-    d_plain = 2 * k + R * 4 * k + R * 7 * k
+    d_plain = 2 * k + R * (2 if ntt_weights else 4) * k + R * 7 * k
     mask = structural_diagonals(R, Dim, n)
     if B is None:
         B = choose_baby_steps(mask)
     babies, ngroups, g_ks = _rotation_counts(mask, B)
     terms = int(mask.sum())
-    g_plain = babies * 2 * k + terms * 2 * k + ngroups * 2 * k
+    g_plain = babies * 2 * k + (0 if ntt_weights else terms * 2 * k) + ngroups * 2 * k
     default, diagonal = d_ks * per_ks + d_plain, g_ks * per_ks + g_plain
     return {"default": default, "diagonal": diagonal, "choice": "diagonal" if diagonal < default else "default", "B": B,
             "default_key_switches": d_ks, "diagonal_key_switches": g_ks, "default_plain_transforms": d_plain, "diagonal_plain_transforms": g_plain,

@@ -76,6 +76,11 @@ DEVICE_SPLIT = True
 # (the same integer linear map mod t); the ciphertext words and the noise differ.  False (default): the calls and words of the default path, always.
 # profiles/diag_dense.md: what was measured.
 DIAGONAL_DENSE = False
+# NTT_WEIGHTS = True: the weight plaintexts a row-major matrix keeps on the device for its products - the row plaintexts and one-hot masks of RowsDotProduct, the
+# pre-rotated diagonals of DiagonalDense - are kept in NTT form (cn_pt_transform): every later product multiplies without transforming them again.
+# Same ciphertext words.  The arrays are k times the coefficient form (CIFAR: rows 5.4 GiB, diagonals 16 GiB per prime), so this is asked for, never a default;
+# a backend without pt_transform (the CPU oracle of the tests) keeps the coefficient form.
+NTT_WEIGHTS = False
 
 
 def _device_split_ok(env, encrypt):
@@ -152,11 +157,11 @@ class ClientCrypto:
 
 # ------------------------------------------------------------------------------------------------ device buffers
 class _Buf:
-    """Ref-counted device array of ciphertexts (kind 'ct') or dense plaintexts (kind 'pt')."""
+    """Ref-counted device array of ciphertexts (kind 'ct'), dense plaintexts (kind 'pt') or NTT-form plaintexts (kind 'ptn')."""
 
     def __init__(self, ctx, kind, count, size=2):
         self.ctx, self.kind, self.count, self.size, self.refs = ctx, kind, count, size, 0
-        self.h = ctx.ct_alloc(count, size) if kind == "ct" else ctx.pt_alloc(count)
+        self.h = ctx.ct_alloc(count, size) if kind == "ct" else (ctx.ptn_alloc(count) if kind == "ptn" else ctx.pt_alloc(count))
 
     def view(self, first=0, count=None):
         return _View(self, first, self.count - first if count is None else count)
@@ -1637,7 +1642,7 @@ class EncryptedSealBfvMatrix:
         return r
 
     def Dispose(self):
-        for cache in ("_rowpt", "_rowmask"):
+        for cache in ("_rowpt", "_rowmask", "_rowptn"):
             for buf in self.__dict__.pop(cache, {}).values():
                 buf.release()
         for (_, pts) in self.__dict__.pop("_diagplan", {}).values():
@@ -1880,6 +1885,18 @@ class EncryptedSealBfvMatrix:
             cache[key] = buf
         return cache[key]
 
+    def _row_ptn(self, i, env_i):
+        """the rows of _row_plaintexts in NTT form (NTT_WEIGHTS): what RowsDotProduct hands to rowdot_batch - transformed once per context (level).  The
+        coefficient-form rows stay: _diagonal_plan and the bias path read them"""
+        cache = self.__dict__.setdefault("_rowptn", {})
+        key = (i, env_i.ctx)
+        if key not in cache:
+            rows = self._row_plaintexts(i, env_i)
+            buf = _Buf(env_i.ctx, "ptn", rows.count).view()
+            env_i.ctx.pt_transform(rows.h, rows.first, rows.count, buf.h, 0)
+            cache[key] = buf
+        return cache[key]
+
     def _can_batch_rows(self, v):
         return (not LITERAL and self.Format == EMatrixFormat.RowMajor and v.IsEncrypted and v.Format == EVectorFormat.dense
                 and all(a.encData.count == 1 for a in v.eVectors)
@@ -1901,7 +1918,8 @@ class EncryptedSealBfvMatrix:
         def one_prime(i, e):
             ctx, slots = e.ctx, e.SlotCount
             src = v.eVectors[i].encData
-            pts = self._row_plaintexts(i, e)
+            ntt = NTT_WEIGHTS and hasattr(ctx, "pt_transform")
+            pts = self._row_ptn(i, e) if ntt else self._row_plaintexts(i, e)
             work = _Buf(ctx, "ct", R)
             wv = work.view()
             ln = INT_MAX if full else int(length)
@@ -1915,11 +1933,15 @@ class EncryptedSealBfvMatrix:
             fmt = EVectorFormat.sparse if ln >= slots else EVectorFormat.dense
             if ForceOutputInColumns:
                 mcache = self.__dict__.setdefault("_rowmask", {})
-                if (i, ctx) not in mcache:                           # one-hot masks e_r (SumAllSlots ForceOutputInColumn, :936-945), per context (level)
+                if (i, ctx, ntt) not in mcache:                      # one-hot masks e_r (SumAllSlots ForceOutputInColumn, :936-945), per context (level) and form
                     masks = _Buf(ctx, "pt", R).view()
                     ctx.encode_batch(np.eye(R, dtype=np.uint64), masks.h, 0)          # e_0 .. e_{R-1} in one call
-                    mcache[(i, ctx)] = masks
-                masks = mcache[(i, ctx)]
+                    if ntt:
+                        coeff, masks = masks, _Buf(ctx, "ptn", R).view()
+                        ctx.pt_transform(coeff.h, 0, R, masks.h, 0)
+                        coeff.release()
+                    mcache[(i, ctx, ntt)] = masks
+                masks = mcache[(i, ctx, ntt)]
                 ctx.mul_plain(work.h, 0, masks.h, 0, work.h, 0, R)
                 tot = _Buf(ctx, "ct", 1)
                 ctx.add_many(work.h, list(range(R)), tot.h, 0)
@@ -1954,7 +1976,7 @@ class EncryptedSealBfvMatrix:
         R, n = len(self.leVectors), ctx.n
         if R > n or v.Dim > n:
             return None
-        return diagonal.dense_path_counts(R, int(v.Dim), n, len(ctx.q), diagonal.ks_digits(ctx.q, ctx.gdbc))
+        return diagonal.dense_path_counts(R, int(v.Dim), n, len(ctx.q), diagonal.ks_digits(ctx.q, ctx.gdbc), ntt_weights=NTT_WEIGHTS and hasattr(ctx, "pt_transform"))
 
     def DiagonalDenseWins(self, v, env):
         c = self.DiagonalDenseCounts(v, env)
@@ -1962,25 +1984,36 @@ class EncryptedSealBfvMatrix:
 
     def _diagonal_plan(self, i, env_i, B=None):
         """(plan, device array of its pre-rotated diagonal plaintexts) for prime i - built once per context (level), like _row_plaintexts: the weights are the
-        integers the row plaintexts hold, rotated in slot space on the host and encoded in chunks"""
+        integers the row plaintexts hold, rotated in slot space on the host and encoded in chunks.  Under NTT_WEIGHTS the array holds the diagonals in NTT form: each
+        chunk is encoded into a chunk-sized plaintext buffer and transformed into the array, so the resident footprint is k times the coefficient form, not k + 1"""
         from . import diagonal
         cache = self.__dict__.setdefault("_diagplan", {})
-        key = (i, env_i.ctx, B)
+        ntt = NTT_WEIGHTS and hasattr(env_i.ctx, "pt_transform")
+        key = (i, env_i.ctx, B, ntt)
         if key not in cache:
             ctx = env_i.ctx
             R, dim = len(self.leVectors), int(self.leVectors[0].Dim)
             rows = self._row_plaintexts(i, env_i)
             W = np.ascontiguousarray(ctx.decode_batch(rows.h, rows.first, R)[:, :dim])
             bound = int(diagonal.structural_diagonals(R, dim, ctx.n).sum())
-            pts = _Buf(ctx, "pt", bound).view()
+            chunk = 256
+            pts = _Buf(ctx, "ptn" if ntt else "pt", bound).view()
+            stage = _Buf(ctx, "pt", min(chunk, bound)).view() if ntt else None
 
             def emit(first, slots):
-                ctx.encode_batch(slots, pts.h, pts.first + first)
+                if ntt:
+                    ctx.encode_batch(slots, stage.h, 0)
+                    ctx.pt_transform(stage.h, 0, len(slots), pts.h, pts.first + first)
+                else:
+                    ctx.encode_batch(slots, pts.h, pts.first + first)
             try:
-                plan = diagonal.build_plan(W, ctx.n, emit, B=B)
+                plan = diagonal.build_plan(W, ctx.n, emit, B=B, chunk=chunk)
             except BaseException:
                 pts.release()
                 raise
+            finally:
+                if stage is not None:
+                    stage.release()
             cache[key] = (plan, pts)
         return cache[key]
 

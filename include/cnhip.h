@@ -139,6 +139,8 @@ int cn_mod_switch(cn_ctx *src, cn_handle in, uint32_t ii, uint32_t count, cn_ctx
  *                                                                   link's permuted c1 beside its result (no permutation pass between links)
  *   "mp_bcast"       flag    1                     -                cn_rowdot_batch transforms its ONE ciphertext once and the row plaintexts inside the
  *                                                                   product kernel; 0 = k_lift_ntt + k_mul_plain_fused
+ *   "ptn_order"      0..1    0                     CN_PTN_ORDER     cn_mul_plain_sum on NTT-form plaintexts, workgroup order: 0 limb-major, 1 limb = workgroup
+ *                                                                   index mod k (one limb per XCD where k = 8)
  *   "defer"          0..2    0                     -                deferred submission of per-ciphertext calls (below)
  *   "defer_square_gemm" flag 0                     -                queued squarings keep their relinearisation back for the dense layer that
  *                                                                   reads them: one key switch per dense output (below); 0 = every squaring relinearises
@@ -434,6 +436,25 @@ int cn_rowdot_batch(cn_ctx *ctx, cn_handle v, uint32_t vi, cn_handle pt, uint32_
  * value, like those of cn_add_many and cn_copy_many. */
 int cn_mul_plain_sum(cn_ctx *ctx, cn_handle ct, uint32_t ci, cn_handle pt, uint32_t pi, const uint32_t *grp_off, const uint32_t *ct_idx, uint32_t G,
                      cn_handle out, uint32_t oi);
+/* ---- NTT-form plaintext arrays: the weights of a fixed model, transformed once (Evaluator.TransformToNtt(Plaintext, parms_id), SEAL 3.2 evaluator.cpp; the
+ * reference has no such call - every plaintext product of EncryptedSealBfvMatrix.cs:79-120 transforms its plaintext again).
+ * An array holds `count` plaintexts as [count][k][N] words of ONE context: limb j of plaintext p is NTT_j(lift_j(m_p)), canonical residues mod q_j in the
+ * library's transform order - the words of cn_ct_ntt on a polynomial whose limb j is lift_j(m).  It costs k times the memory of the coefficient form, so it is a
+ * form the caller asks for.  A handle belongs to its context: a level context makes its own array (its first `limbs` limbs, transformed again).
+ * cn_pt_transform: ptn[oi + i] = TransformToNtt(pt[pi + i]), i < count, with the plaintexts' zero flags; one kernel launch on 1024 <= N <= 16384 (allowed while
+ * a graph is recorded and on level contexts); CN_ERR_ARG when either range leaves its handle.
+ * cn_ptn_upload / cn_ptn_download move [count][k][N] words (a plan kept on disk or sent to another device); upload returns CN_ERR_ARG, nothing written, when a word
+ * is not below its q_j, and derives the zero flags from the words.
+ * cn_mul_plain, cn_rowdot_batch and cn_mul_plain_sum accept such a handle where they take `pt` (indices and strides count plaintexts): same words as with the
+ * coefficient form, without any transform of the plaintexts - cn_mul_plain runs the product kernel alone (and is never queued under "defer": the queue is
+ * flushed and the call runs at once), cn_rowdot_batch multiplies the rows where they lie, cn_mul_plain_sum streams them through one multiply-accumulate kernel
+ * (cn_get_option "ptn_sum" / "ptn_bcast" count the launches of the last two; "ptn_sum_interval" is the number of terms between two recentrings of the FP64
+ * accumulators).  CN_ERR_ZERO for a zero plaintext as before.  Every other call that takes a plaintext handle (cn_add_plain, cn_encrypt*, cn_decode*,
+ * cn_pt_upload / cn_pt_download, the bias of cn_gemm_plan_create, the split / join calls) returns CN_ERR_ARG for one. */
+int cn_ptn_alloc(cn_ctx *ctx, uint32_t count, cn_handle *out);
+int cn_pt_transform(cn_ctx *ctx, cn_handle pt, uint32_t pi, uint32_t count, cn_handle ptn, uint32_t oi);
+int cn_ptn_upload(cn_ctx *ctx, cn_handle h, uint32_t first, uint32_t count, const uint64_t *host);
+int cn_ptn_download(cn_ctx *ctx, cn_handle h, uint32_t first, uint32_t count, uint64_t *host);
 
 /* ---- client side on the device (what SEAL's KeyGenerator / Encryptor / Decryptor do for
  * AtomicSealBfvEncryptedEnvironment.SetKeys / Encrypt / Decrypt, AtomicSealBfvVector.cs:62-74,1030-1110,1202-1232), for data

@@ -11,6 +11,12 @@ with the flag off and on - time of the 5488 x 16268 layer inside the network (bi
 decrypted outputs equal the integer model (networks.lola_cifar_dense_model).
 
     python tools/diag_dense_probe.py [--shapes tiny,cifar,large,network] [--primes 1] [--rounds 3] [--out profiles/diag_dense.md]
+
+--ntt-weights: the diagonal path with its plan in coefficient form and in NTT form (hewrapper.NTT_WEIGHTS, cn_pt_transform: DESIGN 6h), both resident in one
+process, timed in alternating rounds on the same input ciphertext after one untimed round each; plan build time and resident bytes of each form; all decrypted
+slots compared across the two forms and with W v mod t.  --rowdot adds RowsDotProduct (cn_rowdot_batch over all rows, no masks) with the flag off and on.
+
+    python tools/diag_dense_probe.py --ntt-weights [--rowdot] [--shapes tiny,cifar,large] [--primes 1] [--rounds 5] [--out profiles/ntt_weights.md]
 """
 import argparse
 import os
@@ -140,6 +146,107 @@ def probe(name, nprimes, rounds, say):
     return equal and model
 
 
+def probe_ntt(name, nprimes, rounds, rowdot, say):
+    """coefficient-form plan against NTT-form plan of the diagonal path, alternating rounds in one process"""
+    s = SHAPES[name]
+    parms = dict(s["parms"])
+    parms["primes"] = tuple(parms["primes"])[:nprimes]
+    R, Dim = s["R"], s["Dim"]
+    rng = np.random.default_rng(11)
+    W = rng.integers(-s["wmax"], s["wmax"] + 1, size=(R, Dim)).astype(float)
+    W[:, 0] = np.where(W.any(axis=1), W[:, 0], 1)
+    v = rng.integers(-s["vmax"], s["vmax"] + 1, size=Dim).astype(float)
+    F = EncryptedSealBfvFactory(**parms)
+    env = F.AllocateComputationEnv()
+    ctx0 = env.Environments[0].ctx
+    k, n = len(ctx0.q), ctx0.n
+    mat = F.GetPlainMatrix(W, EMatrixFormat.RowMajor, 1.0)
+    vec = F.GetEncryptedVector(v, EVectorFormat.dense, 1.0)
+    say("### %s: %d x %d, N = %d, k = %d, %d plaintext prime(s) %s" % (name, R, Dim, n, k, len(parms["primes"]), list(parms["primes"])))
+    say("")
+    hewrapper.DIAGONAL_DENSE = True
+    build, plans = {}, {}
+    for flag in (False, True):                                       # plans of both forms become resident (cache keys carry the flag)
+        hewrapper.NTT_WEIGHTS = flag
+        if flag:
+            mat._row_plaintexts(0, env.Environments[0])              # (the rows the plan reads are there already: only the plan itself is timed)
+        sync(env)
+        t0 = time.perf_counter()
+        plans[flag] = [mat._diagonal_plan(i, e)[0] for i, e in enumerate(env.Environments)]
+        sync(env)
+        build[flag] = time.perf_counter() - t0
+        mat.DiagonalDense(vec, env).Dispose()                        # untimed round
+    ms, outs = {False: [], True: []}, {False: None, True: None}
+    launches0 = [e.ctx.get_option("ptn_sum") for e in env.Environments]
+    for _ in range(rounds):
+        for flag in (False, True):
+            hewrapper.NTT_WEIGHTS = flag
+            if outs[flag] is not None:
+                outs[flag].Dispose()
+            sync(env)
+            t0 = time.perf_counter()
+            outs[flag] = mat.DiagonalDense(vec, env)
+            sync(env)
+            ms[flag].append((time.perf_counter() - t0) * 1e3)
+    ran = [e.ctx.get_option("ptn_sum") - l for e, l in zip(env.Environments, launches0)]
+    a, _ = slots_and_budgets(outs[False], env)
+    b, _ = slots_and_budgets(outs[True], env)
+    words = all(np.array_equal(e.ctx.ct_download(x.encData.h, x.encData.first, 1), e.ctx.ct_download(y.encData.h, y.encData.first, 1))
+                for x, y, e in zip(outs[False].eVectors, outs[True].eVectors, env.Environments))
+    equal = all(np.array_equal(x, y) for x, y in zip(a, b))
+    t = [int(e.ctx.t) for e in env.Environments]
+    want = (W.astype(np.int64) @ v.astype(np.int64))
+    model = all(np.array_equal(x[:R].astype(np.int64), np.mod(want, ti)) and not x[R:].any() for x, ti in zip(b, t))
+    p = plans[True][0]
+    say("| diagonal path | coefficient-form plan | NTT-form plan |")
+    say("|---|---|---|")
+    say("| time per layer, ms (min / median of %d, alternating) | %.2f / %.2f | %.2f / %.2f |"
+        % (rounds, min(ms[False]), statistics.median(ms[False]), min(ms[True]), statistics.median(ms[True])))
+    say("| plan built in, s (all primes; host rotation + encode%s) | %.2f | %.2f |" % (", + cn_pt_transform per chunk", build[False], build[True]))
+    say("| resident plan plaintexts per prime, MiB | %.1f | %.1f |" % (p.terms * n * 8 / 2 ** 20, p.terms * k * n * 8 / 2 ** 20))
+    say("")
+    say("ratio coefficient / NTT form (medians): %.2f.  %d diagonals, %d rotated inputs, %d groups; `k_mul_ptn_sum` launches in the timed rounds per prime: %s.  "
+        "Ciphertext words equal: %s; all %d decrypted slots equal across the two forms: %s; equal to W v mod t with zeros at %d and above: %s."
+        % (statistics.median(ms[False]) / statistics.median(ms[True]), p.terms, len(p.babies), len(p.groups), ran, words, n, equal, R, model))
+    say("")
+    ok = words and equal and model
+    for x in outs.values():
+        x.Dispose()
+    if rowdot:
+        hewrapper.DIAGONAL_DENSE = False
+        rms, rout = {False: [], True: []}, {}
+        for flag in (False, True):
+            hewrapper.NTT_WEIGHTS = flag
+            for x in mat.RowsDotProduct(vec, env):                   # untimed: the rows (and their NTT form) become resident
+                x.Dispose()
+        for _ in range(rounds):
+            for flag in (False, True):
+                hewrapper.NTT_WEIGHTS = flag
+                for x in rout.get(flag, []):
+                    x.Dispose()
+                sync(env)
+                t0 = time.perf_counter()
+                rout[flag] = mat.RowsDotProduct(vec, env)
+                sync(env)
+                rms[flag].append((time.perf_counter() - t0) * 1e3)
+        same = all(np.array_equal(e.ctx.ct_download(rout[False][0].eVectors[i].encData.buf.h, 0, R), e.ctx.ct_download(rout[True][0].eVectors[i].encData.buf.h, 0, R))
+                   for i, e in enumerate(env.Environments))
+        say("`RowsDotProduct` (cn_rowdot_batch, %d rows, all slots), ms, min / median of %d alternating rounds: coefficient-form rows %.2f / %.2f, NTT-form rows %.2f / %.2f "
+            "(resident rows %.1f against %.1f MiB per prime); all ciphertext words equal: %s."
+            % (R, rounds, min(rms[False]), statistics.median(rms[False]), min(rms[True]), statistics.median(rms[True]), R * n * 8 / 2 ** 20, R * k * n * 8 / 2 ** 20, same))
+        say("")
+        ok = ok and same
+        for outs_ in rout.values():
+            for x in outs_:
+                x.Dispose()
+    hewrapper.DIAGONAL_DENSE = hewrapper.NTT_WEIGHTS = False
+    vec.Dispose()
+    mat.Dispose()
+    for e in env.Environments:
+        e.ctx.close()
+    return ok
+
+
 def mulmod(a, b, p):
     b = np.asarray(b, dtype=np.uint64)
     hi = (a * (b >> np.uint64(20))) % p
@@ -215,22 +322,35 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="tiny,cifar,large")
     ap.add_argument("--primes", type=int, default=1, help="plaintext primes of the N = 16384 shapes (the tiny shape always takes its two)")
-    ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "diag_dense.md"))
+    ap.add_argument("--rounds", type=int, default=None, help="timed rounds (default 3; 5 with --ntt-weights)")
+    ap.add_argument("--ntt-weights", action="store_true", help="coefficient-form plan against NTT-form plan of the diagonal path, alternating rounds")
+    ap.add_argument("--rowdot", action="store_true", help="with --ntt-weights: RowsDotProduct with the flag off and on as well")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    a.rounds = a.rounds or (5 if a.ntt_weights else 3)
+    a.out = a.out or os.path.join(ROOT, "profiles", "ntt_weights.md" if a.ntt_weights else "diag_dense.md")
     lines = []
 
     def say(x):
         print(x, flush=True)
         lines.append(x)
-    say("# Dense layers by generalized diagonals: `tools/diag_dense_probe.py`")
-    say("")
-    say("One MI355X, one process, one image; both paths on the same input ciphertext, plans and plaintexts resident, wall clock around `Mul(..., ForceDenseFormat=True)` and a")
-    say("host wait on every context.  Synthetic integer weights, a fresh input encryption (see the tool's docstring).")
-    say("")
     ok = True
-    for name in a.shapes.split(","):
-        ok = (network(say) if name == "network" else probe(name, 2 if name == "tiny" else a.primes, a.rounds, say)) and ok
+    if a.ntt_weights:
+        say("# NTT-form weight plaintexts: `tools/diag_dense_probe.py --ntt-weights`, %d plaintext prime(s) at N = 16384" % a.primes)
+        say("")
+        say("One MI355X, one process, one image; the diagonal path with its plan in coefficient form and in NTT form (`hewrapper.NTT_WEIGHTS`), both resident, alternating")
+        say("rounds on the same input ciphertext after an untimed round each, wall clock around `DiagonalDense` and a host wait on every context, clocks as found.")
+        say("")
+        for name in a.shapes.split(","):
+            ok = probe_ntt(name, 2 if name == "tiny" else a.primes, a.rounds, a.rowdot, say) and ok
+    else:
+        say("# Dense layers by generalized diagonals: `tools/diag_dense_probe.py`")
+        say("")
+        say("One MI355X, one process, one image; both paths on the same input ciphertext, plans and plaintexts resident, wall clock around `Mul(..., ForceDenseFormat=True)` and a")
+        say("host wait on every context.  Synthetic integer weights, a fresh input encryption (see the tool's docstring).")
+        say("")
+        for name in a.shapes.split(","):
+            ok = (network(say) if name == "network" else probe(name, 2 if name == "tiny" else a.primes, a.rounds, say)) and ok
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
         f.write("\n".join(lines) + "\n")
