@@ -18,7 +18,7 @@ SOURCES = [os.path.join(CSRC, f) for f in (
     "cn_api.hip", "cn_eval.hip", "cn_client.hip", "cn_defer.hip", "cn_multi.hip", "cn_host.cpp", "cn_tables.cpp", "cn_l_gemm.hip", "cn_l_behz.hip",
     "cn_l_rr_u64.hip", "cn_l_rr_f64.hip", "cn_l_rr_f64l.hip", "cn_l_ks_u64.hip", "cn_l_ks_f64.hip", "cn_l_ks_f64l.hip", "cn_level.hip", "cn_l_modswitch.hip",
     "cn_l_modswitch_f64.hip", "cn_l_noise.hip", "cn_l_seeded.hip", "cn_l_keygen.hip", "cn_l_packed.hip", "cn_l_join.hip",
-    "cn_l_split.hip", "cn_l_diag.hip", "cn_l_ptn.hip")]
+    "cn_l_split.hip", "cn_l_diag.hip", "cn_l_ptn.hip", "cn_l_diagplan.hip")]
 OBJ_DIR = os.path.join(_PKG, "lib", "obj")
 
 U64P = C.POINTER(C.c_uint64)
@@ -185,6 +185,8 @@ SIGNATURES = {
     "cn_pt_transform": (C.c_int, [_CTX, _H, _u32, _u32, _H, _u32]),
     "cn_ptn_upload": (C.c_int, [_CTX, _H, _u32, _u32, U64P]),
     "cn_ptn_download": (C.c_int, [_CTX, _H, _u32, _u32, U64P]),
+    "cn_diag_scan": (C.c_int, [_CTX, _H, _u32, _u32, _u32, C.POINTER(C.c_uint8)]),
+    "cn_diag_encode": (C.c_int, [_CTX, _H, _u32, _u32, _u32, U32P, _u32, _H, _u32]),
     "cn_set_rng_salt": (C.c_int, [_CTX, C.c_uint64]),
     "cn_set_rng_key": (C.c_int, [_CTX, C.c_char_p]),
     "cn_rng_selftest": (C.c_int, [_CTX, C.c_char_p, C.c_uint64, C.c_uint64, U32P]),
@@ -552,6 +554,18 @@ class Context:
         out = np.empty((count, self.k, self.n), dtype=np.uint64)
         self._chk(self.L.cn_ptn_download(self._h, h, first, count, _p64(out)))
         return out
+
+    def diag_scan(self, rows, ri, R, dim):
+        """bool [2, N / 2]: does the generalized diagonal (c, i) of the R x dim matrix whose rows are the plaintexts rows[ri .. ri + R) hold a non-zero?  (cn_diag_scan)"""
+        out = np.zeros((2, self.n // 2), dtype=np.uint8)
+        self._chk(self.L.cn_diag_scan(self._h, rows, ri, R, dim, out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out.astype(bool)
+
+    def diag_encode(self, rows, ri, R, dim, terms, out, oi):
+        """out[oi + e] = the encoded pre-rotated diagonal diagonal.pre_rotated_rows(W, n, [terms[e]]) of that matrix, terms = [(c, J, b)]; out: a pt_alloc or a
+        ptn_alloc array (cn_diag_encode)"""
+        t = np.ascontiguousarray(terms, dtype=np.uint32).reshape(-1, 3)
+        self._chk(self.L.cn_diag_encode(self._h, rows, ri, R, dim, t.ctypes.data_as(U32P), t.shape[0], out, oi))
 
     def encode(self, values, pt, pi):
         v = np.ascontiguousarray(values, dtype=np.uint64)

@@ -415,6 +415,9 @@ extern "C" int cn_get_option(cn_ctx *ctx, const char *name, int *value) { API_BO
     else if (!strcmp(name, "ptn_order")) *value = ctx->ptn_order;
     else if (!strcmp(name, "ptn_sum")) *value = (int)std::min<uint64_t>(ctx->ptn_sum, 0x7fffffff);                        // launches of k_mul_ptn_sum (cn_mul_plain_sum on NTT-form plaintexts)
     else if (!strcmp(name, "ptn_bcast")) *value = (int)std::min<uint64_t>(ctx->ptn_bcast, 0x7fffffff);                    // launches of k_mul_plain_bcast on NTT-form plaintexts
+    else if (!strcmp(name, "scratch_mib")) *value = (int)std::min<size_t>((ctx->scap + (1u << 20) - 1) >> 20, 0x7fffffff);       // size of the scratch arena right now (it only grows)
+    else if (!strcmp(name, "diag_scan")) *value = (int)std::min<uint64_t>(ctx->diag_scan, 0x7fffffff);                    // launches of k_diag_scan (cn_diag_scan)
+    else if (!strcmp(name, "diag_encode")) *value = (int)std::min<uint64_t>(ctx->diag_encode, 0x7fffffff);                // launches of k_diag_gather (cn_diag_encode)
     else if (!strcmp(name, "ptn_sum_interval")) *value = (int)cn_ptn_sum_interval(cn_mod_range(ctx->hc, 0, ctx->hc.k).qmax);   // terms between two recentrings of its FP64 accumulators
     else if (!strcmp(name, "packed_bad_residues")) *value = (int)std::min<uint64_t>(ctx->packed_bad.load(), 0x7fffffff);      // packed uploads that held a residue >= its modulus
     else if (!strcmp(name, "mul_relin_pipelined")) *value = (int)std::min<uint64_t>(ctx->mr_pipelined, 0x7fffffff);      // Multiply + Relinearize batches run in parts over two streams
@@ -865,6 +868,115 @@ extern "C" int cn_decode_batch(cn_ctx *ctx, cn_handle pt, uint32_t pi, uint32_t 
     return 0;
 API_END }
 extern "C" int cn_decode(cn_ctx *ctx, cn_handle pt, uint32_t pi, uint64_t *values) { return cn_decode_batch(ctx, pt, pi, 1, values); }
+// ---- a generalized-diagonal plan built where the weights lie (cn_diag_scan, cn_diag_encode; cn_l_diagplan.hip).  Both decode the row plaintexts
+// rows[ri .. ri + R) into the slot-order matrix S [R][N] in scratch - the device half of cn_decode_batch - and keep nothing between calls.
+static int diag_check(cn_ctx *ctx, const char *what, Buffer *B, uint32_t ri, uint32_t R, uint32_t dim) {
+    const uint32_t n = ctx->hc.n;
+    if (!ctx->hc.batching) return fail(CN_ERR_ARG, "%s: plain modulus does not support batching", what);
+    if (n < 2) return fail(CN_ERR_ARG, "%s: a ring of %u coefficients has no slot rows", what, n);
+    if (R > n) return fail(CN_ERR_ARG, "%s: R = %u rows do not fit the %u slots", what, R, n);
+    if (!dim || dim > n) return fail(CN_ERR_ARG, "%s: dim = %u is not in 1 .. %u", what, dim, n);
+    if (!range_ok(B, ri, R)) return fail(CN_ERR_ARG, "%s: rows[ri .. ri + R) leaves its handle", what);
+    return 0;
+}
+// bytes of diag_decode_rows' two arrays / the decode itself: copy, forward transform mod t, gather into slot order (*S)
+static size_t diag_decode_bytes(cn_ctx *ctx, uint32_t R) { return 2 * al((size_t)R * ctx->hc.n * 8); }
+static int diag_decode_rows(cn_ctx *ctx, Buffer *B, uint32_t ri, uint32_t R, uint64_t **S) {
+    const uint32_t n = ctx->hc.n;
+    const size_t words = (size_t)R * n;
+    uint64_t *tmp = salloc<uint64_t>(ctx, words), *slots = salloc<uint64_t>(ctx, words);
+    if (!tmp || !slots) return fail(CN_ERR_HIP, "internal: scratch exhausted in the decode of a diagonal plan");
+    *S = slots;
+    if (!R) return 0;
+    HIPCHK(hipMemcpyAsync(tmp, B->d + (size_t)ri * n, words * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    CHECK(cn_run_ntt(ctx, tmp, R, ctx->hc.k + ctx->hc.kb, 1, 0));
+    hipLaunchKernelGGL(k_decode_gather, dim3((n + 255) / 256, R), dim3(256), 0, ctx->stream, tmp, ctx->d_index_map, slots, n);
+    HIPCHK(hipGetLastError()); launch_count(ctx);
+    return 0;
+}
+extern "C" int cn_diag_scan(cn_ctx *ctx, cn_handle rows, uint32_t ri, uint32_t R, uint32_t dim, uint8_t *nonzero) { API_BODY
+    LOCK; NOT_CAPTURING("cn_diag_scan");
+    Buffer *B = getbuf(ctx, rows, 1);
+    if (!B) return fail(CN_ERR_ARG, "cn_diag_scan: rows is not a coefficient-form plaintext handle");
+    CHECK(diag_check(ctx, "cn_diag_scan", B, ri, R, dim));
+    if (!nonzero) return fail(CN_ERR_ARG, "cn_diag_scan: nonzero is null");
+    const uint32_t n = ctx->hc.n;
+    CHECK(ensure_index_map(ctx));
+    CHECK(ensure_scratch(ctx, diag_decode_bytes(ctx, R) + al(n)));
+    uint64_t *S; CHECK(diag_decode_rows(ctx, B, ri, R, &S));
+    uint8_t *flags = salloc<uint8_t>(ctx, n);
+    if (!flags) return fail(CN_ERR_HIP, "internal: scratch exhausted in cn_diag_scan");
+    HIPCHK(hipMemsetAsync(flags, 0, n, ctx->stream));
+    CHECK(cn_l_diag_scan(ctx, S, R, dim, flags));
+    HIPCHK(hipMemcpyAsync(nonzero, flags, n, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return 0;
+API_END }
+static const uint32_t DIAG_STAGE = 256, DIAG_PT_CHUNK = 8192;       // terms per gather launch: into the staging array of an NTT-form output / into a coefficient-form output
+extern "C" int cn_diag_encode(cn_ctx *ctx, cn_handle rows, uint32_t ri, uint32_t R, uint32_t dim, const uint32_t *terms, uint32_t count, cn_handle out, uint32_t oi) { API_BODY
+    LOCK; NOT_CAPTURING("cn_diag_encode");
+    Buffer *B = getbuf(ctx, rows, 1);
+    if (!B) return fail(CN_ERR_ARG, "cn_diag_encode: rows is not a coefficient-form plaintext handle");
+    CHECK(diag_check(ctx, "cn_diag_encode", B, ri, R, dim));
+    Buffer *O = getbuf(ctx, out, 1);
+    if (!O) O = getbuf(ctx, out, 4);
+    if (!O) return fail(CN_ERR_ARG, "cn_diag_encode: out is neither a plaintext handle nor an NTT-form plaintext handle");
+    if (O == B) return fail(CN_ERR_ARG, "cn_diag_encode: out must not be rows");
+    if (!range_ok(O, oi, count)) return fail(CN_ERR_ARG, "cn_diag_encode: out[oi .. oi + count) leaves its handle");
+    if (count && !terms) return fail(CN_ERR_ARG, "cn_diag_encode: terms is null");
+    const uint32_t n = ctx->hc.n, m = n / 2, k = ctx->hc.k;
+    for (uint32_t e = 0; e < count; e++) {
+        const uint32_t *t3 = terms + (size_t)e * 3;
+        if (t3[0] > 1) return fail(CN_ERR_ARG, "cn_diag_encode: terms[%u]: c = %u is not 0 or 1", e, t3[0]);
+        if (t3[1] >= m) return fail(CN_ERR_ARG, "cn_diag_encode: terms[%u]: J = %u is not below N / 2 = %u", e, t3[1], m);
+        if (t3[2] >= m) return fail(CN_ERR_ARG, "cn_diag_encode: terms[%u]: b = %u is not below N / 2 = %u", e, t3[2], m);
+    }
+    if (!count) return 0;
+    const bool ntt = O->kind == 4;
+    const uint32_t chunk = ntt ? DIAG_STAGE : DIAG_PT_CHUNK;
+    // runs: neighbours with the same (c, J) and consecutive b, cut at CN_DIAG_RUN terms and at the chunks; `first` counts from the chunk's first term
+    std::vector<DiagRunHost> runs;
+    std::vector<uint32_t> run0;                                      // first run of every chunk, and the end
+    for (uint32_t e = 0; e < count; e++) {
+        const uint32_t *t3 = terms + (size_t)e * 3;
+        if (e % chunk == 0) run0.push_back((uint32_t)runs.size());
+        if (e % chunk && runs.back().len < CN_DIAG_RUN && runs.back().c == t3[0] && runs.back().J == t3[1] && runs.back().b0 + runs.back().len == t3[2]) runs.back().len++;
+        else runs.push_back(DiagRunHost{t3[0], t3[1], t3[2], 1, e % chunk});
+    }
+    run0.push_back((uint32_t)runs.size());
+    CHECK(ensure_index_map(ctx));
+    const uint32_t stage_n = ntt ? std::min(count, DIAG_STAGE) : 0;
+    CHECK(ensure_scratch(ctx, diag_decode_bytes(ctx, R) + al((size_t)stage_n * n * 8) + al(runs.size() * sizeof(DiagRunHost)) + al(count)));
+    uint64_t *S; CHECK(diag_decode_rows(ctx, B, ri, R, &S));
+    uint64_t *stage = salloc<uint64_t>(ctx, (size_t)stage_n * n);
+    DiagRunHost *druns; CHECK(upload_tmp(ctx, runs.data(), runs.size(), &druns));
+    uint8_t *nz = salloc<uint8_t>(ctx, count);
+    if (!stage || !nz) return fail(CN_ERR_HIP, "internal: scratch exhausted in cn_diag_encode");
+    HIPCHK(hipMemsetAsync(nz, 0, count, ctx->stream));
+    const int pol = cn_policy(cn_mod_range(ctx->hc, 0, k), ctx->opt.f64);
+    for (uint32_t e0 = 0, ch = 0; e0 < count; e0 += chunk, ch++) {
+        const uint32_t cnt = std::min(chunk, count - e0);
+        uint64_t *coef = ntt ? stage : O->d + (size_t)(oi + e0) * n;
+        CHECK(cn_l_diag_gather(ctx, S, R, dim, druns + run0[ch], run0[ch + 1] - run0[ch], ctx->d_index_map, coef, nz + e0));
+        CHECK(cn_run_ntt(ctx, coef, cnt, k + ctx->hc.kb, 1, 1));
+        if (!ntt) continue;
+        uint64_t *dst = O->d + (size_t)(oi + e0) * O->item_words;   // the staging chunk into the NTT form, as cn_pt_transform writes it
+        if (rr_kernels(ctx)) {
+            rr_ops[pol]->mul_plain_fused(ctx, stage, 1, cnt, dst, nullptr, 0, 0, nullptr, 0, 0);
+            HIPCHK(hipGetLastError()); launch_count(ctx);
+            ctx->st.ntt_forward_limbs += (uint64_t)cnt * k;
+        } else {
+            hipLaunchKernelGGL(k_lift_plain, dim3(cnt * k * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, stage, dst, ctx->dc, ctx->chunks, 1u);
+            HIPCHK(hipGetLastError()); launch_count(ctx);
+            CHECK(cn_run_ntt(ctx, dst, cnt * k, 0, k, 0));
+        }
+    }
+    std::vector<uint8_t> hnz(count);
+    HIPCHK(hipMemcpyAsync(hnz.data(), nz, count, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));                       // the one wait of the call: the zero flags
+    for (uint32_t e = 0; e < count; e++) O->pt_zero[oi + e] = !hnz[e];
+    return 0;
+API_END }
 extern "C" int cn_copy(cn_ctx *ctx, cn_handle src, uint32_t sfirst, cn_handle dst, uint32_t dfirst, uint32_t count) { API_BODY
     LOCK_ONLY;
     Buffer *s = ctx->bufs.find(src), *d = ctx->bufs.find(dst);

@@ -224,6 +224,7 @@ struct cn_ctx {
     uint64_t ks_dig_i32 = 0;   // key switches launched on int32 digit sums ("ks_digits_i32")
     int ptn_order = 0;         // k_mul_ptn_sum, workgroup order ("ptn_order", CN_PTN_ORDER): 0 limb-major, 1 limb = workgroup index mod k (a limb per XCD at k = 8)
     uint64_t ptn_sum = 0, ptn_bcast = 0;   // launches of k_mul_ptn_sum / of k_mul_plain_bcast on NTT-form plaintexts ("ptn_sum", "ptn_bcast")
+    uint64_t diag_scan = 0, diag_encode = 0;   // launches of k_diag_scan / of k_diag_gather ("diag_scan", "diag_encode")
     bool defer_square_gemm = false;  // cn_set_option "defer_square_gemm" (default 0: its effect on the literal call sequence has not been measured, profiles/deferred_square_gemm.md): queued squarings launched by a layer-boundary flush keep their relinearisation back; scalar products that read
                                // nothing else run as cn_square_gemm's second half - one key switch per dense OUTPUT (cn_defer.hip); false: every queued squaring relinearises at once.
                                // Set by name like "digit_mfma" (no environment override)
@@ -370,6 +371,13 @@ int cn_l_diag_set_attrs(uint32_t logn, size_t lds);
 int cn_l_mul_ptn_sum(cn_ctx *c, int policy, const MulPlainSumLaunch &a);
 bool cn_l_mul_ptn_sum_kernel(int policy, uint32_t logn);
 int cn_l_ptn_set_attrs(uint32_t logn, size_t lds);
+// a diagonal plan built on the device (cn_diag_scan, cn_diag_encode; cn_l_diagplan.hip, cn_k_diagplan.hip.h): S = the slot-order weight matrix [R][N] decoded from the row
+// plaintexts, of which rows below R and columns below dim are read.  A run = up to CN_DIAG_RUN terms (c, J, b0 + db) that are neighbours in the term list; `first` counts
+// from the `out` / `nz` of the launch.  The scan ORs into flags [2][N / 2], the gather into nz [terms] (bytes, zeroed by the caller) and writes every word of its terms
+struct DiagRunHost { uint32_t c, J, b0, len, first; };
+static const uint32_t CN_DIAG_RUN = 32, CN_DIAG_MAX_RUNS = 65535;
+int cn_l_diag_scan(cn_ctx *c, const uint64_t *S, uint32_t R, uint32_t dim, uint8_t *flags);
+int cn_l_diag_gather(cn_ctx *c, const uint64_t *S, uint32_t R, uint32_t dim, const DiagRunHost *runs, uint32_t nruns, const uint32_t *index_map, uint64_t *out, uint8_t *nz);
 // modulus switching (cn_l_modswitch.hip): `items` (ciphertext, poly) pairs [items][ks][N] -> [items][kd][N] on c's stream with the constants of the source context
 int cn_l_mod_switch(cn_ctx *c, const uint64_t *src, uint64_t *dst, const DevConsts *src_consts, uint32_t ks, uint32_t kd, uint32_t items, uint32_t logn,
                     bool f64, bool *ran_f64);

@@ -157,6 +157,34 @@ def pre_rotated_rows(W, n, terms):
     return out
 
 
+def plan_from_flags(nz, n, R, Dim, B=None):
+    """(DiagonalPlan, terms) from the non-zero flags of the generalized diagonals alone: nz bool [2, m], nz[c, i] = diag_(c,i) of the R x Dim matrix has a non-zero
+    (what `pre_rotated_rows(...).any(axis=1)` says of every structural candidate, or Context.diag_scan on the device).  The plan build_plan returns for a matrix with
+    those diagonals; terms = [(c, j B, b)] in term order - the rows pre_rotated_rows / Context.diag_encode make of them are the plan's plaintexts."""
+    m = n // 2
+    mask = structural_diagonals(R, Dim, n)
+    nz = np.asarray(nz, dtype=bool).reshape(2, m)
+    if B is None:
+        B = choose_baby_steps(mask)
+    if B < 1 or B & (B - 1) or m % B:
+        raise ValueError("B must be a power of two that divides %d" % m)
+    plan = DiagonalPlan(n, R, Dim, B)
+    keep = (nz & mask).reshape(2, m // B, B)
+    kept = [(int(j), int(c), int(b)) for (j, c, b) in np.argwhere(keep.transpose(1, 0, 2))]      # ascending (j, c, b): the terms of a group are neighbours
+    if not kept:
+        raise ValueError("the matrix is zero")
+    plan.babies = sorted({0} | {b for (_, _, b) in kept})
+    pos = {b: i for i, b in enumerate(plan.babies)}
+    for (j, c, b) in kept:
+        if not plan.groups or plan.groups[-1] != (j, c):
+            if plan.groups:
+                plan.grp_off.append(len(plan.ct_idx))
+            plan.groups.append((j, c))
+        plan.ct_idx.append(pos[b])
+    plan.grp_off.append(len(plan.ct_idx))
+    return plan, [(c, j * B, b) for (j, c, b) in kept]
+
+
 def build_plan(W, n, emit, B=None, chunk=256):
     """Plan the product with the integer matrix W (R x Dim residues mod t) on n slots.  All-zero diagonals are dropped; the slot values of the kept plaintexts, already
     rotated, are handed to emit(first_term, rows[count, n]) in term order, at most `chunk` candidates at a time (the caller encodes them and forgets them: at

@@ -81,6 +81,12 @@ DIAGONAL_DENSE = False
 # Same ciphertext words.  The arrays are k times the coefficient form (CIFAR: rows 5.4 GiB, diagonals 16 GiB per prime), so this is asked for, never a default;
 # a backend without pt_transform (the CPU oracle of the tests) keeps the coefficient form.
 NTT_WEIGHTS = False
+# DEVICE_DIAGONAL_PLAN = True: the pre-rotated diagonals of DiagonalDense are built where the weights lie (cn_diag_scan, cn_diag_encode): one scan of the row
+# plaintexts for the non-zero diagonals, the plan from those flags (diagonal.plan_from_flags), an array of exactly plan.terms plaintexts and ONE call that fills it -
+# instead of decode_batch to the host, numpy index arrays and encode_batch per chunk of 256 candidates.  The same plan and plaintext words, hence the same ciphertext
+# words.  False (default) until the two routes have been measured side by side (profiles/diag_device_plan.md); a backend without diag_scan (the CPU oracle of the
+# tests) keeps the host route.
+DEVICE_DIAGONAL_PLAN = False
 
 
 def _device_split_ok(env, encrypt):
@@ -1985,11 +1991,25 @@ class EncryptedSealBfvMatrix:
     def _diagonal_plan(self, i, env_i, B=None):
         """(plan, device array of its pre-rotated diagonal plaintexts) for prime i - built once per context (level), like _row_plaintexts: the weights are the
         integers the row plaintexts hold, rotated in slot space on the host and encoded in chunks.  Under NTT_WEIGHTS the array holds the diagonals in NTT form: each
-        chunk is encoded into a chunk-sized plaintext buffer and transformed into the array, so the resident footprint is k times the coefficient form, not k + 1"""
+        chunk is encoded into a chunk-sized plaintext buffer and transformed into the array, so the resident footprint is k times the coefficient form, not k + 1.
+        Under DEVICE_DIAGONAL_PLAN (and a context with diag_scan) nothing travels: the same plan from the flags of cn_diag_scan, the same words from cn_diag_encode"""
         from . import diagonal
         cache = self.__dict__.setdefault("_diagplan", {})
         ntt = NTT_WEIGHTS and hasattr(env_i.ctx, "pt_transform")
-        key = (i, env_i.ctx, B, ntt)
+        dev = DEVICE_DIAGONAL_PLAN and hasattr(env_i.ctx, "diag_scan")
+        key = (i, env_i.ctx, B, ntt, dev)
+        if key not in cache and dev:                                 # scan, plan, an array of exactly its terms, one call that fills it (DESIGN 6i)
+            ctx = env_i.ctx
+            R, dim = len(self.leVectors), int(self.leVectors[0].Dim)
+            rows = self._row_plaintexts(i, env_i)
+            plan, terms = diagonal.plan_from_flags(ctx.diag_scan(rows.h, rows.first, R, dim), ctx.n, R, dim, B=B)
+            pts = _Buf(ctx, "ptn" if ntt else "pt", plan.terms).view()
+            try:
+                ctx.diag_encode(rows.h, rows.first, R, dim, terms, pts.h, pts.first)
+            except BaseException:
+                pts.release()
+                raise
+            cache[key] = (plan, pts)
         if key not in cache:
             ctx = env_i.ctx
             R, dim = len(self.leVectors), int(self.leVectors[0].Dim)

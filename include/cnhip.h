@@ -225,6 +225,8 @@ int cn_set_option(cn_ctx *ctx, const char *name, int value);
  *   "mul_sum_min_k"            the smallest K for which cn_mul_relin_sum takes the one-key-switch form
  *   "digit_gemm_mfma"          digit GEMMs of cn_square_gemm launched in the matrix-core form ("digit_mfma"; counts up)
  *   "ks_digits_i32"            key switches launched on int32 digit sums ("digit_i32"; counts up)
+ *   "scratch_mib"              MiB of the context's scratch arena right now, rounded up (it grows to the largest call's need and stays)
+ *   "diag_scan", "diag_encode" launches of k_diag_scan / k_diag_gather (cn_diag_scan, cn_diag_encode; count up)
  *   "pool_arrays"              device arrays cached for reuse (the temporaries of a live graph are reserved out of them)
  *   "stream_tries"             streams cn_ctx_create tried until one had a hardware queue of its own (< 0: none had; CN_STREAM_PROBE=0 takes the first) */
 int cn_get_option(cn_ctx *ctx, const char *name, int *value);
@@ -455,6 +457,27 @@ int cn_ptn_alloc(cn_ctx *ctx, uint32_t count, cn_handle *out);
 int cn_pt_transform(cn_ctx *ctx, cn_handle pt, uint32_t pi, uint32_t count, cn_handle ptn, uint32_t oi);
 int cn_ptn_upload(cn_ctx *ctx, cn_handle h, uint32_t first, uint32_t count, const uint64_t *host);
 int cn_ptn_download(cn_ctx *ctx, cn_handle h, uint32_t first, uint32_t count, uint64_t *host);
+/* ---- the plaintexts of a generalized-diagonal dense layer, built where the weights lie (hewrapper.DEVICE_DIAGONAL_PLAN).  The reference encodes weight
+ * ROWS (LLDenseLayer.Prepare -> EncryptedSealBfvMatrix.cs:79-120) and has no diagonal form; a host that wants one would decode the rows, index them along the diagonals
+ * and encode again - 2 GiB of host traffic per plaintext prime at LoLa-CIFAR shapes.  These two calls read the matrix along its diagonals on the device.
+ * rows[ri .. ri + R) are coefficient-form plaintexts of this context; row r holds W[r, x] in slot x for x < dim (W is zero outside R x dim, whatever the slots at dim
+ * and above hold).  m = N / 2, slot s = h m + p.
+ * cn_diag_scan: nonzero[c m + i] = 1 iff the generalized diagonal diag_(c,i)[h, p] = W[h m + p, (h ^ c) m + (p + i) mod m] has a non-zero slot, else 0 - every
+ * non-zero W[h_r m + p_r, h_c m + x] sets flag (h_r ^ h_c, (x - p_r) mod m).  nonzero: N bytes of host memory.
+ * cn_diag_encode: out[oi + e] = BatchEncoder.Encode(pre_e), e < count, for terms[e] = (c, J, b):
+ *     pre_(c,J,b)[h, p] = W[(h ^ c) m + (p - J) mod m, h m + (p + b) mod m]
+ * - diagonal (c, J + b) rotated back by the giant step J, the plaintext a baby-step giant-step product multiplies with the input rotated by b.  `out` is a cn_pt_alloc
+ * array (the words of cn_encode_batch on those slot values) or a cn_ptn_alloc array (the words cn_pt_transform would then write; the staging in between is scratch of
+ * at most 256 plaintexts).  The zero flags of `out` are those of cn_encode_batch / cn_pt_transform: an all-zero term is legal and leaves a zero plaintext, which the
+ * products refuse with CN_ERR_ZERO.  Terms that are neighbours in the list with the same (c, J) and consecutive b - the order of a plan - are gathered 32 at a time
+ * from contiguous row segments; any other order gives the same words, more slowly.
+ * Both need batching (t == 1 mod 2N) and work on every ring size and on level contexts; an NTT-form `out` takes cn_pt_transform's path.  CN_ERR_ARG with a message that
+ * names the argument, and nothing written: R > N, dim = 0 or dim > N, c > 1, J >= m, b >= m, a range that leaves `rows` or `out`, `rows` not a coefficient-form
+ * plaintext handle, `out` the handle of `rows`, and under cn_graph_begin.  Queued calls ("defer") are submitted first.  Each call decodes the rows into scratch
+ * (2 R N words) and keeps nothing; each waits for the device once, at its end.  cn_get_option "diag_scan" / "diag_encode" count the launches of their kernels. */
+int cn_diag_scan(cn_ctx *ctx, cn_handle rows, uint32_t ri, uint32_t R, uint32_t dim, uint8_t *nonzero /* host, [2][N/2] */);
+int cn_diag_encode(cn_ctx *ctx, cn_handle rows, uint32_t ri, uint32_t R, uint32_t dim, const uint32_t *terms /* host, [count][3] = c, J, b */, uint32_t count,
+                   cn_handle out, uint32_t oi);
 
 /* ---- client side on the device (what SEAL's KeyGenerator / Encryptor / Decryptor do for
  * AtomicSealBfvEncryptedEnvironment.SetKeys / Encrypt / Decrypt, AtomicSealBfvVector.cs:62-74,1030-1110,1202-1232), for data

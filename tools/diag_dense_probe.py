@@ -17,6 +17,12 @@ process, timed in alternating rounds on the same input ciphertext after one unti
 slots compared across the two forms and with W v mod t.  --rowdot adds RowsDotProduct (cn_rowdot_batch over all rows, no masks) with the flag off and on.
 
     python tools/diag_dense_probe.py --ntt-weights [--rowdot] [--shapes tiny,cifar,large] [--primes 1] [--rounds 5] [--out profiles/ntt_weights.md]
+
+--device-plan: the plan itself built on the host route and on the device route (hewrapper.DEVICE_DIAGONAL_PLAN: cn_diag_scan, cn_diag_encode), alternating
+in one process with 1 .. --primes plaintext primes, in coefficient form and in NTT form: "plan built in" of both, equality of every plaintext word of the two arrays,
+the layer on either plan, resident bytes, the scratch arena.
+
+    python tools/diag_dense_probe.py --device-plan [--shapes tiny,cifar,large] [--primes 2] [--rounds 3] [--out profiles/diag_device_plan.md]
 """
 import argparse
 import os
@@ -247,6 +253,103 @@ def probe_ntt(name, nprimes, rounds, rowdot, say):
     return ok
 
 
+def probe_device_plan(name, nprimes, rounds, say):
+    """the plan of the diagonal path built on the host route (decode_batch, numpy, encode_batch per chunk: hewrapper.DEVICE_DIAGONAL_PLAN = False) and on the device
+    route (cn_diag_scan, diagonal.plan_from_flags, one cn_diag_encode), alternating in one process, for the coefficient form and the NTT form"""
+    s = SHAPES[name]
+    parms = dict(s["parms"])
+    parms["primes"] = tuple(parms["primes"])[:nprimes]
+    R, Dim = s["R"], s["Dim"]
+    rng = np.random.default_rng(11)
+    W = rng.integers(-s["wmax"], s["wmax"] + 1, size=(R, Dim)).astype(float)
+    W[:, 0] = np.where(W.any(axis=1), W[:, 0], 1)
+    v = rng.integers(-s["vmax"], s["vmax"] + 1, size=Dim).astype(float)
+    F = EncryptedSealBfvFactory(**parms)
+    env = F.AllocateComputationEnv()
+    ctx0 = env.Environments[0].ctx
+    k, n = len(ctx0.q), ctx0.n
+    mat = F.GetPlainMatrix(W, EMatrixFormat.RowMajor, 1.0)
+    vec = F.GetEncryptedVector(v, EVectorFormat.dense, 1.0)
+    say("### %s: %d x %d, N = %d, k = %d, %d plaintext prime(s) %s" % (name, R, Dim, n, k, len(parms["primes"]), list(parms["primes"])))
+    say("")
+    hewrapper.DIAGONAL_DENSE = True
+    for i, e in enumerate(env.Environments):
+        mat._row_plaintexts(i, e)                                    # (the rows both routes read are resident: only the plan itself is timed)
+
+    def drop():
+        for (_, pts) in mat.__dict__.pop("_diagplan", {}).values():
+            pts.release()
+
+    def build(dev):
+        hewrapper.DEVICE_DIAGONAL_PLAN = dev
+        sync(env)
+        t0 = time.perf_counter()
+        got = [mat._diagonal_plan(i, e) for i, e in enumerate(env.Environments)]
+        sync(env)
+        return time.perf_counter() - t0, got
+
+    def same_words(ctx, a, b, count, ntt):
+        item = (k if ntt else 1) * n * 8
+        step = max(1, (256 << 20) // item)
+        down = ctx.ptn_download if ntt else ctx.pt_download
+        return all(np.array_equal(down(a.h, a.first + c, min(step, count - c)), down(b.h, b.first + c, min(step, count - c))) for c in range(0, count, step))
+    ok = True
+    say("| plan form | plan built in, s, host route (all primes; %d alternating builds) | device route | ratio of the medians | every plaintext word equal | layer on the host-built / device-built plan, ms (median of %d) "
+        "| resident plan plaintexts per prime, MiB, host / device route | scratch arena per context after the device build, MiB |" % (rounds, rounds))
+    say("|---|---|---|---|---|---|---|---|")
+    for ntt in (False, True):
+        hewrapper.NTT_WEIGHTS = ntt
+        for dev in (False, True):                                    # one untimed build of each
+            build(dev)
+            drop()
+        secs = {False: [], True: []}
+        for r in range(rounds):
+            plans = {}
+            for dev in (False, True):
+                dt, plans[dev] = build(dev)
+                secs[dev].append(dt)
+            if r + 1 < rounds:
+                drop()
+        equal = all(hp.terms == dp.terms and hp.grp_off == dp.grp_off and hp.ct_idx == dp.ct_idx and hp.babies == dp.babies and hp.groups == dp.groups
+                    and same_words(e.ctx, hb, db, hp.terms, ntt) for (hp, hb), (dp, db), e in zip(plans[False], plans[True], env.Environments))
+        ms, outs = {False: [], True: []}, {}
+        for dev in (False, True):
+            hewrapper.DEVICE_DIAGONAL_PLAN = dev
+            mat.DiagonalDense(vec, env).Dispose()                    # untimed
+        for _ in range(rounds):
+            for dev in (False, True):
+                hewrapper.DEVICE_DIAGONAL_PLAN = dev
+                if dev in outs:
+                    outs[dev].Dispose()
+                sync(env)
+                t0 = time.perf_counter()
+                outs[dev] = mat.DiagonalDense(vec, env)
+                sync(env)
+                ms[dev].append((time.perf_counter() - t0) * 1e3)
+        words = all(np.array_equal(e.ctx.ct_download(x.encData.h, x.encData.first, 1), e.ctx.ct_download(y.encData.h, y.encData.first, 1))
+                    for x, y, e in zip(outs[False].eVectors, outs[True].eVectors, env.Environments))
+        item = (k if ntt else 1) * n * 8 / 2 ** 20
+        say("| %s | %s (median %.2f) | %s (median %.3f) | %.0f | %s | %.2f / %.2f (ciphertext words equal: %s) | %.1f / %.1f | %.1f |"
+            % ("NTT" if ntt else "coefficient", ", ".join("%.2f" % x for x in secs[False]), statistics.median(secs[False]), ", ".join("%.3f" % x for x in secs[True]),
+               statistics.median(secs[True]), statistics.median(secs[False]) / statistics.median(secs[True]), equal, statistics.median(ms[False]), statistics.median(ms[True]), words,
+               plans[False][0][1].buf.count * item, plans[True][0][1].buf.count * item, ctx0.get_option("scratch_mib")))
+        ok = ok and equal and words
+        for x in outs.values():
+            x.Dispose()
+        drop()
+    p = plans[True][0][0]
+    say("")
+    say("%d diagonals kept of %d structural candidates, B = %d, %d groups; `k_diag_scan` / `k_diag_gather` launches per context: %d / %d."
+        % (p.terms, int(diagonal.structural_diagonals(R, Dim, n).sum()), p.B, len(p.groups), ctx0.get_option("diag_scan"), ctx0.get_option("diag_encode")))
+    say("")
+    hewrapper.DIAGONAL_DENSE = hewrapper.NTT_WEIGHTS = hewrapper.DEVICE_DIAGONAL_PLAN = False
+    vec.Dispose()
+    mat.Dispose()
+    for e in env.Environments:
+        e.ctx.close()
+    return ok
+
+
 def mulmod(a, b, p):
     b = np.asarray(b, dtype=np.uint64)
     hi = (a * (b >> np.uint64(20))) % p
@@ -321,21 +424,33 @@ def network(say):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="tiny,cifar,large")
-    ap.add_argument("--primes", type=int, default=1, help="plaintext primes of the N = 16384 shapes (the tiny shape always takes its two)")
+    ap.add_argument("--primes", type=int, default=None, help="plaintext primes of the N = 16384 shapes, default 1 (the tiny shape always takes its two); --device-plan: 1 .. primes, default 2")
     ap.add_argument("--rounds", type=int, default=None, help="timed rounds (default 3; 5 with --ntt-weights)")
     ap.add_argument("--ntt-weights", action="store_true", help="coefficient-form plan against NTT-form plan of the diagonal path, alternating rounds")
     ap.add_argument("--rowdot", action="store_true", help="with --ntt-weights: RowsDotProduct with the flag off and on as well")
+    ap.add_argument("--device-plan", action="store_true", help="the plan built on the host route against the device route (hewrapper.DEVICE_DIAGONAL_PLAN), with 1 .. --primes primes")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    a.primes = a.primes or (2 if a.device_plan else 1)
     a.rounds = a.rounds or (5 if a.ntt_weights else 3)
-    a.out = a.out or os.path.join(ROOT, "profiles", "ntt_weights.md" if a.ntt_weights else "diag_dense.md")
+    a.out = a.out or os.path.join(ROOT, "profiles", "diag_device_plan.md" if a.device_plan else ("ntt_weights.md" if a.ntt_weights else "diag_dense.md"))
     lines = []
 
     def say(x):
         print(x, flush=True)
         lines.append(x)
     ok = True
-    if a.ntt_weights:
+    if a.device_plan:
+        say("# Diagonal plans built on the device: `tools/diag_dense_probe.py --device-plan`")
+        say("")
+        say("One MI355X, one process; the plan of the diagonal path (`_diagonal_plan`: every plaintext prime, rows resident) built on the host route - the parent's code, unchanged -")
+        say("and on the device route (`hewrapper.DEVICE_DIAGONAL_PLAN`), alternating after one untimed build of each, wall clock around the builds and a host wait on every context,")
+        say("clocks as found.  Synthetic integer weights (every structural diagonal holds a non-zero).")
+        say("")
+        for name in a.shapes.split(","):
+            for np_ in ([2] if name == "tiny" else range(1, a.primes + 1)):
+                ok = probe_device_plan(name, np_, a.rounds, say) and ok
+    elif a.ntt_weights:
         say("# NTT-form weight plaintexts: `tools/diag_dense_probe.py --ntt-weights`, %d plaintext prime(s) at N = 16384" % a.primes)
         say("")
         say("One MI355X, one process, one image; the diagonal path with its plan in coefficient form and in NTT form (`hewrapper.NTT_WEIGHTS`), both resident, alternating")
