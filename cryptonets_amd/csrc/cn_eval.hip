@@ -78,7 +78,7 @@ int mul_plain_fused(cn_ctx *ctx, CtSpan A, bool a_bcast, PtSpan P, CtSpan O, uin
         rr_ops[pol]->mul_plain_bcast(ctx, P.d, pstride, ctn, o, count, polys, nx ? (uint32_t)nx->elt : 0u, nx ? nx->out : nullptr, P.ntt);
         HIPCHK(hipGetLastError()); launch_count(ctx);
         if (P.ntt) ctx->ptn_bcast++;                               // (NTT-form rows: no transform of the plaintexts ran)
-        if (!P.ntt) ctx->st.ntt_forward_limbs += (uint64_t)polys * k + (uint64_t)count * polys * k;      // (NTT-form rows: the polys k limbs cn_run_ntt counted are all that ran)
+        if (!P.ntt) ctx->st.ntt_forward_limbs += (uint64_t)count * polys * k;      // the rows, beside the polys k limbs cn_run_ntt counted (NTT-form rows: those are all that ran)
         ctx->st.ntt_inverse_limbs += (uint64_t)count * polys * k;
         ctx->st.PlainMultiplication += count;
         return 0;
@@ -1287,7 +1287,7 @@ extern "C" int cn_mul_plain_sum(cn_ctx *ctx, cn_handle ct, uint32_t ci, cn_handl
     if (ptn) CHECK(cn_l_mul_ptn_sum(ctx, pol, MulPlainSumLaunch{P->d + (size_t)pi * P->item_words, ctn, dgo, dslot, O->d + (size_t)oi * O->item_words, G,
                                                                 pol == POL_U64 ? 0xffffffffu : cn_ptn_sum_interval(qr.qmax)}));
     else CHECK(cn_l_mul_plain_sum(ctx, pol, MulPlainSumLaunch{P->d + (size_t)pi * n, ctn, dgo, dslot, O->d + (size_t)oi * O->item_words, G, accmax}));
-    if (!ptn) ctx->st.ntt_forward_limbs += (uint64_t)D * 2 * k + (uint64_t)E * 2 * k;      // (NTT-form plaintexts: the D 2k limbs cn_run_ntt counted are all that ran)
+    if (!ptn) ctx->st.ntt_forward_limbs += (uint64_t)E * 2 * k;      // the plaintexts, beside the D 2k limbs cn_run_ntt counted (NTT-form plaintexts: those are all that ran)
     ctx->st.ntt_inverse_limbs += (uint64_t)G * 2 * k;
     ctx->st.PlainMultiplication += E; ctx->st.AddMany += G; ctx->st.AddManyItemCount += E;
     return 0;

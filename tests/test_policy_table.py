@@ -12,13 +12,14 @@ import pytest
 
 from conftest import PARAMS
 from oracle.cno import COEFF_MODULUS_128
+from size_policy_sets import CELLS, NAME, SETS as SIZE_POLICY_SETS      # one set per (policy, ring size) of tests/test_gpu_size_policy_matrix.py
 from test_gpu_wide_moduli import SETS                       # the wide-modulus sets and ring sizes (a prime search at import, no device)
 from test_oracle_math import is_prime
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "cryptonets_amd", "csrc")
-ALL_SETS = dict(PARAMS, **SETS)
-assert len(ALL_SETS) == len(PARAMS) + len(SETS)
+ALL_SETS = dict(PARAMS, **SETS, **SIZE_POLICY_SETS)
+assert len(ALL_SETS) == len(PARAMS) + len(SETS) + len(SIZE_POLICY_SETS) and len(SIZE_POLICY_SETS) == 15
 
 
 def build(extra=()):
@@ -126,6 +127,23 @@ def test_anchors(tables):
         assert q(name) == "U64"
     assert policy(tables, "MIX2048", 0, 2) == "F64L" and policy(tables, "MIX2048", 0, 3) == "U64"
     assert tables["c3"][1][(1, 0, 0)][:4] == (1, 1, 0, 0)                                        # the empty range: bits 0, no clz of 0
+
+
+def test_size_policy_cells_take_the_policy_they_are_named_for(tables):
+    """the 15 cells of the size x policy matrix: the q range, its two-limb prefix (the level context) and every single limb take the named policy; the BEHZ
+    auxiliary base has k + 1 primes, 61-bit ones (U64) beside the 60-bit set and 49-bit ones (F64) beside the other two"""
+    want = {"u64": ("U64", "U64"), "f64": ("F64", "F64"), "f64l": ("F64L", "F64")}
+    for pol, n in CELLS:
+        name = NAME(pol, n)
+        hdr = tables[name][0]
+        assert (hdr["n"], hdr["k"], hdr["kb"], hdr["batching"]) == (n, 3, 4, 1), name
+        assert (policy(tables, name, 0, 3), policy(tables, name, 3, 4)) == want[pol], name
+        assert policy(tables, name, 0, 2) == want[pol][0], name
+        assert all(row[4] == "U64" for key, row in tables[name][1].items() if key[0] == 0), name
+    for n in (1024, 16384):
+        assert [policy(tables, NAME("u64", n), j, 1) for j in range(3)] == ["U64"] * 3
+        assert [policy(tables, NAME("f64", n), j, 1) for j in range(3)] == ["F64"] * 3
+        assert [policy(tables, NAME("f64l", n), j, 1) for j in range(3)] == ["F64L"] * 3
 
 
 def test_policy_header_is_clean_under_the_sanitizers(tables):
