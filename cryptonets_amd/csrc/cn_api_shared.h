@@ -1,9 +1,11 @@
 // Shared internals of the translation units the host runtime of libcnhip.so is built from (round 6: cn_api.hip was one 3 200-line unit):
 //   cn_api.hip     contexts, streams, options, buffers, graphs, uploads / downloads, encoder, raw transforms, timing, statistics
-//   cn_eval.hip    the evaluator: linear operations, scalar GEMM planning, BEHZ multiply, key switching, rotations
+//   cn_eval.hip    the evaluator: linear operations, scalar GEMM plans and their launches, BEHZ multiply, key switching, rotations
 //   cn_client.hip  the data owner's side on the device: keys, sampler, keygen, encrypt, decrypt, noise
 //   cn_defer.hip   deferred submission of per-ciphertext calls (queue, hazards, flush) and the consumer side of the lock-free submission ring
 //   cn_multi.hip   the key broadcast between contexts (RCCL)
+// How a scalar GEMM is planned - weight class, kernel form, pairing and grouping of gather lists, weight tiles, the device image - is decided in cn_gemm_plan.h
+// (host-only; included by the two units that plan: cn_eval.hip, and cn_defer.hip for the flush of queued scalar products).
 // Which arithmetic policy a modulus range takes and which ring sizes have the register-radix kernels is decided in cn_policy.h (cn_mod_range, cn_policy, cn_rr_size).
 // Everything here is internal: the C ABI is include/cnhip.h.  The element-wise kernels (cn_k_elem.hip.h) have internal linkage - every unit that launches one
 // carries its own copy.
@@ -22,7 +24,7 @@
 #include <cstring>
 
 #define fail cn_fail
-struct DOp; struct DeferQueue; struct GemmPlan; struct GemmArith; struct Tab2; struct RotJob; struct BcastNext; struct Slab;
+struct DOp; struct DeferQueue; struct GemmPlan; struct GemmSwitches; struct Tab2; struct RotJob; struct BcastNext; struct Slab;
 
 static const RrOps *const rr_ops[3] = {&cn_rr_u64, &cn_rr_f64, &cn_rr_f64l};
 static const KsOps *const ks_ops[3] = {&cn_ks_u64, &cn_ks_f64, &cn_ks_f64l};
@@ -96,23 +98,16 @@ struct GaloisCall {
 // A row-dot batch whose SumAllSlots chain follows: the product kernel leaves sigma_elt(c1) of every product in `out` ([row][k][N], the chain's first scratch array) and takes
 // its transformed ciphertext from `ctn` - both inside the scratch arena the caller has sized for the whole call (no ensure_scratch in between: the arena must not move)
 struct BcastNext { uint64_t elt; uint64_t *out, *ctn; };
-struct GemmArith { bool small, two; uint32_t lazy; int bits; };
 // A scalar GEMM is planned once per (gather table, weight matrix): validation, grouping of the outputs that share a gather list,
 // weight tiles in the kernel's layout.  A plan can live in HBM (cn_gemm_plan_create: the weights of a layer are uploaded once, every
 // inference only launches) or in the per-call scratch (cn_scalar_gemm).
-struct GemmPlan {
-    uint32_t O = 0, K = 0, Kp = 0, G = 0, M = 0, MT = 0, lazy = 0, max_in = 0;
-    bool small = false, two = false, one = false, has_bias = false, mfma = false;
-    uint32_t P = 0, mtiles = 0, ksteps = 0;  // matrix-core form: weight digit planes, 32-row output tiles, 32-term steps
+struct GemmPlan : GemmLayout {               // the layout of its image (cn_policy.h), filled by gemm_plan_indices (cn_gemm_plan.h)
+    uint32_t O = 0, max_in = 0;
+    bool has_bias = false;
     cn_handle bias_pt = 0; uint32_t bias_count = 0;
     uint64_t nnz = 0;                        // non-zero, non-padded terms (statistics)
-    std::vector<char> host;                  // [idx | out_idx | bias_idx | weights], each 256 B aligned
-    size_t off_oidx = 0, off_bidx = 0, off_w = 0;
+    std::vector<char> host;                  // the image until it is uploaded
     char *dev = nullptr;                     // persistent plans: device copy of `host`
-    // cn_square_gemm: the layer may run on the digits of the unrelinearized products (square_gemm_plan_ok) - signed weights [G][mtiles][dKw][dMT] at off_dw
-    // dig_mfma: the digit GEMM runs on the matrix cores from the fragments at off_w (no table at off_dw)
-    // dig_i32: every digit sum fits a signed 32-bit word (cn_digit_sum_fits_i32 of the largest row, "digit_i32" on): S is stored and read as int32 words
-    bool dig = false, dig_mfma = false, dig_i32 = false; uint32_t dMT = 0, dKw = 0; size_t off_dw = 0;
 };
 // ---- deferred squarings that feed the next dense layer (cn_set_option "defer_square_gemm", cn_defer.hip).  A layer-boundary flush runs only the Multiply half of the
 // squarings it launches: the size-3 products stay in `arr` ([slot][3][k][N], owned by the context, grown on demand and never while a graph is alive), the callers'
@@ -178,17 +173,13 @@ int add_plain_body(cn_ctx *ctx, cn_handle a, uint32_t ai, cn_handle pt, uint32_t
 bool shifted_overlap(const uint64_t *a, const uint64_t *o, size_t words);
 bool mul_plain_takes_bcast(cn_ctx *ctx, uint32_t count);
 int mul_plain_impl(cn_ctx *ctx, CtSpan A, bool a_bcast, PtSpan P, CtSpan O, uint32_t polys, const BcastNext *nx = nullptr);
-uint64_t lift_scalar(const DevConsts &hc, uint64_t w, uint32_t j);
-bool gemm_weights_small(cn_ctx *ctx, const uint64_t *W, size_t count);
-GemmArith gemm_arith(cn_ctx *ctx, bool weights_small);
-bool gemm_mfma_ok(cn_ctx *ctx, const GemmArith &ar, uint32_t M, uint32_t K);
-uint32_t gemm_weight_planes(cn_ctx *ctx, const uint64_t *W, size_t count);
+GemmSwitches gemm_switches(const cn_ctx *ctx);           // (cn_gemm_plan.h)
 int free_gemm_plan(cn_ctx *ctx, Buffer &b);
-bool pair_gather_lists(uint32_t O, uint32_t &K, std::vector<int32_t> &gidx, const uint64_t *W, std::vector<uint64_t> &W2);
 int build_gemm_plan(cn_ctx *ctx, const int32_t *idx, const uint64_t *W, uint32_t O, uint32_t K, Buffer *BP, cn_handle bias_pt, const int32_t *bias_idx, GemmPlan &P);
 int run_gemm_plan(cn_ctx *ctx, const GemmPlan &P, const char *tables, Buffer *I, Buffer *OB, uint32_t oi, const uint64_t *in3 = nullptr);
-int launch_gemm_plan(cn_ctx *ctx, const GemmPlan &P, const char *tables, const void *idx, const uint64_t *in, uint32_t in_unit, uint32_t polys, const uint64_t *bias, const void *bidx,
-                     uint32_t bias_unit, uint64_t *out, uint32_t obase);
+// the launch of a planned layout whose image is at `tables` (operands by name: GemmLaunch, cn_runtime.h) and the kernel family it goes to
+inline GemmLaunch gemm_launch(const cn_ctx *ctx, const GemmLayout &L, const char *tables) { return GemmLaunch::of(L, tables, (uint32_t)ctx->opt.gemm_order); }
+inline int run_gemm_launch(cn_ctx *ctx, const GemmLayout &L, const GemmLaunch &gl) { return L.mfma ? cn_l_gemm_mfma(ctx, gl) : cn_l_gemm(ctx, gl); }
 bool square_gemm_ctx_ok(cn_ctx *ctx);
 bool square_gemm_fused_ok(cn_ctx *ctx, const GemmPlan &P);
 bool run_intt_tensor(cn_ctx *c, const uint64_t *A, const uint64_t *B, uint64_t *D, uint32_t cnt, uint32_t base_off, uint32_t Lm, bool lazy);
@@ -385,75 +376,4 @@ template <class K> static int big_lds(K kern, size_t bytes) {
 template <int EPT> static int set_ks_attr(size_t bytes) {
     HIPCHK(hipFuncSetAttribute((const void *)k_keyswitch<EPT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
     return 0;
-}
-
-// HOT LOOP A
-// weight tiles of a planned GEMM in kernel layout; row(g, m): the K weights (residues mod t) of member m of group g, or null
-// tap_ok(g, kk): term kk of group g gathers a ciphertext; a padded tap gets the weight 0 whatever the caller passed (k_scalar_gemm_f64 multiplies a valid word
-// by it instead of selecting per lane)
-template <class ROW, class TAP> static void pack_gemm_weights(cn_ctx *ctx, uint32_t G, uint32_t M, uint32_t K, bool small, ROW row, TAP tap_ok, uint32_t &MT, std::vector<char> &wbytes) {
-    const uint32_t k = ctx->hc.k; const uint64_t t = ctx->hc.t.q;
-    if (small) {
-        const uint32_t MTf = M >= 16 ? 20 : (M >= 8 ? 10 : (M >= 3 ? 5 : 1)), mtf = (M + MTf - 1) / MTf;
-        const uint32_t Kw = gemm_f64_rows(K);
-        std::vector<double> hWd((size_t)G * mtf * Kw * MTf, 0.0);           // [g][mtile][kk < Kw][m], zero padded (gemm_f64_rows)
-        for (uint32_t g = 0; g < G; g++) for (uint32_t m = 0; m < M; m++) {
-            const uint64_t *wr = row(g, m);
-            if (!wr) continue;
-            double *dst = &hWd[(((size_t)g * mtf + m / MTf) * Kw) * MTf + m % MTf];
-            for (uint32_t kk = 0; kk < K; kk++) { uint64_t w = tap_ok(g, kk) ? wr[kk] : 0; dst[(size_t)kk * MTf] = w >= ctx->hc.t_half ? -(double)(t - w) : (double)w; }
-        }
-        MT = MTf;
-        wbytes.assign((const char *)hWd.data(), (const char *)(hWd.data() + hWd.size()));
-    } else {
-        const uint32_t MTi = M >= 8 ? 10 : (M >= 3 ? 5 : 1), mti = (M + MTi - 1) / MTi;
-        std::vector<uint64_t> hW((size_t)k * G * mti * K * MTi, 0);         // [j][g][mtile][kk][m], zero padded
-        for (uint32_t j = 0; j < k; j++) for (uint32_t g = 0; g < G; g++) for (uint32_t m = 0; m < M; m++) {
-            const uint64_t *wr = row(g, m);
-            if (!wr) continue;
-            uint64_t *dst = &hW[((((size_t)j * G + g) * mti + m / MTi) * K) * MTi + m % MTi];
-            for (uint32_t kk = 0; kk < K; kk++) { uint64_t w = tap_ok(g, kk) ? wr[kk] : 0; dst[(size_t)kk * MTi] = w ? lift_scalar(ctx->hc, w, j) : 0; }
-        }
-        MT = MTi;
-        wbytes.assign((const char *)hW.data(), (const char *)(hW.data() + hW.size()));
-    }
-}
-
-// One-limb form of the small-weight kernel: sum_k w_k x_k with x_k < q_max is an exact double as long as (sum_k |w_k| + 1) q_max <= 2^53 for every output row
-// (all partial sums are integers below 2^53; the + 1 leaves room for the recentred carry of the fold) - the words are then not split into limbs at all: ONE FMA
-// per MAC instead of two, no masks and shifts, one recentring per output.  True for the CryptoNets convolution (row sums <= 373 with the trained weights,
-// 44-bit moduli); the dense layers have larger row sums and keep the two-limb form (or the matrix cores).  Needs the whole term list in one block (K <= lazy).
-template <class ROW, class TAP> static bool gemm_one_limb(cn_ctx *ctx, const GemmArith &ar, uint32_t G, uint32_t M, uint32_t K, ROW row, TAP tap_ok) {
-    static const bool on = !(getenv("CN_GEMM_ONE_LIMB") && !atoi(getenv("CN_GEMM_ONE_LIMB")));
-    if (!on || !ar.small || ar.bits > 49 || K > ar.lazy) return false;
-    const uint64_t room = (1ull << 53) / cn_mod_range(ctx->hc, 0, ctx->hc.k).qmax;   // sum |w| + 1 <= room
-    const uint64_t t = ctx->hc.t.q;
-    for (uint32_t g = 0; g < G; g++) for (uint32_t m = 0; m < M; m++) {
-        const uint64_t *wr = row(g, m);
-        if (!wr) continue;
-        uint64_t sum = 1;
-        for (uint32_t kk = 0; kk < K; kk++) if (tap_ok(g, kk)) { const uint64_t w = wr[kk]; sum += w >= ctx->hc.t_half ? t - w : w; if (sum > room) return false; }
-    }
-    return true;
-}
-// fragments [g][p][mtile][kstep][lane][16]: lane l, byte t = digit p of the weight of output row 32 mtile + (l & 31) for term
-// 32 kstep + 16 (l >> 5) + t; zero for padded rows / terms / taps.  row(g, m): residues mod t of member m, or null; tap_ok(g, kk).
-template <class ROW, class TAP> static void pack_gemm_mfma(cn_ctx *ctx, uint32_t G, uint32_t M, uint32_t K, uint32_t P, ROW row, TAP tap_ok, std::vector<char> &wbytes) {
-    const uint32_t mtiles = (M + 31) / 32, ksteps = (K + 31) / 32;
-    const uint64_t t = ctx->hc.t.q;
-    wbytes.assign((size_t)G * P * mtiles * ksteps * 1024, 0);
-    for (uint32_t g = 0; g < G; g++) for (uint32_t m = 0; m < M; m++) {
-        const uint64_t *wr = row(g, m);
-        if (!wr) continue;
-        const uint32_t mt = m / 32, r = m % 32;
-        for (uint32_t kk = 0; kk < K; kk++) {
-            const uint64_t w = wr[kk];
-            if (!w || !tap_ok(g, kk)) continue;
-            const int64_t sw = w >= ctx->hc.t_half ? -(int64_t)(t - w) : (int64_t)w;
-            const uint32_t rec = ((uint32_t)(sw + 0x808080) ^ 0x808080u);          // byte p = signed digit p
-            const uint32_t ks = kk / 32, half = (kk % 32) / 16, tt = kk % 16;
-            for (uint32_t p = 0; p < P; p++)
-                wbytes[((((size_t)g * P + p) * mtiles + mt) * ksteps + ks) * 1024 + (size_t)(half * 32 + r) * 16 + tt] = (char)(uint8_t)(rec >> (8 * p));
-        }
-    }
 }

@@ -1,6 +1,7 @@
 // libcnhip.so host runtime (4/5): deferred submission of per-ciphertext calls (queue, hazard levels, flush as batched launches) and the consumer side of the
 // lock-free submission ring (cn_submit.h).
 #include "cn_api_shared.h"
+#include "cn_gemm_plan.h"
 
 
 // ---------------------------------------------------------------- deferred submission of per-ciphertext calls
@@ -102,100 +103,23 @@ __global__ void k_add_plain_tab(const Tab3 *__restrict__ tab, const DevConsts *_
 // all queued DenseMatrixBySparseVectorMultiply calls of one level with K terms each: ONE scalar GEMM over address tables
 int flush_gemm_group(cn_ctx *ctx, DeferQueue *q, const std::vector<const DOp *> &ops, uint32_t K) {
     const uint32_t O = (uint32_t)ops.size();
-    bool wsmall = true;
-    for (const DOp *op : ops) wsmall = wsmall && gemm_weights_small(ctx, &q->wt[op->terms], K);
-    const GemmArith ar = gemm_arith(ctx, wsmall);
     // the calls' lists, contiguous: A[o][kk] = address of term kk of output o (0 = padded tap), Wt[o][kk] its weight
-    std::vector<uint64_t> A((size_t)O * K), Wt((size_t)O * K);
+    std::vector<uint64_t> A((size_t)O * K), Wt((size_t)O * K), out(O), bias(O);
     for (uint32_t o = 0; o < O; o++) {
         memcpy(&A[(size_t)o * K], &q->addr[ops[o]->terms], (size_t)K * 8);
         memcpy(&Wt[(size_t)o * K], &q->wt[ops[o]->terms], (size_t)K * 8);
+        out[o] = (uint64_t)ops[o]->out; bias[o] = (uint64_t)ops[o]->bias;
     }
     // (the gather lists are not paired here as cn_gemm_plan_create pairs them: end to end neutral, the pairing's host time at the head of a batch - profiles/r06_defer_pair_ab.txt)
-    // group the outputs that gather the same inputs (PoolLayer: every map of one corner shares its patch; a dense layer: one group)
-    std::map<std::vector<uint64_t>, std::vector<uint32_t>> groups;
-    for (uint32_t o = 0; o < O; o++) groups[std::vector<uint64_t>(A.begin() + (size_t)o * K, A.begin() + (size_t)(o + 1) * K)].push_back(o);
-    const uint32_t G = (uint32_t)groups.size();
-    uint32_t M = 0;
-    for (auto &g : groups) M = std::max<uint32_t>(M, (uint32_t)g.second.size());
-    const bool mfma = gemm_mfma_ok(ctx, ar, M, K);
-    const uint32_t Kp = mfma ? ((K + 31) / 32) * 32 : ((K + 15) & ~15u) + 16;       // gather rows: 16 spare entries (the VALU kernels request up to 2 x 8 terms ahead)
-    const uint32_t NONE = 0xffffffffu;
-    std::vector<uint64_t> hidx((size_t)G * Kp, 0), hoidx((size_t)G * M, 0), hbidx((size_t)G * M, 0);
-    std::vector<uint32_t> member((size_t)G * M, NONE);
-    bool any_bias = false, all_bias = true;
-    const uint64_t *fallback = nullptr;
-    {
-        uint32_t g = 0;
-        for (auto &kv : groups) {
-            memcpy(&hidx[(size_t)g * Kp], kv.first.data(), (size_t)K * 8);
-            for (uint32_t m = 0; m < kv.second.size(); m++) {
-                const DOp *op = ops[kv.second[m]];
-                member[(size_t)g * M + m] = kv.second[m]; hoidx[(size_t)g * M + m] = (uint64_t)op->out; hbidx[(size_t)g * M + m] = (uint64_t)op->bias;
-                any_bias = any_bias || op->bias; all_bias = all_bias && op->bias;
-            }
-            for (uint64_t a : kv.first) if (a && !fallback) fallback = (const uint64_t *)a;
-            g++;
-        }
-    }
-    const bool small = ar.small, two = ar.two; const uint32_t lazy = ar.lazy; uint32_t MT = 1, WP = 0;
-    bool one = false;
-    std::vector<char> wbytes;
-    auto row = [&](uint32_t g, uint32_t m) -> const uint64_t * { const uint32_t o = member[(size_t)g * M + m]; return o == NONE ? nullptr : &Wt[(size_t)o * K]; };
-    if (mfma) {
-        WP = gemm_weight_planes(ctx, Wt.data(), Wt.size());
-        pack_gemm_mfma(ctx, G, M, K, WP, row, [&](uint32_t g, uint32_t kk) { return hidx[(size_t)g * Kp + kk] != 0; }, wbytes);
-    } else {
-        auto tap = [&](uint32_t g, uint32_t kk) { return hidx[(size_t)g * Kp + kk] != 0; };
-        pack_gemm_weights(ctx, G, M, K, small, row, tap, MT, wbytes);
-        one = gemm_one_limb(ctx, ar, G, M, K, row, tap);
-    }
-    // Index tables instead of address tables (round 6).  Every array the library hands out starts on a 256-byte boundary, so the operands of a flush group are 32-bit offsets in units
-    // of 32 words from the lowest address among them - the INDEX-table kernels of a plan (one 16-byte scalar load per four gather entries, offsets multiplied on the scalar unit)
-    // instead of the address-table variants (two loads per four, a 64-bit select per term): dense layer 242 -> 221 us alone on the device, convolution 506 -> 492
-    // (310 with the gather lists paired, profiles/r06_defer_pair_ab.txt); end to end neutral.  Needs a bias on every output or on none; CN_DEFER_REL=0 keeps the address tables (A/B).
-    static const bool rel_on = !(getenv("CN_DEFER_REL") && !atoi(getenv("CN_DEFER_REL")));
-    uint64_t ibase = ~0ull, obase_a = ~0ull, bbase = ~0ull;
-    bool rel = rel_on && (!any_bias || all_bias);
-    if (rel) {
-        for (uint64_t a : hidx) if (a) ibase = std::min(ibase, a);
-        for (uint64_t a : hoidx) if (a) obase_a = std::min(obase_a, a);
-        for (uint64_t a : hbidx) if (a) bbase = std::min(bbase, a);
-        auto fits = [](uint64_t a, uint64_t base) { return !a || (((a - base) & 255) == 0 && ((a - base) >> 8) < 0x7fffffffull); };
-        for (uint64_t a : hidx) rel = rel && fits(a, ibase);
-        for (uint64_t a : hoidx) rel = rel && fits(a, obase_a);
-        for (uint64_t a : hbidx) rel = rel && fits(a, bbase);
-        rel = rel && ibase != ~0ull && obase_a != ~0ull;
-    }
-    if (rel) {
-        std::vector<int32_t> ridx(hidx.size(), -1), roidx(hoidx.size(), -1), rbidx(hbidx.size(), 0);
-        for (size_t x = 0; x < hidx.size(); x++) if (hidx[x]) ridx[x] = (int32_t)((hidx[x] - ibase) >> 8);
-        for (size_t x = 0; x < hoidx.size(); x++) if (hoidx[x]) roidx[x] = (int32_t)((hoidx[x] - obase_a) >> 8);
-        if (any_bias) for (size_t x = 0; x < hbidx.size(); x++) if (hbidx[x]) rbidx[x] = (int32_t)((hbidx[x] - bbase) >> 8);
-        const size_t off_oidx = al(ridx.size() * 4), off_bidx = off_oidx + al(roidx.size() * 4), off_w = off_bidx + al(rbidx.size() * 4);
-        std::vector<char> host(off_w + al(wbytes.size()), 0);
-        memcpy(host.data(), ridx.data(), ridx.size() * 4);
-        memcpy(host.data() + off_oidx, roidx.data(), roidx.size() * 4);
-        memcpy(host.data() + off_bidx, rbidx.data(), rbidx.size() * 4);
-        memcpy(host.data() + off_w, wbytes.data(), wbytes.size());
-        CHECK(ensure_scratch(ctx, al(host.size())));
-        char *tables; CHECK(upload_tmp(ctx, host.data(), host.size(), &tables));
-        GemmLaunch gl{small, two, false, MT, (const uint64_t *)ibase, tables, tables + off_w, tables + off_oidx, any_bias ? (const uint64_t *)bbase : nullptr, tables + off_bidx,
-                      (uint64_t *)obase_a, G, M, K, lazy, Kp, 0, WP, (M + 31) / 32, (K + 31) / 32, 2, (uint32_t)ctx->opt.gemm_order, one};
-        gl.in_unit = gl.out_unit = gl.bias_unit = 32;
-        return mfma ? cn_l_gemm_mfma(ctx, gl) : cn_l_gemm(ctx, gl);
-    }
-    const size_t off_oidx = al(hidx.size() * 8), off_bidx = off_oidx + al(hoidx.size() * 8), off_w = off_bidx + al(hbidx.size() * 8);
-    std::vector<char> host(off_w + al(wbytes.size()), 0);
-    memcpy(host.data(), hidx.data(), hidx.size() * 8);
-    memcpy(host.data() + off_oidx, hoidx.data(), hoidx.size() * 8);
-    memcpy(host.data() + off_bidx, hbidx.data(), hbidx.size() * 8);
-    memcpy(host.data() + off_w, wbytes.data(), wbytes.size());
-    CHECK(ensure_scratch(ctx, al(host.size())));
-    char *tables; CHECK(upload_tmp(ctx, host.data(), host.size(), &tables));
-    GemmLaunch gl{small, two, true, MT, fallback, tables, tables + off_w, tables + off_oidx, nullptr, any_bias ? tables + off_bidx : nullptr, nullptr,
-                  G, M, K, lazy, Kp, 0, WP, (M + 31) / 32, (K + 31) / 32, 2, (uint32_t)ctx->opt.gemm_order, one};
-    return mfma ? cn_l_gemm_mfma(ctx, gl) : cn_l_gemm(ctx, gl);
+    static const bool rel_on = !(getenv("CN_DEFER_REL") && !atoi(getenv("CN_DEFER_REL")));        // 0 keeps the address tables (A/B)
+    GemmAddressPlan R;
+    gemm_plan_addresses(ctx->hc, gemm_switches(ctx), A.data(), Wt.data(), out.data(), bias.data(), O, K, rel_on, R);
+    CHECK(ensure_scratch(ctx, al(R.image.size())));
+    char *tables; CHECK(upload_tmp(ctx, R.image.data(), R.image.size(), &tables));
+    GemmLaunch gl = gemm_launch(ctx, R.L, tables);
+    if (R.abs) gl.addresses((const uint64_t *)R.some_input, R.any_bias);
+    else gl.inputs((const uint64_t *)R.ibase, 32, 2).bias_at(R.any_bias ? (const uint64_t *)R.bbase : nullptr, tables + R.L.off_bidx, 32).outputs((uint64_t *)R.obase, 0, 32);
+    return run_gemm_launch(ctx, R.L, gl);
 }
 int flush_elementwise_group(cn_ctx *ctx, const std::vector<const DOp *> &ops, int type) {
     std::vector<Tab3> tab(ops.size());
@@ -305,8 +229,8 @@ static SgPlan *sg_plan(cn_ctx *ctx, DeferSquare &sq, uint32_t O, uint32_t K, std
     if (build_gemm_plan(ctx, p->cidx.data(), p->W.data(), O, K, nullptr, 0, nullptr, P)) return nullptr;     // (unreachable for queued calls: their weights and rows were checked when they were queued)
     p->ok = P.dig;                                                // (a layer outside the digit bound stays cached as such: it is not planned again every batch)
     if (p->ok) {
-        p->idx.assign((const int32_t *)P.host.data(), (const int32_t *)P.host.data() + (size_t)P.G * P.Kp);
-        p->oidx.assign((const int32_t *)(P.host.data() + P.off_oidx), (const int32_t *)(P.host.data() + P.off_oidx) + (size_t)P.G * P.M);
+        p->idx.assign(P.gather<int32_t>(P.host.data()), P.gather<int32_t>(P.host.data()) + (size_t)P.G * P.Kp);
+        p->oidx.assign(P.members<int32_t>(P.host.data()), P.members<int32_t>(P.host.data()) + (size_t)P.G * P.M);
         if (hipMalloc((void **)&P.dev, P.host.size()) != hipSuccess || hipMemcpy(P.dev, P.host.data(), P.host.size(), hipMemcpyHostToDevice) != hipSuccess) {
             (void)hipGetLastError();
             if (P.dev) (void)hipFree(P.dev);
@@ -411,11 +335,8 @@ static int sg_run(cn_ctx *ctx, DeferQueue *q, const SgGroup &g) {
     CHECK(upload_tmp(ctx, pidx.data(), pidx.size(), &dpidx)); CHECK(upload_tmp(ctx, bidx.data(), bidx.size(), &dbidx)); CHECK(upload_tmp(ctx, outs.data(), outs.size(), &douts));
     const uint64_t *arr = q->sq->arr;
     // two components of every product, three apart; bias polynomials as 256-byte offsets from the lowest one (as flush_gemm_group)
-    CHECK(launch_gemm_plan(ctx, P, P.dev, dpidx, arr, (uint32_t)(3 * kn), 2u, bias ? (const uint64_t *)bbase : nullptr, dbidx, 32, T, 0));
-    DigitGemmLaunch dg{arr + 2 * kn, 3 * kn, dpidx, P.dev + P.off_dw, P.dev + P.off_oidx, S, P.G, P.M, P.K, P.Kp, P.dKw, P.dMT};
-    if (P.dig_mfma) { dg.W = P.dev + P.off_w; dg.mfma = true; dg.P = P.P; dg.mtiles = P.mtiles; dg.ksteps = P.ksteps; }
-    dg.i32 = P.dig_i32;
-    CHECK(cn_l_digit_gemm(ctx, dg));
+    CHECK(run_gemm_launch(ctx, P, gemm_launch(ctx, P, P.dev).gather(dpidx).inputs(arr, (uint32_t)(3 * kn), 2).bias_at(bias ? (const uint64_t *)bbase : nullptr, dbidx, 32).outputs(T, 0, 0)));
+    CHECK(cn_l_digit_gemm(ctx, DigitGemmLaunch::of(P, P.dev, arr + 2 * kn, 3 * kn, dpidx, S)));
     CHECK(do_keyswitch(ctx, ctx->rlk, KsCall::relin_digits(S, P.dig_i32, T, kn, P.O).to_table(douts)));
     ctx->dsg_fused++;
     if (defer_trace()) fprintf(stderr, "defer %p level %d: fuses %u scalar products over %zu pending products (GEMM, digit GEMM%s, %u key switches)\n", (void *)ctx, g.level, P.O,

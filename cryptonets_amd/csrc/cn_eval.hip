@@ -1,5 +1,6 @@
 // libcnhip.so host runtime (2/5): the evaluator - linear operations, scalar GEMM planning, BEHZ multiply, key switching, rotations (launch logic behind the C ABI).
 #include "cn_api_shared.h"
+#include "cn_gemm_plan.h"
 
 // ---------------------------------------------------------------- linear ops
 int addsub(cn_ctx *ctx, cn_handle a, uint32_t ai, cn_handle b, uint32_t bi, cn_handle out, uint32_t oi, uint32_t count, int op) {
@@ -194,7 +195,6 @@ extern "C" int cn_pt_transform(cn_ctx *ctx, cn_handle pt, uint32_t pi, uint32_t 
     for (uint32_t c = 0; c < count; c++) O->pt_zero[oi + c] = P->pt_zero[pi + c];
     return 0;
 API_END }
-uint64_t lift_scalar(const DevConsts &hc, uint64_t w, uint32_t j) { return w >= hc.t_half ? w + hc.lift_inc[j] : w; }
 extern "C" int cn_mul_scalar(cn_ctx *ctx, cn_handle a, uint32_t ai, const uint64_t *scalars, uint32_t sstride, cn_handle out, uint32_t oi, uint32_t count) { API_BODY
     LOCK; GETCT(A, a, 0); GETCT(O, out, A->size);
     if (!range_ok(A, ai, count) || !range_ok(O, oi, count) || !scalars) return fail(CN_ERR_ARG, "index out of range");
@@ -216,209 +216,21 @@ extern "C" int cn_mul_scalar(cn_ctx *ctx, cn_handle a, uint32_t ai, const uint64
     ctx->st.PlainMultiplication += count;
     return 0;
 API_END }
-// small signed weights (|w| < 2^20 after centring mod t - every PoolLayer weight round(w*scale) is): exact-FP64 limb-split kernel
-bool gemm_weights_small(cn_ctx *ctx, const uint64_t *W, size_t count) {
-    for (size_t x = 0; x < count; x++) {
-        const uint64_t w = W[x], a = w >= ctx->hc.t_half ? ctx->hc.t.q - w : w;
-        if (a >> 20) return false;
-    }
-    return true;
-}
-GemmArith gemm_arith(cn_ctx *ctx, bool weights_small) {
-    const CnModRange qr = cn_mod_range(ctx->hc, 0, ctx->hc.k);
-    const int bits = qr.bits;
-    GemmArith g;
-    g.bits = bits;
-    g.small = weights_small && ctx->opt.f64 && bits <= 49;       // the kernel folds its limb sums with exact-FP64 modular arithmetic (q < 2^49.4)
-    g.two = qr.light;                                            // 2 limbs of 22 bits, else 3 limbs of 17 bits
-    if (g.small) g.lazy = g.two ? 1024u : 32768u;                // terms whose limb products (< 2^42 / 2^37) still sum exactly below 2^52
-    else g.lazy = (2 * bits >= 127) ? 1u : (uint32_t)std::min<uint64_t>(1u << 20, 1ull << (127 - 2 * bits));   // products of two values < q_max in 128 bits
-    return g;
-}
-
-// ---- the matrix-core form of a scalar GEMM (k_scalar_gemm_mfma): eligibility, weight digit planes, A fragments
-// 6 signed base-256 digits cover residues below 2^46 (x + 0x80..80 must stay below 2^48); i32 accumulators hold K * P * 2^14 < 2^31
-bool gemm_mfma_ok(cn_ctx *ctx, const GemmArith &ar, uint32_t M, uint32_t K) {
-    return ctx->opt.gemm_mfma && ar.small && ar.bits <= 46 && M >= 16 && (uint64_t)K * 3 < (1u << 17) && !(ctx->hc.n & 31);
-}
-uint32_t gemm_weight_planes(cn_ctx *ctx, const uint64_t *W, size_t count) {
-    uint64_t amax = 0;
-    for (size_t x = 0; x < count; x++) { const uint64_t w = W[x]; amax = std::max(amax, w >= ctx->hc.t_half ? ctx->hc.t.q - w : w); }
-    return amax <= 127 ? 1u : (amax <= 32639 ? 2u : 3u);          // signed digits -128..127: |w| <= 127 / 32639 / 8355711
-}
+// ---------------------------------------------------------------- scalar GEMM (planned in cn_gemm_plan.h)
+static_assert(GEMM_ERR_ARG == CN_ERR_ARG, "the planner's refusals are argument errors");
+// the switches of this context that the planner reads; a change of one drops the cached plans (defer_square_drop_plans)
+GemmSwitches gemm_switches(const cn_ctx *ctx) { return {ctx->opt.f64 != 0, ctx->opt.gemm_mfma != 0, ctx->opt.gemm_pair != 0, ctx->digit_mfma != 0, ctx->digit_i32 != 0}; }
 int free_gemm_plan(cn_ctx *ctx, Buffer &b) {
     if (b.plan && b.plan->dev) { HIPCHK(hipStreamSynchronize(ctx->stream)); HIPCHK(hipFree(b.plan->dev)); b.plan->dev = nullptr; }
     return 0;
 }
-// Gather lists that overlap are merged in PAIRS (round 5).  A convolution window of 25 taps shares 15 of them with its neighbour; as two gather lists every shared
-// input word travels from L2 to a CU twice - and that traffic, not HBM and not instruction issue, is what the layer waits for (profiles/HISTORY.md, round 5: the
-// CryptoNets convolution 370-380 us with one list per window, 300-320 us with the windows in pairs; wider tiles lose again: their outputs no longer fit the
-// 10-output register tile).  Two lists that share at least half of their inputs become ONE list (the union, 35 entries for two neighbouring 5 x 5 windows at stride
-// 2) whose outputs carry the weight 0 for the entries of the other list: a zero weight is "no term" in DenseMatrixBySparseVectorMultiply, the outputs are the same
-// words.  Only for small signed weights (the FP64 kernels), lists of at most 64 entries without repeated inputs and at most 5 outputs each (a pair then fills the
-// 10-output tile).  gidx / W2 / K are rewritten in place; returns false when nothing was merged.
-bool pair_gather_lists(uint32_t O, uint32_t &K, std::vector<int32_t> &gidx, const uint64_t *W, std::vector<uint64_t> &W2) {
-    if (K > 64 || O < 2) return false;
-    std::map<std::vector<int32_t>, std::vector<uint32_t>> groups;
-    for (uint32_t o = 0; o < O; o++) groups[std::vector<int32_t>(gidx.begin() + (size_t)o * K, gidx.begin() + (size_t)(o + 1) * K)].push_back(o);
-    const size_t G = groups.size();
-    if (G < 2 || G > 65536) return false;
-    struct L { std::vector<int32_t> in; const std::vector<uint32_t> *outs; const std::vector<int32_t> *list; int32_t mate = -1; };
-    std::vector<L> ls; ls.reserve(G);
-    for (auto &kv : groups) {
-        if (kv.second.size() > 5) return false;
-        L l; l.outs = &kv.second; l.list = &kv.first;
-        for (int32_t id : kv.first) if (id >= 0) l.in.push_back(id);
-        std::sort(l.in.begin(), l.in.end());
-        if (std::adjacent_find(l.in.begin(), l.in.end()) != l.in.end()) return false;       // an input twice in one list: its two weights would have to be added
-        ls.push_back(std::move(l));
-    }
-    std::unordered_map<int32_t, std::vector<uint32_t>> where;                               // input -> lists that gather it
-    for (uint32_t i = 0; i < G; i++) for (int32_t id : ls[i].in) where[id].push_back(i);
-    bool any = false;
-    std::vector<uint32_t> cnt(G, 0), touched;
-    for (uint32_t i = 0; i < G; i++) {
-        if (ls[i].mate >= 0) continue;
-        touched.clear();
-        for (int32_t id : ls[i].in) for (uint32_t j : where[id]) if (j > i && ls[j].mate < 0) { if (!cnt[j]++) touched.push_back(j); }
-        uint32_t best = 0; int32_t bj = -1;
-        for (uint32_t j : touched) { if (cnt[j] > best || (cnt[j] == best && (int32_t)j < bj)) { best = cnt[j]; bj = (int32_t)j; } cnt[j] = 0; }
-        if (bj >= 0 && 2 * best >= std::min(ls[i].in.size(), ls[bj].in.size()) && ls[i].in.size() + ls[bj].in.size() - best <= 64) { ls[i].mate = bj; ls[bj].mate = (int32_t)i; any = true; }
-    }
-    if (!any) return false;
-    // the union of a pair: the first list's entries in their order, then the second list's new ones; K2 = the longest list after merging
-    std::vector<std::vector<int32_t>> uni(G);
-    uint32_t K2 = 0;
-    for (uint32_t i = 0; i < G; i++) {
-        const int32_t m = ls[i].mate;
-        if (m >= 0 && (uint32_t)m < i) { uni[i] = uni[m]; continue; }
-        for (int32_t id : *ls[i].list) if (id >= 0) uni[i].push_back(id);
-        if (m >= 0) for (int32_t id : *ls[m].list) if (id >= 0 && !std::binary_search(ls[i].in.begin(), ls[i].in.end(), id)) uni[i].push_back(id);
-        K2 = std::max<uint32_t>(K2, (uint32_t)uni[i].size());
-    }
-    std::vector<int32_t> g2((size_t)O * K2, -1);
-    W2.assign((size_t)O * K2, 0);
-    for (uint32_t i = 0; i < G; i++) {
-        std::unordered_map<int32_t, uint32_t> pos;
-        for (uint32_t x = 0; x < uni[i].size(); x++) pos[uni[i][x]] = x;
-        for (uint32_t o : *ls[i].outs) {
-            for (uint32_t x = 0; x < uni[i].size(); x++) g2[(size_t)o * K2 + x] = uni[i][x];
-            for (uint32_t kk = 0; kk < K; kk++) { const int32_t id = gidx[(size_t)o * K + kk]; if (id >= 0) W2[(size_t)o * K2 + pos[id]] = W[(size_t)o * K + kk]; }
-        }
-    }
-    gidx.swap(g2); K = K2;
-    return true;
-}
 int build_gemm_plan(cn_ctx *ctx, const int32_t *idx, const uint64_t *W, uint32_t O, uint32_t K, Buffer *BP, cn_handle bias_pt, const int32_t *bias_idx,
                            GemmPlan &P) {
-    if (!O || !K || !W) return fail(CN_ERR_ARG, "empty scalar GEMM");
-    if (bias_pt && (!BP || !bias_idx)) return fail(CN_ERR_ARG, "invalid bias plaintext handle");
-    const uint64_t t = ctx->hc.t.q;
-    // validate + default gather (identity) + reference semantics: zero weights are skipped, all-zero row is an error
-    std::vector<int32_t> gidx((size_t)O * K);
-    for (uint32_t o = 0; o < O; o++) {
-        bool any = false;
-        for (uint32_t kk = 0; kk < K; kk++) {
-            int32_t id = idx ? idx[(size_t)o * K + kk] : (int32_t)kk;
-            uint64_t w = W[(size_t)o * K + kk];
-            if (w >= t) return fail(CN_ERR_ARG, "weight >= plain modulus");
-            if (id >= 0) P.max_in = std::max<uint32_t>(P.max_in, (uint32_t)id + 1);
-            if (id >= 0 && w) { any = true; P.nnz++; }
-            gidx[(size_t)o * K + kk] = id;
-        }
-        if (!any) return fail(CN_ERR_ARG, "output %u has no non-zero term (AddMany of nothing)", o);
-        if (BP && (bias_idx[o] < 0 || (uint32_t)bias_idx[o] >= BP->count)) return fail(CN_ERR_ARG, "bias index out of range");
-    }
-    std::vector<uint64_t> W2;
-    if (ctx->opt.gemm_pair && gemm_arith(ctx, gemm_weights_small(ctx, W, (size_t)O * K)).small && pair_gather_lists(O, K, gidx, W, W2)) W = W2.data();
-    // group outputs that gather the same inputs (PoolLayer: every map of one corner shares its patch)
-    std::map<std::vector<int32_t>, std::vector<uint32_t>> groups;
-    for (uint32_t o = 0; o < O; o++) groups[std::vector<int32_t>(gidx.begin() + (size_t)o * K, gidx.begin() + (size_t)(o + 1) * K)].push_back(o);
-    // groups may differ in size (a tiled convolution has smaller tiles at the border): M = the largest, the missing members of
-    // smaller groups get output index -1 (nothing stored) and all-zero weight rows
-    const uint32_t NONE = 0xffffffffu;
-    uint32_t G = (uint32_t)groups.size(), M = 0;
-    for (auto &g : groups) M = std::max<uint32_t>(M, (uint32_t)g.second.size());
-    const GemmArith ar = gemm_arith(ctx, gemm_weights_small(ctx, W, (size_t)O * K));
-    const bool small = ar.small, mfma = gemm_mfma_ok(ctx, ar, M, K);
-    // gather rows padded with -1 to 16 B multiples (+ 8 spare): the kernels read 4 at a time; matrix-core form: 32 entries per K step
-    const uint32_t Kp = mfma ? ((K + 31) / 32) * 32 : ((K + 15) & ~15u) + 16;       // gather rows: 16 spare entries (the VALU kernels request up to 2 x 8 terms ahead)
-    std::vector<int32_t> hidx((size_t)G * Kp, -1), hoidx((size_t)G * M, -1), hbidx((size_t)G * M, 0);
-    std::vector<uint32_t> member((size_t)G * M, NONE);           // output index of (group, m)
-    {
-        uint32_t g = 0;
-        for (auto &kv : groups) {
-            memcpy(&hidx[(size_t)g * Kp], kv.first.data(), K * 4);
-            for (uint32_t m = 0; m < kv.second.size(); m++) member[(size_t)g * M + m] = kv.second[m];
-            g++;
-        }
-    }
-    for (size_t x = 0; x < member.size(); x++) if (member[x] != NONE) { hoidx[x] = (int32_t)member[x]; if (BP) hbidx[x] = bias_idx[member[x]]; }   // relative to the output base
-    P.O = O; P.K = K; P.Kp = Kp; P.G = G; P.M = M; P.small = small; P.has_bias = BP != nullptr; P.bias_pt = bias_pt; P.bias_count = BP ? BP->count : 0;
-    P.two = ar.two; P.lazy = ar.lazy; P.mfma = mfma;
-    std::vector<char> wbytes;
-    auto row = [&](uint32_t g, uint32_t m) -> const uint64_t * { return member[(size_t)g * M + m] == NONE ? nullptr : W + (size_t)member[(size_t)g * M + m] * K; };
-    if (mfma) {
-        P.P = gemm_weight_planes(ctx, W, (size_t)O * K); P.mtiles = (M + 31) / 32; P.ksteps = (K + 31) / 32;
-        pack_gemm_mfma(ctx, G, M, K, P.P, row, [&](uint32_t g, uint32_t kk) { return hidx[(size_t)g * Kp + kk] >= 0; }, wbytes);
-    } else {
-        auto tap = [&](uint32_t g, uint32_t kk) { return hidx[(size_t)g * Kp + kk] >= 0; };
-        pack_gemm_weights(ctx, G, M, K, small, row, tap, P.MT, wbytes);
-        P.one = gemm_one_limb(ctx, ar, G, M, K, row, tap);
-    }
-    // cn_square_gemm: may this layer run on the DIGITS of unrelinearized products (k_digit_gemm)?  Small signed weights and, for every output, sum_k |w| (2^dbc - 1)
-    // below q_j / 2 for every j and below 2^52: the combined digit polynomial is then an exact double and a recentred lazy value of every limb's FP64 policy.
-    std::vector<double> dW;
-    if (small && ctx->hc.k >= 2 && ctx->hc.dbc >= 1 && ctx->hc.dbc <= 30) {
-        uint64_t qmin = ~0ull; for (uint32_t j = 0; j < ctx->hc.k; j++) qmin = std::min(qmin, ctx->hc.q[j].q);
-        const uint64_t dmax = (1ull << ctx->hc.dbc) - 1, lim = std::min<uint64_t>((qmin - 1) / 2, (1ull << 52) - 1) / dmax;      // sum |w| <= lim
-        bool ok = true;
-        uint64_t sum_max = 0;                                     // the largest sum_k |w_ok| of any output: the plan's digit bound is sum_max (2^dbc - 1)
-        for (uint32_t g = 0; g < G && ok; g++) for (uint32_t m = 0; m < M && ok; m++) {
-            const uint64_t *wr = row(g, m);
-            if (!wr) continue;
-            uint64_t sum = 0;
-            for (uint32_t kk = 0; kk < K; kk++) if (hidx[(size_t)g * Kp + kk] >= 0) { const uint64_t w = wr[kk]; sum += w >= ctx->hc.t_half ? t - w : w; }
-            ok = sum <= lim;
-            sum_max = std::max(sum_max, sum);
-        }
-        // Matrix-core form (k_digit_gemm_mfma) where the plan's own GEMM takes the matrix cores (P.mfma: small weights in P <= 3 signed byte digits |w_p| <= 128, M >= 16,
-        // 3 K < 2^17, rows of 32 K gather entries, fragments at off_w) and a digit splits into two int8 pieces: dg + 128 = (lo + 128) + 256 hi with hi <= 127 needs
-        // 2^dbc - 1 + 128 < 2^15, dbc <= 14 (then hi <= 64).  i32 head-room: a diagonal receives per term one lo x w_p product (<= 128 * 128) and one hi x w_(p-1) product
-        // (<= 64 * 128), K <= 43690 terms: 43690 * 24576 = 1 073 725 440 < 2^31.  N a multiple of 256: the column tiles of a slice are dealt to the 8 XCDs.
-        // Otherwise the FP64 form k_digit_gemm with its own table of signed doubles.
-        // int32 words for S ("digit_i32"): the plan's digit bound sum_max (2^dbc - 1) is at most 2^31 - 1; anything larger keeps doubles
-        if (ok) { P.dig = true; P.dig_mfma = mfma && ctx->digit_mfma && ctx->hc.dbc <= 14 && !(ctx->hc.n & 255); P.dig_i32 = ctx->digit_i32 && cn_digit_sum_fits_i32(sum_max, ctx->hc.dbc); }
-        if (ok && !P.dig_mfma) {
-            P.dMT = digit_gemm_tile(M); P.dKw = digit_gemm_rows(K);
-            const uint32_t mtd = (M + P.dMT - 1) / P.dMT;
-            dW.assign((size_t)G * mtd * P.dKw * P.dMT, 0.0);
-            for (uint32_t g = 0; g < G; g++) for (uint32_t m = 0; m < M; m++) {
-                const uint64_t *wr = row(g, m);
-                if (!wr) continue;
-                double *dst = &dW[(((size_t)g * mtd + m / P.dMT) * P.dKw) * P.dMT + m % P.dMT];
-                for (uint32_t kk = 0; kk < K; kk++) { const uint64_t w = hidx[(size_t)g * Kp + kk] >= 0 ? wr[kk] : 0; dst[(size_t)kk * P.dMT] = w >= ctx->hc.t_half ? -(double)(t - w) : (double)w; }
-            }
-        }
-    }
-    P.off_oidx = al(hidx.size() * 4); P.off_bidx = P.off_oidx + al(hoidx.size() * 4); P.off_w = P.off_bidx + al(hbidx.size() * 4);
-    P.off_dw = P.off_w + al(wbytes.size());
-    P.host.assign(P.off_dw + al(dW.size() * 8), 0);
-    memcpy(P.host.data() + P.off_dw, dW.data(), dW.size() * 8);
-    memcpy(P.host.data(), hidx.data(), hidx.size() * 4);
-    memcpy(P.host.data() + P.off_oidx, hoidx.data(), hoidx.size() * 4);
-    memcpy(P.host.data() + P.off_bidx, hbidx.data(), hbidx.size() * 4);
-    memcpy(P.host.data() + P.off_w, wbytes.data(), wbytes.size());
+    if (O && K && W && bias_pt && (!BP || !bias_idx)) return fail(CN_ERR_ARG, "invalid bias plaintext handle");
+    const GemmRefusal no = gemm_plan_indices(ctx->hc, gemm_switches(ctx), idx, W, O, K, BP ? bias_idx : nullptr, BP ? BP->count : 0, P, P.host, P.max_in, P.nnz);
+    if (no) return fail(no.rc, "%s", no.msg);
+    P.O = O; P.has_bias = BP != nullptr; P.bias_pt = bias_pt; P.bias_count = BP ? BP->count : 0;
     return 0;
-}
-// the launch of a plan from raw pointers: weights and output members at `tables`, gather rows at idx, inputs in_unit words apart (0: one ciphertext of `polys` polynomials; the
-// size-3 products of cn_square_gemm: 3 k N with polys = 2), bias polynomials bias_unit words apart (0: one plaintext; the deferred queue: 32 = 256-byte offsets), outputs from obase
-int launch_gemm_plan(cn_ctx *ctx, const GemmPlan &P, const char *tables, const void *idx, const uint64_t *in, uint32_t in_unit, uint32_t polys, const uint64_t *bias, const void *bidx,
-                     uint32_t bias_unit, uint64_t *out, uint32_t obase) {
-    GemmLaunch gl{P.small, P.two, false, P.MT, in, idx, tables + P.off_w, tables + P.off_oidx, bias, bidx, out,
-                  P.G, P.M, P.K, P.lazy, P.Kp, obase, P.P, P.mtiles, P.ksteps, polys, (uint32_t)ctx->opt.gemm_order, P.one};
-    gl.in_unit = in_unit; gl.bias_unit = bias_unit;
-    return P.mfma ? cn_l_gemm_mfma(ctx, gl) : cn_l_gemm(ctx, gl);
 }
 // tables: device image of P.host (scratch or the plan's own allocation)
 // in3 (cn_square_gemm): the inputs are the first TWO components of the size-3 products at in3 (P.max_in of them, checked by the caller) instead of the ciphertexts of I
@@ -437,7 +249,10 @@ int run_gemm_plan(cn_ctx *ctx, const GemmPlan &P, const char *tables, Buffer *I,
         if (!BP || BP->count < P.bias_count) return fail(CN_ERR_ARG, "invalid bias plaintext handle");
         bias = BP->d;
     }
-    CHECK(launch_gemm_plan(ctx, P, tables, tables, in3 ? in3 : I->d, in3 ? (uint32_t)(3 * ctx->hc.k * ctx->hc.n) : 0u, in3 ? 2u : I->size, bias, tables + P.off_bidx, 0, OB->d, oi));
+    // the size-3 products of cn_square_gemm: 3 k N words apart, their first two components; else the ciphertexts of I, one after the other
+    GemmLaunch gl = gemm_launch(ctx, P, tables).bias_at(bias, tables + P.off_bidx, 0).outputs(OB->d, oi, 0);
+    if (in3) gl.inputs(in3, (uint32_t)(3 * ctx->hc.k * ctx->hc.n), 2); else gl.inputs(I->d, 0, I->size);
+    CHECK(run_gemm_launch(ctx, P, gl));
     ctx->st.PlainMultiplication += P.nnz; ctx->st.Addition += P.nnz - P.O;
     if (P.has_bias) ctx->st.PlainAddition += P.O;
     return 0;
@@ -784,10 +599,7 @@ extern "C" int cn_square_gemm(cn_ctx *ctx, cn_handle plan, cn_handle in, uint32_
         CHECK(do_multiply(ctx, pa + (size_t)s * I->item_words, 1, pa + (size_t)s * I->item_words, 1, t3 + (size_t)s * 3 * kn, c));
     }
     CHECK(run_gemm_plan(ctx, P, P.dev, nullptr, OB, oi, t3));                     // components 0 and 1 (+ bias) straight into the outputs
-    DigitGemmLaunch dg{t3 + 2 * kn, 3 * kn, P.dev, P.dev + P.off_dw, P.dev + P.off_oidx, S, P.G, P.M, P.K, P.Kp, P.dKw, P.dMT};
-    if (P.dig_mfma) { dg.W = P.dev + P.off_w; dg.mfma = true; dg.P = P.P; dg.mtiles = P.mtiles; dg.ksteps = P.ksteps; }
-    dg.i32 = P.dig_i32;
-    CHECK(cn_l_digit_gemm(ctx, dg));
+    CHECK(cn_l_digit_gemm(ctx, DigitGemmLaunch::of(P, P.dev, t3 + 2 * kn, 3 * kn, P.dev, S)));
     uint64_t *o = OB->d + oi * OB->item_words;
     CHECK(do_keyswitch(ctx, ctx->rlk, KsCall::relin_digits(S, P.dig_i32, o, kn, P.O).to(o)));
     ctx->st.Relinarization += cnt; ctx->sg_fused++;

@@ -185,7 +185,7 @@ __global__ void __launch_bounds__(256) k_scalar_gemm_f64(const uint64_t *__restr
 #endif
     constexpr int PF = (MT <= 5) ? GEMM_PF_SMALL : 4;
     static_assert(PF % 4 == 0, "gather indices travel in 16 B scalar loads of four");
-    // A padded tap (-1 / address 0 in the gather row) and a term past K carry the WEIGHT 0 in the table (pack_gemm_weights) and read a valid word (element
+    // A padded tap (-1 / address 0 in the gather row) and a term past K carry the WEIGHT 0 in the table (pack_gemm_f64) and read a valid word (element
     // 0 / the fallback ciphertext); a block of `lazy` terms ends on a multiple of 2 PF unless it ends at K: no per-lane select on the 64-bit words.
     auto fetch = [&](uint64_t (&x)[PF], uint32_t kk) {
         // ONE 16 B scalar load per four gather indices (four dependent s_load_dword + wait chains cost more than the FMAs)
@@ -593,7 +593,7 @@ __global__ void __launch_bounds__(256) k_digit_gemm(const uint64_t *__restrict__
 // and hi = t >> 8 in 0..64 - exact by construction, both int8.  Products lo w_p have weight 256^p, hi w_p weight 256^(p + 1): P + 1 diagonals per digit,
 //   S = sum_j 256^j acc_j,   acc_j = sum_k (lo_k w_(k,j) + hi_k w_(k,j-1)).
 // A diagonal receives at most two products per term, together at most 128 * 128 + 64 * 128 = 24576 in magnitude; the plan takes this form only with 3 K < 2^17
-// (gemm_mfma_ok), K <= 43690 terms: |acc_j| <= 1 073 725 440 < 2^31 (the bound is enforced where the plan is built, cn_eval.hip).
+// (gemm_mfma_ok), K <= 43690 terms: |acc_j| <= 1 073 725 440 < 2^31 (the bound is enforced where the plan is built, cn_gemm_plan.h).
 // Fold in FP64, lowest diagonal first: every partial sum is an integer below 2^53 in magnitude - acc_0 + 256 acc_1 + 65536 acc_2 < 2^47.1 for any i32 values, and the top
 // diagonal of P = 3 holds only hi w_2 products (|w_2| <= 128: |acc_3| < 2^28.5, 2^24 |acc_3| < 2^52.5) - so each FMA is exact and the result is the S of k_digit_gemm
 // (|S| < 2^52 by the plan's digit check), stored where that kernel stores it.  An accumulator register holds 32 consecutive coefficients per half-wave: 256 B per store.

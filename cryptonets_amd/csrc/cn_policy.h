@@ -32,6 +32,26 @@ inline bool cn_digit_sum_fits_i32(uint64_t sum_abs_w, int dbc) {
     if (dbc < 1 || dbc > 31) return false;
     return (unsigned __int128)sum_abs_w * ((1ull << dbc) - 1) <= 0x7fffffffull;
 }
+// The tables of a planned scalar GEMM (HOT LOOP A), as the planner (cn_gemm_plan.h) writes them and the launchers (cn_l_gemm.hip) read them.
+// k_scalar_gemm_f64: rows of the weight table per (group, output tile) - K terms + zero rows up to a multiple of 16 + 16: the kernel's sets of 4 (or 8) terms run past K
+// and multiply whatever word the padded gather entry reads by these zeros
+inline uint32_t gemm_f64_rows(uint32_t K) { return ((K + 15) & ~15u) + 16; }
+inline uint32_t digit_gemm_tile(uint32_t M) { return M > 2 ? 10u : 2u; }
+inline uint32_t digit_gemm_rows(uint32_t K) { return ((K + 7) & ~7u) + 8; }        // K terms + zero rows: the kernel's sets of four terms run past K
+// image: [gather rows G x Kp | output members G x M | bias entries G x M | weights | digit-GEMM weights], every table on a 256-byte boundary; 4-byte entries (indices,
+// -1 = padded tap / no output) or 8-byte ones (device addresses, 0 likewise: the deferred queue's address-table form)
+struct GemmLayout {
+    uint32_t K = 0, Kp = 0, G = 0, M = 0, MT = 0, lazy = 0;
+    bool small = false, two = false, one = false, mfma = false;
+    uint32_t P = 0, mtiles = 0, ksteps = 0;  // matrix-core form: weight digit planes, 32-row output tiles, 32-term steps
+    // cn_square_gemm: the layer may run on the digits of the unrelinearized products (square_gemm_fused_ok) - signed weights [G][mtiles][dKw][dMT] at off_dw
+    // dig_mfma: the digit GEMM runs on the matrix cores from the fragments at off_w (no table at off_dw)
+    // dig_i32: every digit sum fits a signed 32-bit word (cn_digit_sum_fits_i32 of the largest row, "digit_i32" on): S is stored and read as int32 words
+    bool dig = false, dig_mfma = false, dig_i32 = false; uint32_t dMT = 0, dKw = 0;
+    size_t off_oidx = 0, off_bidx = 0, off_w = 0, off_dw = 0;
+    template <class E> const E *gather(const char *image) const { return (const E *)image; }                  // [G][Kp]
+    template <class E> const E *members(const char *image) const { return (const E *)(image + off_oidx); }    // [G][M]
+};
 // Sums over NTT-form plaintexts on the FP64 policies (k_mul_ptn_sum, cn_k_ptn.hip.h): a term is ArF64T::mulmod of two canonical words below q < 2^50, exact with
 // |term| <= q/2 + 3 q^2 / 2^53 (the quotient is rint of a product rounded three times).  cn_ptn_term_bound rounds that up to an integer; cn_ptn_sum_interval is how
 // many terms the lazy accumulators take between two recentrings: the largest count with count x bound < 2^52 (a recentred accumulator adds at most q/2 + 1 < 2^49:

@@ -337,10 +337,20 @@ struct GemmLaunch {
     uint32_t order = 0;                              // workgroup order of the VALU kernels: 0 group-major, 1 slice-major (gemm_block_coords)
     bool one = false;                                // k_scalar_gemm_f64<MT, 1, 0>: the words are not split (gemm_one_limb)
     uint32_t in_unit = 0, out_unit = 0, bias_unit = 0;   // words per index unit of the table-driven kernels; 0 = one ciphertext / one plaintext (plans).  Deferred calls: 32 (256 B offsets from the lowest address)
+    // the launch of a planned layout (GemmLayout, cn_policy.h) whose image is at `tables`: weights, output members and - until inputs() / bias_at() name others -
+    // gather rows and bias entries at their offsets; order: the "gemm_order" option.  Then the operands by name, `unit` as in_unit / bias_unit / out_unit above
+    static GemmLaunch of(const GemmLayout &L, const char *tables, uint32_t order) {
+        return {.small = L.small, .two = L.two, .abs = false, .MT = L.MT, .in = nullptr, .idx = tables, .W = tables + L.off_w, .oidx = tables + L.off_oidx, .bias = nullptr,
+                .bidx = tables + L.off_bidx, .out = nullptr, .G = L.G, .M = L.M, .K = L.K, .lazy = L.lazy, .Kp = L.Kp, .obase = 0, .P = L.P, .mtiles = L.mtiles, .ksteps = L.ksteps,
+                .order = order, .one = L.one};
+    }
+    GemmLaunch &inputs(const uint64_t *base, uint32_t unit, uint32_t polys_) { in = base; in_unit = unit; polys = polys_; return *this; }
+    GemmLaunch &gather(const void *rows) { idx = rows; return *this; }                             // gather rows made per call (the plan's own: at `tables`)
+    GemmLaunch &bias_at(const uint64_t *base, const void *entries, uint32_t unit) { bias = base; bidx = entries; bias_unit = unit; return *this; }      // base null: no bias
+    GemmLaunch &outputs(uint64_t *base, uint32_t first, uint32_t unit) { out = base; obase = first; out_unit = unit; return *this; }
+    // address-table form: every table entry is a device address; `any`: some input (the kernels read a valid word at padded taps); bias entries only where a call has one
+    GemmLaunch &addresses(const uint64_t *any, bool with_bias) { abs = true; in = any; if (!with_bias) bidx = nullptr; return *this; }
 };
-// k_scalar_gemm_f64: rows of the weight table per (group, output tile) - K terms + zero rows up to a multiple of 16 + 16: the kernel's sets of 4 (or 8) terms run past K
-// and multiply whatever word the padded gather entry reads by these zeros
-inline uint32_t gemm_f64_rows(uint32_t K) { return ((K + 15) & ~15u) + 16; }
 int cn_l_gemm(cn_ctx *c, const GemmLaunch &g);
 int cn_l_gemm_mfma(cn_ctx *c, const GemmLaunch &g);   // k_scalar_gemm_mfma: W = weight digit fragments, idx rows of ksteps * 32 entries
 // digit GEMM of cn_square_gemm (k_digit_gemm): in = component 2 of product 0 (products in_unit words apart), S [outputs][rl_tot][N] doubles (i32: int32 words); W = signed doubles
@@ -350,10 +360,14 @@ struct DigitGemmLaunch {
     uint32_t G, M, K, Kp, Kw, MT;
     bool mfma = false; uint32_t P = 0, mtiles = 0, ksteps = 0;
     bool i32 = false;
+    // the digit GEMM of a plan that has one (GemmLayout::dig): component 2 of the products at `in`, in_unit words apart, gathered through idx
+    static DigitGemmLaunch of(const GemmLayout &L, const char *tables, const uint64_t *in, size_t in_unit, const void *idx, void *S) {
+        return {.in = in, .in_unit = in_unit, .idx = idx, .W = tables + (L.dig_mfma ? L.off_w : L.off_dw), .oidx = tables + L.off_oidx, .S = S, .G = L.G, .M = L.M, .K = L.K,
+                .Kp = L.Kp, .Kw = L.dKw, .MT = L.dMT, .mfma = L.dig_mfma, .P = L.dig_mfma ? L.P : 0, .mtiles = L.dig_mfma ? L.mtiles : 0, .ksteps = L.dig_mfma ? L.ksteps : 0,
+                .i32 = L.dig_i32};
+    }
 };
 inline uint32_t digit_gemm_mfma_group(uint32_t P) { return P <= 2 ? 3u : 2u; }     // digits per workgroup: 16 (P + 1) DG accumulator registers per wave
-inline uint32_t digit_gemm_tile(uint32_t M) { return M > 2 ? 10u : 2u; }
-inline uint32_t digit_gemm_rows(uint32_t K) { return ((K + 7) & ~7u) + 8; }        // K terms + zero rows: the kernel's sets of four terms run past K
 int cn_l_digit_gemm(cn_ctx *c, const DigitGemmLaunch &g);
 // sum of unrelinearized products (cn_mul_relin_sum, k_product_sum): prod [outputs][K][3][k][N] -> components 0 and 1 summed mod q_l into out [outputs][2][k][N],
 // the digit sums of component 2 into S [outputs][rl_tot][N] doubles (i32: int32 words).  Every source limb has at most PRODUCT_SUM_MAX_DIGITS digits of at most 31 bits

@@ -145,6 +145,60 @@ def test_deferred_calls_equal_the_oracle(rng):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("weights", ["small", "wide"])
+def test_deferred_gemm_group_with_bias_on_some_outputs(weights, rng):
+    """Three scalar products over the same gather list (K = 4, one padded tap) on ONE level, an AddPlain folded onto outputs 0 and 2 only: a flush group with a
+    bias on some outputs cannot take the index tables, it runs the address-table kernels (gemm_plan_addresses) - the FP64 one for small weights, the integer one
+    with a weight of 2^20 and more.  No residue mod the 14-bit plain modulus of `tiny` is that large: the wide case runs on the `tiny` ring under a 23-bit one.
+    Output 1 is first the target of a queued addition, so that its scalar product waits on level 1, where the fold puts the other two."""
+    if weights == "small":
+        o, g, own = get_oracle("tiny", galois=False), get_gpu("tiny", galois=False), False
+    else:
+        from cryptonets_amd._native import Context
+        from oracle.cno import Oracle
+        p = dict(PARAMS["tiny"], t=4206593)                            # prime, 1 mod 2N
+        o = Oracle(p["n"], p["t"], q=p["q"], dbc=p["dbc"], gdbc=p["gdbc"])
+        o.keygen(11, galois=False)
+        g, own = Context(p["n"], p["t"], q=p["q"], dbc=p["dbc"], gdbc=p["gdbc"], device=0), True
+    cts = _fresh(o, rng, 3)
+    bias = np.stack([o.encode(np.full(o.n, b, dtype=np.uint64)) for b in (5, 7)])
+    W = rng.integers(1, 30, size=(3, 3), dtype=np.uint64)
+    W[1, 2] = o.t - 4
+    if weights == "wide":
+        W[0, 1], W[2, 0] = (1 << 20) + 3, o.t - (1 << 20) - 1
+    g.set_option("defer", 1)
+    try:
+        hs = []
+        for c in cts:
+            h = g.ct_alloc(1)
+            g.ct_upload(h, 0, c[None, :])
+            hs.append(h)
+        ph = g.pt_alloc(2)
+        g.pt_upload(ph, 0, bias)
+        taps, z = [hs[0], hs[1], 0, hs[2]], np.zeros(4, dtype=np.uint32)
+        row = lambda r: [W[r, 0], W[r, 1], 9, W[r, 2]]                # (the weight of a padded tap is ignored)
+        outs = [g.ct_alloc(1) for _ in range(3)]
+        g.add(hs[0], 0, hs[1], 0, outs[1], 0)
+        for r in (0, 2):
+            conv = g.ct_alloc(1)
+            g.scalar_dot(taps, z, row(r), conv, 0)
+            g.add_plain(conv, 0, ph, r // 2, outs[r], 0)
+            g.free(conv)
+        g.scalar_dot(taps, z, row(1), outs[1], 0)
+        assert g.get_option("pending_calls") == 6
+        got = np.stack([g.ct_download(h, 0, 1)[0] for h in outs])
+    finally:
+        g.set_option("defer", 0)
+    lin = o.scalar_gemm(cts, W)
+    want = np.stack([o.add_plain_batch(lin[0:1], bias[0:1])[0], lin[1], o.add_plain_batch(lin[2:3], bias[1:2])[0]])
+    assert np.array_equal(got, want)
+    for h in hs + outs + [ph]:
+        g.free(h)
+    if own:
+        g.close()
+
+
+@pytest.mark.gpu
 def test_deferred_argument_errors_are_immediate():
     from cryptonets_amd._native import CnError
     g = get_gpu("tiny", galois=False)

@@ -1,5 +1,5 @@
 """Host model, in plain integers, of what k_digit_gemm_mfma computes: the two-piece int8 split of a key-switch digit, the signed byte digits of a weight
-(pack_gemm_mfma), the P + 1 diagonals of their products and the fold back to S = sum_k w_k dig_k - and the bounds the plan relies on (cn_eval.hip)."""
+(pack_gemm_mfma), the P + 1 diagonals of their products and the fold back to S = sum_k w_k dig_k - and the bounds the plan relies on (cn_gemm_plan.h)."""
 import numpy as np
 import pytest
 

@@ -1,6 +1,6 @@
 """cn_digit_sum_fits_i32 (cryptonets_amd/csrc/cn_policy.h) - the plan-level decision "the digit sums of this layer fit int32 words" - against Python integers.
 
-build_gemm_plan asks it with the largest sum_k |w_ok| of any output, cn_mul_relin_sum with K (unit weights): true iff sum (2^dbc - 1) <= 2^31 - 1.  The two boundary
+gemm_digit_form (cn_gemm_plan.h) asks it with the largest sum_k |w_ok| of any output, cn_mul_relin_sum with K (unit weights): true iff sum (2^dbc - 1) <= 2^31 - 1.  The two boundary
 values of the product, 2^31 - 1 and 2^31, are reached exactly only at dbc = 1 (2^31 - 1 is prime) and, for the lower one, at dbc = 31 with sum 1; every other
 dbc is asked at the last sum that fits and the first that does not.  tests/cpp/digit_sum_bound.cpp is a plain g++ program: no device."""
 import os
