@@ -233,19 +233,10 @@ template <class FM, class FK> static int pipelined_halves(cn_ctx *ctx, uint32_t 
 size_t mul_scratch_per_ct(cn_ctx *c, bool square);
 int do_multiply(cn_ctx *ctx, const uint64_t *a, uint32_t astride, const uint64_t *b, uint32_t bstride, uint64_t *out3, uint32_t cnt, const uint64_t *const *atab = nullptr, const uint64_t *const *btab = nullptr);
 int ensure_ks_part(cn_ctx *ctx, size_t need);
-uint32_t ks_digit_max_blocks();
-uint32_t ks_wide_max_blocks();
-int ks_planned_mode(cn_ctx *ctx, uint32_t cnt, int galois);
-// may a Multiply + Relinearize of c ciphertexts run through pipelined_halves?  Only if the key switch of every part is the fused kernel: the two-launch forms keep their
-// partial products in the context's ONE arena ks_part (and may re-allocate it), which the parts on the two streams would share
-static inline bool pipeline_fused_ks(cn_ctx *ctx, uint32_t c) {
-    uint32_t first[4];
-    const uint32_t P = pipeline_cuts(c, first);
-    for (uint32_t i = 0; i < P; i++) if (ks_planned_mode(ctx, first[i + 1] - first[i], 0) != 0) return false;
-    return P >= 2;
-}
+KsSwitches ks_switches(const cn_ctx *ctx);
+KsPlan ks_plan(const cn_ctx *ctx, const KsKey &key, uint32_t cnt, int galois);
+bool halves_pipeline_ok(cn_ctx *ctx, uint32_t c, int sq_halves_min);
 int do_keyswitch(cn_ctx *ctx, const KsKey &key, const KsCall &call);
-bool ks_pair14_ok(cn_ctx *ctx, uint32_t cnt, int galois, const KsKey &key);
 uint32_t chunk_for(cn_ctx *ctx, size_t per_ct, uint32_t count);
 int mul_relin_body(cn_ctx *ctx, cn_handle a, uint32_t ai, uint32_t astride, cn_handle b, uint32_t bi, uint32_t bstride, cn_handle out, uint32_t oi, uint32_t count);
 const KsKey *galois_key(cn_ctx *ctx, uint64_t elt);          // null: not present
@@ -338,8 +329,6 @@ static inline void rec_galois(cn_ctx *ctx, uint64_t elt) {                // cn_
 #define NOT_LEVEL(what) do { if (ctx->level) return fail(CN_ERR_ARG, what " is not possible on a level context (its keys are its parent's, sliced)"); } while (0)
 // the BEHZ multiply and the key switch are not run on one coefficient modulus (include/cnhip.h: cn_ctx_create_level)
 #define TWO_LIMBS(what) do { if (ctx->hc.k < 2) return fail(CN_ERR_ARG, what " needs at least 2 coefficient moduli (a 1-limb context runs the linear operations, encryption and decryption)"); } while (0)
-#define KS_DIGIT_MAX_BLOCKS ks_digit_max_blocks()
-#define KS_WIDE_MAX_BLOCKS ks_wide_max_blocks()
 #define DISPATCH_K2(fn, ...) switch (ctx->hc.k) { \
     case 1: fn<1>(__VA_ARGS__); break; case 2: fn<2>(__VA_ARGS__); break; case 3: fn<3>(__VA_ARGS__); break; case 4: fn<4>(__VA_ARGS__); break; \
     case 5: fn<5>(__VA_ARGS__); break; case 6: fn<6>(__VA_ARGS__); break; case 7: fn<7>(__VA_ARGS__); break; case 8: fn<8>(__VA_ARGS__); break; \

@@ -368,7 +368,7 @@ int flush_mulrelin_group(cn_ctx *ctx, const std::vector<const DOp *> &all, const
             if (!t3) return fail(CN_ERR_HIP, "internal: scratch exhausted in deferred multiply");
             auto mul = [&](uint32_t f, uint32_t n_) { return do_multiply(ctx, nullptr, 1, nullptr, 1, t3 + (size_t)f * 3 * kn, n_, da + f, (sq ? da : db) + f); };
             auto ksw = [&](uint32_t f, uint32_t n_) { return do_keyswitch(ctx, ctx->rlk, KsCall::relin(t3 + (size_t)f * 3 * kn, kn, n_).to_table(dout + f)); };
-            if (ctx->opt.sq_halves >= 2 && ctx->hc.logn <= 13 && c >= SQ_HALVES_MIN && !ctx->capturing && pipeline_fused_ks(ctx, c) && aux_stream_ready(ctx)) {
+            if (halves_pipeline_ok(ctx, c, 2)) {
                 CHECK(pipelined_halves(ctx, c, mul, ksw)); continue;
             }
             CHECK(mul(0, c));
@@ -422,7 +422,7 @@ int flush_staged_group(cn_ctx *ctx, const std::vector<const DOp *> &all, int typ
         for (size_t i = 0; i < all.size(); i++) tab[i] = {(const NTT_GLOBAL uint64_t *)all[i]->a, (NTT_GLOBAL uint64_t *)all[i]->out};
         return copy_by_table(ctx, tab, (Tab2 *)ctx->stage, (uint32_t)ctx->ctw2);
     }
-    if (type == DOP_ROT && all.size() * ctx->hc.k <= KS_WIDE_MAX_BLOCKS) {     // few rotations, any step counts: one launch chain per hop round
+    if (type == DOP_ROT && ks_few_rotations(ctx->hc, ks_switches(ctx), all.size())) {     // few rotations, any step counts: one launch chain per hop round
         std::vector<RotJob> jobs(all.size());
         for (size_t i = 0; i < all.size(); i++) jobs[i] = {all[i]->a, all[i]->out, (int)all[i]->arg};
         return rotate_jobs(ctx, jobs);

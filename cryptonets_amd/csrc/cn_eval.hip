@@ -387,59 +387,35 @@ int ensure_ks_part(cn_ctx *ctx, size_t need) {
     ctx->ks_part_cap = need;
     return 0;
 }
-// auto: the fused kernel runs cnt*k workgroups.  Up to 32 of them (1-6 ciphertexts) every digit gets its own workgroup; up to 160
-// every source limb does; above that the fused kernel fills the chip by itself.
-uint32_t ks_digit_max_blocks() {              // (ciphertext, limb) blocks up to which the two-launch key switch runs one workgroup per DIGIT (above: per source limb); CN_KS_DIGIT_MAX overrides (A/B)
-    // 10 since round 3 (1-2 ciphertexts; 32 before): with the four chains of an image on four hardware queues, per-source-limb workgroups cost the
-    // chip less for 3-6 ciphertexts too (four chains 5.13-5.24 vs 5.36 ms per image, one chain alone unchanged; 50 / 65: 6.4 / 7.5 ms)
-    static const uint32_t v = getenv("CN_KS_DIGIT_MAX") ? (uint32_t)atoi(getenv("CN_KS_DIGIT_MAX")) : 10u;
-    return v;
+// the switches of this context that the key-switch planner reads (cn_ks_plan.h); CN_KS_DIGIT_MAX / CN_KS_WIDE_MAX override the two block thresholds (A/B), read once
+KsSwitches ks_switches(const cn_ctx *ctx) {
+    static const uint32_t digit_max = getenv("CN_KS_DIGIT_MAX") ? (uint32_t)atoi(getenv("CN_KS_DIGIT_MAX")) : 10u;
+    static const uint32_t wide_max = getenv("CN_KS_WIDE_MAX") ? (uint32_t)atoi(getenv("CN_KS_WIDE_MAX")) : 160u;
+    return {ctx->opt.ks_wide, ctx->opt.ks_split14, ctx->opt.ks_pair14, ctx->opt.ks_xcd, ctx->opt.ks_perm_fused, rr_kernels(ctx), ctx->hc.twdh != nullptr, digit_max, wide_max, ctx->smax};
 }
-uint32_t ks_wide_max_blocks() {               // (ciphertext, limb) blocks up to which a key switch runs as two launches; CN_KS_WIDE_MAX overrides (A/B)
-    static const uint32_t v = getenv("CN_KS_WIDE_MAX") ? (uint32_t)atoi(getenv("CN_KS_WIDE_MAX")) : 160u;
-    return v;
+KsPlan ks_plan(const cn_ctx *ctx, const KsKey &key, uint32_t cnt, int galois) { return cn_ks_plan(ctx->hc, ks_switches(ctx), key.f64, cnt, galois); }
+// may a Multiply + Relinearize of c ciphertexts run through pipelined_halves ("sq_halves" at least sq_halves_min)?  Only if no part's key switch writes the context's
+// ONE arena ks_part (the two-launch forms keep their partial products there and may re-allocate it), which the parts on the two streams would share
+bool halves_pipeline_ok(cn_ctx *ctx, uint32_t c, int sq_halves_min) {
+    if (ctx->opt.sq_halves < sq_halves_min || ctx->hc.logn > 13 || c < SQ_HALVES_MIN || ctx->capturing) return false;
+    uint32_t first[4];
+    const uint32_t P = pipeline_cuts(c, first);
+    for (uint32_t i = 0; i < P; i++) if (ks_writes_arena(ks_plan(ctx, ctx->rlk, first[i + 1] - first[i], 0))) return false;
+    return P >= 2 && aux_stream_ready(ctx);
 }
-// the variant do_keyswitch takes for `cnt` ciphertexts: 0 = the fused kernel, 1 / 2 = two launches (KsArgs::mode)
-int ks_planned_mode(cn_ctx *ctx, uint32_t cnt, int galois) {
-    const uint32_t k = ctx->hc.k, tot_dig = galois ? ctx->hc.gk_tot : ctx->hc.rl_tot;
-    if (!(rr_kernels(ctx) && (ctx->opt.ks_wide > 0 || (ctx->opt.ks_wide < 0 && cnt * k <= KS_WIDE_MAX_BLOCKS)))) return 0;
-    // N = 16384: 1024-thread workgroups cannot hold two accumulator sets without spilling -> per-digit only
-    const int mode = ctx->opt.ks_wide == 2 || (ctx->opt.ks_wide < 0 && cnt * k > KS_DIGIT_MAX_BLOCKS && ctx->hc.logn < 14) ? 2 : 1;
-    return (size_t)cnt * (mode == 2 ? k : tot_dig) * ctx->ctw2 * 8 > ctx->smax ? 0 : mode;
-}
-// One key switch.  call: the operands by name (KsCall, cn_runtime.h); the key words, accmax, mode, xcd_cts and the arena sizes are derived here.
-// perm_elt != 0 (two-launch variants only - the caller asks ks_planned_mode first): target / add0 are the c1 / c0 of the ciphertext a rotation
+// One key switch.  call: the operands by name (KsCall, cn_runtime.h); the key words and the plan (cn_ks_plan.h: form, accmax, xcd_cts, arena bytes) are added here.
+// perm_elt != 0 (two-launch forms only - the caller asks ks_perm_on_load first): target / add0 are the c1 / c0 of the ciphertext a rotation
 // READS and the kernels apply the automorphism x -> x^perm_elt while loading them
-// N = 16384, fused path: one launch per key switch (k_keyswitch_pair14).  A rotation then hands in target = sigma(c1) (permuted ahead of time: k_galois_limbs, or the
+// KS_PAIR14 (N = 16384): one launch per key switch.  A rotation then hands in target = sigma(c1) (permuted ahead of time: k_galois_limbs, or the
 // previous link of a rotate-and-add chain), add0 = the unpermuted c0 and perm_elt; next_elt / next_out ask for sigma_next of the new c1 on the side.
 int do_keyswitch(cn_ctx *ctx, const KsKey &key, const KsCall &call) {
     const uint32_t n = ctx->hc.n, k = ctx->hc.k, cnt = call.cnt, tot_dig = call.galois ? ctx->hc.gk_tot : ctx->hc.rl_tot;
-    const CnModRange qr = cn_mod_range(ctx->hc, 0, k);
-    const int bits = qr.bits, pol = cn_policy(qr, key.f64);          // by the form the key was loaded in (keys_as_f64 then), not by the "f64" option now
-    KsArgs a{call, key.d,
-             key.f64 ? (bits >= 50 ? 1u : (1u << std::min(10, 50 - bits))) : 0xffffffffu,     // lazy FP64 accumulators: |term| <= 2.1 q, sum below 2^52
-             ks_planned_mode(ctx, cnt, call.galois)};
-    if (ctx->opt.ks_xcd == 1) a.xcd_cts = cnt & ~7u;
-    else if (ctx->opt.ks_xcd == 2) a.xcd_cts = 0x80000000u;
-    const bool rr = rr_kernels(ctx);
-    if (a.mode) CHECK(ensure_ks_part(ctx, (size_t)cnt * (a.mode == 2 ? k : tot_dig) * ctx->ctw2 * 8));
-    if (a.dig && !(rr && key.f64 && ctx->hc.logn <= 13 && !a.galois && !ctx->hc.ks_xi)) return fail(CN_ERR_ARG, "internal: ready-made digits outside the FP64 register-radix key switch");
-    const bool pair = ks_pair14_ok(ctx, cnt, a.galois, key);
-    if ((a.perm_elt || a.items || a.next_elt) && !a.mode && !(pair && !a.items)) return fail(CN_ERR_ARG, "internal: automorphism inside the fused key switch");
-    if (pair) {                                                                                      // N = 16384: both 8192-point halves of a limb in one workgroup, one launch
-        CHECK(ensure_ks_part(ctx, (size_t)cnt * ctx->ctw2 * 8));
-        a.xcd_cts = ctx->opt.ks_xcd == 1 ? (cnt & ~7u) : 0u;
-        ks_ops[pol]->pair14(ctx, a);
-    } else if (a.mode == 0 && rr && key.f64 && ctx->hc.logn == 14 && ctx->hc.twdh && ctx->opt.ks_split14) {   // ... as two workgroups per limb + a combining pass (rounds 1-4; A/B)
-        CHECK(ensure_ks_part(ctx, (size_t)cnt * ctx->ctw2 * 8));
-        ks_ops[pol]->split14(ctx, a);
-        hipLaunchKernelGGL(k_ks_combine14, dim3(cnt * 2 * k * (n / 512)), dim3(256), 0, ctx->stream, (const uint64_t *)ctx->ks_part, a.add0, a.add1, a.astride, a.out, ctx->dc,
-                           a.extra, a.xstride, a.out_tab);
-        launch_count(ctx);
-    } else {
-        const bool done = rr && ks_ops[pol]->launch(ctx, a);
-        if (!done && key.f64) return fail(CN_ERR_ARG, "internal: FP64 key without FP64 kernel");
-        if (!done) {                        // radix-2 LDS fallback (N < 1024, legacy_ntt): no fused accumulator -> one element-wise add behind it
+    KsArgs a{call, key.d, ks_plan(ctx, key, cnt, call.galois)};
+    const KsRefusal no = ks_refusal(ctx->hc, a.plan, key.f64, a.galois, {a.dig != nullptr, a.perm_elt != 0, a.items != nullptr, a.next_elt != 0});
+    if (no) return fail(no.rc, "%s", no.msg);
+    CHECK(ensure_ks_part(ctx, a.plan.arena_bytes));
+    switch (a.plan.form) {
+        case KS_LEGACY: {                   // radix-2 LDS (N < 1024, legacy_ntt): no fused accumulator -> one element-wise add behind it
             // The accumulator may be the result's own array (SumAllSlots adds in place): the key switch then writes into the key-switch arena
             // (unused by this path) and the add reads it beside the untouched accumulator.  (Writing `out` first doubled the key switch there.)
             uint64_t *const out = a.out;
@@ -462,15 +438,20 @@ int do_keyswitch(cn_ctx *ctx, const KsKey &key, const KsCall &call) {
                                    ctx->chunks, 0);
                 launch_count(ctx);
             }
+            break;
         }
+        default:
+            if (!ks_ops[a.plan.policy]->launch(ctx, a)) return fail(CN_ERR_ARG, "internal: key-switch form without a kernel of its policy");
+            if (a.plan.form == KS_SPLIT14) {        // the halves of k_keyswitch_split14 lie in ks_part: the combining pass (rounds 1-4; A/B)
+                hipLaunchKernelGGL(k_ks_combine14, dim3(cnt * 2 * k * (n / 512)), dim3(256), 0, ctx->stream, (const uint64_t *)ctx->ks_part, a.add0, a.add1, a.astride, a.out, ctx->dc,
+                                   a.extra, a.xstride, a.out_tab);
+                launch_count(ctx);
+            }
     }
     HIPCHK(hipGetLastError()); launch_count(ctx);
     if (a.dig && a.dig_i32) ctx->ks_dig_i32++;
     ctx->st.ntt_forward_limbs += (uint64_t)cnt * tot_dig * k; ctx->st.ntt_inverse_limbs += (uint64_t)cnt * 2 * k;
     return 0;
-}
-bool ks_pair14_ok(cn_ctx *ctx, uint32_t cnt, int galois, const KsKey &key) {
-    return ctx->opt.ks_pair14 && ctx->opt.ks_split14 && rr_kernels(ctx) && ctx->hc.logn == 14 && ctx->hc.twdh && key.f64 && ks_planned_mode(ctx, cnt, galois) == 0;
 }
 uint32_t chunk_for(cn_ctx *ctx, size_t per_ct, uint32_t count) {
     size_t c = std::max<size_t>(1, ctx->smax / per_ct);
@@ -538,7 +519,7 @@ int mul_relin_body(cn_ctx *ctx, cn_handle a, uint32_t ai, uint32_t astride, cn_h
         uint64_t *t3 = salloc<uint64_t>(ctx, (size_t)c * 3 * kn);
         auto mul = [&](uint32_t f, uint32_t n_) { return do_multiply(ctx, pa + (size_t)(s + f) * astride * A->item_words, astride, pb + (size_t)(s + f) * bstride * B->item_words, bstride, t3 + (size_t)f * 3 * kn, n_); };
         auto ksw = [&](uint32_t f, uint32_t n_) { return do_keyswitch(ctx, ctx->rlk, KsCall::relin(t3 + (size_t)f * 3 * kn, kn, n_).to(O->d + (oi + s + f) * O->item_words)); };
-        if (ctx->opt.sq_halves && ctx->hc.logn <= 13 && c >= SQ_HALVES_MIN && !ctx->capturing && pipeline_fused_ks(ctx, c) && aux_stream_ready(ctx)) {
+        if (halves_pipeline_ok(ctx, c, 1)) {
             CHECK(pipelined_halves(ctx, c, mul, ksw)); continue;
         }
         CHECK(mul(0, c));
@@ -742,21 +723,27 @@ int do_galois(cn_ctx *ctx, const GaloisCall &g) {
     // before anything is written (they used to be refused on every path).
     const bool shifted = shifted_overlap(g.in, g.out, count * ctx->ctw2);
     CHECK(add_overlap(ctx, nullptr, g.acc, g.out, count));
+    // how the automorphism reaches the key switch, decided once: c1 permuted ahead and c0 inside KS_PAIR14 (N = 16384, batch); applied by the two-launch kernels
+    // while they load c1 and c0 (small batches: no permutation pass); or a permutation pass over the whole ciphertext
+    enum { PERM_AHEAD, PERM_ON_LOAD, PERM_PASS } via = PERM_PASS;
+    if (!shifted && ks_plan(ctx, *key, count, 1).form == KS_PAIR14) via = PERM_AHEAD;
+    else if (!shifted && ks_perm_on_load(ctx->hc, ks_switches(ctx), count)) via = PERM_ON_LOAD;
+    if (via != PERM_AHEAD && (g.pre || g.next_elt)) return fail(CN_ERR_ARG, "internal: rotation chain outside the one-launch key switch");
     KsCall ks;
-    if (!shifted && ks_pair14_ok(ctx, count, 1, *key)) {                 // N = 16384, batch: c1 is permuted once (here unless the caller brings it), c0 inside the key switch
-        if (!g.pre) {
-            hipLaunchKernelGGL(k_galois_limbs, dim3(count * ctx->hc.k), dim3(1024), (size_t)ctx->hc.n * 8, ctx->stream, g.in + kn, 2 * kn, g.tmp, kn, ctx->dc, g.elt);
+    switch (via) {
+        case PERM_AHEAD:                                                 // c1 is permuted once (here unless the caller brings it)
+            if (!g.pre) {
+                hipLaunchKernelGGL(k_galois_limbs, dim3(count * ctx->hc.k), dim3(1024), (size_t)ctx->hc.n * 8, ctx->stream, g.in + kn, 2 * kn, g.tmp, kn, ctx->dc, g.elt);
+                HIPCHK(hipGetLastError()); launch_count(ctx);
+            }
+            ks = KsCall::galois_of(g.pre ? g.pre : g.tmp, kn, g.in, kn, count).perm(elt).next((uint32_t)g.next_elt, g.next_out);
+            break;
+        case PERM_ON_LOAD: ks = KsCall::galois_of(g.in + kn, 2 * kn, g.in, kn, count).perm(elt); break;
+        case PERM_PASS:
+            if (ctx->hc.n >= 1024) hipLaunchKernelGGL(k_galois_lds, dim3(limbs), dim3(std::min<uint32_t>(1024, ctx->hc.n / 4)), (size_t)ctx->hc.n * 8, ctx->stream, g.in, g.tmp, ctx->dc, g.elt);
+            else hipLaunchKernelGGL(k_galois, dim3(limbs * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, g.in, g.tmp, ctx->dc, ctx->chunks, g.elt);
             HIPCHK(hipGetLastError()); launch_count(ctx);
-        }
-        ks = KsCall::galois_of(g.pre ? g.pre : g.tmp, kn, g.in, kn, count).perm(elt).next((uint32_t)g.next_elt, g.next_out);
-    } else if (g.pre || g.next_elt) return fail(CN_ERR_ARG, "internal: rotation chain outside the one-launch key switch");
-    else if (!shifted && ctx->opt.ks_perm_fused && ks_planned_mode(ctx, count, 1) != 0)      // small batches (two-launch key switch): no permutation pass - the
-        ks = KsCall::galois_of(g.in + kn, 2 * kn, g.in, kn, count).perm(elt);                // key-switch kernels apply the automorphism while they load c1 and c0
-    else {
-        if (ctx->hc.n >= 1024) hipLaunchKernelGGL(k_galois_lds, dim3(limbs), dim3(std::min<uint32_t>(1024, ctx->hc.n / 4)), (size_t)ctx->hc.n * 8, ctx->stream, g.in, g.tmp, ctx->dc, g.elt);
-        else hipLaunchKernelGGL(k_galois, dim3(limbs * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, g.in, g.tmp, ctx->dc, ctx->chunks, g.elt);
-        HIPCHK(hipGetLastError()); launch_count(ctx);
-        ks = KsCall::galois_of(g.tmp + kn, 2 * kn, g.tmp, kn, count);
+            ks = KsCall::galois_of(g.tmp + kn, 2 * kn, g.tmp, kn, count);
     }
     CHECK(do_keyswitch(ctx, *key, ks.to(g.out).plus(g.acc, ctx->ctw2)));
     ctx->st.Rotation += count;
@@ -814,13 +801,13 @@ int rotate_jobs(cn_ctx *ctx, std::vector<RotJob> &jobs) {
     for (RotJob &j : jobs) { CHECK(plan_rotation(ctx, j.steps, &j.plan)); rounds = std::max(rounds, j.plan.hops); }
     bool aliased = false;
     for (uint32_t a = 0; a < n && !aliased; a++) for (uint32_t b = 0; b < n; b++) if (a != b && (jobs[a].dst == jobs[b].src || jobs[a].dst == jobs[b].dst)) { aliased = true; break; }
-    bool tables_ok = ctx->opt.ks_perm_fused && !aliased && ks_planned_mode(ctx, n, 1) != 0;
-    if (!tables_ok && !aliased && ctx->opt.ks_perm_fused && n > 1) {
+    const KsSwitches sw = ks_switches(ctx);
+    const bool tables_ok = !aliased && ks_perm_on_load(ctx->hc, sw, n);
+    if (!tables_ok && !aliased && n > 1) {
         // More rotations than ONE table-driven two-launch key switch takes (LoLa-CIFAR's ConvertToColumnVector: 83 maps at N = 16384 - 664 (ciphertext, limb)
         // blocks against the 160 up to which a key switch runs as two launches): pieces of the largest size that does, each a launch chain of its own, instead
         // of 83 x ~4 single-ciphertext rotations of two launches each (round 5: 632 -> ~40 launches per plaintext prime and image).  Independent jobs: any order.
-        uint32_t piece = 0;
-        for (uint32_t c = std::min<uint32_t>(n - 1, 64); c >= 2; c--) if (ks_planned_mode(ctx, c, 1) != 0) { piece = c; break; }
+        const uint32_t piece = ks_largest_perm_on_load(ctx->hc, sw, std::min<uint32_t>(n - 1, 64));
         if (piece) {
             for (uint32_t s0 = 0; s0 < n; s0 += piece) {
                 std::vector<RotJob> part(jobs.begin() + s0, jobs.begin() + std::min<uint32_t>(n, s0 + piece));
@@ -952,7 +939,7 @@ std::vector<uint64_t> sum_slots_chain_elts(cn_ctx *ctx, uint32_t count, uint32_t
     uint32_t l2 = length ? length : n;
     if (l2 >= half) { elts.push_back(2ull * n - 1); l2 = half; }
     for (uint32_t steps = 1; steps < l2 && ok; steps *= 2) elts.push_back(cn_elt_of_step(n, -(int)steps));
-    for (uint64_t e : elts) { const KsKey *key = galois_key(ctx, e); if (!key || !ks_pair14_ok(ctx, count, 1, *key)) { ok = false; break; } }
+    for (uint64_t e : elts) { const KsKey *key = galois_key(ctx, e); if (!key || ks_plan(ctx, *key, count, 1).form != KS_PAIR14) { ok = false; break; } }
     if (!ok || elts.size() < 2) elts.clear();
     return elts;
 }

@@ -44,22 +44,20 @@ static int set_attrs(uint32_t logn, size_t bytes) {
     }
     return 0;
 }
-// the LDS copy of the twiddle table pays once a workgroup runs enough digit transforms of its modulus
-static const uint32_t KS_TWL_MIN_DIGITS = 12;
 template <int L, bool XI, class ARS = AR> static void launch_fused_x(cn_ctx *c, const KsArgs &a) {
     const uint32_t tot = a.galois ? c->hc.gk_tot : c->hc.rl_tot;
     constexpr bool DIG = KsSrc<ARS>::dig;
     const uint64_t *tgt = DIG ? (const uint64_t *)a.dig : a.target;
     const size_t tstride = DIG ? (size_t)tot * c->hc.n : a.tstride;
     if constexpr (KsFwd<AR, L>::lds) {
-        if (tot >= KS_TWL_MIN_DIGITS) {
+        if (a.plan.twl) {
             hipLaunchKernelGGL((k_keyswitch_rr<L, ARS, 1, true, XI>), dim3(a.cnt * c->hc.k), dim3(NttPlan<L>::NT), ks_twl_lds<L>(), c->stream, tgt, tstride, a.add0, a.add1,
-                               a.astride, (const void *)a.key, a.out, c->dc, a.galois, a.accmax, a.extra, a.xstride, a.out_tab, a.xcd_cts);
+                               a.astride, (const void *)a.key, a.out, c->dc, a.galois, a.plan.accmax, a.extra, a.xstride, a.out_tab, a.plan.xcd_cts);
             return;
         }
     }
     hipLaunchKernelGGL((k_keyswitch_rr<L, ARS, 1, false, XI>), dim3(a.cnt * c->hc.k), dim3(NttPlan<L>::NT), (size_t)ntt_lds_words(1u << L) * 8, c->stream, tgt, tstride,
-                       a.add0, a.add1, a.astride, (const void *)a.key, a.out, c->dc, a.galois, a.accmax, a.extra, a.xstride, a.out_tab, a.xcd_cts);
+                       a.add0, a.add1, a.astride, (const void *)a.key, a.out, c->dc, a.galois, a.plan.accmax, a.extra, a.xstride, a.out_tab, a.plan.xcd_cts);
 }
 template <int L> static void launch_fused(cn_ctx *c, const KsArgs &a) {
     if constexpr (kF64) {
@@ -74,14 +72,15 @@ template <int L> static void launch_fused(cn_ctx *c, const KsArgs &a) {
 // first launch of the two-launch forms from ready-made digit polynomials (DS: KsDigits<AR> or KsDigits<AR, int32_t>)
 template <int L, class DS> static void launch_dig_mac(cn_ctx *c, const KsArgs &a, uint32_t tot, size_t lds) {
     const uint32_t k = c->hc.k;
-    if (a.mode == 2) hipLaunchKernelGGL((k_ks_limb_mac<L, DS>), dim3(a.cnt * k * k), dim3(NttPlan<L>::NT), lds, c->stream, (const uint64_t *)a.dig, (size_t)tot * c->hc.n,
-                                        (const void *)a.key, c->ks_part, c->dc, a.galois, a.accmax, 0u, (const KsItem *)nullptr);
+    if (a.plan.form == KS_LIMB_MAC) hipLaunchKernelGGL((k_ks_limb_mac<L, DS>), dim3(a.cnt * k * k), dim3(NttPlan<L>::NT), lds, c->stream, (const uint64_t *)a.dig, (size_t)tot * c->hc.n,
+                                        (const void *)a.key, c->ks_part, c->dc, a.galois, a.plan.accmax, 0u, (const KsItem *)nullptr);
     else hipLaunchKernelGGL((k_ks_digit_mac<L, DS>), dim3(a.cnt * tot * k), dim3(NttPlan<L>::NT), lds, c->stream, (const uint64_t *)a.dig, (size_t)tot * c->hc.n,
                             (const void *)a.key, c->ks_part, c->dc, a.galois, tot, 0u, (const KsItem *)nullptr);
 }
 template <int L> static void launch_two_phase(cn_ctx *c, const KsArgs &a) {
     const uint32_t tot = a.galois ? c->hc.gk_tot : c->hc.rl_tot, k = c->hc.k;
     const size_t lds = (size_t)ntt_lds_words(1u << L) * 8;
+    const bool limb = a.plan.form == KS_LIMB_MAC;
     bool dig = false;
     if constexpr (kF64) dig = a.dig != nullptr;
     if (dig) {                      // ready-made digit polynomials: the same two forms, first launch from KsArgs::dig
@@ -92,25 +91,59 @@ template <int L> static void launch_two_phase(cn_ctx *c, const KsArgs &a) {
             if (!i32) launch_dig_mac<L, KsDigits<AR>>(c, a, tot, lds);
         }
         hipLaunchKernelGGL((k_ks_sum_intt<L, AR>), dim3(a.cnt * k * 2), dim3(NttPlan<L>::NT), lds, c->stream, (const void *)c->ks_part, a.add0, a.add1, a.astride,
-                           a.out, c->dc, a.mode == 2 ? k : tot, a.mode == 2 ? 0xffffffffu : a.accmax, a.extra, a.xstride, a.out_tab, a.perm_elt, a.items);
-    } else if (a.mode == 2) {       // one partial per (ct, source limb): k*k workgroups per ciphertext, k partials to sum
+                           a.out, c->dc, limb ? k : tot, limb ? 0xffffffffu : a.plan.accmax, a.extra, a.xstride, a.out_tab, a.perm_elt, a.items);
+    } else if (limb) {              // one partial per (ct, source limb): k*k workgroups per ciphertext, k partials to sum
         hipLaunchKernelGGL((k_ks_limb_mac<L, AR>), dim3(a.cnt * k * k), dim3(NttPlan<L>::NT), lds, c->stream, a.target, a.tstride, (const void *)a.key, c->ks_part,
-                           c->dc, a.galois, a.accmax, a.perm_elt, a.items);
+                           c->dc, a.galois, a.plan.accmax, a.perm_elt, a.items);
         hipLaunchKernelGGL((k_ks_sum_intt<L, AR>), dim3(a.cnt * k * 2), dim3(NttPlan<L>::NT), lds, c->stream, (const void *)c->ks_part, a.add0, a.add1, a.astride,
                            a.out, c->dc, k, 0xffffffffu, a.extra, a.xstride, a.out_tab, a.perm_elt, a.items);
     } else {                        // one partial per (ct, digit)
         hipLaunchKernelGGL((k_ks_digit_mac<L, AR>), dim3(a.cnt * tot * k), dim3(NttPlan<L>::NT), lds, c->stream, a.target, a.tstride, (const void *)a.key, c->ks_part,
                            c->dc, a.galois, tot, a.perm_elt, a.items);
         hipLaunchKernelGGL((k_ks_sum_intt<L, AR>), dim3(a.cnt * k * 2), dim3(NttPlan<L>::NT), lds, c->stream, (const void *)c->ks_part, a.add0, a.add1, a.astride,
-                           a.out, c->dc, tot, a.accmax, a.extra, a.xstride, a.out_tab, a.perm_elt, a.items);
+                           a.out, c->dc, tot, a.plan.accmax, a.extra, a.xstride, a.out_tab, a.perm_elt, a.items);
     }
     cn_launch_count(c);
 }
 template <int L> static void launch_rr(cn_ctx *c, const KsArgs &a) {
-    if (a.mode) { launch_two_phase<L>(c, a); return; }
+    if (ks_two_launch(a.plan.form)) { launch_two_phase<L>(c, a); return; }
     launch_fused<L>(c, a);
 }
+// N = 16384 as two 8192-point halves per limb: partial halves into c->ks_part (the caller runs k_ks_combine14 behind it)
+static bool split14(cn_ctx *c, const KsArgs &a) {
+    if constexpr (kF64) {
+        if (c->hc.ks_xi)
+            hipLaunchKernelGGL((k_keyswitch_split14<AR, true>), dim3(a.cnt * c->hc.k * 2), dim3(NttPlan<13>::NT), (size_t)ntt_lds_words(8192) * 8, c->stream, a.target, a.tstride,
+                               (const void *)a.key, (uint64_t *)c->ks_part, c->dc, a.galois, a.plan.accmax);
+        else
+            hipLaunchKernelGGL((k_keyswitch_split14<AR>), dim3(a.cnt * c->hc.k * 2), dim3(NttPlan<13>::NT), (size_t)ntt_lds_words(8192) * 8, c->stream, a.target, a.tstride,
+                               (const void *)a.key, (uint64_t *)c->ks_part, c->dc, a.galois, a.plan.accmax);
+        return true;
+    }
+    return false;
+}
+// N = 16384 in one launch: both halves per (ciphertext, output limb) workgroup (k_keyswitch_pair14); a.target = sigma(c1) for rotations
+template <bool XI, bool WHOLE> static void launch_pair14(cn_ctx *c, const KsArgs &a) {
+    if constexpr (kF64)
+        hipLaunchKernelGGL((k_keyswitch_pair14<AR, XI, WHOLE>), dim3(a.cnt * c->hc.k), dim3(NttPlan<13>::NT), PAIR14_LDS, c->stream, a.target, a.tstride, a.add0, a.add1, a.astride,
+                           (const void *)a.key, a.out, (double *)c->ks_part, c->dc, a.galois, a.plan.accmax, a.extra, a.xstride, a.out_tab, a.perm_elt, a.next_elt, a.next_out, a.plan.xcd_cts);
+}
+static bool pair14(cn_ctx *c, const KsArgs &a) {
+    if constexpr (kF64) {
+        if (c->hc.ks_xi) { if (a.plan.whole) launch_pair14<true, true>(c, a); else launch_pair14<true, false>(c, a); }
+        else { if (a.plan.whole) launch_pair14<false, true>(c, a); else launch_pair14<false, false>(c, a); }
+        return true;
+    }
+    return false;
+}
+// the kernels of a.plan.form (cn_ks_plan.h); false: this policy or ring size has no instantiation of it
 static bool launch(cn_ctx *c, const KsArgs &a) {
+    switch (a.plan.form) {
+        case KS_LEGACY: return false;           // (k_keyswitch is launched by do_keyswitch itself)
+        case KS_SPLIT14: return split14(c, a);
+        case KS_PAIR14: return pair14(c, a);
+        default: break;
+    }
     switch (c->hc.logn) {
         case 10: launch_rr<10>(c, a); return true;
         case 11: launch_rr<11>(c, a); return true;
@@ -120,43 +153,6 @@ static bool launch(cn_ctx *c, const KsArgs &a) {
         default: return false;
     }
 }
-// N = 16384 as two 8192-point halves per limb: partial halves into c->ks_part (the caller runs k_ks_combine14 behind it)
-static bool split14(cn_ctx *c, const KsArgs &a) {
-    if constexpr (kF64) {
-        if (c->hc.ks_xi)
-            hipLaunchKernelGGL((k_keyswitch_split14<AR, true>), dim3(a.cnt * c->hc.k * 2), dim3(NttPlan<13>::NT), (size_t)ntt_lds_words(8192) * 8, c->stream, a.target, a.tstride,
-                               (const void *)a.key, (uint64_t *)c->ks_part, c->dc, a.galois, a.accmax);
-        else
-            hipLaunchKernelGGL((k_keyswitch_split14<AR>), dim3(a.cnt * c->hc.k * 2), dim3(NttPlan<13>::NT), (size_t)ntt_lds_words(8192) * 8, c->stream, a.target, a.tstride,
-                               (const void *)a.key, (uint64_t *)c->ks_part, c->dc, a.galois, a.accmax);
-        return true;
-    }
-    return false;
-}
-// N = 16384 in one launch: both halves per (ciphertext, output limb) workgroup (k_keyswitch_pair14); a.target = sigma(c1) for rotations
-template <bool XI, bool WHOLE> static void launch_pair14(cn_ctx *c, const KsArgs &a) {
-    if constexpr (kF64)
-        hipLaunchKernelGGL((k_keyswitch_pair14<AR, XI, WHOLE>), dim3(a.cnt * c->hc.k), dim3(NttPlan<13>::NT), PAIR14_LDS, c->stream, a.target, a.tstride, a.add0, a.add1, a.astride,
-                           (const void *)a.key, a.out, (double *)c->ks_part, c->dc, a.galois, a.accmax, a.extra, a.xstride, a.out_tab, a.perm_elt, a.next_elt, a.next_out, a.xcd_cts);
-}
-static bool pair14(cn_ctx *c, const KsArgs &a0) {
-    if constexpr (kF64) {
-        // lazy accumulators of THIS kernel: the forward half-transform (L = 13: five stages behind its one recentring) leaves |v| <= 4.82 q, a term
-        // mulmod(v, key) is then at most (1/2 + 0.1875 x 4.82) q = 1.41 q (cn_ntt_core.hip.h), and 2^53 / q >= 16 for q < 2^49: 8 terms (+ the q/2 a recentred
-        // accumulator starts from) stay below 11.8 q.  The generic bound of do_keyswitch (2.1 q per term, sum below 2^52) allows 2 at 49 bits: a recentring of
-        // both accumulator sets every other digit, 2 % of the kernel's FP64 instructions at the reference's N = 16384 parameters.
-        KsArgs a = a0;
-        const CnModRange qr = cn_mod_range(c->hc, 0, c->hc.k);
-        if (!qr.light && qr.bits <= 49) a.accmax = std::max(a.accmax, 1u << (52 - qr.bits));
-        // one digit per source limb that covers the limb (the reference's N = 16384 parameter sets, dbc 60): the digit is the word itself
-        const int dbc = a.galois ? c->hc.gdbc : c->hc.dbc;
-        const bool whole = (a.galois ? c->hc.gk_tot : c->hc.rl_tot) == c->hc.k && dbc < 64 && (qr.qmax >> dbc) == 0;
-        if (c->hc.ks_xi) { if (whole) launch_pair14<true, true>(c, a); else launch_pair14<true, false>(c, a); }
-        else { if (whole) launch_pair14<false, true>(c, a); else launch_pair14<false, false>(c, a); }
-        return true;
-    }
-    return false;
-}
 #ifndef __HIP_DEVICE_COMPILE__      // host-side table (in the device pass a const global would be emitted as device data)
-extern const KsOps KS_NAME = {set_attrs, launch, split14, pair14};
+extern const KsOps KS_NAME = {set_attrs, launch};
 #endif

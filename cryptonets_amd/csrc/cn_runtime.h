@@ -4,6 +4,7 @@
 #pragma once
 #include "../../include/cnhip.h"
 #include "cn_policy.h"
+#include "cn_ks_plan.h"
 #include "cn_submit.h"
 #include <hip/hip_runtime.h>
 #include <atomic>
@@ -256,7 +257,7 @@ struct cn_ctx {
 // (c0 at in, c1 behind it), the Galois key of its element, the element
 struct KsItem { const uint64_t *in; const void *key; uint32_t elt, pad; };
 // KsCall: the operands a caller of do_keyswitch names - by designated initialisers or through the constructors of the three shapes that occur; do_keyswitch
-// derives the rest of KsArgs (key words, accmax, mode, xcd_cts) and the launchers read both parts
+// adds the rest of KsArgs (key words, the plan of cn_ks_plan.h) and the launchers read both parts
 struct KsCall {
     const uint64_t *target = nullptr; size_t tstride = 0;
     const uint64_t *add0 = nullptr, *add1 = nullptr; size_t astride = 0;
@@ -290,9 +291,7 @@ struct KsCall {
 };
 struct KsArgs : KsCall {
     const uint64_t *key;
-    uint32_t accmax;          // FP64 accumulators: terms between recentrings
-    int mode;                 // 0 fused, 1 two launches / workgroup per digit, 2 two launches / workgroup per source limb
-    uint32_t xcd_cts = 0;     // fused kernel: ciphertexts (a multiple of 8) placed XCD-aware, see k_keyswitch_rr
+    KsPlan plan;              // form, accmax, xcd_cts, twl, whole (cn_ks_plan.h)
 };
 // k_encrypt_fold (cn_k_rr.hip.h): a scalar-product output that receives the weighted sum of `count` folded zero encryptions, and the terms of all outputs
 struct FoldOut { uint64_t *out; uint32_t first, count; };               // terms [first, first + count) of the term table
@@ -312,9 +311,7 @@ struct RrOps {                // register-radix kernels of one arithmetic policy
 };
 struct KsOps {
     int (*set_attrs)(uint32_t logn, size_t lds);
-    bool (*launch)(cn_ctx *c, const KsArgs &a);                        // fused / two-phase by a.mode
-    bool (*split14)(cn_ctx *c, const KsArgs &a);                       // N = 16384 as two 8192-point halves (FP64 policies), k_ks_combine14 behind it
-    bool (*pair14)(cn_ctx *c, const KsArgs &a);                        // N = 16384 in one launch: both halves per (ciphertext, limb) workgroup (FP64 policies)
+    bool (*launch)(cn_ctx *c, const KsArgs &a);                        // the kernels of a.plan.form; false: this policy (or ring size) has no instantiation of it
 };
 extern const RrOps cn_rr_u64, cn_rr_f64, cn_rr_f64l;
 extern const KsOps cn_ks_u64, cn_ks_f64, cn_ks_f64l;

@@ -1,8 +1,8 @@
 """cn_mul_relin (hot loop B) on every code path it can take, against the CPU oracle word for word.
 
 The library picks the path of a Multiply + Relinearize by the ciphertext count and the context's options: the key-switch variant
-(ks_planned_mode: fused kernel, two launches with a workgroup per digit, two launches with a workgroup per source limb; "ks_wide" forces
-one), and for >= 512 ciphertexts at N <= 8192 the batch in parts over the context's two streams ("sq_halves", pipelined_halves).  The
+(cn_ks_plan, cn_ks_plan.h: fused kernel, two launches with a workgroup per digit, two launches with a workgroup per source limb; "ks_wide"
+forces one), and for >= 512 ciphertexts at N <= 8192 the batch in parts over the context's two streams ("sq_halves", pipelined_halves).  The
 counts below sit on both sides of every threshold; each is derived from the number of limbs k and the block limits, not written out.
 Every result is compared with the oracle, never with another GPU setting.  "mul_relin_pipelined" reads back whether a call ran in parts:
 a deterministic check of which path was taken, independent of whether a race between the two streams happens to fire in one run.
@@ -17,8 +17,8 @@ from conftest import PARAMS, get_oracle
 
 pytestmark = pytest.mark.gpu
 
-KS_DIGIT_MAX_BLOCKS = 10      # (ciphertext, limb) blocks up to which the two-launch key switch has a workgroup per digit (cn_eval.hip: ks_digit_max_blocks)
-KS_WIDE_MAX_BLOCKS = 160      # ... up to which a key switch runs as two launches at all (ks_wide_max_blocks)
+KS_DIGIT_MAX_BLOCKS = 10      # (ciphertext, limb) blocks up to which the two-launch key switch has a workgroup per digit (cn_ks_plan.h: KsSwitches::digit_max_blocks)
+KS_WIDE_MAX_BLOCKS = 160      # ... up to which a key switch runs as two launches at all (KsSwitches::wide_max_blocks)
 SQ_HALVES_MIN = 512           # ciphertexts from which cn_mul_relin runs in parts over two streams (cn_api_shared.h)
 SETS = ("tiny", "c3")
 LARGEST = {"tiny": 700, "c3": 845}             # c3: the squaring layer of CryptoNets

@@ -8,7 +8,7 @@ test_square_gemm inside the reused helpers).  The helpers of the other modules a
 test_gpu_ptn looks its context up by name in conftest.PARAMS, so the row-dot family restates it here on the cell's own context - and compares every row with
 the oracle's chain, not only the first.
 
-FORM - which form of a call must run in a cell - is written by hand below from cn_policy.h and the launchers and asserted through the library's counters, so a
+FORM - which form of a call must run in a cell - is written by hand below from cn_policy.h, cn_ks_plan.h (the key switch: ks_form) and the launchers and asserted through the library's counters, so a
 silent fall-back cannot pass as coverage:
   kernel     the size-templated kernel (named in the rule)
   composed   other calls of the library do the work (named in the rule)
@@ -70,15 +70,15 @@ FP64 = ("f64", "f64l")
 
 
 def ks_form(policy, n, width, ks_wide):
-    """the kernels of one key switch (cn_l_ks.inc.h; do_keyswitch, cn_eval.hip) under "ks_wide" 0, 1, 2"""
+    """the kernels of one key switch (cn_ks_plan, cn_ks_plan.h; launched by cn_l_ks.inc.h) under "ks_wide" 0, 1, 2"""
     if ks_wide == 1:
         return "k_ks_digit_mac + k_ks_sum_intt"                     # launch_two_phase, a workgroup per digit
     if ks_wide == 2:
         return "k_ks_limb_mac + k_ks_sum_intt"                      # launch_two_phase, a workgroup per source limb
-    if n == 16384 and policy in FP64:                               # ks_pair14_ok; WHOLE: one digit per limb that covers the limb (pair14)
+    if n == 16384 and policy in FP64:                               # KS_PAIR14; KsPlan::whole: one digit per limb that covers the limb
         return "k_keyswitch_pair14<WHOLE>" if width == 60 else "k_keyswitch_pair14"
     if n <= 8192 and policy in FP64 and DIGITS[policy][width] >= 12:
-        return "k_keyswitch_rr<TWL>"                                # KsFwd<AR, L>::lds and KS_TWL_MIN_DIGITS = 12 (launch_fused_x)
+        return "k_keyswitch_rr<TWL>"                                # KsPlan::twl: KsFwd<AR, L>::lds and KS_TWL_MIN_DIGITS = 12
     return "k_keyswitch_rr"
 
 
