@@ -6,12 +6,15 @@
 //   cn_multi.hip   the key broadcast between contexts (RCCL)
 // How a scalar GEMM is planned - weight class, kernel form, pairing and grouping of gather lists, weight tiles, the device image - is decided in cn_gemm_plan.h
 // (host-only; included by the two units that plan: cn_eval.hip, and cn_defer.hip for the flush of queued scalar products).
+// What a flush of the deferred queue launches - the arrays a queued call reads, admission and the layer-boundary rule, the three queue rewrites, pending squarings,
+// parking, staging layout, the ordered steps - is decided in cn_defer_plan.h (host-only; the queue's types DOp and DeferQueue live there; cn_defer.hip does the device work).
 // Which arithmetic policy a modulus range takes and which ring sizes have the register-radix kernels is decided in cn_policy.h (cn_mod_range, cn_policy, cn_rr_size).
 // Everything here is internal: the C ABI is include/cnhip.h.  The element-wise kernels (cn_k_elem.hip.h) have internal linkage - every unit that launches one
 // carries its own copy.
 #pragma once
 #include "cn_runtime.h"
 #include "cn_rotation.h"
+#include "cn_defer_plan.h"
 #include <thread>
 #include "cn_k_elem.hip.h"
 #include <algorithm>
@@ -24,59 +27,11 @@
 #include <cstring>
 
 #define fail cn_fail
-struct DOp; struct DeferQueue; struct GemmPlan; struct GemmSwitches; struct Tab2; struct RotJob; struct BcastNext; struct Slab;
+struct GemmPlan; struct GemmSwitches; struct Tab2; struct RotJob; struct BcastNext; struct Slab;
 
 static const RrOps *const rr_ops[3] = {&cn_rr_u64, &cn_rr_f64, &cn_rr_f64l};
 static const KsOps *const ks_ops[3] = {&cn_ks_u64, &cn_ks_f64, &cn_ks_f64l};
 inline bool rr_kernels(const cn_ctx *c, uint32_t max_logn = 14) { return !c->opt.legacy_ntt && cn_rr_size(c->hc.logn, max_logn); }   // the context runs register-radix kernels
-enum { DOP_GEMM1 = 0, DOP_ADD, DOP_SUB, DOP_ADDPLAIN, DOP_SUBPLAIN, DOP_MULRELIN, DOP_ENCRYPT,
-       DOP_COPY, DOP_MULPLAIN, DOP_ROT, DOP_ROTADD, DOP_COLS, DOP_COLSADD, DOP_SUMSLOTS, DOP_TYPES };      // DOP_COPY .. : staged (gather / batched call / scatter) at flush time
-struct DOp {
-    int type; int32_t level;
-    uint64_t *out;                 // output ciphertext (size 2)
-    const uint64_t *a, *b;         // operands (ADD/SUB/MULRELIN: ciphertexts; ADDPLAIN/SUBPLAIN: b = plaintext polynomial)
-    uint32_t K; size_t terms;      // GEMM1: K (address, weight) pairs from DeferQueue::addr / ::wt [terms ..)
-    const uint64_t *bias;          // GEMM1: plaintext polynomial added to the result (an AddPlain folded in at flush time), or null
-    uint64_t nonce = 0, item = 0;  // ENCRYPT: the call's seed and the sampler item of this ciphertext (a = plaintext polynomial or null)
-    int64_t arg = 0;               // staged kinds: rotation steps (ROT, ROTADD) / slot count (SUMSLOTS); MULPLAIN: b = plaintext polynomial; ROTADD / COLSADD: b = accumulator
-    int32_t fold_first = -1; uint32_t fold_count = 0;   // GEMM1: terms [fold_first, +fold_count) of DeferQueue::folds - zero encryptions folded onto this output (cn_defer_flush)
-};
-struct DeferQueue {
-    std::vector<DOp> ops;
-    std::vector<uint64_t> addr, wt;
-    struct Haz { int32_t w = -1, r = -1, wop = -1; uint32_t readers = 0; int32_t hd = 0; };   // level of the last writer / deepest reader since / index of the writing op / readers since / heavy depth of the value (defer_push)
-    // address -> hazard record: open addressing, cleared by bumping the epoch (a dense-layer call touches 845 records)
-    struct HazMap {
-        struct E { const uint64_t *key = nullptr; uint32_t epoch = 0; Haz v; };
-        std::vector<E> tab = std::vector<E>(1 << 12);
-        uint32_t epoch = 1; size_t used = 0;
-        static size_t hash(const uint64_t *p) { uint64_t x = (uint64_t)p >> 8; x *= 0x9E3779B97F4A7C15ull; return (size_t)(x >> 20); }
-        Haz *find(const uint64_t *p) {
-            for (size_t i = hash(p) & (tab.size() - 1);; i = (i + 1) & (tab.size() - 1)) {
-                if (tab[i].epoch != epoch) return nullptr;
-                if (tab[i].key == p) return &tab[i].v;
-            }
-        }
-        Haz &operator[](const uint64_t *p) {
-            if (2 * (used + 1) > tab.size()) grow();
-            for (size_t i = hash(p) & (tab.size() - 1);; i = (i + 1) & (tab.size() - 1)) {
-                if (tab[i].epoch != epoch) { tab[i].key = p; tab[i].epoch = epoch; tab[i].v = Haz(); used++; return tab[i].v; }
-                if (tab[i].key == p) return tab[i].v;
-            }
-        }
-        void grow() {
-            std::vector<E> old; old.swap(tab);
-            tab.assign(old.size() * 2, E()); used = 0;
-            for (const E &e : old) if (e.epoch == epoch) (*this)[e.key] = e.v;
-        }
-        void clear() { used = 0; if (++epoch == 0) { for (E &e : tab) e.epoch = 0; epoch = 1; } }
-    } haz;
-    int32_t maxlevel = -1;
-    std::vector<std::pair<uint64_t *, size_t>> frees;      // arrays released by the caller while calls were pending: back to the pool after the flush
-    struct Fold { int32_t enc; uint64_t w; };               // a zero encryption (index of its DOp) folded into a scalar product with weight w (residue mod t)
-    std::vector<Fold> folds;
-    struct DeferSquare *sq = nullptr;                       // squarings whose relinearisation is held back for the next dense layer (below; cn_defer.hip)
-};
 // Small arrays (a per-ciphertext caller allocates every Ciphertext on its own: thousands of 640 KiB arrays per layer) are carved out of
 // slabs - one hipMalloc per SLAB_PIECES arrays, neighbours in the address space - and only ever travel between the handles and the pool;
 // the slabs themselves are released with the context.
@@ -260,14 +215,14 @@ int decrypt_phase(cn_ctx *ctx, Buffer *I, uint32_t ci, uint32_t count, uint64_t 
 DeferQueue *cn_defer_new();
 void cn_defer_delete(DeferQueue *q);
 bool cn_defer_pending(cn_ctx *ctx);
-int32_t defer_level(DeferQueue *q, const uint64_t *const *ins, uint32_t nin, const uint64_t *out);
-int defer_push(cn_ctx *ctx, DOp op, const uint64_t *const *ins, uint32_t nin);
-int flush_gemm_group(cn_ctx *ctx, DeferQueue *q, const std::vector<const DOp *> &ops, uint32_t K);
+DeferSwitches defer_switches(cn_ctx *ctx);                   // (cn_defer_plan.h; null: the environment switches alone)
+int defer_push(cn_ctx *ctx, DOp op);
+int flush_gemm_group(cn_ctx *ctx, DeferQueue *q, const std::vector<const DOp *> &ops, uint32_t K, const DeferSwitches &sw);
 int flush_elementwise_group(cn_ctx *ctx, const std::vector<const DOp *> &ops, int type);
-int flush_mulrelin_group(cn_ctx *ctx, const std::vector<const DOp *> &all, const std::map<const uint64_t *, size_t> *park = nullptr, int32_t level = 0);
+int flush_mulrelin_group(cn_ctx *ctx, const std::vector<const DOp *> &ops, bool sq);
 int ensure_stage(cn_ctx *ctx, size_t bytes);
 int copy_by_table(cn_ctx *ctx, const std::vector<Tab2> &tab, Tab2 *dtab, uint32_t words_per_item);
-int flush_staged_group(cn_ctx *ctx, const std::vector<const DOp *> &all, int type);
+int flush_staged_group(cn_ctx *ctx, const DeferStep &step, const DeferSwitches &sw);
 int defer_staged(cn_ctx *ctx, int type, CtSpan a, CtSpan b, CtSpan o, int64_t arg, const uint64_t *plain = nullptr, uint32_t pstride_words = 0);
 int flush_encrypt_group(cn_ctx *ctx, const std::vector<const DOp *> &ops);
 bool zero_fold_ok(cn_ctx *ctx);

@@ -16,64 +16,43 @@
 // full, and before every entry point that is not deferrable (cn_sync, downloads, rotations, key changes ...).  Results are the same
 // words as the immediate calls - every operation is exact modular arithmetic, batching changes no value.  Errors of a flush (HIP
 // failures) surface at the call that triggered it; argument errors are still reported by the call that made them.
-// A flush is triggered by demand (any entry point that needs results), by a full queue, and at LAYER BOUNDARIES, so that the device works on
-// one layer while the callers queue the next.  A boundary is recognised by the "heavy depth" of a value: 0 for anything that was not
-// produced by a queued call, and for fresh encryptions; a scalar product (DenseMatrixBySparseVectorMultiply) or a Multiply + Relinearize
-// produces depth 1 + the deepest of its inputs; additions, plaintext products, rotations and copies pass the depth of their inputs on.  A heavy call that would reach depth 2 reads
-// the result of another queued heavy call: the layer that produced it is complete (its callers have returned) - everything queued is
-// launched, if at least DEFER_FLUSH_MIN calls wait.  (Round 2 used the plain dependency level for this; with the literal padded taps -
-// encryption -> scalar product -> plain addition inside ONE layer - several caller threads interleave those levels and the layer was cut
-// into dozens of small launches: 0.47 of the batched rate at 4-32 threads against 0.84 at one.  Flushing whenever the stream had run dry
-// instead cut the first layers into 256-call pieces and lost the bias folding: 0.85 against 0.93.)
-static const size_t DEFER_FLUSH_MIN = 64, DEFER_MAX_OPS = 32768;
+// What a flush launches is decided in cn_defer_plan.h (host-only: admission and the layer-boundary rule, the three queue rewrites, pending squarings, parking, staging
+// layout, the ordered steps); this unit keeps the queue's plumbing and the device work.
 DeferQueue *cn_defer_new() { DeferQueue *q = new DeferQueue(); q->sq = new DeferSquare(); return q; }
 void cn_defer_delete(DeferQueue *q) { if (q) delete q->sq; delete q; }
 // (products whose relinearisation is held back count as pending work: an array released meanwhile waits in DeferQueue::frees for the flush that settles them)
 bool cn_defer_pending(cn_ctx *ctx) { return ctx->dq && (!ctx->dq->ops.empty() || !ctx->dq->sq->out.empty()); }
 
-int32_t defer_level(DeferQueue *q, const uint64_t *const *ins, uint32_t nin, const uint64_t *out) {
-    int32_t lv = 0;
-    for (uint32_t i = 0; i < nin; i++) {
-        if (!ins[i]) continue;
-        const DeferQueue::Haz *h = q->haz.find(ins[i]);
-        if (h) lv = std::max(lv, h->w + 1);
-    }
-    const DeferQueue::Haz *ho = q->haz.find(out);
-    if (ho) lv = std::max(lv, std::max(ho->w, ho->r) + 1);
-    return lv;
+// what the planner reads of the environment and of a context; null: the switches alone, all that admission reads.  The only reader of the three variables:
+// CN_DEFER_TRACE=1 one line per (flush, level), 2 also the host time of every flush; CN_DEFER_MERGE_GEMM=0, CN_DEFER_REL=0 (A/B)
+DeferSwitches defer_switches(cn_ctx *ctx) {
+    static const DeferSwitches env = [] {
+        auto num = [](const char *name, int unset) { const char *v = getenv(name); return v ? atoi(v) : unset; };
+        DeferSwitches s;
+        s.trace = num("CN_DEFER_TRACE", 0); s.merge_gemm = num("CN_DEFER_MERGE_GEMM", 1) != 0; s.rel = num("CN_DEFER_REL", 1) != 0;
+        return s; }();
+    DeferSwitches s = env;
+    if (!ctx) return s;
+    s.fold_zero = ctx->opt.fold_zero && zero_fold_ok(ctx); s.t_half = ctx->hc.t_half;
+    s.square_gemm = ctx->defer_square_gemm && square_gemm_ctx_ok(ctx) && ctx->rlk.d;
+    s.ctw2 = ctx->ctw2; s.n = ctx->hc.n; s.park_max = ctx->smax / 4;
+    return s;
 }
-// queue one operation; ins: the ciphertexts it reads
-int defer_push(cn_ctx *ctx, DOp op, const uint64_t *const *ins, uint32_t nin) {
+// queue one operation (what it reads: defer_reads)
+int defer_push(cn_ctx *ctx, DOp op) {
     DeferQueue *q = ctx->dq;
-    int32_t lv = defer_level(q, ins, nin, op.out);
-    const bool heavy = op.type == DOP_GEMM1 || op.type == DOP_MULRELIN;      // (rotations counted as heavy too was measured: the LoLa rows were cut into more, smaller
-                                                                               // launches - 388 instead of 309 per prime, 14.3 instead of 12.1 ms per image)
-    int32_t hd = 0;
-    for (uint32_t i = 0; i < nin; i++) if (ins[i]) { const DeferQueue::Haz *h = q->haz.find(ins[i]); if (h) hd = std::max(hd, h->hd); }
-    hd += heavy ? 1 : 0;
-    const bool full = q->ops.size() >= DEFER_MAX_OPS;
-    if (full || (heavy && hd >= 2 && q->ops.size() >= DEFER_FLUSH_MIN)) {
+    const DeferAdmit ad = defer_admit(*q, op, defer_switches(nullptr));
+    if (ad.flush) {
         // a layer boundary (or a full queue): launch what is queued, the callers go on queueing the next layer behind it
         std::vector<uint64_t> ta, tw;
         if (op.type == DOP_GEMM1) {                     // the terms of this call sit at the end of the term arrays: keep them over the flush
             ta.assign(q->addr.begin() + op.terms, q->addr.end()); tw.assign(q->wt.begin() + op.terms, q->wt.end());
             q->addr.resize(op.terms); q->wt.resize(op.terms);
         }
-        CHECK(cn_defer_flush(ctx, !full));
+        CHECK(cn_defer_flush(ctx, ad.flush == DEFER_FLUSH_BOUNDARY));
         if (op.type == DOP_GEMM1) { op.terms = 0; q->addr = ta; q->wt = tw; }
-        lv = 0; hd = heavy ? 1 : 0;
     }
-    op.level = lv;
-    const int32_t me = (int32_t)q->ops.size();
-    for (uint32_t i = 0; i < nin; i++) {
-        if (!ins[i]) continue;
-        DeferQueue::Haz &h = q->haz[ins[i]];
-        h.r = std::max(h.r, lv); h.readers++;
-    }
-    DeferQueue::Haz &ho = q->haz[op.out];
-    ho.w = lv; ho.r = -1; ho.wop = me; ho.readers = 0; ho.hd = hd;
-    q->maxlevel = std::max(q->maxlevel, lv);
-    q->ops.push_back(op);
+    defer_record(*q, op, ad);
     return 0;
 }
 
@@ -101,7 +80,7 @@ __global__ void k_add_plain_tab(const Tab3 *__restrict__ tab, const DevConsts *_
 }
 
 // all queued DenseMatrixBySparseVectorMultiply calls of one level with K terms each: ONE scalar GEMM over address tables
-int flush_gemm_group(cn_ctx *ctx, DeferQueue *q, const std::vector<const DOp *> &ops, uint32_t K) {
+int flush_gemm_group(cn_ctx *ctx, DeferQueue *q, const std::vector<const DOp *> &ops, uint32_t K, const DeferSwitches &sw) {
     const uint32_t O = (uint32_t)ops.size();
     // the calls' lists, contiguous: A[o][kk] = address of term kk of output o (0 = padded tap), Wt[o][kk] its weight
     std::vector<uint64_t> A((size_t)O * K), Wt((size_t)O * K), out(O), bias(O);
@@ -111,9 +90,8 @@ int flush_gemm_group(cn_ctx *ctx, DeferQueue *q, const std::vector<const DOp *> 
         out[o] = (uint64_t)ops[o]->out; bias[o] = (uint64_t)ops[o]->bias;
     }
     // (the gather lists are not paired here as cn_gemm_plan_create pairs them: end to end neutral, the pairing's host time at the head of a batch - profiles/r06_defer_pair_ab.txt)
-    static const bool rel_on = !(getenv("CN_DEFER_REL") && !atoi(getenv("CN_DEFER_REL")));        // 0 keeps the address tables (A/B)
     GemmAddressPlan R;
-    gemm_plan_addresses(ctx->hc, gemm_switches(ctx), A.data(), Wt.data(), out.data(), bias.data(), O, K, rel_on, R);
+    gemm_plan_addresses(ctx->hc, gemm_switches(ctx), A.data(), Wt.data(), out.data(), bias.data(), O, K, sw.rel, R);      // (CN_DEFER_REL=0 keeps the address tables, A/B)
     CHECK(ensure_scratch(ctx, al(R.image.size())));
     char *tables; CHECK(upload_tmp(ctx, R.image.data(), R.image.size(), &tables));
     GemmLaunch gl = gemm_launch(ctx, R.L, tables);
@@ -133,7 +111,7 @@ int flush_elementwise_group(cn_ctx *ctx, const std::vector<const DOp *> &ops, in
     return 0;
 }
 // ---- deferred squarings that feed the next dense layer (DeferSquare, cn_api_shared.h)
-static bool defer_trace() { static const bool on = getenv("CN_DEFER_TRACE") && atoi(getenv("CN_DEFER_TRACE")); return on; }
+static bool defer_trace() { static const bool on = defer_switches(nullptr).trace != 0; return on; }
 void defer_square_drop_plans(cn_ctx *ctx) {
     if (!ctx->dq || ctx->dq->sq->plans.empty()) return;
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
@@ -147,25 +125,13 @@ void defer_square_release(cn_ctx *ctx) {
     if (sq.arr) (void)hipFree(sq.arr);
     sq.arr = nullptr; sq.cap = 0; sq.out.clear(); sq.slot.clear();
 }
-// The squarings of one level at a layer-boundary flush keep their relinearisation back if every one of them is the last writer of its output array, nothing queued
-// reads that array, the caller has not released it, and the products fit the context's product array (a quarter of the scratch limit at most; the array is not grown
-// while a graph is alive).  Only the Multiply half runs: products into slots 0 .. n - 1, output array -> slot noted.  False: the caller relinearises them at once.
-// has the caller released the buffer that holds p?  (DeferQueue::frees lists whole buffers: an output may be an element of a handle of several ciphertexts)
-static bool in_freed(const std::map<const uint64_t *, size_t> &freed, const uint64_t *p) {
-    auto it = freed.upper_bound(p);
-    if (it == freed.begin()) return false;
-    --it;
-    return (const char *)p < (const char *)it->first + it->second;
-}
-static bool park_squarings(cn_ctx *ctx, DeferQueue *q, const std::vector<const DOp *> &ops, const std::map<const uint64_t *, size_t> &freed, int32_t level, int *rc) {
+// The squarings of one level at a layer-boundary flush that may keep their relinearisation back (defer_can_park) do so if the products fit the context's product array
+// (the array is not grown while a graph is alive).  Only the Multiply half runs: products into slots 0 .. n - 1, output array -> slot noted.  False: the caller
+// relinearises them at once.
+static bool park_squarings(cn_ctx *ctx, DeferQueue *q, const std::vector<const DOp *> &ops, const DeferReleased &released, const DeferSwitches &sw, int32_t level, int *rc) {
     DeferSquare &sq = *q->sq;
-    const size_t kn = (size_t)ctx->hc.k * ctx->hc.n, need = ops.size() * 3 * kn * 8;
-    if (!sq.out.empty() || need > ctx->smax / 4) return false;
-    std::unordered_map<const uint64_t *, int> seen;
-    for (const DOp *op : ops) {
-        const DeferQueue::Haz *h = q->haz.find(op->out);
-        if (!h || h->wop != (int32_t)(op - q->ops.data()) || h->readers || in_freed(freed, op->out) || seen[op->out]++) return false;
-    }
+    if (!defer_can_park(*q, ops, released, sw, !sq.out.empty())) return false;
+    const size_t kn = (size_t)ctx->hc.k * ctx->hc.n, need = ops.size() * sw.product_bytes();
     if (need > sq.cap) {
         if (ctx->capturing || ctx->graphs_alive) return false;
         if (hipStreamSynchronize(ctx->stream) != hipSuccess) { *rc = fail(CN_ERR_HIP, "hipStreamSynchronize failed"); return true; }
@@ -209,7 +175,6 @@ static int pending_materialise(cn_ctx *ctx, DeferSquare &sq, const std::vector<u
     if (defer_trace()) fprintf(stderr, "defer %p: materialises %u of %u pending products (one key switch each)\n", (void *)ctx, done, n);
     return 0;
 }
-struct SgGroup { int32_t level; SgPlan *plan; std::vector<const DOp *> rows; std::vector<int32_t> slot_of; };       // rows: the scalar products in the plan's output order; slot_of: renumbered slot -> slot
 // the plan of a dense layer on deferred squarings: found by (O, K, weights, renumbered slot pattern) or built (build_gemm_plan: validation, grouping, weight tiles,
 // GemmPlan::dig) and kept, its weights on the device.  `keep`: entries used since this tick belong to the flush at hand and are not evicted
 static SgPlan *sg_plan(cn_ctx *ctx, DeferSquare &sq, uint32_t O, uint32_t K, std::vector<uint64_t> &W, std::vector<int32_t> &cidx, uint64_t keep) {
@@ -245,76 +210,26 @@ static size_t sg_scratch(cn_ctx *ctx, const GemmPlan &P) {
     const size_t kn = (size_t)ctx->hc.k * ctx->hc.n;
     return al((size_t)P.O * 2 * kn * 8) + al((size_t)P.O * ctx->hc.rl_tot * ctx->hc.n * (P.dig_i32 ? 4 : 8)) + al((size_t)P.G * P.Kp * 4) + al((size_t)P.G * P.M * 4) + al((size_t)P.O * 8) + 8192;
 }
-// The decision of a flush that finds products pending (once, all or nothing): may every queued reader of a pending array run in cn_square_gemm's second half?
-//   (a) the caller has released every pending output array, (b) only scalar products read pending arrays - and those form groups (one level, one term count)
-//   whose plan passes square_gemm_fused_ok, with a bias on every output or on none, (c) every gathered term of such a scalar product is a pending array (and no zero
-//   encryption was folded onto it), (d) no queued call writes a pending array.
-// need[slot]: the product has to be relinearised if the answer is no - somebody reads its array or the caller still holds it.
-static bool sg_prepare(cn_ctx *ctx, DeferQueue *q, const std::vector<uint8_t> &dead, const std::map<const uint64_t *, size_t> &freed, std::vector<SgGroup> &groups,
-                       std::vector<int32_t> &sg_of, std::vector<uint8_t> &need) {
+// The device half of the decision about pending products (defer_pending_decide has rules (a)-(d) and the candidate groups): the plan of every group is found or built,
+// passes square_gemm_fused_ok and fits the scratch limits, and the group's biases are addressable - or the answer is no for all.  plans[g]: the plan of groups[g]
+static bool sg_prepare(cn_ctx *ctx, DeferQueue *q, const std::vector<uint8_t> &dead, const DeferReleased &released, const DeferSwitches &sw, std::vector<DeferSgGroup> &groups,
+                       std::vector<SgPlan *> &plans, std::vector<uint8_t> &need) {
     DeferSquare &sq = *q->sq;
-    const std::vector<DOp> &ops = q->ops;
-    const uint32_t n = (uint32_t)sq.out.size();
-    need.assign(n, 0);
-    bool ok = ctx->defer_square_gemm && square_gemm_ctx_ok(ctx) && ctx->rlk.d;
-    auto slot_of = [&](const uint64_t *p) -> int32_t { if (!p) return -1; auto it = sq.slot.find(p); return it == sq.slot.end() ? -1 : (int32_t)it->second; };
-    std::map<std::pair<int32_t, uint32_t>, std::vector<size_t>> cand;            // (level, term count) -> scalar products that read pending arrays
-    for (size_t x = 0; x < ops.size(); x++) {
-        if (dead[x]) continue;
-        const DOp &X = ops[x];
-        if (slot_of(X.out) >= 0) ok = false;                                         // (d)
-        if (X.type == DOP_GEMM1) {
-            uint32_t np = 0, other = 0;
-            for (uint32_t kk = 0; kk < X.K; kk++) {
-                const uint64_t *a = (const uint64_t *)q->addr[X.terms + kk];
-                if (!a) continue;
-                const int32_t s = slot_of(a);
-                if (s >= 0) { need[s] = 1; np++; } else other++;
-            }
-            if (!np) continue;
-            if (other || X.fold_count) ok = false;                                   // (c)
-            cand[{X.level, X.K}].push_back(x);
-            continue;
-        }
-        if (X.type == DOP_ENCRYPT) continue;                                         // (a = plaintext polynomial)
-        const bool b_plain = X.type == DOP_ADDPLAIN || X.type == DOP_SUBPLAIN || X.type == DOP_MULPLAIN;
-        for (const uint64_t *p : {X.a, b_plain ? nullptr : X.b}) { const int32_t s = slot_of(p); if (s >= 0) { need[s] = 1; ok = false; } }      // (b)
-    }
-    for (uint32_t s = 0; s < n; s++) if (!in_freed(freed, sq.out[s])) { need[s] = 1; ok = false; }      // (a)
-    if (!ok) return false;
+    if (!defer_pending_decide(*q, dead, released, sq.out, sq.slot, sw, need, groups)) return false;
     const uint64_t keep = sq.tick;
-    for (auto &kv : cand) {
-        const uint32_t K = kv.first.second, O = (uint32_t)kv.second.size();
-        SgGroup g; g.level = kv.first.first;
-        for (size_t x : kv.second) g.rows.push_back(&ops[x]);
-        // the key must not depend on the order in which the caller's threads issued the calls: rows by their weights, slots by first appearance
-        std::stable_sort(g.rows.begin(), g.rows.end(), [&](const DOp *x, const DOp *y) {
-            return std::lexicographical_compare(&q->wt[x->terms], &q->wt[x->terms] + K, &q->wt[y->terms], &q->wt[y->terms] + K); });
-        std::vector<uint64_t> W((size_t)O * K); std::vector<int32_t> cidx((size_t)O * K, -1), canon(n, -1);
-        for (uint32_t o = 0; o < O; o++) {
-            memcpy(&W[(size_t)o * K], &q->wt[g.rows[o]->terms], (size_t)K * 8);
-            for (uint32_t kk = 0; kk < K; kk++) {
-                const int32_t s = slot_of((const uint64_t *)q->addr[g.rows[o]->terms + kk]);
-                if (s < 0) continue;
-                if (canon[s] < 0) { canon[s] = (int32_t)g.slot_of.size(); g.slot_of.push_back(s); }
-                cidx[(size_t)o * K + kk] = canon[s];
-            }
-        }
-        g.plan = sg_plan(ctx, sq, O, K, W, cidx, keep);
-        if (!g.plan || !g.plan->ok || !square_gemm_fused_ok(ctx, g.plan->P) || sg_scratch(ctx, g.plan->P) > ctx->smax) return false;
-        if (sg_scratch(ctx, g.plan->P) > ctx->scap && ctx->graphs_alive) return false;       // (the scratch arena does not grow while a graph is alive)
-        uint64_t bbase = ~0ull;
-        for (const DOp *r : g.rows) { if ((r->bias != nullptr) != (g.rows[0]->bias != nullptr)) return false; if (r->bias) bbase = std::min(bbase, (uint64_t)r->bias); }
-        for (const DOp *r : g.rows) if (r->bias && ((((uint64_t)r->bias - bbase) & 255) || (((uint64_t)r->bias - bbase) >> 8) >= 0x7fffffffull)) return false;
-        for (size_t x : kv.second) sg_of[x] = (int32_t)groups.size();
-        groups.push_back(std::move(g));
+    for (DeferSgGroup &g : groups) {
+        SgPlan *plan = sg_plan(ctx, sq, (uint32_t)g.rows.size(), g.K, g.W, g.cidx, keep);
+        if (!plan || !plan->ok || !square_gemm_fused_ok(ctx, plan->P) || sg_scratch(ctx, plan->P) > ctx->smax) return false;
+        if (sg_scratch(ctx, plan->P) > ctx->scap && ctx->graphs_alive) return false;       // (the scratch arena does not grow while a graph is alive)
+        if (!g.bias_ok) return false;
+        plans.push_back(plan);
     }
     return true;
 }
 // one group in cn_square_gemm's second half: the GEMM over components 0 and 1 of the products (+ the folded bias) into a contiguous temporary, the digit GEMM into S,
 // one KsDigits key switch per output that adds the temporary and writes the callers' arrays through its output table (no scatter copy)
-static int sg_run(cn_ctx *ctx, DeferQueue *q, const SgGroup &g) {
-    const SgPlan &sp = *g.plan; const GemmPlan &P = sp.P;
+static int sg_run(cn_ctx *ctx, DeferQueue *q, const DeferSgGroup &g, const SgPlan &sp) {
+    const GemmPlan &P = sp.P;
     const uint32_t n = ctx->hc.n, k = ctx->hc.k, tot = ctx->hc.rl_tot;
     const size_t kn = (size_t)k * n;
     std::vector<int32_t> pidx(sp.idx.size()), bidx(sp.oidx.size(), 0);
@@ -344,15 +259,11 @@ static int sg_run(cn_ctx *ctx, DeferQueue *q, const SgGroup &g) {
     return 0;
 }
 
-// all queued Multiply + Relinearize calls of one level: the batched BEHZ pipeline + ONE key switch, operands and results through tables
-// park (a layer-boundary flush, cn_set_option "defer_square_gemm"): the squarings may keep their relinearisation back (park_squarings)
-int flush_mulrelin_group(cn_ctx *ctx, const std::vector<const DOp *> &all, const std::map<const uint64_t *, size_t> *park, int32_t level) {
+// the queued squarings (SquareActivation: the fused kernel) or the queued general products (separate launches) of one level, as the schedule splits them: the batched
+// BEHZ pipeline + ONE key switch, operands and results through tables
+int flush_mulrelin_group(cn_ctx *ctx, const std::vector<const DOp *> &ops, bool sq) {
     const size_t kn = (size_t)ctx->hc.k * ctx->hc.n;
-    for (int sq = 1; sq >= 0; sq--) {                    // squarings (SquareActivation) take the fused kernel; general products the separate launches
-        std::vector<const DOp *> ops;
-        for (const DOp *op : all) if ((op->a == op->b) == (sq == 1)) ops.push_back(op);
-        if (ops.empty()) continue;
-        if (sq && park) { int rc = 0; if (park_squarings(ctx, ctx->dq, ops, *park, level, &rc)) { CHECK(rc); continue; } }
+    {
         const size_t per = mul_scratch_per_ct(ctx, sq == 1) + al(3 * kn * 8) + 3 * 8 + 64;
         const uint32_t ch = chunk_for(ctx, per, (uint32_t)ops.size());
         for (uint32_t s0 = 0; s0 < ops.size(); s0 += ch) {
@@ -415,68 +326,54 @@ int copy_by_table(cn_ctx *ctx, const std::vector<Tab2> &tab, Tab2 *dtab, uint32_
     HIPCHK(hipGetLastError()); launch_count(ctx);
     return 0;
 }
-int flush_staged_group(cn_ctx *ctx, const std::vector<const DOp *> &all, int type) {
-    if (type == DOP_COPY) {                                  // Ciphertext copies: the table copy is the operation
-        CHECK(ensure_stage(ctx, al(all.size() * sizeof(Tab2))));
-        std::vector<Tab2> tab(all.size());
-        for (size_t i = 0; i < all.size(); i++) tab[i] = {(const NTT_GLOBAL uint64_t *)all[i]->a, (NTT_GLOBAL uint64_t *)all[i]->out};
+static_assert(sizeof(Tab2) == DEFER_TAB2_BYTES, "defer_staged_layout sizes the copy tables");
+// one step of a staged kind, as the schedule cuts them: all copies of a level, few rotations by any step counts, or the calls of one kind and one argument
+int flush_staged_group(cn_ctx *ctx, const DeferStep &step, const DeferSwitches &sw) {
+    const std::vector<const DOp *> &ops = step.ops;
+    const int type = step.type;
+    if (step.kind == DSTEP_COPY) {                           // Ciphertext copies: the table copy is the operation
+        CHECK(ensure_stage(ctx, al(ops.size() * sizeof(Tab2))));
+        std::vector<Tab2> tab(ops.size());
+        for (size_t i = 0; i < ops.size(); i++) tab[i] = {(const NTT_GLOBAL uint64_t *)ops[i]->a, (NTT_GLOBAL uint64_t *)ops[i]->out};
         return copy_by_table(ctx, tab, (Tab2 *)ctx->stage, (uint32_t)ctx->ctw2);
     }
-    if (type == DOP_ROT && ks_few_rotations(ctx->hc, ks_switches(ctx), all.size())) {     // few rotations, any step counts: one launch chain per hop round
-        std::vector<RotJob> jobs(all.size());
-        for (size_t i = 0; i < all.size(); i++) jobs[i] = {all[i]->a, all[i]->out, (int)all[i]->arg};
+    if (step.kind == DSTEP_ROT_JOBS) {                       // few rotations, any step counts: one launch chain per hop round
+        std::vector<RotJob> jobs(ops.size());
+        for (size_t i = 0; i < ops.size(); i++) jobs[i] = {ops[i]->a, ops[i]->out, (int)ops[i]->arg};
         return rotate_jobs(ctx, jobs);
     }
-    std::map<int64_t, std::vector<const DOp *>> by_arg;      // one batched call per parameter value (rotation steps, slot count)
-    for (const DOp *op : all) by_arg[op->arg].push_back(op);
-    const uint32_t n = ctx->hc.n; const size_t ctw = ctx->ctw2;
-    for (auto &kv : by_arg) {
-        const std::vector<const DOp *> &ops = kv.second;
-        const uint32_t cnt = (uint32_t)ops.size();
-        const bool has_b = type == DOP_ROTADD || type == DOP_COLSADD, has_p = type == DOP_MULPLAIN, in_place = type == DOP_SUMSLOTS;
-        const size_t tabs = al(3 * cnt * sizeof(Tab2)) + al(cnt * sizeof(Tab2)), ctb = al(cnt * ctw * 8);
-        CHECK(ensure_stage(ctx, tabs + ctb * (1 + (has_b ? 1 : 0) + (in_place ? 0 : 1)) + (has_p ? al((size_t)cnt * n * 8) : 0)));
-        char *base = ctx->stage;
-        Tab2 *t_in = (Tab2 *)base, *t_pt = t_in + 2 * cnt, *t_out = (Tab2 *)(base + al(3 * cnt * sizeof(Tab2)));
-        uint64_t *A = (uint64_t *)(base + tabs), *B = has_b ? A + ctb / 8 : nullptr;
-        uint64_t *O = in_place ? A : A + (ctb / 8) * (has_b ? 2 : 1), *P = has_p ? O + ctb / 8 : nullptr;
-        // an operand whose addresses are equally spaced already IS the array the batched implementation wants (always so for a single call -
-        // 12 rotations by 12 different step counts are 12 groups of one): it is used in place; only scattered operands are gathered
-        auto spaced = [&](auto get, size_t words) { for (uint32_t i = 1; i < cnt; i++) if (get(ops[i]) != get(ops[0]) + (size_t)i * words) return false; return true; };
-        // MultiplyPlain of ONE ciphertext by the plaintexts of several rows (the per-row DotProduct of a dense layer: every row multiplies the same vector): the broadcast form -
-        // the ciphertext is transformed once, not once per row, and nothing is gathered (round 6)
-        bool same_a = has_p && cnt >= 2;
-        for (uint32_t i = 1; i < cnt && same_a; i++) same_a = ops[i]->a == ops[0]->a;
-        for (uint32_t i = 0; i < cnt && same_a; i++) same_a = (const uint64_t *)ops[i]->out != ops[0]->a;      // (the shared operand is nobody's result)
-        const bool da = same_a || spaced([](const DOp *o) { return o->a; }, ctw), db = has_b && spaced([](const DOp *o) { return o->b; }, ctw),
-                   dp = has_p && spaced([](const DOp *o) { return o->b; }, n), dout = spaced([](const DOp *o) { return (const uint64_t *)o->out; }, ctw);
-        std::vector<Tab2> gin, gpt, gout;
-        for (uint32_t i = 0; i < cnt; i++) {
-            if (!da) gin.push_back({(const NTT_GLOBAL uint64_t *)ops[i]->a, (NTT_GLOBAL uint64_t *)(A + (size_t)i * ctw)});
-            if (has_b && !db) gin.push_back({(const NTT_GLOBAL uint64_t *)ops[i]->b, (NTT_GLOBAL uint64_t *)(B + (size_t)i * ctw)});
-            if (has_p && !dp) gpt.push_back({(const NTT_GLOBAL uint64_t *)ops[i]->b, (NTT_GLOBAL uint64_t *)(P + (size_t)i * n)});
-            if (!dout) gout.push_back({(const NTT_GLOBAL uint64_t *)(O + (size_t)i * ctw), (NTT_GLOBAL uint64_t *)ops[i]->out});
-        }
-        if (in_place && da != dout) return fail(CN_ERR_ARG, "internal: in-place staged call with different operand and result addresses");
-        if (da) A = const_cast<uint64_t *>(ops[0]->a);
-        if (db) B = const_cast<uint64_t *>(ops[0]->b);
-        if (dp) P = const_cast<uint64_t *>(ops[0]->b);
-        if (dout) O = ops[0]->out;
-        if (!gin.empty()) CHECK(copy_by_table(ctx, gin, t_in, (uint32_t)ctw));
-        if (!gpt.empty()) CHECK(copy_by_table(ctx, gpt, t_pt, n));
-        const CtSpan sa{A, same_a ? 1u : cnt}, sb{B, cnt}, so{O, cnt};
-        int rc = 0;
-        switch (type) {
-        case DOP_MULPLAIN: rc = mul_plain_impl(ctx, sa, same_a, PtSpan{P, 1, nullptr}, so, 2); break;      // (zero plaintexts were refused when the calls were queued)
-        case DOP_ROT: rc = rotate_rows_impl(ctx, sa, (int)kv.first, so); break;
-        case DOP_ROTADD: rc = rotate_rows_add_impl(ctx, sa, (int)kv.first, sb, so); break;
-        case DOP_COLS: case DOP_COLSADD: rc = galois_impl(ctx, sa, 2ull * n - 1, sb, so); break;
-        case DOP_SUMSLOTS: rc = sum_slots_impl(ctx, sa, (uint32_t)kv.first); break;
-        default: rc = fail(CN_ERR_ARG, "internal: staged kind %d", type);
-        }
-        CHECK(rc);
-        if (!gout.empty()) CHECK(copy_by_table(ctx, gout, t_out, (uint32_t)ctw));
+    // one batched call: operands the callers hold equally spaced are used in place, the others gathered into the staging arena (defer_staged_layout)
+    const uint32_t n = ctx->hc.n, cnt = (uint32_t)ops.size(); const size_t ctw = ctx->ctw2;
+    const DeferStaged L = defer_staged_layout(type, ops, sw);
+    if (!L.consistent) return fail(CN_ERR_ARG, "internal: in-place staged call with different operand and result addresses");
+    CHECK(ensure_stage(ctx, L.total));
+    char *base = ctx->stage;
+    Tab2 *t_in = (Tab2 *)(base + L.off_tin), *t_pt = (Tab2 *)(base + L.off_tpt), *t_out = (Tab2 *)(base + L.off_tout);
+    uint64_t *A = L.a_direct ? const_cast<uint64_t *>(ops[0]->a) : (uint64_t *)(base + L.off_a);
+    uint64_t *B = !L.has_b ? nullptr : L.b_direct ? const_cast<uint64_t *>(ops[0]->b) : (uint64_t *)(base + L.off_b);
+    uint64_t *P = !L.has_p ? nullptr : L.p_direct ? const_cast<uint64_t *>(ops[0]->b) : (uint64_t *)(base + L.off_p);
+    uint64_t *O = L.out_direct ? ops[0]->out : (uint64_t *)(base + L.off_o);
+    std::vector<Tab2> gin, gpt, gout;
+    for (uint32_t i = 0; i < cnt; i++) {
+        if (!L.a_direct) gin.push_back({(const NTT_GLOBAL uint64_t *)ops[i]->a, (NTT_GLOBAL uint64_t *)(A + (size_t)i * ctw)});
+        if (L.has_b && !L.b_direct) gin.push_back({(const NTT_GLOBAL uint64_t *)ops[i]->b, (NTT_GLOBAL uint64_t *)(B + (size_t)i * ctw)});
+        if (L.has_p && !L.p_direct) gpt.push_back({(const NTT_GLOBAL uint64_t *)ops[i]->b, (NTT_GLOBAL uint64_t *)(P + (size_t)i * n)});
+        if (!L.out_direct) gout.push_back({(const NTT_GLOBAL uint64_t *)(O + (size_t)i * ctw), (NTT_GLOBAL uint64_t *)ops[i]->out});
     }
+    if (!gin.empty()) CHECK(copy_by_table(ctx, gin, t_in, (uint32_t)ctw));
+    if (!gpt.empty()) CHECK(copy_by_table(ctx, gpt, t_pt, n));
+    const CtSpan sa{A, L.same_a ? 1u : cnt}, sb{B, cnt}, so{O, cnt};
+    int rc = 0;
+    switch (type) {
+    case DOP_MULPLAIN: rc = mul_plain_impl(ctx, sa, L.same_a, PtSpan{P, 1, nullptr}, so, 2); break;      // (zero plaintexts were refused when the calls were queued)
+    case DOP_ROT: rc = rotate_rows_impl(ctx, sa, (int)step.key, so); break;
+    case DOP_ROTADD: rc = rotate_rows_add_impl(ctx, sa, (int)step.key, sb, so); break;
+    case DOP_COLS: case DOP_COLSADD: rc = galois_impl(ctx, sa, 2ull * n - 1, sb, so); break;
+    case DOP_SUMSLOTS: rc = sum_slots_impl(ctx, sa, (uint32_t)step.key); break;
+    default: rc = fail(CN_ERR_ARG, "internal: staged kind %d", type);
+    }
+    CHECK(rc);
+    if (!gout.empty()) CHECK(copy_by_table(ctx, gout, t_out, (uint32_t)ctw));
     return 0;
 }
 // queue `count` per-ciphertext operations of a staged kind (arguments were checked by the caller)
@@ -485,8 +382,7 @@ int defer_staged(cn_ctx *ctx, int type, CtSpan a, CtSpan b, CtSpan o, int64_t ar
         const uint64_t *pa = a.d + c * ctx->ctw2, *pb = b.d ? b.d + c * ctx->ctw2 : nullptr;
         DOp op{type, 0, o.d + c * ctx->ctw2, pa, plain ? plain + (size_t)c * pstride_words : pb, 0, 0, nullptr};
         op.arg = arg;
-        const uint64_t *ins[2] = {pa, pb};
-        CHECK(defer_push(ctx, op, ins, 2));
+        CHECK(defer_push(ctx, op));
     }
     return 0;
 }
@@ -574,185 +470,68 @@ int defer_encrypt(cn_ctx *ctx, const uint64_t *ptd, uint32_t pt_stride_words, Bu
     for (uint32_t c = 0; c < count; c++) {
         DOp op{DOP_ENCRYPT, 0, O->d + (size_t)(oi + c) * O->item_words, ptd ? ptd + (size_t)c * pt_stride_words : nullptr, nullptr, 0, 0, nullptr};
         op.nonce = seed; op.item = ctx->rng_item++;
-        CHECK(defer_push(ctx, op, nullptr, 0));
+        CHECK(defer_push(ctx, op));
     }
     return 0;
 }
 
+// CN_DEFER_TRACE: one line per (flush, level) - calls per kind with the number of their arguments, launches (the steps of the level begin at steps[first])
+static void defer_trace_level(cn_ctx *ctx, int32_t lv, const std::vector<DeferStep> &steps, size_t first, uint64_t l0) {
+    size_t calls[DOP_TYPES] = {}; std::map<int64_t, int> args[DOP_TYPES];
+    for (size_t i = first; i < steps.size() && steps[i].level == lv; i++) {
+        if (steps[i].kind == DSTEP_ZERO_FOLD) continue;      // (its scalar products are counted with their own step)
+        for (const DOp *op : steps[i].ops) { calls[op->type]++; args[op->type][op->arg]++; }
+    }
+    char line[512]; int o = snprintf(line, sizeof line, "defer %p level %d:", (void *)ctx, lv);
+    for (int t = 0; t < DOP_TYPES; t++) if (calls[t]) o += snprintf(line + o, sizeof line - o, " kind%d x%zu (%zu args)", t, calls[t], args[t].size());
+    fprintf(stderr, "%s -> %llu launches\n", line, (unsigned long long)(ctx->st.kernel_launches - l0));
+}
+// the flush: the planner's rewrites and steps (cn_defer_plan.h), one batched launch chain per step
 int cn_defer_flush(cn_ctx *ctx, bool boundary) {
     DeferQueue *q = ctx->dq;
     if (!q) return 0;
     int rc = 0;
     DeferSquare &sqs = *q->sq;
+    const bool work = !q->ops.empty() || !sqs.out.empty();
+    const DeferSwitches sw = defer_switches(work ? ctx : nullptr);      // (every locked entry point comes through here: an empty queue reads nothing of the context)
     // CN_DEFER_TRACE=2: host time of every flush (the flush runs on the thread of the call that triggered it, under the context lock: every other caller of the
     // context waits for it, and so does the device if it has run dry)
-    static const bool timing = getenv("CN_DEFER_TRACE") && atoi(getenv("CN_DEFER_TRACE")) >= 2;
     struct FlushTimer { bool on; size_t nops; cn_ctx *c; std::chrono::steady_clock::time_point t0; ~FlushTimer() {
         if (on && nops) fprintf(stderr, "defer %p flush of %zu calls: %.0f us of host time\n", (void *)c, nops,
                                 1e6 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()); } }
-        ft{timing, q->ops.size(), ctx, std::chrono::steady_clock::now()};
-    if (!q->ops.empty() || !sqs.out.empty()) {
-        std::vector<DOp> &ops = q->ops;
-        // ---- an AddPlain that only adds the bias to a DenseMatrixBySparseVectorMultiply result the caller has already released
-        // (PoolLayer.cs:184-186: `using (conv = ConvolveOnce(..)) res[k] = conv.Add(bias)`) is folded into the GEMM's epilogue - the GEMM
-        // then runs at the AddPlain's level and writes its output: safe when nothing else reads the intermediate and no later call
-        // overwrites the GEMM's inputs
-        std::vector<uint8_t> dead(ops.size(), 0);
-        std::unordered_map<const uint64_t *, int> freed;
-        for (auto &f : q->frees) freed[f.first] = 1;
-        {
-            for (size_t x = 0; x < ops.size(); x++) {
-                DOp &X = ops[x];
-                if (X.type != DOP_ADDPLAIN || X.a == X.out) continue;
-                const DeferQueue::Haz *hi = q->haz.find(X.a);
-                // the recorded writer must be the op that PRODUCED X's operand: a handle reused as the output of a later call has its last
-                // writer BEHIND X (GEMM1 -> tmp, AddPlain(tmp) -> r1, GEMM2 -> tmp ...: folding GEMM2 into the first AddPlain would be wrong)
-                if (!hi || hi->wop < 0 || hi->wop >= (int32_t)x || hi->readers != 1 || !freed.count(X.a)) continue;
-                if (ops[hi->wop].level >= X.level) continue;
-                DOp &Gm = ops[hi->wop];
-                if (Gm.type != DOP_GEMM1 || Gm.bias || Gm.out != X.a || dead[hi->wop]) continue;
-                bool ok = true;
-                for (uint32_t kk = 0; kk < Gm.K && ok; kk++) {
-                    const uint64_t *in = (const uint64_t *)q->addr[Gm.terms + kk];
-                    if (!in) continue;
-                    const DeferQueue::Haz *h2 = q->haz.find(in);
-                    if (h2 && h2->wop > hi->wop) ok = false;
-                }
-                if (!ok) continue;
-                Gm.out = X.out; Gm.bias = X.b; Gm.level = X.level;
-                dead[x] = 1;
-            }
-        }
-        // ---- fresh encryptions of ZERO that only feed one queued scalar product and have been released (PoolLayer.ElementAt / ReleaseTemp, PoolLayer.cs:67-90) are
-        // not materialised: their weighted sum is folded onto the scalar product's output by linearity (k_encrypt_fold: same words, a fifth of the transforms, the
-        // scalar product reads no extra ciphertexts and the outputs of a border patch share their gather list again).  Conditions, all on whole arrays: the
-        // encryption is the last writer of its array, exactly one queued call reads it - a scalar product on a deeper level - and the caller has released it.
-        if (ctx->opt.fold_zero && zero_fold_ok(ctx)) {
-            std::unordered_map<const uint64_t *, int32_t> cand;
-            size_t zero_encs = 0;
-            for (size_t x = 0; x < ops.size(); x++) {
-                const DOp &E = ops[x];
-                if (dead[x] || E.type != DOP_ENCRYPT || E.a) continue;
-                zero_encs++;
-                const DeferQueue::Haz *h = q->haz.find(E.out);
-                if (h && h->wop == (int32_t)x && h->readers == 1 && freed.count(E.out)) cand[E.out] = (int32_t)x;
-            }
-            // all or nothing: a caller that parks its releases (cn_free_many of 32 at a time, the locked twin of rounds 3-5) leaves some of a layer's zero vectors alive at
-            // the flush - folding the rest would run BOTH chains (samplers + k_encrypt_fused for the live ones, samplers + k_encrypt_fold for the others) and cut the scalar
-            // products of a layer into more gather groups: 17.4 against 15.8 ms per batch (profiles/r06_bench_default_flags.json, `locked`)
-            if (cand.size() != zero_encs) cand.clear();
-            const uint64_t t_half = ctx->hc.t_half, max_terms = (1ull << 52) / std::max<uint64_t>(1, t_half * 20);
-            if (!cand.empty()) for (size_t x = 0; x < ops.size(); x++) {
-                DOp &G = ops[x];
-                if (dead[x] || G.type != DOP_GEMM1 || G.level == 0) continue;
-                uint32_t nf = 0, left = 0;
-                for (uint32_t kk = 0; kk < G.K; kk++) {
-                    const uint64_t a = q->addr[G.terms + kk];
-                    if (!a) continue;
-                    auto it = cand.find((const uint64_t *)a);
-                    if (it != cand.end() && ops[it->second].level < G.level) nf++; else if (q->wt[G.terms + kk]) left++;
-                }
-                if (!nf || !left || nf > max_terms) continue;              // (a scalar product keeps at least one real term: its launch writes the output the fold adds onto)
-                G.fold_first = (int32_t)q->folds.size();
-                for (uint32_t kk = 0; kk < G.K; kk++) {
-                    const uint64_t a = q->addr[G.terms + kk];
-                    if (!a) continue;
-                    auto it = cand.find((const uint64_t *)a);
-                    if (it == cand.end() || ops[it->second].level >= G.level) continue;
-                    if (q->wt[G.terms + kk]) { q->folds.push_back({it->second, q->wt[G.terms + kk]}); G.fold_count++; }      // (weight 0: the term contributes nothing, AtomicSealBfvVector.cs:468)
-                    q->addr[G.terms + kk] = 0; q->wt[G.terms + kk] = 0;
-                    dead[it->second] = 2;
-                    cand.erase(it);
-                }
-                ctx->folded_zero += nf;
-            }
-        }
-        // ---- scalar products of one term count on different levels of the same flush become ONE launch where nothing stands in the way (round 5).  The
-        // literal PoolLayer pattern puts the outputs that read a fresh encryption of zero (a padded tap) one level behind the others: two GEMM launches per
-        // convolution, the second one a fifth the size and barely half as efficient (k_scalar_gemm<1>: 0.30 ms for 125 outputs against 0.50 ms for 720).
-        // A scalar product may wait for the deepest level that holds others of its kind if, behind its own level, nobody reads or writes its output and
-        // nobody writes its inputs (checked against every queued call, conservatively: any later level counts).  CN_DEFER_MERGE_GEMM=0 switches it off (A/B).
-        static const bool merge_gemm = !(getenv("CN_DEFER_MERGE_GEMM") && !atoi(getenv("CN_DEFER_MERGE_GEMM")));
-        if (merge_gemm) {
-            std::map<uint32_t, std::pair<int32_t, int32_t>> span;          // term count -> (shallowest, deepest) level of its live scalar products
-            for (size_t x = 0; x < ops.size(); x++) if (!dead[x] && ops[x].type == DOP_GEMM1) {
-                auto it = span.find(ops[x].K);
-                if (it == span.end()) span[ops[x].K] = {ops[x].level, ops[x].level};
-                else { it->second.first = std::min(it->second.first, ops[x].level); it->second.second = std::max(it->second.second, ops[x].level); }
-            }
-            bool any = false;
-            for (auto &kv : span) any = any || kv.second.first != kv.second.second;
-            if (any) {
-                struct RW { int32_t r = -1, w = -1; };                      // deepest level at which a queued call reads / writes the array
-                std::unordered_map<const uint64_t *, RW> touch;
-                touch.reserve(ops.size() * 2);
-                auto rd = [&](const uint64_t *p, int32_t lv) { if (p) { RW &t = touch[p]; t.r = std::max(t.r, lv); } };
-                for (size_t x = 0; x < ops.size(); x++) {
-                    if (dead[x]) continue;
-                    const DOp &X = ops[x];
-                    if (X.type == DOP_GEMM1) { for (uint32_t kk = 0; kk < X.K; kk++) rd((const uint64_t *)q->addr[X.terms + kk], X.level); }
-                    else if (X.type == DOP_ADDPLAIN || X.type == DOP_SUBPLAIN || X.type == DOP_MULPLAIN) rd(X.a, X.level);      // (b is a plaintext: never the output of a queued call)
-                    else if (X.type != DOP_ENCRYPT) { rd(X.a, X.level); rd(X.b, X.level); }
-                    RW &t = touch[X.out]; t.w = std::max(t.w, X.level);
-                }
-                for (size_t x = 0; x < ops.size(); x++) {
-                    DOp &X = ops[x];
-                    if (dead[x] || X.type != DOP_GEMM1) continue;
-                    const int32_t deep = span[X.K].second;
-                    if (X.level >= deep) continue;
-                    const RW &to = touch[X.out];
-                    bool ok = to.r <= X.level && to.w <= X.level;
-                    for (uint32_t kk = 0; kk < X.K && ok; kk++) {
-                        const uint64_t *in = (const uint64_t *)q->addr[X.terms + kk];
-                        if (in) { auto it = touch.find(in); ok = it == touch.end() || it->second.w <= X.level; }
-                    }
-                    if (ok) X.level = deep;
-                }
-            }
-        }
-        // ---- products whose relinearisation an earlier layer-boundary flush held back: the scalar products that read them run in cn_square_gemm's second half (at their
+        ft{sw.trace >= 2, q->ops.size(), ctx, std::chrono::steady_clock::now()};
+    if (work) {
+        const DeferReleased released(q->frees);
+        std::vector<uint8_t> dead(q->ops.size(), 0);
+        defer_fold_bias(*q, dead, released);
+        ctx->folded_zero += defer_fold_zero(*q, dead, released, sw);
+        defer_merge_gemm(*q, dead, sw);
+        // products whose relinearisation an earlier layer-boundary flush held back: the scalar products that read them run in cn_square_gemm's second half (at their
         // level, below), or every product is relinearised into its own array first and the flush proceeds as ever
-        std::vector<int32_t> sg_of(ops.size(), -1);
-        std::vector<SgGroup> sgs;
-        std::map<const uint64_t *, size_t> freed_rng;            // released buffers as address ranges
-        for (auto &f : q->frees) freed_rng[f.first] = f.second;
-        int32_t sg_deepest = -1;
+        std::vector<DeferSgGroup> sgs; std::vector<SgPlan *> plans;
         if (!sqs.out.empty()) {
             std::vector<uint8_t> need;
-            if (sg_prepare(ctx, q, dead, freed_rng, sgs, sg_of, need)) { for (const SgGroup &g : sgs) sg_deepest = std::max(sg_deepest, g.level); }
-            else { sgs.clear(); std::fill(sg_of.begin(), sg_of.end(), -1); rc = pending_materialise(ctx, sqs, need); }
+            if (!sg_prepare(ctx, q, dead, released, sw, sgs, plans, need)) { sgs.clear(); rc = pending_materialise(ctx, sqs, need); }
             sqs.out.clear(); sqs.slot.clear();              // (the groups carry the slots they read; released arrays without a reader just give their slots back)
         }
-        // ---- launches: level by level, one batched launch per kind (and per term count for the GEMMs)
-        const int32_t levels = q->maxlevel + 1;
-        static const bool trace = getenv("CN_DEFER_TRACE") && atoi(getenv("CN_DEFER_TRACE"));       // one line per (flush, level): calls per kind, launches
-        for (int32_t lv = 0; lv < levels && !rc; lv++) {
-            std::vector<const DOp *> by_type[DOP_TYPES];
-            for (size_t x = 0; x < ops.size(); x++) if (!dead[x] && ops[x].level == lv) by_type[ops[x].type].push_back(&ops[x]);
+        const std::vector<DeferStep> steps = defer_schedule(*q, dead, sgs, boundary, sw, [&](size_t count) { return ks_few_rotations(ctx->hc, ks_switches(ctx), count); });
+        size_t at = 0;
+        for (int32_t lv = 0; lv <= q->maxlevel && !rc; lv++) {
             const uint64_t l0 = ctx->st.kernel_launches;
-            struct Tr { cn_ctx *c; int32_t lv; uint64_t l0; std::vector<const DOp *> *bt; bool on; ~Tr() {
-                if (!on) return;
-                char line[512]; int o = snprintf(line, sizeof line, "defer %p level %d:", (void *)c, lv);
-                for (int t = 0; t < DOP_TYPES; t++) if (!bt[t].empty()) {
-                    std::map<int64_t, int> args; for (const DOp *op : bt[t]) args[op->arg]++;
-                    o += snprintf(line + o, sizeof line - o, " kind%d x%zu (%zu args)", t, bt[t].size(), args.size());
+            const size_t first = at;
+            for (; at < steps.size() && steps[at].level == lv && !rc; at++) {
+                const DeferStep &s = steps[at];
+                switch (s.kind) {
+                case DSTEP_GEMM: rc = flush_gemm_group(ctx, q, s.ops, (uint32_t)s.key, sw); break;
+                case DSTEP_FUSED: rc = sg_run(ctx, q, sgs[s.key], *plans[s.key]); break;
+                case DSTEP_ZERO_FOLD: rc = flush_zero_folds(ctx, q, s.ops); break;
+                case DSTEP_ELEMENTWISE: rc = flush_elementwise_group(ctx, s.ops, s.type); break;
+                case DSTEP_ENCRYPT: rc = flush_encrypt_group(ctx, s.ops); break;
+                case DSTEP_COPY: case DSTEP_ROT_JOBS: case DSTEP_STAGED: rc = flush_staged_group(ctx, s, sw); break;
+                case DSTEP_MULRELIN: if (!(s.park && park_squarings(ctx, q, s.ops, released, sw, lv, &rc))) rc = flush_mulrelin_group(ctx, s.ops, s.key == 1); break;
                 }
-                fprintf(stderr, "%s -> %llu launches\n", line, (unsigned long long)(c->st.kernel_launches - l0)); } } tr{ctx, lv, l0, by_type, trace};
-            if (!by_type[DOP_GEMM1].empty()) {
-                std::map<uint32_t, std::vector<const DOp *>> byK;
-                for (const DOp *op : by_type[DOP_GEMM1]) if (sg_of[op - ops.data()] < 0) byK[op->K].push_back(op);
-                for (auto &kv : byK) if (!rc) rc = flush_gemm_group(ctx, q, kv.second, kv.first);
-                for (const SgGroup &g : sgs) if (!rc && g.level == lv) rc = sg_run(ctx, q, g);
-                std::vector<const DOp *> folded;
-                for (const DOp *op : by_type[DOP_GEMM1]) if (op->fold_count) folded.push_back(op);
-                if (!rc && !folded.empty()) rc = flush_zero_folds(ctx, q, folded);
             }
-            for (int t : {DOP_ADD, DOP_SUB, DOP_ADDPLAIN, DOP_SUBPLAIN}) if (!rc && !by_type[t].empty()) rc = flush_elementwise_group(ctx, by_type[t], t);
-            if (!rc && !by_type[DOP_ENCRYPT].empty()) rc = flush_encrypt_group(ctx, by_type[DOP_ENCRYPT]);
-            for (int t = DOP_COPY; t <= DOP_SUMSLOTS; t++) if (!rc && !by_type[t].empty()) rc = flush_staged_group(ctx, by_type[t], t);
-            // (new products take the slots from 0: only behind the last group that still reads the old ones)
-            const bool park = boundary && ctx->defer_square_gemm && lv > sg_deepest && square_gemm_ctx_ok(ctx);
-            if (!rc && !by_type[DOP_MULRELIN].empty()) rc = flush_mulrelin_group(ctx, by_type[DOP_MULRELIN], park ? &freed_rng : nullptr, lv);
+            if (sw.trace) defer_trace_level(ctx, lv, steps, first, l0);
         }
     }
     if (rc) { sqs.out.clear(); sqs.slot.clear(); }          // an error drops the pending state with the queue
@@ -781,11 +560,6 @@ int scalar_dot_body(cn_ctx *ctx, const cn_handle *in, const uint32_t *in_idx, co
     if (oi >= O->count) return fail(CN_ERR_ARG, "index out of range");
     DeferQueue *q = ctx->dq;
     const size_t t0 = q->addr.size();
-    const uint64_t *ins_small[64];                           // (no heap allocation per call for the usual window sizes: 25 taps)
-    std::vector<const uint64_t *> ins_big;
-    const uint64_t **ins_p = ins_small;
-    if (K > 64) { ins_big.assign(K, nullptr); ins_p = ins_big.data(); } else for (uint32_t kk = 0; kk < K; kk++) ins_small[kk] = nullptr;
-    struct InsView { const uint64_t **p; const uint64_t *&operator[](uint32_t i) { return p[i]; } const uint64_t **data() { return p; } } ins{ins_p};
     bool any = false;
     uint64_t *o = O->d + (size_t)oi * O->item_words;
     uint64_t nnz = 0;
@@ -799,14 +573,14 @@ int scalar_dot_body(cn_ctx *ctx, const cn_handle *in, const uint32_t *in_idx, co
             if (!I || I->size != 2 || ii >= I->count) { q->addr.resize(t0); q->wt.resize(t0); return fail(CN_ERR_ARG, "invalid input ciphertext %u", kk); }
             const uint64_t *p = I->d + (size_t)ii * I->item_words;
             if (p == o) { q->addr.resize(t0); q->wt.resize(t0); return fail(CN_ERR_ARG, "scalar product cannot run in place"); }
-            a = (uint64_t)p; ins[kk] = p;                    // (a zero weight keeps its address: outputs that share a patch still share a gather list)
+            a = (uint64_t)p;                  // (a zero weight keeps its address: outputs that share a patch still share a gather list)
             if (wk) { any = true; nnz++; }                   // zero weights contribute nothing (AtomicSealBfvVector.cs:468 skips them)
         }
         q->addr.push_back(a); q->wt.push_back(a ? wk : 0);
     }
     if (!any) { q->addr.resize(t0); q->wt.resize(t0); return fail(CN_ERR_ARG, "output has no non-zero term (AddMany of nothing)"); }
     DOp op{DOP_GEMM1, 0, o, nullptr, nullptr, K, t0, nullptr};
-    CHECK(defer_push(ctx, op, ins.data(), K));
+    CHECK(defer_push(ctx, op));
     ctx->st.PlainMultiplication += nnz; ctx->st.Addition += nnz - 1;
     if (!deferring(ctx)) return cn_defer_flush(ctx);
     return 0;
@@ -821,8 +595,7 @@ int defer_addsub(cn_ctx *ctx, cn_handle a, uint32_t ai, cn_handle b, uint32_t bi
     if (A->size != 2) return 1;
     for (uint32_t c = 0; c < count; c++) {
         const uint64_t *pa = A->d + (size_t)(ai + c) * A->item_words, *pb = B->d + (size_t)(bi + c) * B->item_words;
-        const uint64_t *ins[2] = {pa, pb};
-        CHECK(defer_push(ctx, DOp{op ? DOP_SUB : DOP_ADD, 0, O->d + (size_t)(oi + c) * O->item_words, pa, pb, 0, 0, nullptr}, ins, 2));
+        CHECK(defer_push(ctx, DOp{op ? DOP_SUB : DOP_ADD, 0, O->d + (size_t)(oi + c) * O->item_words, pa, pb, 0, 0, nullptr}));
     }
     if (op) ctx->st.Subtraction += count; else ctx->st.Addition += count;
     return 0;
@@ -833,8 +606,7 @@ int defer_add_plain(cn_ctx *ctx, cn_handle a, uint32_t ai, cn_handle pt, uint32_
     if (A->size != 2) return 1;
     for (uint32_t c = 0; c < count; c++) {
         const uint64_t *pa = A->d + (size_t)(ai + c) * A->item_words;
-        const uint64_t *ins[1] = {pa};
-        CHECK(defer_push(ctx, DOp{subtract ? DOP_SUBPLAIN : DOP_ADDPLAIN, 0, O->d + (size_t)(oi + c) * O->item_words, pa, P->d + (size_t)(pi + c) * ctx->hc.n, 0, 0, nullptr}, ins, 1));
+        CHECK(defer_push(ctx, DOp{subtract ? DOP_SUBPLAIN : DOP_ADDPLAIN, 0, O->d + (size_t)(oi + c) * O->item_words, pa, P->d + (size_t)(pi + c) * ctx->hc.n, 0, 0, nullptr}));
     }
     if (subtract) ctx->st.PlainSubtraction += count; else ctx->st.PlainAddition += count;
     return 0;
@@ -846,8 +618,7 @@ int defer_mul_relin(cn_ctx *ctx, cn_handle a, uint32_t ai, uint32_t astride, cn_
     if (!ctx->rlk.d) return fail(CN_ERR_NOKEY, "relinearization keys not set");
     for (uint32_t c = 0; c < count; c++) {
         const uint64_t *pa = A->d + ((size_t)ai + (size_t)c * astride) * A->item_words, *pb = B->d + ((size_t)bi + (size_t)c * bstride) * B->item_words;
-        const uint64_t *ins[2] = {pa, pb};
-        CHECK(defer_push(ctx, DOp{DOP_MULRELIN, 0, O->d + (size_t)(oi + c) * O->item_words, pa, pb, 0, 0, nullptr}, ins, 2));
+        CHECK(defer_push(ctx, DOp{DOP_MULRELIN, 0, O->d + (size_t)(oi + c) * O->item_words, pa, pb, 0, 0, nullptr}));
     }
     ctx->st.Relinarization += count;          // (Multiplication is counted by the batched multiply at flush time)
     return 0;

@@ -417,6 +417,77 @@ def test_bias_fold_with_a_reused_output_handle(rng):
         g.set_option("defer", 0)
 
 
+# (kernel launches, zero encryptions folded) of each program below under "defer" = 1, measured on the commit before the flush planner moved into
+# cn_defer_plan.h (profiles/defer_plan_refactor.md)
+BLOCKED_REWRITES = {"zero_read_twice": (4, 0), "input_overwritten_deeper": (6, 0), "output_read_deeper": (6, 0), "nothing_in_the_way": (4, 1)}
+
+
+@pytest.mark.gpu
+def test_blocked_queue_rewrites_give_the_immediate_words():
+    """The hazards that keep a flush from rewriting the queue, as real calls: a zero encryption read by TWO scalar products is not folded; a scalar product
+    whose input is overwritten on a deeper level, or whose output is read on a deeper level, is not merged into the deeper launch of its term count.  A fourth
+    program has nothing in the way (one fold, one merge).  Same words as the immediate calls; launches and folds as the literals above."""
+    from cryptonets_amd._native import Context
+    p = PARAMS["tiny"]
+    w2, w3 = np.array([5, 7], dtype=np.uint64), np.array([3, p["t"] - 2, 9], dtype=np.uint64)
+    words, seen = {}, {}
+    for defer in (0, 1):
+        g = Context(p["n"], p["t"], q=p["q"], dbc=p["dbc"], gdbc=p["gdbc"], device=0)
+        g.keygen(42, galois=False)
+        ph = g.pt_alloc(5)
+        g.encode_batch(np.arange(1, 16, dtype=np.uint64).reshape(5, 3), ph, 0)
+
+        def enc(i, seed):                                    # i < 0: an encryption of zero
+            h = g.ct_alloc(1)
+            g.encrypt(ph if i >= 0 else 0, max(i, 0), h, 0, 1, seed=seed)
+            return h
+
+        def dot(src, w):
+            out = g.ct_alloc(1)
+            g.scalar_dot(src, np.zeros(len(src), dtype=np.uint32), w, out, 0)
+            return out
+
+        def zero_read_twice(x):
+            z = enc(-1, 200)
+            outs = [dot([x[0], x[1], z], w3), dot([x[1], x[2], z], w3)]
+            g.free(z)
+            return outs
+
+        def input_overwritten_deeper(x):
+            e = enc(4, 201)
+            outs = [dot([x[0], x[1]], w2), dot([x[0], e], w2)]          # levels 0 and 1
+            g.add(x[2], 0, x[3], 0, x[0], 0)                             # level 2: behind both readers of x[0]
+            return outs + [e, x[0]]
+
+        def output_read_deeper(x):
+            e = enc(4, 202)
+            outs = [dot([x[1], x[2]], w2), dot([x[1], e], w2)]
+            s = g.ct_alloc(1)
+            g.add(outs[0], 0, x[3], 0, s, 0)                             # level 1 reads the level-0 output
+            return outs + [e, s]
+
+        def nothing_in_the_way(x):
+            z = enc(-1, 203)
+            outs = [dot([x[1], x[2]], w2), dot([x[1], z], w2)]
+            g.free(z)
+            return outs
+
+        x = [enc(i, 100 + i) for i in range(4)]
+        g.ct_download(x[0], 0, 1)
+        g.set_option("defer", defer)
+        for prog in (zero_read_twice, input_overwritten_deeper, output_read_deeper, nothing_in_the_way):
+            l0, f0 = g.stats()["kernel_launches"], g.get_option("folded_zero_encryptions")
+            outs = prog(x)
+            seen[defer, prog.__name__] = (g.stats()["kernel_launches"] - l0, g.get_option("folded_zero_encryptions") - f0)      # (cn_stats_get flushes)
+            words[defer, prog.__name__] = np.stack([g.ct_download(h, 0, 1)[0] for h in outs])
+        g.set_option("defer", 0)
+        g.close()
+    print({k[1]: v for k, v in seen.items() if k[0] == 1})
+    for name, want in BLOCKED_REWRITES.items():
+        assert np.array_equal(words[0, name], words[1, name]), name
+        assert seen[1, name] == want, (name, seen[1, name], want)
+
+
 @pytest.mark.gpu
 def test_stats_and_destroy_drain_the_queue(rng):
     """OperationsCount read without a sync counts the queued multiplications (cn_stats_get flushes); a context destroyed with calls and
