@@ -8,6 +8,8 @@
 // (host-only; included by the two units that plan: cn_eval.hip, and cn_defer.hip for the flush of queued scalar products).
 // What a flush of the deferred queue launches - the arrays a queued call reads, admission and the layer-boundary rule, the three queue rewrites, pending squarings,
 // parking, staging layout, the ordered steps - is decided in cn_defer_plan.h (host-only; the queue's types DOp and DeferQueue live there; cn_defer.hip does the device work).
+// What a ciphertext product launches - tensor form, FP64 / lazy choice, squaring kernels, scratch list -, how its batches are cut into chunks under the scratch limit and
+// the gates of the one-key-switch-per-output forms are decided in cn_mul_plan.h (host-only; mul_switches in cn_eval.hip builds what it reads of a context).
 // Which arithmetic policy a modulus range takes and which ring sizes have the register-radix kernels is decided in cn_policy.h (cn_mod_range, cn_policy, cn_rr_size).
 // Everything here is internal: the C ABI is include/cnhip.h.  The element-wise kernels (cn_k_elem.hip.h) have internal linkage - every unit that launches one
 // carries its own copy.
@@ -135,31 +137,14 @@ int run_gemm_plan(cn_ctx *ctx, const GemmPlan &P, const char *tables, Buffer *I,
 // the launch of a planned layout whose image is at `tables` (operands by name: GemmLaunch, cn_runtime.h) and the kernel family it goes to
 inline GemmLaunch gemm_launch(const cn_ctx *ctx, const GemmLayout &L, const char *tables) { return GemmLaunch::of(L, tables, (uint32_t)ctx->opt.gemm_order); }
 inline int run_gemm_launch(cn_ctx *ctx, const GemmLayout &L, const GemmLaunch &gl) { return L.mfma ? cn_l_gemm_mfma(ctx, gl) : cn_l_gemm(ctx, gl); }
-bool square_gemm_ctx_ok(cn_ctx *ctx);
-bool square_gemm_fused_ok(cn_ctx *ctx, const GemmPlan &P);
-bool run_intt_tensor(cn_ctx *c, const uint64_t *A, const uint64_t *B, uint64_t *D, uint32_t cnt, uint32_t base_off, uint32_t Lm, bool lazy);
-bool square_fused_ok(cn_ctx *c, uint32_t base_off, uint32_t Lm);
-void run_square_fused(cn_ctx *c, const uint64_t *A, size_t astride, const uint64_t *const *atab, uint64_t *D, uint32_t cnt, uint32_t base_off, uint32_t Lm);
+MulSwitches mul_switches(const cn_ctx *ctx);               // (cn_mul_plan.h)
 bool aux_stream_ready(cn_ctx *ctx);
 // "sq_halves": Multiply + Relinearize of a batch software-pipelined in parts over the context's two streams (round 6): part i on stream i % 2, its Multiply behind the Multiply
 // of the part before it (event), its key switch behind its own Multiply (stream order) - [mul 0][ks 0 | mul 1][ks 1 | mul 2][ks 2]: the HBM-bound base extension / floor and
 // the transform kernels of a Multiply fill what the FP64-bound key switch of the part before leaves.  The context's stream continues behind the last part of either stream.
 // Three parts of 30 / 40 / 30 % measured best for the CryptoNets batch (profiles/r06_mulrelin_parts.txt: plain loop of the two primes 12.6 -> 12.0-12.2 ms, the half-batch
 // stagger of the primes 12.2-12.6; two parts 12.4-12.5, four 12.7, five 12.4).
-// mul(first, count), ks(first, count) launch on ctx->stream.
-static const uint32_t SQ_HALVES_MIN = 512;       // (the 100-ciphertext layer of CryptoNets pipelined as well: 12.35 -> 13.4 ms per batch, visit AY)
-// cn_mul_relin_sum: the smallest K that takes the one-key-switch-per-output form (cn_get_option "mul_sum_min_k").  2 = every sum of products: at C3, K = 2 takes
-// 0.53 (one output) and 0.69 (eight outputs) of the literal sequence's time, the spreads of the two sides apart (profiles/mul_relin_sum.md, tools/mul_sum_probe.py)
-static const uint32_t MUL_SUM_MIN_K = 2;
-// the parts of a pipelined batch of c ciphertexts: part i = [first[i], first[i + 1]); returns the number of parts P = min(3, max(1, c / 128)) (first[] holds P + 1
-// entries).  Three parts are cut at 30 and 70 %, two at the half; every cut is rounded up to a multiple of 8.
-static inline uint32_t pipeline_cuts(uint32_t c, uint32_t first[4]) {
-    const uint32_t P = std::min<uint32_t>(3, std::max<uint32_t>(1, c / 128));
-    first[0] = 0; first[P] = c;
-    if (P == 2) first[1] = (c / 2 + 7) & ~7u;
-    if (P == 3) { first[1] = (uint32_t)(((uint64_t)c * 3 / 10 + 7) & ~7ull); first[2] = (uint32_t)(((uint64_t)c * 7 / 10 + 7) & ~7ull); }
-    return P;
-}
+// mul(first, count), ks(first, count) launch on ctx->stream.  When a batch takes it, and its cuts: mul_pipeline_parts, pipeline_cuts (cn_mul_plan.h)
 template <class FM, class FK> static int pipelined_halves(cn_ctx *ctx, uint32_t c, FM mul, FK ks) {
     uint32_t first[4];
     const uint32_t P = pipeline_cuts(c, first);
@@ -185,14 +170,19 @@ template <class FM, class FK> static int pipelined_halves(cn_ctx *ctx, uint32_t 
     HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
     return 0;
 }
-size_t mul_scratch_per_ct(cn_ctx *c, bool square);
 int do_multiply(cn_ctx *ctx, const uint64_t *a, uint32_t astride, const uint64_t *b, uint32_t bstride, uint64_t *out3, uint32_t cnt, const uint64_t *const *atab = nullptr, const uint64_t *const *btab = nullptr);
 int ensure_ks_part(cn_ctx *ctx, size_t need);
 KsSwitches ks_switches(const cn_ctx *ctx);
 KsPlan ks_plan(const cn_ctx *ctx, const KsKey &key, uint32_t cnt, int galois);
-bool halves_pipeline_ok(cn_ctx *ctx, uint32_t c, int sq_halves_min);
 int do_keyswitch(cn_ctx *ctx, const KsKey &key, const KsCall &call);
-uint32_t chunk_for(cn_ctx *ctx, size_t per_ct, uint32_t count);
+// Multiply + Relinearize of a batch (run_mul_relin, cn_eval.hip).  Operand i: a + i * astride ciphertexts (stride 0: one for all), or the i-th address of a host list
+// (hb == ha: squarings); result i: out + i ciphertexts, or the i-th address of a host list.  The lists reach the device per chunk
+struct MulRelinCall {
+    const uint64_t *a = nullptr, *b = nullptr; uint32_t astride = 0, bstride = 0;
+    const uint64_t *const *ha = nullptr, *const *hb = nullptr;
+    uint64_t *out = nullptr; uint64_t *const *ho = nullptr;
+};
+int run_mul_relin(cn_ctx *ctx, const MulRelinCall &m, uint32_t count, MulSite site, int sq_halves_min);
 int mul_relin_body(cn_ctx *ctx, cn_handle a, uint32_t ai, uint32_t astride, cn_handle b, uint32_t bi, uint32_t bstride, cn_handle out, uint32_t oi, uint32_t count);
 const KsKey *galois_key(cn_ctx *ctx, uint64_t elt);          // null: not present
 int do_galois(cn_ctx *ctx, const GaloisCall &g);
@@ -261,6 +251,18 @@ static inline void rec_galois(cn_ctx *ctx, uint64_t elt) {                // cn_
     if (elt == m - 1) { ctx->rec_cols = true; return; }
     uint64_t e = 1;
     for (uint64_t s2 = 1; s2 < n / 2; s2++) { e = (e * 3) & (m - 1); if (e == elt) { ctx->rec_set.insert(s2 <= n / 4 ? (int)s2 : (int)s2 - (int)(n / 2)); return; } }
+}
+
+// the chunks of a planned batch (mul_batch, cn_mul_plan.h), body(first, c) for each.  own_arena: every chunk sizes the scratch arena for itself (ensure_scratch rewinds
+// it); else the caller has sized it and every chunk's scratch starts where the caller's ends
+template <class F> static int mul_chunks(cn_ctx *ctx, const MulBatch &B, uint32_t count, bool own_arena, F body) {
+    const size_t mark = ctx->soff;
+    for (uint32_t s = 0; s < count; s += B.chunk) {
+        const uint32_t c = std::min(B.chunk, count - s);
+        if (own_arena) CHECK(ensure_scratch(ctx, B.ensure(c))); else ctx->soff = mark;
+        CHECK(body(s, c));
+    }
+    return 0;
 }
 
 #define GETCT(var, h, sz) Buffer *var = getbuf(ctx, h, 0); if (!var) return fail(CN_ERR_ARG, "invalid ciphertext handle " #h); \

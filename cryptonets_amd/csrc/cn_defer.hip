@@ -34,7 +34,7 @@ DeferSwitches defer_switches(cn_ctx *ctx) {
     DeferSwitches s = env;
     if (!ctx) return s;
     s.fold_zero = ctx->opt.fold_zero && zero_fold_ok(ctx); s.t_half = ctx->hc.t_half;
-    s.square_gemm = ctx->defer_square_gemm && square_gemm_ctx_ok(ctx) && ctx->rlk.d;
+    s.square_gemm = mul_defers_square_gemm(ctx->hc, mul_switches(ctx));
     s.ctw2 = ctx->ctw2; s.n = ctx->hc.n; s.park_max = ctx->smax / 4;
     return s;
 }
@@ -142,17 +142,13 @@ static bool park_squarings(cn_ctx *ctx, DeferQueue *q, const std::vector<const D
         sq.cap = want;
     }
     const uint32_t n = (uint32_t)ops.size();
-    const size_t per = mul_scratch_per_ct(ctx, true) + 8 + 64;
-    const uint32_t ch = chunk_for(ctx, per, n);
-    for (uint32_t s0 = 0; s0 < n && !*rc; s0 += ch) {
-        const uint32_t c = std::min<uint32_t>(ch, n - s0);
-        if ((*rc = ensure_scratch(ctx, per * c + al((size_t)c * 8) + 8192))) break;
-        std::vector<const uint64_t *> ha(c);
-        for (uint32_t i = 0; i < c; i++) ha[i] = ops[s0 + i]->a;
+    std::vector<const uint64_t *> ha(n);
+    for (uint32_t i = 0; i < n; i++) ha[i] = ops[i]->a;
+    *rc = mul_chunks(ctx, mul_batch(ctx->hc, mul_switches(ctx), MUL_AT_PARK, n, true), n, true, [&](uint32_t s0, uint32_t c) -> int {
         const uint64_t **da;
-        if ((*rc = upload_tmp(ctx, ha.data(), c, &da))) break;
-        *rc = do_multiply(ctx, nullptr, 1, nullptr, 1, sq.arr + (size_t)s0 * 3 * kn, c, da, da);
-    }
+        CHECK(upload_tmp(ctx, ha.data() + s0, c, &da));
+        return do_multiply(ctx, nullptr, 1, nullptr, 1, sq.arr + (size_t)s0 * 3 * kn, c, da, da);
+    });
     if (*rc) return true;
     sq.out.resize(n);
     for (uint32_t i = 0; i < n; i++) { sq.out[i] = ops[i]->out; sq.slot[ops[i]->out] = i; }
@@ -206,10 +202,6 @@ static SgPlan *sg_plan(cn_ctx *ctx, DeferSquare &sq, uint32_t O, uint32_t K, std
     sq.plans.push_back(std::move(p));
     return sq.plans.back().get();
 }
-static size_t sg_scratch(cn_ctx *ctx, const GemmPlan &P) {
-    const size_t kn = (size_t)ctx->hc.k * ctx->hc.n;
-    return al((size_t)P.O * 2 * kn * 8) + al((size_t)P.O * ctx->hc.rl_tot * ctx->hc.n * (P.dig_i32 ? 4 : 8)) + al((size_t)P.G * P.Kp * 4) + al((size_t)P.G * P.M * 4) + al((size_t)P.O * 8) + 8192;
-}
 // The device half of the decision about pending products (defer_pending_decide has rules (a)-(d) and the candidate groups): the plan of every group is found or built,
 // passes square_gemm_fused_ok and fits the scratch limits, and the group's biases are addressable - or the answer is no for all.  plans[g]: the plan of groups[g]
 static bool sg_prepare(cn_ctx *ctx, DeferQueue *q, const std::vector<uint8_t> &dead, const DeferReleased &released, const DeferSwitches &sw, std::vector<DeferSgGroup> &groups,
@@ -219,8 +211,8 @@ static bool sg_prepare(cn_ctx *ctx, DeferQueue *q, const std::vector<uint8_t> &d
     const uint64_t keep = sq.tick;
     for (DeferSgGroup &g : groups) {
         SgPlan *plan = sg_plan(ctx, sq, (uint32_t)g.rows.size(), g.K, g.W, g.cidx, keep);
-        if (!plan || !plan->ok || !square_gemm_fused_ok(ctx, plan->P) || sg_scratch(ctx, plan->P) > ctx->smax) return false;
-        if (sg_scratch(ctx, plan->P) > ctx->scap && ctx->graphs_alive) return false;       // (the scratch arena does not grow while a graph is alive)
+        if (!plan || !plan->ok || !square_gemm_fused_ok(ctx->hc, mul_switches(ctx), plan->P) || mul_sg_scratch(ctx->hc, plan->P, plan->P.O) > ctx->smax) return false;
+        if (mul_sg_scratch(ctx->hc, plan->P, plan->P.O) > ctx->scap && ctx->graphs_alive) return false;       // (the scratch arena does not grow while a graph is alive)
         if (!g.bias_ok) return false;
         plans.push_back(plan);
     }
@@ -242,7 +234,7 @@ static int sg_run(cn_ctx *ctx, DeferQueue *q, const DeferSgGroup &g, const SgPla
         for (size_t x = 0; x < bidx.size(); x++) if (sp.oidx[x] >= 0) bidx[x] = (int32_t)(((uint64_t)g.rows[sp.oidx[x]]->bias - bbase) >> 8);
     }
     for (uint32_t o = 0; o < P.O; o++) outs[o] = g.rows[o]->out;
-    CHECK(ensure_scratch(ctx, sg_scratch(ctx, P)));
+    CHECK(ensure_scratch(ctx, mul_sg_scratch(ctx->hc, P, P.O)));
     uint64_t *T = salloc<uint64_t>(ctx, (size_t)P.O * 2 * kn);
     void *S = salloc<char>(ctx, (size_t)P.O * tot * n * (P.dig_i32 ? 4 : 8));       // int32 words where the plan's digit bound allows (GemmPlan::dig_i32)
     if (!T || !S) return fail(CN_ERR_HIP, "internal: scratch exhausted in the deferred square + dense form");
@@ -262,31 +254,11 @@ static int sg_run(cn_ctx *ctx, DeferQueue *q, const DeferSgGroup &g, const SgPla
 // the queued squarings (SquareActivation: the fused kernel) or the queued general products (separate launches) of one level, as the schedule splits them: the batched
 // BEHZ pipeline + ONE key switch, operands and results through tables
 int flush_mulrelin_group(cn_ctx *ctx, const std::vector<const DOp *> &ops, bool sq) {
-    const size_t kn = (size_t)ctx->hc.k * ctx->hc.n;
-    {
-        const size_t per = mul_scratch_per_ct(ctx, sq == 1) + al(3 * kn * 8) + 3 * 8 + 64;
-        const uint32_t ch = chunk_for(ctx, per, (uint32_t)ops.size());
-        for (uint32_t s0 = 0; s0 < ops.size(); s0 += ch) {
-            const uint32_t c = std::min<uint32_t>(ch, (uint32_t)ops.size() - s0);
-            CHECK(ensure_scratch(ctx, per * c + 3 * al((size_t)c * 8) + 8192));
-            std::vector<const uint64_t *> ha(c), hb(c); std::vector<uint64_t *> ho(c);
-            for (uint32_t i = 0; i < c; i++) { ha[i] = ops[s0 + i]->a; hb[i] = ops[s0 + i]->b; ho[i] = ops[s0 + i]->out; }
-            const uint64_t **da, **db = nullptr; uint64_t **dout;
-            CHECK(upload_tmp(ctx, ha.data(), c, &da));
-            if (!sq) CHECK(upload_tmp(ctx, hb.data(), c, &db));
-            CHECK(upload_tmp(ctx, ho.data(), c, &dout));
-            uint64_t *t3 = salloc<uint64_t>(ctx, (size_t)c * 3 * kn);
-            if (!t3) return fail(CN_ERR_HIP, "internal: scratch exhausted in deferred multiply");
-            auto mul = [&](uint32_t f, uint32_t n_) { return do_multiply(ctx, nullptr, 1, nullptr, 1, t3 + (size_t)f * 3 * kn, n_, da + f, (sq ? da : db) + f); };
-            auto ksw = [&](uint32_t f, uint32_t n_) { return do_keyswitch(ctx, ctx->rlk, KsCall::relin(t3 + (size_t)f * 3 * kn, kn, n_).to_table(dout + f)); };
-            if (halves_pipeline_ok(ctx, c, 2)) {
-                CHECK(pipelined_halves(ctx, c, mul, ksw)); continue;
-            }
-            CHECK(mul(0, c));
-            CHECK(ksw(0, c));
-        }
-    }
-    return 0;
+    std::vector<const uint64_t *> ha(ops.size()), hb(sq ? 0 : ops.size()); std::vector<uint64_t *> ho(ops.size());
+    for (size_t i = 0; i < ops.size(); i++) { ha[i] = ops[i]->a; ho[i] = ops[i]->out; if (!sq) hb[i] = ops[i]->b; }
+    MulRelinCall m;
+    m.ha = ha.data(); m.hb = sq ? ha.data() : hb.data(); m.ho = ho.data();
+    return run_mul_relin(ctx, m, (uint32_t)ops.size(), MUL_AT_DEFERRED, 2);
 }
 
 // ---- staged kinds (DOP_COPY .. DOP_SUMSLOTS): the per-ciphertext calls of an unchanged LoLa-style caller - one MultiplyPlain, SumAllSlots,
@@ -426,7 +398,7 @@ int flush_encrypt_group(cn_ctx *ctx, const std::vector<const DOp *> &ops) {
     std::vector<EncTab> tab(ops.size());
     for (size_t i = 0; i < ops.size(); i++) tab[i] = {(NTT_GLOBAL uint64_t *)ops[i]->out, (const NTT_GLOBAL uint64_t *)ops[i]->a, ops[i]->nonce, ops[i]->item};
     const size_t per = (size_t)ctx->hc.k * ctx->hc.n * 8 + 3 * (size_t)ctx->hc.n + sizeof(EncTab) + 64;
-    const uint32_t ch = chunk_for(ctx, per, (uint32_t)ops.size());
+    const uint32_t ch = cn_chunk_of(ctx->smax, per, (uint32_t)ops.size());
     for (uint32_t s0 = 0; s0 < ops.size(); s0 += ch) {
         const uint32_t c = std::min<uint32_t>(ch, (uint32_t)ops.size() - s0);
         CHECK(encrypt_chain(ctx, c, nullptr, 0, nullptr, 0, tab.data() + s0));

@@ -71,7 +71,7 @@ struct DeferSwitches {
     // of the context (left as they stand where no context was given: admission reads none of them)
     bool fold_zero = false;        // "fold_zero" is on and the context has the kernels of the fold (zero_fold_ok)
     uint64_t t_half = 0;           // DevConsts::t_half
-    bool square_gemm = false;      // "defer_square_gemm" is on, the context takes cn_square_gemm's second half (square_gemm_ctx_ok) and has relinearisation keys
+    bool square_gemm = false;      // "defer_square_gemm" is on, the context takes cn_square_gemm's second half (square_gemm_ctx_ok) and has relinearisation keys: mul_defers_square_gemm, cn_mul_plan.h
     size_t ctw2 = 0; uint32_t n = 0;      // words of a size-2 ciphertext, ring size
     size_t park_max = 0;           // bytes of products a flush may park: a quarter of the scratch limit
     size_t product_bytes() const { return ctw2 / 2 * 3 * 8; }      // one size-3 product
@@ -249,10 +249,10 @@ inline void defer_merge_gemm(DeferQueue &q, const std::vector<uint8_t> &dead, co
 // ---- products whose relinearisation an earlier layer-boundary flush held back (pending[slot] = the output array of the product in that slot, slot_of the inverse).
 // The decision of a flush that finds products pending (once, all or nothing): may every queued reader of a pending array run in cn_square_gemm's second half?
 //   (a) the caller has released every pending output array, (b) only scalar products read pending arrays - and those form groups (one level, one term count)
-//   whose plan passes square_gemm_fused_ok, with a bias on every output or on none, (c) every gathered term of such a scalar product is a pending array (and no zero
+//   whose plan passes square_gemm_fused_ok (cn_mul_plan.h), with a bias on every output or on none, (c) every gathered term of such a scalar product is a pending array (and no zero
 //   encryption was folded onto it), (d) no queued call writes a pending array.
 // need[slot]: the product has to be relinearised if the answer is no - somebody reads its array or the caller still holds it.
-// This is the pure half: rules (a)-(d) and the candidate groups with the key their plan is found by; the plan itself, square_gemm_fused_ok and the scratch limits are
+// This is the pure half: rules (a)-(d) and the candidate groups with the key their plan is found by; the plan itself, square_gemm_fused_ok and the scratch limits (mul_sg_scratch, cn_mul_plan.h) are
 // sg_prepare's (cn_defer.hip), which says no for all groups if it says no for one.
 struct DeferSgGroup {
     int32_t level; uint32_t K;

@@ -290,25 +290,10 @@ extern "C" int cn_gemm_plan_apply(cn_ctx *ctx, cn_handle plan, cn_handle in, cn_
 API_END }
 
 // ---------------------------------------------------------------- BEHZ multiply / key switching
-// tensor product fused into the inverse transform (register-radix sizes only); returns false when the caller must fall back
-// lazy: D leaves as lazy-FP64 hand-off words for k_behz_floor_f64<.., true> (the caller checked cn_behz_lazy: every modulus takes an FP64 policy)
-bool run_intt_tensor(cn_ctx *c, const uint64_t *A, const uint64_t *B, uint64_t *D, uint32_t cnt, uint32_t base_off, uint32_t Lm, bool lazy) {
-    if (!rr_kernels(c)) return false;
-    const int pol = cn_policy(cn_mod_range(c->hc, base_off, Lm), c->opt.f64);
-    if (lazy && pol == POL_U64) return false;
-    bool ok = rr_ops[pol]->intt_tensor(c, A, B, D, cnt, base_off, Lm, lazy);
-    if (ok) { launch_count(c); c->st.ntt_inverse_limbs += (uint64_t)cnt * 3 * Lm; }
-    return ok;
-}
-// squaring: forward transforms, tensor and inverse transforms of one (ciphertext, limb) in ONE kernel (FP64 policies)
-bool square_fused_ok(cn_ctx *c, uint32_t base_off, uint32_t Lm) {
-    return c->opt.sq_fused && c->opt.f64 && rr_kernels(c) && cn_mod_range(c->hc, base_off, Lm).f64ok;
-}
-// (the caller asked square_fused_ok: the range is on an FP64 policy, the pick here is between the two)
-void run_square_fused(cn_ctx *c, const uint64_t *A, size_t astride, const uint64_t *const *atab, uint64_t *D, uint32_t cnt, uint32_t base_off, uint32_t Lm) {
-    rr_ops[cn_policy(cn_mod_range(c->hc, base_off, Lm), true)]->square_fused(c, A, astride, atab, D, cnt, base_off, Lm);
-    launch_count(c);
-    c->st.ntt_forward_limbs += (uint64_t)cnt * 2 * Lm; c->st.ntt_inverse_limbs += (uint64_t)cnt * 3 * Lm;
+// the switches of this context that the multiply planner reads (cn_mul_plan.h): the only place that copies them out of a context for the multiply family
+MulSwitches mul_switches(const cn_ctx *ctx) {
+    return {ctx->opt.f64, ctx->opt.sq_fused, ctx->opt.sq_pipe, ctx->opt.sq_lds, ctx->opt.sq_halves, ctx->mul_sum, ctx->digit_i32, ctx->defer_square_gemm, rr_kernels(ctx), rr_kernels(ctx, 13),
+            ctx->cus, ctx->capturing.load(), ctx->smax, ctx->rlk.d != nullptr, ctx->rlk.f64, ks_switches(ctx)};
 }
 // the context's second stream (squaring overlap): created on first use, kept only if it runs beside the context's own stream (a hardware queue of its own)
 bool aux_stream_ready(cn_ctx *ctx) {
@@ -330,46 +315,42 @@ bool aux_stream_ready(cn_ctx *ctx) {
     ctx->stream2 = cand[got];
     return true;
 }
-size_t mul_scratch_per_ct(cn_ctx *c, bool square) {
-    size_t n = c->hc.n, k = c->hc.k, kb = c->hc.kb;
-    size_t w = (square ? 1 : 2) * 2 * (k + kb) * n + 3 * (k + kb) * n;
-    return al(w * 8) + 1024;
-}
 // a, b: pointers to first operand ciphertext (size 2); out3: [cnt][3][k][N]; scratch must be ensured by caller.  atab / btab: one
-// operand address per ciphertext instead of a + ct*astride*ctw (deferred per-ciphertext calls; atab == btab: squarings)
+// operand address per ciphertext instead of a + ct*astride*ctw (deferred per-ciphertext calls; atab == btab: squarings).  What is launched: MulPlan (cn_mul_plan.h)
 int do_multiply(cn_ctx *ctx, const uint64_t *a, uint32_t astride, const uint64_t *b, uint32_t bstride, uint64_t *out3, uint32_t cnt,
                        const uint64_t *const *atab, const uint64_t *const *btab) {
     const uint32_t n = ctx->hc.n, k = ctx->hc.k, kb = ctx->hc.kb;
     const bool square = atab ? atab == btab : (a == b && astride == bstride);
-    // squarings on the FP64 path: one fused kernel per base does forward transforms, tensor and inverse transforms; its q side reads the
-    // input ciphertexts in place, so k_behz_extend only has to produce the Bsk limbs
-    const bool fused = square && ctx->hc.behz_f64 && square_fused_ok(ctx, 0, k) && square_fused_ok(ctx, k, kb);
-    uint64_t *aq = fused ? nullptr : salloc<uint64_t>(ctx, (size_t)cnt * 2 * k * n), *ab = salloc<uint64_t>(ctx, (size_t)cnt * 2 * kb * n);
-    uint64_t *bq = aq, *bb = ab;
-    if (!square) { bq = salloc<uint64_t>(ctx, (size_t)cnt * 2 * k * n); bb = salloc<uint64_t>(ctx, (size_t)cnt * 2 * kb * n); }
-    uint64_t *dq = salloc<uint64_t>(ctx, (size_t)cnt * 3 * k * n), *db = salloc<uint64_t>(ctx, (size_t)cnt * 3 * kb * n);
-    if ((!fused && !aq) || !ab || (!square && (!bq || !bb)) || !dq || !db) return fail(CN_ERR_HIP, "internal: scratch exhausted in multiply");
-    CHECK(cn_l_behz_extend(ctx, a, astride, atab, aq, ab, cnt));
-    if (!square) CHECK(cn_l_behz_extend(ctx, b, bstride, btab, bq, bb, cnt));
-    // dq / db reach the floor as lazy-FP64 hand-off words (lazy_word, cn_dev_common.hip.h) when the tensor kernels of BOTH bases and the floor are on the
-    // FP64 policy - the fused squaring kernels always (`fused` implies it), k_intt_tensor when asked; the element-wise fall-back writes canonical words
-    bool lazy = cn_behz_lazy(ctx);
-    if (fused) {
-        run_square_fused(ctx, a, (size_t)astride * 2 * k * n, atab, dq, cnt, 0, k);
-        run_square_fused(ctx, ab, (size_t)2 * kb * n, nullptr, db, cnt, k, kb);
+    const MulPlan p = cn_mul_plan(ctx->hc, mul_switches(ctx), square, cnt);
+    uint64_t *arr[MUL_ARRAYS] = {};
+    for (uint32_t i = 0; i < p.arrays; i++)
+        if (!(arr[p.scratch[i].id] = (uint64_t *)salloc<char>(ctx, p.scratch[i].bytes))) return fail(CN_ERR_HIP, "internal: scratch exhausted in multiply");
+    uint64_t *const aq = arr[MUL_AQ], *const ab = arr[MUL_AB], *const bq = square ? aq : arr[MUL_BQ], *const bb = square ? ab : arr[MUL_BB], *const dq = arr[MUL_DQ], *const db = arr[MUL_DB];
+    CHECK(cn_l_behz_extend(ctx, a, astride, atab, aq, ab, cnt, p.behz_f64));
+    if (!square) CHECK(cn_l_behz_extend(ctx, b, bstride, btab, bq, bb, cnt, p.behz_f64));
+    const char *const no_kernel = "internal: tensor form without a kernel of its policy";
+    if (p.form == MUL_SQUARE_FUSED) {
+        if (!rr_ops[p.q.policy]->square_fused(ctx, a, (size_t)astride * 2 * k * n, atab, dq, cnt, 0, k, p.q)) return fail(CN_ERR_ARG, no_kernel);
+        if (!rr_ops[p.bsk.policy]->square_fused(ctx, ab, (size_t)2 * kb * n, nullptr, db, cnt, k, kb, p.bsk)) return fail(CN_ERR_ARG, no_kernel);
+        launch_count(ctx, 2);
+        ctx->st.ntt_forward_limbs += (uint64_t)cnt * 2 * (k + kb); ctx->st.ntt_inverse_limbs += (uint64_t)cnt * 3 * (k + kb);
     } else {
-    CHECK(cn_run_ntt(ctx, aq, cnt * 2 * k, 0, k, 0)); CHECK(cn_run_ntt(ctx, ab, cnt * 2 * kb, k, kb, 0));
-    if (!square) { CHECK(cn_run_ntt(ctx, bq, cnt * 2 * k, 0, k, 0)); CHECK(cn_run_ntt(ctx, bb, cnt * 2 * kb, k, kb, 0)); }
-    if (!run_intt_tensor(ctx, aq, bq, dq, cnt, 0, k, lazy) || !run_intt_tensor(ctx, ab, bb, db, cnt, k, kb, lazy)) {
-        lazy = false;
-        hipLaunchKernelGGL(k_tensor, dim3(cnt * k * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, aq, bq, dq, ctx->dc, ctx->chunks, k, 0u);
-        hipLaunchKernelGGL(k_tensor, dim3(cnt * kb * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, ab, bb, db, ctx->dc, ctx->chunks, kb, k);
-        HIPCHK(hipGetLastError()); launch_count(ctx, 2);
-        CHECK(cn_run_ntt(ctx, dq, cnt * 3 * k, 0, k, 1)); CHECK(cn_run_ntt(ctx, db, cnt * 3 * kb, k, kb, 1));
-    }
+        CHECK(cn_run_ntt(ctx, aq, cnt * 2 * k, 0, k, 0)); CHECK(cn_run_ntt(ctx, ab, cnt * 2 * kb, k, kb, 0));
+        if (!square) { CHECK(cn_run_ntt(ctx, bq, cnt * 2 * k, 0, k, 0)); CHECK(cn_run_ntt(ctx, bb, cnt * 2 * kb, k, kb, 0)); }
+        if (p.form == MUL_INTT_TENSOR) {
+            if (!rr_ops[p.q.policy]->intt_tensor(ctx, aq, bq, dq, cnt, 0, k, p.lazy)) return fail(CN_ERR_ARG, no_kernel);
+            if (!rr_ops[p.bsk.policy]->intt_tensor(ctx, ab, bb, db, cnt, k, kb, p.lazy)) return fail(CN_ERR_ARG, no_kernel);
+            launch_count(ctx, 2);
+            ctx->st.ntt_inverse_limbs += (uint64_t)cnt * 3 * (k + kb);
+        } else {
+            hipLaunchKernelGGL(k_tensor, dim3(cnt * k * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, aq, bq, dq, ctx->dc, ctx->chunks, k, 0u);
+            hipLaunchKernelGGL(k_tensor, dim3(cnt * kb * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, ab, bb, db, ctx->dc, ctx->chunks, kb, k);
+            HIPCHK(hipGetLastError()); launch_count(ctx, 2);
+            CHECK(cn_run_ntt(ctx, dq, cnt * 3 * k, 0, k, 1)); CHECK(cn_run_ntt(ctx, db, cnt * 3 * kb, k, kb, 1));
+        }
     }
     HIPCHK(hipGetLastError());
-    CHECK(cn_l_behz_floor(ctx, dq, db, out3, cnt, lazy));
+    CHECK(cn_l_behz_floor(ctx, dq, db, out3, cnt, p.behz_f64, p.lazy));
     ctx->st.Multiplication += cnt;
     return 0;
 }
@@ -394,15 +375,6 @@ KsSwitches ks_switches(const cn_ctx *ctx) {
     return {ctx->opt.ks_wide, ctx->opt.ks_split14, ctx->opt.ks_pair14, ctx->opt.ks_xcd, ctx->opt.ks_perm_fused, rr_kernels(ctx), ctx->hc.twdh != nullptr, digit_max, wide_max, ctx->smax};
 }
 KsPlan ks_plan(const cn_ctx *ctx, const KsKey &key, uint32_t cnt, int galois) { return cn_ks_plan(ctx->hc, ks_switches(ctx), key.f64, cnt, galois); }
-// may a Multiply + Relinearize of c ciphertexts run through pipelined_halves ("sq_halves" at least sq_halves_min)?  Only if no part's key switch writes the context's
-// ONE arena ks_part (the two-launch forms keep their partial products there and may re-allocate it), which the parts on the two streams would share
-bool halves_pipeline_ok(cn_ctx *ctx, uint32_t c, int sq_halves_min) {
-    if (ctx->opt.sq_halves < sq_halves_min || ctx->hc.logn > 13 || c < SQ_HALVES_MIN || ctx->capturing) return false;
-    uint32_t first[4];
-    const uint32_t P = pipeline_cuts(c, first);
-    for (uint32_t i = 0; i < P; i++) if (ks_writes_arena(ks_plan(ctx, ctx->rlk, first[i + 1] - first[i], 0))) return false;
-    return P >= 2 && aux_stream_ready(ctx);
-}
 // One key switch.  call: the operands by name (KsCall, cn_runtime.h); the key words and the plan (cn_ks_plan.h: form, accmax, xcd_cts, arena bytes) are added here.
 // perm_elt != 0 (two-launch forms only - the caller asks ks_perm_on_load first): target / add0 are the c1 / c0 of the ciphertext a rotation
 // READS and the kernels apply the automorphism x -> x^perm_elt while loading them
@@ -453,9 +425,35 @@ int do_keyswitch(cn_ctx *ctx, const KsKey &key, const KsCall &call) {
     ctx->st.ntt_forward_limbs += (uint64_t)cnt * tot_dig * k; ctx->st.ntt_inverse_limbs += (uint64_t)cnt * 2 * k;
     return 0;
 }
-uint32_t chunk_for(cn_ctx *ctx, size_t per_ct, uint32_t count) {
-    size_t c = std::max<size_t>(1, ctx->smax / per_ct);
-    return (uint32_t)std::min<size_t>(c, count);
+// Multiply + Relinearize of `count` products in the chunks of mul_batch: per chunk the address tables (if any), the size-3 products, the multiply and ONE key switch -
+// or the same in parts over the two streams (mul_pipeline_parts, pipelined_halves).  Chunks and parts write results while later ones still read operands
+int run_mul_relin(cn_ctx *ctx, const MulRelinCall &m, uint32_t count, MulSite site, int sq_halves_min) {
+    const size_t kn = (size_t)ctx->hc.k * ctx->hc.n, ctw = ctx->ctw2;
+    const bool square = m.ha ? m.ha == m.hb : (m.a == m.b && m.astride == m.bstride);
+    const MulSwitches sw = mul_switches(ctx);
+    return mul_chunks(ctx, mul_batch(ctx->hc, sw, site, count, square), count, true, [&](uint32_t s, uint32_t c) -> int {
+        const uint64_t **da = nullptr, **db = nullptr; uint64_t **dout = nullptr;
+        if (m.ha) {
+            CHECK(upload_tmp(ctx, m.ha + s, c, &da));
+            db = da;
+            if (!square) CHECK(upload_tmp(ctx, m.hb + s, c, &db));
+        }
+        if (m.ho) CHECK(upload_tmp(ctx, m.ho + s, c, &dout));
+        uint64_t *t3 = salloc<uint64_t>(ctx, (size_t)c * 3 * kn);
+        if (!t3) return fail(CN_ERR_HIP, "internal: scratch exhausted in multiply + relinearize");
+        auto mul = [&](uint32_t f, uint32_t n_) {
+            if (m.ha) return do_multiply(ctx, nullptr, 1, nullptr, 1, t3 + (size_t)f * 3 * kn, n_, da + f, db + f);
+            return do_multiply(ctx, m.a + (size_t)(s + f) * m.astride * ctw, m.astride, m.b + (size_t)(s + f) * m.bstride * ctw, m.bstride, t3 + (size_t)f * 3 * kn, n_);
+        };
+        auto ksw = [&](uint32_t f, uint32_t n_) {
+            KsCall ks = KsCall::relin(t3 + (size_t)f * 3 * kn, kn, n_);
+            return do_keyswitch(ctx, ctx->rlk, m.ho ? ks.to_table(dout + f) : ks.to(m.out + (size_t)(s + f) * ctw));
+        };
+        uint32_t first[4];
+        if (mul_pipeline_parts(ctx->hc, sw, c, sq_halves_min, first) && aux_stream_ready(ctx)) return pipelined_halves(ctx, c, mul, ksw);
+        CHECK(mul(0, c));
+        return ksw(0, c);
+    });
 }
 
 extern "C" int cn_multiply(cn_ctx *ctx, cn_handle a, uint32_t ai, cn_handle b, uint32_t bi, cn_handle out3, uint32_t oi, uint32_t count) { API_BODY TWO_LIMBS("cn_multiply");
@@ -463,14 +461,9 @@ extern "C" int cn_multiply(cn_ctx *ctx, cn_handle a, uint32_t ai, cn_handle b, u
     if (!range_ok(A, ai, count) || !range_ok(B, bi, count) || !range_ok(O, oi, count)) return fail(CN_ERR_ARG, "index out of range");
     if (!count) return 0;
     const uint64_t *pa = A->d + ai * A->item_words, *pb = B->d + bi * B->item_words;
-    size_t per = mul_scratch_per_ct(ctx, pa == pb);
-    uint32_t ch = chunk_for(ctx, per, count);
-    for (uint32_t s = 0; s < count; s += ch) {
-        uint32_t c = std::min(ch, count - s);
-        CHECK(ensure_scratch(ctx, per * c + 4096));
-        CHECK(do_multiply(ctx, pa + s * A->item_words, 1, pb + s * B->item_words, 1, O->d + (oi + s) * O->item_words, c));
-    }
-    return 0;
+    return mul_chunks(ctx, mul_batch(ctx->hc, mul_switches(ctx), MUL_AT_MULTIPLY, count, pa == pb), count, true, [&](uint32_t s, uint32_t c) {
+        return do_multiply(ctx, pa + s * A->item_words, 1, pb + s * B->item_words, 1, O->d + (oi + s) * O->item_words, c);
+    });
 API_END }
 extern "C" int cn_relinearize(cn_ctx *ctx, cn_handle in3, uint32_t ii, cn_handle out, uint32_t oi, uint32_t count) { API_BODY TWO_LIMBS("cn_relinearize");
     LOCK; GETCT(I, in3, 3); GETCT(O, out, 2);
@@ -508,23 +501,9 @@ int mul_relin_body(cn_ctx *ctx, cn_handle a, uint32_t ai, uint32_t astride, cn_h
         return fail(CN_ERR_ARG, "index out of range");
     if (!ctx->rlk.d) return fail(CN_ERR_NOKEY, "relinearization keys not set");
     if (!count) return 0;
-    const size_t kn = (size_t)ctx->hc.k * ctx->hc.n;
-    const uint64_t *pa = A->d + ai * A->item_words, *pb = B->d + bi * B->item_words;
-    const bool square = (pa == pb && astride == bstride);
-    size_t per = mul_scratch_per_ct(ctx, square) + al(3 * kn * 8);
-    uint32_t ch = chunk_for(ctx, per, count);
-    for (uint32_t s = 0; s < count; s += ch) {
-        uint32_t c = std::min(ch, count - s);
-        CHECK(ensure_scratch(ctx, per * c + 8192));
-        uint64_t *t3 = salloc<uint64_t>(ctx, (size_t)c * 3 * kn);
-        auto mul = [&](uint32_t f, uint32_t n_) { return do_multiply(ctx, pa + (size_t)(s + f) * astride * A->item_words, astride, pb + (size_t)(s + f) * bstride * B->item_words, bstride, t3 + (size_t)f * 3 * kn, n_); };
-        auto ksw = [&](uint32_t f, uint32_t n_) { return do_keyswitch(ctx, ctx->rlk, KsCall::relin(t3 + (size_t)f * 3 * kn, kn, n_).to(O->d + (oi + s + f) * O->item_words)); };
-        if (halves_pipeline_ok(ctx, c, 1)) {
-            CHECK(pipelined_halves(ctx, c, mul, ksw)); continue;
-        }
-        CHECK(mul(0, c));
-        CHECK(ksw(0, c));
-    }
+    MulRelinCall m;
+    m.a = A->d + ai * A->item_words; m.astride = astride; m.b = B->d + bi * B->item_words; m.bstride = bstride; m.out = O->d + oi * O->item_words;
+    CHECK(run_mul_relin(ctx, m, count, MUL_AT_MUL_RELIN, 1));
     ctx->st.Relinarization += count;
     return 0;
 }
@@ -537,11 +516,7 @@ int mul_relin_body(cn_ctx *ctx, cn_handle a, uint32_t ai, uint32_t astride, cn_h
 // 845 + 100 for CryptoNets, the same ciphertext words.  (Not forward_relinearize_late's "relinearize the sum": there the digits are those of the sum.)
 // Runs when the plan allows it (GemmPlan::dig: small weights, |S| below every q_j / 2 and 2^52), every modulus and the key are on an FP64 policy, the ring has the
 // register-radix kernels up to N = 8192 and the decomposition is the plain one; anything else takes the two separate steps inside the same call.
-// (square_gemm_ctx_ok: everything but the plan - the deferred queue asks it before it holds the relinearisation of queued squarings back, cn_defer.hip)
-bool square_gemm_ctx_ok(cn_ctx *ctx) {
-    return ctx->opt.f64 && rr_kernels(ctx, 13) && !ctx->hc.ks_xi && ctx->rlk.f64 && cn_mod_range(ctx->hc, 0, ctx->hc.k).f64ok;
-}
-bool square_gemm_fused_ok(cn_ctx *ctx, const GemmPlan &P) { return P.dig && square_gemm_ctx_ok(ctx); }
+// (square_gemm_fused_ok and square_gemm_ctx_ok, cn_mul_plan.h; the product loop in the chunks of mul_batch)
 extern "C" int cn_square_gemm(cn_ctx *ctx, cn_handle plan, cn_handle in, uint32_t ii, cn_handle out, uint32_t oi) { TWO_LIMBS("cn_square_gemm"); API_BODY
     LOCK; GETCT(I, in, 2); GETCT(OB, out, 2);
     Buffer *PB = getbuf(ctx, plan, 2);
@@ -554,10 +529,9 @@ extern "C" int cn_square_gemm(cn_ctx *ctx, cn_handle plan, cn_handle in, uint32_
     if (!ctx->rlk.d) return fail(CN_ERR_NOKEY, "relinearization keys not set");
     const uint32_t n = ctx->hc.n, k = ctx->hc.k, tot = ctx->hc.rl_tot;
     const size_t kn = (size_t)k * n;
-    const size_t per = mul_scratch_per_ct(ctx, true);
-    const size_t sw = P.dig_i32 ? 4 : 8;                                          // bytes per word of S
-    const size_t fixed = al((size_t)cnt * 3 * kn * 8) + al((size_t)P.O * tot * n * sw) + 8192;
-    if (!square_gemm_fused_ok(ctx, P) || fixed + per > ctx->smax) {               // the two steps as they are: square + relinearize into a temporary, the GEMM from it
+    const MulSwitches sw = mul_switches(ctx);
+    const MulBatch B = mul_batch(ctx->hc, sw, MUL_AT_SQUARE_GEMM, cnt, true, P.O, P.dig_i32);
+    if (!square_gemm_fused_ok(ctx->hc, sw, P) || !B.fits) {                       // the two steps as they are: square + relinearize into a temporary, the GEMM from it
         cn_handle tmp = 0;
         CHECK(alloc_buf(ctx, 0, cnt, 2, &tmp));
         int rc = mul_relin_body(ctx, in, ii, 1, in, ii, 1, tmp, 0, cnt);
@@ -567,18 +541,14 @@ extern "C" int cn_square_gemm(cn_ctx *ctx, cn_handle plan, cn_handle in, uint32_
         const int rf = free_body(ctx, tmp);
         return rc ? rc : rf;
     }
-    const uint32_t ch = (uint32_t)std::min<size_t>(cnt, (ctx->smax - fixed) / per);
-    CHECK(ensure_scratch(ctx, fixed + per * ch + 4096));
+    CHECK(ensure_scratch(ctx, B.ensure(B.chunk)));
     uint64_t *t3 = salloc<uint64_t>(ctx, (size_t)cnt * 3 * kn);
-    void *S = salloc<char>(ctx, (size_t)P.O * tot * n * sw);
+    void *S = salloc<char>(ctx, (size_t)P.O * tot * n * (P.dig_i32 ? 4 : 8));     // int32 words where the plan's digit bound allows (GemmPlan::dig_i32)
     if (!t3 || !S) return fail(CN_ERR_HIP, "internal: scratch exhausted in cn_square_gemm");
-    const size_t mark = ctx->soff;
     const uint64_t *pa = I->d + ii * I->item_words;
-    for (uint32_t s = 0; s < cnt; s += ch) {                                      // the products, all of them, before the first sum
-        const uint32_t c = std::min(ch, cnt - s);
-        ctx->soff = mark;
-        CHECK(do_multiply(ctx, pa + (size_t)s * I->item_words, 1, pa + (size_t)s * I->item_words, 1, t3 + (size_t)s * 3 * kn, c));
-    }
+    CHECK(mul_chunks(ctx, B, cnt, false, [&](uint32_t s, uint32_t c) {           // the products, all of them, before the first sum
+        return do_multiply(ctx, pa + (size_t)s * I->item_words, 1, pa + (size_t)s * I->item_words, 1, t3 + (size_t)s * 3 * kn, c);
+    }));
     CHECK(run_gemm_plan(ctx, P, P.dev, nullptr, OB, oi, t3));                     // components 0 and 1 (+ bias) straight into the outputs
     CHECK(cn_l_digit_gemm(ctx, DigitGemmLaunch::of(P, P.dev, t3 + 2 * kn, 3 * kn, P.dev, S)));
     uint64_t *o = OB->d + oi * OB->item_words;
@@ -592,23 +562,8 @@ API_END }
 // 888-900) form out = sum_k Relinearize(Multiply(a_k, b_k)).  With ct_k = (d0_k + KS0(d2_k), d1_k + KS1(d2_k)) this is the identity above with unit weights:
 //   out = (sum_k d0_k, sum_k d1_k) + KS(S),   S_(l,d) = sum_k digit_(l,d)(d2_k)   - the digits cut per product, before the sum: the reference's words,
 // K multiplies and ONE key switch per output instead of K.  k_product_sum forms the three sums in one pass over the products.
-// The fused form runs when square_gemm_ctx_ok holds, "mul_sum" is on, K >= MUL_SUM_MIN_K, S is a lazy value the KsDigits kernels take (K (2^dbc - 1) below every
-// q_j / 2 and below 2^52), the kernel's 64-bit accumulators hold the sums of components 0 and 1 exactly (K (q_max - 1) < 2^64), its digit registers hold every limb's
-// digits (at most PRODUCT_SUM_MAX_DIGITS of at most 31 bits) and the scratch limit leaves room for the products of one output; anything else takes the literal
-// sequence - cn_mul_relin per term into a temporary, AddMany per output - inside the same call.
-static bool mul_sum_fused_ok(cn_ctx *ctx, uint32_t K) {
-    if (!ctx->mul_sum || K < MUL_SUM_MIN_K || !square_gemm_ctx_ok(ctx)) return false;
-    const int dbc = ctx->hc.dbc;
-    if (dbc < 1 || dbc > 31) return false;
-    const unsigned __int128 s = (unsigned __int128)K * ((1ull << dbc) - 1);
-    if (s >= ((unsigned __int128)1 << 52)) return false;
-    const uint64_t qmax = cn_mod_range(ctx->hc, 0, ctx->hc.k).qmax;
-    for (uint32_t j = 0; j < ctx->hc.k; j++) {
-        if (s >= ctx->hc.q[j].q / 2) return false;
-        if (ctx->hc.rl_dig[j] > PRODUCT_SUM_MAX_DIGITS) return false;
-    }
-    return (unsigned __int128)K * (qmax - 1) < ((unsigned __int128)1 << 64) && !(ctx->hc.n & 511);      // PRODUCT_SUM_MAX_TERMS: floor((2^64 - 1) / (q_max - 1))
-}
+// The fused form runs when mul_sum_fused_ok holds (cn_mul_plan.h: the switches, K and the kernel's numeric bounds) and the scratch limit leaves room for the products
+// of one output (mul_sum_batch); anything else takes the literal sequence - cn_mul_relin per term into a temporary, AddMany per output - inside the same call.
 // AddMany of the K terms of every output out of the temporary of the literal sequence (term k of output i at k * count + i): one table, one launch per output
 static int add_many_terms(cn_ctx *ctx, Buffer *T, uint32_t K, Buffer *O, uint32_t oi, uint32_t count) {
     std::vector<uint32_t> idx((size_t)count * K);
@@ -651,13 +606,11 @@ extern "C" int cn_mul_relin_sum(cn_ctx *ctx, const cn_handle *a, const uint32_t 
         if (!rc) { ctx->st.AddMany += count; ctx->st.AddManyItemCount += count; }
         return rc;
     }
-    // outputs per group: the products [output][term][3][k][N], S [output][rl_tot][N] and the two address tables of a group beside the scratch of one product
-    const size_t per = mul_scratch_per_ct(ctx, false);
-    const bool s32 = ctx->digit_i32 && cn_digit_sum_fits_i32(K, ctx->hc.dbc);      // unit weights: K (2^dbc - 1) <= 2^31 - 1 - S as int32 words
-    const size_t sw = s32 ? 4 : 8;
-    const size_t per_out = (size_t)K * 3 * kn * 8 + (size_t)tot * n * sw + (size_t)K * 16, slack = 4 * 256 + 8192;
-    const size_t g_fit = ctx->smax > per + slack ? (ctx->smax - per - slack) / per_out : 0;
-    if (!mul_sum_fused_ok(ctx, K) || !g_fit) {                                    // the literal sequence: Multiply + Relinearize per term into a temporary, AddMany per output
+    const MulSwitches sw = mul_switches(ctx);
+    const MulSumBatch G = mul_sum_batch(ctx->hc, sw, K, count);                   // outputs per group, S as int32 words
+    const bool s32 = G.s32;
+    const uint32_t g = G.group;
+    if (!mul_sum_fused_ok(ctx->hc, sw, K) || !g) {                                    // the literal sequence: Multiply + Relinearize per term into a temporary, AddMany per output
         cn_handle tmp = 0;
         CHECK(alloc_buf(ctx, 0, K * count, 2, &tmp));
         int rc = 0;
@@ -668,15 +621,13 @@ extern "C" int cn_mul_relin_sum(cn_ctx *ctx, const cn_handle *a, const uint32_t 
         const int rf = free_body(ctx, tmp);
         return rc ? rc : rf;
     }
-    const uint32_t g = (uint32_t)std::min<size_t>(count, g_fit);
     std::vector<const uint64_t *> ha((size_t)g * K), hb((size_t)g * K);
     for (uint32_t o0 = 0; o0 < count; o0 += g) {                                  // the groups, one after the other
         const uint32_t go = std::min(g, count - o0), np = go * K;
-        const size_t fixed = al((size_t)np * 3 * kn * 8) + al((size_t)go * tot * n * sw) + 2 * al((size_t)np * 8) + 8192;
-        const uint32_t ch = (uint32_t)std::min<size_t>(np, std::max<size_t>(1, (ctx->smax - std::min(ctx->smax, fixed)) / per));
-        CHECK(ensure_scratch(ctx, fixed + per * ch + 4096));
+        const MulBatch B = mul_batch(ctx->hc, sw, MUL_AT_SUM_GROUP, np, false, go, s32);
+        CHECK(ensure_scratch(ctx, B.ensure(B.chunk)));
         uint64_t *t3 = salloc<uint64_t>(ctx, (size_t)np * 3 * kn);
-        void *S = salloc<char>(ctx, (size_t)go * tot * n * sw);
+        void *S = salloc<char>(ctx, (size_t)go * tot * n * (s32 ? 4 : 8));
         if (!t3 || !S) return fail(CN_ERR_HIP, "internal: scratch exhausted in cn_mul_relin_sum");
         for (uint32_t i = 0; i < go; i++) for (uint32_t kk = 0; kk < K; kk++) {
             const Buffer *A = getbuf(ctx, a[kk], 0), *B = getbuf(ctx, b[kk], 0);
@@ -685,12 +636,9 @@ extern "C" int cn_mul_relin_sum(cn_ctx *ctx, const cn_handle *a, const uint32_t 
         }
         const uint64_t **da, **db;
         CHECK(upload_tmp(ctx, ha.data(), np, &da)); CHECK(upload_tmp(ctx, hb.data(), np, &db));
-        const size_t mark = ctx->soff;
-        for (uint32_t s = 0; s < np; s += ch) {                                   // the products, all of them, before the sum
-            const uint32_t c = std::min(ch, np - s);
-            ctx->soff = mark;
-            CHECK(do_multiply(ctx, nullptr, 1, nullptr, 1, t3 + (size_t)s * 3 * kn, c, da + s, db + s));
-        }
+        CHECK(mul_chunks(ctx, B, np, false, [&](uint32_t s, uint32_t c) {        // the products, all of them, before the sum
+            return do_multiply(ctx, nullptr, 1, nullptr, 1, t3 + (size_t)s * 3 * kn, c, da + s, db + s);
+        }));
         uint64_t *o = O->d + (size_t)(oi + o0) * O->item_words;
         CHECK(cn_l_product_sum(ctx, ProductSumLaunch{t3, K, o, S, go, s32}));     // (sum d0, sum d1) straight into the outputs, the digit sums into S
         CHECK(do_keyswitch(ctx, ctx->rlk, KsCall::relin_digits(S, s32, o, kn, go).to(o)));

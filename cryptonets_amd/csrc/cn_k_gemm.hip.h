@@ -740,7 +740,7 @@ __global__ void __launch_bounds__(256, 2) k_digit_gemm_mfma(const uint64_t *__re
 // them over workgroups: components 0 and 1 would be summed twice.  Terms in sets of four, two register sets ping-pong (k_digit_gemm): twelve 16-byte loads per
 // thread in flight before the first use; whole pairs of sets run without a branch, the at most seven terms behind them in a tail; a load behind the last term repeats it.
 // Accumulators are plain 64-bit integers: the host admits K (q_l - 1) < 2^64 for every l (components 0 and 1, one reduction mod q_l per stored word) and
-// K (2^dbc - 1) < 2^52 (digit sums: exact as doubles, lazy values the KsDigits kernels take) - PRODUCT_SUM_MAX_TERMS / mul_sum_fused_ok, cn_eval.hip.
+// K (2^dbc - 1) < 2^52 (digit sums: exact as doubles, lazy values the KsDigits kernels take) - PRODUCT_SUM_MAX_TERMS / mul_sum_fused_ok, cn_mul_plan.h.
 typedef uint64_t ps_u64x2 __attribute__((ext_vector_type(2)));
 typedef double ps_f64x2 __attribute__((ext_vector_type(2)));
 DEV uint64_t ps_reduce(uint64_t x, const DMod &m) {              // x mod q for any 64-bit x: r1 = floor(2^64 / q), the quotient estimate is low by at most one

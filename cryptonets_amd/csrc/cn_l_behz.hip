@@ -5,13 +5,13 @@
 
 // NB = primes of the auxiliary base B (the auxiliary limbs are B then m_sk): k (SEAL's shape, and the small base where it is large enough)
 // or k + 1 (N = 16384 with 7 - 8 data primes of 48-49 bits: one more small prime makes the Shenoy-Kumaresan bound hold)
-template <int K, int NB> static void launch_extend(cn_ctx *c, const uint64_t *src, uint32_t stride, const uint64_t *const *tab, uint64_t *aq, uint64_t *ab, uint32_t cnt) {
-    if (c->hc.behz_f64 && c->opt.f64) hipLaunchKernelGGL((k_behz_extend_f64<K, NB>), dim3(cnt * 2 * c->chunks), dim3(c->bs), 0, c->stream, src, stride, tab, aq, ab, c->dc, c->chunks);
+template <int K, int NB> static void launch_extend(cn_ctx *c, const uint64_t *src, uint32_t stride, const uint64_t *const *tab, uint64_t *aq, uint64_t *ab, uint32_t cnt, bool f64) {
+    if (f64) hipLaunchKernelGGL((k_behz_extend_f64<K, NB>), dim3(cnt * 2 * c->chunks), dim3(c->bs), 0, c->stream, src, stride, tab, aq, ab, c->dc, c->chunks);
     else hipLaunchKernelGGL((k_behz_extend<K, NB>), dim3(cnt * 2 * c->chunks), dim3(c->bs), 0, c->stream, src, stride, tab, aq, ab, c->dc, c->chunks);
 }
-template <int K, int NB> static void launch_floor(cn_ctx *c, const uint64_t *dq, const uint64_t *db, uint64_t *out, uint32_t cnt, bool lazy) {
+template <int K, int NB> static void launch_floor(cn_ctx *c, const uint64_t *dq, const uint64_t *db, uint64_t *out, uint32_t cnt, bool f64, bool lazy) {
     if (lazy) hipLaunchKernelGGL((k_behz_floor_f64<K, NB, true>), dim3(cnt * 3 * c->chunks), dim3(c->bs), 0, c->stream, dq, db, out, c->dc, c->chunks);
-    else if (c->hc.behz_f64 && c->opt.f64) hipLaunchKernelGGL((k_behz_floor_f64<K, NB>), dim3(cnt * 3 * c->chunks), dim3(c->bs), 0, c->stream, dq, db, out, c->dc, c->chunks);
+    else if (f64) hipLaunchKernelGGL((k_behz_floor_f64<K, NB>), dim3(cnt * 3 * c->chunks), dim3(c->bs), 0, c->stream, dq, db, out, c->dc, c->chunks);
     else hipLaunchKernelGGL((k_behz_floor<K, NB>), dim3(cnt * 3 * c->chunks), dim3(c->bs), 0, c->stream, dq, db, out, c->dc, c->chunks);
 }
 #define DISPATCH_K(fn, ...) do { \
@@ -25,15 +25,15 @@ template <int K, int NB> static void launch_floor(cn_ctx *c, const uint64_t *dq,
         default: return cn_fail(CN_ERR_ARG, "internal: auxiliary base of k + 1 primes for k = %u", c->hc.k); } \
     else return cn_fail(CN_ERR_ARG, "internal: auxiliary base size"); } while (0)
 
-int cn_l_behz_extend(cn_ctx *c, const uint64_t *src, uint32_t stride, const uint64_t *const *src_tab, uint64_t *aq, uint64_t *ab, uint32_t cnt) {
-    DISPATCH_K(launch_extend, c, src, stride, src_tab, aq, ab, cnt);
+int cn_l_behz_extend(cn_ctx *c, const uint64_t *src, uint32_t stride, const uint64_t *const *src_tab, uint64_t *aq, uint64_t *ab, uint32_t cnt, bool f64) {
+    DISPATCH_K(launch_extend, c, src, stride, src_tab, aq, ab, cnt, f64);
     HIPCHK(hipGetLastError()); cn_launch_count(c);
     return 0;
 }
-// lazy: dq / db hold the lazy-FP64 hand-off words of an FP64 tensor kernel (cn_behz_lazy(c) must hold), else canonical residues
-int cn_l_behz_floor(cn_ctx *c, const uint64_t *dq, const uint64_t *db, uint64_t *out, uint32_t cnt, bool lazy) {
-    if (lazy && !cn_behz_lazy(c)) return cn_fail(CN_ERR_ARG, "internal: lazy tensor words without the FP64 floor");
-    DISPATCH_K(launch_floor, c, dq, db, out, cnt, lazy);
+// f64, lazy: the plan's choice (MulPlan::behz_f64, MulPlan::lazy).  lazy: dq / db hold the lazy-FP64 hand-off words of an FP64 tensor kernel, else canonical residues
+int cn_l_behz_floor(cn_ctx *c, const uint64_t *dq, const uint64_t *db, uint64_t *out, uint32_t cnt, bool f64, bool lazy) {
+    if (lazy && !f64) return cn_fail(CN_ERR_ARG, "internal: lazy tensor words without the FP64 floor");
+    DISPATCH_K(launch_floor, c, dq, db, out, cnt, f64, lazy);
     HIPCHK(hipGetLastError()); cn_launch_count(c);
     return 0;
 }

@@ -52,18 +52,16 @@ static bool intt_tensor(cn_ctx *c, const uint64_t *A, const uint64_t *B, uint64_
     BY_SIZE(l_intt_tensor, c, A, B, D, cnt, base_off, Lm, lazy)
 }
 
-// squaring: forward transforms, tensor and inverse transforms of one (ciphertext, limb) in ONE kernel (FP64 policies)
-template <int L> static void l_square_fused(cn_ctx *c, const uint64_t *A, size_t astride, const uint64_t *const *atab, uint64_t *D, uint32_t cnt, uint32_t base_off, uint32_t Lm) {
+// squaring: forward transforms, tensor and inverse transforms of one (ciphertext, limb) in ONE kernel (FP64 policies); which one: MulBase (cn_mul_plan.h)
+template <int L> static void l_square_fused(cn_ctx *c, const uint64_t *A, size_t astride, const uint64_t *const *atab, uint64_t *D, uint32_t cnt, uint32_t base_off, uint32_t Lm, const MulBase &b) {
     if constexpr (kF64) {
         const size_t lds = (size_t)ntt_lds_words(1u << L) * 8;
         if constexpr (L <= 13) {
-            // pipelined resident kernel (k_square_pipe): one workgroup per CU and modulus for the whole launch; pays once a workgroup squares several blocks
-            const uint32_t per_limb = std::min<uint32_t>((uint32_t)std::max(1, c->cus) / Lm, cnt);
-            if (per_limb >= 1 && (c->opt.sq_pipe == 2 || (c->opt.sq_pipe && cnt >= 4 * per_limb))) {
-                hipLaunchKernelGGL((k_square_pipe<L, AR>), dim3(per_limb * Lm), dim3(NttPlan<L>::NT), lds + ((size_t)8 << L), c->stream, A, astride, atab, D, c->dc, base_off, Lm, cnt);
+            if (b.sq == SQ_PIPE) {
+                hipLaunchKernelGGL((k_square_pipe<L, AR>), dim3(b.per_limb * Lm), dim3(NttPlan<L>::NT), lds + ((size_t)8 << L), c->stream, A, astride, atab, D, c->dc, base_off, Lm, cnt);
                 return;
             }
-            if (c->opt.sq_lds) {             // NTT-form operand parked in LDS (one workgroup per CU) instead of in the outputs' place (two)
+            if (b.sq == SQ_LDS) {
                 hipLaunchKernelGGL((k_square_fused<L, AR, true>), dim3(cnt * Lm), dim3(NttPlan<L>::NT), lds + ((size_t)8 << L), c->stream, A, astride, atab, D, c->dc, base_off, Lm);
                 return;
             }
@@ -71,9 +69,9 @@ template <int L> static void l_square_fused(cn_ctx *c, const uint64_t *A, size_t
         hipLaunchKernelGGL((k_square_fused<L, AR>), dim3(cnt * Lm), dim3(NttPlan<L>::NT), lds, c->stream, A, astride, atab, D, c->dc, base_off, Lm);
     }
 }
-static bool square_fused(cn_ctx *c, const uint64_t *A, size_t astride, const uint64_t *const *atab, uint64_t *D, uint32_t cnt, uint32_t base_off, uint32_t Lm) {
-    if (!kF64) return false;
-    BY_SIZE(l_square_fused, c, A, astride, atab, D, cnt, base_off, Lm)
+static bool square_fused(cn_ctx *c, const uint64_t *A, size_t astride, const uint64_t *const *atab, uint64_t *D, uint32_t cnt, uint32_t base_off, uint32_t Lm, const MulBase &b) {
+    if (!kF64 || (b.sq != SQ_PLAIN && c->hc.logn > 13)) return false;
+    BY_SIZE(l_square_fused, c, A, astride, atab, D, cnt, base_off, Lm, b)
 }
 
 // dense MultiplyPlain in two launches (k_lift_ntt, k_mul_plain_fused).  pt null: `lift` holds the NTT form already (an NTT-form plaintext array: the product

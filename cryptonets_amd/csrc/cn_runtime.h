@@ -5,6 +5,7 @@
 #include "../../include/cnhip.h"
 #include "cn_policy.h"
 #include "cn_ks_plan.h"
+#include "cn_mul_plan.h"
 #include "cn_submit.h"
 #include <hip/hip_runtime.h>
 #include <atomic>
@@ -300,7 +301,8 @@ struct RrOps {                // register-radix kernels of one arithmetic policy
     int (*set_attrs)(uint32_t logn, size_t lds);
     bool (*ntt)(cn_ctx *c, uint64_t *data, uint32_t limbs, uint32_t base_off, uint32_t nmod, int inverse);
     bool (*intt_tensor)(cn_ctx *c, const uint64_t *A, const uint64_t *B, uint64_t *D, uint32_t cnt, uint32_t base_off, uint32_t Lm, bool lazy);   // lazy (FP64 policies): D as lazy-FP64 hand-off words
-    bool (*square_fused)(cn_ctx *c, const uint64_t *A, size_t astride, const uint64_t *const *atab, uint64_t *D, uint32_t cnt, uint32_t base_off, uint32_t Lm);   // FP64 policies; D: lazy-FP64 hand-off words
+    // FP64 policies; D: lazy-FP64 hand-off words; b: the planned kernel of the base (MulBase, cn_mul_plan.h)
+    bool (*square_fused)(cn_ctx *c, const uint64_t *A, size_t astride, const uint64_t *const *atab, uint64_t *D, uint32_t cnt, uint32_t base_off, uint32_t Lm, const MulBase &b);
     bool (*mul_plain_fused)(cn_ctx *c, const uint64_t *pt, uint32_t pitch, uint32_t npt, uint64_t *lift, const uint64_t *src, size_t sstride, uint32_t pstride,
                             uint64_t *out, uint32_t count, uint32_t polys);            // pt null: `lift` is the NTT form already; src null: the lift alone
     bool (*enc_tail)(cn_ctx *c, const uint64_t *u, const uint64_t *pt, uint32_t pts, uint64_t *out, uint32_t cnt, const int8_t *noise, const void *tab);   // U64, F64; tab: EncTab[cnt] or null
@@ -317,11 +319,9 @@ extern const RrOps cn_rr_u64, cn_rr_f64, cn_rr_f64l;
 extern const KsOps cn_ks_u64, cn_ks_f64, cn_ks_f64l;
 
 // BEHZ element-wise steps (cn_l_behz.hip); src_tab: one source address per ciphertext instead of src + ct*stride*2kN
-int cn_l_behz_extend(cn_ctx *c, const uint64_t *src, uint32_t stride, const uint64_t *const *src_tab, uint64_t *aq, uint64_t *ab, uint32_t cnt);
-int cn_l_behz_floor(cn_ctx *c, const uint64_t *dq, const uint64_t *db, uint64_t *out, uint32_t cnt, bool lazy);
-// the FP64 floor runs, so FP64 tensor kernels may hand it their inverse transforms' registers (lazy_word, cn_dev_common.hip.h): both element-wise BEHZ steps
-// and - every modulus being below 2^49 - the transforms of BOTH bases are on an FP64 policy
-inline bool cn_behz_lazy(const cn_ctx *c) { return c->hc.behz_f64 && c->opt.f64; }
+// f64, lazy: MulPlan::behz_f64 and MulPlan::lazy of the chain (cn_mul_plan.h) - the FP64 kernels; dq / db hold the lazy-FP64 hand-off words of an FP64 tensor kernel
+int cn_l_behz_extend(cn_ctx *c, const uint64_t *src, uint32_t stride, const uint64_t *const *src_tab, uint64_t *aq, uint64_t *ab, uint32_t cnt, bool f64);
+int cn_l_behz_floor(cn_ctx *c, const uint64_t *dq, const uint64_t *db, uint64_t *out, uint32_t cnt, bool f64, bool lazy);
 
 // scalar GEMM (cn_l_gemm.hip).  Relative addressing: input / output ciphertext = base + index * ctw; absolute (ABS): the tables hold
 // device addresses (deferred per-ciphertext calls: every ciphertext is its own array), 0 = padded tap / no output.
@@ -368,8 +368,7 @@ inline uint32_t digit_gemm_mfma_group(uint32_t P) { return P <= 2 ? 3u : 2u; }  
 int cn_l_digit_gemm(cn_ctx *c, const DigitGemmLaunch &g);
 // sum of unrelinearized products (cn_mul_relin_sum, k_product_sum): prod [outputs][K][3][k][N] -> components 0 and 1 summed mod q_l into out [outputs][2][k][N],
 // the digit sums of component 2 into S [outputs][rl_tot][N] doubles (i32: int32 words).  Every source limb has at most PRODUCT_SUM_MAX_DIGITS digits of at most 31 bits
-struct ProductSumLaunch { const uint64_t *prod; uint32_t K; uint64_t *out; void *S; uint32_t outputs; bool i32 = false; };
-static const uint32_t PRODUCT_SUM_MAX_DIGITS = 8;
+struct ProductSumLaunch { const uint64_t *prod; uint32_t K; uint64_t *out; void *S; uint32_t outputs; bool i32 = false; };      // (PRODUCT_SUM_MAX_DIGITS: cn_mul_plan.h)
 int cn_l_product_sum(cn_ctx *c, const ProductSumLaunch &g);
 // sums of plaintext x ciphertext products (cn_mul_plain_sum; cn_l_diag.hip, k_mul_plain_sum): group g < groups = terms [grp_off[g], grp_off[g + 1]), term e = plaintext
 // pt + e N (coefficients mod t) times the NTT-form ciphertext ctn + slot[e] 2kN; out [groups][2][k][N].  grp_off / slot: device memory.  policy: cn_policy of the q limbs

@@ -19,7 +19,7 @@ pytestmark = pytest.mark.gpu
 
 KS_DIGIT_MAX_BLOCKS = 10      # (ciphertext, limb) blocks up to which the two-launch key switch has a workgroup per digit (cn_ks_plan.h: KsSwitches::digit_max_blocks)
 KS_WIDE_MAX_BLOCKS = 160      # ... up to which a key switch runs as two launches at all (KsSwitches::wide_max_blocks)
-SQ_HALVES_MIN = 512           # ciphertexts from which cn_mul_relin runs in parts over two streams (cn_api_shared.h)
+SQ_HALVES_MIN = 512           # ciphertexts from which cn_mul_relin runs in parts over two streams (cn_mul_plan.h)
 SETS = ("tiny", "c3")
 LARGEST = {"tiny": 700, "c3": 845}             # c3: the squaring layer of CryptoNets
 SETTINGS = [(wide, halves) for wide in (-1, 0, 1, 2) for halves in (0, 1)]

@@ -330,6 +330,11 @@ def test_the_call_sees_the_result_of_a_queued_add(defer):
 
 
 # ------------------------------------------------------------------ 10. groups
+# (kernel_launches, Multiplication, Relinarization, mul_sum_groups) of the call below on the commit before cn_mul_plan.h (profiles/mul_plan_refactor.md): the groups
+# and the chunks of products inside a group are mul_batch's, a count that moves is a boundary that moved
+GROUPED_LITERALS = (252, 54, 54, 3)
+
+
 def test_outputs_run_in_groups_when_the_scratch_limit_is_small():
     """K = 9, count = 6 on tiny: the products of one output are 9 * 3 * 3 * 1024 * 8 = 663 552 bytes, its digit sums 12 * 1024 * 8 = 98 304; a limit of 0.00224 GiB
     (2.4 MB) holds two or three outputs beside the scratch of one multiply (0.4-0.5 MB), so the six outputs take at least two groups"""
@@ -352,12 +357,14 @@ def test_outputs_run_in_groups_when_the_scratch_limit_is_small():
         A, B = operands(o, K, count, 0, 0x620)
         ha, hb = [upload(g, A[k]) for k in range(K)], [upload(g, B[k]) for k in range(K)]
         out = g.ct_alloc(count)
-        before = g.get_option("mul_sum_fused")
+        before, s0 = g.get_option("mul_sum_fused"), g.stats()
         g.mul_relin_sum(ha, None, hb, None, 0, out, 0, count)
-        groups = g.get_option("mul_sum_groups")
-        print("mul_sum_groups", groups)
+        groups, s1 = g.get_option("mul_sum_groups"), g.stats()
+        moved = tuple(s1[c] - s0[c] for c in ("kernel_launches", "Multiplication", "Relinarization")) + (groups,)
+        print("mul_sum_groups", groups, "moved", moved)
         assert g.get_option("mul_sum_fused") == before + 1
         assert groups >= 2
+        assert moved == GROUPED_LITERALS
         assert np.array_equal(g.ct_download(out, 0, count), expected(o, A, B, 0))
     finally:
         g.close()

@@ -8,7 +8,7 @@ test_square_gemm inside the reused helpers).  The helpers of the other modules a
 test_gpu_ptn looks its context up by name in conftest.PARAMS, so the row-dot family restates it here on the cell's own context - and compares every row with
 the oracle's chain, not only the first.
 
-FORM - which form of a call must run in a cell - is written by hand below from cn_policy.h, cn_ks_plan.h (the key switch: ks_form) and the launchers and asserted through the library's counters, so a
+FORM - which form of a call must run in a cell - is written by hand below from cn_policy.h, cn_ks_plan.h (the key switch: ks_form), cn_mul_plan.h (the gates of family f) and the launchers and asserted through the library's counters, so a
 silent fall-back cannot pass as coverage:
   kernel     the size-templated kernel (named in the rule)
   composed   other calls of the library do the work (named in the rule)
@@ -96,8 +96,8 @@ def form(family, policy, n, width):
         return "kernel", "k_mul_plain_bcast<L, AR, true>"
     if family in ("square_gemm", "mul_relin_sum"):
         if policy in FP64 and n <= 8192 and width == 10:
-            return "kernel", "square_gemm_ctx_ok (cn_eval.hip: FP64 policy, N <= 8192) and digit width <= 30 / 31 bits: one key switch per output"
-        return "literal", "square_gemm_ctx_ok / GemmPlan::dig (dbc <= 30) / mul_sum_fused_ok (dbc <= 31) fail: cn_mul_relin + GEMM or AddMany"
+            return "kernel", "square_gemm_ctx_ok (cn_mul_plan.h: FP64 policy, N <= 8192) and digit width <= 30 / 31 bits: one key switch per output"
+        return "literal", "square_gemm_ctx_ok / GemmPlan::dig (dbc <= 30) / mul_sum_fused_ok (dbc <= 31; cn_mul_plan.h) fail: cn_mul_relin + GEMM or AddMany"
     raise KeyError(family)
 
 
