@@ -375,6 +375,11 @@ extern "C" int cn_set_option(cn_ctx *ctx, const char *name, int value) { API_BOD
     if (!strcmp(name, "defer_square_gemm")) { ctx->defer_square_gemm = value != 0; return 0; }     // (LOCK has settled what the queue held back under the old value)
     if (!strcmp(name, "digit_mfma")) { ctx->digit_mfma = value != 0; defer_square_drop_plans(ctx); return 0; }     // the digit GEMM of plans made AFTER the call: matrix cores where eligible / FP64 (cn_eval.hip)
     if (!strcmp(name, "digit_i32")) { ctx->digit_i32 = value != 0; defer_square_drop_plans(ctx); return 0; }       // the digit sums of plans made AFTER the call (and of cn_mul_relin_sum): int32 words where they fit / doubles
+    if (!strcmp(name, "sg_prefloor")) {          // cn_square_gemm: one floor tail per dense output for components 0 and 1 - 0 never, 1 where the gate allows, 2 also below SG_PREFLOOR_MIN_K (cn_mul_plan.h)
+        if (value < 0 || value > 2) return fail(CN_ERR_ARG, "sg_prefloor: 0, 1 or 2");
+        ctx->sg_prefloor_mode = value;
+        return 0;
+    }
     if (!strcmp(name, "mul_sum")) { ctx->mul_sum = value != 0; return 0; }       // cn_mul_relin_sum: one key switch per output where it can / always the literal sequence (cn_eval.hip)
     if (!strcmp(name, "ptn_order")) {            // k_mul_ptn_sum, workgroup order: 0 limb-major, 1 limb = workgroup index mod k (cn_l_ptn.hip)
         if (value < 0 || value > 1) return fail(CN_ERR_ARG, "ptn_order: 0 or 1");
@@ -400,11 +405,14 @@ extern "C" int cn_get_option(cn_ctx *ctx, const char *name, int *value) { API_BO
     else if (!strcmp(name, "digit_i32")) *value = ctx->digit_i32;
     else if (!strcmp(name, "defer_square_gemm")) *value = ctx->defer_square_gemm;
     else if (!strcmp(name, "mul_sum")) *value = ctx->mul_sum;
+    else if (!strcmp(name, "sg_prefloor")) *value = ctx->sg_prefloor_mode;
     // read-only diagnostics: choices the library made and counters (tests)
     else if (!strcmp(name, "pin_laps")) *value = (int)ctx->pin_laps;                      // laps of the pinned upload ring (each one waits for the stream)
     else if (!strcmp(name, "ready_handles")) *value = (int)ctx->ready->size();          // allocated single-ciphertext arrays waiting for a lock-free cn_ct_alloc
     else if (!strcmp(name, "folded_zero_encryptions")) *value = (int)std::min<uint64_t>(ctx->folded_zero, 0x7fffffff);    // zero encryptions folded so far
     else if (!strcmp(name, "square_gemm_fused")) *value = (int)std::min<uint64_t>(ctx->sg_fused, 0x7fffffff);
+    else if (!strcmp(name, "square_gemm_prefloor")) *value = (int)std::min<uint64_t>(ctx->sg_prefloor, 0x7fffffff);       // ... of which with one floor tail per dense output
+    else if (!strcmp(name, "sg_prefloor_min_k")) *value = (int)SG_PREFLOOR_MIN_K;                                           // smallest K that takes that form under "sg_prefloor" = 1
     else if (!strcmp(name, "defer_square_gemm_fused")) *value = (int)std::min<uint64_t>(ctx->dsg_fused, 0x7fffffff);       // groups of queued scalar products run on deferred squarings
     else if (!strcmp(name, "mul_sum_fused")) *value = (int)std::min<uint64_t>(ctx->ms_fused, 0x7fffffff);                 // cn_mul_relin_sum calls that ran one key switch per output
     else if (!strcmp(name, "mul_sum_groups")) *value = (int)ctx->ms_groups;                                                // output groups of the last cn_mul_relin_sum (0: the literal sequence)

@@ -170,7 +170,11 @@ template <class FM, class FK> static int pipelined_halves(cn_ctx *ctx, uint32_t 
     HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
     return 0;
 }
-int do_multiply(cn_ctx *ctx, const uint64_t *a, uint32_t astride, const uint64_t *b, uint32_t bstride, uint64_t *out3, uint32_t cnt, const uint64_t *const *atab = nullptr, const uint64_t *const *btab = nullptr);
+// keep (cn_square_gemm's pre-floor form, squarings on the fused kernels): the tensor words stay in the caller's arrays dq / db [cnt][3][k | kb][N] - components 0 and 1
+// of db in NTT form (MulBase::ntt01) - and only component 2 is floored into out3
+struct MulKeep { uint64_t *dq, *db; };
+int do_multiply(cn_ctx *ctx, const uint64_t *a, uint32_t astride, const uint64_t *b, uint32_t bstride, uint64_t *out3, uint32_t cnt, const uint64_t *const *atab = nullptr, const uint64_t *const *btab = nullptr,
+                const MulKeep *keep = nullptr);
 int ensure_ks_part(cn_ctx *ctx, size_t need);
 KsSwitches ks_switches(const cn_ctx *ctx);
 KsPlan ks_plan(const cn_ctx *ctx, const KsKey &key, uint32_t cnt, int galois);

@@ -293,7 +293,7 @@ API_END }
 // the switches of this context that the multiply planner reads (cn_mul_plan.h): the only place that copies them out of a context for the multiply family
 MulSwitches mul_switches(const cn_ctx *ctx) {
     return {ctx->opt.f64, ctx->opt.sq_fused, ctx->opt.sq_pipe, ctx->opt.sq_lds, ctx->opt.sq_halves, ctx->mul_sum, ctx->digit_i32, ctx->defer_square_gemm, rr_kernels(ctx), rr_kernels(ctx, 13),
-            ctx->cus, ctx->capturing.load(), ctx->smax, ctx->rlk.d != nullptr, ctx->rlk.f64, ks_switches(ctx)};
+            ctx->cus, ctx->capturing.load(), ctx->smax, ctx->rlk.d != nullptr, ctx->rlk.f64, ks_switches(ctx), ctx->sg_prefloor_mode};
 }
 // the context's second stream (squaring overlap): created on first use, kept only if it runs beside the context's own stream (a hardware queue of its own)
 bool aux_stream_ready(cn_ctx *ctx) {
@@ -318,13 +318,17 @@ bool aux_stream_ready(cn_ctx *ctx) {
 // a, b: pointers to first operand ciphertext (size 2); out3: [cnt][3][k][N]; scratch must be ensured by caller.  atab / btab: one
 // operand address per ciphertext instead of a + ct*astride*ctw (deferred per-ciphertext calls; atab == btab: squarings).  What is launched: MulPlan (cn_mul_plan.h)
 int do_multiply(cn_ctx *ctx, const uint64_t *a, uint32_t astride, const uint64_t *b, uint32_t bstride, uint64_t *out3, uint32_t cnt,
-                       const uint64_t *const *atab, const uint64_t *const *btab) {
+                       const uint64_t *const *atab, const uint64_t *const *btab, const MulKeep *keep) {
     const uint32_t n = ctx->hc.n, k = ctx->hc.k, kb = ctx->hc.kb;
     const bool square = atab ? atab == btab : (a == b && astride == bstride);
-    const MulPlan p = cn_mul_plan(ctx->hc, mul_switches(ctx), square, cnt);
+    MulPlan p = cn_mul_plan(ctx->hc, mul_switches(ctx), square, cnt);
+    if (keep && (p.form != MUL_SQUARE_FUSED || !p.lazy || p.bsk.sq == SQ_PLAIN)) return fail(CN_ERR_ARG, "internal: kept tensor words without the fused squaring kernels");
+    if (keep) p.bsk.ntt01 = true;
     uint64_t *arr[MUL_ARRAYS] = {};
-    for (uint32_t i = 0; i < p.arrays; i++)
+    for (uint32_t i = 0; i < p.arrays; i++) {
+        if (keep && (p.scratch[i].id == MUL_DQ || p.scratch[i].id == MUL_DB)) { arr[p.scratch[i].id] = p.scratch[i].id == MUL_DQ ? keep->dq : keep->db; continue; }
         if (!(arr[p.scratch[i].id] = (uint64_t *)salloc<char>(ctx, p.scratch[i].bytes))) return fail(CN_ERR_HIP, "internal: scratch exhausted in multiply");
+    }
     uint64_t *const aq = arr[MUL_AQ], *const ab = arr[MUL_AB], *const bq = square ? aq : arr[MUL_BQ], *const bb = square ? ab : arr[MUL_BB], *const dq = arr[MUL_DQ], *const db = arr[MUL_DB];
     CHECK(cn_l_behz_extend(ctx, a, astride, atab, aq, ab, cnt, p.behz_f64));
     if (!square) CHECK(cn_l_behz_extend(ctx, b, bstride, btab, bq, bb, cnt, p.behz_f64));
@@ -333,7 +337,7 @@ int do_multiply(cn_ctx *ctx, const uint64_t *a, uint32_t astride, const uint64_t
         if (!rr_ops[p.q.policy]->square_fused(ctx, a, (size_t)astride * 2 * k * n, atab, dq, cnt, 0, k, p.q)) return fail(CN_ERR_ARG, no_kernel);
         if (!rr_ops[p.bsk.policy]->square_fused(ctx, ab, (size_t)2 * kb * n, nullptr, db, cnt, k, kb, p.bsk)) return fail(CN_ERR_ARG, no_kernel);
         launch_count(ctx, 2);
-        ctx->st.ntt_forward_limbs += (uint64_t)cnt * 2 * (k + kb); ctx->st.ntt_inverse_limbs += (uint64_t)cnt * 3 * (k + kb);
+        ctx->st.ntt_forward_limbs += (uint64_t)cnt * 2 * (k + kb); ctx->st.ntt_inverse_limbs += (uint64_t)cnt * (3 * k + (keep ? 1 : 3) * kb);
     } else {
         CHECK(cn_run_ntt(ctx, aq, cnt * 2 * k, 0, k, 0)); CHECK(cn_run_ntt(ctx, ab, cnt * 2 * kb, k, kb, 0));
         if (!square) { CHECK(cn_run_ntt(ctx, bq, cnt * 2 * k, 0, k, 0)); CHECK(cn_run_ntt(ctx, bb, cnt * 2 * kb, k, kb, 0)); }
@@ -350,7 +354,7 @@ int do_multiply(cn_ctx *ctx, const uint64_t *a, uint32_t astride, const uint64_t
         }
     }
     HIPCHK(hipGetLastError());
-    CHECK(cn_l_behz_floor(ctx, dq, db, out3, cnt, p.behz_f64, p.lazy));
+    if (keep) CHECK(cn_l_behz_floor_c2(ctx, dq, db, out3, cnt)); else CHECK(cn_l_behz_floor(ctx, dq, db, out3, cnt, p.behz_f64, p.lazy));
     ctx->st.Multiplication += cnt;
     return 0;
 }
@@ -517,6 +521,9 @@ int mul_relin_body(cn_ctx *ctx, cn_handle a, uint32_t ai, uint32_t astride, cn_h
 // Runs when the plan allows it (GemmPlan::dig: small weights, |S| below every q_j / 2 and 2^52), every modulus and the key are on an FP64 policy, the ring has the
 // register-radix kernels up to N = 8192 and the decomposition is the plain one; anything else takes the two separate steps inside the same call.
 // (square_gemm_fused_ok and square_gemm_ctx_ok, cn_mul_plan.h; the product loop in the chunks of mul_batch)
+// The pre-floor form (square_gemm_prefloor_ok, "sg_prefloor"): the fast floor is linear too, in the Bsk residues of the tensor and in the canonical y of its q
+// residues - so components 0 and 1 are not floored per input either: the Bsk words of d0, d1 stay in NTT form, the plan's weights sum them mod b and their y as exact
+// integers, and ONE floor tail per output (+ bias) writes what the GEMM over the floored words wrote.  Component 2 keeps its floor: its digits are cut per product.
 extern "C" int cn_square_gemm(cn_ctx *ctx, cn_handle plan, cn_handle in, uint32_t ii, cn_handle out, uint32_t oi) { TWO_LIMBS("cn_square_gemm"); API_BODY
     LOCK; GETCT(I, in, 2); GETCT(OB, out, 2);
     Buffer *PB = getbuf(ctx, plan, 2);
@@ -530,7 +537,14 @@ extern "C" int cn_square_gemm(cn_ctx *ctx, cn_handle plan, cn_handle in, uint32_
     const uint32_t n = ctx->hc.n, k = ctx->hc.k, tot = ctx->hc.rl_tot;
     const size_t kn = (size_t)k * n;
     const MulSwitches sw = mul_switches(ctx);
-    const MulBatch B = mul_batch(ctx->hc, sw, MUL_AT_SQUARE_GEMM, cnt, true, P.O, P.dig_i32);
+    MulBatch B = mul_batch(ctx->hc, sw, MUL_AT_SQUARE_GEMM, cnt, true, P.O, P.dig_i32);
+    // the pre-floor form (square_gemm_prefloor_ok, cn_mul_plan.h) where its arrays fit beside the old form's; else the old form with the old chunks
+    bool pre = B.fits && square_gemm_prefloor_ok(ctx->hc, sw, P);
+    const SgPrefloorScratch PS = square_gemm_prefloor_scratch(ctx->hc, cnt, P.O);
+    if (pre) {
+        if (B.fixed + PS.total + B.per > sw.smax) pre = false;
+        else { B.fixed += PS.total; B.chunk = (uint32_t)std::min<size_t>(cnt, (sw.smax - B.fixed) / B.per); }
+    }
     if (!square_gemm_fused_ok(ctx->hc, sw, P) || !B.fits) {                       // the two steps as they are: square + relinearize into a temporary, the GEMM from it
         cn_handle tmp = 0;
         CHECK(alloc_buf(ctx, 0, cnt, 2, &tmp));
@@ -546,9 +560,30 @@ extern "C" int cn_square_gemm(cn_ctx *ctx, cn_handle plan, cn_handle in, uint32_
     void *S = salloc<char>(ctx, (size_t)P.O * tot * n * (P.dig_i32 ? 4 : 8));     // int32 words where the plan's digit bound allows (GemmPlan::dig_i32)
     if (!t3 || !S) return fail(CN_ERR_HIP, "internal: scratch exhausted in cn_square_gemm");
     const uint64_t *pa = I->d + ii * I->item_words;
+    uint64_t *sg[SG_ARRAYS] = {};
+    if (pre) for (const auto &a : PS.scratch) if (!(sg[a.id] = (uint64_t *)salloc<char>(ctx, a.bytes))) return fail(CN_ERR_HIP, "internal: scratch exhausted in cn_square_gemm");
+    const size_t kbn = (size_t)ctx->hc.kb * n;
     CHECK(mul_chunks(ctx, B, cnt, false, [&](uint32_t s, uint32_t c) {           // the products, all of them, before the first sum
-        return do_multiply(ctx, pa + (size_t)s * I->item_words, 1, pa + (size_t)s * I->item_words, 1, t3 + (size_t)s * 3 * kn, c);
+        const MulKeep keep{sg[SG_DQ] + (size_t)s * 3 * kn, sg[SG_DB] + (size_t)s * 3 * kbn};
+        return do_multiply(ctx, pa + (size_t)s * I->item_words, 1, pa + (size_t)s * I->item_words, 1, t3 + (size_t)s * 3 * kn, c, nullptr, nullptr, pre ? &keep : nullptr);
     }));
+    if (pre) {
+        // components 0 and 1: X = the weighted sums of the NTT-form Bsk words, back to coefficients once per output; Y = the exact sums of the canonical y; one floor
+        // tail per output (+ bias) straight into the outputs.  The plan's own tables and weight fragments
+        const uint64_t *bias = nullptr;
+        if (P.has_bias) {
+            Buffer *BP = getbuf(ctx, P.bias_pt, 1);
+            if (!BP || BP->count < P.bias_count) return fail(CN_ERR_ARG, "invalid bias plaintext handle");
+            bias = BP->d;
+        }
+        CHECK(cn_l_gemm_mfma(ctx, gemm_launch(ctx, P, P.dev).inputs(sg[SG_DB], (uint32_t)(3 * kbn), 2).outputs(sg[SG_X], 0, (uint32_t)(2 * kbn)).prefloor(1)));
+        CHECK(cn_l_gemm_mfma(ctx, gemm_launch(ctx, P, P.dev).inputs(sg[SG_DQ], (uint32_t)(3 * kn), 2).outputs(sg[SG_Y], 0, (uint32_t)(2 * kn)).prefloor(2)));
+        CHECK(cn_run_ntt(ctx, sg[SG_X], P.O * 2 * ctx->hc.kb, k, ctx->hc.kb, 1));
+        CHECK(cn_l_behz_floor_out(ctx, {sg[SG_X], sg[SG_Y], (const int32_t *)(P.dev + P.off_oidx), bias, (const int32_t *)(P.dev + P.off_bidx), OB->d, oi, P.G * P.M}));
+        ctx->st.PlainMultiplication += P.nnz; ctx->st.Addition += P.nnz - P.O;
+        if (P.has_bias) ctx->st.PlainAddition += P.O;
+        ctx->sg_prefloor++;
+    } else
     CHECK(run_gemm_plan(ctx, P, P.dev, nullptr, OB, oi, t3));                     // components 0 and 1 (+ bias) straight into the outputs
     CHECK(cn_l_digit_gemm(ctx, DigitGemmLaunch::of(P, P.dev, t3 + 2 * kn, 3 * kn, P.dev, S)));
     uint64_t *o = OB->d + oi * OB->item_words;

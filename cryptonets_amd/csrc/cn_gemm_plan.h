@@ -260,7 +260,7 @@ template <class KEY> inline void gemm_digit_form(const DevConsts &hc, const Gemm
     const uint64_t dmax = (1ull << hc.dbc) - 1, lim = std::min<uint64_t>((qmin - 1) / 2, (1ull << 52) - 1) / dmax;      // sum |w| <= lim
     const uint64_t sum_max = gemm_row_sum_max(hc, gr, lim);       // the plan's digit bound is sum_max (2^dbc - 1)
     if (sum_max > lim) return;
-    L.dig = true; L.dig_mfma = L.mfma && sw.digit_mfma && hc.dbc <= 14 && !(hc.n & 255); L.dig_i32 = sw.digit_i32 && cn_digit_sum_fits_i32(sum_max, hc.dbc);
+    L.dig = true; L.sum_abs_w = sum_max; L.dig_mfma = L.mfma && sw.digit_mfma && hc.dbc <= 14 && !(hc.n & 255); L.dig_i32 = sw.digit_i32 && cn_digit_sum_fits_i32(sum_max, hc.dbc);
     if (L.dig_mfma) return;
     L.dMT = digit_gemm_tile(L.M); L.dKw = digit_gemm_rows(L.K);
     pack_gemm_f64(hc, gr, L.dMT, L.dKw, dbytes);

@@ -359,16 +359,27 @@ DEV uint32_t byte_perm(uint32_t hi, uint32_t lo, uint32_t sel) { return __builti
 #ifndef GEMM_MFMA_DEPTH
 #define GEMM_MFMA_DEPTH 2          // K steps of input words in flight beside the one being multiplied (1 or 2)
 #endif
-template <int P, bool ABS>
+// FORM (the pre-floor form of cn_square_gemm, relative addressing only; the same weight fragments and tables):
+//   GEMM_BSK: the limbs are those of the auxiliary base Bsk (kb per polynomial, moduli k .. k + kb - 1, below 2^49: SEVEN signed digits), canonical words in,
+//             canonical words out, no bias - X_o = sum_k w_ok x_k mod b on the NTT-form tensor words of components 0 and 1;
+//   GEMM_Y:   the inputs are the lazy-FP64 hand-off words of the q-side tensor; the load path forms the floor's canonical y = [x t (q/q_j)^-1]_{q_j} (k_behz_floor_f64's
+//             own expression) and the diagonals are folded to the EXACT signed 64-bit integer Y_o = sum_k w_ok y_k (two's complement; no modular fold, no bias).
+// (A pack of at most one tag type: the ciphertext form keeps its name k_scalar_gemm_mfma<P, ABS>.)
+enum { GEMM_CT = 0, GEMM_BSK = 1, GEMM_Y = 2 };
+struct GemmBskForm { static constexpr int form = GEMM_BSK; };
+struct GemmYForm { static constexpr int form = GEMM_Y; };
+template <int P, bool ABS, class... FORM_>
 __global__ void __launch_bounds__(256, 2) k_scalar_gemm_mfma(const uint64_t *__restrict__ in, const void *__restrict__ idx_, const int8_t *__restrict__ Wf,
                                                              const void *__restrict__ out_idx_, const uint64_t *__restrict__ bias, const void *__restrict__ bias_idx_,
                                                              uint64_t *__restrict__ out, const DevConsts *__restrict__ C, uint32_t G, uint32_t M, uint32_t mtiles,
                                                              uint32_t ksteps, uint32_t obase, uint32_t polys, GemmUnits U) {
+    constexpr int FORM = (GEMM_CT + ... + FORM_::form);
+    static_assert(sizeof...(FORM_) <= 1 && (FORM == GEMM_CT || !ABS), "the pre-floor forms use relative addressing");
     typedef typename GemmTab<ABS>::T TT;
     const TT *idx = (const TT *)idx_, *out_idx = (const TT *)out_idx_, *bias_idx = (const TT *)bias_idx_;
-    constexpr int ND = 6, D = ND + P - 1, NB = GEMM_MFMA_DEPTH + 1;
-    __shared__ __align__(16) uint32_t frag[NB][ND][64][4];         // [buffer][digit plane][lane][slot group q]: 6 KiB each
-    const uint32_t n = C->n, k = C->k, limbs = polys * k, ctiles = n >> 5;
+    constexpr int ND = FORM == GEMM_BSK ? 7 : 6, D = ND + P - 1, NB = GEMM_MFMA_DEPTH + 1;
+    __shared__ __align__(16) uint32_t frag[NB][ND][64][4];         // [buffer][digit plane][lane][slot group q]: 6 (7) KiB each
+    const uint32_t n = C->n, k = FORM == GEMM_BSK ? C->kb : C->k, limbs = polys * k, ctiles = n >> 5;
     // the wave number as a SCALAR: the gather-table entries of a wave's K slots are then wave-uniform and travel through the scalar cache (lgkmcnt).  As vector
     // loads they sat on vmcnt IN FRONT of the input loads that need them: every step waited for the table (vmcnt(0) - which also drained whatever input words
     // were still in flight), then for the inputs: two exposed round trips per K step, 1.9 us of them against 0.2 us of matrix instructions.
@@ -390,7 +401,7 @@ __global__ void __launch_bounds__(256, 2) k_scalar_gemm_mfma(const uint64_t *__r
     for (int d = 0; d < D; d++)
 #pragma unroll
         for (int r = 0; r < 16; r++) acc[d][r] = 0;
-    const uint64_t BIAS = 0x0000808080808080ull;
+    const uint64_t BIAS = FORM == GEMM_BSK ? 0x0080808080808080ull : 0x0000808080808080ull;
     // Requests behind the last step are NOT skipped but repeat the last step (a few words re-read from L2): with a branch around the loads the compiler's wait
     // counts at the join assume the path WITHOUT them - "at most 5 younger loads" where 11 are in flight - and every step drained the sets requested ahead.
     const uint32_t klast = ksteps - 1;
@@ -430,7 +441,15 @@ __global__ void __launch_bounds__(256, 2) k_scalar_gemm_mfma(const uint64_t *__r
         // recode: byte i of y = signed digit i; transpose the 4 words into one dword per digit plane; publish
         uint32_t lo[4], hi[4];
 #pragma unroll
-        for (int u = 0; u < 4; u++) { const uint64_t y = (x[u] + BIAS) ^ BIAS; lo[u] = (uint32_t)y; hi[u] = (uint32_t)(y >> 32); }
+        for (int u = 0; u < 4; u++) {
+            uint64_t xw = x[u];
+            if constexpr (FORM == GEMM_Y) {                                // the floor's canonical y of a lazy tensor word (an exact integer below q_j < 2^47)
+                const BzF::Mod mq = {C->qd[j], C->qinvd[j]};
+                const double yv = bz_canon(BzF::mulmod(lazy_value(xw), C->bd.fl_c1n_q[j], mq), mq);
+                xw = (uint64_t)__double_as_longlong(__dadd_rn(yv, 4503599627370496.0)) & 0x000FFFFFFFFFFFFFull;
+            }
+            const uint64_t y = (xw + BIAS) ^ BIAS; lo[u] = (uint32_t)y; hi[u] = (uint32_t)(y >> 32);
+        }
         const uint32_t ab02 = byte_perm(lo[1], lo[0], 0x06020400u), cd02 = byte_perm(lo[3], lo[2], 0x06020400u);     // (a0 b0 a2 b2), (c0 d0 c2 d2)
         const uint32_t ab13 = byte_perm(lo[1], lo[0], 0x07030501u), cd13 = byte_perm(lo[3], lo[2], 0x07030501u);     // (a1 b1 a3 b3), (c1 d1 c3 d3)
         const uint32_t hab = byte_perm(hi[1], hi[0], 0x05010400u), hcd = byte_perm(hi[3], hi[2], 0x05010400u);       // (a4 b4 a5 b5), (c4 d4 c5 d5)
@@ -440,6 +459,10 @@ __global__ void __launch_bounds__(256, 2) k_scalar_gemm_mfma(const uint64_t *__r
         fb[3][lane][wave] = byte_perm(cd13, ab13, 0x07060302u);
         fb[4][lane][wave] = byte_perm(hcd, hab, 0x05040100u);
         fb[5][lane][wave] = byte_perm(hcd, hab, 0x07060302u);
+        if constexpr (ND == 7) {                                         // (a6 b6 . .), (c6 d6 . .) -> a6 b6 c6 d6
+            const uint32_t hab6 = byte_perm(hi[1], hi[0], 0x06020602u), hcd6 = byte_perm(hi[3], hi[2], 0x06020602u);
+            fb[ND - 1][lane][wave] = byte_perm(hcd6, hab6, 0x05040100u);
+        }
         load_x(xn, nidx); load_a(afn, ks + GEMM_MFMA_DEPTH);             // in flight over the barriers and matrix instructions of the next GEMM_MFMA_DEPTH steps
         load_idx(nidx, ks + GEMM_MFMA_DEPTH + 1);
         __syncthreads();
@@ -465,9 +488,24 @@ __global__ void __launch_bounds__(256, 2) k_scalar_gemm_mfma(const uint64_t *__r
     for (int s = 0; s < NB - 1; s++)
         if (ks + s < ksteps) step(xs[s], afs[s], xs[(s + GEMM_MFMA_DEPTH) % NB], afs[(s + GEMM_MFMA_DEPTH) % NB], ks + s, frag[s]);
     if (!active) return;
+    if constexpr (FORM == GEMM_Y) {
+        // ---- the exact integer: sum_d acc_d 256^d in two's complement (|Y| < 2^63 by the plan's gate - cn_prefloor_bound_ok, cn_policy.h - so the wrapped sum is Y)
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const uint32_t row = (uint32_t)(r & 3) + 8u * (uint32_t)(r >> 2) + 4u * half, o = g * M + mt * 32 + row;
+            if (mt * 32 + row >= M) continue;
+            uint64_t v = 0;
+#pragma unroll
+            for (int d = 0; d < D; d++) v += (uint64_t)(int64_t)acc[d][r] << (8 * d);
+            if (out_idx[o] < 0) continue;
+            out[(size_t)(obase + (uint32_t)out_idx[o]) * ou + e] = v;
+        }
+        return;
+    }
     // ---- fold the diagonals: value = sum_d acc_d 256^d mod q_j (exact FP64), bias, store
-    const BzF::Mod mq = {C->qd[j], C->qinvd[j]};
-    const DMod qm = C->q[j];
+    const uint32_t jm = FORM == GEMM_BSK ? C->k + j : j;
+    const BzF::Mod mq = {C->qd[jm], C->qinvd[jm]};
+    const DMod qm = C->q[FORM == GEMM_BSK ? 0 : j];
     // three neighbouring diagonals at a time: a_d + 256 a_(d+1) + 65536 a_(d+2) is an exact double (|a| < 2^31: below 2^47.1), so a row costs two modular
     // products (by 2^24 and 2^48 mod q_j) instead of one per diagonal
     const double c24 = BzF::center(16777216.0, mq), c48 = BzF::center(__dmul_rn(c24, 16777216.0), mq);       // exact: |c24| <= 2^24
@@ -490,7 +528,7 @@ __global__ void __launch_bounds__(256, 2) k_scalar_gemm_mfma(const uint64_t *__r
             gmem_w(out_idx[o])[e] = res;
         } else {
             if (out_idx[o] < 0) continue;
-            if (bias && limb < k) { const uint64_t bv = bias[(size_t)bias_idx[o] * bu + (size_t)ctile * 32 + col]; if (bv) res = addmod(res, scale_plain(C, bv, j), qm.q); }
+            if (FORM == GEMM_CT && bias && limb < k) { const uint64_t bv = bias[(size_t)bias_idx[o] * bu + (size_t)ctile * 32 + col]; if (bv) res = addmod(res, scale_plain(C, bv, j), qm.q); }
             out[(size_t)(obase + (uint32_t)out_idx[o]) * ou + e] = res;
         }
     }

@@ -241,13 +241,18 @@ __global__ void __launch_bounds__(NttPlan<L>::NT) k_intt_tensor(const uint64_t *
 // PLDS (N <= 8192): the NTT-form operand is parked in LDS behind the exchange image instead (the thread's own 16 B slots, no barrier):
 // nothing but the algorithmic 2 reads + 3 writes per block reaches memory, at the price of ONE workgroup per CU (image + 8 N bytes =
 // 132 KiB of the 160 KiB) instead of two.
-template <int L, class AR, bool PLDS = false>
+// NX (PLDS form and k_square_pipe, the Bsk side of cn_square_gemm's pre-floor form): d0 and d1 leave in NTT form instead - canonical words at the positions the thread
+// holds after the forward transform (tail_index, the layout k_ntt_rr<.., true> reads), no inverse transform; d2 as above.
+// (A pack of at most one tag type, NttOut01: the default forms keep their names k_square_fused<L, AR, PLDS> and k_square_pipe<L, AR>.)
+struct NttOut01 {};
+template <int L, class AR, bool PLDS = false, class... NX_>
 __global__ void __launch_bounds__(NttPlan<L>::NT, PLDS ? 2 : 4) k_square_fused(const uint64_t *__restrict__ A_, size_t a_stride, const uint64_t *const *__restrict__ a_tab,
                                                                     uint64_t *__restrict__ D, const DevConsts *__restrict__ C, uint32_t base_off, uint32_t Lm) {
     // 4 waves per SIMD: two 512-thread workgroups per CU.  a_stride: words between the operands of consecutive ciphertexts (the q side
     // reads the input ciphertexts in place, the Bsk side k_behz_extend's array); a_tab: one operand address per ciphertext instead
     // (deferred per-ciphertext calls: every input ciphertext is its own array)
     typedef typename AR::T T;
+    constexpr bool NX = sizeof...(NX_) != 0;
     static_assert(std::is_same<T, double>::value, "FP64 policies only");
     extern __shared__ __align__(16) unsigned char smem[];
     T *s = reinterpret_cast<T *>(smem);
@@ -319,6 +324,18 @@ __global__ void __launch_bounds__(NttPlan<L>::NT, PLDS ? 2 : 4) k_square_fused(c
             }
             __syncthreads();                                     // no forward transform in this step: the previous inverse's image is free
         }
+        if constexpr (NX) {
+            static_assert(!NX || PLDS, "NTT-form d0, d1: the LDS-parked form only");
+            if (step < 2) {                                      // (the next forward transform's PRE barrier / step 2's barrier free the image)
+                uint64_t *on = step ? d1 : d0;
+#pragma unroll
+                for (int r = 0; r < 16; r += 2) {
+                    ulonglong2 w; w.x = A.canon(v[r]); w.y = A.canon(v[r + 1]);
+                    *reinterpret_cast<ulonglong2 *>(on + tail_index<L>(tl, r)) = w;
+                }
+                continue;
+            }
+        }
         uint32_t ti = tid;
         asm volatile("" : "+v"(ti));                             // the inverse transform's address math starts here, not before the forward one
         ntt_inverse_regs<AR, L>(v, s, A.iv, A.m, ti);
@@ -345,10 +362,11 @@ __global__ void __launch_bounds__(NttPlan<L>::NT, PLDS ? 2 : 4) k_square_fused(c
 // Same words as the separate launches (tests/test_gpu_evaluator.py::test_squaring_fused_kernel_is_the_separate_launches).
 template <class AR> struct LdsTwiddles;
 template <int RN> struct LdsTwiddles<ArF64T<RN>> { typedef ArF64LdsT<RN> type; };
-template <int L, class AR>
+template <int L, class AR, class... NX_>
 __global__ void __launch_bounds__(NttPlan<L>::NT, 2) k_square_pipe(const uint64_t *__restrict__ A_, size_t a_stride, const uint64_t *const *__restrict__ a_tab,
                                                                     uint64_t *__restrict__ D, const DevConsts *__restrict__ C, uint32_t base_off, uint32_t Lm, uint32_t cnt) {
     typedef typename AR::T T;
+    constexpr bool NX = sizeof...(NX_) != 0;
     static_assert(std::is_same<T, double>::value && L <= 13, "FP64 policies, N <= 8192");
     extern __shared__ __align__(16) unsigned char smem[];
     T *s = reinterpret_cast<T *>(smem);
@@ -413,6 +431,17 @@ __global__ void __launch_bounds__(NttPlan<L>::NT, 2) k_square_pipe(const uint64_
 #pragma unroll
                 for (int r = 0; r < 16; r++) v[r] = AR::mulmod(P[r], P[r], A.m);
                 __syncthreads();                                 // no forward transform in this step: the previous inverse's image is free
+            }
+            if constexpr (NX) {
+                if (step < 2) {                                  // NTT-form d0, d1 (see k_square_fused)
+                    uint64_t *on = d0 + (size_t)step * Ln;
+#pragma unroll
+                    for (int r = 0; r < 16; r += 2) {
+                        ulonglong2 w; w.x = A.canon(v[r]); w.y = A.canon(v[r + 1]);
+                        *reinterpret_cast<ulonglong2 *>(on + tail_index<L>(tl, r)) = w;
+                    }
+                    continue;
+                }
             }
             uint32_t ti = tid;
             asm volatile("" : "+v"(ti));

@@ -14,6 +14,13 @@ template <int K, int NB> static void launch_floor(cn_ctx *c, const uint64_t *dq,
     else if (f64) hipLaunchKernelGGL((k_behz_floor_f64<K, NB>), dim3(cnt * 3 * c->chunks), dim3(c->bs), 0, c->stream, dq, db, out, c->dc, c->chunks);
     else hipLaunchKernelGGL((k_behz_floor<K, NB>), dim3(cnt * 3 * c->chunks), dim3(c->bs), 0, c->stream, dq, db, out, c->dc, c->chunks);
 }
+// the pre-floor form of cn_square_gemm (FP64 floor on lazy words only): the floor of component 2 alone, and the floor tail per dense output
+template <int K, int NB> static void launch_floor_c2(cn_ctx *c, const uint64_t *dq, const uint64_t *db, uint64_t *out, uint32_t cnt) {
+    hipLaunchKernelGGL((k_behz_floor_f64<K, NB, true, FloorComp>), dim3(cnt * c->chunks), dim3(c->bs), 0, c->stream, dq, db, out, c->dc, c->chunks, 2u, 3u);
+}
+template <int K, int NB> static void launch_floor_out(cn_ctx *c, const FloorOutLaunch &g) {
+    hipLaunchKernelGGL((k_behz_floor_out<K, NB>), dim3(g.slots * 2 * c->chunks), dim3(c->bs), 0, c->stream, g.X, g.Y, g.oidx, g.bias, g.bidx, g.out, g.obase, c->dc, c->chunks);
+}
 #define DISPATCH_K(fn, ...) do { \
     if (c->hc.kb == c->hc.k + 1) switch (c->hc.k) { \
         case 1: fn<1, 1>(__VA_ARGS__); break; case 2: fn<2, 2>(__VA_ARGS__); break; case 3: fn<3, 3>(__VA_ARGS__); break; \
@@ -34,6 +41,18 @@ int cn_l_behz_extend(cn_ctx *c, const uint64_t *src, uint32_t stride, const uint
 int cn_l_behz_floor(cn_ctx *c, const uint64_t *dq, const uint64_t *db, uint64_t *out, uint32_t cnt, bool f64, bool lazy) {
     if (lazy && !f64) return cn_fail(CN_ERR_ARG, "internal: lazy tensor words without the FP64 floor");
     DISPATCH_K(launch_floor, c, dq, db, out, cnt, f64, lazy);
+    HIPCHK(hipGetLastError()); cn_launch_count(c);
+    return 0;
+}
+// component 2 of `cnt` products ([ct][3][..] arrays as above) - components 0 and 1 of dq / db are not read, those of out not written
+int cn_l_behz_floor_c2(cn_ctx *c, const uint64_t *dq, const uint64_t *db, uint64_t *out, uint32_t cnt) {
+    DISPATCH_K(launch_floor_c2, c, dq, db, out, cnt);
+    HIPCHK(hipGetLastError()); cn_launch_count(c);
+    return 0;
+}
+int cn_l_behz_floor_out(cn_ctx *c, const FloorOutLaunch &g) {
+    if ((uint64_t)g.slots * 2 * c->chunks >= (1ull << 31)) return cn_fail(CN_ERR_ARG, "internal: floor tail grid");
+    DISPATCH_K(launch_floor_out, c, g);
     HIPCHK(hipGetLastError()); cn_launch_count(c);
     return 0;
 }

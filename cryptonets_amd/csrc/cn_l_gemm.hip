@@ -52,11 +52,22 @@ int cn_l_gemm(cn_ctx *c, const GemmLaunch &g) { return g.abs ? launch<true>(c, g
 
 template <int P, bool ABS> static void launch_mfma(cn_ctx *c, const GemmLaunch &g) {
     const uint32_t mgroups = (g.mtiles + 3) / 4;
+    if constexpr (!ABS && P <= 2) {                            // the pre-floor forms of cn_square_gemm (GemmLaunch::form): Bsk limbs / exact integer sums of canonical y
+        if (g.form) {                                          // (one or two weight planes: with three the y form spills - square_gemm_prefloor_ok, cn_mul_plan.h)
+            const size_t pblocks = (size_t)g.G * mgroups * g.polys * (g.form == GEMM_BSK ? c->hc.kb : c->hc.k) * (c->hc.n / 32);
+            if (g.form == GEMM_BSK) hipLaunchKernelGGL((k_scalar_gemm_mfma<P, false, GemmBskForm>), dim3((uint32_t)pblocks), dim3(256), 0, c->stream, g.in, g.idx, (const int8_t *)g.W, g.oidx,
+                                                       nullptr, nullptr, g.out, c->dc, g.G, g.M, g.mtiles, g.ksteps, g.obase, g.polys, GemmUnits{g.in_unit, g.out_unit, 0u});
+            else hipLaunchKernelGGL((k_scalar_gemm_mfma<P, false, GemmYForm>), dim3((uint32_t)pblocks), dim3(256), 0, c->stream, g.in, g.idx, (const int8_t *)g.W, g.oidx,
+                                    nullptr, nullptr, g.out, c->dc, g.G, g.M, g.mtiles, g.ksteps, g.obase, g.polys, GemmUnits{g.in_unit, g.out_unit, 0u});
+            return;
+        }
+    }
     const size_t blocks = (size_t)g.G * mgroups * g.polys * c->hc.k * (c->hc.n / 32);
     hipLaunchKernelGGL((k_scalar_gemm_mfma<P, ABS>), dim3((uint32_t)blocks), dim3(256), 0, c->stream, g.in, g.idx, (const int8_t *)g.W, g.oidx, g.bias, g.bidx, g.out,
                        c->dc, g.G, g.M, g.mtiles, g.ksteps, g.obase, g.polys, GemmUnits{g.in_unit, g.out_unit, g.bias_unit});
 }
 template <bool ABS> static int launch_mfma_p(cn_ctx *c, const GemmLaunch &g) {
+    if (g.form && (ABS || g.P > 2 || g.form > GEMM_Y || !g.in_unit || !g.out_unit)) return cn_fail(CN_ERR_ARG, "internal: pre-floor GEMM form %u", g.form);
     switch (g.P) {
         case 1: launch_mfma<1, ABS>(c, g); break;
         case 2: launch_mfma<2, ABS>(c, g); break;

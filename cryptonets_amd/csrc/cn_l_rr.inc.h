@@ -15,7 +15,8 @@ template <int L> static int set_attrs_l(size_t bytes) {
     CHECK(big_lds(k_ntt_rr<L, AR, false>, bytes)); CHECK(big_lds(k_ntt_rr<L, AR, true>, bytes)); CHECK(big_lds(k_intt_tensor<L, AR>, bytes));
     if constexpr (kF64) {
         CHECK(big_lds(k_square_fused<L, AR>, bytes));
-        if constexpr (L <= 13) { CHECK(big_lds(k_square_fused<L, AR, true>, bytes + ((size_t)8 << L))); CHECK(big_lds(k_square_pipe<L, AR>, bytes + ((size_t)8 << L))); }
+        if constexpr (L <= 13) { CHECK(big_lds(k_square_fused<L, AR, true>, bytes + ((size_t)8 << L))); CHECK(big_lds(k_square_pipe<L, AR>, bytes + ((size_t)8 << L)));
+                                 CHECK(big_lds(k_square_fused<L, AR, true, NttOut01>, bytes + ((size_t)8 << L))); CHECK(big_lds(k_square_pipe<L, AR, NttOut01>, bytes + ((size_t)8 << L))); }
     }
     CHECK(big_lds(k_lift_ntt<L, AR>, bytes)); CHECK(big_lds(k_mul_plain_fused<L, AR>, bytes)); CHECK(big_lds(k_mul_plain_bcast<L, AR>, bytes));
     if constexpr (kF64 || L <= 13) CHECK(big_lds(k_mul_plain_bcast<L, AR, true>, bytes));
@@ -27,7 +28,8 @@ template <int L> static int set_attrs_l(size_t bytes) {
     return 0;
 }
 static int set_attrs(uint32_t logn, size_t bytes) {      // transforms whose padded LDS image exceeds the default dynamic-LDS limit (N >= 8192)
-    if constexpr (kF64) { if (logn == 12) { CHECK(big_lds(k_square_fused<12, AR, true>, bytes + ((size_t)8 << 12))); CHECK(big_lds(k_square_pipe<12, AR>, bytes + ((size_t)8 << 12))); } }   // image + parked operand / root table = 66.5 KiB
+    if constexpr (kF64) { if (logn == 12) { CHECK(big_lds(k_square_fused<12, AR, true>, bytes + ((size_t)8 << 12))); CHECK(big_lds(k_square_pipe<12, AR>, bytes + ((size_t)8 << 12)));
+                                          CHECK(big_lds(k_square_fused<12, AR, true, NttOut01>, bytes + ((size_t)8 << 12))); CHECK(big_lds(k_square_pipe<12, AR, NttOut01>, bytes + ((size_t)8 << 12))); } }   // image + parked operand / root table = 66.5 KiB
     if (logn == 13) return set_attrs_l<13>(bytes);
     if (logn == 14) return set_attrs_l<14>(bytes);
     return 0;
@@ -57,6 +59,14 @@ template <int L> static void l_square_fused(cn_ctx *c, const uint64_t *A, size_t
     if constexpr (kF64) {
         const size_t lds = (size_t)ntt_lds_words(1u << L) * 8;
         if constexpr (L <= 13) {
+            if (b.ntt01 && b.sq == SQ_PIPE) {                  // d0, d1 leave in NTT form (cn_square_gemm's pre-floor form, Bsk side)
+                hipLaunchKernelGGL((k_square_pipe<L, AR, NttOut01>), dim3(b.per_limb * Lm), dim3(NttPlan<L>::NT), lds + ((size_t)8 << L), c->stream, A, astride, atab, D, c->dc, base_off, Lm, cnt);
+                return;
+            }
+            if (b.ntt01 && b.sq == SQ_LDS) {
+                hipLaunchKernelGGL((k_square_fused<L, AR, true, NttOut01>), dim3(cnt * Lm), dim3(NttPlan<L>::NT), lds + ((size_t)8 << L), c->stream, A, astride, atab, D, c->dc, base_off, Lm);
+                return;
+            }
             if (b.sq == SQ_PIPE) {
                 hipLaunchKernelGGL((k_square_pipe<L, AR>), dim3(b.per_limb * Lm), dim3(NttPlan<L>::NT), lds + ((size_t)8 << L), c->stream, A, astride, atab, D, c->dc, base_off, Lm, cnt);
                 return;
@@ -70,7 +80,7 @@ template <int L> static void l_square_fused(cn_ctx *c, const uint64_t *A, size_t
     }
 }
 static bool square_fused(cn_ctx *c, const uint64_t *A, size_t astride, const uint64_t *const *atab, uint64_t *D, uint32_t cnt, uint32_t base_off, uint32_t Lm, const MulBase &b) {
-    if (!kF64 || (b.sq != SQ_PLAIN && c->hc.logn > 13)) return false;
+    if (!kF64 || (b.sq != SQ_PLAIN && c->hc.logn > 13) || (b.ntt01 && (b.sq == SQ_PLAIN || c->hc.logn > 13))) return false;
     BY_SIZE(l_square_fused, c, A, astride, atab, D, cnt, base_off, Lm, b)
 }
 

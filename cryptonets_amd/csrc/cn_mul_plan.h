@@ -17,6 +17,7 @@ struct MulSwitches {
     size_t smax;              // the scratch limit (CN_SCRATCH_GB)
     bool rlk, rlk_f64;        // a relinearisation key is present; it was loaded in FP64 form (KsKey::f64)
     KsSwitches ks;
+    int sg_prefloor = 0;      // "sg_prefloor": 0 = cn_square_gemm floors every product (the old form), 1 = the pre-floor form where square_gemm_prefloor_ok says so, 2 = ... for any K (tests)
 };
 inline size_t mul_al(size_t b) { return (b + 255) & ~(size_t)255; }      // the scratch arena hands out multiples of 256 bytes (al, salloc)
 
@@ -33,7 +34,10 @@ enum SqKernel {
     SQ_PIPE               // k_square_pipe: `per_limb` resident workgroups per modulus for the whole launch; pays once a workgroup squares several blocks (N <= 8192)
 };
 enum MulArray { MUL_AQ, MUL_AB, MUL_BQ, MUL_BB, MUL_DQ, MUL_DB, MUL_ARRAYS };      // operands a, b extended to q / Bsk, the tensor d on q / Bsk
-struct MulBase { int policy; SqKernel sq; uint32_t per_limb; };                     // policy: cn_policy of the base under "f64"; sq, per_limb: MUL_SQUARE_FUSED only
+struct MulBase {                                                                    // policy: cn_policy of the base under "f64"; sq, per_limb: MUL_SQUARE_FUSED only
+    int policy; SqKernel sq; uint32_t per_limb;
+    bool ntt01 = false;   // SQ_LDS / SQ_PIPE: components 0 and 1 leave in NTT form (canonical words, tail_index layout) - the Bsk side of cn_square_gemm's pre-floor form
+};
 struct MulPlan {
     MulForm form;
     bool lazy;            // the tensor leaves as lazy-FP64 hand-off words (lazy_word, cn_dev_common.hip.h) and the floor is told so: the tensor kernels of BOTH bases and the
@@ -136,6 +140,34 @@ static const uint32_t PRODUCT_SUM_MAX_DIGITS = 8;      // k_product_sum keeps th
 inline bool square_gemm_ctx_ok(const DevConsts &hc, const MulSwitches &sw) { return sw.f64 && sw.rr13 && !hc.ks_xi && sw.rlk_f64 && cn_mod_range(hc, 0, hc.k).f64ok; }
 inline bool square_gemm_fused_ok(const DevConsts &hc, const MulSwitches &sw, const GemmLayout &L) { return L.dig && square_gemm_ctx_ok(hc, sw); }
 inline bool mul_defers_square_gemm(const DevConsts &hc, const MulSwitches &sw) { return sw.defer_square_gemm && square_gemm_ctx_ok(hc, sw) && sw.rlk; }
+// cn_square_gemm's pre-floor form ("One floor tail per dense output"): components 0 and 1 of the products are never floored per input - their Bsk words
+// are summed in NTT form on the matrix cores, the canonical y of their q words as exact integers, and ONE floor tail per output gives the words of the old form.
+// Runs when "sg_prefloor" is on, the old fused form would run (square_gemm_fused_ok) with the plan's GEMM on the matrix cores, the products come from the fused squaring
+// kernels with the operand parked in LDS or registers (MUL_SQUARE_FUSED, lazy hand-off, "sq_lds": no SQ_PLAIN launch at any chunk size), the weights have one or two signed byte digits (|w| <= 32639: the
+// three-plane instantiation of the y GEMM would spill registers), every auxiliary prime is below
+// 2^49 (seven signed byte digits), the bound on |V_o| holds (cn_prefloor_bound_ok, cn_policy.h) and the layer has at least SG_PREFLOOR_MIN_K terms ("sg_prefloor" 2: any).
+// SG_PREFLOOR_MIN_K: measured at C3 with 100 outputs, both forms alternating in one process - K = 64, 128, 256: the old form is faster (the new one pays two more GEMM launches,
+// a transform and a floor launch whatever K is); K = 512 and 845: the new form's slowest repetition beats the old form's fastest (profiles/square_gemm_prefloor.md)
+static const uint32_t SG_PREFLOOR_MIN_K = 512;
+inline bool square_gemm_prefloor_ok(const DevConsts &hc, const MulSwitches &sw, const GemmLayout &L) {
+    if (!sw.sg_prefloor || !L.mfma || !L.P || L.P > 2 || !square_gemm_fused_ok(hc, sw, L) || (sw.sg_prefloor < 2 && L.K < SG_PREFLOOR_MIN_K)) return false;
+    const MulPlan p = cn_mul_plan(hc, sw, true, 1);
+    if (p.form != MUL_SQUARE_FUSED || !p.lazy || !p.behz_f64 || !sw.sq_lds || hc.logn > 13 || hc.kb != hc.k + 1 || cn_mod_range(hc, hc.k, hc.kb).bits > 49) return false;
+    uint64_t q[CN_MAXK], b[CN_MAXK + 1];
+    for (uint32_t j = 0; j < hc.k; j++) q[j] = hc.q[j].q;
+    for (uint32_t j = 0; j < hc.kb; j++) b[j] = hc.bsk[j].q;
+    return cn_prefloor_bound_ok(L.sum_abs_w, hc.t.q, hc.n, q, hc.k, b, hc.kb);
+}
+// what the form keeps beside the old form's arrays for the whole call: the tensor words of ALL `count` products on both bases (the GEMMs read them after the last
+// chunk), X and Y of the `outputs` outputs.  cn_square_gemm adds the total to MulBatch::fixed before it asks whether the call fits
+enum SgArray { SG_DQ, SG_DB, SG_X, SG_Y, SG_ARRAYS };
+struct SgPrefloorScratch { struct { SgArray id; size_t bytes; } scratch[SG_ARRAYS]; size_t total; };
+inline SgPrefloorScratch square_gemm_prefloor_scratch(const DevConsts &hc, uint32_t count, uint32_t outputs) {
+    const size_t n = hc.n, k = hc.k, kb = hc.kb;
+    SgPrefloorScratch s{{{SG_DQ, mul_al(count * 3 * k * n * 8)}, {SG_DB, mul_al(count * 3 * kb * n * 8)}, {SG_X, mul_al(outputs * 2 * kb * n * 8)}, {SG_Y, mul_al(outputs * 2 * k * n * 8)}}, 0};
+    for (const auto &a : s.scratch) s.total += a.bytes;
+    return s;
+}
 // cn_mul_relin_sum: "mul_sum" on, K >= MUL_SUM_MIN_K, S is a lazy value the KsDigits kernels take (K (2^dbc - 1) below every q_j / 2 and below 2^52), the kernel's
 // 64-bit accumulators hold the sums of components 0 and 1 exactly (K (q_max - 1) < 2^64: PRODUCT_SUM_MAX_TERMS), its digit registers hold every limb's digits (at
 // most PRODUCT_SUM_MAX_DIGITS of at most 31 bits) and its blocks of 512 coefficients tile the ring

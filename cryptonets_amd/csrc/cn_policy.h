@@ -32,6 +32,21 @@ inline bool cn_digit_sum_fits_i32(uint64_t sum_abs_w, int dbc) {
     if (dbc < 1 || dbc > 31) return false;
     return (unsigned __int128)sum_abs_w * ((1ull << dbc) - 1) <= 0x7fffffffull;
 }
+// cn_square_gemm's pre-floor form runs ONE floor tail per dense output on the weighted sums of the inputs' floor operands.  Its Shenoy-Kumaresan
+// conversion returns V_o = sum_k w_ok W_k exactly iff |V_o| < B m_sk / 2, where W_k = floor(t d_k / q) - a_k is the integer the per-input floor computes: |d| <= 2 N q^2
+// for a coefficient of the cross term of operands below q, so |W| < 4 t N q and |V_o| < 4 R t N q with R = sum_abs_w.  One-sided: true implies 8 R t N q <= B m_sk / 2
+// (a bit to spare) - the logarithms are doubles whose errors (below 2^-40 in the sum) the margin 2^-20 covers; false may be a near miss.  Also true only if the exact
+// sums Y_oj = sum_k w_ok y_kj (|y| < q_j) stay below 2^63, R q_j < 2^63 for every j: the GEMM forms them in two's complement 64-bit words.
+inline bool cn_prefloor_bound_ok(uint64_t sum_abs_w, uint64_t t, uint32_t n, const uint64_t *q, uint32_t k, const uint64_t *base, uint32_t kb) {
+    if (!sum_abs_w || !t || !n || !k || !kb) return false;
+    double lhs = __builtin_log2((double)sum_abs_w) + __builtin_log2((double)t) + __builtin_log2((double)n) + 3.0, rhs = -1.0;
+    for (uint32_t j = 0; j < k; j++) {
+        if (!q[j] || (unsigned __int128)sum_abs_w * q[j] >= ((unsigned __int128)1 << 63)) return false;
+        lhs += __builtin_log2((double)q[j]);
+    }
+    for (uint32_t b = 0; b < kb; b++) { if (base[b] < 2) return false; rhs += __builtin_log2((double)base[b]); }
+    return lhs + 0x1p-20 <= rhs;
+}
 // The tables of a planned scalar GEMM (HOT LOOP A), as the planner (cn_gemm_plan.h) writes them and the launchers (cn_l_gemm.hip) read them.
 // k_scalar_gemm_f64: rows of the weight table per (group, output tile) - K terms + zero rows up to a multiple of 16 + 16: the kernel's sets of 4 (or 8) terms run past K
 // and multiply whatever word the padded gather entry reads by these zeros
@@ -49,6 +64,7 @@ struct GemmLayout {
     // dig_i32: every digit sum fits a signed 32-bit word (cn_digit_sum_fits_i32 of the largest row, "digit_i32" on): S is stored and read as int32 words
     bool dig = false, dig_mfma = false, dig_i32 = false; uint32_t dMT = 0, dKw = 0;
     size_t off_oidx = 0, off_bidx = 0, off_w = 0, off_dw = 0;
+    uint64_t sum_abs_w = 0;                  // with `dig`: the largest sum_k |w_ok| of any output (the plan's digit bound is sum_abs_w (2^dbc - 1)); 0 = not known: no pre-floor form
     template <class E> const E *gather(const char *image) const { return (const E *)image; }                  // [G][Kp]
     template <class E> const E *members(const char *image) const { return (const E *)(image + off_oidx); }    // [G][M]
 };

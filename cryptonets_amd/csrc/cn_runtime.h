@@ -212,6 +212,7 @@ struct cn_ctx {
     uint64_t folded_zero = 0;  // zero encryptions folded so far
     uint64_t mr_pipelined = 0; // cn_mul_relin chunks and flushed Multiply + Relinearize groups that ran through pipelined_halves
     uint64_t sg_fused = 0;     // cn_square_gemm calls that ran the one-key-switch-per-output form
+    uint64_t sg_prefloor = 0;  // ... of which in the pre-floor form: one floor tail per dense output for components 0 and 1 ("square_gemm_prefloor")
     uint64_t dsg_fused = 0;    // groups of queued scalar products that ran on deferred squarings in the one-key-switch-per-output form ("defer_square_gemm_fused")
     uint64_t dg_mfma = 0;      // digit GEMMs launched in the matrix-core form
     std::atomic<uint64_t> packed_bad{0};       // packed uploads whose rows held a residue >= its modulus (counted where the flag is read)
@@ -227,6 +228,9 @@ struct cn_ctx {
     int ptn_order = 0;         // k_mul_ptn_sum, workgroup order ("ptn_order", CN_PTN_ORDER): 0 limb-major, 1 limb = workgroup index mod k (a limb per XCD at k = 8)
     uint64_t ptn_sum = 0, ptn_bcast = 0;   // launches of k_mul_ptn_sum / of k_mul_plain_bcast on NTT-form plaintexts ("ptn_sum", "ptn_bcast")
     uint64_t diag_scan = 0, diag_encode = 0;   // launches of k_diag_scan / of k_diag_gather ("diag_scan", "diag_encode")
+    int sg_prefloor_mode = 1;  // cn_set_option "sg_prefloor": cn_square_gemm - 1 = components 0 and 1 take ONE floor tail per dense output where square_gemm_prefloor_ok allows (cn_mul_plan.h:
+                               // layers of at least SG_PREFLOOR_MIN_K terms); 0 = every product is floored (the old form); 2 = the new form for any K (tests).  The same words.  Set by
+                               // name like "digit_mfma" (no environment override)
     bool defer_square_gemm = false;  // cn_set_option "defer_square_gemm" (default 0: its effect on the literal call sequence has not been measured, profiles/deferred_square_gemm.md): queued squarings launched by a layer-boundary flush keep their relinearisation back; scalar products that read
                                // nothing else run as cn_square_gemm's second half - one key switch per dense OUTPUT (cn_defer.hip); false: every queued squaring relinearises at once.
                                // Set by name like "digit_mfma" (no environment override)
@@ -322,6 +326,11 @@ extern const KsOps cn_ks_u64, cn_ks_f64, cn_ks_f64l;
 // f64, lazy: MulPlan::behz_f64 and MulPlan::lazy of the chain (cn_mul_plan.h) - the FP64 kernels; dq / db hold the lazy-FP64 hand-off words of an FP64 tensor kernel
 int cn_l_behz_extend(cn_ctx *c, const uint64_t *src, uint32_t stride, const uint64_t *const *src_tab, uint64_t *aq, uint64_t *ab, uint32_t cnt, bool f64);
 int cn_l_behz_floor(cn_ctx *c, const uint64_t *dq, const uint64_t *db, uint64_t *out, uint32_t cnt, bool f64, bool lazy);
+// cn_square_gemm's pre-floor form (FP64 floor, lazy words): the floor of component 2 alone; the floor tail once per dense output (k_behz_floor_out, cn_k_behz.hip.h) -
+// X [output][2][kb][N] canonical coefficients, Y [output][2][k][N] exact 64-bit sums, oidx / bidx the plan's member and bias tables of `slots` entries, bias null: none
+int cn_l_behz_floor_c2(cn_ctx *c, const uint64_t *dq, const uint64_t *db, uint64_t *out, uint32_t cnt);
+struct FloorOutLaunch { const uint64_t *X, *Y; const int32_t *oidx; const uint64_t *bias; const int32_t *bidx; uint64_t *out; uint32_t obase, slots; };
+int cn_l_behz_floor_out(cn_ctx *c, const FloorOutLaunch &g);
 
 // scalar GEMM (cn_l_gemm.hip).  Relative addressing: input / output ciphertext = base + index * ctw; absolute (ABS): the tables hold
 // device addresses (deferred per-ciphertext calls: every ciphertext is its own array), 0 = padded tap / no output.
@@ -334,6 +343,7 @@ struct GemmLaunch {
     uint32_t order = 0;                              // workgroup order of the VALU kernels: 0 group-major, 1 slice-major (gemm_block_coords)
     bool one = false;                                // k_scalar_gemm_f64<MT, 1, 0>: the words are not split (gemm_one_limb)
     uint32_t in_unit = 0, out_unit = 0, bias_unit = 0;   // words per index unit of the table-driven kernels; 0 = one ciphertext / one plaintext (plans).  Deferred calls: 32 (256 B offsets from the lowest address)
+    uint32_t form = 0;                               // matrix-core kernel, the pre-floor form of cn_square_gemm: 1 = Bsk limbs (7 digits, mod b), 2 = lazy q words -> canonical y -> exact int64 sums (cn_k_gemm.hip.h)
     // the launch of a planned layout (GemmLayout, cn_policy.h) whose image is at `tables`: weights, output members and - until inputs() / bias_at() name others -
     // gather rows and bias entries at their offsets; order: the "gemm_order" option.  Then the operands by name, `unit` as in_unit / bias_unit / out_unit above
     static GemmLaunch of(const GemmLayout &L, const char *tables, uint32_t order) {
@@ -346,6 +356,7 @@ struct GemmLaunch {
     GemmLaunch &bias_at(const uint64_t *base, const void *entries, uint32_t unit) { bias = base; bidx = entries; bias_unit = unit; return *this; }      // base null: no bias
     GemmLaunch &outputs(uint64_t *base, uint32_t first, uint32_t unit) { out = base; obase = first; out_unit = unit; return *this; }
     // address-table form: every table entry is a device address; `any`: some input (the kernels read a valid word at padded taps); bias entries only where a call has one
+    GemmLaunch &prefloor(uint32_t form_) { form = form_; bias = nullptr; return *this; }
     GemmLaunch &addresses(const uint64_t *any, bool with_bias) { abs = true; in = any; if (!with_bias) bidx = nullptr; return *this; }
 };
 int cn_l_gemm(cn_ctx *c, const GemmLaunch &g);

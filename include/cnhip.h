@@ -139,6 +139,10 @@ int cn_mod_switch(cn_ctx *src, cn_handle in, uint32_t ii, uint32_t count, cn_ctx
  *                                                                   link's permuted c1 beside its result (no permutation pass between links)
  *   "mp_bcast"       flag    1                     -                cn_rowdot_batch transforms its ONE ciphertext once and the row plaintexts inside the
  *                                                                   product kernel; 0 = k_lift_ntt + k_mul_plain_fused
+ *   "sg_prefloor"    0..2    1                     -                cn_square_gemm: components 0 and 1 of the products take ONE fast floor per dense output
+ *                                                                   (sums of their Bsk words in NTT form and of their canonical y on the matrix cores)
+ *                                                                   where the plan and the layer size allow; 0 = one floor per product; 2 = for any
+ *                                                                   layer size (tests).  The same words.  A context switch like "digit_mfma"
  *   "ptn_order"      0..1    0                     CN_PTN_ORDER     cn_mul_plain_sum on NTT-form plaintexts, workgroup order: 0 limb-major, 1 limb = workgroup
  *                                                                   index mod k (one limb per XCD where k = 8)
  *   "defer"          0..2    0                     -                deferred submission of per-ciphertext calls (below)
@@ -218,6 +222,8 @@ int cn_set_option(cn_ctx *ctx, const char *name, int value);
  *   "mul_relin_pipelined"      cn_mul_relin chunks and flushed groups of queued Multiply + Relinearize calls that ran in parts over the context's two
  *                              streams ("sq_halves"; counts up)
  *   "square_gemm_fused"        cn_square_gemm calls that ran one key switch per output (counts up; the others took the two separate steps)
+ *   "square_gemm_prefloor"     ... of which with one fast floor per dense output for components 0 and 1 ("sg_prefloor"; counts up)
+ *   "sg_prefloor_min_k"        the smallest K for which cn_square_gemm takes that form under "sg_prefloor" = 1
  *   "defer_square_gemm_fused"  groups of queued scalar products that ran on held-back squarings with one key switch per output ("defer_square_gemm"; counts up)
  *   "defer_pending_products"   squarings whose relinearisation is held back right now (0 after every flush that is not a layer boundary)
  *   "mul_sum_fused"            cn_mul_relin_sum calls that ran one key switch per output (counts up; the others took the literal sequence)

@@ -203,8 +203,8 @@ def static_counts(obj, kernel):
                 rndne=sum(op.startswith("v_rndne_f64") for _, op, _ in ins))
 
 
-PIPE_KERNEL = "_Z13k_square_pipeILi13E6ArF64TILi0EEE"                 # k_square_pipe<13, ArF64T<0>>: the squaring of the CryptoNets batches
-SQUARE_KERNEL = "_Z14k_square_fusedILi13E6ArF64TILi0EELb1EE"          # k_square_fused<13, ArF64T<0>, true>: fused squaring, operand parked in LDS
+PIPE_KERNEL = "_Z13k_square_pipeILi13E6ArF64TILi0EEJEE"               # k_square_pipe<13, ArF64T<0>>: the squaring of the CryptoNets batches
+SQUARE_KERNEL = "_Z14k_square_fusedILi13E6ArF64TILi0EELb1EJEE"        # k_square_fused<13, ArF64T<0>, true>: fused squaring, operand parked in LDS
 
 
 def _branches(ins):
