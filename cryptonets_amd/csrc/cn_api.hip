@@ -961,23 +961,13 @@ extern "C" int cn_diag_encode(cn_ctx *ctx, cn_handle rows, uint32_t ri, uint32_t
     uint8_t *nz = salloc<uint8_t>(ctx, count);
     if (!stage || !nz) return fail(CN_ERR_HIP, "internal: scratch exhausted in cn_diag_encode");
     HIPCHK(hipMemsetAsync(nz, 0, count, ctx->stream));
-    const int pol = cn_policy(cn_mod_range(ctx->hc, 0, k), ctx->opt.f64);
     for (uint32_t e0 = 0, ch = 0; e0 < count; e0 += chunk, ch++) {
         const uint32_t cnt = std::min(chunk, count - e0);
         uint64_t *coef = ntt ? stage : O->d + (size_t)(oi + e0) * n;
         CHECK(cn_l_diag_gather(ctx, S, R, dim, druns + run0[ch], run0[ch + 1] - run0[ch], ctx->d_index_map, coef, nz + e0));
         CHECK(cn_run_ntt(ctx, coef, cnt, k + ctx->hc.kb, 1, 1));
         if (!ntt) continue;
-        uint64_t *dst = O->d + (size_t)(oi + e0) * O->item_words;   // the staging chunk into the NTT form, as cn_pt_transform writes it
-        if (rr_kernels(ctx)) {
-            rr_ops[pol]->mul_plain_fused(ctx, stage, 1, cnt, dst, nullptr, 0, 0, nullptr, 0, 0);
-            HIPCHK(hipGetLastError()); launch_count(ctx);
-            ctx->st.ntt_forward_limbs += (uint64_t)cnt * k;
-        } else {
-            hipLaunchKernelGGL(k_lift_plain, dim3(cnt * k * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, stage, dst, ctx->dc, ctx->chunks, 1u);
-            HIPCHK(hipGetLastError()); launch_count(ctx);
-            CHECK(cn_run_ntt(ctx, dst, cnt * k, 0, k, 0));
-        }
+        CHECK(pt_to_ntt(ctx, stage, cnt, O->d + (size_t)(oi + e0) * O->item_words));   // the staging chunk into the NTT form, as cn_pt_transform writes it
     }
     std::vector<uint8_t> hnz(count);
     HIPCHK(hipMemcpyAsync(hnz.data(), nz, count, hipMemcpyDeviceToHost, ctx->stream));

@@ -10,6 +10,8 @@
 // parking, staging layout, the ordered steps - is decided in cn_defer_plan.h (host-only; the queue's types DOp and DeferQueue live there; cn_defer.hip does the device work).
 // What a ciphertext product launches - tensor form, FP64 / lazy choice, squaring kernels, scratch list -, how its batches are cut into chunks under the scratch limit and
 // the gates of the one-key-switch-per-output forms are decided in cn_mul_plan.h (host-only; mul_switches in cn_eval.hip builds what it reads of a context).
+// What a plaintext product launches - broadcast, NTT-form, lift + product or the separate launches -, its scratch list, the SumAllSlots sequence and its one-launch chain,
+// the arena of a chained row-dot batch and the kernel / composition of cn_mul_plain_sum are decided in cn_plain_plan.h (host-only; plain_switches in cn_eval.hip).
 // Which arithmetic policy a modulus range takes and which ring sizes have the register-radix kernels is decided in cn_policy.h (cn_mod_range, cn_policy, cn_rr_size).
 // Everything here is internal: the C ABI is include/cnhip.h.  The element-wise kernels (cn_k_elem.hip.h) have internal linkage - every unit that launches one
 // carries its own copy.
@@ -17,6 +19,7 @@
 #include "cn_runtime.h"
 #include "cn_rotation.h"
 #include "cn_defer_plan.h"
+#include "cn_plain_plan.h"
 #include <thread>
 #include "cn_k_elem.hip.h"
 #include <algorithm>
@@ -128,7 +131,8 @@ int addsub(cn_ctx *ctx, cn_handle a, uint32_t ai, cn_handle b, uint32_t bi, cn_h
 int addsub_body(cn_ctx *ctx, cn_handle a, uint32_t ai, cn_handle b, uint32_t bi, cn_handle out, uint32_t oi, uint32_t count, int op);
 int add_plain_body(cn_ctx *ctx, cn_handle a, uint32_t ai, cn_handle pt, uint32_t pi, int subtract, cn_handle out, uint32_t oi, uint32_t count);
 bool shifted_overlap(const uint64_t *a, const uint64_t *o, size_t words);
-bool mul_plain_takes_bcast(cn_ctx *ctx, uint32_t count);
+PlainSwitches plain_switches(const cn_ctx *ctx);           // (cn_plain_plan.h)
+int pt_to_ntt(cn_ctx *ctx, const uint64_t *src, uint32_t count, uint64_t *dst);      // dst[i] = NTT form ([k][N]) of the coefficient-form plaintext src + i N
 int mul_plain_impl(cn_ctx *ctx, CtSpan A, bool a_bcast, PtSpan P, CtSpan O, uint32_t polys, const BcastNext *nx = nullptr);
 GemmSwitches gemm_switches(const cn_ctx *ctx);           // (cn_gemm_plan.h)
 int free_gemm_plan(cn_ctx *ctx, Buffer &b);
@@ -195,8 +199,7 @@ int plan_rotation(cn_ctx *ctx, int steps, CnRotPlan *plan = nullptr);      // nu
 int rotate_rows_impl(cn_ctx *ctx, CtSpan in, int steps, CtSpan out);
 int rotate_jobs(cn_ctx *ctx, std::vector<RotJob> &jobs);
 int rotate_rows_add_impl(cn_ctx *ctx, CtSpan in, int steps, CtSpan acc, CtSpan out);
-std::vector<uint64_t> sum_slots_chain_elts(cn_ctx *ctx, uint32_t count, uint32_t length);
-int sum_slots_impl(cn_ctx *ctx, CtSpan h, uint32_t length, bool first_ready = false);
+int sum_slots_impl(cn_ctx *ctx, CtSpan h, uint32_t length, const RowdotPlan *ready = nullptr);
 int set_plain_key(cn_ctx *ctx, uint64_t **slot, const uint64_t *words, size_t count, size_t expect, bool is_dev = false, bool coeff_form = false);
 RngKey rng_key_of(const cn_ctx *ctx);
 int sample_poly(cn_ctx *ctx, uint64_t *dst, uint32_t polys, int kind, uint64_t seed, uint64_t stream);
@@ -244,10 +247,9 @@ static inline void rec_rows(cn_ctx *ctx, int steps) { if (ctx->rec_steps && step
 static inline void rec_columns(cn_ctx *ctx) { if (ctx->rec_steps) ctx->rec_cols = true; }
 static inline void rec_sum_slots(cn_ctx *ctx, uint32_t length) {          // the chain of sum_slots_impl
     if (!ctx->rec_steps) return;
-    const uint32_t n = ctx->hc.n, half = n / 2;
-    uint32_t len = length ? length : n;
-    if (len >= half) { ctx->rec_cols = true; len = half; }
-    for (uint32_t st = 1; st < len; st *= 2) ctx->rec_set.insert(-(int)st);
+    const SumSlotsSeq seq = sum_slots_seq(ctx->hc.n, length);
+    if (seq.columns) ctx->rec_cols = true;
+    for (uint32_t i = 0; i < seq.rows; i++) ctx->rec_set.insert(-(int)(1u << i));
 }
 static inline void rec_galois(cn_ctx *ctx, uint64_t elt) {                // cn_apply_galois: 2N - 1 = the column swap, 3^s = RotateRows(s)
     if (!ctx->rec_steps) return;

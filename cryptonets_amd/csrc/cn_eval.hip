@@ -63,61 +63,8 @@ int add_plain_body(cn_ctx *ctx, cn_handle a, uint32_t ai, cn_handle pt, uint32_t
     if (subtract) ctx->st.PlainSubtraction += count; else ctx->st.PlainAddition += count;
     return 0;
 }
-int mul_plain_fused(cn_ctx *ctx, CtSpan A, bool a_bcast, PtSpan P, CtSpan O, uint32_t polys, const BcastNext *nx) {
-    const uint32_t n = ctx->hc.n, k = ctx->hc.k, count = O.count, pstride = P.stride, npt = pstride ? count : 1;
-    const size_t item_words = (size_t)polys * k * n;
-    uint64_t *o = O.d;
-    const uint64_t *src = A.d;
-    // one input ciphertext broadcast over the outputs: it must survive until the last block has read it
-    const int pol = cn_policy(cn_mod_range(ctx->hc, 0, k), ctx->opt.f64);
-    if (a_bcast && pstride && count >= 4 && ctx->opt.mp_bcast && !(P.ntt && !cn_rr_ptn_bcast(pol, ctx->hc.logn))) {      // one ciphertext x many plaintexts: transform the ciphertext once, the plaintexts inside the product kernel
-        uint64_t *ctn = nx ? nx->ctn : nullptr;
-        if (!nx) { CHECK(ensure_scratch(ctx, al(item_words * 8))); ctn = salloc<uint64_t>(ctx, item_words); }
-        if (!ctn) return fail(CN_ERR_HIP, "internal: scratch exhausted in multiply_plain");
-        HIPCHK(hipMemcpyAsync(ctn, src, item_words * 8, hipMemcpyDeviceToDevice, ctx->stream));
-        CHECK(cn_run_ntt(ctx, ctn, polys * k, 0, k, 0));
-        rr_ops[pol]->mul_plain_bcast(ctx, P.d, pstride, ctn, o, count, polys, nx ? (uint32_t)nx->elt : 0u, nx ? nx->out : nullptr, P.ntt);
-        HIPCHK(hipGetLastError()); launch_count(ctx);
-        if (P.ntt) ctx->ptn_bcast++;                               // (NTT-form rows: no transform of the plaintexts ran)
-        if (!P.ntt) ctx->st.ntt_forward_limbs += (uint64_t)count * polys * k;      // the rows, beside the polys k limbs cn_run_ntt counted (NTT-form rows: those are all that ran)
-        ctx->st.ntt_inverse_limbs += (uint64_t)count * polys * k;
-        ctx->st.PlainMultiplication += count;
-        return 0;
-    }
-    const bool alias = a_bcast && src >= o && src < o + (size_t)count * item_words;
-    if (P.ntt) {                                                   // NTT-form plaintexts: k_mul_plain_fused alone, reading the array where it lies (pstride as given)
-        if (nx) return fail(CN_ERR_ARG, "internal: chained row-dot batch outside the broadcast product");
-        if (alias) {
-            CHECK(ensure_scratch(ctx, al(item_words * 8)));
-            uint64_t *keep = salloc<uint64_t>(ctx, item_words);
-            if (!keep) return fail(CN_ERR_HIP, "internal: scratch exhausted in multiply_plain");
-            HIPCHK(hipMemcpyAsync(keep, src, item_words * 8, hipMemcpyDeviceToDevice, ctx->stream));
-            src = keep;
-        }
-        rr_ops[pol]->mul_plain_fused(ctx, nullptr, 0, 0, const_cast<uint64_t *>(P.d), src, a_bcast ? 0 : item_words, pstride, o, count, polys);
-        HIPCHK(hipGetLastError()); launch_count(ctx);
-        ctx->st.ntt_forward_limbs += (uint64_t)count * polys * k; ctx->st.ntt_inverse_limbs += (uint64_t)count * polys * k;
-        ctx->st.PlainMultiplication += count;
-        return 0;
-    }
-    CHECK(ensure_scratch(ctx, al((size_t)npt * k * n * 8) + (alias ? al(item_words * 8) : 0)));
-    uint64_t *lift = salloc<uint64_t>(ctx, (size_t)npt * k * n);
-    if (alias) {
-        uint64_t *keep = salloc<uint64_t>(ctx, item_words);
-        if (!keep) return fail(CN_ERR_HIP, "internal: scratch exhausted in multiply_plain");
-        HIPCHK(hipMemcpyAsync(keep, src, item_words * 8, hipMemcpyDeviceToDevice, ctx->stream));
-        src = keep;
-    }
-    if (!lift) return fail(CN_ERR_HIP, "internal: scratch exhausted in multiply_plain");
-    const size_t sstride = a_bcast ? 0 : item_words;
-    const uint32_t pitch = pstride ? pstride : 1u, ps = pstride ? 1u : 0u;
-    rr_ops[pol]->mul_plain_fused(ctx, P.d, pitch, npt, lift, src, sstride, ps, o, count, polys);
-    HIPCHK(hipGetLastError()); launch_count(ctx, 2);
-    ctx->st.ntt_forward_limbs += (uint64_t)npt * k + (uint64_t)count * polys * k; ctx->st.ntt_inverse_limbs += (uint64_t)count * polys * k;
-    ctx->st.PlainMultiplication += count;
-    return 0;
-}
-bool mul_plain_takes_bcast(cn_ctx *ctx, uint32_t count) { return ctx->opt.mp_fused && ctx->opt.mp_bcast && rr_kernels(ctx) && count >= 4; }
+// the switches of this context that the plaintext planner reads (cn_plain_plan.h): the only place that copies them out of a context for the plaintext family
+PlainSwitches plain_switches(const cn_ctx *ctx) { return {ctx->opt.f64, ctx->opt.mp_fused, ctx->opt.mp_bcast, ctx->opt.ks_chain, ctx->ptn_order, rr_kernels(ctx), ks_switches(ctx)}; }
 // neither the same range nor disjoint: `words` words at a and at o overlap with a shift (a null operand overlaps nothing)
 bool shifted_overlap(const uint64_t *a, const uint64_t *o, size_t words) { return a && a != o && a < o + words && o < a + words; }
 static int mul_plain_overlap(const CtSpan &A, const CtSpan &O, size_t item_words) {      // block c writes out[c] while another block still reads in[c']
@@ -128,36 +75,63 @@ static int plain_not_zero(const PtSpan &P, uint32_t count) {
     for (uint32_t c = 0; P.zero && c < (P.stride ? count : 1u); c++) if (P.zero[c * P.stride]) return fail(CN_ERR_ZERO, "plain cannot be zero");
     return 0;
 }
+// MultiplyPlain as planned (PlainPlan, cn_plain_plan.h): checks, the plan, its scratch arrays, the launches of its form
 int mul_plain_impl(cn_ctx *ctx, CtSpan A, bool a_bcast, PtSpan P, CtSpan O, uint32_t polys, const BcastNext *nx) {
     const uint32_t n = ctx->hc.n, k = ctx->hc.k, count = O.count, pstride = P.stride, npt = pstride ? count : 1;
     const size_t item_words = (size_t)polys * k * n;
     if (!count) return 0;
     if (!a_bcast) CHECK(mul_plain_overlap(A, O, item_words));
     CHECK(plain_not_zero(P, count));
-    if (ctx->opt.mp_fused && rr_kernels(ctx)) return mul_plain_fused(ctx, A, a_bcast, P, O, polys, nx);
-    if (nx) return fail(CN_ERR_ARG, "internal: chained row-dot batch outside the fused product");
-    const uint64_t *lift = P.d;                                    // NTT-form plaintexts are multiplied where they lie: no lift, no transform of theirs
-    uint32_t dstride = pstride;
-    if (!P.ntt) {
-        CHECK(ensure_scratch(ctx, al((size_t)npt * k * n * 8)));
-        uint64_t *lf = salloc<uint64_t>(ctx, (size_t)npt * k * n);
-        // lift every referenced plaintext into the k limbs (one launch), NTT them
-        hipLaunchKernelGGL(k_lift_plain, dim3(npt * k * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, P.d, lf, ctx->dc, ctx->chunks, pstride ? pstride : 1u);
-        HIPCHK(hipGetLastError()); launch_count(ctx);
-        CHECK(cn_run_ntt(ctx, lf, npt * k, 0, k, 0));
-        lift = lf; dstride = pstride ? 1u : 0u;
-    }
     uint64_t *o = O.d;
     const uint64_t *src = A.d;
-    if (a_bcast) {
-        for (uint32_t c = 0; c < count; c++)
-            if (o + c * item_words != src) HIPCHK(hipMemcpyAsync(o + c * item_words, src, item_words * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    } else if (o != src) HIPCHK(hipMemcpyAsync(o, src, count * item_words * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    uint32_t limbs = count * polys * k;
-    CHECK(cn_run_ntt(ctx, o, limbs, 0, k, 0));
-    hipLaunchKernelGGL(k_dyadic_pt, dim3(limbs * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, o, lift, dstride, ctx->dc, ctx->chunks, polys);
-    HIPCHK(hipGetLastError()); launch_count(ctx);
-    CHECK(cn_run_ntt(ctx, o, limbs, 0, k, 1));
+    const bool alias = a_bcast && src >= o && src < o + (size_t)count * item_words;
+    const PlainPlan p = cn_plain_plan(ctx->hc, plain_switches(ctx), {count, polys, pstride, P.ntt, a_bcast, nx != nullptr, alias});
+    if (p.refusal) return fail(CN_ERR_ARG, "%s", p.refusal);
+    uint64_t *arr[PLAIN_ARRAYS] = {nx ? nx->ctn : nullptr, nullptr, nullptr};      // (a chained batch brings its `ctn`: no ensure_scratch, the caller's arena must not move)
+    size_t bytes = 0;
+    for (uint32_t i = 0; i < p.arrays; i++) bytes += al(p.scratch[i].bytes);
+    if (p.arrays) CHECK(ensure_scratch(ctx, bytes));
+    for (uint32_t i = 0; i < p.arrays; i++)
+        if (!(arr[p.scratch[i].id] = salloc<uint64_t>(ctx, p.scratch[i].bytes / 8))) return fail(CN_ERR_HIP, "internal: scratch exhausted in multiply_plain");
+    if (arr[PLAIN_KEEP]) {                                         // one input ciphertext broadcast over the outputs: it must survive until the last block has read it
+        HIPCHK(hipMemcpyAsync(arr[PLAIN_KEEP], src, item_words * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        src = arr[PLAIN_KEEP];
+    }
+    const RrOps *rr = rr_ops[p.policy];
+    switch (p.form) {
+    case PLAIN_BCAST:                                              // transform the ciphertext once, the plaintexts inside the product kernel
+        HIPCHK(hipMemcpyAsync(arr[PLAIN_CTN], src, item_words * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        CHECK(cn_run_ntt(ctx, arr[PLAIN_CTN], polys * k, 0, k, 0));
+        rr->mul_plain_bcast(ctx, P.d, pstride, arr[PLAIN_CTN], o, count, polys, nx ? (uint32_t)nx->elt : 0u, nx ? nx->out : nullptr, P.ntt);
+        break;
+    case PLAIN_PTN_FUSED:                                          // pstride as given
+        rr->mul_plain_fused(ctx, nullptr, 0, 0, const_cast<uint64_t *>(P.d), src, a_bcast ? 0 : item_words, pstride, o, count, polys);
+        break;
+    case PLAIN_LIFT_FUSED:
+        rr->mul_plain_fused(ctx, P.d, pstride ? pstride : 1u, npt, arr[PLAIN_LIFT], src, a_bcast ? 0 : item_words, pstride ? 1u : 0u, o, count, polys);
+        break;
+    case PLAIN_LEGACY: {
+        const uint64_t *lift = P.d;                                // NTT-form plaintexts are multiplied where they lie: no lift, no transform of theirs
+        if (!P.ntt) {                                              // lift every referenced plaintext into the k limbs (one launch), NTT them
+            hipLaunchKernelGGL(k_lift_plain, dim3(npt * k * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, P.d, arr[PLAIN_LIFT], ctx->dc, ctx->chunks, pstride ? pstride : 1u);
+            HIPCHK(hipGetLastError());
+            CHECK(cn_run_ntt(ctx, arr[PLAIN_LIFT], npt * k, 0, k, 0));
+            lift = arr[PLAIN_LIFT];
+        }
+        if (a_bcast) {
+            for (uint32_t c = 0; c < count; c++)
+                if (o + c * item_words != src) HIPCHK(hipMemcpyAsync(o + c * item_words, src, item_words * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        } else if (o != src) HIPCHK(hipMemcpyAsync(o, src, count * item_words * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        const uint32_t limbs = count * polys * k;
+        CHECK(cn_run_ntt(ctx, o, limbs, 0, k, 0));
+        hipLaunchKernelGGL(k_dyadic_pt, dim3(limbs * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, o, lift, P.ntt ? pstride : (pstride ? 1u : 0u), ctx->dc, ctx->chunks, polys);
+        HIPCHK(hipGetLastError());
+        CHECK(cn_run_ntt(ctx, o, limbs, 0, k, 1));
+        break;
+    }
+    }
+    HIPCHK(hipGetLastError()); launch_count(ctx, p.launches);
+    ctx->ptn_bcast += p.ptn_bcast; ctx->st.ntt_forward_limbs += p.fwd_limbs; ctx->st.ntt_inverse_limbs += p.inv_limbs;
     ctx->st.PlainMultiplication += count;
     return 0;
 }
@@ -173,25 +147,27 @@ extern "C" int cn_mul_plain(cn_ctx *ctx, cn_handle a, uint32_t ai, cn_handle pt,
 API_END }
 // ptn[oi + i] = NTT-form of pt[pi + i], i < count: Evaluator.TransformToNtt(plain, parms_id) of SEAL (evaluator.cpp; the reference never calls it - its plaintext
 // products transform their operand on every call, EncryptedSealBfvMatrix.cs:79-120).  The words the product kernels read: limb j = NTT_j(lift_j(m)), canonical.
-// Register-radix sizes: ONE launch of k_lift_ntt into the array; other sizes and "legacy_ntt": k_lift_plain + the generic transform.  Only kernel launches: allowed
-// while a graph is recorded; the zero flags travel at call time.
+// Only kernel launches: allowed while a graph is recorded; the zero flags travel at call time.
+// pt_to_ntt: register-radix sizes ONE launch of k_lift_ntt into the array; other sizes and "legacy_ntt": k_lift_plain + the generic transform (cn_diag_encode writes its
+// NTT-form output through it, too)
+int pt_to_ntt(cn_ctx *ctx, const uint64_t *src, uint32_t count, uint64_t *dst) {
+    const uint32_t k = ctx->hc.k;
+    const PlainSwitches sw = plain_switches(ctx);
+    if (sw.rr) {
+        rr_ops[plain_policy(ctx->hc, sw)]->mul_plain_fused(ctx, src, 1, count, dst, nullptr, 0, 0, nullptr, 0, 0);
+        HIPCHK(hipGetLastError()); launch_count(ctx);
+        ctx->st.ntt_forward_limbs += (uint64_t)count * k;
+        return 0;
+    }
+    hipLaunchKernelGGL(k_lift_plain, dim3(count * k * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, src, dst, ctx->dc, ctx->chunks, 1u);
+    HIPCHK(hipGetLastError()); launch_count(ctx);
+    return cn_run_ntt(ctx, dst, count * k, 0, k, 0);
+}
 extern "C" int cn_pt_transform(cn_ctx *ctx, cn_handle pt, uint32_t pi, uint32_t count, cn_handle ptn, uint32_t oi) { API_BODY
     LOCK; GETPT(P, pt); GETPTN(O, ptn);
     if (!range_ok(P, pi, count) || !range_ok(O, oi, count)) return fail(CN_ERR_ARG, "index out of range");
     if (!count) return 0;
-    const uint32_t n = ctx->hc.n, k = ctx->hc.k;
-    const uint64_t *src = P->d + (size_t)pi * n;
-    uint64_t *dst = O->d + (size_t)oi * O->item_words;
-    if (rr_kernels(ctx)) {
-        const int pol = cn_policy(cn_mod_range(ctx->hc, 0, k), ctx->opt.f64);
-        rr_ops[pol]->mul_plain_fused(ctx, src, 1, count, dst, nullptr, 0, 0, nullptr, 0, 0);
-        HIPCHK(hipGetLastError()); launch_count(ctx);
-        ctx->st.ntt_forward_limbs += (uint64_t)count * k;
-    } else {
-        hipLaunchKernelGGL(k_lift_plain, dim3(count * k * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, src, dst, ctx->dc, ctx->chunks, 1u);
-        HIPCHK(hipGetLastError()); launch_count(ctx);
-        CHECK(cn_run_ntt(ctx, dst, count * k, 0, k, 0));
-    }
+    CHECK(pt_to_ntt(ctx, P->d + (size_t)pi * ctx->hc.n, count, O->d + (size_t)oi * O->item_words));
     for (uint32_t c = 0; c < count; c++) O->pt_zero[oi + c] = P->pt_zero[pi + c];
     return 0;
 API_END }
@@ -914,50 +890,38 @@ extern "C" int cn_rotate_columns_add(cn_ctx *ctx, cn_handle in, uint32_t ii, cn_
 API_END }
 // SumAllSlots(length) of AtomicSealBfvVector.cs:888-935 on `count` single-block ciphertexts at once, in place: the column swap when
 // length >= N/2, then log2 rotate-and-add steps (RotateRows(-2^s) + AddInplace).  length 0 = all N slots.
-// the Galois elements of SumAllSlots(length) if the whole chain runs on the one-launch key switch with every link handing sigma_next(c1) on (N = 16384, batch); else empty
-std::vector<uint64_t> sum_slots_chain_elts(cn_ctx *ctx, uint32_t count, uint32_t length) {
-    const uint32_t n = ctx->hc.n, half = n / 2;
-    std::vector<uint64_t> elts;
-    bool ok = ctx->opt.ks_chain && count > 0;
-    uint32_t l2 = length ? length : n;
-    if (l2 >= half) { elts.push_back(2ull * n - 1); l2 = half; }
-    for (uint32_t steps = 1; steps < l2 && ok; steps *= 2) elts.push_back(cn_elt_of_step(n, -(int)steps));
-    for (uint64_t e : elts) { const KsKey *key = galois_key(ctx, e); if (!key || ks_plan(ctx, *key, count, 1).form != KS_PAIR14) { ok = false; break; } }
-    if (!ok || elts.size() < 2) elts.clear();
-    return elts;
-}
-// first_ready: the scratch arena already holds sigma_(elts[0])(c1) of every ciphertext at its start (written by the producer of h: k_mul_plain_bcast) and is large enough
-int sum_slots_impl(cn_ctx *ctx, CtSpan h, uint32_t length, bool first_ready) {
-    const uint32_t n = ctx->hc.n, half = n / 2, count = h.count;
-    uint32_t len = length ? length : n;
-    {   // N = 16384, batch: the links of the chain as ONE launch each - link s leaves sigma_(s+1) of its new c1 beside its result (k_keyswitch_pair14), so only the
-        // first link needs a permutation pass (none when the producer has left it).  Same words as the loop below (the same key switches on the same operands).
-        const std::vector<uint64_t> elts = sum_slots_chain_elts(ctx, count, length);
-        if (elts.empty() && first_ready) return fail(CN_ERR_ARG, "internal: chained row-dot batch without a chain");
-        if (!elts.empty()) {
-            const size_t kn = (size_t)ctx->hc.k * n;
-            if (first_ready) ctx->soff = 0; else CHECK(ensure_scratch(ctx, al(count * ctx->ctw2 * 8)));
-            uint64_t *pp[2]; pp[0] = salloc<uint64_t>(ctx, count * ctx->ctw2); pp[1] = pp[0] + (size_t)count * kn;
-            for (size_t s = 0; s < elts.size(); s++) {
-                const bool last = s + 1 == elts.size();
-                CHECK(do_galois(ctx, {.in = h.d, .elt = elts[s], .out = h.d, .tmp = pp[s & 1], .count = count, .acc = h.d, .pre = (s || first_ready) ? pp[s & 1] : nullptr,
-                                      .next_elt = last ? 0 : elts[s + 1], .next_out = pp[(s + 1) & 1]}));
-            }
-            return 0;
+// (the sequence and whether it runs as the one-launch chain: sum_slots_seq / sum_slots_plan, cn_plain_plan.h)
+static int galois_key_form(cn_ctx *ctx, uint64_t elt) { const KsKey *key = galois_key(ctx, elt); return key ? (int)key->f64 : -1; }
+// ready: the chained row-dot batch's plan - its arena already holds sigma_(chain[0])(c1) of every ciphertext at chain_off (written by the producer of h: k_mul_plain_bcast)
+int sum_slots_impl(cn_ctx *ctx, CtSpan h, uint32_t length, const RowdotPlan *ready) {
+    const uint32_t n = ctx->hc.n, count = h.count;
+    // N = 16384, batch: the links of the chain as ONE launch each - link s leaves sigma_(s+1) of its new c1 beside its result (k_keyswitch_pair14), so only the
+    // first link needs a permutation pass (none when the producer has left it).  Same words as the loop below (the same key switches on the same operands).
+    const std::vector<uint64_t> elts = ready ? ready->chain : sum_slots_plan(ctx->hc, plain_switches(ctx), count, length, [&](uint64_t e) { return galois_key_form(ctx, e); });
+    if (elts.empty() && ready) return fail(CN_ERR_ARG, "internal: chained row-dot batch without a chain");
+    if (!elts.empty()) {
+        const size_t kn = (size_t)ctx->hc.k * n;
+        if (ready) ctx->soff = ready->chain_off; else CHECK(ensure_scratch(ctx, al(count * ctx->ctw2 * 8)));
+        uint64_t *pp[2]; pp[0] = salloc<uint64_t>(ctx, count * ctx->ctw2); pp[1] = pp[0] + (size_t)count * kn;
+        for (size_t s = 0; s < elts.size(); s++) {
+            const bool last = s + 1 == elts.size();
+            CHECK(do_galois(ctx, {.in = h.d, .elt = elts[s], .out = h.d, .tmp = pp[s & 1], .count = count, .acc = h.d, .pre = (s || ready) ? pp[s & 1] : nullptr,
+                                  .next_elt = last ? 0 : elts[s + 1], .next_out = pp[(s + 1) & 1]}));
         }
+        return 0;
     }
-    if (len >= half) { CHECK(galois_impl(ctx, h, 2ull * n - 1, h, h)); len = half; }
-    for (uint32_t steps = 1; steps < len; steps *= 2) CHECK(rotate_rows_add_impl(ctx, h, -(int)steps, h, h));
+    const SumSlotsSeq seq = sum_slots_seq(n, length);
+    if (seq.columns) CHECK(galois_impl(ctx, h, 2ull * n - 1, h, h));
+    for (uint32_t i = 0; i < seq.rows; i++) CHECK(rotate_rows_add_impl(ctx, h, -(int)(1u << i), h, h));
     return 0;
 }
 extern "C" int cn_sum_slots(cn_ctx *ctx, cn_handle h, uint32_t first, uint32_t count, uint32_t length) { API_BODY TWO_LIMBS("cn_sum_slots");
     LOCK_ONLY; GETCT(H, h, 2); SPAN(sh, H, first, count);
     if (!count) return 0;
     if (queues(ctx, count)) {
-        const uint32_t n = ctx->hc.n, half = n / 2;
-        uint32_t len = length ? length : n;
-        if (len >= half) { CHECK(columns_key(ctx)); len = half; }
-        for (uint32_t st = 1; st < len; st *= 2) CHECK(plan_rotation(ctx, -(int)st));
+        const SumSlotsSeq seq = sum_slots_seq(ctx->hc.n, length);
+        if (seq.columns) CHECK(columns_key(ctx));
+        for (uint32_t i = 0; i < seq.rows; i++) CHECK(plan_rotation(ctx, -(int)(1u << i)));
         rec_sum_slots(ctx, length);
         return defer_staged(ctx, DOP_SUMSLOTS, sh, CtSpan{}, sh, length);
     }
@@ -974,19 +938,14 @@ extern "C" int cn_rowdot_batch(cn_ctx *ctx, cn_handle v, uint32_t vi, cn_handle 
     if (V == O && vi >= oi && vi < oi + rows) return fail(CN_ERR_ARG, "row-dot batch cannot overwrite its input");
     SPAN(sv, V, vi, 1); SPAN(so, O, oi, rows); PTSPAN(sp, P, pi, rows, 1u);
     if (length != 1) rec_sum_slots(ctx, length);
-    const bool ptn_fused = sp.ntt && !cn_rr_ptn_bcast(cn_policy(cn_mod_range(ctx->hc, 0, ctx->hc.k), ctx->opt.f64), ctx->hc.logn);   // NTT-form rows without a broadcast kernel
-    if (length != 1 && mul_plain_takes_bcast(ctx, rows) && !ptn_fused) {
-        // the product kernel hands the chain its first permuted c1 (no k_galois_limbs pass over the products): one arena for the chain's two scratch arrays and the
-        // transformed ciphertext, sized here and left where it is until the chain has run
-        const std::vector<uint64_t> elts = sum_slots_chain_elts(ctx, rows, length);
-        if (!elts.empty()) {
-            CHECK(ensure_scratch(ctx, al(rows * ctx->ctw2 * 8) + al(ctx->ctw2 * 8)));
-            uint64_t *p0 = salloc<uint64_t>(ctx, rows * ctx->ctw2), *ctn = salloc<uint64_t>(ctx, ctx->ctw2);
-            if (!p0 || !ctn) return fail(CN_ERR_HIP, "internal: scratch exhausted in the row-dot batch");
-            const BcastNext nx{elts[0], p0, ctn};
-            CHECK(mul_plain_impl(ctx, sv, true, sp, so, 2, &nx));
-            return sum_slots_impl(ctx, so, length, true);
-        }
+    const RowdotPlan rd = rowdot_plan(ctx->hc, plain_switches(ctx), rows, length, sp.ntt, [&](uint64_t e) { return galois_key_form(ctx, e); });
+    if (!rd.chain.empty()) {                                       // one arena for the chain's two scratch arrays and the transformed ciphertext (RowdotPlan)
+        CHECK(ensure_scratch(ctx, al(rd.pp_bytes) + al(rd.ctn_bytes)));
+        uint64_t *p0 = salloc<uint64_t>(ctx, rd.pp_bytes / 8), *ctn = salloc<uint64_t>(ctx, rd.ctn_bytes / 8);
+        if (!p0 || !ctn) return fail(CN_ERR_HIP, "internal: scratch exhausted in the row-dot batch");
+        const BcastNext nx{rd.chain[0], p0, ctn};
+        CHECK(mul_plain_impl(ctx, sv, true, sp, so, 2, &nx));
+        return sum_slots_impl(ctx, so, length, &rd);
     }
     CHECK(mul_plain_impl(ctx, sv, true, sp, so, 2));
     if (length == 1) return 0;
@@ -1014,10 +973,9 @@ extern "C" int cn_mul_plain_sum(cn_ctx *ctx, cn_handle ct, uint32_t ci, cn_handl
         if (A == O && ci + ct_idx[e] >= oi && ci + ct_idx[e] < oi + G) return fail(CN_ERR_ARG, "cn_mul_plain_sum cannot overwrite a ciphertext it reads");
     }
     for (uint32_t e = 0; e < E; e++) if (P->pt_zero[pi + e]) return fail(CN_ERR_ZERO, "plain cannot be zero");
-    const uint32_t n = ctx->hc.n, k = ctx->hc.k;
-    const CnModRange qr = cn_mod_range(ctx->hc, 0, k);
-    const int pol = cn_policy(qr, ctx->opt.f64);
-    if (!(ctx->opt.mp_fused && rr_kernels(ctx) && (ptn ? cn_l_mul_ptn_sum_kernel(pol, ctx->hc.logn) : cn_l_mul_plain_sum_kernel(pol, ctx->hc.logn)))) {      // compose the existing calls
+    const uint32_t k = ctx->hc.k;
+    const PlainSumPlan sp = plain_sum_plan(ctx->hc, plain_switches(ctx), ptn, G, E);
+    if (!sp.kernel) {                                                // compose the existing calls
         cn_handle tmp = 0;
         CHECK(alloc_buf(ctx, 0, maxlen, 2, &tmp));
         int rc = 0;
@@ -1042,33 +1000,18 @@ extern "C" int cn_mul_plain_sum(cn_ctx *ctx, cn_handle ct, uint32_t ci, cn_handl
         const int rf = free_body(ctx, tmp);
         return rc ? rc : rf;
     }
-    // the distinct ciphertexts, in order of first appearance -> slots of the NTT-form scratch copy
-    std::vector<uint32_t> slot(E), src;
-    {
-        std::unordered_map<uint32_t, uint32_t> seen;
-        for (uint32_t e = 0; e < E; e++) {
-            auto it = seen.find(ct_idx[e]);
-            if (it == seen.end()) { it = seen.emplace(ct_idx[e], (uint32_t)src.size()).first; src.push_back(ct_idx[e]); }
-            slot[e] = it->second;
-        }
-    }
-    const uint32_t D = (uint32_t)src.size();
-    CHECK(ensure_scratch(ctx, al((size_t)D * A->item_words * 8) + al((size_t)(G + 1) * 4) + al((size_t)E * 4)));
+    const PlainSumSlots ss = plain_sum_slots(ct_idx, E);             // the distinct ciphertexts -> slots of the NTT-form scratch copy
+    const uint32_t D = (uint32_t)ss.src.size();
+    CHECK(ensure_scratch(ctx, al(D * sp.src_bytes) + al(sp.grp_bytes) + al(sp.slot_bytes)));
     uint64_t *ctn = salloc<uint64_t>(ctx, (size_t)D * A->item_words);
     if (!ctn) return fail(CN_ERR_HIP, "internal: scratch exhausted in cn_mul_plain_sum");
     uint32_t *dgo, *dslot;
-    CHECK(upload_tmp(ctx, grp_off, (size_t)G + 1, &dgo)); CHECK(upload_tmp(ctx, slot.data(), E, &dslot));
-    for (uint32_t s = 0; s < D;) {                                                // runs of neighbouring ciphertexts travel in one copy (baby steps: one run)
-        uint32_t r = 1;
-        while (s + r < D && src[s + r] == src[s] + r) r++;
-        HIPCHK(hipMemcpyAsync(ctn + (size_t)s * A->item_words, A->d + (size_t)(ci + src[s]) * A->item_words, (size_t)r * A->item_words * 8, hipMemcpyDeviceToDevice, ctx->stream));
-        s += r;
-    }
+    CHECK(upload_tmp(ctx, grp_off, (size_t)G + 1, &dgo)); CHECK(upload_tmp(ctx, ss.slot.data(), E, &dslot));
+    for (const PlainSumSlots::Run &r : ss.runs)                      // runs of neighbouring ciphertexts travel in one copy
+        HIPCHK(hipMemcpyAsync(ctn + (size_t)r.first * A->item_words, A->d + (size_t)(ci + ss.src[r.first]) * A->item_words, (size_t)r.len * A->item_words * 8, hipMemcpyDeviceToDevice, ctx->stream));
     CHECK(cn_run_ntt(ctx, ctn, D * 2 * k, 0, k, 0));
-    const uint32_t accmax = pol == POL_U64 ? 0xffffffffu : (qr.bits >= 50 ? 1u : (1u << std::min(10, 50 - qr.bits)));      // lazy FP64 accumulators: |term| <= 2.1 q, sum below 2^52
-    if (ptn) CHECK(cn_l_mul_ptn_sum(ctx, pol, MulPlainSumLaunch{P->d + (size_t)pi * P->item_words, ctn, dgo, dslot, O->d + (size_t)oi * O->item_words, G,
-                                                                pol == POL_U64 ? 0xffffffffu : cn_ptn_sum_interval(qr.qmax)}));
-    else CHECK(cn_l_mul_plain_sum(ctx, pol, MulPlainSumLaunch{P->d + (size_t)pi * n, ctn, dgo, dslot, O->d + (size_t)oi * O->item_words, G, accmax}));
+    const MulPlainSumLaunch launch{P->d + (size_t)pi * P->item_words, ctn, dgo, dslot, O->d + (size_t)oi * O->item_words, G, sp.accmax, sp.order};
+    CHECK(ptn ? cn_l_mul_ptn_sum(ctx, sp.policy, launch) : cn_l_mul_plain_sum(ctx, sp.policy, launch));
     if (!ptn) ctx->st.ntt_forward_limbs += (uint64_t)E * 2 * k;      // the plaintexts, beside the D 2k limbs cn_run_ntt counted (NTT-form plaintexts: those are all that ran)
     ctx->st.ntt_inverse_limbs += (uint64_t)G * 2 * k;
     ctx->st.PlainMultiplication += E; ctx->st.AddMany += G; ctx->st.AddManyItemCount += E;

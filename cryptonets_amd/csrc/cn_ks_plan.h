@@ -54,7 +54,7 @@ inline KsPlan cn_ks_plan(const DevConsts &hc, const KsSwitches &sw, bool key_f64
     KsPlan p{ks_two_launch_form(hc, sw, cnt, galois), cn_policy(qr, key_f64), 0, 0, 0, false, false};
     const bool halves = sw.rr && hc.logn == 14 && sw.half_tables && key_f64 && sw.ks_split14;      // N = 16384 as 8192-point halves (FP64 policies)
     if (!ks_two_launch(p.form)) p.form = halves ? (sw.ks_pair14 ? KS_PAIR14 : KS_SPLIT14) : (sw.rr ? KS_FUSED : KS_LEGACY);
-    p.accmax = key_f64 ? (qr.bits >= 50 ? 1u : (1u << std::min(10, 50 - qr.bits))) : 0xffffffffu;      // lazy FP64 accumulators: |term| <= 2.1 q, sum below 2^52
+    p.accmax = key_f64 ? cn_f64_acc_interval(qr.bits) : 0xffffffffu;
     p.xcd_cts = sw.ks_xcd == 1 ? (cnt & ~7u) : (sw.ks_xcd == 2 ? 0x80000000u : 0u);
     switch (p.form) {
         case KS_DIGIT_MAC: p.arena_bytes = (size_t)cnt * tot * ct_bytes; break;

@@ -7,10 +7,8 @@ template <class K> static int diag_big_lds(K kern, size_t bytes) {
     HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
     return 0;
 }
-// The integer policy has no kernel at N = 16384: the integer transform beside 16 64-bit accumulators does not fit the 128 registers a 1024-thread workgroup leaves a
-// thread (25 spilled registers when built) - cn_mul_plain_sum composes the existing calls there (cn_l_mul_plain_sum_kernel)
-template <int L, class AR> static constexpr bool diag_has() { return L <= 13 || !std::is_same<typename AR::T, uint64_t>::value; }
-bool cn_l_mul_plain_sum_kernel(int policy, uint32_t logn) { return cn_rr_size(logn) && !(policy == POL_U64 && logn == 14); }
+// instantiated where cn_plain_wide (cn_policy.h) says so: the plan (cn_plain_plan.h) composes the existing calls elsewhere
+template <int L, class AR> static constexpr bool diag_has() { return cn_plain_wide(std::is_same<typename AR::T, uint64_t>::value ? POL_U64 : POL_F64, L); }
 template <int L> static int diag_attrs_l(size_t bytes) {
     if constexpr (diag_has<L, ArU64>()) CHECK(diag_big_lds(k_mul_plain_sum<L, ArU64>, bytes));
     CHECK(diag_big_lds(k_mul_plain_sum<L, ArF64>, bytes)); CHECK(diag_big_lds(k_mul_plain_sum<L, ArF64L>, bytes));

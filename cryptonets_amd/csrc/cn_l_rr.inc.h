@@ -6,6 +6,7 @@
 
 typedef RR_POLICY AR;
 static constexpr bool kF64 = std::is_same<typename AR::T, double>::value;
+template <int L> static constexpr bool kPtnBcast = cn_plain_wide(kF64 ? POL_F64 : POL_U64, L);      // k_mul_plain_bcast<L, AR, true> is instantiated
 
 template <class K> static int big_lds(K kern, size_t bytes) {
     HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
@@ -19,7 +20,7 @@ template <int L> static int set_attrs_l(size_t bytes) {
                                  CHECK(big_lds(k_square_fused<L, AR, true, NttOut01>, bytes + ((size_t)8 << L))); CHECK(big_lds(k_square_pipe<L, AR, NttOut01>, bytes + ((size_t)8 << L))); }
     }
     CHECK(big_lds(k_lift_ntt<L, AR>, bytes)); CHECK(big_lds(k_mul_plain_fused<L, AR>, bytes)); CHECK(big_lds(k_mul_plain_bcast<L, AR>, bytes));
-    if constexpr (kF64 || L <= 13) CHECK(big_lds(k_mul_plain_bcast<L, AR, true>, bytes));
+    if constexpr (kPtnBcast<L>) CHECK(big_lds(k_mul_plain_bcast<L, AR, true>, bytes));
 #ifdef RR_ENC_TAIL
     CHECK(big_lds(k_encrypt_tail<L, AR>, bytes));
 #endif
@@ -98,9 +99,9 @@ static bool mul_plain_fused(cn_ctx *c, const uint64_t *pt, uint32_t pitch, uint3
 // one ciphertext (NTT form in ctn) times `count` plaintexts: one launch.  ptn: the plaintexts are rows of an NTT-form array ([row][k][N], pitch in rows)
 template <int L> static void l_mul_plain_bcast(cn_ctx *c, const uint64_t *pt, uint32_t pitch, const uint64_t *ctn, uint64_t *out, uint32_t count, uint32_t polys, uint32_t next_elt,
                                                uint64_t *next_out, bool ptn) {
-    // (no NTT-form instantiation under the integer policy at N = 16384, where it spills like the default form does: cn_rr_ptn_bcast, the caller runs k_mul_plain_fused alone)
+    // (NTT-form rows where cn_plain_wide says so; elsewhere the plan runs k_mul_plain_fused alone, cn_plain_plan.h)
     if (ptn) {
-        if constexpr (kF64 || L <= 13)
+        if constexpr (kPtnBcast<L>)
             hipLaunchKernelGGL((k_mul_plain_bcast<L, AR, true>), dim3(count * polys * c->hc.k), dim3(NttPlan<L>::NT), (size_t)ntt_lds_words(1u << L) * 8, c->stream, pt, pitch, ctn, out,
                                c->dc, polys, next_elt, next_out);
     } else hipLaunchKernelGGL((k_mul_plain_bcast<L, AR>), dim3(count * polys * c->hc.k), dim3(NttPlan<L>::NT), (size_t)ntt_lds_words(1u << L) * 8, c->stream, pt, pitch, ctn, out, c->dc, polys,

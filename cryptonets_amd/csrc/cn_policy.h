@@ -82,7 +82,13 @@ inline uint32_t cn_ptn_sum_interval(uint64_t qmax, bool *capped = nullptr) {
     if (capped) *capped = fit > CN_PTN_INTERVAL_CAP;
     return fit > CN_PTN_INTERVAL_CAP ? CN_PTN_INTERVAL_CAP : (fit ? (uint32_t)fit : 1u);
 }
-// k_mul_plain_bcast on NTT-form rows: every register-radix size but N = 16384 under the integer policy (spills; the product kernel alone runs there)
-inline bool cn_rr_ptn_bcast(int policy, uint32_t logn) { return !(policy == POL_U64 && logn == 14); }
+// The wide plaintext kernels - k_mul_plain_bcast on NTT-form rows, k_mul_plain_sum, k_mul_ptn_sum - exist at every register-radix size but N = 16384 under the integer
+// policy: beside a 1024-thread workgroup's 128 registers per thread the integer transform leaves no room for their accumulators or row loads (25, 50 and 2 spilled
+// registers when built).  There the row-dot batch runs k_mul_plain_fused alone and cn_mul_plain_sum composes cn_mul_plain and AddMany (cn_plain_plan.h); the launchers
+// instantiate by the same predicate, so a kernel the plan picks is a kernel that was built.
+constexpr bool cn_plain_wide(int policy, uint32_t logn) { return !(policy == POL_U64 && logn == 14); }
+// Lazy FP64 accumulators of products of canonical words (the key switch's digit sums, k_mul_plain_sum): |term| <= 2.1 q, so this many terms between two recentrings
+// keep the sum below 2^52
+inline uint32_t cn_f64_acc_interval(int bits) { return bits >= 50 ? 1u : 1u << (50 - bits < 10 ? 50 - bits : 10); }
 // the ring sizes of the register-radix kernels: 1024 <= N <= 16384, or N <= 8192 (max_logn = 13) for the kernels that stop there
 inline bool cn_rr_size(uint32_t logn, uint32_t max_logn = 14) { return logn >= 10 && logn <= max_logn; }

@@ -383,14 +383,13 @@ struct ProductSumLaunch { const uint64_t *prod; uint32_t K; uint64_t *out; void 
 int cn_l_product_sum(cn_ctx *c, const ProductSumLaunch &g);
 // sums of plaintext x ciphertext products (cn_mul_plain_sum; cn_l_diag.hip, k_mul_plain_sum): group g < groups = terms [grp_off[g], grp_off[g + 1]), term e = plaintext
 // pt + e N (coefficients mod t) times the NTT-form ciphertext ctn + slot[e] 2kN; out [groups][2][k][N].  grp_off / slot: device memory.  policy: cn_policy of the q limbs
-struct MulPlainSumLaunch { const uint64_t *pt, *ctn; const uint32_t *grp_off, *slot; uint64_t *out; uint32_t groups, accmax; };
+// Both launchers have a kernel where cn_plain_wide (cn_policy.h) holds; accmax and order come from the plan (PlainSumPlan, cn_plain_plan.h)
+struct MulPlainSumLaunch { const uint64_t *pt, *ctn; const uint32_t *grp_off, *slot; uint64_t *out; uint32_t groups, accmax, order; };      // order: k_mul_ptn_sum only ("ptn_order")
 int cn_l_mul_plain_sum(cn_ctx *c, int policy, const MulPlainSumLaunch &a);
-bool cn_l_mul_plain_sum_kernel(int policy, uint32_t logn);      // is there a kernel?  Every register-radix size but N = 16384 under the integer policy
 int cn_l_diag_set_attrs(uint32_t logn, size_t lds);
 // the same sums over an NTT-form plaintext array (cn_l_ptn.hip, k_mul_ptn_sum): a.pt = the NTT-form words of term 0 ([term][k][N], cn_pt_transform), a.accmax = the
-// recentring interval of the lazy FP64 accumulators (cn_ptn_sum_interval, cn_policy.h).  A kernel at every register-radix size but N = 16384 under the integer policy
+// recentring interval of the lazy FP64 accumulators (cn_ptn_sum_interval, cn_policy.h)
 int cn_l_mul_ptn_sum(cn_ctx *c, int policy, const MulPlainSumLaunch &a);
-bool cn_l_mul_ptn_sum_kernel(int policy, uint32_t logn);
 int cn_l_ptn_set_attrs(uint32_t logn, size_t lds);
 // a diagonal plan built on the device (cn_diag_scan, cn_diag_encode; cn_l_diagplan.hip, cn_k_diagplan.hip.h): S = the slot-order weight matrix [R][N] decoded from the row
 // plaintexts, of which rows below R and columns below dim are read.  A run = up to CN_DIAG_RUN terms (c, J, b0 + db) that are neighbours in the term list; `first` counts

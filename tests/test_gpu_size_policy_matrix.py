@@ -88,11 +88,11 @@ def form(family, policy, n, width):
         return "kernel", "a kernel at every register-radix size and policy (BY_SIZE, cn_l_rr.inc.h; launch, cn_l_ks.inc.h)"
     if family in ("mul_plain_sum", "mul_ptn_sum"):
         if policy == "u64" and n == 16384:
-            return "composed", "cn_l_mul_plain_sum_kernel / cn_l_mul_ptn_sum_kernel (cn_l_diag.hip:13, cn_l_ptn.hip:36): cn_mul_plain per term + k_add_many"
+            return "composed", "cn_plain_wide (cn_policy.h) through plain_sum_plan (cn_plain_plan.h): cn_mul_plain per term + k_add_many"
         return "kernel", "k_mul_plain_sum<L, AR> / k_mul_ptn_sum<L, AR, 2, WS, D>"
     if family == "ptn_bcast":
         if policy == "u64" and n == 16384:
-            return "composed", "cn_rr_ptn_bcast (cn_policy.h:50): k_mul_plain_fused alone on the NTT-form rows"
+            return "composed", "cn_plain_wide (cn_policy.h) through cn_plain_plan (cn_plain_plan.h): k_mul_plain_fused alone on the NTT-form rows"
         return "kernel", "k_mul_plain_bcast<L, AR, true>"
     if family in ("square_gemm", "mul_relin_sum"):
         if policy in FP64 and n <= 8192 and width == 10:
@@ -337,7 +337,7 @@ def test_d_mul_plain_on_both_plaintext_forms(cell):
 @pytest.mark.parametrize("ks_wide", [-1, 0])
 def test_d_rowdot_batch_on_both_plaintext_forms(cell, ks_wide):
     """5 rows of length 8 against one ciphertext: the broadcast product kernel on coefficient rows and on NTT-form rows, then the rotate-and-add chain.  Under
-    "ks_wide" 0 at N = 16384 (FP64 policies) the product kernel hands the chain its first permuted c1.  "ptn_bcast" moves exactly where cn_rr_ptn_bcast holds."""
+    "ks_wide" 0 at N = 16384 (FP64 policies) the product kernel hands the chain its first permuted c1.  "ptn_bcast" moves exactly where cn_plain_wide holds."""
     o, g = cell.o, cell.g
     rng = np.random.default_rng(0xD8 + cell.n)
     rows = 5
