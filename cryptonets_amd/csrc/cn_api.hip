@@ -186,34 +186,6 @@ int pick_stream(cn_ctx *c) {
     for (hipStream_t s : rejected) if (s != c->stream) (void)hipStreamDestroy(s);
     return 0;
 }
-// The tunables of CnTunables (cn_runtime.h): cn_set_option / cn_get_option by name and, where `env` is set, an environment override read at creation.
-// A flag stores "non-zero = on"; an enumerated switch refuses a value outside lo..hi, its environment override is clamped into the range.
-struct OptionSpec { const char *name; int CnTunables::*member; int lo, hi; bool flag; const char *env; };
-static const OptionSpec kOptions[] = {
-    {"f64",           &CnTunables::f64,           0, 1, true,  nullptr},          // default: CN_NO_F64 (ctx_init); affects keys uploaded AFTER the call
-    {"legacy_ntt",    &CnTunables::legacy_ntt,    0, 1, true,  "CN_LEGACY_NTT"},
-    {"gemm_order",    &CnTunables::gemm_order,    0, 1, false, "CN_GEMM_ORDER"},
-    {"ks_perm_fused", &CnTunables::ks_perm_fused, 0, 1, true,  nullptr},
-    {"ks_xcd",        &CnTunables::ks_xcd,        0, 2, false, "CN_KS_XCD"},      // default by N (ctx_init)
-    {"sq_fused",      &CnTunables::sq_fused,      0, 1, true,  "CN_SQ_FUSED"},
-    {"sq_lds",        &CnTunables::sq_lds,        0, 1, true,  "CN_SQ_LDS"},
-    {"sq_pipe",       &CnTunables::sq_pipe,       0, 2, false, "CN_SQ_PIPE"},
-    {"sq_halves",     &CnTunables::sq_halves,     0, 2, false, "CN_SQ_HALVES"},
-    {"enc_fused",     &CnTunables::enc_fused,     0, 2, false, "CN_ENC_FUSED"},
-    {"fold_zero",     &CnTunables::fold_zero,     0, 1, true,  "CN_FOLD_ZERO"},
-    {"gemm_mfma",     &CnTunables::gemm_mfma,     0, 1, true,  "CN_GEMM_MFMA"},   // affects GEMMs planned AFTER the call
-    {"gemm_pair",     &CnTunables::gemm_pair,     0, 1, true,  "CN_GEMM_PAIR"},   // likewise
-    {"mp_fused",      &CnTunables::mp_fused,      0, 1, true,  "CN_MP_FUSED"},
-    {"ks_wide",       &CnTunables::ks_wide,      -1, 2, false, nullptr},
-    {"ks_split14",    &CnTunables::ks_split14,    0, 1, true,  nullptr},
-    {"ks_pair14",     &CnTunables::ks_pair14,     0, 1, true,  "CN_KS_PAIR14"},
-    {"ks_chain",      &CnTunables::ks_chain,      0, 1, true,  "CN_KS_CHAIN"},
-    {"mp_bcast",      &CnTunables::mp_bcast,      0, 1, true,  nullptr},
-};
-static const OptionSpec *find_option(const char *name) {
-    for (const OptionSpec &o : kOptions) if (!strcmp(name, o.name)) return &o;
-    return nullptr;
-}
 extern "C" int cn_ctx_create(uint32_t n, const uint64_t *q, uint32_t k, uint64_t t, int dbc, int gdbc, int device, cn_ctx **out) {
     if (!out || !q) return fail(CN_ERR_ARG, "null argument");
     int ndev = cn_device_count();
@@ -272,14 +244,8 @@ int ctx_init(cn_ctx *c, uint32_t n, uint32_t k, int device, std::vector<uint64_t
     c->smax = (size_t)((env ? atof(env) : 24.0) * (double)(1ull << 30));
     env = getenv("CN_POOL_GB");
     c->pool_max = (size_t)((env ? atof(env) : 8.0) * (double)(1ull << 30));
-    c->opt.f64 = !(getenv("CN_NO_F64") && atoi(getenv("CN_NO_F64")));
-    c->ptn_order = getenv("CN_PTN_ORDER") && atoi(getenv("CN_PTN_ORDER")) == 1;
-    // fused key switch, workgroup order: limb-major up to N = 8192 (one key slice per XCD L2 at a time: 2.34 GiB fetched per 845-ciphertext launch
-    // against 3.99 GiB in (ciphertext, limb) order and 3.0 GiB with the limbs of a ciphertext on one XCD, same kernel time -
-    // profiles/r03_pmc_keyswitch_orders.txt); (ciphertext, limb) order at N = 16384, where limb-major measured 30 % slower in round 1
-    c->opt.ks_xcd = c->hc.logn <= 13 ? 2 : 1;        // N = 16384 (k_keyswitch_pair14): the k workgroups of a ciphertext on one XCD - they share its source limbs in that L2 (34.3 vs 35.1 ms per 5488-ciphertext link)
-    for (const OptionSpec &o : kOptions)
-        if (const char *e = o.env ? getenv(o.env) : nullptr) c->opt.*o.member = o.flag ? atoi(e) != 0 : std::max(o.lo, std::min(o.hi, atoi(e)));
+    c->opt = cn_option_defaults(c->hc.logn);
+    cn_options_from_env(c->opt, getenv);
     HIPCHK(hipDeviceGetAttribute(&c->cus, hipDeviceAttributeMultiprocessorCount, device));
     size_t lds = (size_t)ntt_lds_words(n) * 8;
     if (lds > 48 * 1024) {                 // N >= 8192: the padded LDS image exceeds the default dynamic-LDS limit
@@ -346,98 +312,71 @@ void ctx_teardown(cn_ctx *ctx) {
     delete ctx->ring; delete ctx->ready;
     delete ctx;
 }
+// ---- options.  The switches (CnTunables) and the counters (CnCounters) go by the tables of cn_options.h; kValues below names whatever else cn_get_option reads -
+// state of the context, choices the library made (tests, diagnostics) - and, where `set` is there, cn_set_option writes.  The setters run under cn_set_option's LOCK
+static int set_defer(cn_ctx *ctx, int value) {      // 0 immediate, 1 queued under the context lock, 2 queued through the lock-free submission ring; the queue was drained by LOCK
+    if (value < 0 || value > 2) return fail(CN_ERR_ARG, "defer: 0, 1 or 2");
+    ctx->defer.store(value, std::memory_order_release);
+    if (value != 2) {                        // the ready single-ciphertext arrays of the lock-free mode go back to the pool
+        while (const cn_handle h = ctx->ready->pop()) CHECK(free_body(ctx, h));
+        ctx->ready->misses.store(0, std::memory_order_relaxed);
+    }
+    return 0;
+}
+static int set_ks_xi(cn_ctx *ctx, int value) {      // decomposition convention of the key switch (DevConsts::ks_xi); the keys must be of the same convention
+    if (ctx->level && (value != 0) != (ctx->hc.ks_xi != 0)) return fail(CN_ERR_ARG, "ks_xi of a level context is its parent's (its keys are)");
+    if (ctx->capturing || ctx->graphs_alive) return fail(CN_ERR_ARG, "ks_xi cannot change while a graph is recorded or alive (its kernels were chosen for the other convention)");
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    ctx->hc.ks_xi = value != 0;
+    HIPCHK(hipMemcpy(ctx->dc, &ctx->hc, sizeof(DevConsts), hipMemcpyHostToDevice));
+    return 0;
+}
+static int set_record_steps(cn_ctx *ctx, int value) {      // 1: record the RotateRows steps and column rotations asked for from now on (cn_rotation_steps); 0: stop and clear
+    ctx->rec_steps = value != 0;
+    if (!value) { ctx->rec_set.clear(); ctx->rec_cols = false; }
+    return 0;
+}
+static int sat(size_t v) { return (int)std::min<size_t>(v, 0x7fffffff); }
+struct ValueSpec { const char *name; int (*get)(cn_ctx *); int (*set)(cn_ctx *, int); };
+static const ValueSpec kValues[] = {
+    {"defer", [](cn_ctx *c) { return c->defer.load(std::memory_order_relaxed); }, set_defer},
+    {"ks_xi", [](cn_ctx *c) { return (int)c->hc.ks_xi; }, set_ks_xi},
+    {"record_steps", [](cn_ctx *c) { return (int)c->rec_steps; }, set_record_steps},
+    {"pin_laps", [](cn_ctx *c) { return (int)c->pin_laps; }, nullptr},                          // laps of the pinned upload ring (each one waits for the stream)
+    {"ready_handles", [](cn_ctx *c) { return (int)c->ready->size(); }, nullptr},                // allocated single-ciphertext arrays waiting for a lock-free cn_ct_alloc
+    {"sg_prefloor_min_k", [](cn_ctx *) { return (int)SG_PREFLOOR_MIN_K; }, nullptr},            // smallest K that takes the pre-floor form under "sg_prefloor" = 1
+    {"mul_sum_groups", [](cn_ctx *c) { return (int)c->ms_groups; }, nullptr},                   // output groups of the last cn_mul_relin_sum (0: the literal sequence)
+    {"mul_sum_min_k", [](cn_ctx *) { return (int)MUL_SUM_MIN_K; }, nullptr},                    // smallest K that takes the one-key-switch form
+    {"defer_pending_products", [](cn_ctx *c) { return (int)c->dq->sq->out.size(); }, nullptr},  // squarings whose relinearisation is held back right now
+    {"scratch_mib", [](cn_ctx *c) { return sat((c->scap + (1u << 20) - 1) >> 20); }, nullptr},  // size of the scratch arena right now (it only grows)
+    {"ptn_sum_interval", [](cn_ctx *c) { return (int)cn_ptn_sum_interval(cn_mod_range(c->hc, 0, c->hc.k).qmax); }, nullptr},   // terms between two recentrings of k_mul_ptn_sum's FP64 accumulators
+    {"packed_bad_residues", [](cn_ctx *c) { return sat(c->packed_bad.load()); }, nullptr},      // packed uploads that held a residue >= its modulus
+    {"behz_small_base", [](cn_ctx *c) { return (int)(c->hc.bsk[c->hc.kb - 1].q < (1ull << 49)); }, nullptr},     // auxiliary primes below 2^49 (FP64 kernels) instead of SEAL's 61-bit ones
+    {"behz_f64", [](cn_ctx *c) { return (int)(c->hc.behz_f64 && c->opt.f64); }, nullptr},
+    {"mod_switch_f64", [](cn_ctx *c) { return (int)c->ms_f64; }, nullptr},                      // the last cn_mod_switch on this context ran in FP64
+    {"aux_primes", [](cn_ctx *c) { return (int)c->hc.kb; }, nullptr},
+    {"pending_calls", [](cn_ctx *c) { return (int)c->dq->ops.size(); }, nullptr},
+    {"pool_arrays", [](cn_ctx *c) { size_t n = 0; for (auto &kv : c->pool) n += kv.second.size(); return sat(n); }, nullptr},   // cached arrays (a graph reserves its temporaries out of the pool)
+    {"stream_tries", [](cn_ctx *c) { return c->stream_tries; }, nullptr},                       // streams created until one had a hardware queue of its own (< 0: none had)
+};
 extern "C" int cn_set_option(cn_ctx *ctx, const char *name, int value) { API_BODY
     LOCK;
     if (!name) return fail(CN_ERR_ARG, "null option name");
-    if (const OptionSpec *o = find_option(name)) {
-        if (!o->flag && (value < o->lo || value > o->hi)) return fail(CN_ERR_ARG, "%s: %d .. %d", name, o->lo, o->hi);
-        ctx->opt.*o->member = o->flag ? value != 0 : value;
-        if (o->member == &CnTunables::f64 || o->member == &CnTunables::gemm_mfma || o->member == &CnTunables::gemm_pair) defer_square_drop_plans(ctx);   // (the switches build_gemm_plan reads)
+    bool refused;
+    if (const OptionSpec *o = cn_option_set(ctx->opt, name, value, &refused)) {
+        if (refused) return fail(CN_ERR_ARG, "%s: %d .. %d", name, o->lo, o->hi);
+        if (o->replan) defer_square_drop_plans(ctx);
         return 0;
     }
-    if (!strcmp(name, "defer")) {                // 0 immediate, 1 queued under the context lock, 2 queued through the lock-free submission ring; the queue was drained by LOCK
-        if (value < 0 || value > 2) return fail(CN_ERR_ARG, "defer: 0, 1 or 2");
-        ctx->defer.store(value, std::memory_order_release);
-        if (value != 2) {                        // the ready single-ciphertext arrays of the lock-free mode go back to the pool
-            while (const cn_handle h = ctx->ready->pop()) CHECK(free_body(ctx, h));
-            ctx->ready->misses.store(0, std::memory_order_relaxed);
-        }
-        return 0;
-    }
-    if (!strcmp(name, "ks_xi")) {                // decomposition convention of the key switch (DevConsts::ks_xi); the keys must be of the same convention
-        if (ctx->level && (value != 0) != (ctx->hc.ks_xi != 0)) return fail(CN_ERR_ARG, "ks_xi of a level context is its parent's (its keys are)");
-        if (ctx->capturing || ctx->graphs_alive) return fail(CN_ERR_ARG, "ks_xi cannot change while a graph is recorded or alive (its kernels were chosen for the other convention)");
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        ctx->hc.ks_xi = value != 0;
-        HIPCHK(hipMemcpy(ctx->dc, &ctx->hc, sizeof(DevConsts), hipMemcpyHostToDevice));
-        return 0;
-    }
-    if (!strcmp(name, "defer_square_gemm")) { ctx->defer_square_gemm = value != 0; return 0; }     // (LOCK has settled what the queue held back under the old value)
-    if (!strcmp(name, "digit_mfma")) { ctx->digit_mfma = value != 0; defer_square_drop_plans(ctx); return 0; }     // the digit GEMM of plans made AFTER the call: matrix cores where eligible / FP64 (cn_eval.hip)
-    if (!strcmp(name, "digit_i32")) { ctx->digit_i32 = value != 0; defer_square_drop_plans(ctx); return 0; }       // the digit sums of plans made AFTER the call (and of cn_mul_relin_sum): int32 words where they fit / doubles
-    if (!strcmp(name, "sg_prefloor")) {          // cn_square_gemm: one floor tail per dense output for components 0 and 1 - 0 never, 1 where the gate allows, 2 also below SG_PREFLOOR_MIN_K (cn_mul_plan.h)
-        if (value < 0 || value > 2) return fail(CN_ERR_ARG, "sg_prefloor: 0, 1 or 2");
-        ctx->sg_prefloor_mode = value;
-        return 0;
-    }
-    if (!strcmp(name, "mul_sum")) { ctx->mul_sum = value != 0; return 0; }       // cn_mul_relin_sum: one key switch per output where it can / always the literal sequence (cn_eval.hip)
-    if (!strcmp(name, "ptn_order")) {            // k_mul_ptn_sum, workgroup order: 0 limb-major, 1 limb = workgroup index mod k (cn_l_ptn.hip)
-        if (value < 0 || value > 1) return fail(CN_ERR_ARG, "ptn_order: 0 or 1");
-        ctx->ptn_order = value;
-        return 0;
-    }
-    if (!strcmp(name, "record_steps")) {         // 1: record the RotateRows steps and column rotations asked for from now on (cn_rotation_steps); 0: stop and clear
-        ctx->rec_steps = value != 0;
-        if (!value) { ctx->rec_set.clear(); ctx->rec_cols = false; }
-        return 0;
-    }
+    for (const ValueSpec &v : kValues) if (v.set && !strcmp(name, v.name)) return v.set(ctx, value);
     return fail(CN_ERR_ARG, "unknown option %s", name);
 API_END }
-// read-back of the switches and of choices the library made (tests, diagnostics)
 extern "C" int cn_get_option(cn_ctx *ctx, const char *name, int *value) { API_BODY
     LOCK_ONLY;
     if (!name || !value) return fail(CN_ERR_ARG, "null argument");
-    if (const OptionSpec *o = find_option(name)) *value = ctx->opt.*o->member;
-    else if (!strcmp(name, "defer")) *value = ctx->defer.load(std::memory_order_relaxed);
-    else if (!strcmp(name, "ks_xi")) *value = (int)ctx->hc.ks_xi;
-    else if (!strcmp(name, "record_steps")) *value = ctx->rec_steps;
-    else if (!strcmp(name, "digit_mfma")) *value = ctx->digit_mfma;
-    else if (!strcmp(name, "digit_i32")) *value = ctx->digit_i32;
-    else if (!strcmp(name, "defer_square_gemm")) *value = ctx->defer_square_gemm;
-    else if (!strcmp(name, "mul_sum")) *value = ctx->mul_sum;
-    else if (!strcmp(name, "sg_prefloor")) *value = ctx->sg_prefloor_mode;
-    // read-only diagnostics: choices the library made and counters (tests)
-    else if (!strcmp(name, "pin_laps")) *value = (int)ctx->pin_laps;                      // laps of the pinned upload ring (each one waits for the stream)
-    else if (!strcmp(name, "ready_handles")) *value = (int)ctx->ready->size();          // allocated single-ciphertext arrays waiting for a lock-free cn_ct_alloc
-    else if (!strcmp(name, "folded_zero_encryptions")) *value = (int)std::min<uint64_t>(ctx->folded_zero, 0x7fffffff);    // zero encryptions folded so far
-    else if (!strcmp(name, "square_gemm_fused")) *value = (int)std::min<uint64_t>(ctx->sg_fused, 0x7fffffff);
-    else if (!strcmp(name, "square_gemm_prefloor")) *value = (int)std::min<uint64_t>(ctx->sg_prefloor, 0x7fffffff);       // ... of which with one floor tail per dense output
-    else if (!strcmp(name, "sg_prefloor_min_k")) *value = (int)SG_PREFLOOR_MIN_K;                                           // smallest K that takes that form under "sg_prefloor" = 1
-    else if (!strcmp(name, "defer_square_gemm_fused")) *value = (int)std::min<uint64_t>(ctx->dsg_fused, 0x7fffffff);       // groups of queued scalar products run on deferred squarings
-    else if (!strcmp(name, "mul_sum_fused")) *value = (int)std::min<uint64_t>(ctx->ms_fused, 0x7fffffff);                 // cn_mul_relin_sum calls that ran one key switch per output
-    else if (!strcmp(name, "mul_sum_groups")) *value = (int)ctx->ms_groups;                                                // output groups of the last cn_mul_relin_sum (0: the literal sequence)
-    else if (!strcmp(name, "mul_sum_min_k")) *value = (int)MUL_SUM_MIN_K;                                                   // smallest K that takes that form
-    else if (!strcmp(name, "defer_pending_products")) *value = (int)ctx->dq->sq->out.size();                             // squarings whose relinearisation is held back right now
-    else if (!strcmp(name, "digit_gemm_mfma")) *value = (int)std::min<uint64_t>(ctx->dg_mfma, 0x7fffffff);                 // digit GEMMs launched in the matrix-core form
-    else if (!strcmp(name, "ks_digits_i32")) *value = (int)std::min<uint64_t>(ctx->ks_dig_i32, 0x7fffffff);                // key switches launched on int32 digit sums
-    else if (!strcmp(name, "ptn_order")) *value = ctx->ptn_order;
-    else if (!strcmp(name, "ptn_sum")) *value = (int)std::min<uint64_t>(ctx->ptn_sum, 0x7fffffff);                        // launches of k_mul_ptn_sum (cn_mul_plain_sum on NTT-form plaintexts)
-    else if (!strcmp(name, "ptn_bcast")) *value = (int)std::min<uint64_t>(ctx->ptn_bcast, 0x7fffffff);                    // launches of k_mul_plain_bcast on NTT-form plaintexts
-    else if (!strcmp(name, "scratch_mib")) *value = (int)std::min<size_t>((ctx->scap + (1u << 20) - 1) >> 20, 0x7fffffff);       // size of the scratch arena right now (it only grows)
-    else if (!strcmp(name, "diag_scan")) *value = (int)std::min<uint64_t>(ctx->diag_scan, 0x7fffffff);                    // launches of k_diag_scan (cn_diag_scan)
-    else if (!strcmp(name, "diag_encode")) *value = (int)std::min<uint64_t>(ctx->diag_encode, 0x7fffffff);                // launches of k_diag_gather (cn_diag_encode)
-    else if (!strcmp(name, "ptn_sum_interval")) *value = (int)cn_ptn_sum_interval(cn_mod_range(ctx->hc, 0, ctx->hc.k).qmax);   // terms between two recentrings of its FP64 accumulators
-    else if (!strcmp(name, "packed_bad_residues")) *value = (int)std::min<uint64_t>(ctx->packed_bad.load(), 0x7fffffff);      // packed uploads that held a residue >= its modulus
-    else if (!strcmp(name, "mul_relin_pipelined")) *value = (int)std::min<uint64_t>(ctx->mr_pipelined, 0x7fffffff);      // Multiply + Relinearize batches run in parts over two streams
-    else if (!strcmp(name, "behz_small_base")) *value = ctx->hc.bsk[ctx->hc.kb - 1].q < (1ull << 49);     // auxiliary primes below 2^49 (FP64 kernels) instead of SEAL's 61-bit ones
-    else if (!strcmp(name, "behz_f64")) *value = ctx->hc.behz_f64 && ctx->opt.f64;
-    else if (!strcmp(name, "mod_switch_f64")) *value = ctx->ms_f64;                     // the last cn_mod_switch on this context ran in FP64
-    else if (!strcmp(name, "aux_primes")) *value = (int)ctx->hc.kb;
-    else if (!strcmp(name, "pending_calls")) *value = (int)ctx->dq->ops.size();
-    else if (!strcmp(name, "pool_arrays")) { size_t c = 0; for (auto &kv : ctx->pool) c += kv.second.size(); *value = (int)std::min<size_t>(c, 0x7fffffff); }   // cached arrays (a graph reserves its temporaries out of the pool)
-    else if (!strcmp(name, "stream_tries")) *value = ctx->stream_tries;           // streams created until one had a hardware queue of its own (< 0: none had)
-    else return fail(CN_ERR_ARG, "unknown option %s", name);
-    return 0;
+    if (cn_option_get(ctx->opt, ctx->cnt, name, value)) return 0;
+    for (const ValueSpec &v : kValues) if (!strcmp(name, v.name)) { *value = v.get(ctx); return 0; }
+    return fail(CN_ERR_ARG, "unknown option %s", name);
 API_END }
 extern "C" int cn_sync(cn_ctx *ctx) { API_BODY LOCK; NOT_CAPTURING("cn_sync"); HIPCHK(hipStreamSynchronize(ctx->stream)); ctx->staged.clear(); return 0; API_END }
 extern "C" void *cn_stream(cn_ctx *ctx) { return (void *)ctx->stream; }

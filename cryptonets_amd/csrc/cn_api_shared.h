@@ -153,7 +153,7 @@ template <class FM, class FK> static int pipelined_halves(cn_ctx *ctx, uint32_t 
     uint32_t first[4];
     const uint32_t P = pipeline_cuts(c, first);
     if (P < 2) { CHECK(mul(0u, c)); return ks(0u, c); }
-    ctx->mr_pipelined++;
+    ctx->cnt.mr_pipelined++;
     int rc = 0;
     for (uint32_t i = 0; i < P && !rc; i++) {
         const bool aux = (i & 1) != 0;

@@ -245,7 +245,7 @@ static int sg_run(cn_ctx *ctx, DeferQueue *q, const DeferSgGroup &g, const SgPla
     CHECK(run_gemm_launch(ctx, P, gemm_launch(ctx, P, P.dev).gather(dpidx).inputs(arr, (uint32_t)(3 * kn), 2).bias_at(bias ? (const uint64_t *)bbase : nullptr, dbidx, 32).outputs(T, 0, 0)));
     CHECK(cn_l_digit_gemm(ctx, DigitGemmLaunch::of(P, P.dev, arr + 2 * kn, 3 * kn, dpidx, S)));
     CHECK(do_keyswitch(ctx, ctx->rlk, KsCall::relin_digits(S, P.dig_i32, T, kn, P.O).to_table(douts)));
-    ctx->dsg_fused++;
+    ctx->cnt.dsg_fused++;
     if (defer_trace()) fprintf(stderr, "defer %p level %d: fuses %u scalar products over %zu pending products (GEMM, digit GEMM%s, %u key switches)\n", (void *)ctx, g.level, P.O,
                                g.slot_of.size(), P.dig_mfma ? " on the matrix cores" : "", P.O);
     return 0;
@@ -476,7 +476,7 @@ int cn_defer_flush(cn_ctx *ctx, bool boundary) {
         const DeferReleased released(q->frees);
         std::vector<uint8_t> dead(q->ops.size(), 0);
         defer_fold_bias(*q, dead, released);
-        ctx->folded_zero += defer_fold_zero(*q, dead, released, sw);
+        ctx->cnt.folded_zero += defer_fold_zero(*q, dead, released, sw);
         defer_merge_gemm(*q, dead, sw);
         // products whose relinearisation an earlier layer-boundary flush held back: the scalar products that read them run in cn_square_gemm's second half (at their
         // level, below), or every product is relinearised into its own array first and the flush proceeds as ever

@@ -64,7 +64,7 @@ int add_plain_body(cn_ctx *ctx, cn_handle a, uint32_t ai, cn_handle pt, uint32_t
     return 0;
 }
 // the switches of this context that the plaintext planner reads (cn_plain_plan.h): the only place that copies them out of a context for the plaintext family
-PlainSwitches plain_switches(const cn_ctx *ctx) { return {ctx->opt.f64, ctx->opt.mp_fused, ctx->opt.mp_bcast, ctx->opt.ks_chain, ctx->ptn_order, rr_kernels(ctx), ks_switches(ctx)}; }
+PlainSwitches plain_switches(const cn_ctx *ctx) { return {ctx->opt.f64, ctx->opt.mp_fused, ctx->opt.mp_bcast, ctx->opt.ks_chain, ctx->opt.ptn_order, rr_kernels(ctx), ks_switches(ctx)}; }
 // neither the same range nor disjoint: `words` words at a and at o overlap with a shift (a null operand overlaps nothing)
 bool shifted_overlap(const uint64_t *a, const uint64_t *o, size_t words) { return a && a != o && a < o + words && o < a + words; }
 static int mul_plain_overlap(const CtSpan &A, const CtSpan &O, size_t item_words) {      // block c writes out[c] while another block still reads in[c']
@@ -131,7 +131,7 @@ int mul_plain_impl(cn_ctx *ctx, CtSpan A, bool a_bcast, PtSpan P, CtSpan O, uint
     }
     }
     HIPCHK(hipGetLastError()); launch_count(ctx, p.launches);
-    ctx->ptn_bcast += p.ptn_bcast; ctx->st.ntt_forward_limbs += p.fwd_limbs; ctx->st.ntt_inverse_limbs += p.inv_limbs;
+    ctx->cnt.ptn_bcast += p.ptn_bcast; ctx->st.ntt_forward_limbs += p.fwd_limbs; ctx->st.ntt_inverse_limbs += p.inv_limbs;
     ctx->st.PlainMultiplication += count;
     return 0;
 }
@@ -195,7 +195,7 @@ API_END }
 // ---------------------------------------------------------------- scalar GEMM (planned in cn_gemm_plan.h)
 static_assert(GEMM_ERR_ARG == CN_ERR_ARG, "the planner's refusals are argument errors");
 // the switches of this context that the planner reads; a change of one drops the cached plans (defer_square_drop_plans)
-GemmSwitches gemm_switches(const cn_ctx *ctx) { return {ctx->opt.f64 != 0, ctx->opt.gemm_mfma != 0, ctx->opt.gemm_pair != 0, ctx->digit_mfma != 0, ctx->digit_i32 != 0}; }
+GemmSwitches gemm_switches(const cn_ctx *ctx) { return {ctx->opt.f64 != 0, ctx->opt.gemm_mfma != 0, ctx->opt.gemm_pair != 0, ctx->opt.digit_mfma != 0, ctx->opt.digit_i32 != 0}; }
 int free_gemm_plan(cn_ctx *ctx, Buffer &b) {
     if (b.plan && b.plan->dev) { HIPCHK(hipStreamSynchronize(ctx->stream)); HIPCHK(hipFree(b.plan->dev)); b.plan->dev = nullptr; }
     return 0;
@@ -268,8 +268,8 @@ API_END }
 // ---------------------------------------------------------------- BEHZ multiply / key switching
 // the switches of this context that the multiply planner reads (cn_mul_plan.h): the only place that copies them out of a context for the multiply family
 MulSwitches mul_switches(const cn_ctx *ctx) {
-    return {ctx->opt.f64, ctx->opt.sq_fused, ctx->opt.sq_pipe, ctx->opt.sq_lds, ctx->opt.sq_halves, ctx->mul_sum, ctx->digit_i32, ctx->defer_square_gemm, rr_kernels(ctx), rr_kernels(ctx, 13),
-            ctx->cus, ctx->capturing.load(), ctx->smax, ctx->rlk.d != nullptr, ctx->rlk.f64, ks_switches(ctx), ctx->sg_prefloor_mode};
+    return {ctx->opt.f64, ctx->opt.sq_fused, ctx->opt.sq_pipe, ctx->opt.sq_lds, ctx->opt.sq_halves, ctx->opt.mul_sum != 0, ctx->opt.digit_i32 != 0, ctx->opt.defer_square_gemm != 0, rr_kernels(ctx), rr_kernels(ctx, 13),
+            ctx->cus, ctx->capturing.load(), ctx->smax, ctx->rlk.d != nullptr, ctx->rlk.f64, ks_switches(ctx), ctx->opt.sg_prefloor};
 }
 // the context's second stream (squaring overlap): created on first use, kept only if it runs beside the context's own stream (a hardware queue of its own)
 bool aux_stream_ready(cn_ctx *ctx) {
@@ -401,7 +401,7 @@ int do_keyswitch(cn_ctx *ctx, const KsKey &key, const KsCall &call) {
             }
     }
     HIPCHK(hipGetLastError()); launch_count(ctx);
-    if (a.dig && a.dig_i32) ctx->ks_dig_i32++;
+    if (a.dig && a.dig_i32) ctx->cnt.ks_dig_i32++;
     ctx->st.ntt_forward_limbs += (uint64_t)cnt * tot_dig * k; ctx->st.ntt_inverse_limbs += (uint64_t)cnt * 2 * k;
     return 0;
 }
@@ -558,13 +558,13 @@ extern "C" int cn_square_gemm(cn_ctx *ctx, cn_handle plan, cn_handle in, uint32_
         CHECK(cn_l_behz_floor_out(ctx, {sg[SG_X], sg[SG_Y], (const int32_t *)(P.dev + P.off_oidx), bias, (const int32_t *)(P.dev + P.off_bidx), OB->d, oi, P.G * P.M}));
         ctx->st.PlainMultiplication += P.nnz; ctx->st.Addition += P.nnz - P.O;
         if (P.has_bias) ctx->st.PlainAddition += P.O;
-        ctx->sg_prefloor++;
+        ctx->cnt.sg_prefloor++;
     } else
     CHECK(run_gemm_plan(ctx, P, P.dev, nullptr, OB, oi, t3));                     // components 0 and 1 (+ bias) straight into the outputs
     CHECK(cn_l_digit_gemm(ctx, DigitGemmLaunch::of(P, P.dev, t3 + 2 * kn, 3 * kn, P.dev, S)));
     uint64_t *o = OB->d + oi * OB->item_words;
     CHECK(do_keyswitch(ctx, ctx->rlk, KsCall::relin_digits(S, P.dig_i32, o, kn, P.O).to(o)));
-    ctx->st.Relinarization += cnt; ctx->sg_fused++;
+    ctx->st.Relinarization += cnt; ctx->cnt.sg_fused++;
     return 0;
 API_END }
 
@@ -656,7 +656,7 @@ extern "C" int cn_mul_relin_sum(cn_ctx *ctx, const cn_handle *a, const uint32_t 
         ctx->ms_groups++;
     }
     ctx->st.Relinarization += (uint64_t)K * count; ctx->st.AddMany += count; ctx->st.AddManyItemCount += (uint64_t)count * K;
-    ctx->ms_fused++;
+    ctx->cnt.ms_fused++;
     return 0;
 API_END }
 

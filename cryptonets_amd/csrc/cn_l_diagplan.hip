@@ -9,7 +9,7 @@ int cn_l_diag_scan(cn_ctx *c, const uint64_t *S, uint32_t R, uint32_t dim, uint8
     if (!R) return 0;
     hipLaunchKernelGGL(k_diag_scan, dim3((R + DSC_ROWS - 1) / DSC_ROWS), dim3(DSC_THREADS), (size_t)((c->hc.n + 3) & ~3u), c->stream, S, R, dim, c->hc.logn, flags);
     HIPCHK(hipGetLastError()); cn_launch_count(c);
-    c->diag_scan++;
+    c->cnt.diag_scan++;
     return 0;
 }
 // the terms of `nruns` runs (device table; DiagRun::first counts from out / nz) into out [term][N], slot order -> SEAL's coefficient positions (index_map)
@@ -19,6 +19,6 @@ int cn_l_diag_gather(cn_ctx *c, const uint64_t *S, uint32_t R, uint32_t dim, con
     if (nruns > CN_DIAG_MAX_RUNS) return cn_fail(CN_ERR_ARG, "internal: %u runs in one launch of k_diag_gather", nruns);
     hipLaunchKernelGGL(k_diag_gather, dim3((m + DGA_T - 1) / DGA_T, 2, nruns), dim3(DGA_THREADS), 0, c->stream, S, R, dim, c->hc.logn, (const DiagRun *)runs, index_map, out, nz);
     HIPCHK(hipGetLastError()); cn_launch_count(c);
-    c->diag_encode++;
+    c->cnt.diag_encode++;
     return 0;
 }

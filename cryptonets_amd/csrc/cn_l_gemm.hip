@@ -108,7 +108,7 @@ static int digit_gemm_mfma(cn_ctx *c, const DigitGemmLaunch &g, uint32_t ndmax) 
     }
     HIPCHK(hipGetLastError());
     cn_launch_count(c);
-    c->dg_mfma++;
+    c->cnt.dg_mfma++;
     return 0;
 }
 int cn_l_digit_gemm(cn_ctx *c, const DigitGemmLaunch &g) {

@@ -55,6 +55,6 @@ int cn_l_mul_ptn_sum(cn_ctx *c, int policy, const MulPlainSumLaunch &a) {
     const bool ok = policy == POL_U64 ? by_size<ArU64>(c, a) : (policy == POL_F64 ? by_size<ArF64>(c, a) : by_size<ArF64L>(c, a));
     if (!ok) return cn_fail(CN_ERR_ARG, "internal: cn_mul_plain_sum (NTT-form plaintexts) without a kernel for N = 2^%u", c->hc.logn);
     HIPCHK(hipGetLastError()); cn_launch_count(c);
-    c->ptn_sum++;
+    c->cnt.ptn_sum++;
     return 0;
 }

@@ -28,7 +28,7 @@ static int slice_ks_key(cn_ctx *child, const cn_ctx *parent, const KsKey &from, 
 }
 static int adopt_from_parent(cn_ctx *c, cn_ctx *parent) {
     const uint32_t k = c->hc.k;
-    c->opt = parent->opt; c->defer_square_gemm = parent->defer_square_gemm; c->mul_sum = parent->mul_sum; c->sg_prefloor_mode = parent->sg_prefloor_mode; c->digit_i32 = parent->digit_i32; c->ptn_order = parent->ptn_order;
+    c->opt = parent->opt;
     memcpy(c->rng_key, parent->rng_key, sizeof c->rng_key);
     c->hc.ks_xi = parent->hc.ks_xi;
     for (uint32_t l = 0; l < k; l++) c->hc.ks_inv_qhat_q[l] = parent->hc.ks_inv_qhat_q[l];

@@ -4,6 +4,7 @@
 #pragma once
 #include "../../include/cnhip.h"
 #include "cn_policy.h"
+#include "cn_options.h"
 #include "cn_ks_plan.h"
 #include "cn_mul_plan.h"
 #include "cn_submit.h"
@@ -129,41 +130,11 @@ struct CnGuard {
     CnGuard &operator=(const CnGuard &) = delete;
 };
 
-// Per-context tuning switches, all producing the same words.  Names, ranges and environment overrides: the option table of cn_api.hip
-// (cn_set_option / cn_get_option, include/cnhip.h); a level context copies them from its parent whole.  Booleans are 0 / 1.
-// Switches removed after their variants measured no gain: staggered squaring groups in the flush (profiles/r06_stagger_ab.txt), the q side of a batched squaring on the
-// second stream (profiles/r06_square_overlap.txt), the 128-VGPR fused key switch (profiles/HISTORY.md, round 1).
-struct CnTunables {
-    int f64 = 1;              // transforms of moduli < 2^49 and key switching in exact FP64; 0 (CN_NO_F64=1): integer (Shoup) transforms everywhere
-    int legacy_ntt = 0;       // 1: radix-2 LDS kernels (the only ones below N = 1024)
-    int gemm_order = 1;       // scalar GEMM (VALU kernels): 1 = slice-major workgroup order (every input slice fetched once per XCD), 0 = group-major
-    int ks_perm_fused = 1;    // rotations through the two-launch key switch apply the automorphism while loading (no k_galois_lds pass)
-    int ks_xcd = 0;           // fused key switch, workgroup order: 0 (ciphertext, limb); 1 the k workgroups of a ciphertext on one XCD (share its source limbs in
-                              // that L2); 2 limb-major (one key slice per XCD L2 at a time).  Default by N (ctx_init)
-    int sq_fused = 1;         // squarings: forward transforms + tensor + inverse transforms in one kernel; 0 = separate launches
-    int sq_lds = 1;           // fused squaring with the NTT-form operand parked in LDS (N <= 8192) - HBM traffic = the algorithmic 2 reads + 3 writes per
-                              // block (profiles/r02_pmc_square_gemm.txt); 0: parked in the outputs' place (two workgroups per CU)
-    int sq_pipe = 1;          // 1: fused squaring of a batch (>= 4 blocks per resident workgroup) on the pipelined resident kernel k_square_pipe; 0: k_square_fused; 2: k_square_pipe for any count (tests)
-    int sq_halves = 1;        // Multiply + Relinearize of >= 512 ciphertexts (N <= 8192) in parts software-pipelined over the context's two streams (pipelined_halves,
-                              // cn_api_shared.h).  1: the batched entry point cn_mul_relin; 2: also the queued per-ciphertext calls of a flush (measured slower there); 0: off
-    int enc_fused = 2;        // 2: a block per (ciphertext, component, limb) - k_encrypt_split, two workgroups per CU: 420 against 542 us per 784 ciphertexts; 1: one block per
-                              // (ciphertext, limb) behind the samplers (k_encrypt_fused, N <= 8192); 0: expand + batched transform + k_encrypt_tail
-    int fold_zero = 1;        // queued fresh encryptions of zero whose only reader is a queued scalar product and which have been released: folded by linearity (k_encrypt_fold); 0: materialised
-    int gemm_mfma = 1;        // scalar GEMMs with >= 16 outputs per gather list on the int8 matrix cores (exact); 0: FP64 kernel
-    int gemm_pair = 1;        // planned scalar GEMMs: gather lists that share at least half of their inputs are merged in pairs (pair_gather_lists); 0: the caller's lists
-    int mp_fused = 1;         // dense MultiplyPlain as k_lift_ntt + k_mul_plain_fused; 0 = the six separate launches
-    int ks_wide = -1;         // -1 auto (small batches), 0 fused kernel, 1 two-launch with a workgroup per digit, 2 two-launch per source limb
-    int ks_split14 = 1;       // N = 16384: key switch as two 8192-point halves per limb (no register spills); 0 = fused 1024-thread kernel
-    int ks_pair14 = 1;        // ... both halves in ONE launch per rotation (k_keyswitch_pair14); 0 = k_keyswitch_split14 + k_ks_combine14 (+ k_galois_lds)
-    int ks_chain = 1;         // SumAllSlots at N = 16384: every link of the rotate-and-add chain hands sigma_next(c1) to the next one (no permutation pass between links)
-    int mp_bcast = 1;         // one ciphertext x many plaintexts (row-dot batches) as ONE launch that transforms the plaintexts (k_mul_plain_bcast); 0: k_lift_ntt + k_mul_plain_fused
-};
-
 struct DeferQueue;            // cn_api_shared.h / cn_defer.hip
 struct cn_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
-    CnTunables opt;
+    CnTunables opt;           // every switch of cn_set_option's table (cn_options.h)
     DevConsts hc;             // host copy
     DevConsts *dc = nullptr;  // device copy
     uint64_t *tw = nullptr;
@@ -209,31 +180,9 @@ struct cn_ctx {
     int member_graphs = 0;
     hipEvent_t ev_graph = nullptr;
     int cus = 0;              // compute units of the device
-    uint64_t folded_zero = 0;  // zero encryptions folded so far
-    uint64_t mr_pipelined = 0; // cn_mul_relin chunks and flushed Multiply + Relinearize groups that ran through pipelined_halves
-    uint64_t sg_fused = 0;     // cn_square_gemm calls that ran the one-key-switch-per-output form
-    uint64_t sg_prefloor = 0;  // ... of which in the pre-floor form: one floor tail per dense output for components 0 and 1 ("square_gemm_prefloor")
-    uint64_t dsg_fused = 0;    // groups of queued scalar products that ran on deferred squarings in the one-key-switch-per-output form ("defer_square_gemm_fused")
-    uint64_t dg_mfma = 0;      // digit GEMMs launched in the matrix-core form
+    CnCounters cnt;           // what cn_get_option reads back by the names of kCounters (cn_options.h)
     std::atomic<uint64_t> packed_bad{0};       // packed uploads whose rows held a residue >= its modulus (counted where the flag is read)
-    uint64_t ms_fused = 0;     // cn_mul_relin_sum calls that ran one key switch per output ("mul_sum_fused")
     uint32_t ms_groups = 0;    // output groups of the last cn_mul_relin_sum call ("mul_sum_groups"; 0: it took the literal sequence)
-    bool mul_sum = true;       // cn_set_option "mul_sum": cn_mul_relin_sum sums the unrelinearized products and runs one key switch per output where it can (k_product_sum, the
-                               // same words); false: always Multiply + Relinearize per term and AddMany.  A switch between two live forms of one call, set by name like "digit_mfma"
-    bool digit_mfma = true;    // cn_set_option "digit_mfma": plans made from now on run their digit GEMM on the int8 matrix cores where they can (k_digit_gemm_mfma, exact); false: always
-                               // the FP64 kernel k_digit_gemm.  A switch between two live forms of one step of cn_square_gemm, set by name like "ks_xi" (no environment override)
-    bool digit_i32 = true;     // cn_set_option "digit_i32": plans made from now on (and cn_mul_relin_sum calls) hand their digit sums S to the key switch as int32 words where the bound
-                               // allows it (cn_digit_sum_fits_i32, cn_policy.h: half the bytes of S); false: always doubles.  Set by name like "digit_mfma" (no environment override)
-    uint64_t ks_dig_i32 = 0;   // key switches launched on int32 digit sums ("ks_digits_i32")
-    int ptn_order = 0;         // k_mul_ptn_sum, workgroup order ("ptn_order", CN_PTN_ORDER): 0 limb-major, 1 limb = workgroup index mod k (a limb per XCD at k = 8)
-    uint64_t ptn_sum = 0, ptn_bcast = 0;   // launches of k_mul_ptn_sum / of k_mul_plain_bcast on NTT-form plaintexts ("ptn_sum", "ptn_bcast")
-    uint64_t diag_scan = 0, diag_encode = 0;   // launches of k_diag_scan / of k_diag_gather ("diag_scan", "diag_encode")
-    int sg_prefloor_mode = 1;  // cn_set_option "sg_prefloor": cn_square_gemm - 1 = components 0 and 1 take ONE floor tail per dense output where square_gemm_prefloor_ok allows (cn_mul_plan.h:
-                               // layers of at least SG_PREFLOOR_MIN_K terms); 0 = every product is floored (the old form); 2 = the new form for any K (tests).  The same words.  Set by
-                               // name like "digit_mfma" (no environment override)
-    bool defer_square_gemm = false;  // cn_set_option "defer_square_gemm" (default 0: its effect on the literal call sequence has not been measured, profiles/deferred_square_gemm.md): queued squarings launched by a layer-boundary flush keep their relinearisation back; scalar products that read
-                               // nothing else run as cn_square_gemm's second half - one key switch per dense OUTPUT (cn_defer.hip); false: every queued squaring relinearises at once.
-                               // Set by name like "digit_mfma" (no environment override)
     uint64_t uid = 0;         // creation order within the process (cn_ctx_create)
     hipStream_t stream2 = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr; bool stream2_failed = false;   // second stream of pipelined_halves (aux_stream_ready)
     // deferred submission (cn_set_option("defer", 1)): per-ciphertext calls are queued and flushed as batched launches; 2: ... and submitted without the

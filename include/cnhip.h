@@ -142,13 +142,13 @@ int cn_mod_switch(cn_ctx *src, cn_handle in, uint32_t ii, uint32_t count, cn_ctx
  *   "sg_prefloor"    0..2    1                     -                cn_square_gemm: components 0 and 1 of the products take ONE fast floor per dense output
  *                                                                   (sums of their Bsk words in NTT form and of their canonical y on the matrix cores)
  *                                                                   where the plan and the layer size allow; 0 = one floor per product; 2 = for any
- *                                                                   layer size (tests).  The same words.  A context switch like "digit_mfma"
+ *                                                                   layer size (tests).  The same words
  *   "ptn_order"      0..1    0                     CN_PTN_ORDER     cn_mul_plain_sum on NTT-form plaintexts, workgroup order: 0 limb-major, 1 limb = workgroup
  *                                                                   index mod k (one limb per XCD where k = 8)
  *   "defer"          0..2    0                     -                deferred submission of per-ciphertext calls (below)
  *   "defer_square_gemm" flag 0                     -                queued squarings keep their relinearisation back for the dense layer that
  *                                                                   reads them: one key switch per dense output (below); 0 = every squaring relinearises
- *                                                                   at once.  A context flag like "digit_mfma"
+ *                                                                   at once
  *   "ks_xi"          flag    0                     -                decomposition convention of the key switch (below)
  *   "record_steps"   flag    0                     -                note the rotation steps the caller asks for (cn_rotation_steps); 0 stops and clears
  *

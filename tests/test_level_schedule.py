@@ -46,9 +46,9 @@ def test_fp64_mod_switch_kernel_uses_global_not_flat_memory_instructions():
 
 def test_fp64_mod_switch_diagnostic_is_documented_and_read_only():
     src = open(os.path.join(ROOT, "cryptonets_amd", "csrc", "cn_api.hip")).read()
-    get = src[src.index('extern "C" int cn_get_option('):]
-    assert 'strcmp(name, "mod_switch_f64")' in get[:get.index("API_END }")]
-    assert '{"mod_switch_f64"' not in src                   # not a tunable of the option table
+    rows = [line for line in src.split("\n") if '{"mod_switch_f64",' in line]
+    assert len(rows) == 1 and "nullptr}," in rows[0]        # a row of cn_get_option's table of values, without a setter
+    assert '"mod_switch_f64"' not in open(os.path.join(ROOT, "cryptonets_amd", "csrc", "cn_options.h")).read()      # not a tunable of the option table
     assert '"mod_switch_f64"' in open(os.path.join(ROOT, "include", "cnhip.h")).read()
 
 
