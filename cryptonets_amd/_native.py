@@ -26,6 +26,11 @@ I32P = C.POINTER(C.c_int32)
 U32P = C.POINTER(C.c_uint32)
 
 
+CN_ERR_ARG, CN_ERR_NOKEY = -1, -3                            # include/cnhip.h
+# the two refusals of the hoisted-rotation planner (cn_ks_hoist_plan, cn_ks_plan.h) that mean "this context has no kernel for the call", as they begin
+HOISTED_UNAVAILABLE = ("hoisted rotations need the register-radix kernels", "hoisted rotations: no kernel under the integer policy")
+
+
 class CnError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("libcnhip error %d: %s" % (code, msg))
@@ -175,6 +180,8 @@ SIGNATURES = {
     "cn_apply_galois": (C.c_int, [_CTX, _H, _u32, C.c_uint64, _H, _u32, _u32]),
     "cn_rotate_rows": (C.c_int, [_CTX, _H, _u32, C.c_int, _H, _u32, _u32]),
     "cn_rotate_rows_many": (C.c_int, [_CTX, _H, C.POINTER(C.c_uint32), C.POINTER(C.c_int), _u32, _H, C.POINTER(C.c_uint32)]),
+    "cn_apply_galois_hoisted": (C.c_int, [_CTX, _H, _u32, U64P, _u32, _H, C.POINTER(C.c_uint32)]),
+    "cn_rotate_rows_hoisted": (C.c_int, [_CTX, _H, _u32, C.POINTER(C.c_int), _u32, _H, C.POINTER(C.c_uint32)]),
     "cn_rotate_columns": (C.c_int, [_CTX, _H, _u32, _H, _u32, _u32]),
     "cn_rotate_rows_add": (C.c_int, [_CTX, _H, _u32, C.c_int, _H, _u32, _H, _u32, _u32]),
     "cn_rotate_columns_add": (C.c_int, [_CTX, _H, _u32, _H, _u32, _H, _u32, _u32]),
@@ -389,6 +396,7 @@ class Context:
         self._ct_size = {}
         self._h = h
         self._parent, self._levels = parent, {}
+        self._hoisted_wanted = set()     # note_hoisted_steps: steps a hoisted call asked for while "record_steps" was on and a key was missing
 
     # ---- modulus switching (SEAL 3.2 ModSwitchToNext / ModSwitchTo; include/cnhip.h: cn_ctx_create_level, cn_mod_switch)
     @property
@@ -429,6 +437,14 @@ class Context:
 
     def set_option(self, name, value):
         self._chk(self.L.cn_set_option(self._h, name.encode(), int(value)))
+        if name == "record_steps" and not int(value):        # switching the recording off clears it: the library's list and the steps noted here
+            self._hoisted_wanted.clear()
+
+    def note_hoisted_steps(self, steps):
+        """a hoisted call (rotate_rows_hoisted) was refused for a missing key: while "record_steps" is on, its non-zero steps count as asked for - rotation_steps
+        returns them beside the library's list, so that keys for exactly the direct steps can be generated.  Nothing is noted while recording is off."""
+        if self.get_option("record_steps"):
+            self._hoisted_wanted.update(int(s) for s in steps if int(s))
 
     def get_option(self, name):
         v = C.c_int()
@@ -733,6 +749,21 @@ class Context:
         self._chk(self.L.cn_rotate_rows_many(self._h, src, a.ctypes.data_as(C.POINTER(C.c_uint32)), st.ctypes.data_as(C.POINTER(C.c_int)), len(a), out,
                                              o.ctypes.data_as(C.POINTER(C.c_uint32))))
 
+    def rotate_rows_hoisted(self, src, ii, steps, out, ois):
+        """out[ois[r]] = the hoisted rotation of src[ii] by steps[r] (0: a copy): n rotations of ONE ciphertext on one set of digit transforms, every step
+        with its own Galois key (CN_ERR_NOKEY otherwise).  The words are those of tests/hoisted_model.py, not cn_rotate_rows'; the plaintext is the same"""
+        st = np.ascontiguousarray(steps, dtype=np.int32)
+        o = np.ascontiguousarray(ois, dtype=np.uint32)
+        assert len(st) == len(o)
+        self._chk(self.L.cn_rotate_rows_hoisted(self._h, src, ii, st.ctypes.data_as(C.POINTER(C.c_int)), len(st), out, o.ctypes.data_as(C.POINTER(C.c_uint32))))
+
+    def apply_galois_hoisted(self, src, ii, elts, out, ois):
+        """the same by Galois elements (1: a copy)"""
+        e = np.ascontiguousarray(elts, dtype=np.uint64)
+        o = np.ascontiguousarray(ois, dtype=np.uint32)
+        assert len(e) == len(o)
+        self._chk(self.L.cn_apply_galois_hoisted(self._h, src, ii, e.ctypes.data_as(U64P), len(e), out, o.ctypes.data_as(C.POINTER(C.c_uint32))))
+
     def rotate_rows_add(self, src, ii, steps, acc, ai, out, oi, count=1):
         """out = acc + RotateRows(src, steps) (fused rotate-and-add of SumAllSlots)"""
         self._chk(self.L.cn_rotate_rows_add(self._h, src, ii, steps, acc, ai, out, oi, count))
@@ -794,12 +825,13 @@ class Context:
         return [int(x) for x in out[:cnt.value]]
 
     def rotation_steps(self):
-        """(sorted distinct RotateRows steps, was a column rotation asked for) recorded since set_option("record_steps", 1) (cn_rotation_steps)"""
+        """(sorted distinct RotateRows steps, was a column rotation asked for) recorded since set_option("record_steps", 1) (cn_rotation_steps), with the steps of
+        note_hoisted_steps among them"""
         cnt, cols = C.c_uint32(), C.c_int()
         self._chk(self.L.cn_rotation_steps(self._h, None, 0, C.byref(cnt), C.byref(cols)))
         out = (C.c_int * max(1, cnt.value))()
         self._chk(self.L.cn_rotation_steps(self._h, out, len(out), C.byref(cnt), C.byref(cols)))
-        return [int(out[i]) for i in range(cnt.value)], bool(cols.value)
+        return sorted({int(out[i]) for i in range(cnt.value)} | self._hoisted_wanted), bool(cols.value)
 
     def set_public_key(self, words):
         w = np.ascontiguousarray(words, dtype=np.uint64)

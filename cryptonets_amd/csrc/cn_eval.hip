@@ -836,6 +836,64 @@ extern "C" int cn_rotate_rows_many(cn_ctx *ctx, cn_handle in, const uint32_t *ii
     CHECK(cn_defer_flush(ctx));
     return rotate_jobs(ctx, jobs);
 API_END }
+// n rotations of ONE ciphertext that share its digit transforms (include/cnhip.h; the plan: cn_ks_hoist_plan, the kernels: k_ks_digit_ntt + k_ks_hoist_mac).  steps != null:
+// RotateRows step counts (0: a copy), else Galois elements (1: a copy).  Every check comes before the first launch: a refused call leaves `out` as it is
+static int hoisted_rotations(cn_ctx *ctx, cn_handle in, uint32_t ii, const uint64_t *elts, const int *steps, uint32_t n, cn_handle out, const uint32_t *oi) {
+    GETCT(I, in, 0); GETCT(O, out, 0);
+    if (I->size != 2 || O->size != 2) return fail(CN_ERR_ARG, "hoisted rotations: operands must be size-2 ciphertexts");
+    if (!n) return fail(CN_ERR_ARG, "hoisted rotations: an empty list");
+    if (!oi || (!elts && !steps)) return fail(CN_ERR_ARG, "null argument");
+    SPAN(si, I, ii, 1);
+    const uint64_t N = ctx->hc.n;
+    std::vector<uint64_t> e(n);
+    const KsKey *first = nullptr;
+    uint32_t nrot = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        if (!range_ok(O, oi[i], 1)) return fail(CN_ERR_ARG, "index out of range");
+        if (O == I && oi[i] == ii) return fail(CN_ERR_ARG, "hoisted rotations: an output is the input ciphertext");
+        for (uint32_t j = 0; j < i; j++) if (oi[i] == oi[j]) return fail(CN_ERR_ARG, "hoisted rotations: an output index is listed twice");
+        e[i] = steps ? (steps[i] ? cn_elt_of_step(N, steps[i]) : 1) : elts[i];
+        if (steps && !e[i]) return fail(CN_ERR_ARG, "step count too large");
+        if (!(e[i] & 1) || e[i] >= 2 * N) return fail(CN_ERR_ARG, "invalid Galois element");
+    }
+    for (uint32_t i = 0; i < n; i++) {                     // every element needs its OWN key: a chain of non-adjacent-form hops is sequential, nothing to hoist
+        if (e[i] == 1) continue;
+        const KsKey *key = galois_key(ctx, e[i]);
+        if (!key) return fail(CN_ERR_NOKEY, "Galois key not present");
+        if (first && key->f64 != first->f64) return fail(CN_ERR_ARG, "hoisted rotations: the Galois keys were loaded in different forms (\"f64\" changed between the uploads)");
+        if (!first) first = key;
+        nrot++;
+    }
+    KsHoistPlan plan{};
+    if (nrot) {
+        plan = cn_ks_hoist_plan(ctx->hc, ks_switches(ctx), first->f64, nrot);
+        if (plan.rc) return fail(plan.rc, "%s", plan.msg);
+        CHECK(ensure_ks_part(ctx, plan.arena_bytes));
+        CHECK(ensure_scratch(ctx, al(nrot * sizeof(KsHoistItem))));
+    }
+    if (nrot) {                                            // the rotations first: nothing has been written when the launcher still refuses
+        std::vector<KsHoistItem> items;
+        for (uint32_t i = 0; i < n; i++) if (e[i] != 1) items.push_back({galois_key(ctx, e[i])->d, O->d + (size_t)oi[i] * O->item_words, (uint32_t)e[i], 0u});
+        KsHoistItem *d_items; CHECK(upload_tmp(ctx, items.data(), items.size(), &d_items));      // (by value: a recorded call replays this list)
+        if (!ks_ops[plan.policy]->hoist(ctx, {si.d, d_items, plan})) return fail(CN_ERR_ARG, "internal: hoisted rotations without a kernel of their policy");
+        HIPCHK(hipGetLastError());
+        ctx->st.ntt_forward_limbs += plan.fwd_limbs; ctx->st.ntt_inverse_limbs += plan.inv_limbs;
+        ctx->st.Rotation += nrot;
+        ctx->ks_hoisted++;
+    }
+    for (uint32_t i = 0; i < n; i++)                       // step 0 / element 1: copies
+        if (e[i] == 1) HIPCHK(hipMemcpyAsync(O->d + (size_t)oi[i] * O->item_words, si.d, ctx->ctw2 * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    for (uint32_t i = 0; i < n; i++) { if (steps) rec_rows(ctx, steps[i]); else if (e[i] != 1) rec_galois(ctx, e[i]); }
+    return 0;
+}
+extern "C" int cn_apply_galois_hoisted(cn_ctx *ctx, cn_handle in, uint32_t ii, const uint64_t *elts, uint32_t n, cn_handle out, const uint32_t *oi) { API_BODY TWO_LIMBS("cn_apply_galois_hoisted");
+    LOCK; if (n && !elts) return fail(CN_ERR_ARG, "null argument");
+    return hoisted_rotations(ctx, in, ii, elts, nullptr, n, out, oi);
+API_END }
+extern "C" int cn_rotate_rows_hoisted(cn_ctx *ctx, cn_handle in, uint32_t ii, const int *steps, uint32_t n, cn_handle out, const uint32_t *oi) { API_BODY TWO_LIMBS("cn_rotate_rows_hoisted");
+    LOCK; if (n && !steps) return fail(CN_ERR_ARG, "null argument");
+    return hoisted_rotations(ctx, in, ii, nullptr, steps, n, out, oi);
+API_END }
 static int add_kernel(cn_ctx *ctx, const uint64_t *a, const uint64_t *b, uint64_t *out, uint32_t count) {
     hipLaunchKernelGGL(k_addsub, dim3(count * 2 * ctx->hc.k * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, a, b, out, ctx->dc, ctx->chunks, 0);
     HIPCHK(hipGetLastError()); launch_count(ctx);

@@ -544,6 +544,17 @@ template <int L> NTT_DEV void ks_gather_automorphism(uint64_t (&raw)[16], const 
     for (int r = 0; r < 16; r++) raw[r] = s[lds_pos(pass_index<L, NttPlan<L>::SA, 0>(tid, r))];
     __syncthreads();                                   // the image is the transform's again
 }
+// its first half alone: sigma(a) stays in the image (the caller synchronises and reads position lds_pos(e) for coefficient e)
+template <int L> NTT_DEV void ks_stage_automorphism(const NTT_GLOBAL uint64_t *limb, uint32_t elt, uint64_t q, void *image, uint32_t tid) {
+    constexpr uint32_t n = 1u << L, NT = NttPlan<L>::NT;
+    uint64_t *s = reinterpret_cast<uint64_t *>(image);
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const uint32_t i = tid + NT * (uint32_t)r, pos = (i * elt) & (2 * n - 1);
+        const uint64_t v = limb[i];
+        s[lds_pos(pos & (n - 1))] = (pos >> L) ? (v ? q - v : 0) : v;
+    }
+}
 // Latency variant of the key switch for SMALL batches (LoLa: one image = 1..13 ciphertexts per rotation): the fused kernel above
 // runs count*k workgroups, each pushing all digit transforms through one CU in sequence - 5 busy CUs of 256 at count 1.  Here
 // the digit transforms are spread over the chip and the sum is a second launch:
@@ -759,5 +770,130 @@ __global__ void __launch_bounds__(NttPlan<L>::NT) k_ks_sum_intt(const void *__re
         if (ad) val = addmod(val, addv[r], qm.q);
         if (extra) val = addmod(val, extra[(size_t)ct * ex_stride + (size_t)p * kn + (size_t)j * n + e], qm.q);
         o[e] = val;
+    }
+}
+// Hoisted rotations (cn_rotate_rows_hoisted / cn_apply_galois_hoisted): n rotations of ONE ciphertext.  The digits of c1 do not depend on the rotation and the
+// automorphism x -> x^g is a pure permutation of a transform's output (no sign): NTT_j(s_g(D)) = P_g(NTT_j(D mod q_j)), where position p (SEAL's bit-reversed
+// output order: the evaluation at psi^(2 brev(p) + 1)) reads position brev(((2 brev(p) + 1) g mod 2N - 1) / 2).  So the tot k digit transforms run ONCE
+// (k_ks_digit_ntt) and every rotation is a permuted read of them, a multiply-accumulate with its own key and 2 inverse transforms per limb (k_ks_hoist_mac).
+//   k_ks_digit_ntt : block = (digit g, limb j): the digit cut and forward transform of k_ks_digit_mac without the key product; the transformed digit leaves as
+//                    dig[g][j][N] in transform order (the 16 B/lane pattern of the key reads), as the lazy values the fused kernels multiply with the key
+//   k_ks_hoist_mac : block = (rotation r, limb j) or - PC, N = 16384, where a 1024-thread workgroup has no room for two accumulator sets - (r, j, component p):
+//                    for every digit a gather of dig through P_(g_r), times key r into register accumulators (lazy FP64 ones recentred every accmax terms: the
+//                    terms are those of the fused kernel), inverse transform, + s_g(c0) for component 0 (staged through the image at its permuted positions),
+//                    canonical words to out_r.  No atomics, no partial products in HBM.
+// The gather: positions 2m and 2m + 1 hold the evaluations at psi^e and psi^(e + N), which x -> x^g sends to psi^(e g) and psi^(e g + N) - a pair of
+// neighbours again, swapped when e g mod 2N >= N.  A thread therefore keeps 8 pair addresses and 8 swap bits for its 16 positions, computed once (two bit
+// reversals and a product each), and every digit costs 8 loads of 16 B beside the key's: no index table in HBM.
+// (KsHoistItem, cn_runtime.h: per rotation its Galois key, its output ciphertext, its element)
+template <int L, class AR>
+__global__ void __launch_bounds__(NttPlan<L>::NT) k_ks_digit_ntt(const uint64_t *__restrict__ c1, void *__restrict__ dig_, const DevConsts *__restrict__ C, uint32_t tot) {
+    typedef typename AR::T T;
+    extern __shared__ __align__(16) unsigned char smem[];
+    T *s = reinterpret_cast<T *>(smem);
+    constexpr uint32_t n = 1u << L;
+    constexpr int SA = NttPlan<L>::SA;
+    const uint32_t k = C->k, tid = threadIdx.x;
+    const uint32_t j = blockIdx.x % k, g = blockIdx.x / k;
+    uint32_t l = 0, d = g;
+    for (;; l++) { const uint32_t nd = C->gk_dig[l]; if (d < nd) break; d -= nd; }
+    const DMod qm = C->q[j];
+    const uint64_t q = qm.q;
+    const ArCtx<AR> A(C, j);
+    const int dbc = C->gdbc, sh = dbc * (int)d;
+    const uint64_t mask = (1ull << dbc) - 1;
+    const uint64_t *src = c1 + (size_t)l * n;
+    uint64_t raw[16];
+#pragma unroll
+    for (int r = 0; r < 16; r++) raw[r] = src[pass_index<L, SA, 0>(tid, r)];
+    ks_premultiply(raw, C, l);
+    T v[16];
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        uint64_t t = (raw[r] >> sh) & mask;
+        if constexpr (std::is_same<T, uint64_t>::value) { if (mask >= q) t = t >= q ? bred128(t, 0, qm) : t; }
+        v[r] = A.load(t);
+    }
+    if constexpr (std::is_same<T, double>::value) { if (mask >= q) AR::renorm(v, A.m); }
+    ntt_forward_regs<AR, L>(v, s, A.fw, A.m, tid);
+    T *o = reinterpret_cast<T *>(dig_) + ((size_t)g * k + j) * n;
+    struct alignas(16) P2 { T a, b; };
+#pragma unroll
+    for (int r = 0; r < 16; r += 2) *reinterpret_cast<P2 *>(o + tail_index<L>(tid, r)) = P2{v[r], v[r + 1]};
+}
+template <int L, class AR, bool PC>
+__global__ void __launch_bounds__(NttPlan<L>::NT) k_ks_hoist_mac(const void *__restrict__ dig_, const uint64_t *__restrict__ c0, const KsHoistItem *__restrict__ items,
+                                                                  const DevConsts *__restrict__ C, uint32_t tot, uint32_t accmax) {
+    typedef typename AR::T T;
+    extern __shared__ __align__(16) unsigned char smem[];
+    T *s = reinterpret_cast<T *>(smem);
+    constexpr uint32_t n = 1u << L;
+    constexpr int SA = NttPlan<L>::SA, NP = PC ? 1 : 2;
+    const uint32_t k = C->k, tid = threadIdx.x;
+    const uint32_t b = PC ? blockIdx.x >> 1 : blockIdx.x, p0 = PC ? blockIdx.x & 1 : 0u;
+    const uint32_t j = b % k, rot = b / k;
+    const KsHoistItem it = items[rot];
+    const uint32_t elt = it.elt;
+    const DMod qm = C->q[j];
+    const ArCtx<AR> A(C, j);
+    const size_t kn = (size_t)k * n;
+    // P_elt of this thread's 8 position pairs: the pair it reads (an even position, as a byte offset) and whether the pair arrives swapped
+    uint32_t src[8], swp = 0;
+#pragma unroll
+    for (int r = 0; r < 16; r += 2) {
+        const uint32_t pos = tail_index<L>(tid, r), e = 2 * (__brev(pos) >> (32 - L)) + 1, x = (e * elt) & (2 * n - 1), idx = __brev((x - 1) >> 1) >> (32 - L);
+        src[r >> 1] = (idx & ~1u) * (uint32_t)sizeof(T);                 // (byte offsets: uniform base + 32-bit lane offset addresses the load)
+        swp |= (idx & 1u) << (r >> 1);
+    }
+    T acc0[16], acc1[PC ? 1 : 16];                       // PC: the one component p0 in acc0
+#pragma unroll
+    for (int r = 0; r < 16; r++) { acc0[r] = 0; if constexpr (!PC) acc1[r] = 0; }
+    const NTT_GLOBAL T *dg = (const NTT_GLOBAL T *)dig_ + (size_t)j * n;                                    // digit g: kn words behind digit g - 1
+    const NTT_GLOBAL T *kp = (const NTT_GLOBAL T *)it.key + (size_t)p0 * kn + (size_t)j * n;                // digit g: component 0 at kp + g 2kN, component 1 kN behind
+    uint32_t terms = 0;
+    for (uint32_t g = 0; g < tot; g++, dg += kn, kp += 2 * kn) {
+        uint32_t tl = tid;
+        asm volatile("" : "+v"(tl));                       // as in k_keyswitch_rr: the key addresses are rebuilt per digit instead of living in registers
+#pragma unroll
+        for (int r = 0; r < 16; r += 2) {
+            // integer path, and the 1024-thread workgroups of N = 16384 (128 registers per thread): bounds the key and digit words in flight
+            if (std::is_same<T, uint64_t>::value || (L == 14 && (r & 7) == 0)) __builtin_amdgcn_sched_barrier(0);
+            const uint32_t pos = tail_index<L>(tl, r) * (uint32_t)sizeof(T);
+            T x0, x1, ka, kb;
+            ks_load2<T>((const NTT_GLOBAL T *)((const NTT_GLOBAL char *)dg + src[r >> 1]), x0, x1);
+            if ((swp >> (r >> 1)) & 1u) { const T t = x0; x0 = x1; x1 = t; }
+            ks_load2<T>((const NTT_GLOBAL T *)((const NTT_GLOBAL char *)kp + pos), ka, kb);
+            KsMac<AR>::mac(acc0[r], x0, ka, qm, A); KsMac<AR>::mac(acc0[r + 1], x1, kb, qm, A);
+            if constexpr (!PC) {
+                ks_load2<T>((const NTT_GLOBAL T *)((const NTT_GLOBAL char *)(kp + kn) + pos), ka, kb);
+                KsMac<AR>::mac(acc1[r], x0, ka, qm, A); KsMac<AR>::mac(acc1[r + 1], x1, kb, qm, A);
+            }
+        }
+        if (++terms == accmax) { terms = 0; KsMac<AR>::settle(acc0, A); if constexpr (!PC) KsMac<AR>::settle(acc1, A); }
+    }
+    NTT_GLOBAL uint64_t *ob = (NTT_GLOBAL uint64_t *)it.out + (size_t)j * n;
+#pragma unroll 1
+    for (uint32_t p = p0; p < p0 + NP; p++) {
+        T v[16];
+#pragma unroll
+        for (int r = 0; r < 16; r++) { if constexpr (PC) v[r] = acc0[r]; else v[r] = p ? acc1[r] : acc0[r]; }
+        uint32_t tl = tid;
+        asm volatile("" : "+v"(tl));                       // no sharing of address math across the two transforms
+        ntt_inverse_regs<AR, L>(v, s, A.iv, A.m, tl);
+        const uint64_t *img = reinterpret_cast<const uint64_t *>(smem);
+        if (p == 0) {                                      // s_g(c0), limb j, staged in the image at its permuted positions (as k_keyswitch_pair14 stages it): the
+            __syncthreads();                               // whole limb is read before a word of the result is written; everybody has taken its coefficients out
+            ks_stage_automorphism<L>((const NTT_GLOBAL uint64_t *)c0 + (size_t)j * n, elt, qm.q, smem, tl);
+            __syncthreads();
+        }
+        NTT_GLOBAL uint64_t *o = ob + (size_t)p * kn;
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const uint32_t e = pass_index<L, SA, 0>(tl, r);
+            uint64_t val = A.scaled(v[r]);
+            if (p == 0) val = addmod(val, img[lds_pos(e)], qm.q);
+            o[e] = val;
+        }
+        __syncthreads();
     }
 }

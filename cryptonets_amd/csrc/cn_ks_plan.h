@@ -91,6 +91,38 @@ inline bool ks_writes_arena(const KsPlan &p) { return p.arena_bytes != 0; }
 // queued rotations by any step counts run as one launch chain per hop round (rotate_jobs) while they are few: by their blocks alone, whatever "ks_wide" says
 inline bool ks_few_rotations(const DevConsts &hc, const KsSwitches &sw, size_t count) { return count * hc.k <= sw.wide_max_blocks; }
 
+// ---- hoisted rotations (cn_rotate_rows_hoisted / cn_apply_galois_hoisted): n rotations of ONE ciphertext share the tot k forward transforms of its digits.
+// Two launches: k_ks_digit_ntt, a workgroup per (digit, limb), leaves the transformed digits in the arena; k_ks_hoist_mac, a workgroup per (rotation, limb) - at
+// N = 16384, where a 1024-thread workgroup has no room for two accumulator sets, per (rotation, limb, component) - reads them through the rotation's permutation.
+// The kernels exist at every register-radix size under all three policies but N = 16384 under the integer policy (cn_ks_hoist_built): beside a 1024-thread
+// workgroup's 128 registers per thread the integer inverse transform leaves no room for the rest of k_ks_hoist_mac even with one accumulator set (59 spilled
+// registers when built) - refused here, as cn_plain_wide refuses the wide plaintext kernels there; the launchers instantiate by the same predicate.  N < 1024 and
+// "legacy_ntt" are refused as well (as cn_encrypt_symmetric refuses them).  The arena is the context's ONE key-switch arena on its own stream: tot k N words,
+// whatever n is.
+constexpr bool cn_ks_hoist_built(int policy, uint32_t logn) { return logn >= 10 && logn <= 14 && !(policy == POL_U64 && logn == 14); }
+struct KsHoistPlan {
+    int rc; const char *msg;      // the refusal (0: none)
+    int policy;                   // cn_policy of the q limbs by the form the keys were loaded in
+    uint32_t accmax;              // FP64 accumulators: terms between recentrings (cn_f64_acc_interval: canonical words times key words, as in the fused kernel)
+    size_t arena_bytes;           // of cn_ctx::ks_part: dig[tot][k][N]
+    bool per_component;           // second launch: a workgroup per (rotation, limb, component) instead of per (rotation, limb)
+    uint32_t blocks_ntt, blocks_mac;      // workgroups of the two launches
+    uint64_t fwd_limbs, inv_limbs;        // what the call adds to ntt_forward_limbs / ntt_inverse_limbs
+};
+inline KsHoistPlan cn_ks_hoist_plan(const DevConsts &hc, const KsSwitches &sw, bool key_f64, uint32_t n) {
+    const uint32_t k = hc.k, tot = hc.gk_tot;
+    const CnModRange qr = cn_mod_range(hc, 0, k);
+    KsHoistPlan p{0, nullptr, cn_policy(qr, key_f64), key_f64 ? cn_f64_acc_interval(qr.bits) : 0xffffffffu, (size_t)tot * k * hc.n * 8, hc.logn == 14, tot * k, 0, (uint64_t)tot * k, (uint64_t)n * 2 * k};
+    p.blocks_mac = n * k * (p.per_component ? 2u : 1u);
+    auto refuse = [&p](const char *text) { p.rc = CN_ERR_ARG; p.msg = text; p.arena_bytes = 0; p.blocks_ntt = p.blocks_mac = 0; p.fwd_limbs = p.inv_limbs = 0; return p; };
+    if (!n) return refuse("hoisted rotations: an empty list");
+    if (!sw.rr) return refuse("hoisted rotations need the register-radix kernels (1024 <= N <= 16384, \"legacy_ntt\" off)");
+    if (key_f64 && !qr.f64ok) return refuse("internal: FP64 key without FP64 kernel");
+    if (!cn_ks_hoist_built(p.policy, hc.logn)) return refuse("hoisted rotations: no kernel under the integer policy at N = 16384 (it does not fit a 1024-thread workgroup's registers)");
+    if ((uint64_t)n * k * 2 > 0x7fffffffu) return refuse("hoisted rotations: too many rotations for one launch");
+    return p;
+}
+
 // ---- the call shapes a form does not take (internal errors: a caller asked the wrong reader)
 struct KsShape { bool dig, perm_elt, items, next_elt; };      // KsCall: ready-made digits; automorphism on load; per-ciphertext operand table; sigma_next(c1) on the side
 struct KsRefusal {

@@ -22,10 +22,13 @@ template <int L, class DS> static int set_attrs_dig(size_t bytes) {
     CHECK(big_lds(k_ks_digit_mac<L, DS>, bytes)); CHECK(big_lds(k_ks_limb_mac<L, DS>, bytes));
     return 0;
 }
+// hoisted rotations: the instantiations the planner's predicate admits (cn_ks_hoist_built, cn_ks_plan.h)
+template <int L> static constexpr bool kHoist = cn_ks_hoist_built(kF64 ? POL_F64 : POL_U64, L);
 template <int L> static int set_attrs_l(size_t bytes) {
     CHECK(big_lds(k_keyswitch_rr<L, AR>, bytes)); CHECK(big_lds(k_keyswitch_rr<L, AR, 1, false, true>, bytes));
     if constexpr (KsFwd<AR, L>::lds) { CHECK(big_lds(k_keyswitch_rr<L, AR, 1, true>, ks_twl_lds<L>())); CHECK(big_lds(k_keyswitch_rr<L, AR, 1, true, true>, ks_twl_lds<L>())); }
     CHECK(big_lds(k_ks_digit_mac<L, AR>, bytes)); CHECK(big_lds(k_ks_limb_mac<L, AR>, bytes)); CHECK(big_lds(k_ks_sum_intt<L, AR>, bytes));
+    if constexpr (kHoist<L>) { CHECK(big_lds(k_ks_digit_ntt<L, AR>, bytes)); CHECK(big_lds(k_ks_hoist_mac<L, AR, L == 14>, bytes)); }
     if constexpr (kF64) { CHECK((set_attrs_dig<L, KsDigits<AR>>(bytes))); if constexpr (kDig32<L>) CHECK((set_attrs_dig<L, KsDigits<AR, int32_t>>(bytes))); }
     return 0;
 }
@@ -153,6 +156,29 @@ static bool launch(cn_ctx *c, const KsArgs &a) {
         default: return false;
     }
 }
+// hoisted rotations: the digit transforms of the one input into c->ks_part, then every rotation's permuted read, key product and inverse transforms (KsHoistPlan;
+// its per_component is N = 16384, which is the kernel's template argument here)
+template <int L> static bool launch_hoist(cn_ctx *c, const KsHoistArgs &a) {
+    if constexpr (kHoist<L>) {
+        const size_t lds = (size_t)ntt_lds_words(1u << L) * 8, kn = (size_t)c->hc.k << L;
+        hipLaunchKernelGGL((k_ks_digit_ntt<L, AR>), dim3(a.plan.blocks_ntt), dim3(NttPlan<L>::NT), lds, c->stream, a.in + kn, c->ks_part, c->dc, c->hc.gk_tot);
+        hipLaunchKernelGGL((k_ks_hoist_mac<L, AR, L == 14>), dim3(a.plan.blocks_mac), dim3(NttPlan<L>::NT), lds, c->stream, (const void *)c->ks_part, a.in, a.items, c->dc, c->hc.gk_tot,
+                           a.plan.accmax);
+        cn_launch_count(c, 2);
+        return true;
+    }
+    return false;
+}
+static bool hoist(cn_ctx *c, const KsHoistArgs &a) {
+    switch (c->hc.logn) {
+        case 10: return launch_hoist<10>(c, a);
+        case 11: return launch_hoist<11>(c, a);
+        case 12: return launch_hoist<12>(c, a);
+        case 13: return launch_hoist<13>(c, a);
+        case 14: return launch_hoist<14>(c, a);
+        default: return false;
+    }
+}
 #ifndef __HIP_DEVICE_COMPILE__      // host-side table (in the device pass a const global would be emitted as device data)
-extern const KsOps KS_NAME = {set_attrs, launch};
+extern const KsOps KS_NAME = {set_attrs, launch, hoist};
 #endif

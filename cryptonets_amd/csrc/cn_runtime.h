@@ -182,6 +182,7 @@ struct cn_ctx {
     int cus = 0;              // compute units of the device
     CnCounters cnt;           // what cn_get_option reads back by the names of kCounters (cn_options.h)
     std::atomic<uint64_t> packed_bad{0};       // packed uploads whose rows held a residue >= its modulus (counted where the flag is read)
+    uint64_t ks_hoisted = 0;   // calls of cn_rotate_rows_hoisted / cn_apply_galois_hoisted that launched ("ks_hoisted")
     uint32_t ms_groups = 0;    // output groups of the last cn_mul_relin_sum call ("mul_sum_groups"; 0: it took the literal sequence)
     uint64_t uid = 0;         // creation order within the process (cn_ctx_create)
     hipStream_t stream2 = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr; bool stream2_failed = false;   // second stream of pipelined_halves (aux_stream_ready)
@@ -264,9 +265,14 @@ struct RrOps {                // register-radix kernels of one arithmetic policy
                             uint64_t *next_out, bool ptn);                             // ONE ciphertext (NTT form) x count plaintexts (+ sigma_next(c1) of every product on the side); ptn: NTT-form plaintexts
     bool (*enc_fold)(cn_ctx *c, const int8_t *us, const int8_t *noise, const void *fout, const void *terms, uint32_t outputs);   // FP64 policies, N <= 8192: k_encrypt_fold
 };
+// hoisted rotations (cn_ks_plan.h: KsHoistPlan): per rotation its Galois key, its output ciphertext and its element (the table k_ks_hoist_mac reads); the call:
+// the ONE input ciphertext (c0, c1 behind it), the table on the device (the plan's blocks_mac says how many rotations it holds)
+struct KsHoistItem { const void *key; uint64_t *out; uint32_t elt, pad; };
+struct KsHoistArgs { const uint64_t *in; const KsHoistItem *items; KsHoistPlan plan; };
 struct KsOps {
     int (*set_attrs)(uint32_t logn, size_t lds);
     bool (*launch)(cn_ctx *c, const KsArgs &a);                        // the kernels of a.plan.form; false: this policy (or ring size) has no instantiation of it
+    bool (*hoist)(cn_ctx *c, const KsHoistArgs &a);                    // k_ks_digit_ntt + k_ks_hoist_mac of this policy; false: no instantiation at this ring size
 };
 extern const RrOps cn_rr_u64, cn_rr_f64, cn_rr_f64l;
 extern const KsOps cn_ks_u64, cn_ks_f64, cn_ks_f64l;

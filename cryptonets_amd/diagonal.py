@@ -71,7 +71,7 @@ def choose_baby_steps(mask):
     return best[1]
 
 
-def dense_path_counts(R, Dim, n, k, digits, length=None, B=None, ntt_weights=False):
+def dense_path_counts(R, Dim, n, k, digits, length=None, B=None, ntt_weights=False, hoisted=False):
     """Limb transforms (one N-point transform of one limb) of the two ways to compute the dense product of an R x Dim plaintext matrix with one packed ciphertext on a
     ring of n slots with k coefficient moduli and `digits` digit polynomials per key switch (ks_digits of the Galois decomposition bit count):
 
@@ -85,6 +85,9 @@ def dense_path_counts(R, Dim, n, k, digits, length=None, B=None, ntt_weights=Fal
 
     ntt_weights: the row plaintexts / the diagonals are resident in NTT form (hewrapper.NTT_WEIGHTS, cn_pt_transform) - their transforms drop out of both counts:
     2 k per row on the default path, 2 k per diagonal on the diagonal path.
+
+    hoisted: the baby steps are ONE hoisted call (hewrapper.HOISTED_ROTATIONS, cn_rotate_rows_hoisted: every baby step with its own key) - their key switches share
+    the digits k forward transforms of the input and cost 2 k inverse transforms each, instead of digits k + 2 k each.  The default path does not change.
 
     Weights are taken as dense inside R x Dim (structural_diagonals).  Returns a dict with the two totals, their parts and "choice": "diagonal" if and only if its
     total is lower."""
@@ -104,6 +107,9 @@ def dense_path_counts(R, Dim, n, k, digits, length=None, B=None, ntt_weights=Fal
     terms = int(mask.sum())
     g_plain = babies * 2 * k + (0 if ntt_weights else terms * 2 * k) + ngroups * 2 * k
     default, diagonal = d_ks * per_ks + d_plain, g_ks * per_ks + g_plain
+    baby_ks = max(babies - (1 if mask.reshape(2, -1, B)[:, :, 0].any() else 0), 0)
+    if hoisted and baby_ks:
+        diagonal -= baby_ks * per_ks - (digits * k + baby_ks * 2 * k)
     return {"default": default, "diagonal": diagonal, "choice": "diagonal" if diagonal < default else "default", "B": B,
             "default_key_switches": d_ks, "diagonal_key_switches": g_ks, "default_plain_transforms": d_plain, "diagonal_plain_transforms": g_plain,
             "diagonals": terms, "babies": babies, "groups": ngroups}

@@ -89,6 +89,42 @@ NTT_WEIGHTS = False
 DEVICE_DIAGONAL_PLAN = False
 
 
+# HOISTED_ROTATIONS = True: the places that rotate ONE ciphertext by many step counts - the copies of Duplicate, the baby steps of DiagonalDense - ask for one hoisted
+# call (cn_rotate_rows_hoisted, DESIGN 6j: the digit transforms of the input once, two launches, every copy one key switch away from the input) when the context
+# holds the own Galois key of every step; the baby steps are then never "by doubling".  A context that lacks a key (CN_ERR_NOKEY) or has no kernel for the call (the
+# planner's refusals for the ring size / "legacy_ntt" and for the integer policy at N = 16384) takes the present route; any other error is raised.  The decrypted slots are the same; the ciphertext words and the noise differ (the words of tests/hoisted_model.py).  Direct
+# keys for B - 1 baby steps cost (B - 1) digits 2 k N 8 bytes per plaintext prime (2 GiB at the CIFAR layer, against the 7 keys of doubling): networks.rotation_steps
+# reports the direct steps under this switch, so GenerateEncryptionKeys(steps=...) makes exactly them.  False (default): nothing changes - the switch stays off until
+# the routes have been measured side by side (profiles/hoisted_rotations.md).
+HOISTED_ROTATIONS = False
+
+
+def _rotate_hoisted(ctx, h, first, steps, out_h, out_idx):
+    """out_h[out_idx[r]] = the rotation of h[first] by steps[r] through one hoisted call; False (nothing written): the switch is off, the backend has no such
+    call, a key is missing (CN_ERR_NOKEY) or the context has no kernel for it (the two refusals of the planner: ring size / "legacy_ntt", the integer policy at
+    N = 16384) - the caller takes its present route.  Every other error is the caller's and is raised.  While the context records steps, a call that lacks a key
+    still notes the steps it asked for (Context.note_hoisted_steps; rotation_steps returns them): the keys to generate are those of the direct steps."""
+    if not HOISTED_ROTATIONS or not hasattr(ctx, "rotate_rows_hoisted"):
+        return False
+    from ._native import CN_ERR_ARG, CN_ERR_NOKEY, HOISTED_UNAVAILABLE, CnError
+    steps = [int(s) for s in steps]
+    try:
+        ctx.rotate_rows_hoisted(h, first, steps, out_h, list(out_idx))
+        return True
+    except CnError as e:
+        if e.code == CN_ERR_NOKEY:
+            ctx.note_hoisted_steps(steps)
+            return False
+        if e.code == CN_ERR_ARG and any(text in str(e) for text in HOISTED_UNAVAILABLE):
+            return False
+        raise
+
+
+def _hoisted_keys_held(ctx, B):
+    """does the context hold the own Galois key of every baby step 1 .. B - 1 (what a hoisted call of DiagonalDense needs)?"""
+    return hasattr(ctx, "rotate_rows_hoisted") and all(ctx.has_galois_key(ctx.galois_elt_from_step(s)) for s in range(1, B))
+
+
 def _device_split_ok(env, encrypt):
     """may cn_split_encode / cn_split_encrypt serve this CRT environment?  Device clients on library contexts, at most 8 primes; encryption on the ring
     sizes cn_encrypt takes"""
@@ -1238,7 +1274,10 @@ class AtomicSealBfvEncryptedVector:
                 steps.append(-target)
             if 1 in srcs:
                 ctx.rotate_columns(self.encData.h, self.encData.first, work.h, 1, 1)
-            ctx.rotate_rows_many(work.h, srcs, steps, work.h, [2 + i for i in range(n)])
+            # HOISTED_ROTATIONS: the copies of each of the two sources are one hoisted call; a refusal of either leaves the present route for all
+            by_src = [[i for i in range(n) if srcs[i] == c] for c in (0, 1)]
+            if not all(_rotate_hoisted(ctx, work.h, c, [steps[i] for i in idx], work.h, [2 + i for i in idx]) for c, idx in enumerate(by_src) if idx):
+                ctx.rotate_rows_many(work.h, srcs, steps, work.h, [2 + i for i in range(n)])
             res = _Buf(ctx, "ct", 1).view()
             ctx.add_many(work.h, [0] + [2 + i for i in range(n)], res.h, 0)
             work.release()
@@ -1982,7 +2021,13 @@ class EncryptedSealBfvMatrix:
         R, n = len(self.leVectors), ctx.n
         if R > n or v.Dim > n:
             return None
-        return diagonal.dense_path_counts(R, int(v.Dim), n, len(ctx.q), diagonal.ks_digits(ctx.q, ctx.gdbc), ntt_weights=NTT_WEIGHTS and hasattr(ctx, "pt_transform"))
+        args = (R, int(v.Dim), n, len(ctx.q), diagonal.ks_digits(ctx.q, ctx.gdbc))
+        c = diagonal.dense_path_counts(*args, ntt_weights=NTT_WEIGHTS and hasattr(ctx, "pt_transform"))
+        # HOISTED_ROTATIONS: the baby steps are priced as one hoisted call only where the context holds their direct keys - without them the run goes by doubling.
+        # (Not foreseen here: a context whose planner refuses the call - the integer policy at N = 16384 - is still priced as hoisted when it holds the keys.)
+        if HOISTED_ROTATIONS and _hoisted_keys_held(ctx, c["B"]):
+            c = diagonal.dense_path_counts(*args, B=c["B"], ntt_weights=NTT_WEIGHTS and hasattr(ctx, "pt_transform"), hoisted=True)
+        return c
 
     def DiagonalDenseWins(self, v, env):
         c = self.DiagonalDenseCounts(v, env)
@@ -2052,7 +2097,9 @@ class EncryptedSealBfvMatrix:
             bab, u = _Buf(ctx, "ct", nb), _Buf(ctx, "ct", ng)
             bv, uv = bab.view(), u.view()
             ctx.copy(src.h, src.first, bab.h, 0, 1)
-            if plan.babies_by_doubling:
+            if nb > 1 and _rotate_hoisted(ctx, bab.h, 0, plan.babies[1:], bab.h, range(1, nb)):
+                pass                                                 # HOISTED_ROTATIONS: every baby step one key switch away from the input, never by doubling
+            elif plan.babies_by_doubling:
                 s = 1
                 while s < Bs:                                        # rho_(b + s)(v) = rho_s(rho_b(v)) for all b < s at once
                     ctx.rotate_rows(bab.h, 0, s, bab.h, s, s)

@@ -362,7 +362,9 @@ def rotation_steps(network, Factory, record=1):
     """Which rotations does `network` ask for?  Evaluates `record` record(s) (one is enough: the steps depend on the layer shapes, not on the data)
     with cn_set_option("record_steps", 1) on the context of every plaintext prime and on every level context that exists when the evaluation
     ends (a scheduled chain creates them on the way), and returns the union as (sorted distinct RotateRows steps, was a column rotation asked
-    for) - what GenerateEncryptionKeys(steps=...) / EncryptedSealBfvFactory(steps=...) take.  The contexts need keys that can serve the network
+    for) - what GenerateEncryptionKeys(steps=...) / EncryptedSealBfvFactory(steps=...) take.  Under hewrapper.HOISTED_ROTATIONS the union holds the DIRECT steps of
+    every hoisted call (the baby steps of a diagonal dense layer, the copies of a Duplicate), also where the recording contexts lack their keys and take the present
+    route (Context.rotation_steps returns what Context.note_hoisted_steps noted).  The contexts need keys that can serve the network
     already (the default set does); recording is switched off and cleared afterwards."""
     env = Factory.AllocateComputationEnv()
     roots = [e.ctx for e in env.Environments]

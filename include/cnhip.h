@@ -414,6 +414,30 @@ int cn_rotate_rows(cn_ctx *ctx, cn_handle in, uint32_t ii, int steps, cn_handle 
  * and the element of ITS step count - so a single-image network pays the dispatches of the longest rotation instead of the sum (n <= 32 / k; more
  * run one after the other).  in == out is allowed when no result overwrites another rotation's operand or result (its own is fine). */
 int cn_rotate_rows_many(cn_ctx *ctx, cn_handle in, const uint32_t *ii, const int *steps, uint32_t n, cn_handle out, const uint32_t *oi);
+/* Hoisted rotations: n rotations of ONE ciphertext, out[oi[r]] = the rotation of in[ii] by elts[r] / steps[r], with ONE set of digit transforms.  The reference
+ * rotates one ciphertext by many step counts in Duplicate (AtomicSealBfvVector.cs:1370-1396: a rotate-and-add chain over copies of one vector), for the equal-source
+ * vectors of Interleave / Vectorize (AtomicSealBfvVector.cs:625-660, 1458) and - through this package's diagonal dense layers - for the baby steps of a matrix-vector
+ * product; every Evaluator.RotateRows there cuts c1 into its gk_tot digit polynomials and transforms each of them for each of the k limbs.  The digits do not depend
+ * on the rotation and x -> x^g permutes a transform's output without a sign, so this call runs gk_tot k forward transforms once and 2 k inverse transforms per
+ * rotation, in two launches (k_ks_digit_ntt, k_ks_hoist_mac).
+ * THE WORDS are not those of cn_rotate_rows: SEAL permutes c1 and cuts digits afterwards, and a negated coefficient q_l - x has other digits than x.  With
+ *     D_(l,d)[i]          = digit d (base 2^gdbc, low to high) of c1 limb l, coefficient i           ("ks_xi": of [c1_l (q/q_l)^-1]_(q_l))
+ *     s_g(D)_j[i g mod N] = +- (D[i] mod q_j), negative when (i g mod 2N) >= N                        (canonical)
+ *     out_p limb j        = INTT_j( sum_(l,d) NTT_j(s_g(D_(l,d))_j) . K_g[(l,d)][p][j] )  +  (p == 0 ? s_g(c0)_j : 0)
+ * for the Galois key K_g of element g.  The result decrypts to the plaintext of cn_apply_galois; its key-switch noise is a sum over the same digits against the same
+ * key errors, permuted (tests/hoisted_model.py states the formula in Python integers, tests/test_gpu_hoisted_rotations.py holds the device to it).
+ * The steps form maps a step through cn_galois_elt_from_step's rule; step 0 and element 1 are plain copies.  Every element needs its OWN key - there are no
+ * non-adjacent-form hops, a hop chain is sequential: CN_ERR_NOKEY otherwise.  CN_ERR_ARG: a step of N/2 or more, an even element or one >= 2N, n = 0, an output
+ * index listed twice, operands not of size 2, an output that is in[ii] itself, N < 1024 or "legacy_ntt", keys loaded in different forms.  A refused call launches
+ * nothing and leaves the outputs untouched.  Queued calls ("defer") are submitted first and the call runs at once.  Under cn_graph_begin the lists are captured by
+ * value (as for cn_add_many); the transformed digits live in the key-switch arena (gk_tot k N words), which cannot grow while a graph is recorded or alive - run
+ * the sequence once before recording.  Works on level contexts with the sliced keys, in both key-switch conventions ("ks_xi") and with keys loaded in either form
+ * ("f64"); "record_steps" notes the steps as cn_rotate_rows_many / cn_apply_galois do.  cn_get_option "ks_hoisted" counts the calls that launched the two kernels (counts
+ * up, read-only); ntt_forward_limbs / ntt_inverse_limbs grow by gk_tot k and 2 k per rotation.
+ * Key memory: direct keys for B - 1 baby steps are (B - 1) gk_tot 2 k N 8 bytes per plaintext prime - 2 GiB at N = 16384, k = gk_tot = 8, B = 128, against the 7 keys
+ * of baby steps by doubling. */
+int cn_apply_galois_hoisted(cn_ctx *ctx, cn_handle in, uint32_t ii, const uint64_t *elts, uint32_t n, cn_handle out, const uint32_t *oi);
+int cn_rotate_rows_hoisted(cn_ctx *ctx, cn_handle in, uint32_t ii, const int *steps, uint32_t n, cn_handle out, const uint32_t *oi);
 /* Evaluator.RotateColumns(/Inplace) (AtomicSealBfvVector.cs:709,914,1391) */
 int cn_rotate_columns(cn_ctx *ctx, cn_handle in, uint32_t ii, cn_handle out, uint32_t oi, uint32_t count);
 /* out[i] = acc[i] + RotateRows(in[i], steps) / + RotateColumns(in[i]): the rotate-and-add step of SumAllSlots / RotateRowsAndAdd
