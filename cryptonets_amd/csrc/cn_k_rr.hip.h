@@ -352,14 +352,19 @@ __global__ void __launch_bounds__(NttPlan<L>::NT, PLDS ? 2 : 4) k_square_fused(c
 // issue floor of 349 / 419 us).  Here:
 //   * the grid is RESIDENT: gridDim.x = Lm * G workgroups (one per CU), workgroup (l, w) squares limb l of ciphertexts w, w + G, ... - one modulus per
 //     workgroup for its whole life, so
-//   * the INVERSE root table of that modulus is copied into LDS once (8 N bytes behind the exchange image - the room the parked operand took) and the
-//     three inverse transforms of every block read their roots with ds_read instead of global loads; the first-pass roots of the forward transforms
-//     live in SGPRs (ArPassA) - the two devices of the fused key switch (cn_k_ks.hip.h);
+//   * EVERY root of that modulus is resident, in the 8 N bytes behind the exchange image (the room the parked operand took) and in registers: the last pass
+//     uses indices [N/2, N) and a thread the same 8 of them in every transform - they are loaded once into 16 + 16 VGPRs (ArTailRegs) - so half a table per
+//     direction is enough for the other passes: indices [0, N/2) of the forward and of the inverse table, 4 N bytes each, read with ds_read; the first-pass
+//     roots of the forward transforms live in SGPRs (ArPassA).  No transform of the step loop issues a vector-memory load: its only global loads are the 16
+//     operand words (200 / 202 VGPRs at every size, no scratch);
 //   * the NTT-form operand is parked in REGISTERS (16 doubles: one workgroup per CU leaves 256 VGPRs per thread);
-//   * the NEXT operand (a1 of this block, a0 of the workgroup's next block) is requested right behind the forward transform - after its last root load,
-//     so that no later wait on a vector-memory counter has to drain it early (the counter is in-order) - and arrives under the tensor, the inverse
-//     transform (no vector-memory loads any more) and the stores.
-// Same words as the separate launches (tests/test_gpu_evaluator.py::test_squaring_fused_kernel_is_the_separate_launches).
+//   * the NEXT operand (a1 of this block, a0 of the workgroup's next block) is requested right behind the forward transform and arrives under the tensor,
+//     the inverse transform and the stores.
+// Measured (profiles/square_pipe_resident_roots.md; 845 / 100 products, five and six limbs): resident forward roots take the q side 590 -> 576 / 205 -> 198 us,
+// the Bsk side of the five-transform form 245 -> 239 us (100 products) and the NttOut01 form 524 -> 484 us.  Requesting the next operand at the TOP of the step
+// (the forward transform issues no load that would drain it) was slower in every form - 198 -> 217, 239 -> 261, 484 -> 497 us - and so was that with the
+// arrival wait moved in front of the step's stores (213, 256, 493): the request stays behind the forward transform.
+// Same words as the separate launches (tests/test_gpu_evaluator.py::test_squaring_fused_kernel_is_the_separate_launches, tests/test_gpu_square_pipe_roots.py).
 template <class AR> struct LdsTwiddles;
 template <int RN> struct LdsTwiddles<ArF64T<RN>> { typedef ArF64LdsT<RN> type; };
 template <int L, class AR, class... NX_>
@@ -376,16 +381,19 @@ __global__ void __launch_bounds__(NttPlan<L>::NT, 2) k_square_pipe(const uint64_
     const uint32_t G = gridDim.x / Lm, l = blockIdx.x % Lm, w0 = blockIdx.x / Lm, mod = base_off + l;
     const ArCtx<AR> A(C, mod);
     const size_t Ln = (size_t)Lm * n;
-    typedef ArPassA<AR> FW;
+    typedef ArTailRegs<ArPassA<typename LdsTwiddles<AR>::type>> FW;
+    typedef ArTailRegs<typename LdsTwiddles<AR>::type> IV;
     typename FW::Tw fwt;
-    static_cast<typename AR::Tw &>(fwt) = A.fw;
-    ntt_load_pass_a<SA>(fwt, A.fw.w);
-    typedef typename LdsTwiddles<AR>::type IV;
     typename IV::Tw ivt;
     {
-        double *tws = reinterpret_cast<double *>(smem) + ntt_lds_words(n);
-        stage_table(tws, A.iv.w, n, tid, NttPlan<L>::NT);
-        ivt.w = (const __attribute__((address_space(3))) double *)tws;
+        typedef const __attribute__((address_space(3))) double *LP;
+        double *tws = reinterpret_cast<double *>(smem) + ntt_lds_words(n);   // roots [0, N/2) of the forward table, then of the inverse table: 4 N bytes each
+        stage_table(tws, A.fw.w, n / 2, tid, NttPlan<L>::NT);
+        stage_table(tws + n / 2, A.iv.w, n / 2, tid, NttPlan<L>::NT);
+        fwt.w = (LP)tws; ivt.w = (LP)(tws + n / 2);
+        ntt_load_pass_a<SA>(fwt, A.fw.w);
+        ntt_load_tail<L>(fwt, A.fw.w, tid);
+        ntt_load_tail<L>(ivt, A.iv.w, tid);
         __syncthreads();
     }
     auto operand = [&](uint32_t ct) { return (const NTT_GLOBAL uint64_t *)(a_tab ? a_tab[ct] : A_ + (size_t)ct * a_stride) + (size_t)l * n; };

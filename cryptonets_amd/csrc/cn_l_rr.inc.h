@@ -30,7 +30,8 @@ template <int L> static int set_attrs_l(size_t bytes) {
 }
 static int set_attrs(uint32_t logn, size_t bytes) {      // transforms whose padded LDS image exceeds the default dynamic-LDS limit (N >= 8192)
     if constexpr (kF64) { if (logn == 12) { CHECK(big_lds(k_square_fused<12, AR, true>, bytes + ((size_t)8 << 12))); CHECK(big_lds(k_square_pipe<12, AR>, bytes + ((size_t)8 << 12)));
-                                          CHECK(big_lds(k_square_fused<12, AR, true, NttOut01>, bytes + ((size_t)8 << 12))); CHECK(big_lds(k_square_pipe<12, AR, NttOut01>, bytes + ((size_t)8 << 12))); } }   // image + parked operand / root table = 66.5 KiB
+                                          CHECK(big_lds(k_square_fused<12, AR, true, NttOut01>, bytes + ((size_t)8 << 12))); CHECK(big_lds(k_square_pipe<12, AR, NttOut01>, bytes + ((size_t)8 << 12))); } }   // image + parked operand / root tables = 66.5 KiB
+    // (k_square_pipe: 8 N bytes behind the image as before - indices [0, N/2) of the forward AND of the inverse root table, 4 N bytes each, in the room of one full table)
     if (logn == 13) return set_attrs_l<13>(bytes);
     if (logn == 14) return set_attrs_l<14>(bytes);
     return 0;

@@ -171,6 +171,29 @@ template <int SA, class TW> NTT_DEV void ntt_load_pass_a(TW &t, const NTT_GLOBAL
     for (int i = 1; i < (1 << SA); i++) t.wa[i] = ntt_uniform(table[i]);
 }
 
+// Last-pass twiddles in VGPRs (D = 1).  In the last pass thread tid pairs neighbours at the positions tail_index(tid, 2p), p = 0..7, and so uses the SAME 8
+// roots - roots[N/2 + (tail_index(tid, 2p) >> 1)] - in every transform of one modulus and direction.  A resident kernel loads them once (ntt_load_tail) and
+// fwd_tail / inv_tail take them from the registers; the table behind BASE::Tw then only has to hold the indices below N/2 that the other passes use (half the
+// bytes: a forward and an inverse half-table fit where one full table did).  BASE = ArF64LdsT<RN> or ArPassA<ArF64LdsT<RN>>.
+template <class BASE> struct ArTailRegs : BASE {
+    typedef typename BASE::T T;
+    typedef typename BASE::Mod Mod;
+    struct Tw : BASE::Tw { double wt[8]; };
+    static constexpr bool tailRegs = true;
+    static NTT_DEV void fwdT(T &X, T &Y, const Tw &t, int p, const Mod &m) {
+        const double r = BASE::mulmod(Y, t.wt[p], m);
+        Y = __dadd_rn(X, -r);
+        X = __dadd_rn(X, r);
+    }
+    static NTT_DEV void invT(T &U, T &V, const Tw &t, int p, const Mod &m) {
+        const double s = __dadd_rn(U, V), d = __dadd_rn(U, -V);
+        U = s;
+        V = BASE::mulmod(d, t.wt[p], m);
+    }
+};
+template <class AR, class = void> struct HasTailRegs { static constexpr bool value = false; };
+template <class AR> struct HasTailRegs<AR, decltype((void)AR::tailRegs)> { static constexpr bool value = true; };
+
 template <int L> struct NttPlan {
     static constexpr int D = (L == 14) ? 2 : 1;      // stages of the last (adjacent-coefficient) pass
     static constexpr int SA = L - 8 - D;             // stages of the first pass (1..4)
@@ -290,8 +313,20 @@ template <class T, int L> NTT_DEV void lds_get_tail(T (&x)[16], const T *s, uint
         x[r] = v.a; x[r + 1] = v.b;
     }
 }
+// wt[p] <- table[N/2 + (tail_index(tid, 2p) >> 1)] of a GLOBAL root table: consecutive lanes, consecutive roots (ArTailRegs)
+template <int L, class TW> NTT_DEV void ntt_load_tail(TW &t, const NTT_GLOBAL double *table, uint32_t tid) {
+    static_assert(NttPlan<L>::D == 1, "one root per register pair: D = 1");
+#pragma unroll
+    for (int p = 0; p < 8; p++) t.wt[p] = table[(1u << (L - 1)) + (tail_index<L>(tid, 2 * p) >> 1)];
+}
 template <class AR, int L> NTT_DEV void fwd_tail(typename AR::T (&x)[16], const typename AR::Tw &tw, const typename AR::Mod &m, uint32_t tid) {
     constexpr int D = NttPlan<L>::D, NT = NttPlan<L>::NT;
+    if constexpr (HasTailRegs<AR>::value) {
+        static_assert(D == 1, "ArTailRegs: D = 1");
+#pragma unroll
+        for (int p = 0; p < 8; p++) AR::fwdT(x[2 * p], x[2 * p + 1], tw, p, m);
+        return;
+    }
     if (D == 2) {
 #pragma unroll
         for (int g = 0; g < 4; g++) {
@@ -308,6 +343,12 @@ template <class AR, int L> NTT_DEV void fwd_tail(typename AR::T (&x)[16], const 
 }
 template <class AR, int L> NTT_DEV void inv_tail(typename AR::T (&x)[16], const typename AR::Tw &tw, const typename AR::Mod &m, uint32_t tid) {
     constexpr int D = NttPlan<L>::D, NT = NttPlan<L>::NT;
+    if constexpr (HasTailRegs<AR>::value) {
+        static_assert(D == 1, "ArTailRegs: D = 1");
+#pragma unroll
+        for (int p = 0; p < 8; p++) AR::invT(x[2 * p], x[2 * p + 1], tw, p, m);
+        return;
+    }
 #pragma unroll
     for (int p = 0; p < 8; p++) {
         const uint32_t pair = tail_index<L>(tid, 2 * p) >> 1, ti = (1u << (L - 1)) + pair;
