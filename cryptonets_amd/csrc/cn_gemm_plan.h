@@ -51,6 +51,7 @@ inline GemmArith gemm_arith(const DevConsts &hc, const GemmSwitches &sw, bool we
 inline bool gemm_mfma_ok(const DevConsts &hc, const GemmSwitches &sw, const GemmArith &ar, uint32_t M, uint32_t K) {
     return sw.gemm_mfma && ar.small && ar.bits <= 46 && M >= 16 && (uint64_t)K * 3 < (1u << 17) && !(hc.n & 31);
 }
+static const uint64_t GEMM_RES_CLIP = 127, GEMM_RES_MAX = 254;      // clipped + residual form (gemm_residual_form): |c| <= 127, |w| <= 254
 inline uint32_t gemm_weight_planes(const DevConsts &hc, const uint64_t *W, size_t count) {
     uint64_t amax = 0;
     for (size_t x = 0; x < count; x++) amax = std::max(amax, gemm_abs_weight(hc, W[x]));
@@ -136,11 +137,16 @@ template <class KEY> struct GemmGroups {
     std::vector<KEY> rows;                 // [G][Kp]
     std::vector<uint32_t> member;          // [G][M]: the output of (group, m)
     const uint64_t *W = nullptr;           // [O][K] residues mod t
+    // clipped + residual form (gemm_residual_form): the K slots of every gather row are permuted, slot kk of group g holds term src[g][kk] of the caller's rows, and the
+    // first kres[g] K steps hold every input with a weight beyond +-127
+    bool res = false;
+    std::vector<uint32_t> src, kres;       // [G][K] (empty: the identity), [G]
+    uint32_t term(uint32_t g, uint32_t kk) const { return src.empty() ? kk : src[(size_t)g * K + kk]; }
     bool tap(uint32_t g, uint32_t kk) const { return rows[(size_t)g * Kp + kk] > PAD; }
     const uint64_t *row(uint32_t g, uint32_t m) const { const uint32_t o = member[(size_t)g * M + m]; return o == GEMM_NONE ? nullptr : W + (size_t)o * K; }
     // weight of term kk in the row wr of group g: a padded tap gets the weight 0 whatever the caller passed (k_scalar_gemm_f64 multiplies a valid word by it
     // instead of selecting per lane)
-    uint64_t weight(uint32_t g, const uint64_t *wr, uint32_t kk) const { return tap(g, kk) ? wr[kk] : 0; }
+    uint64_t weight(uint32_t g, const uint64_t *wr, uint32_t kk) const { return tap(g, kk) ? wr[term(g, kk)] : 0; }
 };
 template <class KEY> inline GemmGroups<KEY> gemm_group(const DevConsts &hc, const GemmSwitches &sw, const GemmArith &ar, const KEY *keys, const uint64_t *W, uint32_t O, uint32_t K) {
     const auto groups = gemm_outputs_by_list(keys, O, K);
@@ -188,10 +194,14 @@ template <class KEY> inline void pack_gemm_int(const DevConsts &hc, const GemmGr
 }
 // fragments [g][p][mtile][kstep][lane][16]: lane l, byte t = digit p of the weight of output row 32 mtile + (l & 31) for term
 // 32 kstep + 16 (l >> 5) + t; zero for padded rows / terms / taps
+// Clipped + residual form (gr.res, gemm_residual_form; P = 2 here, the kernels' P = 1): plane 0 = c = clamp(w, -127, 127), plane 1 = r = w - c in the same
+// fragment layout, the terms in the permuted slot order of gr.rows, r = 0 behind K step kres[g]; then the table kres [G] of 32-bit words, which the kernels read
 template <class KEY> inline void pack_gemm_mfma(const DevConsts &hc, const GemmGroups<KEY> &gr, uint32_t P, std::vector<char> &wbytes) {
     const uint32_t mtiles = (gr.M + 31) / 32, ksteps = (gr.K + 31) / 32;
     const uint64_t t = hc.t.q;
-    wbytes.assign((size_t)gr.G * P * mtiles * ksteps * 1024, 0);
+    const size_t frags = (size_t)gr.G * P * mtiles * ksteps * 1024;
+    wbytes.assign(frags + (gr.res ? gr.G * sizeof(uint32_t) : 0), 0);
+    if (gr.res) memcpy(wbytes.data() + frags, gr.kres.data(), gr.G * sizeof(uint32_t));
     for (uint32_t g = 0; g < gr.G; g++) for (uint32_t m = 0; m < gr.M; m++) {
         const uint64_t *wr = gr.row(g, m);
         if (!wr) continue;
@@ -200,7 +210,9 @@ template <class KEY> inline void pack_gemm_mfma(const DevConsts &hc, const GemmG
             const uint64_t w = gr.weight(g, wr, kk);
             if (!w) continue;
             const int64_t sw = w >= hc.t_half ? -(int64_t)(t - w) : (int64_t)w;
-            const uint32_t rec = ((uint32_t)(sw + 0x808080) ^ 0x808080u);          // byte p = signed digit p
+            const int64_t cl = std::min<int64_t>(std::max<int64_t>(sw, -(int64_t)GEMM_RES_CLIP), (int64_t)GEMM_RES_CLIP);
+            const uint32_t rec = gr.res ? ((uint32_t)(uint8_t)(int8_t)cl | (uint32_t)(uint8_t)(int8_t)(sw - cl) << 8)
+                                        : ((uint32_t)(sw + 0x808080) ^ 0x808080u);   // byte p = signed digit p
             const uint32_t ks = kk / 32, half = (kk % 32) / 16, tt = kk % 16;
             for (uint32_t p = 0; p < P; p++)
                 wbytes[((((size_t)g * P + p) * mtiles + mt) * ksteps + ks) * 1024 + (size_t)(half * 32 + r) * 16 + tt] = (char)(uint8_t)(rec >> (8 * p));
@@ -214,10 +226,58 @@ template <class KEY> inline uint64_t gemm_row_sum_max(const DevConsts &hc, const
         const uint64_t *wr = gr.row(g, m);
         if (!wr) continue;
         uint64_t sum = 0;
-        for (uint32_t kk = 0; kk < gr.K; kk++) if (gr.tap(g, kk)) { sum += gemm_abs_weight(hc, wr[kk]); if (sum > stop) return stop + 1; }
+        for (uint32_t kk = 0; kk < gr.K; kk++) if (gr.tap(g, kk)) { sum += gemm_abs_weight(hc, wr[gr.term(g, kk)]); if (sum > stop) return stop + 1; }
         sum_max = std::max(sum_max, sum);
     }
     return sum_max;
+}
+// ---- the clipped + residual form of the matrix-core kernels (k_scalar_gemm_mfma<1, .., GemmResidual>, k_digit_gemm_mfma<1, .., GemmResidual>)
+// A trained dense layer has a handful of weights beyond +-127 (CryptoNets 845 -> 100: 48 of 84 500, in 31 input columns, max |w| = 165).  As base-256 digits they cost a
+// whole second plane - twice the matrix instructions, a second A fragment per step, one more diagonal of accumulators - that is zero almost everywhere.  Instead
+// w = c + r with c = clamp(w, -127, 127) and r = w - c, |r| <= 127 for |w| <= 254: two int8 planes of the SAME weight 256^0, whose products land in the same
+// accumulators, and the K slots of every gather row are permuted (index entries and weight fragments alike) so that the inputs with any r != 0 come first: only the
+// first kres[g] K steps hold a residual.  The kernels run kres[g] + K steps of the one-plane body (the r fragments of the first kres[g] K steps, then all c
+// fragments).  The sum over k is exact integer arithmetic: the order changes no word.
+// Gate: a matrix-core plan with 127 < max |w| <= 254 (max as gemm_weight_planes takes it); i32 head-room: a diagonal receives per term (c + r) x digit with
+// |c| + |r| = |w| and |digit| <= 128, so |acc| <= 128 R, R = gemm_row_sum_max; 128 R < 2^31 (the digit GEMM receives lo and hi products, (128 + 64) R < 2^31:
+// gemm_digit_form; with 3 K < 2^17 and |w| <= 254 both hold for every plan that gets here, R <= 11 097 260 - they are checked all the same); and the share of
+// residual steps.  The form is CORRECT up to kres[g] = K steps; it PAYS while (K steps + kres) one-plane steps take less time than K two-plane steps.  Measured per
+// step at K = 845 (profiles/gemm_residual_plane.md): one plane 6.52 / 6.21 / 3.40 us (Bsk form, y form, digit GEMM), two planes 7.67 / 6.95 / 5.26 us - break-even
+// at kres / K steps = 0.18 / 0.12 / 0.55.  A residual step repeats the gather, recode and LDS exchange of its K step, which is what these kernels wait for, not
+// only its matrix instructions.  So the gate is GEMM_RES_SHARE kres[g] <= K steps with GEMM_RES_SHARE = 8: at 1/8 the y form breaks even and the other two still
+// gain.  CN_GEMM_RESIDUAL, read whenever a plan is built (A/B; a plan that is cached - cn_gemm_plan_create's, the deferred queue's SgPlan - keeps the form it was
+// built in): 0 keeps the base-256 planes, 2 takes the form up to half the K steps (2 kres[g] <= K steps: for measuring where it stops paying, and for tests on
+// layers of a few K steps).  Permutes gr.rows in place and fills gr.src / gr.kres.
+static const uint32_t GEMM_RES_SHARE = 8;
+inline int gemm_residual_mode() { const char *e = getenv("CN_GEMM_RESIDUAL"); return e ? std::min(std::max(atoi(e), 0), 2) : 1; }
+template <class KEY> inline void gemm_residual_form(const DevConsts &hc, GemmGroups<KEY> &gr) {
+    const int mode = gemm_residual_mode();
+    if (!gr.mfma || !mode) return;
+    uint64_t amax = 0;
+    for (size_t x = 0; x < (size_t)gr.O * gr.K; x++) amax = std::max(amax, gemm_abs_weight(hc, gr.W[x]));
+    if (amax <= GEMM_RES_CLIP || amax > GEMM_RES_MAX) return;
+    const uint32_t K = gr.K, ksteps = (K + 31) / 32;
+    const uint64_t stop = ((1ull << 31) - 1) / 128;
+    if (gemm_row_sum_max(hc, gr, stop) > stop) return;
+    std::vector<uint32_t> src((size_t)gr.G * K), kres(gr.G);
+    for (uint32_t g = 0; g < gr.G; g++) {
+        std::vector<uint8_t> big(K, 0);
+        for (uint32_t m = 0; m < gr.M; m++) {
+            const uint64_t *wr = gr.row(g, m);
+            if (wr) for (uint32_t kk = 0; kk < K; kk++) if (gr.tap(g, kk) && gemm_abs_weight(hc, wr[kk]) > GEMM_RES_CLIP) big[kk] = 1;
+        }
+        uint32_t at = 0;
+        for (uint32_t kk = 0; kk < K; kk++) if (big[kk]) src[(size_t)g * K + at++] = kk;
+        kres[g] = (at + 31) / 32;
+        if ((mode == 2 ? 2 : GEMM_RES_SHARE) * kres[g] > ksteps) return;
+        for (uint32_t kk = 0; kk < K; kk++) if (!big[kk]) src[(size_t)g * K + at++] = kk;
+    }
+    std::vector<KEY> row(K);
+    for (uint32_t g = 0; g < gr.G; g++) {
+        for (uint32_t kk = 0; kk < K; kk++) row[kk] = gr.rows[(size_t)g * gr.Kp + src[(size_t)g * K + kk]];
+        std::copy(row.begin(), row.end(), gr.rows.begin() + (size_t)g * gr.Kp);
+    }
+    gr.res = true; gr.src.swap(src); gr.kres.swap(kres);
 }
 // One-limb form of the small-weight kernel: sum_k w_k x_k with x_k < q_max is an exact double as long as (sum_k |w_k| + 1) q_max <= 2^53 for every output row
 // (all partial sums are integers below 2^53; the + 1 leaves room for the recentred carry of the fold) - the words are then not split into limbs at all: ONE FMA
@@ -235,8 +295,9 @@ template <class KEY> inline void gemm_form_and_pack(const DevConsts &hc, const G
     const uint32_t M = gr.M;
     L.K = gr.K; L.Kp = gr.Kp; L.G = gr.G; L.M = M; L.small = ar.small; L.two = ar.two; L.lazy = ar.lazy; L.mfma = gr.mfma;
     if (gr.mfma) {
-        L.P = gemm_weight_planes(hc, gr.W, (size_t)gr.O * gr.K); L.mtiles = (M + 31) / 32; L.ksteps = (gr.K + 31) / 32;
-        pack_gemm_mfma(hc, gr, L.P, wbytes);
+        L.P = gr.res ? 1 : gemm_weight_planes(hc, gr.W, (size_t)gr.O * gr.K); L.mtiles = (M + 31) / 32; L.ksteps = (gr.K + 31) / 32;
+        L.res = gr.res;
+        pack_gemm_mfma(hc, gr, gr.res ? 2 : L.P, wbytes);
     } else if (ar.small) {
         L.MT = M >= 16 ? 20 : (M >= 8 ? 10 : (M >= 3 ? 5 : 1));
         pack_gemm_f64(hc, gr, L.MT, gemm_f64_rows(gr.K), wbytes);
@@ -252,6 +313,7 @@ template <class KEY> inline void gemm_form_and_pack(const DevConsts &hc, const G
 // 3 K < 2^17, rows of 32 K gather entries, fragments at off_w) and a digit splits into two int8 pieces: dg + 128 = (lo + 128) + 256 hi with hi <= 127 needs
 // 2^dbc - 1 + 128 < 2^15, dbc <= 14 (then hi <= 64).  i32 head-room: a diagonal receives per term one lo x w_p product (<= 128 * 128) and one hi x w_(p-1) product
 // (<= 64 * 128), K <= 43690 terms: 43690 * 24576 = 1 073 725 440 < 2^31.  N a multiple of 256: the column tiles of a slice are dealt to the 8 XCDs.
+// A plan in the clipped + residual form (L.res) adds c and r products of one term into the same diagonal: |acc| <= (128 + 64) sum_k |w_k|, which must stay below 2^31.
 // Otherwise the FP64 form k_digit_gemm with its own table of signed doubles (dbytes).
 // int32 words for S ("digit_i32"): the plan's digit bound sum_max (2^dbc - 1) is at most 2^31 - 1; anything larger keeps doubles
 template <class KEY> inline void gemm_digit_form(const DevConsts &hc, const GemmSwitches &sw, const GemmGroups<KEY> &gr, GemmLayout &L, std::vector<char> &dbytes) {
@@ -260,7 +322,7 @@ template <class KEY> inline void gemm_digit_form(const DevConsts &hc, const Gemm
     const uint64_t dmax = (1ull << hc.dbc) - 1, lim = std::min<uint64_t>((qmin - 1) / 2, (1ull << 52) - 1) / dmax;      // sum |w| <= lim
     const uint64_t sum_max = gemm_row_sum_max(hc, gr, lim);       // the plan's digit bound is sum_max (2^dbc - 1)
     if (sum_max > lim) return;
-    L.dig = true; L.sum_abs_w = sum_max; L.dig_mfma = L.mfma && sw.digit_mfma && hc.dbc <= 14 && !(hc.n & 255); L.dig_i32 = sw.digit_i32 && cn_digit_sum_fits_i32(sum_max, hc.dbc);
+    L.dig = true; L.sum_abs_w = sum_max; L.dig_mfma = L.mfma && sw.digit_mfma && hc.dbc <= 14 && !(hc.n & 255) && (!L.res || sum_max * (128 + 64) < (1ull << 31)); L.dig_i32 = sw.digit_i32 && cn_digit_sum_fits_i32(sum_max, hc.dbc);
     if (L.dig_mfma) return;
     L.dMT = digit_gemm_tile(L.M); L.dKw = digit_gemm_rows(L.K);
     pack_gemm_f64(hc, gr, L.dMT, L.dKw, dbytes);
@@ -304,7 +366,8 @@ inline GemmRefusal gemm_plan_indices(const DevConsts &hc, const GemmSwitches &sw
     const GemmArith ar = gemm_arith(hc, sw, gemm_weights_small(hc, W, (size_t)O * K));      // (pairing adds only zero weights: the class stands)
     std::vector<uint64_t> W2;
     if (sw.gemm_pair && ar.small && pair_gather_lists(O, K, gidx, W, W2)) W = W2.data();
-    const GemmGroups<int32_t> gr = gemm_group(hc, sw, ar, gidx.data(), W, O, K);
+    GemmGroups<int32_t> gr = gemm_group(hc, sw, ar, gidx.data(), W, O, K);
+    gemm_residual_form(hc, gr);
     std::vector<int32_t> hoidx(gr.member.size(), -1), hbidx(gr.member.size(), 0);           // output members relative to the output base, their bias polynomials
     for (size_t x = 0; x < gr.member.size(); x++) if (gr.member[x] != GEMM_NONE) { hoidx[x] = (int32_t)gr.member[x]; if (bias_idx) hbidx[x] = bias_idx[gr.member[x]]; }
     std::vector<char> wbytes, dbytes;
@@ -329,7 +392,8 @@ struct GemmAddressPlan {
 inline void gemm_plan_addresses(const DevConsts &hc, const GemmSwitches &sw, const uint64_t *A, const uint64_t *W, const uint64_t *out, const uint64_t *bias, uint32_t O, uint32_t K,
                                 bool rel_on, GemmAddressPlan &R) {
     const GemmArith ar = gemm_arith(hc, sw, gemm_weights_small(hc, W, (size_t)O * K));
-    const GemmGroups<uint64_t> gr = gemm_group(hc, sw, ar, A, W, O, K);
+    GemmGroups<uint64_t> gr = gemm_group(hc, sw, ar, A, W, O, K);
+    gemm_residual_form(hc, gr);
     std::vector<uint64_t> hoidx(gr.member.size(), 0), hbidx(gr.member.size(), 0);
     bool all_bias = true;
     for (size_t x = 0; x < gr.member.size(); x++) if (gr.member[x] != GEMM_NONE) {

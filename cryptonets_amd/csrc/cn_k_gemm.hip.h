@@ -364,17 +364,29 @@ DEV uint32_t byte_perm(uint32_t hi, uint32_t lo, uint32_t sel) { return __builti
 //             canonical words out, no bias - X_o = sum_k w_ok x_k mod b on the NTT-form tensor words of components 0 and 1;
 //   GEMM_Y:   the inputs are the lazy-FP64 hand-off words of the q-side tensor; the load path forms the floor's canonical y = [x t (q/q_j)^-1]_{q_j} (k_behz_floor_f64's
 //             own expression) and the diagonals are folded to the EXACT signed 64-bit integer Y_o = sum_k w_ok y_k (two's complement; no modular fold, no bias).
-// (A pack of at most one tag type: the ciphertext form keeps its name k_scalar_gemm_mfma<P, ABS>.)
+// (A pack of at most one form tag: the ciphertext form keeps its name k_scalar_gemm_mfma<P, ABS>.)
+// GemmResidual (a further tag, P = 1 only): the plan's clipped + residual form (gemm_residual_form, cn_gemm_plan.h).  Wf holds TWO int8 planes of the same weight
+// 256^0 - c = clamp(w, -127, 127) and r = w - c, laid out as the planes of P = 2 - and behind them the table kres [G]; the K slots are sorted so that r = 0 behind
+// K step kres[g].  The kernel runs kres[g] + ksteps steps of the ONE-plane body: step v < kres multiplies the r fragment of K step v, step v >= kres the c fragment
+// of K step v - kres, into the same accumulators (same weight; the integer sum does not care about the order).  Which plane and which K step a step reads is
+// scalar address arithmetic in the request lambdas: no second loop, no branch around loads in flight, no register beyond those of P = 1 (a second loop for the
+// residual phase, which would save the kres repeated B operands, doubled the live accumulators at its joins: the pre-floor forms spilled; the ciphertext form, 240
+// VGPRs without a spill, was not measured).  A residual step costs a whole step here, which is what the plan's gate on kres counts (GEMM_RES_SHARE, cn_gemm_plan.h).
+// Accumulators, fold and epilogue are those of P = 1: |acc| <= 128 sum_k |w_k| < 2^31 by the plan's gate.  kres = 0 is the P = 1 kernel step for step.
 enum { GEMM_CT = 0, GEMM_BSK = 1, GEMM_Y = 2 };
-struct GemmBskForm { static constexpr int form = GEMM_BSK; };
-struct GemmYForm { static constexpr int form = GEMM_Y; };
+struct GemmBskForm { static constexpr int form = GEMM_BSK; static constexpr bool res = false; };
+struct GemmYForm { static constexpr int form = GEMM_Y; static constexpr bool res = false; };
+struct GemmResidual { static constexpr int form = GEMM_CT; static constexpr bool res = true; };
 template <int P, bool ABS, class... FORM_>
 __global__ void __launch_bounds__(256, 2) k_scalar_gemm_mfma(const uint64_t *__restrict__ in, const void *__restrict__ idx_, const int8_t *__restrict__ Wf,
                                                              const void *__restrict__ out_idx_, const uint64_t *__restrict__ bias, const void *__restrict__ bias_idx_,
                                                              uint64_t *__restrict__ out, const DevConsts *__restrict__ C, uint32_t G, uint32_t M, uint32_t mtiles,
                                                              uint32_t ksteps, uint32_t obase, uint32_t polys, GemmUnits U) {
     constexpr int FORM = (GEMM_CT + ... + FORM_::form);
-    static_assert(sizeof...(FORM_) <= 1 && (FORM == GEMM_CT || !ABS), "the pre-floor forms use relative addressing");
+    constexpr bool RES = (false || ... || FORM_::res);
+    constexpr int PW = RES ? 2 : P;                                // weight planes in Wf
+    static_assert(sizeof...(FORM_) <= (RES ? 2 : 1) && FORM <= GEMM_Y && (FORM == GEMM_CT || !ABS), "the pre-floor forms use relative addressing");
+    static_assert(!RES || P == 1, "clipped + residual weights: one plane and its residual");
     typedef typename GemmTab<ABS>::T TT;
     const TT *idx = (const TT *)idx_, *out_idx = (const TT *)out_idx_, *bias_idx = (const TT *)bias_idx_;
     constexpr int ND = FORM == GEMM_BSK ? 7 : 6, D = ND + P - 1, NB = GEMM_MFMA_DEPTH + 1;
@@ -395,7 +407,7 @@ __global__ void __launch_bounds__(256, 2) k_scalar_gemm_mfma(const uint64_t *__r
     const size_t iu = U.in ? U.in : ctw, ou = U.out ? U.out : ctw, bu = U.bias ? U.bias : n;
     const uint32_t Kp = ksteps * 32;
     const TT *gi = idx + (size_t)g * Kp + 4 * wave;            // + 32 ks + 16 half + u
-    const int8_t *wf = Wf + ((((size_t)g * P) * mtiles + (active ? mt : 0)) * ksteps) * 1024 + (size_t)lane * 16;       // + (p * mtiles * ksteps + ks) * 1024
+    const int8_t *wf = Wf + ((((size_t)g * PW) * mtiles + (active ? mt : 0)) * ksteps) * 1024 + (size_t)lane * 16;      // + (p * mtiles * ksteps + ks) * 1024
     v16i_t acc[D];
 #pragma unroll
     for (int d = 0; d < D; d++)
@@ -405,8 +417,15 @@ __global__ void __launch_bounds__(256, 2) k_scalar_gemm_mfma(const uint64_t *__r
     // Requests behind the last step are NOT skipped but repeat the last step (a few words re-read from L2): with a branch around the loads the compiler's wait
     // counts at the join assume the path WITHOUT them - "at most 5 younger loads" where 11 are in flight - and every step drained the sets requested ahead.
     const uint32_t klast = ksteps - 1;
+    // clipped + residual form: step v of vsteps = kres + ksteps reads plane r of K step v (v < kres) or plane c of K step v - kres; `fragment`: its A fragment, in
+    // units of 1024 bytes from wf.  Otherwise step v is K step v
+    uint32_t kres = 0;
+    if constexpr (RES) kres = reinterpret_cast<const uint32_t *>(Wf + (size_t)G * PW * mtiles * ksteps * 1024)[g];
+    const uint32_t vsteps = RES ? ksteps + kres : ksteps;
+    auto kstep = [&](uint32_t v) { if constexpr (RES) { const uint32_t vv = min(v, vsteps - 1); return vv < kres ? vv : vv - kres; } else return min(v, klast); };
+    auto fragment = [&](uint32_t v) { if constexpr (RES) return min(v, vsteps - 1) < kres ? mtiles * ksteps + kstep(v) : kstep(v); else return min(v, klast); };
     auto load_idx = [&](TT (&s)[8], uint32_t ks) {              // table entries of slots 4 wave .. + 3 (lanes 0..31) and 16 + 4 wave .. + 3 (lanes 32..63): scalar loads
-        const TT *t = gi + (size_t)min(ks, klast) * 32;
+        const TT *t = gi + (size_t)kstep(ks) * 32;
 #pragma unroll
         for (int u = 0; u < 4; u++) { s[u] = t[u]; s[4 + u] = t[16 + u]; }
     };
@@ -427,7 +446,7 @@ __global__ void __launch_bounds__(256, 2) k_scalar_gemm_mfma(const uint64_t *__r
     };
     auto load_a = [&](v4i_t (&af)[P], uint32_t ks) {
 #pragma unroll
-        for (int p = 0; p < P; p++) af[p] = *reinterpret_cast<const v4i_t *>(wf + ((size_t)p * mtiles * ksteps + min(ks, klast)) * 1024);
+        for (int p = 0; p < P; p++) af[p] = *reinterpret_cast<const v4i_t *>(wf + ((size_t)p * mtiles * ksteps + fragment(ks)) * 1024);
     };
     // x / af: NB register sets in a ring - set (ks mod NB) holds step ks, requested GEMM_MFMA_DEPTH steps ahead; `nidx` = the table entries of the step whose
     // inputs are requested next (asked for one step before they are needed; refilled right after use)
@@ -480,13 +499,13 @@ __global__ void __launch_bounds__(256, 2) k_scalar_gemm_mfma(const uint64_t *__r
     // the set that step ks refills is the one step ks - 1 consumed
     // (for the same reason the loop has ONE exit, at its end: whole turns of the ring, then the ksteps mod NB steps left over)
     uint32_t ks = 0;
-    for (; ks + NB <= ksteps; ks += NB) {
+    for (; ks + NB <= vsteps; ks += NB) {
 #pragma unroll
         for (int s = 0; s < NB; s++) step(xs[s], afs[s], xs[(s + GEMM_MFMA_DEPTH) % NB], afs[(s + GEMM_MFMA_DEPTH) % NB], ks + s, frag[s]);
     }
 #pragma unroll
     for (int s = 0; s < NB - 1; s++)
-        if (ks + s < ksteps) step(xs[s], afs[s], xs[(s + GEMM_MFMA_DEPTH) % NB], afs[(s + GEMM_MFMA_DEPTH) % NB], ks + s, frag[s]);
+        if (ks + s < vsteps) step(xs[s], afs[s], xs[(s + GEMM_MFMA_DEPTH) % NB], afs[(s + GEMM_MFMA_DEPTH) % NB], ks + s, frag[s]);
     if (!active) return;
     if constexpr (FORM == GEMM_Y) {
         // ---- the exact integer: sum_d acc_d 256^d in two's complement (|Y| < 2^63 by the plan's gate - cn_prefloor_bound_ok, cn_policy.h - so the wrapped sum is Y)
@@ -547,6 +566,8 @@ __global__ void __launch_bounds__(256, 2) k_scalar_gemm_mfma(const uint64_t *__r
 // k_digit_gemm<MT, DG, int32_t>: the same exact integer in half the bytes, read by the KsDigits<AR, int32_t> key switch.  (A parameter pack: the double forms keep their names.)
 template <class... E> struct DigitWord { typedef double type; };
 template <> struct DigitWord<int32_t> { typedef int32_t type; };
+template <> struct DigitWord<GemmResidual> { typedef double type; };                  // (k_digit_gemm_mfma alone: the plan's clipped + residual weights)
+template <> struct DigitWord<int32_t, GemmResidual> { typedef int32_t type; };
 template <int MT, int DG, class... E>
 __global__ void __launch_bounds__(256) k_digit_gemm(const uint64_t *__restrict__ in, size_t in_unit, const int32_t *__restrict__ idx, const double *__restrict__ Wd,
                                                     const int32_t *__restrict__ out_idx, typename DigitWord<E...>::type *__restrict__ S, const DevConsts *__restrict__ C, uint32_t G, uint32_t M,
@@ -640,11 +661,20 @@ __global__ void __launch_bounds__(256) k_digit_gemm(const uint64_t *__restrict__
 // skip the absent ones (rl_dig), a group without any digit leaves at once.
 // int32 words (k_digit_gemm_mfma<P, DG, int32_t>): |S| <= 2^31 - 1, so the fold runs in 32-bit integers - exact modulo 2^32 whatever the partial sums do - and
 // the word is stored as it is: no conversion, half the bytes (an accumulator register then stores 128 B per half-wave).
+// Clipped + residual weights (k_digit_gemm_mfma<1, DG, .., GemmResidual>; gemm_residual_form, cn_gemm_plan.h): as in k_scalar_gemm_mfma the kernel runs kres[g] + ksteps
+// steps of the one-plane body - the r fragments of the first kres[g] K steps, then the c fragments of all of them - into the SAME two diagonals (r has the weight 256^0
+// of c).  A diagonal then receives (c + r) lo or (c + r) hi with |c| + |r| = |w|: |acc_j| <= (128 + 64) sum_k |w_k| < 2^31 by the plan's gate (gemm_digit_form).
+// With 32 accumulator registers per digit instead of 48 this form takes DG = DIGIT_GEMM_RES_GROUP = 5 digits per workgroup - every digit of a CryptoNets limb: the slice
+// is read once and the B operand built once instead of twice (207 VGPRs, two workgroups per CU; 95 us against 109 us with DG = 3 at 146 VGPRs, profiles/gemm_residual_plane.md).
+constexpr int DIGIT_GEMM_RES_GROUP = 5;
 template <int P, int DG, class... E>
 __global__ void __launch_bounds__(256, 2) k_digit_gemm_mfma(const uint64_t *__restrict__ in, size_t in_unit, const int32_t *__restrict__ idx, const int8_t *__restrict__ Wf,
                                                             const int32_t *__restrict__ out_idx, typename DigitWord<E...>::type *__restrict__ S, const DevConsts *__restrict__ C, uint32_t G,
                                                             uint32_t M, uint32_t mtiles, uint32_t ksteps, uint32_t ndg) {
     constexpr int NP = 2 * DG, D = P + 1, NB = GEMM_MFMA_DEPTH + 1;
+    constexpr bool RES = (false || ... || std::is_same<E, GemmResidual>::value);
+    constexpr int PW = RES ? 2 : P;                                // weight planes in Wf
+    static_assert(!RES || P == 1, "clipped + residual weights: one plane and its residual");
     __shared__ __align__(16) uint32_t frag[NB][NP][64][4];         // [buffer][digit, piece][lane][slot group q]
     const uint32_t n = C->n, k = C->k, ctiles = n >> 5;            // n is a multiple of 256 (launcher)
     const uint32_t lane = threadIdx.x & 63, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), half = lane >> 5, col = lane & 31;
@@ -668,7 +698,7 @@ __global__ void __launch_bounds__(256, 2) k_digit_gemm_mfma(const uint64_t *__re
     const size_t e = (size_t)l * n + (size_t)ctile * 32 + col;
     const uint32_t Kp = ksteps * 32;
     const int32_t *gi = idx + (size_t)g * Kp + 4 * wave;       // + 32 ks + 16 half + u
-    const int8_t *wf = Wf + ((((size_t)g * P) * mtiles + (active ? mt : 0)) * ksteps) * 1024 + (size_t)lane * 16;       // + (p * mtiles * ksteps + ks) * 1024
+    const int8_t *wf = Wf + ((((size_t)g * PW) * mtiles + (active ? mt : 0)) * ksteps) * 1024 + (size_t)lane * 16;      // + (p * mtiles * ksteps + ks) * 1024
     v16i_t acc[DG][D];
 #pragma unroll
     for (int d = 0; d < DG; d++)
@@ -678,8 +708,14 @@ __global__ void __launch_bounds__(256, 2) k_digit_gemm_mfma(const uint64_t *__re
             for (int r = 0; r < 16; r++) acc[d][j][r] = 0;
     // requests behind the last step repeat the last step, as in k_scalar_gemm_mfma (no branch around loads in flight)
     const uint32_t klast = ksteps - 1;
+    // clipped + residual form: step v of vsteps = kres + ksteps reads plane r of K step v (v < kres) or plane c of K step v - kres (k_scalar_gemm_mfma)
+    uint32_t kres = 0;
+    if constexpr (RES) kres = reinterpret_cast<const uint32_t *>(Wf + (size_t)G * PW * mtiles * ksteps * 1024)[g];
+    const uint32_t vsteps = RES ? ksteps + kres : ksteps;
+    auto kstep = [&](uint32_t v) { if constexpr (RES) { const uint32_t vv = min(v, vsteps - 1); return vv < kres ? vv : vv - kres; } else return min(v, klast); };
+    auto fragment = [&](uint32_t v) { if constexpr (RES) return min(v, vsteps - 1) < kres ? mtiles * ksteps + kstep(v) : kstep(v); else return min(v, klast); };
     auto load_idx = [&](int32_t (&s)[8], uint32_t ks) {
-        const int32_t *t = gi + (size_t)min(ks, klast) * 32;
+        const int32_t *t = gi + (size_t)kstep(ks) * 32;
 #pragma unroll
         for (int u = 0; u < 4; u++) { s[u] = t[u]; s[4 + u] = t[16 + u]; }
     };
@@ -693,7 +729,7 @@ __global__ void __launch_bounds__(256, 2) k_digit_gemm_mfma(const uint64_t *__re
     };
     auto load_a = [&](v4i_t (&af)[P], uint32_t ks) {
 #pragma unroll
-        for (int p = 0; p < P; p++) af[p] = *reinterpret_cast<const v4i_t *>(wf + ((size_t)p * mtiles * ksteps + min(ks, klast)) * 1024);
+        for (int p = 0; p < P; p++) af[p] = *reinterpret_cast<const v4i_t *>(wf + ((size_t)p * mtiles * ksteps + fragment(ks)) * 1024);
     };
     uint64_t xs[NB][4];
     v4i_t afs[NB][P];
@@ -728,13 +764,13 @@ __global__ void __launch_bounds__(256, 2) k_digit_gemm_mfma(const uint64_t *__re
         }
     };
     uint32_t ks = 0;
-    for (; ks + NB <= ksteps; ks += NB) {
+    for (; ks + NB <= vsteps; ks += NB) {
 #pragma unroll
         for (int s = 0; s < NB; s++) step(xs[s], afs[s], xs[(s + GEMM_MFMA_DEPTH) % NB], afs[(s + GEMM_MFMA_DEPTH) % NB], ks + s, frag[s]);
     }
 #pragma unroll
     for (int s = 0; s < NB - 1; s++)
-        if (ks + s < ksteps) step(xs[s], afs[s], xs[(s + GEMM_MFMA_DEPTH) % NB], afs[(s + GEMM_MFMA_DEPTH) % NB], ks + s, frag[s]);
+        if (ks + s < vsteps) step(xs[s], afs[s], xs[(s + GEMM_MFMA_DEPTH) % NB], afs[(s + GEMM_MFMA_DEPTH) % NB], ks + s, frag[s]);
     if (!active) return;
     // ---- fold the diagonals of every digit to one exact double and store it: the table entries of the 16 rows first (one round trip)
     const uint32_t tot = C->rl_tot, olast = G * M - 1;

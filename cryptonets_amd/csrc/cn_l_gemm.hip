@@ -50,26 +50,28 @@ template <bool ABS> static int launch(cn_ctx *c, const GemmLaunch &g) {
 }
 int cn_l_gemm(cn_ctx *c, const GemmLaunch &g) { return g.abs ? launch<true>(c, g) : launch<false>(c, g); }
 
-template <int P, bool ABS> static void launch_mfma(cn_ctx *c, const GemmLaunch &g) {
+// RES...: GemmResidual for a plan in the clipped + residual form (GemmLaunch::res, P = 1), else nothing
+template <int P, bool ABS, class... RES> static void launch_mfma(cn_ctx *c, const GemmLaunch &g) {
     const uint32_t mgroups = (g.mtiles + 3) / 4;
     if constexpr (!ABS && P <= 2) {                            // the pre-floor forms of cn_square_gemm (GemmLaunch::form): Bsk limbs / exact integer sums of canonical y
         if (g.form) {                                          // (one or two weight planes: with three the y form spills - square_gemm_prefloor_ok, cn_mul_plan.h)
             const size_t pblocks = (size_t)g.G * mgroups * g.polys * (g.form == GEMM_BSK ? c->hc.kb : c->hc.k) * (c->hc.n / 32);
-            if (g.form == GEMM_BSK) hipLaunchKernelGGL((k_scalar_gemm_mfma<P, false, GemmBskForm>), dim3((uint32_t)pblocks), dim3(256), 0, c->stream, g.in, g.idx, (const int8_t *)g.W, g.oidx,
+            if (g.form == GEMM_BSK) hipLaunchKernelGGL((k_scalar_gemm_mfma<P, false, GemmBskForm, RES...>), dim3((uint32_t)pblocks), dim3(256), 0, c->stream, g.in, g.idx, (const int8_t *)g.W, g.oidx,
                                                        nullptr, nullptr, g.out, c->dc, g.G, g.M, g.mtiles, g.ksteps, g.obase, g.polys, GemmUnits{g.in_unit, g.out_unit, 0u});
-            else hipLaunchKernelGGL((k_scalar_gemm_mfma<P, false, GemmYForm>), dim3((uint32_t)pblocks), dim3(256), 0, c->stream, g.in, g.idx, (const int8_t *)g.W, g.oidx,
+            else hipLaunchKernelGGL((k_scalar_gemm_mfma<P, false, GemmYForm, RES...>), dim3((uint32_t)pblocks), dim3(256), 0, c->stream, g.in, g.idx, (const int8_t *)g.W, g.oidx,
                                     nullptr, nullptr, g.out, c->dc, g.G, g.M, g.mtiles, g.ksteps, g.obase, g.polys, GemmUnits{g.in_unit, g.out_unit, 0u});
             return;
         }
     }
     const size_t blocks = (size_t)g.G * mgroups * g.polys * c->hc.k * (c->hc.n / 32);
-    hipLaunchKernelGGL((k_scalar_gemm_mfma<P, ABS>), dim3((uint32_t)blocks), dim3(256), 0, c->stream, g.in, g.idx, (const int8_t *)g.W, g.oidx, g.bias, g.bidx, g.out,
+    hipLaunchKernelGGL((k_scalar_gemm_mfma<P, ABS, RES...>), dim3((uint32_t)blocks), dim3(256), 0, c->stream, g.in, g.idx, (const int8_t *)g.W, g.oidx, g.bias, g.bidx, g.out,
                        c->dc, g.G, g.M, g.mtiles, g.ksteps, g.obase, g.polys, GemmUnits{g.in_unit, g.out_unit, g.bias_unit});
 }
 template <bool ABS> static int launch_mfma_p(cn_ctx *c, const GemmLaunch &g) {
     if (g.form && (ABS || g.P > 2 || g.form > GEMM_Y || !g.in_unit || !g.out_unit)) return cn_fail(CN_ERR_ARG, "internal: pre-floor GEMM form %u", g.form);
+    if (g.res && g.P != 1) return cn_fail(CN_ERR_ARG, "internal: residual weights with %u planes", g.P);
     switch (g.P) {
-        case 1: launch_mfma<1, ABS>(c, g); break;
+        case 1: if (g.res) launch_mfma<1, ABS, GemmResidual>(c, g); else launch_mfma<1, ABS>(c, g); break;
         case 2: launch_mfma<2, ABS>(c, g); break;
         case 3: launch_mfma<3, ABS>(c, g); break;
         default: return cn_fail(CN_ERR_ARG, "internal: %u weight digit planes", g.P);
@@ -89,19 +91,20 @@ template <int MT> static void launch_digit(cn_ctx *c, const DigitGemmLaunch &g, 
     else hipLaunchKernelGGL((k_digit_gemm<MT, 5>), dim3((uint32_t)blocks), dim3(256), 0, c->stream, g.in, g.in_unit, (const int32_t *)g.idx, (const double *)g.W,
                             (const int32_t *)g.oidx, (double *)g.S, c->dc, g.G, g.M, g.K, mtiles, g.Kp, g.Kw, ndg);
 }
-// matrix-core form: DG = digit_gemm_mfma_group(P) digits per workgroup; the digit groups of a (column tile, limb) take block ids 8 apart (k_digit_gemm_mfma)
-template <int P, int DG> static void launch_digit_mfma(cn_ctx *c, const DigitGemmLaunch &g, uint32_t ndg, size_t blocks) {
-    if (g.i32) hipLaunchKernelGGL((k_digit_gemm_mfma<P, DG, int32_t>), dim3((uint32_t)blocks), dim3(256), 0, c->stream, g.in, g.in_unit, (const int32_t *)g.idx, (const int8_t *)g.W,
+// matrix-core form: DG = digit_gemm_mfma_group(P) digits per workgroup (DIGIT_GEMM_RES_GROUP for a plan in the clipped + residual form, g.res); the digit groups of a (column tile, limb) take block ids 8 apart (k_digit_gemm_mfma)
+template <int P, int DG, class... RES> static void launch_digit_mfma(cn_ctx *c, const DigitGemmLaunch &g, uint32_t ndg, size_t blocks) {
+    if (g.i32) hipLaunchKernelGGL((k_digit_gemm_mfma<P, DG, int32_t, RES...>), dim3((uint32_t)blocks), dim3(256), 0, c->stream, g.in, g.in_unit, (const int32_t *)g.idx, (const int8_t *)g.W,
                                   (const int32_t *)g.oidx, (int32_t *)g.S, c->dc, g.G, g.M, g.mtiles, g.ksteps, ndg);
-    else hipLaunchKernelGGL((k_digit_gemm_mfma<P, DG>), dim3((uint32_t)blocks), dim3(256), 0, c->stream, g.in, g.in_unit, (const int32_t *)g.idx, (const int8_t *)g.W,
+    else hipLaunchKernelGGL((k_digit_gemm_mfma<P, DG, RES...>), dim3((uint32_t)blocks), dim3(256), 0, c->stream, g.in, g.in_unit, (const int32_t *)g.idx, (const int8_t *)g.W,
                             (const int32_t *)g.oidx, (double *)g.S, c->dc, g.G, g.M, g.mtiles, g.ksteps, ndg);
 }
 static int digit_gemm_mfma(cn_ctx *c, const DigitGemmLaunch &g, uint32_t ndmax) {
-    const uint32_t DG = digit_gemm_mfma_group(g.P), ndg = (ndmax + DG - 1) / DG, mgroups = (g.mtiles + 3) / 4;
+    if (g.res && g.P != 1) return cn_fail(CN_ERR_ARG, "internal: residual weights with %u planes", g.P);
+    const uint32_t DG = g.res ? DIGIT_GEMM_RES_GROUP : digit_gemm_mfma_group(g.P), ndg = (ndmax + DG - 1) / DG, mgroups = (g.mtiles + 3) / 4;
     const uint64_t blocks = (uint64_t)g.G * mgroups * c->hc.k * (c->hc.n / 32) * ndg;
     if ((c->hc.n & 255) || !g.ksteps || blocks >= (1ull << 31)) return cn_fail(CN_ERR_ARG, "internal: digit GEMM grid");
     switch (g.P) {
-        case 1: launch_digit_mfma<1, 3>(c, g, ndg, blocks); break;
+        case 1: if (g.res) launch_digit_mfma<1, DIGIT_GEMM_RES_GROUP, GemmResidual>(c, g, ndg, blocks); else launch_digit_mfma<1, 3>(c, g, ndg, blocks); break;
         case 2: launch_digit_mfma<2, 3>(c, g, ndg, blocks); break;
         case 3: launch_digit_mfma<3, 2>(c, g, ndg, blocks); break;
         default: return cn_fail(CN_ERR_ARG, "internal: %u weight digit planes", g.P);

@@ -59,6 +59,9 @@ struct GemmLayout {
     uint32_t K = 0, Kp = 0, G = 0, M = 0, MT = 0, lazy = 0;
     bool small = false, two = false, one = false, mfma = false;
     uint32_t P = 0, mtiles = 0, ksteps = 0;  // matrix-core form: weight digit planes, 32-row output tiles, 32-term steps
+    // res: the clipped + residual form (gemm_residual_form, cn_gemm_plan.h) - P = 1, the fragments hold two planes c and r of weight 256^0 and the table kres [G] behind
+    // them (the leading K steps with a residual, per gather list), the K slots of the gather rows are permuted
+    bool res = false;
     // cn_square_gemm: the layer may run on the digits of the unrelinearized products (square_gemm_fused_ok) - signed weights [G][mtiles][dKw][dMT] at off_dw
     // dig_mfma: the digit GEMM runs on the matrix cores from the fragments at off_w (no table at off_dw)
     // dig_i32: every digit sum fits a signed 32-bit word (cn_digit_sum_fits_i32 of the largest row, "digit_i32" on): S is stored and read as int32 words

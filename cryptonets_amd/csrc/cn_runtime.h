@@ -297,6 +297,7 @@ struct GemmLaunch {
     uint32_t polys = 2;                              // ciphertext size of inputs and outputs (3: unrelinearized products)
     uint32_t order = 0;                              // workgroup order of the VALU kernels: 0 group-major, 1 slice-major (gemm_block_coords)
     bool one = false;                                // k_scalar_gemm_f64<MT, 1, 0>: the words are not split (gemm_one_limb)
+    bool res = false;                                // matrix-core kernel, P = 1: the clipped + residual form (GemmLayout::res) - the <.., GemmResidual> instantiations
     uint32_t in_unit = 0, out_unit = 0, bias_unit = 0;   // words per index unit of the table-driven kernels; 0 = one ciphertext / one plaintext (plans).  Deferred calls: 32 (256 B offsets from the lowest address)
     uint32_t form = 0;                               // matrix-core kernel, the pre-floor form of cn_square_gemm: 1 = Bsk limbs (7 digits, mod b), 2 = lazy q words -> canonical y -> exact int64 sums (cn_k_gemm.hip.h)
     // the launch of a planned layout (GemmLayout, cn_policy.h) whose image is at `tables`: weights, output members and - until inputs() / bias_at() name others -
@@ -304,7 +305,7 @@ struct GemmLaunch {
     static GemmLaunch of(const GemmLayout &L, const char *tables, uint32_t order) {
         return {.small = L.small, .two = L.two, .abs = false, .MT = L.MT, .in = nullptr, .idx = tables, .W = tables + L.off_w, .oidx = tables + L.off_oidx, .bias = nullptr,
                 .bidx = tables + L.off_bidx, .out = nullptr, .G = L.G, .M = L.M, .K = L.K, .lazy = L.lazy, .Kp = L.Kp, .obase = 0, .P = L.P, .mtiles = L.mtiles, .ksteps = L.ksteps,
-                .order = order, .one = L.one};
+                .order = order, .one = L.one, .res = L.res};
     }
     GemmLaunch &inputs(const uint64_t *base, uint32_t unit, uint32_t polys_) { in = base; in_unit = unit; polys = polys_; return *this; }
     GemmLaunch &gather(const void *rows) { idx = rows; return *this; }                             // gather rows made per call (the plan's own: at `tables`)
@@ -323,11 +324,12 @@ struct DigitGemmLaunch {
     uint32_t G, M, K, Kp, Kw, MT;
     bool mfma = false; uint32_t P = 0, mtiles = 0, ksteps = 0;
     bool i32 = false;
+    bool res = false;                                // mfma, P = 1: the clipped + residual form (GemmLayout::res)
     // the digit GEMM of a plan that has one (GemmLayout::dig): component 2 of the products at `in`, in_unit words apart, gathered through idx
     static DigitGemmLaunch of(const GemmLayout &L, const char *tables, const uint64_t *in, size_t in_unit, const void *idx, void *S) {
         return {.in = in, .in_unit = in_unit, .idx = idx, .W = tables + (L.dig_mfma ? L.off_w : L.off_dw), .oidx = tables + L.off_oidx, .S = S, .G = L.G, .M = L.M, .K = L.K,
                 .Kp = L.Kp, .Kw = L.dKw, .MT = L.dMT, .mfma = L.dig_mfma, .P = L.dig_mfma ? L.P : 0, .mtiles = L.dig_mfma ? L.mtiles : 0, .ksteps = L.dig_mfma ? L.ksteps : 0,
-                .i32 = L.dig_i32};
+                .i32 = L.dig_i32, .res = L.dig_mfma && L.res};
     }
 };
 inline uint32_t digit_gemm_mfma_group(uint32_t P) { return P <= 2 ? 3u : 2u; }     // digits per workgroup: 16 (P + 1) DG accumulator registers per wave

@@ -204,7 +204,9 @@ int cn_mod_switch(cn_ctx *src, cn_handle in, uint32_t ii, uint32_t count, cn_ctx
  * Environment switches read once per process (A/B measurements, all default to the measured best): CN_STREAM_PROBE=0 (no hardware-queue selection),
  * CN_TABLES_ZERO_COPY=0 (small operand tables are copied to the device instead of read from the pinned ring), CN_KS_WIDE_MAX / CN_KS_DIGIT_MAX ((ciphertext,
  * limb) blocks up to which a key switch runs as two launches: 160 / with one workgroup per digit: 10), CN_GEMM_ONE_LIMB=0 (the small-weight GEMM kernel
- * keeps its two-limb form), CN_DEFER_MERGE_GEMM=0 (deferred scalar products of one flush keep their levels: one launch per level instead of one per term
+ * keeps its two-limb form), CN_GEMM_RESIDUAL=0 (read whenever a scalar GEMM is planned, not once - a plan that is kept, cn_gemm_plan_create's or a cached plan of the
+ * deferred queue, stays in the form it was built in: matrix-core plans with 127 < max |w| <= 254 keep their two base-256 weight planes instead of one clipped plane and
+ * a sparse residual; =2: the residual form up to half the K steps instead of one in eight), CN_DEFER_MERGE_GEMM=0 (deferred scalar products of one flush keep their levels: one launch per level instead of one per term
  * count), CN_PIN_RING_MIB (size of the pinned upload ring, 32 MiB), CN_DEFER_TRACE=1 (one stderr line per flushed queue level: calls per kind,
  * launches; one per flush that holds squarings back, runs a dense layer on them or relinearises them after all), CN_LOCK_GRACE_NS / CN_LOCK_COMBINE (the two context-lock experiments that are kept but off, cn_host.cpp). */
 int cn_set_option(cn_ctx *ctx, const char *name, int value);
