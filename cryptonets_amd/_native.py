@@ -182,6 +182,8 @@ SIGNATURES = {
     "cn_rotate_rows_many": (C.c_int, [_CTX, _H, C.POINTER(C.c_uint32), C.POINTER(C.c_int), _u32, _H, C.POINTER(C.c_uint32)]),
     "cn_apply_galois_hoisted": (C.c_int, [_CTX, _H, _u32, U64P, _u32, _H, C.POINTER(C.c_uint32)]),
     "cn_rotate_rows_hoisted": (C.c_int, [_CTX, _H, _u32, C.POINTER(C.c_int), _u32, _H, C.POINTER(C.c_uint32)]),
+    "cn_apply_galois_sum": (C.c_int, [_CTX, _H, C.POINTER(C.c_uint32), U64P, C.POINTER(C.c_uint32), _u32, _H, _u32]),
+    "cn_rotate_rows_sum": (C.c_int, [_CTX, _H, C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.POINTER(C.c_uint32), _u32, _H, _u32]),
     "cn_rotate_columns": (C.c_int, [_CTX, _H, _u32, _H, _u32, _u32]),
     "cn_rotate_rows_add": (C.c_int, [_CTX, _H, _u32, C.c_int, _H, _u32, _H, _u32, _u32]),
     "cn_rotate_columns_add": (C.c_int, [_CTX, _H, _u32, _H, _u32, _H, _u32, _u32]),
@@ -763,6 +765,26 @@ class Context:
         o = np.ascontiguousarray(ois, dtype=np.uint32)
         assert len(e) == len(o)
         self._chk(self.L.cn_apply_galois_hoisted(self._h, src, ii, e.ctypes.data_as(U64P), len(e), out, o.ctypes.data_as(C.POINTER(C.c_uint32))))
+
+    def rotate_rows_sum(self, src, iis, steps, grp_off, out, oi):
+        """out[oi + g] = the sum over e in [grp_off[g], grp_off[g + 1]) of RotateRows(src[iis[e]], steps[e]) (step 0: a plain addend): rotations of DIFFERENT
+        ciphertexts under one inverse transform per output limb.  The words of rotate_rows per term followed by add_many; a step without its own key runs its
+        non-adjacent-form hops"""
+        i = np.ascontiguousarray(iis, dtype=np.uint32)
+        st = np.ascontiguousarray(steps, dtype=np.int32)
+        g = np.ascontiguousarray(grp_off, dtype=np.uint32)
+        assert len(st) == len(i) and (len(g) < 2 or int(g[-1]) == len(i))
+        self._chk(self.L.cn_rotate_rows_sum(self._h, src, i.ctypes.data_as(C.POINTER(C.c_uint32)), st.ctypes.data_as(C.POINTER(C.c_int)),
+                                            g.ctypes.data_as(C.POINTER(C.c_uint32)), max(len(g), 1) - 1, out, oi))
+
+    def apply_galois_sum(self, src, iis, elts, grp_off, out, oi):
+        """the same by Galois elements (1: a plain addend), every element with its own key"""
+        i = np.ascontiguousarray(iis, dtype=np.uint32)
+        e = np.ascontiguousarray(elts, dtype=np.uint64)
+        g = np.ascontiguousarray(grp_off, dtype=np.uint32)
+        assert len(e) == len(i) and (len(g) < 2 or int(g[-1]) == len(i))
+        self._chk(self.L.cn_apply_galois_sum(self._h, src, i.ctypes.data_as(C.POINTER(C.c_uint32)), e.ctypes.data_as(U64P), g.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                             max(len(g), 1) - 1, out, oi))
 
     def rotate_rows_add(self, src, ii, steps, acc, ai, out, oi, count=1):
         """out = acc + RotateRows(src, steps) (fused rotate-and-add of SumAllSlots)"""

@@ -347,6 +347,7 @@ static const ValueSpec kValues[] = {
     {"sg_prefloor_min_k", [](cn_ctx *) { return (int)SG_PREFLOOR_MIN_K; }, nullptr},            // smallest K that takes the pre-floor form under "sg_prefloor" = 1
     {"mul_sum_groups", [](cn_ctx *c) { return (int)c->ms_groups; }, nullptr},                   // output groups of the last cn_mul_relin_sum (0: the literal sequence)
     {"ks_hoisted", [](cn_ctx *c) { return sat(c->ks_hoisted); }, nullptr},                     // hoisted-rotation calls that launched (cn_rotate_rows_hoisted, cn_apply_galois_hoisted)
+    {"ks_summed", [](cn_ctx *c) { return sat(c->ks_summed); }, nullptr},                       // summed-rotation calls that launched the fused form (cn_rotate_rows_sum, cn_apply_galois_sum)
     {"mul_sum_min_k", [](cn_ctx *) { return (int)MUL_SUM_MIN_K; }, nullptr},                    // smallest K that takes the one-key-switch form
     {"defer_pending_products", [](cn_ctx *c) { return (int)c->dq->sq->out.size(); }, nullptr},  // squarings whose relinearisation is held back right now
     {"scratch_mib", [](cn_ctx *c) { return sat((c->scap + (1u << 20) - 1) >> 20); }, nullptr},  // size of the scratch arena right now (it only grows)

@@ -753,11 +753,17 @@ int rotate_rows_impl(cn_ctx *ctx, CtSpan in, int steps, CtSpan out) {
     } else if (out.d != in.d) HIPCHK(hipMemcpyAsync(out.d, in.d, count * ctx->ctw2 * 8, hipMemcpyDeviceToDevice, ctx->stream));
     return rotate_hops(ctx, p, out.d, tmp, count);
 }
+static int rotate_planned(cn_ctx *ctx, std::vector<RotJob> &jobs);
 int rotate_jobs(cn_ctx *ctx, std::vector<RotJob> &jobs) {
+    for (RotJob &j : jobs) CHECK(plan_rotation(ctx, j.steps, &j.plan));
+    return rotate_planned(ctx, jobs);
+}
+// ... with the hops of every job planned already (RotJob::plan; cn_rotate_rows_sum runs all but the last hop of its terms through here)
+static int rotate_planned(cn_ctx *ctx, std::vector<RotJob> &jobs) {
     const uint32_t n = (uint32_t)jobs.size();
     if (!n) return 0;
     uint32_t rounds = 0;
-    for (RotJob &j : jobs) { CHECK(plan_rotation(ctx, j.steps, &j.plan)); rounds = std::max(rounds, j.plan.hops); }
+    for (RotJob &j : jobs) rounds = std::max(rounds, j.plan.hops);
     bool aliased = false;
     for (uint32_t a = 0; a < n && !aliased; a++) for (uint32_t b = 0; b < n; b++) if (a != b && (jobs[a].dst == jobs[b].src || jobs[a].dst == jobs[b].dst)) { aliased = true; break; }
     const KsSwitches sw = ks_switches(ctx);
@@ -770,7 +776,7 @@ int rotate_jobs(cn_ctx *ctx, std::vector<RotJob> &jobs) {
         if (piece) {
             for (uint32_t s0 = 0; s0 < n; s0 += piece) {
                 std::vector<RotJob> part(jobs.begin() + s0, jobs.begin() + std::min<uint32_t>(n, s0 + piece));
-                CHECK(rotate_jobs(ctx, part));
+                CHECK(rotate_planned(ctx, part));
             }
             return 0;
         }
@@ -893,6 +899,131 @@ API_END }
 extern "C" int cn_rotate_rows_hoisted(cn_ctx *ctx, cn_handle in, uint32_t ii, const int *steps, uint32_t n, cn_handle out, const uint32_t *oi) { API_BODY TWO_LIMBS("cn_rotate_rows_hoisted");
     LOCK; if (n && !steps) return fail(CN_ERR_ARG, "null argument");
     return hoisted_rotations(ctx, in, ii, nullptr, steps, n, out, oi);
+API_END }
+// Summed rotations (include/cnhip.h; the plan: cn_ks_sum_plan, the kernels: the term MAC of the two-launch key switch + k_ks_sum_terms): out[oi + g] = the sum over
+// the terms e of group g of the rotation of in[ii[e]].  steps != null: RotateRows step counts (0: a plain addend) with the hops of cn_rotation.h, else Galois elements
+// (1: a plain addend), each with its own key.  Every check and every hop is planned before anything is copied or launched: a refused call leaves `out` as it is.
+// Where the plan says "compose" the literal sequence runs through a temporary - the rotations as cn_rotate_rows_many's rounds, k_add_many per group: the same words.
+static int rotation_sum(cn_ctx *ctx, cn_handle in, const uint32_t *ii, const uint64_t *elts, const int *steps, const uint32_t *grp_off, uint32_t G, cn_handle out, uint32_t oi) {
+    GETCT(I, in, 0); GETCT(O, out, 0);
+    if (I->size != 2 || O->size != 2) return fail(CN_ERR_ARG, "summed rotations: operands must be size-2 ciphertexts");
+    if (!ii || !grp_off || (!elts && !steps)) return fail(CN_ERR_ARG, "null argument");
+    if (!G) return fail(CN_ERR_ARG, "summed rotations: no output group");
+    if (grp_off[0] != 0) return fail(CN_ERR_ARG, "summed rotations: grp_off must start at 0");
+    for (uint32_t g = 0; g < G; g++) if (grp_off[g + 1] <= grp_off[g]) return fail(CN_ERR_ARG, "summed rotations: an empty group (grp_off must increase strictly)");
+    const uint32_t E = grp_off[G];
+    if (E > 0x00ffffffu) return fail(CN_ERR_ARG, "summed rotations: too many terms");
+    if (!range_ok(O, oi, G)) return fail(CN_ERR_ARG, "output index out of range");
+    const uint64_t N = ctx->hc.n;
+    std::vector<CnRotPlan> hops(E);
+    const KsKey *first = nullptr;
+    uint32_t rotated = 0, multi = 0;
+    for (uint32_t e = 0; e < E; e++) {
+        if (!range_ok(I, ii[e], 1)) return fail(CN_ERR_ARG, "index out of range");
+        if (O == I && ii[e] >= oi && ii[e] - oi < G) return fail(CN_ERR_ARG, "summed rotations: the output range contains a ciphertext the call reads");
+        if (!steps && (!(elts[e] & 1) || elts[e] >= 2 * N)) return fail(CN_ERR_ARG, "invalid Galois element");
+    }
+    for (uint32_t e = 0; e < E; e++) {
+        if (steps) CHECK(plan_rotation(ctx, steps[e], &hops[e]));
+        else if (elts[e] != 1) {                           // every element needs its OWN key
+            if (!galois_key(ctx, elts[e])) return fail(CN_ERR_NOKEY, "Galois key not present");
+            hops[e].hops = 1; hops[e].elt[0] = elts[e];
+        }
+        for (uint32_t h = 0; h < hops[e].hops; h++) {
+            const KsKey *key = galois_key(ctx, hops[e].elt[h]);
+            if (first && key->f64 != first->f64) return fail(CN_ERR_ARG, "summed rotations: the Galois keys were loaded in different forms (\"f64\" changed between the uploads)");
+            if (!first) first = key;
+        }
+        rotated += hops[e].hops != 0; multi += hops[e].hops > 1;
+    }
+    uint32_t outputs = 0;                                  // groups with a rotated term: the fused form's; the others are plain AddMany of their operands
+    std::vector<uint8_t> has_rot(G, 0);
+    for (uint32_t g = 0; g < G; g++) { for (uint32_t e = grp_off[g]; e < grp_off[g + 1]; e++) if (hops[e].hops) has_rot[g] = 1; outputs += has_rot[g]; }
+    const KsSumPlan plan = cn_ks_sum_plan(ctx->hc, ks_switches(ctx), first && first->f64, E, rotated, outputs);
+    const bool fused = plan.form != KS_SUM_COMPOSE;
+    if (fused) CHECK(ensure_ks_part(ctx, plan.arena_bytes));          // (the arena cannot grow while a graph records or lives: refused here, before the first launch)
+    const uint32_t tmp_cts = !rotated ? 0 : (fused ? multi : E);      // fused: the terms with earlier hops; composed: every term
+    cn_handle tmp = 0;
+    if (tmp_cts) CHECK(alloc_buf(ctx, 0, tmp_cts, 2, &tmp));
+    int rc = [&]() -> int {
+        Buffer *T = tmp ? getbuf(ctx, tmp, 0) : nullptr;
+        I = getbuf(ctx, in, 0); O = getbuf(ctx, out, 0);              // (the handle table may have moved)
+        auto src_of = [&](uint32_t e) { return I->d + (size_t)ii[e] * I->item_words; };
+        std::vector<uint32_t> slot(E, 0);                  // of a term in the temporary
+        std::vector<RotJob> jobs;
+        for (uint32_t e = 0, m = 0; e < E; e++) {
+            if (!T || (fused && hops[e].hops < 2)) continue;
+            slot[e] = m++;
+            RotJob j{src_of(e), T->d + (size_t)slot[e] * T->item_words, steps ? steps[e] : 0, hops[e]};
+            if (fused) j.plan.hops--;                      // the last hop belongs to the two launches below
+            jobs.push_back(j);
+        }
+        CHECK(rotate_planned(ctx, jobs));
+        const uint32_t limbs = 2 * ctx->hc.k;
+        if (!fused) {                                      // AddMany per group: out of the temporary, or - nothing rotated at all - out of the operands
+            std::vector<uint32_t> idx(E);
+            for (uint32_t e = 0; e < E; e++) idx[e] = rotated ? slot[e] : ii[e];
+            CHECK(ensure_scratch(ctx, al((size_t)E * 4)));
+            uint32_t *didx; CHECK(upload_tmp(ctx, idx.data(), idx.size(), &didx));
+            const Buffer *S = rotated ? T : I;
+            for (uint32_t g = 0; g < G; g++) {
+                hipLaunchKernelGGL(k_add_many, dim3(limbs * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, S->d, didx + grp_off[g], grp_off[g + 1] - grp_off[g], S->item_words,
+                                   O->d + (size_t)(oi + g) * O->item_words, ctx->dc, ctx->chunks);
+                HIPCHK(hipGetLastError()); launch_count(ctx);
+            }
+            return 0;
+        }
+        std::vector<KsItem> items; std::vector<KsSumOut> outs; std::vector<KsSumTerm> terms; std::vector<uint32_t> idx;
+        std::vector<uint32_t> plain_groups;
+        for (uint32_t g = 0; g < G; g++) {
+            if (!has_rot[g]) { plain_groups.push_back(g); continue; }
+            KsSumOut og{O->d + (size_t)(oi + g) * O->item_words, (uint32_t)terms.size(), grp_off[g + 1] - grp_off[g], 0u, 0u};
+            for (uint32_t e = grp_off[g]; e < grp_off[g + 1]; e++) {          // the rotated terms first
+                if (!hops[e].hops) continue;
+                const uint64_t *src = hops[e].hops > 1 ? T->d + (size_t)slot[e] * T->item_words : src_of(e);
+                const uint32_t elt = (uint32_t)hops[e].elt[hops[e].hops - 1];
+                terms.push_back({src, elt, (uint32_t)items.size()});
+                items.push_back({src, galois_key(ctx, elt)->d, elt, 0u});
+                og.rotated++;
+            }
+            for (uint32_t e = grp_off[g]; e < grp_off[g + 1]; e++) if (!hops[e].hops) terms.push_back({src_of(e), 1u, 0u});
+            outs.push_back(og);
+        }
+        for (uint32_t g : plain_groups) for (uint32_t e = grp_off[g]; e < grp_off[g + 1]; e++) idx.push_back(ii[e]);
+        CHECK(ensure_scratch(ctx, al(items.size() * sizeof(KsItem)) + al(outs.size() * sizeof(KsSumOut)) + al(terms.size() * sizeof(KsSumTerm)) + al(idx.size() * 4 + 4)));
+        KsItem *d_items; KsSumOut *d_outs; KsSumTerm *d_terms; uint32_t *didx = nullptr;      // (by value: a recorded call replays these tables)
+        CHECK(upload_tmp(ctx, items.data(), items.size(), &d_items)); CHECK(upload_tmp(ctx, outs.data(), outs.size(), &d_outs));
+        CHECK(upload_tmp(ctx, terms.data(), terms.size(), &d_terms));
+        if (!idx.empty()) CHECK(upload_tmp(ctx, idx.data(), idx.size(), &didx));
+        if (!ks_ops[plan.policy]->sum(ctx, {d_items, d_outs, d_terms, plan})) return fail(CN_ERR_ARG, "internal: summed rotations without a kernel of their policy");
+        HIPCHK(hipGetLastError());
+        ctx->st.ntt_forward_limbs += plan.fwd_limbs; ctx->st.ntt_inverse_limbs += plan.inv_limbs;
+        ctx->st.Rotation += rotated;
+        ctx->ks_summed++;
+        size_t at = 0;
+        for (uint32_t g : plain_groups) {
+            const uint32_t cnt = grp_off[g + 1] - grp_off[g];
+            hipLaunchKernelGGL(k_add_many, dim3(limbs * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, I->d, didx + at, cnt, I->item_words, O->d + (size_t)(oi + g) * O->item_words,
+                               ctx->dc, ctx->chunks);
+            HIPCHK(hipGetLastError()); launch_count(ctx);
+            at += cnt;
+        }
+        return 0;
+    }();
+    if (!rc) {
+        ctx->st.AddMany += G; ctx->st.AddManyItemCount += E;
+        for (uint32_t e = 0; e < E; e++) { if (steps) rec_rows(ctx, steps[e]); else if (elts[e] != 1) rec_galois(ctx, elts[e]); }
+    }
+    const int rf = tmp ? free_body(ctx, tmp) : 0;
+    return rc ? rc : rf;
+}
+extern "C" int cn_apply_galois_sum(cn_ctx *ctx, cn_handle in, const uint32_t *ii, const uint64_t *elts, const uint32_t *grp_off, uint32_t G, cn_handle out, uint32_t oi) { API_BODY TWO_LIMBS("cn_apply_galois_sum");
+    LOCK; if (!elts) return fail(CN_ERR_ARG, "null argument");
+    return rotation_sum(ctx, in, ii, elts, nullptr, grp_off, G, out, oi);
+API_END }
+extern "C" int cn_rotate_rows_sum(cn_ctx *ctx, cn_handle in, const uint32_t *ii, const int *steps, const uint32_t *grp_off, uint32_t G, cn_handle out, uint32_t oi) { API_BODY TWO_LIMBS("cn_rotate_rows_sum");
+    LOCK; if (!steps) return fail(CN_ERR_ARG, "null argument");
+    return rotation_sum(ctx, in, ii, nullptr, steps, grp_off, G, out, oi);
 API_END }
 static int add_kernel(cn_ctx *ctx, const uint64_t *a, const uint64_t *b, uint64_t *out, uint32_t count) {
     hipLaunchKernelGGL(k_addsub, dim3(count * 2 * ctx->hc.k * ctx->chunks), dim3(ctx->bs), 0, ctx->stream, a, b, out, ctx->dc, ctx->chunks, 0);

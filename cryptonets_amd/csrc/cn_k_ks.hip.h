@@ -897,3 +897,132 @@ __global__ void __launch_bounds__(NttPlan<L>::NT) k_ks_hoist_mac(const void *__r
         __syncthreads();
     }
 }
+// The term MAC of the summed rotations (below) for MANY terms (N <= 8192): block = (term, limb j) loops over ALL digits of its term: per source limb the permuted load of c1
+// (ks_gather_automorphism), per digit the cut, the forward transform and the multiply-accumulate with the term's key into register accumulators (lazy FP64 ones
+// recentred every accmax terms: the terms are those of the fused kernel), and leaves ONE partial pair per term, part[term][1][2][k][N] in transform order (the
+// 16 B/lane pattern of the key reads), recentred like k_ks_limb_mac's.  Not built at N = 16384 (cn_ks_term_built): beside a 1024-thread workgroup's 128 registers
+// per thread a 16384-point forward transform leaves no room for even one accumulator set (40 spilled registers per component when built).
+template <int L, class AR>
+__global__ void __launch_bounds__(NttPlan<L>::NT) k_ks_term_mac(void *__restrict__ part_, const DevConsts *__restrict__ C, uint32_t accmax, const KsItem *__restrict__ items) {
+    typedef typename AR::T T;
+    extern __shared__ __align__(16) unsigned char smem[];
+    T *s = reinterpret_cast<T *>(smem);
+    constexpr uint32_t n = 1u << L;
+    const uint32_t k = C->k, tid = threadIdx.x;
+    const uint32_t j = blockIdx.x % k, ct = blockIdx.x / k;
+    const DMod qm = C->q[j];
+    const uint64_t q = qm.q;
+    const ArCtx<AR> A(C, j);
+    const int dbc = C->gdbc;
+    const uint64_t mask = (1ull << dbc) - 1;
+    const size_t kn = (size_t)k * n;
+    const KsItem it = items[ct];
+    const NTT_GLOBAL T *kp = (const NTT_GLOBAL T *)it.key + (size_t)j * n;      // digit g: component 0 at kp + g 2kN, component 1 kN behind
+    T acc0[16], acc1[16];
+#pragma unroll
+    for (int r = 0; r < 16; r++) { acc0[r] = 0; acc1[r] = 0; }
+    uint32_t terms = 0;
+    for (uint32_t l = 0; l < k; l++) {
+        const uint32_t nd = C->gk_dig[l];
+        uint64_t raw[16];                              // the source words of limb l stay in registers for all of its digits
+        uint32_t elt = it.elt;
+        asm volatile("" : "+s"(elt));                  // opaque copy: the 16 products NT r elt stay work of the gather instead of 16 SGPRs hoisted out of the loop
+        if (l) __syncthreads();                        // the last digit's transform has left the image
+        ks_gather_automorphism<L>(raw, (const NTT_GLOBAL uint64_t *)it.in + kn + (size_t)l * n, elt, C->q[l].q, s, tid);
+        ks_premultiply(raw, C, l);
+        for (uint32_t d = 0; d < nd; d++, kp += 2 * kn) {
+            const int sh = dbc * (int)d;
+            uint32_t tl = tid;
+            asm volatile("" : "+v"(tl));
+            T v[16];
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                uint64_t t = (raw[r] >> sh) & mask;
+                if constexpr (std::is_same<T, uint64_t>::value) { if (mask >= q) t = t >= q ? bred128(t, 0, qm) : t; }
+                v[r] = A.load(t);
+            }
+            if constexpr (std::is_same<T, double>::value) { if (mask >= q) AR::renorm(v, A.m); }
+            ntt_forward_regs<AR, L, true>(v, s, A.fw, A.m, tl);
+#pragma unroll
+            for (int r = 0; r < 16; r += 2) {
+                const uint32_t pos = tail_index<L>(tl, r);
+                T ka, kb;
+                ks_load2<T>(kp + pos, ka, kb);
+                KsMac<AR>::mac(acc0[r], v[r], ka, qm, A); KsMac<AR>::mac(acc0[r + 1], v[r + 1], kb, qm, A);
+                ks_load2<T>(kp + kn + pos, ka, kb);
+                KsMac<AR>::mac(acc1[r], v[r], ka, qm, A); KsMac<AR>::mac(acc1[r + 1], v[r + 1], kb, qm, A);
+            }
+            if (++terms == accmax) { terms = 0; KsMac<AR>::settle(acc0, A); KsMac<AR>::settle(acc1, A); }
+        }
+    }
+    KsMac<AR>::settle(acc0, A); KsMac<AR>::settle(acc1, A);        // partials leave recentred: k_ks_sum_terms adds them under the plan's bound
+    T *o0 = reinterpret_cast<T *>(part_) + (size_t)ct * 2 * kn + (size_t)j * n, *o1 = o0 + kn;
+    struct alignas(16) P2 { T a, b; };
+#pragma unroll
+    for (int r = 0; r < 16; r += 2) {
+        const uint32_t pos = tail_index<L>(tid, r);
+        *reinterpret_cast<P2 *>(o0 + pos) = P2{acc0[r], acc0[r + 1]};
+        *reinterpret_cast<P2 *>(o1 + pos) = P2{acc1[r], acc1[r + 1]};
+    }
+}
+// Summed rotations (cn_rotate_rows_sum / cn_apply_galois_sum, the plan: cn_ks_sum_plan): out_g = sum_r Galois(in_r, elt_r) over DIFFERENT ciphertexts.  The inverse
+// transform is linear mod q_j, so the partial products the term MAC left (k_ks_digit_mac / k_ks_limb_mac with their KsItem table: part[term][P][2][k][N], transform
+// order) are summed over ALL terms of an output before ONE inverse transform per (output, limb, component): the words of cn_apply_galois per term + cn_add_many.
+//   block = (output g, limb j, component p): sum of the partials of the output's rotated terms (lazy FP64 sums recentred every `settle` additions: the bound is the
+//   plan's), inverse transform, 1 / N; component 0: + s_(elt_r)(c0_r) of every rotated term, the whole limb through the exchange image between barriers, as
+//   k_ks_sum_intt does for one term; then both components of every unrotated term (element 1); canonical words to out_g.  No atomics.
+// An output's rotated terms come first in its slice of the term table (KsSumOut, KsSumTerm: cn_runtime.h); the call refuses outputs among its operands.
+template <int L, class AR>
+__global__ void __launch_bounds__(NttPlan<L>::NT) k_ks_sum_terms(const void *__restrict__ part_, const KsSumOut *__restrict__ outs, const KsSumTerm *__restrict__ terms,
+                                                                  const DevConsts *__restrict__ C, uint32_t partials, uint32_t settle) {
+    typedef typename AR::T T;
+    extern __shared__ __align__(16) unsigned char smem[];
+    T *s = reinterpret_cast<T *>(smem);
+    constexpr uint32_t n = 1u << L;
+    constexpr int SA = NttPlan<L>::SA;
+    const uint32_t k = C->k, tid = threadIdx.x;
+    const uint32_t p = blockIdx.x & 1, j = (blockIdx.x >> 1) % k;
+    const KsSumOut og = outs[blockIdx.x / (2 * k)];
+    const DMod qm = C->q[j];
+    const ArCtx<AR> A(C, j);
+    const size_t kn = (size_t)k * n;
+    const KsSumTerm *tm = terms + og.first;
+    struct alignas(16) P2 { T a, b; };
+    T v[16];
+#pragma unroll
+    for (int r = 0; r < 16; r++) v[r] = 0;
+    uint32_t added = 0;
+    for (uint32_t t = 0; t < og.rotated; t++) {
+        const T *src = reinterpret_cast<const T *>(part_) + ((size_t)tm[t].part * partials * 2 + p) * kn + (size_t)j * n;
+        for (uint32_t g = 0; g < partials; g++, src += 2 * kn) {
+#pragma unroll
+            for (int r = 0; r < 16; r += 2) {
+                const P2 x = *reinterpret_cast<const P2 *>(src + tail_index<L>(tid, r));
+                v[r] = KsMac<AR>::sum(v[r], x.a, qm); v[r + 1] = KsMac<AR>::sum(v[r + 1], x.b, qm);
+            }
+            if (++added == settle) { added = 0; KsMac<AR>::settle(v, A); }
+        }
+    }
+    ntt_inverse_regs<AR, L>(v, s, A.iv, A.m, tid);
+    uint64_t val[16];
+#pragma unroll
+    for (int r = 0; r < 16; r++) val[r] = A.scaled(v[r]);
+    if (p == 0) {
+        for (uint32_t t = 0; t < og.rotated; t++) {          // s_g(c0): the whole limb is read (through the image) before a word of the result is written
+            const uint64_t *img = reinterpret_cast<const uint64_t *>(smem);
+            __syncthreads();                                   // everybody has taken its coefficients (the previous term's words) out of the image
+            ks_stage_automorphism<L>((const NTT_GLOBAL uint64_t *)tm[t].in + (size_t)j * n, tm[t].elt, qm.q, smem, tid);
+            __syncthreads();
+#pragma unroll
+            for (int r = 0; r < 16; r++) val[r] = addmod(val[r], img[lds_pos(pass_index<L, SA, 0>(tid, r))], qm.q);      // (no second register set: N = 16384 has 128 per thread)
+        }
+    }
+    for (uint32_t t = og.rotated; t < og.count; t++) {       // unrotated terms: plain addends, both components
+        const NTT_GLOBAL uint64_t *ad = (const NTT_GLOBAL uint64_t *)tm[t].in + (size_t)p * kn + (size_t)j * n;
+#pragma unroll
+        for (int r = 0; r < 16; r++) val[r] = addmod(val[r], ad[pass_index<L, SA, 0>(tid, r)], qm.q);
+    }
+    NTT_GLOBAL uint64_t *o = (NTT_GLOBAL uint64_t *)og.out + (size_t)p * kn + (size_t)j * n;
+#pragma unroll
+    for (int r = 0; r < 16; r++) o[pass_index<L, SA, 0>(tid, r)] = val[r];
+}

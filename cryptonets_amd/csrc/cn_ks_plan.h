@@ -123,6 +123,68 @@ inline KsHoistPlan cn_ks_hoist_plan(const DevConsts &hc, const KsSwitches &sw, b
     return p;
 }
 
+// ---- summed rotations (cn_rotate_rows_sum / cn_apply_galois_sum): out_g = sum of rotations of DIFFERENT ciphertexts.  A key switch ends in INTT_j(acc) and the
+// inverse transform is linear mod q_j, so the NTT-domain partial sums of all terms of an output are added BEFORE one pair of inverse transforms per output limb:
+// the words of cn_apply_galois per term + cn_add_many, exactly.  Two launches for the last hop of every term:
+//   1. the term MAC, part[term][P][2][k][N] with P partials per term: k_ks_digit_mac (a workgroup per (term, digit, limb), P = gk_tot) or k_ks_limb_mac (per (term,
+//      source limb, limb), P = k; N <= 8192) with their KsItem table while the terms are few - they leave exactly these partials -, k_ks_term_mac (per (term, limb);
+//      N <= 8192) with P = 1 when they are many;
+//   2. k_ks_sum_terms, a workgroup per (output, limb, component): the sum over the output's terms and their P partials, ONE inverse transform, + s_g(c0) of every
+//      rotated term (component 0), + both components of every unrotated term.
+// Where this does not run the call COMPOSES the literal sequence through a temporary (same words): no register-radix kernels (N < 1024, "legacy_ntt"), the integer
+// policy at N = 16384 (cn_ks_sum_built), an arena above KsSwitches::arena_max even at the coarsest granularity.
+// The thresholds between the granularities START from digit_max_blocks / wide_max_blocks of the plain key switch, counted in (term, limb) blocks: per digit up to
+// the first, per source limb up to the second, per term above.  N = 16384 runs per digit whatever the count: a 1024-thread workgroup (128 registers per thread)
+// has no room for two accumulator sets (k_ks_limb_mac) and, beside a 16384-point forward transform, not even for one (cn_ks_term_built) - the 126 giant steps of
+// the CIFAR layer (k = 8, 8 digits) are 2 GiB of per-digit partials, inside the default arena_max.  NOBODY HAS MEASURED THEM FOR THIS CALL (tools/rotation_sum_probe.py
+// varies them through CN_KS_DIGIT_MAX / CN_KS_WIDE_MAX).  A granularity whose partials exceed arena_max gives way to the next coarser one.
+// The settle interval of the second launch: a per-digit partial is ONE lazy product, |x| <= 2.1 q (cn_f64_acc_interval's term), per-limb and per-term partials
+// leave recentred, |x| <= q / 2; k_ks_sum_terms recentres every `settle` additions, so its sums stay within q / 2 + settle 2.1 q, and settle =
+// cn_f64_acc_interval(bits) = 2^(50 - bits) keeps that below 2^52 for q < 2^bits - the rule of k_ks_sum_intt, whatever the number of terms
+// (tests/cpp/ks_sum_plan.cpp sums the worst case).
+constexpr bool cn_ks_sum_built(int policy, uint32_t logn) { return logn >= 10 && logn <= 14 && !(policy == POL_U64 && logn == 14); }
+constexpr bool cn_ks_term_built(int policy, uint32_t logn) { return cn_ks_sum_built(policy, logn) && logn <= 13; }
+enum KsSumForm { KS_SUM_COMPOSE, KS_SUM_DIGIT, KS_SUM_LIMB, KS_SUM_TERM };
+static const uint32_t KS_SUM_TERM_MILLI_Q = 2100;      // |partial| <= 2.1 q: what the settle interval rests on
+struct KsSumPlan {
+    KsSumForm form; const char *why;      // the granularity of the first launch, or "compose" and its reason
+    int policy;                           // cn_policy of the q limbs by the form the keys were loaded in
+    uint32_t accmax;                      // first launch (k_ks_limb_mac, k_ks_term_mac): terms between recentrings
+    uint32_t settle;                      // second launch: additions between recentrings
+    uint32_t partials;                    // per term: gk_tot (per digit), k (per source limb) or 1 (per term)
+    size_t arena_bytes;                   // of cn_ctx::ks_part: part[rotated][partials][2][k][N]
+    uint32_t blocks_mac, blocks_sum;      // workgroups of the two launches
+    uint64_t fwd_limbs, inv_limbs;        // what the two launches add to ntt_forward_limbs / ntt_inverse_limbs
+};
+// rotated: terms with a key switch (their LAST hop runs here); outputs: groups that hold at least one of them
+inline KsSumPlan cn_ks_sum_plan(const DevConsts &hc, const KsSwitches &sw, bool key_f64, uint32_t terms, uint32_t rotated, uint32_t outputs) {
+    const uint32_t k = hc.k, tot = hc.gk_tot;
+    const CnModRange qr = cn_mod_range(hc, 0, k);
+    const uint32_t interval = key_f64 ? cn_f64_acc_interval(qr.bits) : 0xffffffffu;
+    KsSumPlan p{KS_SUM_COMPOSE, nullptr, cn_policy(qr, key_f64), interval, interval, 0, 0, 0, 0, 0, 0};
+    auto compose = [&p](const char *text) { p.why = text; return p; };
+    if (!rotated || !outputs || rotated > terms) return compose("no rotated term");
+    if (!sw.rr) return compose("no register-radix kernels (N < 1024 or \"legacy_ntt\")");
+    if (key_f64 && !qr.f64ok) return compose("FP64 keys without FP64 kernels");
+    if (!cn_ks_sum_built(p.policy, hc.logn)) return compose("no kernel under the integer policy at N = 16384");
+    if ((uint64_t)rotated * tot * k > 0x7fffffffu) return compose("too many terms for one launch");
+    const uint64_t blocks = (uint64_t)rotated * k;
+    const size_t ct_bytes = (size_t)2 * k * hc.n * 8;
+    auto fits = [&](uint32_t partials) { return (size_t)rotated * partials * ct_bytes <= sw.arena_max; };
+    if (blocks <= sw.digit_max_blocks || hc.logn == 14) p.form = KS_SUM_DIGIT;
+    else if (blocks <= sw.wide_max_blocks) p.form = KS_SUM_LIMB;
+    else p.form = KS_SUM_TERM;
+    if (p.form == KS_SUM_DIGIT && !fits(tot) && hc.logn < 14) p.form = KS_SUM_LIMB;      // the coarser granularity first
+    if (p.form == KS_SUM_LIMB && !fits(k)) p.form = KS_SUM_TERM;
+    if (p.form == KS_SUM_TERM && !cn_ks_term_built(p.policy, hc.logn)) p.form = KS_SUM_COMPOSE;
+    p.partials = p.form == KS_SUM_DIGIT ? tot : (p.form == KS_SUM_LIMB ? k : 1);
+    if (p.form == KS_SUM_COMPOSE || !fits(p.partials)) { p.form = KS_SUM_COMPOSE; p.partials = 0; return compose("the partial products would not fit the key-switch arena"); }
+    p.arena_bytes = (size_t)rotated * p.partials * ct_bytes;
+    p.blocks_mac = rotated * p.partials * k; p.blocks_sum = outputs * k * 2;
+    p.fwd_limbs = (uint64_t)rotated * tot * k; p.inv_limbs = (uint64_t)outputs * 2 * k;
+    return p;
+}
+
 // ---- the call shapes a form does not take (internal errors: a caller asked the wrong reader)
 struct KsShape { bool dig, perm_elt, items, next_elt; };      // KsCall: ready-made digits; automorphism on load; per-ciphertext operand table; sigma_next(c1) on the side
 struct KsRefusal {

@@ -24,10 +24,15 @@ template <int L, class DS> static int set_attrs_dig(size_t bytes) {
 }
 // hoisted rotations: the instantiations the planner's predicate admits (cn_ks_hoist_built, cn_ks_plan.h)
 template <int L> static constexpr bool kHoist = cn_ks_hoist_built(kF64 ? POL_F64 : POL_U64, L);
+// summed rotations: the instantiations the planner's predicate admits (cn_ks_sum_built, cn_ks_plan.h)
+template <int L> static constexpr bool kSum = cn_ks_sum_built(kF64 ? POL_F64 : POL_U64, L);
+template <int L> static constexpr bool kTerm = cn_ks_term_built(kF64 ? POL_F64 : POL_U64, L);
 template <int L> static int set_attrs_l(size_t bytes) {
     CHECK(big_lds(k_keyswitch_rr<L, AR>, bytes)); CHECK(big_lds(k_keyswitch_rr<L, AR, 1, false, true>, bytes));
     if constexpr (KsFwd<AR, L>::lds) { CHECK(big_lds(k_keyswitch_rr<L, AR, 1, true>, ks_twl_lds<L>())); CHECK(big_lds(k_keyswitch_rr<L, AR, 1, true, true>, ks_twl_lds<L>())); }
     CHECK(big_lds(k_ks_digit_mac<L, AR>, bytes)); CHECK(big_lds(k_ks_limb_mac<L, AR>, bytes)); CHECK(big_lds(k_ks_sum_intt<L, AR>, bytes));
+    if constexpr (kSum<L>) CHECK(big_lds(k_ks_sum_terms<L, AR>, bytes));
+    if constexpr (kTerm<L>) CHECK(big_lds(k_ks_term_mac<L, AR>, bytes));
     if constexpr (kHoist<L>) { CHECK(big_lds(k_ks_digit_ntt<L, AR>, bytes)); CHECK(big_lds(k_ks_hoist_mac<L, AR, L == 14>, bytes)); }
     if constexpr (kF64) { CHECK((set_attrs_dig<L, KsDigits<AR>>(bytes))); if constexpr (kDig32<L>) CHECK((set_attrs_dig<L, KsDigits<AR, int32_t>>(bytes))); }
     return 0;
@@ -179,6 +184,37 @@ static bool hoist(cn_ctx *c, const KsHoistArgs &a) {
         default: return false;
     }
 }
+// summed rotations: the partial products of every rotated term into c->ks_part (per digit, per source limb or per term, operand, key and element from the KsItem table, the automorphism applied on load), then per (output, limb, component) their sum, one inverse transform and the addends (KsSumPlan)
+template <int L> static bool launch_sum(cn_ctx *c, const KsSumArgs &a) {
+    if constexpr (kSum<L>) {
+        const size_t lds = (size_t)ntt_lds_words(1u << L) * 8;
+        if (a.plan.form == KS_SUM_LIMB)
+            hipLaunchKernelGGL((k_ks_limb_mac<L, AR>), dim3(a.plan.blocks_mac), dim3(NttPlan<L>::NT), lds, c->stream, (const uint64_t *)nullptr, (size_t)0, (const void *)nullptr, c->ks_part,
+                               c->dc, 1, a.plan.accmax, 0u, a.items);
+        else if (a.plan.form == KS_SUM_DIGIT)
+            hipLaunchKernelGGL((k_ks_digit_mac<L, AR>), dim3(a.plan.blocks_mac), dim3(NttPlan<L>::NT), lds, c->stream, (const uint64_t *)nullptr, (size_t)0, (const void *)nullptr, c->ks_part,
+                               c->dc, 1, c->hc.gk_tot, 0u, a.items);
+        else if (a.plan.form == KS_SUM_TERM) {
+            if constexpr (kTerm<L>) hipLaunchKernelGGL((k_ks_term_mac<L, AR>), dim3(a.plan.blocks_mac), dim3(NttPlan<L>::NT), lds, c->stream, c->ks_part, c->dc, a.plan.accmax, a.items);
+            else return false;
+        } else return false;
+        hipLaunchKernelGGL((k_ks_sum_terms<L, AR>), dim3(a.plan.blocks_sum), dim3(NttPlan<L>::NT), lds, c->stream, (const void *)c->ks_part, a.outs, a.terms, c->dc, a.plan.partials,
+                           a.plan.settle);
+        cn_launch_count(c, 2);
+        return true;
+    }
+    return false;
+}
+static bool sum(cn_ctx *c, const KsSumArgs &a) {
+    switch (c->hc.logn) {
+        case 10: return launch_sum<10>(c, a);
+        case 11: return launch_sum<11>(c, a);
+        case 12: return launch_sum<12>(c, a);
+        case 13: return launch_sum<13>(c, a);
+        case 14: return launch_sum<14>(c, a);
+        default: return false;
+    }
+}
 #ifndef __HIP_DEVICE_COMPILE__      // host-side table (in the device pass a const global would be emitted as device data)
-extern const KsOps KS_NAME = {set_attrs, launch, hoist};
+extern const KsOps KS_NAME = {set_attrs, launch, hoist, sum};
 #endif

@@ -183,6 +183,7 @@ struct cn_ctx {
     CnCounters cnt;           // what cn_get_option reads back by the names of kCounters (cn_options.h)
     std::atomic<uint64_t> packed_bad{0};       // packed uploads whose rows held a residue >= its modulus (counted where the flag is read)
     uint64_t ks_hoisted = 0;   // calls of cn_rotate_rows_hoisted / cn_apply_galois_hoisted that launched ("ks_hoisted")
+    uint64_t ks_summed = 0;    // calls of cn_rotate_rows_sum / cn_apply_galois_sum that launched the fused form ("ks_summed")
     uint32_t ms_groups = 0;    // output groups of the last cn_mul_relin_sum call ("mul_sum_groups"; 0: it took the literal sequence)
     uint64_t uid = 0;         // creation order within the process (cn_ctx_create)
     hipStream_t stream2 = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr; bool stream2_failed = false;   // second stream of pipelined_halves (aux_stream_ready)
@@ -269,10 +270,17 @@ struct RrOps {                // register-radix kernels of one arithmetic policy
 // the ONE input ciphertext (c0, c1 behind it), the table on the device (the plan's blocks_mac says how many rotations it holds)
 struct KsHoistItem { const void *key; uint64_t *out; uint32_t elt, pad; };
 struct KsHoistArgs { const uint64_t *in; const KsHoistItem *items; KsHoistPlan plan; };
+// summed rotations (cn_ks_plan.h: KsSumPlan).  Per output its ciphertext and its slice [first, first + count) of the term table, whose first `rotated` entries
+// are the rotated terms; per term the ciphertext it reads (c0 at in, c1 behind it), its element (1: a plain addend) and - rotated terms - the index of its
+// partial products in the arena, which is its index in the KsItem table of the term MAC
+struct KsSumOut { uint64_t *out; uint32_t first, count, rotated, pad; };
+struct KsSumTerm { const uint64_t *in; uint32_t elt, part; };
+struct KsSumArgs { const KsItem *items; const KsSumOut *outs; const KsSumTerm *terms; KsSumPlan plan; };
 struct KsOps {
     int (*set_attrs)(uint32_t logn, size_t lds);
     bool (*launch)(cn_ctx *c, const KsArgs &a);                        // the kernels of a.plan.form; false: this policy (or ring size) has no instantiation of it
     bool (*hoist)(cn_ctx *c, const KsHoistArgs &a);                    // k_ks_digit_ntt + k_ks_hoist_mac of this policy; false: no instantiation at this ring size
+    bool (*sum)(cn_ctx *c, const KsSumArgs &a);                        // the term MAC of a.plan.form + k_ks_sum_terms; false: no instantiation at this ring size
 };
 extern const RrOps cn_rr_u64, cn_rr_f64, cn_rr_f64l;
 extern const KsOps cn_ks_u64, cn_ks_f64, cn_ks_f64l;

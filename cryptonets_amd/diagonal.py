@@ -71,7 +71,7 @@ def choose_baby_steps(mask):
     return best[1]
 
 
-def dense_path_counts(R, Dim, n, k, digits, length=None, B=None, ntt_weights=False, hoisted=False):
+def dense_path_counts(R, Dim, n, k, digits, length=None, B=None, ntt_weights=False, hoisted=False, summed=False):
     """Limb transforms (one N-point transform of one limb) of the two ways to compute the dense product of an R x Dim plaintext matrix with one packed ciphertext on a
     ring of n slots with k coefficient moduli and `digits` digit polynomials per key switch (ks_digits of the Galois decomposition bit count):
 
@@ -88,6 +88,10 @@ def dense_path_counts(R, Dim, n, k, digits, length=None, B=None, ntt_weights=Fal
 
     hoisted: the baby steps are ONE hoisted call (hewrapper.HOISTED_ROTATIONS, cn_rotate_rows_hoisted: every baby step with its own key) - their key switches share
     the digits k forward transforms of the input and cost 2 k inverse transforms each, instead of digits k + 2 k each.  The default path does not change.
+
+    summed: the giant steps are ONE summed call (hewrapper.SUMMED_ROTATIONS, cn_rotate_rows_sum: one key switch per group with j > 0, priced with its own key as
+    the folding links are) - every one keeps its digits k forward transforms, and the 2 k inverse transforms are paid once per column class with such a group
+    instead of once per key switch.  The default path does not change.
 
     Weights are taken as dense inside R x Dim (structural_diagonals).  Returns a dict with the two totals, their parts and "choice": "diagonal" if and only if its
     total is lower."""
@@ -110,6 +114,9 @@ def dense_path_counts(R, Dim, n, k, digits, length=None, B=None, ntt_weights=Fal
     baby_ks = max(babies - (1 if mask.reshape(2, -1, B)[:, :, 0].any() else 0), 0)
     if hoisted and baby_ks:
         diagonal -= baby_ks * per_ks - (digits * k + baby_ks * 2 * k)
+    if summed:
+        far = mask.reshape(2, -1, B).any(axis=2)[:, 1:]              # groups (c, j) with j > 0: the same number of key switches by folding and by one rotation each
+        diagonal -= (int(far.sum()) - int(far.any(axis=1).sum())) * 2 * k
     return {"default": default, "diagonal": diagonal, "choice": "diagonal" if diagonal < default else "default", "B": B,
             "default_key_switches": d_ks, "diagonal_key_switches": g_ks, "default_plain_transforms": d_plain, "diagonal_plain_transforms": g_plain,
             "diagonals": terms, "babies": babies, "groups": ngroups}

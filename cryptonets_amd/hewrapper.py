@@ -120,6 +120,20 @@ def _rotate_hoisted(ctx, h, first, steps, out_h, out_idx):
         raise
 
 
+# SUMMED_ROTATIONS = True: the places that add up rotations of DIFFERENT ciphertexts - the output blocks of Interleave, the selections of Permute, the giant steps
+# of DiagonalDense - ask for one summed call (cn_rotate_rows_sum, DESIGN 6k: every term its forward digit transforms and key products, ONE pair of inverse
+# transforms per output limb, no rotated term stored, no dependence between the terms).  The call writes the words of the rotations followed by AddMany, so Interleave
+# and Permute return the ciphertext words of the switch-off run; DiagonalDense returns the same slots with other words where the present route folds (folding
+# rotates sums).  A step without its own key runs its non-adjacent-form hops inside the call; with "record_steps" on the giant steps are noted, so
+# networks.rotation_steps and GenerateEncryptionKeys(steps=...) make their direct keys.  A backend without the call (the CPU oracle of the tests) keeps the present
+# route.  False (default): nothing changes - the switch stays off until the routes have been measured side by side (profiles/rotation_sum.md).
+SUMMED_ROTATIONS = False
+
+
+def _summed(ctx):
+    return SUMMED_ROTATIONS and hasattr(ctx, "rotate_rows_sum")
+
+
 def _hoisted_keys_held(ctx, B):
     """does the context hold the own Galois key of every baby step 1 .. B - 1 (what a hoisted call of DiagonalDense needs)?"""
     return hasattr(ctx, "rotate_rows_hoisted") and all(ctx.has_galois_key(ctx.galois_elt_from_step(s)) for s in range(1, B))
@@ -857,6 +871,10 @@ class AtomicSealBfvEncryptedVector:
         # rotations of the interleave are ONE library call (cn_rotate_rows_many: the hops of the 13 differently rotated vectors run in rounds,
         # the same hops and words), straight from the source array when the vectors share one, behind one gather launch otherwise
         steps = [steps_of(k) for k in range(n)]
+        if _summed(ctx) and n > 1:
+            res = AtomicSealBfvEncryptedVector._interleave_summed(vecs, steps, geometry, ones_mask, absShift, outputBlockCount, env)
+            work.release()
+            return res
         if hasattr(ctx, "rotate_rows_many") and n > 1:
             if all(x.buf is vecs[0].buf for x in vecs):
                 ctx.rotate_rows_many(vecs[0].h, [x.first for x in vecs], steps, work.h, list(range(n)))
@@ -910,6 +928,79 @@ class AtomicSealBfvEncryptedVector:
                 ctx.add(res.h, i, tmp.h, 0, res.h, i, 1)
         tmp.release()
         work.release()
+        return res
+
+    @staticmethod
+    def _interleave_summed(vecs, steps, geometry, ones_mask, absShift, outputBlockCount, env):
+        """_Inteleave under SUMMED_ROTATIONS: a vector that goes into a sum unmodified is a TERM of one cn_rotate_rows_sum (two groups per output block, its
+        `lower` list and its `upper` list) and is never stored rotated; a vector that is split (v2, the mask products) is rotated into `work` by the present code
+        and enters the sums as plain addends.  Straight from the source array when nothing is split and the vectors share one, behind copy_many otherwise.  Then
+        the present rotate_columns + add.  The words are those of the switch-off route."""
+        ctx = env.ctx
+        blockSize = env.SlotCount
+        half = blockSize // 2
+        n = len(vecs)
+        lower = [[] for _ in range(outputBlockCount)]      # (slot, step): slot k = vector k unrotated, slot n + k: its split-off part (step 0, like a split slot k)
+        upper = [[] for _ in range(outputBlockCount)]
+        split = []                                         # (vector, mask length, the list its masked part goes to, the list the rest goes to)
+        for k in range(n):
+            thisShift, inBlockShift, startBlock, endBlock = geometry(k)
+            if inBlockShift == 0 or inBlockShift + absShift < half:
+                lower[startBlock].append((k, steps[k]))
+            elif inBlockShift >= half:
+                if startBlock == endBlock:
+                    upper[startBlock].append((k, steps[k]))
+                else:
+                    split.append((k, inBlockShift + absShift - blockSize, lower[endBlock], upper[startBlock]))
+            else:
+                upperPartSize = inBlockShift + absShift - half
+                if upperPartSize > 0:
+                    split.append((k, upperPartSize, upper[startBlock], lower[startBlock]))
+                else:
+                    lower[startBlock].append((k, steps[k]))
+        shared = all(x.buf is vecs[0].buf for x in vecs)
+        work = None
+        if split or not shared:
+            work = _Buf(ctx, "ct", 2 * n).view()
+            ctx.copy_many([x.h for x in vecs], [x.first for x in vecs], work.h, 0)
+            ks = [k for k, _, _, _ in split]
+            if ks:                                           # the vectors that are split: rotated in place, as the present route rotates them
+                ctx.rotate_rows_many(work.h, ks, [steps[k] for k in ks], work.h, ks)
+            for k, size, masked_to, rest_to in split:        # slot k: the masked part, slot n + k: the rest - the present route's operations
+                v, v2 = k, n + k
+                ctx.copy(work.h, v, work.h, v2, 1)
+                p = ones_mask(size)
+                ctx.mul_plain(work.h, v, p.h, 0, work.h, v, 1)
+                ctx.sub(work.h, v2, work.h, v, work.h, v2, 1)
+                masked_to.append((v, 0))
+                rest_to.append((v2, 0))
+            src_h, slot = work.h, (lambda k: k)
+        else:
+            src_h, slot = vecs[0].h, (lambda k: vecs[k].first)
+        groups = []                                          # (block, is_upper)
+        ii, st, off = [], [], [0]
+        for i in range(outputBlockCount):
+            if not lower[i]:
+                raise Exception("AddMany of an empty list")
+            for is_upper, lst in ((False, lower[i]), (True, upper[i])):
+                if lst:
+                    groups.append((i, is_upper))
+                    ii += [slot(k) if k < n else k for k, _ in lst]
+                    st += [s_ for _, s_ in lst]
+                    off.append(len(ii))
+        sums = _Buf(ctx, "ct", len(groups)).view()
+        ctx.rotate_rows_sum(src_h, ii, st, off, sums.h, 0)
+        res = _Buf(ctx, "ct", outputBlockCount).view()
+        at = {g: x for x, g in enumerate(groups)}
+        for i in range(outputBlockCount):
+            if (i, True) in at:
+                ctx.rotate_columns(sums.h, at[(i, True)], sums.h, at[(i, True)], 1)
+                ctx.add(sums.h, at[(i, False)], sums.h, at[(i, True)], res.h, i, 1)
+            else:
+                ctx.copy(sums.h, at[(i, False)], res.h, i, 1)
+        sums.release()
+        if work is not None:
+            work.release()
         return res
 
     @staticmethod
@@ -1320,6 +1411,8 @@ class AtomicSealBfvEncryptedVector:
         if self.encData.count > 1:
             raise Exception("can permute only a single block")
         ctx = env.ctx
+        if _summed(ctx):
+            return self._permute_summed(selections, shifts, outputDim, env)
         work = _Buf(ctx, "ct", 3).view()            # 0: res, 1: t, 2: t3->relin tmp
         first = -1
         for i, s in enumerate(selections):
@@ -1347,6 +1440,34 @@ class AtomicSealBfvEncryptedVector:
         res = _Buf(ctx, "ct", 1).view()
         ctx.copy(work.h, 0, res.h, 0, 1)
         work.release()
+        return AtomicSealBfvEncryptedVector._new(IsSigned=self.IsSigned, Scale=self.Scale * selections[first].Scale, Dim=outputDim, encData=res,
+                                                 Format=EVectorFormat.dense)
+
+    def _permute_summed(self, selections, shifts, outputDim, env):
+        """Permute under SUMMED_ROTATIONS: the selection products as they are, then ONE cn_rotate_rows_sum instead of a rotation and an addition per selection -
+        the same words"""
+        ctx = env.ctx
+        chosen = [i for i, s in enumerate(selections) if s is not None]
+        if not chosen:
+            raise Exception("permuting with no selected values is illigal")
+        first = chosen[0]
+        work = _Buf(ctx, "ct", len(chosen)).view()
+        try:
+            for x, i in enumerate(chosen):
+                s = selections[i]
+                if s.Dim != self.Dim:
+                    raise Exception("dimension of selection vector does not match dimension of data vector")
+                if s.Scale != selections[first].Scale:
+                    raise Exception("scales of all selection vectors should be the same")
+                if s.plainDense is not None:
+                    pd = s._pd(ctx)
+                    ctx.mul_plain(self.encData.h, self.encData.first, pd.h, pd.first, work.h, x, 1)
+                else:
+                    ctx.mul_relin(self.encData.h, self.encData.first, s.encData.h, s.encData.first, work.h, x, 1)
+            res = _Buf(ctx, "ct", 1).view()
+            ctx.rotate_rows_sum(work.h, list(range(len(chosen))), [int(shifts[i]) for i in chosen], [0, len(chosen)], res.h, 0)
+        finally:
+            work.release()
         return AtomicSealBfvEncryptedVector._new(IsSigned=self.IsSigned, Scale=self.Scale * selections[first].Scale, Dim=outputDim, encData=res,
                                                  Format=EVectorFormat.dense)
 
@@ -2025,8 +2146,9 @@ class EncryptedSealBfvMatrix:
         c = diagonal.dense_path_counts(*args, ntt_weights=NTT_WEIGHTS and hasattr(ctx, "pt_transform"))
         # HOISTED_ROTATIONS: the baby steps are priced as one hoisted call only where the context holds their direct keys - without them the run goes by doubling.
         # (Not foreseen here: a context whose planner refuses the call - the integer policy at N = 16384 - is still priced as hoisted when it holds the keys.)
-        if HOISTED_ROTATIONS and _hoisted_keys_held(ctx, c["B"]):
-            c = diagonal.dense_path_counts(*args, B=c["B"], ntt_weights=NTT_WEIGHTS and hasattr(ctx, "pt_transform"), hoisted=True)
+        hoisted = HOISTED_ROTATIONS and _hoisted_keys_held(ctx, c["B"])
+        if hoisted or _summed(ctx):                                  # SUMMED_ROTATIONS: the giant steps of a column class share one pair of inverse transforms per limb
+            c = diagonal.dense_path_counts(*args, B=c["B"], ntt_weights=NTT_WEIGHTS and hasattr(ctx, "pt_transform"), hoisted=hoisted, summed=_summed(ctx))
         return c
 
     def DiagonalDenseWins(self, v, env):
@@ -2119,7 +2241,24 @@ class EncryptedSealBfvMatrix:
                     tv.release()
             bv.release()
             res = _Buf(ctx, "ct", 1)
-            if plan.giants_by_folding:                               # u[nc j + x] += rho_(half B)(u[nc (j + half) + x]) for j < half, every column class at once
+            if _summed(ctx):                                         # SUMMED_ROTATIONS: the giant steps of every column class in ONE call - term (u[g], j B), j = 0 as step 0
+                members = [[g for g, (_, c) in enumerate(plan.groups) if c == cc] for cc in (0, 1)]
+                used = [cc for cc in (0, 1) if members[cc]]
+                idx = [g for cc in used for g in members[cc]]
+                off = [0]
+                for cc in used:
+                    off.append(off[-1] + len(members[cc]))
+                tot = _Buf(ctx, "ct", len(used))
+                tv = tot.view()
+                ctx.rotate_rows_sum(u.h, idx, [plan.groups[g][0] * Bs for g in idx], off, tot.h, 0)
+                if len(used) == 2:
+                    ctx.rotate_columns_add(tot.h, 1, tot.h, 0, res.h, 0, 1)
+                elif used == [1]:
+                    ctx.rotate_columns(tot.h, 0, res.h, 0, 1)
+                else:
+                    ctx.copy(tot.h, 0, res.h, 0, 1)
+                tv.release()
+            elif plan.giants_by_folding:                               # u[nc j + x] += rho_(half B)(u[nc (j + half) + x]) for j < half, every column class at once
                 nc, half = len(plan.classes), Gs // 2
                 while half >= 1:
                     ctx.rotate_rows_add(u.h, nc * half, half * Bs, u.h, 0, u.h, 0, nc * half)

@@ -440,6 +440,34 @@ int cn_rotate_rows_many(cn_ctx *ctx, cn_handle in, const uint32_t *ii, const int
  * of baby steps by doubling. */
 int cn_apply_galois_hoisted(cn_ctx *ctx, cn_handle in, uint32_t ii, const uint64_t *elts, uint32_t n, cn_handle out, const uint32_t *oi);
 int cn_rotate_rows_hoisted(cn_ctx *ctx, cn_handle in, uint32_t ii, const int *steps, uint32_t n, cn_handle out, const uint32_t *oi);
+/* Summed rotations: out[oi + g] = sum over e in [grp_off[g], grp_off[g + 1]) of ApplyGalois(in[ii[e]], elts[e]) / RotateRows(in[ii[e]], steps[e]), g < G - n
+ * rotations of n DIFFERENT ciphertexts under one pair of inverse transforms per output limb.  The reference forms such sums in Interleave
+ * (AtomicSealBfvVector.cs:600-722: RotateRows of the vectors, AddMany per output block) and Permute (:1436-1474: a rotation and an AddInplace per selection); the
+ * giant steps of this package's diagonal dense layers are one more.  A key switch ends in INTT_j(acc) and the inverse transform is linear mod q_j, so
+ *     sum_r ( INTT_j(acc_r) + s_(g_r)(c0_r) )  =  INTT_j( sum_r acc_r ) + sum_r s_(g_r)(c0_r)        (mod q_j, canonical)
+ * holds exactly: every term runs its forward digit transforms and its key products (the term MAC of the two-launch key switch, operand, key and element per term,
+ * the automorphism applied on load), the partial products of all terms of an output are summed and inverted once (k_ks_sum_terms), no rotated term is stored.
+ * THE WORDS: cn_apply_galois_sum writes the canonical words of cn_apply_galois per term followed by cn_add_many per group; cn_rotate_rows_sum those of cn_rotate_rows
+ * per term (the same hops, in the same order, with the same keys as cn_rotate_rows_many) followed by cn_add_many.  Modular sums are exact: the order of the terms
+ * does not matter.  Element 1 / step 0 is a plain addend, both components; a group made only of such terms launches no key-switch kernel (cn_add_many's kernel
+ * runs); a group of one rotated term is cn_apply_galois.  grp_off follows cn_mul_plain_sum: G + 1 entries, starts at 0, strictly increasing; indices in ii may
+ * repeat inside and across groups.
+ * Keys: the element form needs the OWN key of every element (CN_ERR_NOKEY); the steps form runs the non-adjacent-form hops of a step without its own key
+ * (cn_rotation.h) - all but the last hop as cn_rotate_rows_many's rounds into a temporary, the last hop inside the sum - and reports CN_ERR_NOKEY only when the
+ * planner finds no chain; a step of N/2 or more is CN_ERR_ARG.  CN_ERR_ARG, nothing launched, outputs untouched: G = 0, grp_off[0] != 0, an empty group, an index
+ * outside its handle, operands or outputs not of size 2, an output range that contains a ciphertext the call reads, an even element or one >= 2N, a context with
+ * one coefficient modulus, keys of the listed elements loaded in different forms.  Hops and refusals are planned before anything is copied or launched.
+ * NO REFUSAL FOR A MISSING KERNEL: where the fused form does not run - N < 1024, "legacy_ntt", the integer policy at N = 16384, more rotated terms than the per-digit / per-source-limb term MAC takes
+ * (cn_ks_sum_plan, cn_ks_plan.h), partial products that would not fit the key-switch arena - the call composes the literal sequence through a temporary: the same
+ * words, no error.  Works on level contexts with the sliced keys, in both key-switch conventions ("ks_xi") and with keys loaded in either form ("f64").  Queued
+ * calls ("defer") are submitted first and the call runs at once.  Under cn_graph_begin the lists are captured by value; the partial products live in the
+ * key-switch arena, which cannot grow while a graph is recorded or alive - run the sequence once before recording.  "record_steps" notes the steps as
+ * cn_rotate_rows_many / cn_apply_galois do.
+ * Counters: Rotation grows by one per hop, AddMany by G, AddManyItemCount by the number of terms; ntt_forward_limbs by gk_tot k per hop; ntt_inverse_limbs by 2 k
+ * per hop that is not the last of its term plus 2 k per output with at least one rotated term (a composed call: 2 k per hop, what it ran).  cn_get_option
+ * "ks_summed" counts the calls that launched the fused form (counts up, read-only). */
+int cn_apply_galois_sum(cn_ctx *ctx, cn_handle in, const uint32_t *ii, const uint64_t *elts, const uint32_t *grp_off, uint32_t G, cn_handle out, uint32_t oi);
+int cn_rotate_rows_sum(cn_ctx *ctx, cn_handle in, const uint32_t *ii, const int *steps, const uint32_t *grp_off, uint32_t G, cn_handle out, uint32_t oi);
 /* Evaluator.RotateColumns(/Inplace) (AtomicSealBfvVector.cs:709,914,1391) */
 int cn_rotate_columns(cn_ctx *ctx, cn_handle in, uint32_t ii, cn_handle out, uint32_t oi, uint32_t count);
 /* out[i] = acc[i] + RotateRows(in[i], steps) / + RotateColumns(in[i]): the rotate-and-add step of SumAllSlots / RotateRowsAndAdd
